@@ -202,9 +202,32 @@ class SmiSampler:
         self._t.join(10)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def record_arrays(recs):
+    """Per-face result records (frt.RESULT_DTYPE) as one array per field, boxes as [F, 4] (x1, y1, x2, y2)."""
+    return {"boxes": np.stack([recs[k] for k in ("x1", "y1", "x2", "y2")], 1), "score": recs["score"], "frame": recs["frame"],
+            "match_idx": recs["match_idx"], "match_sim": recs["match_sim"], "valid": recs["valid"]}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy; integers widened to float64 (exact), floats as float32 (float64 kept)."""
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = np.ascontiguousarray(a, dtype=np.float64 if (a.dtype.kind in "iub" or a.dtype == np.float64) else np.float32)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("bench.py: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_LIMIT_BYTES))
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def visible_devices():
-    """HIP devices this process can see, counted in a child process (the launcher itself must not initialise HIP: the ranks it starts
-    set GPU_MAX_HW_QUEUES before they do)."""
+    """HIP devices this process can see, counted in a child process (the launcher itself does not initialise HIP: only the ranks it
+    starts open the devices)."""
     code = ("import sys; sys.path.insert(0, %r); import __graft_entry__ as e; print(e.load_pkg().device_count())" % ROOT)
     try:
         o = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
@@ -291,6 +314,9 @@ def main():
     ap.add_argument("--topk", type=int, default=5, help="--sharded-gallery: length of the per-query lists every rank answers with (1..16)")
     ap.add_argument("--dump-final", default=None, help="--sharded-gallery: write the last step's gathered fp16 queries and merged top-k lists (npz) "
                                                        "for an external check against the oracle (tests/test_gpu_dist.py)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed region, write what its last step returned (the per-face records; with --sharded-gallery also the merged "
+                         "top-k lists) as DIR/<name>.npy in float32 / float64, for an output-by-output comparison of two builds")
     ap.add_argument("--stage-profile", default=None, help="write a per-stage HIP-event breakdown (extra untimed steps) to this file")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
     ap.add_argument("--no-extras", action="store_true", help="only the contract's timed region (no side measurements)")
@@ -307,6 +333,8 @@ def main():
         depth = 2 * args.pair + 2   # grouped calls complete N at a time: two groups in the later stages + the detector's calls ahead of them
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` as typed: this process becomes the launcher - one rank per GPU under torch.distributed.run
         # (the same command line the driver uses), rank 0's JSON line passes through on stdout.  Never a silent one-rank run.
@@ -316,13 +344,6 @@ def main():
         raise SystemExit("bench.py: WORLD_SIZE (%s) != --gpus (%d): start as many ranks as --gpus says" % (os.environ["WORLD_SIZE"], args.gpus))
     if os.environ.get("FRT_BENCH_LAUNCH_CHECK") == "1":
         raise SystemExit(launch_check(args, json_out))
-    # Hardware queues (read by the HIP runtime when it initialises, i.e. before torch / libfrt are imported).  ROCm multiplexes a process's
-    # streams onto GPU_MAX_HW_QUEUES (default 4) in-order hardware queues per priority class.  Alone, the pipeline is 1.2 % faster on the
-    # default (39.05 k against 38.5 - 38.7 k faces/s with 6 / 8 / 12 queues, one box); with RCCL in the process and the per-step record
-    # gather running on its own stream (N > 1) four queues put that stream's copies and collective in front of pipeline work: 35.25 k
-    # against 38.4 - 38.6 k with 6 / 8 / 12 (same box, alternating runs, profiles/r03/r03l_hw_queues.txt).  So: 8 whenever a communicator exists.
-    if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("FRT_BENCH_FORCE_DIST") == "1":
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 
     import torch
     import torch.distributed as dist
@@ -595,6 +616,20 @@ def main():
         r = (args.steps - 1) % 4
         own = h_all[r][rank * F * RD.itemsize:(rank + 1) * F * RD.itemsize]
         assert torch.equal(own, h_res[r]), "all-gather mismatch"
+    if args.dump_outputs:
+        # what the last timed step handed back, before the untimed extras below reuse the same buffers
+        last = (args.steps - 1) % NRING
+        if run is run_host or run is run_host_dist:
+            recs = h_views[last].copy()
+        else:
+            recs = np.frombuffer(d_res[last].cpu().numpy().tobytes(), RD)
+        outputs = record_arrays(recs)
+        if args.sharded_gallery:
+            fi, fs = final[0]
+            outputs["topk_idx"] = fi.cpu().numpy()[:world * F]
+            outputs["topk_sim"] = fs.cpu().numpy()[:world * F]
+        suffix = "" if world == 1 else "_rank%d" % rank
+        dump_outputs(args.dump_outputs, {k + suffix: v for k, v in outputs.items()})
     if use_dist:
         dist.barrier()
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")

@@ -267,6 +267,44 @@ def test_bench_line_contract():
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["unit"] == "faces/sec" and c["sample"]
 
 
+def test_bench_dump_outputs_are_the_last_timed_steps_records(frt, synth, blobs, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the records of the LAST timed step (step 2 of 3: the first of the two alternating batches),
+    one float32 / float64 .npy per field, and they equal one synchronous frt_pipeline_run over the same frames and gallery."""
+    import json
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+    B, K, N = 4, 4, 20_000
+    out_dir = tmp_path / "outputs"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", str(B),
+                          "--gallery", str(N), "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(out_dir)],
+                         capture_output=True, text=True, timeout=1500, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and json.loads(lines[0])["steps"] == 3
+    got = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+    assert sorted(got) == ["boxes", "frame", "match_idx", "match_sim", "score", "valid"]
+    assert all(a.dtype in (np.float32, np.float64) and len(a) == B * K for a in got.values())
+    dpath, _ = blobs("det")
+    rpath, _ = blobs("ir")
+    det = frt.RetinaFace(dpath, 640, 640, (3, 640, 640), B, K, 0.4, 0.6)
+    rec = frt.ArcFaceIR50(rpath, 640, 640, (3, 112, 112), 512, B * K, K, 0.65)
+    rec.setGallery(synth.make_gallery(N))
+    rec.initMatMul()
+    pipe = frt.Pipeline(det, rec, B)
+    want = pipe.run(synth.make_frames(B, 640, 640, start=0), want_embeds=False)[0]
+    assert want["valid"].sum() > 0
+    assert np.array_equal(got["boxes"], np.stack([want[k] for k in ("x1", "y1", "x2", "y2")], 1))
+    for k in ("frame", "match_idx", "valid"):
+        assert np.array_equal(got[k], want[k]), k
+    for k in ("score", "match_sim"):
+        assert np.abs(got[k] - want[k]).max() < 1e-6, k
+    pipe.close()
+    det.close()
+    rec.close()
+
+
 @pytest.mark.parametrize("mode", ["ir", "ir_se"])
 def test_configs1_batch1_fp32_one_workload(frt, orc, synth, blobs, mode):
     """BASELINE configs[1] as ONE workload in the precision it names: 640x640, batch 1, 10k x 512 gallery, recogniser in fp32 mode

@@ -1,4 +1,6 @@
 """Batched device-resident pipeline (detect -> crop -> embed -> match) vs the oracle run stage by stage."""
+import os
+
 import numpy as np
 import pytest
 
@@ -476,7 +478,10 @@ def test_run_dev_orders_behind_the_callers_producer(frt, synth, blobs):
 
 def test_stream_overlap_self_check_reports_a_clean_pipeline(frt, synth, blobs):
     """frt_pipeline_check_overlap (round 3): on a freshly created pipeline the three stage streams run their probe kernels side by side
-    (ratio ~ 1) and a wait pending on the caller's stream holds up none of them - no warning; the call leaves the pipeline usable."""
+    (ratio ~ 1) and a wait pending on the caller's stream holds up none of them - no warning; the call leaves the pipeline usable.
+    The three stage streams share one priority level, so running side by side needs one hardware queue each on that level.  A process
+    whose environment caps the queues per level (GPU_MAX_HW_QUEUES) below three cannot overlap them, and there the check must say so:
+    ratio ~ 2 and a hardware-queue warning.  Unset, HIP's default leaves room for all three."""
     import torch
     dpath, _ = blobs("det")
     rpath, _ = blobs("ir")
@@ -491,7 +496,11 @@ def test_stream_overlap_self_check_reports_a_clean_pipeline(frt, synth, blobs):
     st = torch.cuda.Stream()
     pipe.set_stream(st.cuda_stream)
     ratio, warning = pipe.check_overlap()
-    assert 0.5 < ratio < 1.5 and warning == "", (ratio, warning)
+    queues = os.environ.get("GPU_MAX_HW_QUEUES")
+    if queues is None or int(queues) >= 3:
+        assert 0.5 < ratio < 1.5 and warning == "", (ratio, warning)
+    else:
+        assert ratio > 1.5 and "hardware queue" in warning, (ratio, warning)
     got, _ = pipe.run(frames)
     assert np.array_equal(got, want)
     pipe.set_stream(None)

@@ -33,10 +33,8 @@ def main():
     rpath = frt.write_weights(os.path.join(tmp, "rec.frtw"), s.arcface_state(2, "ir", calib=s.load_calibration("ir")), 2)
     s.make_frames(64, 640, 640).tofile(os.path.join(tmp, "frames.bin"))
     exe = build_multi_device(tmp)
-    env = dict(os.environ)
-    env.setdefault("GPU_MAX_HW_QUEUES", "8")  # a communicator lives in the process (DESIGN: streams and hardware queues)
     out = subprocess.run([exe, dpath, rpath, os.path.join(tmp, "frames.bin"), str(args.batch), str(args.gallery), str(args.steps), args.devices],
-                         capture_output=True, text=True, timeout=3000, env=env)
+                         capture_output=True, text=True, timeout=3000)
     sys.stderr.write(out.stderr[-3000:])
     if out.returncode != 0:
         raise SystemExit("multi_device_pipeline failed (%d): %s" % (out.returncode, out.stdout[-2000:]))
