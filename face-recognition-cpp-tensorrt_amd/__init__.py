@@ -675,10 +675,11 @@ class Pipeline:
         _check(lib.frt_pipeline_run(self._h, _ptr(frames), n, _ptr(res), _ptr(emb)))
         return res, emb
 
-    def submit(self, frames, results, embeds=None):
+    def submit(self, frames, results, embeds=None, crops=None):
         """Asynchronous host boundary: queue one batch (``frames`` u8 [n, H, W, 3], ``results`` a RESULT_DTYPE array of
-        n*max_faces records, optional ``embeds`` float32 [n*max_faces, 512]; all C-contiguous, ideally pinned) and return a
-        ticket for :meth:`wait`.  The arrays must stay alive and untouched until then."""
+        n*max_faces records, optional ``embeds`` float32 [n*max_faces, 512], optional ``crops`` u8 [n*max_faces, 112, 112, 3] for the
+        faces' BGR crops (frt_pipeline_submit_crops); all C-contiguous, ideally pinned) and return a ticket for :meth:`wait`.  The
+        arrays must stay alive and untouched until then."""
         if not (frames.flags.c_contiguous and frames.dtype == np.uint8):
             raise ValueError("frames must be a C-contiguous uint8 array")
         n = frames.shape[0]
@@ -686,8 +687,13 @@ class Pipeline:
             raise ValueError("results must be a C-contiguous RESULT_DTYPE array of n*max_faces records")
         if embeds is not None and (embeds.dtype != np.float32 or embeds.size < n * self.max_faces * 512 or not embeds.flags.c_contiguous):
             raise ValueError("embeds must be a C-contiguous float32 [n*max_faces, 512] array")
+        if crops is not None and (crops.dtype != np.uint8 or crops.size < n * self.max_faces * 112 * 112 * 3 or not crops.flags.c_contiguous):
+            raise ValueError("crops must be a C-contiguous uint8 [n*max_faces, 112, 112, 3] array")
         t = ctypes.c_long(-1)
-        _check(lib.frt_pipeline_submit(self._h, _ptr(frames), n, _ptr(results), _ptr(embeds), ctypes.byref(t)))
+        if crops is None:
+            _check(lib.frt_pipeline_submit(self._h, _ptr(frames), n, _ptr(results), _ptr(embeds), ctypes.byref(t)))
+        else:
+            _check(lib.frt_pipeline_submit_crops(self._h, _ptr(frames), n, _ptr(results), _ptr(embeds), _ptr(crops), ctypes.byref(t)))
         return int(t.value)
 
     def wait(self, ticket):

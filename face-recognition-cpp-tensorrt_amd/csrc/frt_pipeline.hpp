@@ -175,14 +175,22 @@ struct frt_pipeline {
     //      operations between the graph launches.  A part is keyed by everything baked into its nodes (buffers, batch, slot,
     //      mode, gallery generation); first sighting of a key runs eagerly (lazy one-time setup inside the launchers), the second
     //      is captured, later ones replay.  Off while the profiling hooks record events (frt_profile_enable).
-    //      OPT-IN (FRT_PIPELINE_GRAPH=1 / frt_pipeline_set_graph(p, 1)): on the benchmark step the replay measured 4.41 ms against
-    //      4.39 ms eager - the launches are queued far enough ahead that the per-dispatch cost hides behind the previous kernel.
+    //      OPT-IN (frt_pipeline_set_graph(p, 1); FRT_PIPELINE_GRAPH=1 only in tuning builds): on the benchmark step the replay measured
+    //      4.41 ms against 4.39 ms eager - the launches are queued far enough ahead that the per-dispatch cost hides behind the previous kernel.
+    //      Part 2 (match + pack) of a call merged from several submit tickets packs each ticket's records with its own frame count from
+    //      zero, so its key also carries the ticket split (nsub, sub_n): a call split 1 + 2 must not replay the graph of one split 2 + 1.
+    //      Parts 0 (detector) and 1 (crop + recogniser) see only the call's frames as a whole and keep nsub = 0.
     struct GraphKey {
         int part;
         const void *frames, *results, *embeds;
         int n, slot, align;
         unsigned gallery_gen;
+        int nsub = 0;  // part 2 of a merged call: its tickets' frame counts; 0 for everything else
+        int sub_n[MAXSUB] = {};
         bool operator==(const GraphKey &o) const {
+            if (nsub != o.nsub) return false;
+            for (int j = 0; j < nsub; ++j)
+                if (sub_n[j] != o.sub_n[j]) return false;
             return part == o.part && frames == o.frames && results == o.results && embeds == o.embeds && n == o.n && slot == o.slot && align == o.align &&
                    gallery_gen == o.gallery_gen;
         }
@@ -196,7 +204,8 @@ struct frt_pipeline {
     std::vector<GraphEntry> graphs;
     bool use_graphs = false;
     // a steady pipelined workload cycles through NSLOT keys of stage 0, up to 2 * NSLOT (slot, activation set) pairs of stage 1 and NSLOT of
-    // stage 2: the cache holds them all (a smaller one evicted every key before it recurred - nothing was ever replayed)
+    // stage 2: the cache holds them all (a smaller one evicted every key before it recurred - nothing was ever replayed).  Merged calls add one
+    // stage-2 key per ticket split seen at a slot; the least recently used keys make room for them
     static constexpr size_t GRAPH_CAP = 4 * NSLOT + 8;
     unsigned long graph_tick = 0;
     long graphs_captured = 0, graphs_replayed = 0;
@@ -586,8 +595,16 @@ struct frt_pipeline {
                 f_off += Fc[i];
             }
         };
-        if (nc == 1) run_part(GraphKey{2, nullptr, c[0].results, c[0].embeds, c[0].n, c[0].slot, akey, gen}, ms, stage_m);
-        else stage_m(ms);
+        if (nc == 1) {
+            GraphKey key{2, nullptr, c[0].results, c[0].embeds, c[0].n, c[0].slot, akey, gen};
+            if (c[0].nsub > 1) {  // (stage_m packs a single-ticket call as one launch whatever its nsub: 0 and 1 are the same graph)
+                key.nsub = c[0].nsub;
+                for (int j = 0; j < c[0].nsub; ++j) key.sub_n[j] = c[0].sub[j].n;
+            }
+            run_part(key, ms, stage_m);
+        } else {
+            stage_m(ms);
+        }
         if (mat) {
             HIPCHK(hipEventRecord(mat->ev_busy, ms));
             mat->busy = true;

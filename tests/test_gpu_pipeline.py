@@ -6,6 +6,102 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+# ---- a deterministic "backed-up" pipeline (adaptive mode, frt_pipeline_set_pairing(p, -1)).  Whether a submit is held, merged with the next
+#      ones or shares a recogniser pass depends on event queries (frt_pipeline::backed_up / tickets_running / recogniser_busy).  Behind a closed
+#      gate - a spin kernel on the pipeline stream with frt_pipeline_set_input_sync on, so that every stage of the window waits for it - every
+#      query answers "still running", and the hold / merge decisions follow from the host rules alone; predict_window restates them.
+NBUF, NSLOT, MAXSUB, MAXG, HOLD_MIN = 12, 10, 4, 4, 5  # frt_pipeline.hpp
+GATE_CYCLES = 200_000_000                            # ~0.1 s of device time (tests/test_gpu_jpeg.py)
+
+
+def predict_window(sizes, max_frames, K, max_batch):
+    """Calls and recogniser passes of one gated window: ``sizes[t]`` frames per submit ticket, submitted back to back while the gate holds,
+    then frt_pipeline_sync.  -> (calls, passes): a call is the list of its tickets, a pass the list of its calls.  The rules are
+    pipeline_submit_impl / pipeline_start_held (frt_pipeline.cpp) and run() / later_stages() (frt_pipeline.hpp): a ticket is held only when
+    2 * n <= max_frames and at least HOLD_MIN tickets have their later stages queued; the next tickets join the held call while it has room
+    and it goes out at MAXSUB tickets or once 2 * n > max_frames; a call of n frames waits for a partner pass while its faces fit twice
+    (gcap >= 2), for up to gcap calls of the same n."""
+    F_cap = max_frames * K
+    held, pend, calls, passes = [], [], [], []
+    st = {"running": 0, "det": False, "rec": False}
+
+    def n_of(tk):
+        return sum(sizes[t] for t in tk)
+
+    def later(grp):
+        passes.append(grp)
+        st["rec"] = True
+        st["running"] += sum(len(c) for c in grp)
+
+    def flush():
+        if pend:
+            later(list(pend))
+            pend.clear()
+
+    def run(tk):
+        F = n_of(tk) * K
+        gcap = min(MAXG, F_cap // F, max_batch // F)
+        if pend and not (gcap >= 2 and n_of(pend[0]) == n_of(tk)):
+            flush()
+        calls.append(tk)
+        st["det"] = True
+        if gcap >= 2 and (pend or (st["rec"] and st["running"] >= HOLD_MIN)):
+            pend.append(tk)
+            if len(pend) == gcap:  # (the other release, "recogniser idle", never fires behind the gate)
+                flush()
+            return
+        later([tk])
+
+    def start_held():
+        if held:
+            tk = list(held)
+            held.clear()
+            run(tk)
+
+    for t, n in enumerate(sizes):
+        if held:
+            nt = n_of(held) + n
+            if len(held) < MAXSUB and nt <= max_frames and nt * K <= max_batch:
+                held.append(t)
+                if len(held) == MAXSUB or 2 * nt > max_frames or st["running"] < HOLD_MIN:
+                    start_held()
+                continue
+            start_held()
+        if 2 * n <= max_frames and 2 * n * K <= max_batch and st["det"] and st["running"] >= HOLD_MIN:
+            held.append(t)
+            continue
+        run([t])
+    start_held()  # frt_pipeline_sync
+    flush()
+    return calls, passes
+
+
+def window_deltas(calls, passes):
+    """-> the (merge_stats, pairing_stats) increments a window with these calls / passes produces"""
+    merged = [c for c in calls if len(c) > 1]
+    return ((len(merged), sum(len(c) for c in merged)), (sum(len(p) > 1 for p in passes), sum(len(p) == 1 for p in passes)))
+
+
+def gated_window(pipe, st, submits, cycles=GATE_CYCLES):
+    """Submit every argument tuple of ``submits`` (Pipeline.submit's) (at most NBUF: no submit waits for a staging set) behind a closed gate on
+    ``st`` - the pipeline's stream, with set_input_sync(True) - then sync and wait.  Configure the pipeline before: every set_* releases held
+    calls.  -> (merge_stats delta, pairing_stats delta, whether the gate was still closed after the last submit)."""
+    import torch
+    assert len(submits) <= NBUF
+    m0, p0 = pipe.merge_stats(), pipe.pairing_stats()
+    with torch.cuda.stream(st):
+        torch.cuda._sleep(cycles)
+        gate = torch.cuda.Event()
+        gate.record(st)
+    tickets = [pipe.submit(*s) for s in submits]
+    closed = not gate.query()
+    pipe.sync()  # held and pending calls go out while the gate still holds: part of the prediction
+    for t in tickets:
+        pipe.wait(t)
+    m1, p1 = pipe.merge_stats(), pipe.pairing_stats()
+    return (m1[0] - m0[0], m1[1] - m0[1]), (p1[0] - p0[0], p1[1] - p0[1]), closed
+
+
 
 def test_pipeline_end_to_end(frt, orc, synth, blobs):
     from oracle import match, nets
@@ -730,6 +826,87 @@ def test_adaptive_pairing_holds_calls_only_behind_a_busy_recogniser(frt, synth, 
     assert pe - pd >= 1, (pe - pd, se - sd)
     for i in range(n_batches):
         assert same(d_res[i].cpu().numpy(), want_res[i]), i
+    pipe.close()
+    det.close()
+    rec.close()
+
+
+def test_graph_replay_of_merged_calls_keeps_each_tickets_frame_count(frt, synth, blobs):
+    """frt_pipeline_set_graph(p, 1) in the default adaptive mode, gated windows that repeat exactly: 12 tickets (NBUF) in 10 calls (NSLOT), so
+    every stage key - staging set, slot, frames - recurs in every window: the first window runs eagerly, the second captures, later ones replay.
+    max_frames 4: the merged calls 1 + 2 and 2 + 1 close by the size rule (n = 3, never paired at the recogniser stage: their match + pack part
+    is always a graph of its own).  A variant window keeps every key but splits its first merged call 2 + 1 instead of 1 + 2: a replay of
+    the 1 + 2 graph would count the records' ``frame`` from the wrong ticket starts.  Reference: the same tickets one at a time, pairing and
+    graphs off - boxes, frame, valid and rows exact, similarity to 2e-4."""
+    import torch
+    dpath, _ = blobs("det")
+    rpath, _ = blobs("ir")
+    M, K, H, W = 4, 4, 320, 320
+    main_sizes = [1, 2, 3, 4, 2, 1, 2, 2, 1, 3, 3, 4]
+    variant_sizes = main_sizes[:5] + [2, 1] + main_sizes[7:]
+    layouts = {"main": predict_window(main_sizes, M, K, 4 * K), "variant": predict_window(variant_sizes, M, K, 4 * K)}
+    for tag, (calls, passes) in layouts.items():
+        assert len(calls) == NSLOT and len(passes) == NSLOT and all(len(p) == 1 for p in passes), (tag, calls, passes)
+    assert layouts["main"][0][5] == [5, 6] and layouts["variant"][0][5] == [5, 6] and layouts["main"][0][6] == [7, 8]
+    det = frt.RetinaFace(dpath, W, H, (3, H, W), M, K, 0.4, 0.6)
+    rec = frt.ArcFaceIR50(rpath, W, H, maxBatchSize=M * K, maxFacesPerScene=K)
+    rec.setGallery(synth.make_gallery(3000))
+    rec.initMatMul()
+    pipe = frt.Pipeline(det, rec, M)
+    # the same 30 distinct frames in both layouts, only split differently between tickets 5 and 6
+    frames = synth.make_frames(sum(main_sizes), H, W, start=40)
+    inputs = {tag: [torch.from_numpy(f).pin_memory() for f in np.split(frames, np.cumsum(sizes)[:-1])]
+              for tag, sizes in (("main", main_sizes), ("variant", variant_sizes))}
+
+    def new_out(sizes):
+        return ([torch.zeros(n * K * frt.RESULT_DTYPE.itemsize, dtype=torch.uint8).pin_memory() for n in sizes],
+                [torch.zeros(n * K, 512).pin_memory() for n in sizes])
+
+    def one_at_a_time(tag):
+        res, emb = new_out(main_sizes if tag == "main" else variant_sizes)
+        for f, r, e in zip(inputs[tag], res, emb):
+            pipe.wait(pipe.submit(f.numpy(), r.numpy().view(frt.RESULT_DTYPE), e.numpy()))
+        return [r.numpy().view(frt.RESULT_DTYPE).copy() for r in res], [e.numpy().copy() for e in emb]
+
+    # reference: one ticket per call; then every face gets its own gallery row, so that the matched rows do not hang on the last bits of an
+    # embedding (a merged pass runs other recogniser tile shapes than the single calls: fp16 rounding differs)
+    pipe.set_pairing(0)
+    _, emb0 = one_at_a_time("main")
+    all_emb = np.concatenate(emb0)
+    ok = np.linalg.norm(all_emb, axis=1) > 0.5
+    gal = synth.make_gallery(3000)
+    gal[(np.arange(len(all_emb)) * 7 + 2)[ok]] = all_emb[ok]
+    rec.setGallery(gal)
+    rec.initMatMul()
+    want = {"main": one_at_a_time("main")[0], "variant": one_at_a_time("variant")[0]}
+    assert sum(int(w["valid"].sum()) for w in want["main"]) > 0
+    # the merged, gated windows with graphs
+    st = torch.cuda.Stream()
+    pipe.set_stream(st.cuda_stream)
+    pipe.set_input_sync(True)
+    pipe.set_pairing(-1)
+    pipe.set_graph(True)
+    torch.cuda.synchronize()
+    # (window, expected (captured, replayed)): main W1 eager, W2 captures 3 parts x 10 calls, W3 replays them; the variant shares the
+    # detector and recogniser parts of all ten calls and the match part of nine - its own split is a new key: eager, captured, replayed
+    plan = [("main", (0, 0)), ("main", (30, 0)), ("main", (0, 30)), ("variant", (0, 29)), ("variant", (1, 29)), ("variant", (0, 30)), ("main", (0, 30))]
+    for w, (tag, (want_c, want_r)) in enumerate(plan):
+        sizes = main_sizes if tag == "main" else variant_sizes
+        res, emb = new_out(sizes)
+        c0, r0 = pipe.graph_stats()
+        dm, dp, closed = gated_window(pipe, st, [(f.numpy(), r.numpy().view(frt.RESULT_DTYPE), e.numpy())
+                                                for f, r, e in zip(inputs[tag], res, emb)], cycles=5 * GATE_CYCLES)
+        c1, r1 = pipe.graph_stats()
+        assert closed and (dm, dp) == window_deltas(*layouts[tag]), (w, tag, closed, dm, dp, layouts[tag])
+        for t in range(len(sizes)):
+            got, ref = res[t].numpy().view(frt.RESULT_DTYPE), want[tag][t]
+            for k in ("frame", "x1", "y1", "x2", "y2", "valid", "match_idx"):
+                assert np.array_equal(got[k], ref[k]), (w, tag, "ticket %d" % t, k, got[k], ref[k])
+            assert float(np.abs(got["match_sim"] - ref["match_sim"]).max()) < 2e-4, (w, tag, t)
+        assert (c1 - c0, r1 - r0) == (want_c, want_r), (w, tag, c1 - c0, r1 - r0)
+    pipe.set_graph(False)
+    pipe.set_input_sync(False)
+    pipe.set_stream(None)
     pipe.close()
     det.close()
     rec.close()
