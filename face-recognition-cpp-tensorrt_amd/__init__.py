@@ -59,6 +59,7 @@ ABI = {
     "frt_resize_frames_dev": (_i, [_vp, _i, _i, _i, _sz, _sz, _vp, _i, _i, _vp]),
     "frt_embedder_create": (_i, [ctypes.c_char_p, _i, _i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "frt_embedder_destroy": (None, [_vp]),
+    "frt_embedder_describe": (_i, [ctypes.c_char_p, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "frt_embedder_preprocess_face": (_i, [_vp, _vp, _vp]),
     "frt_embedder_infer": (_i, [_vp, _vp, _i, _vp]),
     "frt_embedder_forward": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _vp, _vp]),
@@ -194,6 +195,14 @@ def probe_sustained_mfma(device=0, mix=2, seconds=0.25):
 
 def write_weights(path, state, kind):
     return weights_io.write_blob(path, state, kind)
+
+
+def describe_weights(path):
+    """The backbone a recogniser blob holds (frt_embedder_describe: the validation of ArcFaceIR50's constructor, no device needed)
+    -> dict(numLayers=50 | 100 | 152, se=bool, unitsPerStage=(4 ints))."""
+    n, se, units = _i(), _i(), (_i * 4)()
+    _check(lib.frt_embedder_describe(os.fsencode(path), ctypes.byref(n), ctypes.byref(se), units))
+    return dict(numLayers=n.value, se=bool(se.value), unitsPerStage=tuple(units))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -497,12 +506,24 @@ class ArcFaceIR50:
         self.knownPersonThresh = knownPersonThreshold
         _check(lib.frt_embedder_create(os.fsencode(engineFile), *[int(x) for x in inputShape], self.outputDim, self.maxBatchSize, device,
                                        ctypes.byref(self._h)))
+        d = describe_weights(engineFile)
+        self._num_layers, self._se = d["numLayers"], d["se"]
         self.matmul = MatMul(device)
         self.croppedFaces = []  # list of dicts: face (u8 BGR crop), x1, y1, x2, y2  (struct CroppedFace, arcface.h:11-15)
         self.classNames = []
         self.classCount = 0
         self._known = None
         self._embeds = np.zeros((0, self.outputDim), np.float32)
+
+    @property
+    def numLayers(self):
+        """Depth of the backbone the engine file holds: 50, 100 or 152 (the class keeps the reference's name for all six)."""
+        return self._num_layers
+
+    @property
+    def se(self):
+        """True for the IR-SE backbones."""
+        return self._se
 
     def setPrecision(self, fp32):
         """``True``: fp32 activations / weights / products end to end (BASELINE configs[1]'s "fp32"; slow, a few faces per call);

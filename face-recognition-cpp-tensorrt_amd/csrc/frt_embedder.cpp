@@ -56,6 +56,26 @@ std::vector<float> vec_of(const frt::Blob &b, const std::string &name, size_t n)
 
 void frt_embedder::build(const frt::Blob &b) {
     std::vector<float> sc, bi;
+    const bool condition = !(frt_tuning_env("FRT_ARC_CONDITION") && frt_tuning_env("FRT_ARC_CONDITION")[0] == '0');  // (tuning build: the sweep's "off" leg)
+    // Residual-stream conditioning of the deep IR backbones.  The fp16 stream (Y / Z / SC) adds one branch per unit: on the same
+    // kind of weights IR-100 / IR-152 peak 11 / 16 times higher than IR-50 (545 / 783 vs 48), so a stream scale IR-50 holds (1e3) overflows
+    // them.  Where the stream BatchNorms' running statistics say the stream is large (sigma >= 2^6), such a blob runs with the stream scaled by
+    // ds = 2^-4, which gives back exactly the headroom the depth costs (and no more: what overflows IR-50 still overflows them, loudly).
+    // PReLU, MaxPool and the convs are positively homogeneous, so with input_layer.1 and every closing BN scale and bias * ds, every
+    // shortcut BN's bias * ds and every BN that reads the stream (res_layer.0, output_layer.0) scale / ds the network computes the same function;
+    // every factor is a power of two, exact in binary floating point.  IR-50 (24 units) and the IR-SE family (its gates damp the branches:
+    // peaks 5 / 9 / 11) are never touched.
+    stream_scale = 1.0f;
+    if (condition && !se && layout.units.size() > 24) {
+        double var = 0.0;
+        for (size_t i = 0; i <= layout.units.size(); ++i) {
+            const std::string p = i < layout.units.size() ? "body." + std::to_string(i) + ".res_layer.0" : std::string("output_layer.0");
+            const frt::Tensor &v = b.get(p + ".running_var", i < layout.units.size() ? layout.units[i].cin : 512);
+            for (size_t c = 0; c < v.numel; ++c) var = std::max(var, (double)v.data[c]);
+        }
+        if (std::sqrt(var + 1e-5) >= 64.0) stream_scale = 0.0625f;
+    }
+    const float ds = stream_scale;
     // input layer (model_irse.py:139-141)
     {
         const float *src = b.get("input_layer.0.weight", 64 * 27).data;
@@ -64,6 +84,7 @@ void frt_embedder::build(const frt::Blob &b) {
             for (int k = 0; k < 27; ++k) w[k * 64 + co] = src[co * 27 + k];
         in_w = arena.upload(w);
         frt::bn_fold(b, "input_layer.1", 64, sc, bi);
+        for (int co = 0; co < 64; ++co) sc[co] *= ds, bi[co] *= ds;
         in_s0 = arena.upload(sc);
         in_b0 = arena.upload(bi);
         std::vector<uint16_t> wh(64 * 32, 0);  // matrix-core layout (kernels_arc_input.hip): BN folded, bias in tap slot 27
@@ -74,20 +95,21 @@ void frt_embedder::build(const frt::Blob &b) {
         in_wh = reinterpret_cast<half_t *>(arena.upload(wh));
         in_slope = arena.upload(vec_of(b, "input_layer.2.weight", 64));
         frt::bn_fold(b, "body.0.res_layer.0", 64, sc, bi);
+        for (int co = 0; co < 64; ++co) sc[co] /= ds;
         in_s1 = arena.upload(sc);
         in_b1 = arena.upload(bi);
         flops_per_face += 2.0 * 27 * 64 * 112 * 112;
     }
-    // units (model_irse.py:97-109 for IR-50)
-    const int cfg[4][3] = {{64, 64, 3}, {64, 128, 4}, {128, 256, 14}, {256, 512, 3}};
-    const bool condition = !(frt_tuning_env("FRT_ARC_CONDITION") && frt_tuning_env("FRT_ARC_CONDITION")[0] == '0');  // (tuning build: the sweep's "off" leg)
-    int h = 112, idx = 0;
+    // units (model_irse.py:48-90), in the order and shapes frt::arc_layout read from the blob (IR-50 / IR-100 / IR-152, with or without SE)
+    size_t idx = 0;
     for (int st = 0; st < 4; ++st)
-        for (int u = 0; u < cfg[st][2]; ++u) {
+        for (int u = 0; u < layout.stage_units[st]; ++u, ++idx) {
+            const frt::ArcUnitShape &shape = layout.units[idx];
+            const int h = shape.h_in;
             ArcUnit a;
-            a.cin = u == 0 ? cfg[st][0] : cfg[st][1];
-            a.depth = cfg[st][1];
-            a.stride = u == 0 ? 2 : 1;
+            a.cin = shape.cin;
+            a.depth = shape.depth;
+            a.stride = shape.stride;
             a.h_in = h;
             const std::string p = "body." + std::to_string(idx);
             // Conditioning of the branch conv1 -> PReLU -> conv2 -> BN (round 5; model_irse.py:57-66).  conv1's accumulators leave as the fp16
@@ -142,6 +164,7 @@ void frt_embedder::build(const frt::Blob &b) {
             a.prelu = arena.upload(vec_of(b, p + ".res_layer.2.weight", a.depth));
             a.w2 = reinterpret_cast<half_t *>(arena.upload(conv_w_f16(w2v.data(), a.depth, a.depth, 3)));
             frt::bn_fold(b, p + ".res_layer.4", a.depth, sc, bi);
+            for (int k = 0; k < a.depth; ++k) sc[k] *= ds, bi[k] *= ds;
             a.s2f32 = arena.upload(sc);   // (the fp32 path multiplies the blob's own weights: the unconditioned scale)
             for (int k = 0; k < a.depth; ++k) sc[k] *= dinv[k];
             a.s2 = arena.upload(sc);
@@ -151,6 +174,7 @@ void frt_embedder::build(const frt::Blob &b) {
                 const std::vector<uint16_t> fs = conv1x1_w_f16_frag(b, p + ".shortcut_layer.0.weight", a.depth, a.cin);
                 if (!fs.empty()) a.wscf = reinterpret_cast<half_t *>(arena.upload(fs));
                 frt::bn_fold(b, p + ".shortcut_layer.1", a.depth, sc, bi);
+                for (int k = 0; k < a.depth; ++k) bi[k] *= ds;
                 a.ssc = arena.upload(sc);
                 a.bsc = arena.upload(bi);
             }
@@ -158,16 +182,15 @@ void frt_embedder::build(const frt::Blob &b) {
                 a.se_w1 = arena.upload(vec_of(b, p + ".res_layer.5.fc1.weight", (size_t)a.depth / 16 * a.depth));
                 a.se_w2 = arena.upload(vec_of(b, p + ".res_layer.5.fc2.weight", (size_t)a.depth * (a.depth / 16)));
             }
-            const bool last = st == 3 && u == cfg[st][2] - 1;
+            const bool last = idx + 1 == layout.units.size();
             frt::bn_fold(b, last ? std::string("output_layer.0") : "body." + std::to_string(idx + 1) + ".res_layer.0", a.depth, sc, bi);
+            for (int k = 0; k < a.depth; ++k) sc[k] /= ds;
             a.sn = arena.upload(sc);
             a.bn = arena.upload(bi);
             const int ho = h / a.stride;
             flops_per_face += 2.0 * 9 * a.cin * a.depth * h * h + 2.0 * 9 * a.depth * a.depth * ho * ho;
             if (a.wsc) flops_per_face += 2.0 * a.cin * a.depth * ho * ho;
             units.push_back(a);
-            h = ho;
-            ++idx;
         }
     // output layer (model_irse.py:143-147): Linear over the NCHW flatten (index c*49 + hw) re-ordered to NHWC (hw*512 + c)
     {
@@ -533,12 +556,14 @@ int frt_embedder_create(const char *weights_path, int in_c, int in_h, int in_w, 
         std::string err;
         const int rc = blob.load(weights_path, err);
         if (rc) raise(rc, err);
-        if (blob.kind != 2 && blob.kind != 3) raise(FRT_ERR_FORMAT, "embedder: weight blob is not an ArcFace IR-50 / IR-SE-50 blob");
+        if (blob.kind != 2 && blob.kind != 3) raise(FRT_ERR_FORMAT, "embedder: weight blob is not an ArcFace IR / IR-SE blob");
+        const frt::ArcLayout layout = frt::arc_layout(blob, blob.kind == 3);  // (host only: a malformed blob fails before any HIP call)
         use_device(device);
         std::unique_ptr<frt_embedder> e(new frt_embedder);
         e->device = device;
         e->max_batch = max_batch;
         e->se = blob.kind == 3;
+        e->layout = layout;
         e->blob_path = weights_path;
         HIPCHK(hipStreamCreate(&e->stream));
         HIPCHK(hipEventCreateWithFlags(&e->ev_busy[0], hipEventDisableTiming));
@@ -546,6 +571,22 @@ int frt_embedder_create(const char *weights_path, int in_c, int in_h, int in_w, 
         e->build(blob);
         HIPCHK(hipDeviceSynchronize());
         *out = e.release();
+    });
+}
+
+int frt_embedder_describe(const char *weights_path, int *num_layers, int *se, int *units_per_stage) {
+    return guarded([&] {
+        if (!weights_path) raise(FRT_ERR_INVALID, "null argument");
+        frt::Blob blob;
+        std::string err;
+        const int rc = blob.load(weights_path, err);
+        if (rc) raise(rc, err);
+        if (blob.kind != 2 && blob.kind != 3) raise(FRT_ERR_FORMAT, "embedder: weight blob is not an ArcFace IR / IR-SE blob");
+        const frt::ArcLayout layout = frt::arc_layout(blob, blob.kind == 3);
+        if (num_layers) *num_layers = layout.num_layers;
+        if (se) *se = layout.se ? 1 : 0;
+        if (units_per_stage)
+            for (int i = 0; i < 4; ++i) units_per_stage[i] = layout.stage_units[i];
     });
 }
 

@@ -28,6 +28,8 @@ struct frt_embedder {
     Arena arena;
     int max_batch = 1;
     bool se = false;
+    frt::ArcLayout layout;     // backbone read from the blob (frt::arc_layout): IR-50 / 100 / 152, with or without SE
+    float stream_scale = 1.f;  // residual-stream conditioning factor of the fp16 path (a power of two; 1 except for deep IR blobs, build())
     std::vector<ArcUnit> units;
     float *in_w, *in_s0, *in_b0, *in_slope, *in_s1, *in_b1;
     half_t *in_wh = nullptr;

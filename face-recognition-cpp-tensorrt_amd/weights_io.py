@@ -9,11 +9,17 @@ all folding (BatchNorm), layout permutes and fp16 casts happen inside ``libfrt.s
 Layout::
 
     char[8]  magic  = b"FRTW0001"
-    u32      kind   (1 = retinaface mobilenet0.25 trimmed, 2 = arcface IR-50, 3 = arcface IR-SE-50)
+    u32      kind   (1 = retinaface mobilenet0.25 trimmed, 2 = arcface IR family, 3 = arcface IR-SE family)
     u32      n_tensors
     n_tensors x { u16 name_len; char name[name_len]; u8 ndim; u32 dims[ndim]; u64 offset; u64 n_elem }
     ... padding to a 64-byte boundary ...
     float32 data, every tensor 64-byte aligned; ``offset`` is relative to the start of the file.
+
+Kinds 2 and 3 hold any depth of ``conversion/arcface/model_irse.py``: IR-50 / IR-100 / IR-152 (``IR_50``, ``IR_101``, ``IR_152``) and
+their SE variants.  ``libfrt.so`` reads the depth from the tensors (``frt_embedder_describe``); the exporter's ``--kind`` names the depth
+too and refuses a checkpoint whose tensors are another backbone::
+
+    python weights_io.py backbone_ir50_asia.pth rec.frtw --kind ir50       # also: ir100, ir152, ir_se50, ir_se100, ir_se152
 """
 import struct
 from collections import OrderedDict
@@ -24,6 +30,12 @@ MAGIC = b"FRTW0001"
 KIND_RETINAFACE_MNET025 = 1
 KIND_ARCFACE_IR50 = 2
 KIND_ARCFACE_IR_SE50 = 3
+KIND_ARCFACE_IR = KIND_ARCFACE_IR50        # the IR family of any depth
+KIND_ARCFACE_IR_SE = KIND_ARCFACE_IR_SE50  # the IR-SE family of any depth
+# --kind -> (blob kind, layers, SE) for the recogniser backbones of model_irse.py
+ARCFACE_KINDS = {"ir50": (2, 50, False), "ir100": (2, 100, False), "ir152": (2, 152, False),
+                 "ir_se50": (3, 50, True), "ir_se100": (3, 100, True), "ir_se152": (3, 152, True)}
+IR_STAGES = {50: (3, 4, 14, 3), 100: (3, 13, 30, 3), 152: (3, 8, 36, 3)}  # model_irse.py get_blocks
 
 
 def _align(n, a=64):
@@ -89,11 +101,43 @@ def read_blob(path):
     return kind, out
 
 
+def arcface_layout(state):
+    """(num_layers, se) of an IR / IR-SE state dict; ValueError naming the first tensor that does not fit one of the six backbones.
+    The same rules as libfrt's loader (csrc/frt_weights.hpp arc_layout), restated on the names and shapes."""
+    n = 0
+    while "body.%d.res_layer.1.weight" % n in state:
+        n += 1
+    se = "body.0.res_layer.5.fc1.weight" in state
+    stages, prev = [], 64
+    for i in range(n):
+        p = "body.%d" % i
+        depth, cin = np.shape(state[p + ".res_layer.1.weight"])[:2]
+        sc = p + ".shortcut_layer.0.weight" in state
+        if i == 0 or sc or depth != prev:
+            stages.append(0)
+        stages[-1] += 1
+        if len(stages) > 4 or depth != (64, 128, 256, 512)[len(stages) - 1] or cin != prev or sc != (cin != depth):
+            raise ValueError("%s.res_layer.1.weight: unit %d does not fit an IR backbone" % (p, i))
+        if (p + ".res_layer.5.fc1.weight" in state) != se:
+            raise ValueError("%s.res_layer.5.fc1.weight: SE units mixed with plain ones" % p)
+        prev = depth
+    left = sorted(k for k in state if k.startswith("body.") and not (k.split(".")[1].isdigit() and int(k.split(".")[1]) < n))
+    if left:
+        raise ValueError("unexpected tensor %s" % left[0])
+    for layers, table in IR_STAGES.items():
+        if tuple(stages) == table:
+            return layers, se
+    raise ValueError("body.0 - body.%d: stage table %s is none of %s" % (n - 1, tuple(stages), sorted(IR_STAGES.values())))
+
+
 def export_pth(pth_path, out_path, kind):
     """``.pth`` -> FRTW blob; the replacement for ``conversion/*/torch2trt.py``.
 
     Strips the ``module.`` prefix and unwraps a ``state_dict`` key exactly like
     ``/root/reference/conversion/retina/torch2trt.py:41-61``.
+
+    ``kind`` is a blob kind (1, 2, 3) or a name of ``ARCFACE_KINDS``; a named recogniser kind refuses (ValueError) a checkpoint whose
+    tensors are another backbone.
     """
     import torch
 
@@ -104,6 +148,13 @@ def export_pth(pth_path, out_path, kind):
     for k, v in sd.items():
         k = k.split("module.", 1)[-1] if k.startswith("module.") else k
         clean[k] = v.detach().cpu().float().numpy()
+    if kind in ARCFACE_KINDS:
+        kind, layers, se = ARCFACE_KINDS[kind]
+        got = arcface_layout(clean)
+        if got != (layers, se):
+            raise ValueError("%s holds IR%s-%d, not the IR%s-%d asked for" % (pth_path, "-SE" if got[1] else "", got[0], "-SE" if se else "", layers))
+    elif kind == "retinaface":
+        kind = KIND_RETINAFACE_MNET025
     return write_blob(out_path, clean, kind)
 
 
@@ -113,6 +164,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description="Export a PyTorch .pth checkpoint to an FRTW weight blob")
     ap.add_argument("pth")
     ap.add_argument("out")
-    ap.add_argument("--kind", choices=["retinaface", "ir50", "ir_se50"], required=True)
+    ap.add_argument("--kind", choices=["retinaface"] + list(ARCFACE_KINDS), required=True)
     a = ap.parse_args()
-    export_pth(a.pth, a.out, {"retinaface": 1, "ir50": 2, "ir_se50": 3}[a.kind])
+    export_pth(a.pth, a.out, a.kind)

@@ -107,10 +107,16 @@ int frt_crop_faces(const uint8_t *bgr, int rows, int cols, size_t row_stride, co
  * ------------------------------------------------------------------------------------------------------------------ */
 
 /* ArcFaceIR50::ArcFaceIR50 (src/arcface.cpp:21-43) + loadEngine (:45-69) + preInference (:88-103).
- * weights_path: FRTW blob kind 2 (IR-50, the reference's network) or kind 3 (IR-SE-50).  in_c,in_h,in_w must be
- * 3,112,112 and out_dim 512.  max_batch = faces per device launch (the reference default is 1, app/config.json:18). */
+ * weights_path: FRTW blob kind 2 (IR family: IR-50, the reference's network, IR-100, IR-152) or kind 3 (IR-SE family: IR-SE-50 /
+ * 100 / 152); the depth is read from the blob's tensors (frt_embedder_describe).  in_c,in_h,in_w must be 3,112,112 and out_dim 512.
+ * max_batch = faces per device launch (the reference default is 1, app/config.json:18). */
 int frt_embedder_create(const char *weights_path, int in_c, int in_h, int in_w, int out_dim, int max_batch, int device,
                         frt_embedder **out);
+/* The backbone a recogniser blob holds, with the validation frt_embedder_create runs and no HIP call (works without a device).
+ * num_layers <- 50 / 100 / 152, se <- 1 for IR-SE, units_per_stage[4] <- {3,4,14,3} / {3,13,30,3} / {3,8,36,3} (model_irse.py
+ * get_blocks); any output pointer may be NULL.  A blob with a missing or mis-sized tensor, a body.* tensor no unit owns, SE units mixed
+ * with plain ones or another stage table gives FRT_ERR_FORMAT, and frt_last_error() names the tensor. */
+int frt_embedder_describe(const char *weights_path, int *num_layers, int *se, int *units_per_stage);
 void frt_embedder_destroy(frt_embedder *e);
 
 /* IR-SE-50 only (no reference counterpart; the reference's engine is a black box): 1 (default, env FRT_SE_FUSED=0 turns it off) runs the

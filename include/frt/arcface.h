@@ -61,6 +61,9 @@ struct ArcFaceIR50Statics {
 template <class Tag>
 int ArcFaceIR50Statics<Tag>::classCount = 0;
 
+// engineFile (config.json's rec_engine) may be any of the six recogniser blobs weights_io.py exports: IR-50 (the reference's network),
+// IR-100, IR-152 and their SE variants (--kind ir50 | ir100 | ir152 | ir_se50 | ir_se100 | ir_se152).  The depth is read from the
+// blob; the class keeps the reference's name and API for all of them.
 class ArcFaceIR50 : public ArcFaceIR50Statics<> {
   public:
     ArcFaceIR50(TRTLogger gLogger, const std::string engineFile, int frameWidth, int frameHeight, std::string inputName, std::string outputName,

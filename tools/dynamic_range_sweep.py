@@ -17,6 +17,10 @@ function exactly - csrc/frt_embedder.cpp), so the branch sweep is f
 4.8e-4 at 1e-4, non-finite at 1e4).  The tuning build's FRT_ARC_CONDITION=0 restores the unconditioned load for an A/B.
 
     python tools/dynamic_range_sweep.py --out gpurun_out/r03_dynamic_range.json        (GPU box)
+    python tools/dynamic_range_sweep.py --backbones ir100 ir_se152 --which stream --out profiles/r07/r07_deep_range.json
+
+--backbones picks any of the six model_irse.py backbones (default: ir50 ir_se50, the sweep as it was); the deep IR stacks get the load-time
+residual-stream conditioning of DESIGN 3.19.
 """
 import argparse
 import json
@@ -62,10 +66,10 @@ def rescale(sd, s=1.0, t=1.0, mode="ir"):
     return OrderedDict((k, v.astype(np.float32)) for k, v in o.items())
 
 
-def sweep(frt, mode, scales, n_faces=8, which="stream"):
+def sweep(frt, mode, scales, n_faces=8, which="stream", num_layers=50):
     from oracle import nets
     sy = frt.synth
-    base = sy.arcface_state(2, mode, calib=sy.load_calibration(mode))
+    base = sy.arcface_state(2, mode, num_layers=num_layers, calib=sy.load_calibration(mode) if num_layers == 50 else None)
     faces = sy.make_faces(n_faces)
     x = np.ascontiguousarray(((faces[..., ::-1].astype(np.float32) - 127.5) * 0.0078125).transpose(0, 3, 1, 2))
     ref = nets.arcface_forward(base, x)
@@ -84,7 +88,7 @@ def sweep(frt, mode, scales, n_faces=8, which="stream"):
                      "finite": finite, "nonfinite_values": int((~np.isfinite(got)).sum()),
                      "zero_embeddings": int((np.abs(got).sum(1) == 0).sum()),
                      "oracle_self_consistency": float(1 - (o32 * ref).sum(1).min())})
-        print(mode, which, json.dumps(rows[-1]), flush=True)
+        print("%s%d" % (mode, num_layers), which, json.dumps(rows[-1]), flush=True)
     return rows
 
 
@@ -92,14 +96,18 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--faces", type=int, default=8)
+    ap.add_argument("--backbones", nargs="+", default=["ir50", "ir_se50"], choices=["ir50", "ir100", "ir152", "ir_se50", "ir_se100", "ir_se152"])
+    ap.add_argument("--which", nargs="+", default=["stream", "branch"], choices=["stream", "branch"])
     args = ap.parse_args()
     import __graft_entry__ as entry
     frt = entry.load_pkg()
     scales = [1e-4, 1e-3, 1e-2, 1e-1, 1.0, 1e1, 1e2, 1e3, 1e4]
     report = {"what": __doc__.split("\n\n")[0], "tolerance": "north_star: embeddings cosine-equal within 1e-4", "faces": args.faces, "runs": {}}
-    for mode in ("ir", "ir_se"):
-        for which in ("stream", "branch"):
-            report["runs"]["%s/%s" % (mode, which)] = sweep(frt, mode, scales, args.faces, which)
+    for tag in args.backbones:
+        mode, layers = tag[:-3] if tag.endswith(("100", "152")) else tag[:-2], int(tag[-3:] if tag.endswith(("100", "152")) else tag[-2:])
+        for which in args.which:
+            key = "%s/%s" % (mode, which) if layers == 50 else "%s/%s" % (tag, which)  # (IR-50 keys as before)
+            report["runs"][key] = sweep(frt, mode, scales, args.faces, which, layers)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
