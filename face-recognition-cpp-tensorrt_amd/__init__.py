@@ -49,6 +49,7 @@ ABI = {
     "frt_detector_create": (_i, [ctypes.c_char_p, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, ctypes.POINTER(_vp)]),
     "frt_detector_destroy": (None, [_vp]),
     "frt_detector_num_anchors": (_i, [_vp]),
+    "frt_detector_describe": (_i, [ctypes.c_char_p, ctypes.POINTER(_i), ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "frt_detector_find_faces": (_i, [_vp, _vp, _i, _i, _sz, _vp, _vp]),
     "frt_detector_find_faces_batch": (_i, [_vp, _vp, _i, _i, _i, _sz, _sz, _vp, _vp]),
     "frt_detector_preprocess": (_i, [_vp, _vp, _i, _i, _sz, _vp]),
@@ -203,6 +204,17 @@ def describe_weights(path):
     n, se, units = _i(), _i(), (_i * 4)()
     _check(lib.frt_embedder_describe(os.fsencode(path), ctypes.byref(n), ctypes.byref(se), units))
     return dict(numLayers=n.value, se=bool(se.value), unitsPerStage=tuple(units))
+
+
+DETECTOR_FAMILIES = {1: "mnet0.25", 4: "slim", 5: "rfb"}
+
+
+def describe_detector_weights(path):
+    """The network a detector blob holds (frt_detector_describe: the validation of RetinaFace's constructor, no device needed)
+    -> dict(family="mnet0.25" | "slim" | "rfb", kind=1 | 4 | 5, levels=3 | 4, hasLandmarks=bool)."""
+    fam, lv, ldm = _i(), _i(), _i()
+    _check(lib.frt_detector_describe(os.fsencode(path), ctypes.byref(fam), ctypes.byref(lv), ctypes.byref(ldm)))
+    return dict(family=DETECTOR_FAMILIES[fam.value], kind=fam.value, levels=lv.value, hasLandmarks=bool(ldm.value))
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -394,6 +406,7 @@ class RetinaFace:
                                        self.maxFacesPerScene, nms_threshold, bbox_threshold, device, ctypes.byref(self._h)))
         self.numAnchors = lib.frt_detector_num_anchors(self._h)
         self.hasLandmarks = bool(lib.frt_detector_has_landmarks(self._h))
+        self.family = describe_detector_weights(engineFile)["family"]  # "mnet0.25", "slim" or "rfb"
 
     # ---- optional alignment mode (no counterpart in the reference, see include/frt.h)
     def findFaceLandmarks(self, img):

@@ -34,6 +34,19 @@ void fold_pw(const frt::Blob &b, const std::string &conv, const std::string &bn,
         for (int ci = 0; ci < cin; ++ci) w[(size_t)ci * cout + co] = src[(size_t)co * cin + ci] * sc[co];
     bias = bi;
 }
+// bias-only convs (Slim / RFB heads and conv14) as BN-free folds: depthwise [C][9] + bias, pointwise transposed [Cin][Cout] + bias
+void dw_bias(const frt::Blob &b, const std::string &conv, int c, std::vector<float> &w, std::vector<float> &bias) {
+    const float *src = b.get(conv + ".weight", (size_t)c * 9).data, *bs = b.get(conv + ".bias", c).data;
+    w.assign(src, src + (size_t)c * 9);
+    bias.assign(bs, bs + c);
+}
+void pw_bias(const frt::Blob &b, const std::string &conv, int cout, int cin, std::vector<float> &w, std::vector<float> &bias) {
+    const float *src = b.get(conv + ".weight", (size_t)cout * cin).data, *bs = b.get(conv + ".bias", cout).data;
+    w.resize((size_t)cin * cout);
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci) w[(size_t)ci * cout + co] = src[(size_t)co * cin + ci];
+    bias.assign(bs, bs + cout);
+}
 inline int conv_out(int x, int stride) { return (x + 2 - 3) / stride + 1; }
 // [Cin][9][Cout] fp32 -> fp16 hi/lo split [Cin/16][9][64][hi16 | lo16] (kernels_det_conv3h.hip); empty unless Cin is 64 or 16 and 16 <= Cout <= 64
 std::vector<uint16_t> pack_conv3_split(const std::vector<float> &w, int cin, int cout) {
@@ -93,7 +106,159 @@ std::vector<float> pack_conv3_mfma(const std::vector<float> &w, int cin, int cou
     return o;
 }
 
+// ---- Slim / RFB (conversion/retina/models/net_slim.py, net_rfb.py): the tensors of the state_dict, shapes included
+struct TensorSpec {
+    std::string name;
+    std::vector<uint32_t> dims;
+};
+constexpr int SLIM_DW[12][3] = {{16, 32, 1}, {32, 32, 2}, {32, 32, 1}, {32, 64, 2}, {64, 64, 1}, {64, 64, 1}, {64, 64, 1},
+                                {64, 128, 2}, {128, 128, 1}, {128, 128, 1}, {128, 256, 2}, {256, 256, 1}};  // conv2 - conv13: cin, cout, stride
+constexpr int SLIM_HEAD_C[3] = {64, 128, 256}, SLIM_NA[4] = {3, 2, 2, 3};
+// RFB conv8 (BasicRFB(64, 64, scale=1.0), inter_planes 8): branch convs {branch, index, cout, cin, k, dilation}
+constexpr int RFB_CONVS[10][6] = {{0, 0, 8, 64, 1, 1}, {0, 1, 16, 8, 3, 1}, {0, 2, 16, 16, 3, 2}, {1, 0, 8, 64, 1, 1}, {1, 1, 16, 8, 3, 1},
+                                  {1, 2, 16, 16, 3, 3}, {2, 0, 8, 64, 1, 1}, {2, 1, 12, 8, 3, 1}, {2, 2, 16, 12, 3, 1}, {2, 3, 16, 16, 3, 5}};
+
+std::vector<TensorSpec> slim_tensors(bool rfb, bool landmarks) {
+    std::vector<TensorSpec> v;
+    auto bn = [&](const std::string &p, uint32_t c) {
+        for (const char *f : {".weight", ".bias", ".running_mean", ".running_var"}) v.push_back({p + f, {c}});
+    };
+    v.push_back({"conv1.0.weight", {16, 3, 3, 3}});
+    bn("conv1.1", 16);
+    for (int i = 0; i < 12; ++i) {
+        const std::string p = "conv" + std::to_string(i + 2);
+        const uint32_t cin = SLIM_DW[i][0], cout = SLIM_DW[i][1];
+        if (rfb && i == 6) {
+            for (const auto &c : RFB_CONVS) {
+                const std::string q = "conv8.branch" + std::to_string(c[0]) + "." + std::to_string(c[1]);
+                v.push_back({q + ".conv.weight", {(uint32_t)c[2], (uint32_t)c[3], (uint32_t)c[4], (uint32_t)c[4]}});
+                bn(q + ".bn", c[2]);
+            }
+            v.push_back({"conv8.ConvLinear.conv.weight", {64, 48, 1, 1}});
+            bn("conv8.ConvLinear.bn", 64);
+            v.push_back({"conv8.shortcut.conv.weight", {64, 64, 1, 1}});
+            bn("conv8.shortcut.bn", 64);
+            continue;
+        }
+        v.push_back({p + ".0.weight", {cin, 1, 3, 3}});
+        bn(p + ".1", cin);
+        v.push_back({p + ".3.weight", {cout, cin, 1, 1}});
+        bn(p + ".4", cout);
+    }
+    v.push_back({"conv14.0.weight", {64, 256, 1, 1}});
+    v.push_back({"conv14.0.bias", {64}});
+    v.push_back({"conv14.2.0.weight", {64, 1, 3, 3}});
+    v.push_back({"conv14.2.0.bias", {64}});
+    v.push_back({"conv14.2.2.weight", {256, 64, 1, 1}});
+    v.push_back({"conv14.2.2.bias", {256}});
+    const char *heads[3] = {"loc", "conf", "landm"};
+    const uint32_t per[3] = {4, 2, 10};
+    for (int h = 0; h < (landmarks ? 3 : 2); ++h) {
+        for (int k = 0; k < 3; ++k) {
+            const std::string p = std::string(heads[h]) + "." + std::to_string(k);
+            const uint32_t c = SLIM_HEAD_C[k], co = per[h] * SLIM_NA[k];
+            v.push_back({p + ".0.weight", {c, 1, 3, 3}});
+            v.push_back({p + ".0.bias", {c}});
+            v.push_back({p + ".2.weight", {co, c, 1, 1}});
+            v.push_back({p + ".2.bias", {co}});
+        }
+        const std::string p = std::string(heads[h]) + ".3";
+        v.push_back({p + ".weight", {per[h] * SLIM_NA[3], 256, 3, 3}});
+        v.push_back({p + ".bias", {per[h] * SLIM_NA[3]}});
+    }
+    return v;
+}
+
 }  // namespace
+
+// The network a detector blob holds; throws std::runtime_error naming the first missing, misshapen or unexpected tensor of a Slim / RFB blob
+// (FRT_ERR_FORMAT at the C ABI).  Host only: frt_detector_describe runs it without a device.
+DetLayout det_layout(const frt::Blob &b) {
+    DetLayout L;
+    L.family = (int)b.kind;
+    if (b.kind == 1) {  // mnet0.25: validated tensor by tensor while frt_detector::build folds it
+        L.levels = 3;
+        L.has_landmarks = b.has("LandmarkHead.0.conv1x1.weight");
+        return L;
+    }
+    if (b.kind != 4 && b.kind != 5) raise(FRT_ERR_FORMAT, "detector: weight blob is not a RetinaFace mobilenet0.25 / Slim / RFB blob");
+    L.levels = 4;
+    L.has_landmarks = b.has("landm.0.0.weight");
+    const std::vector<TensorSpec> spec = slim_tensors(b.kind == 5, L.has_landmarks);
+    std::map<std::string, int> want;
+    for (const auto &t : spec) {
+        want[t.name] = 1;
+        auto it = b.t.find(t.name);
+        if (it == b.t.end()) throw std::runtime_error("weight blob: missing tensor " + t.name);
+        size_t n = 1;
+        for (uint32_t d : t.dims) n *= d;
+        if (it->second.numel != n || it->second.dims != t.dims)
+            throw std::runtime_error("weight blob: wrong shape for " + t.name);
+    }
+    for (const auto &kv : b.t)
+        if (!want.count(kv.first))
+            throw std::runtime_error("weight blob: unexpected tensor " + kv.first + (b.kind == 4 ? " (not part of the Slim net)" : " (not part of the RFB net)"));
+    return L;
+}
+
+namespace {
+
+}  // namespace
+
+// one conv_dw block (dw3x3 + bias -> ReLU -> 1x1 + bias -> ReLU, BN folded) with every weight layout its kernels may use; its scratch
+// (tmp) is set once the whole op list is known (frt_detector_create: sized from the ops)
+frt_detector::Op frt_detector::dwpw_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias,
+                                       const std::vector<float> &w2, const std::vector<float> &bias2, int cin, int cout, int h, int w_, int oh,
+                                       int ow, int stride) {
+    const int B = max_batch;
+    Op o{};
+    o.type = 0;
+    std::vector<float> w12((size_t)cin * 12, 0.f);
+    for (int ci = 0; ci < cin; ++ci) {
+        for (int t = 0; t < 9; ++t) w12[(size_t)ci * 12 + t] = w[(size_t)ci * 9 + t];
+        w12[(size_t)ci * 12 + 9] = bias[ci];
+    }
+    o.dw = DwPwArgs{in, out, arena.upload(w), arena.upload(bias), arena.upload(w2), arena.upload(bias2), nullptr, 0, 0,
+                    B, cin, h, w_, cout, oh, ow, stride, 1, nullptr, arena.upload(w12), nullptr};
+    {
+        const std::vector<uint16_t> ph = pack_pw_split(w2, cin, cout);
+        if (!ph.empty()) o.dw.wph = reinterpret_cast<const half_t *>(arena.upload(ph));
+        if (cin % 2 == 0) {  // depthwise weights of channel pairs (kernels_det_wave.hip, kernels_det_stem.hip)
+            std::vector<float> wp2((size_t)cin * 10, 0.f);  // [Cin/2][10][2]: taps 0-8, bias; the channel pair interleaved
+            for (int ci = 0; ci < cin; ++ci) {
+                for (int t = 0; t < 9; ++t) wp2[(size_t)(ci / 2) * 20 + 2 * t + (ci & 1)] = w[(size_t)ci * 9 + t];
+                wp2[(size_t)(ci / 2) * 20 + 18 + (ci & 1)] = bias[ci];
+            }
+            o.dw.wdp = arena.upload(wp2);
+            if (cin <= 16) {
+                std::vector<float> wt((size_t)cin * 10, 0.f);
+                for (int ci = 0; ci < cin; ++ci) {
+                    for (int t = 0; t < 9; ++t) wt[((size_t)t * (cin / 2) + ci / 2) * 2 + (ci & 1)] = w[(size_t)ci * 9 + t];
+                    wt[((size_t)9 * (cin / 2) + ci / 2) * 2 + (ci & 1)] = bias[ci];
+                }
+                o.dw.wdt = arena.upload(wt);
+            }
+        }
+        if (!ph.empty() && cout % 32 == 0) {  // the other operands of dwpw_wave_kernel
+            std::vector<uint16_t> pf(ph.size());
+            const int ng = cin / 16, ncb = cout / 32;
+            for (int gq = 0; gq < ng; ++gq)
+                for (int cb = 0; cb < ncb; ++cb)
+                    for (int part = 0; part < 2; ++part)
+                        for (int ln = 0; ln < 64; ++ln)
+                            for (int j = 0; j < 8; ++j)
+                                pf[((((size_t)gq * ncb + cb) * 2 + part) * 64 + ln) * 8 + j] =
+                                    ph[((size_t)(cb * 32 + (ln & 31)) * ng + gq) * 32 + part * 16 + 8 * (ln >> 5) + j];
+            if (!d_wave_zeros) {
+                d_wave_zeros = arena.alloc<float>(dwpw_wave_zero_bytes() / 4);
+                HIPCHK(hipMemset(d_wave_zeros, 0, dwpw_wave_zero_bytes()));
+            }
+            o.dw.zeros = d_wave_zeros;
+            o.dw.wpf = reinterpret_cast<const half_t *>(arena.upload(pf));
+        }
+    }
+    return o;
+}
 
 void frt_detector::build(const frt::Blob &b) {
     const int B = max_batch, H = g.in_h, W = g.in_w;
@@ -189,52 +354,7 @@ void frt_detector::build(const frt::Blob &b) {
             } else {
                 fold_dw(b, p + ".0", p + ".1", l.cin, w, bias);
                 fold_pw(b, p + ".3", p + ".4", l.cout, l.cin, w2, bias2);
-                Op o{};
-                o.type = 0;
-                std::vector<float> w12((size_t)l.cin * 12, 0.f);
-                for (int ci = 0; ci < l.cin; ++ci) {
-                    for (int t = 0; t < 9; ++t) w12[(size_t)ci * 12 + t] = w[(size_t)ci * 9 + t];
-                    w12[(size_t)ci * 12 + 9] = bias[ci];
-                }
-                o.dw = DwPwArgs{cur, out, arena.upload(w), arena.upload(bias), arena.upload(w2), arena.upload(bias2), nullptr, 0, 0,
-                                B, l.cin, ch, cw, l.cout, oh, ow, l.stride, 1, d_tmp, arena.upload(w12), nullptr};
-                {
-                    const std::vector<uint16_t> ph = pack_pw_split(w2, l.cin, l.cout);
-                    if (!ph.empty()) o.dw.wph = reinterpret_cast<const half_t *>(arena.upload(ph));
-                    if (l.cin % 2 == 0) {  // depthwise weights of channel pairs (kernels_det_wave.hip, kernels_det_stem.hip)
-                        std::vector<float> wp2((size_t)l.cin * 10, 0.f);  // [Cin/2][10][2]: taps 0-8, bias; the channel pair interleaved
-                        for (int ci = 0; ci < l.cin; ++ci) {
-                            for (int t = 0; t < 9; ++t) wp2[(size_t)(ci / 2) * 20 + 2 * t + (ci & 1)] = w[(size_t)ci * 9 + t];
-                            wp2[(size_t)(ci / 2) * 20 + 18 + (ci & 1)] = bias[ci];
-                        }
-                        o.dw.wdp = arena.upload(wp2);
-                        if (l.cin <= 16) {
-                            std::vector<float> wt((size_t)l.cin * 10, 0.f);
-                            for (int ci = 0; ci < l.cin; ++ci) {
-                                for (int t = 0; t < 9; ++t) wt[((size_t)t * (l.cin / 2) + ci / 2) * 2 + (ci & 1)] = w[(size_t)ci * 9 + t];
-                                wt[((size_t)9 * (l.cin / 2) + ci / 2) * 2 + (ci & 1)] = bias[ci];
-                            }
-                            o.dw.wdt = arena.upload(wt);
-                        }
-                    }
-                    if (!ph.empty() && l.cout % 32 == 0) {  // the other operands of dwpw_wave_kernel
-                        std::vector<uint16_t> pf(ph.size());
-                        const int ng = l.cin / 16, ncb = l.cout / 32;
-                        for (int gq = 0; gq < ng; ++gq)
-                            for (int cb = 0; cb < ncb; ++cb)
-                                for (int part = 0; part < 2; ++part)
-                                    for (int ln = 0; ln < 64; ++ln)
-                                        for (int j = 0; j < 8; ++j)
-                                            pf[((((size_t)gq * ncb + cb) * 2 + part) * 64 + ln) * 8 + j] =
-                                                ph[((size_t)(cb * 32 + (ln & 31)) * ng + gq) * 32 + part * 16 + 8 * (ln >> 5) + j];
-                        if (!d_wave_zeros) {
-                            d_wave_zeros = arena.alloc<float>(dwpw_wave_zero_bytes() / 4);
-                            HIPCHK(hipMemset(d_wave_zeros, 0, dwpw_wave_zero_bytes()));
-                        }
-                        o.dw.zeros = d_wave_zeros;
-                        o.dw.wpf = reinterpret_cast<const half_t *>(arena.upload(pf));
-                    }
-                }
+                Op o = dwpw_op(cur, out, w, bias, w2, bias2, l.cin, l.cout, ch, cw, oh, ow, l.stride);
                 ops.push_back(o);
                 flops_per_frame += 2.0 * oh * ow * (9.0 * l.cin + (double)l.cin * l.cout);
             }
@@ -357,6 +477,186 @@ void frt_detector::build(const frt::Blob &b) {
     ops.push_back(ho);
 }
 
+// Slim (net_slim.py) and RFB (net_rfb.py): conv_bn + 12 conv_dw blocks (RFB: conv8 is a BasicRFB), conv14, and the loc / conf / landm heads
+// of four levels (x8, x11, x13, x14).  Blob validated by det_layout.
+void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
+    const int B = max_batch, H = g.in_h, W = g.in_w;
+    std::vector<float> w, bias, w2, bias2;
+    auto act = [&](int c, int h, int w_) { return arena.alloc<float>((size_t)B * c * h * w_); };
+    int ch = conv_out(H, 2), cw = conv_out(W, 2);
+    float *cur = act(16, ch, cw);
+    {  // conv1 = conv_bn(3, 16, 2): preprocess + the generic first conv (the fused u8 first conv covers mnet's Cout = 8 only)
+        fold_conv3(b, "conv1.0", "conv1.1", 16, 3, w, bias);
+        Op o{};
+        o.type = 1;
+        o.n = 1;
+        o.c3[0] = Conv3Args{d_input, cur, arena.upload(w), arena.upload(bias), B, 3, H, W, 16, ch, cw, 2, 1, 16, 0};
+        ops.push_back(o);
+        flops_per_frame += 2.0 * 3 * 9 * 16 * ch * cw;
+    }
+    const float *feat[4];
+    int fh[4], fw[4];
+    for (int i = 0; i < 12; ++i) {
+        const int cin = SLIM_DW[i][0], cout = SLIM_DW[i][1], stride = SLIM_DW[i][2];
+        const int oh = conv_out(ch, stride), ow = conv_out(cw, stride);
+        float *out = act(cout, oh, ow);
+        if (rfb && i == 6) {  // conv8 = BasicRFB(64, 64, scale = 1.0): 5 launches (kernels_det_slim.hip)
+            const int HW = ch * cw;
+            float *red = act(24, ch, cw), *sc = act(64, ch, cw), *ta = act(44, ch, cw), *tb = act(16, ch, cw), *cat = act(48, ch, cw);
+            Op o{};
+            o.type = 6;
+            std::vector<float> wp((size_t)64 * 88), bp(88);
+            for (int j = 0; j < 3; ++j) {
+                const std::string q = "conv8.branch" + std::to_string(j) + ".0";
+                fold_pw(b, q + ".conv", q + ".bn", 8, 64, w2, bias2);
+                for (int ci = 0; ci < 64; ++ci)
+                    for (int co = 0; co < 8; ++co) wp[(size_t)ci * 88 + j * 8 + co] = w2[(size_t)ci * 8 + co];
+                for (int co = 0; co < 8; ++co) bp[j * 8 + co] = bias2[co];
+            }
+            fold_pw(b, "conv8.shortcut.conv", "conv8.shortcut.bn", 64, 64, w2, bias2);
+            for (int ci = 0; ci < 64; ++ci)
+                for (int co = 0; co < 64; ++co) wp[(size_t)ci * 88 + 24 + co] = w2[(size_t)ci * 64 + co];
+            for (int co = 0; co < 64; ++co) bp[24 + co] = bias2[co];
+            o.rp = RfbProjArgs{cur, arena.upload(wp), arena.upload(bp), red, sc, B, ch, cw};
+            ops.push_back(o);
+            flops_per_frame += 2.0 * HW * 64 * 88;
+            // 3x3 convs: {branch.index, cin, cout, dilation, relu, in, in_ctotal, in_coff, out, out_ctotal, out_coff}
+            struct C3 {
+                const char *name;
+                int cin, cout, dil, relu;
+                const float *in;
+                int ict, ico;
+                float *out;
+                int oct, oco;
+            };
+            const C3 stages[3][3] = {{{"branch0.1", 8, 16, 1, 1, red, 24, 0, ta, 44, 0}, {"branch1.1", 8, 16, 1, 1, red, 24, 8, ta, 44, 16},
+                                      {"branch2.1", 8, 12, 1, 1, red, 24, 16, ta, 44, 32}},
+                                     {{"branch2.2", 12, 16, 1, 1, ta, 44, 32, tb, 16, 0}, {}, {}},
+                                     {{"branch0.2", 16, 16, 2, 0, ta, 44, 0, cat, 48, 0}, {"branch1.2", 16, 16, 3, 0, ta, 44, 16, cat, 48, 16},
+                                      {"branch2.3", 16, 16, 5, 0, tb, 16, 0, cat, 48, 32}}};
+            for (int st = 0; st < 3; ++st) {
+                Op c{};
+                c.type = 7;
+                c.n = st == 1 ? 1 : 3;
+                c.rc.B = B;
+                c.rc.H = ch;
+                c.rc.W = cw;
+                for (int k = 0; k < c.n; ++k) {
+                    const C3 &d = stages[st][k];
+                    const std::string q = std::string("conv8.") + d.name;
+                    if (d.cin > 16 || d.cout > 16) raise(FRT_ERR_INVALID, "detector: RFB conv shape not covered");
+                    fold_conv3(b, q + ".conv", q + ".bn", d.cout, d.cin, w, bias);
+                    std::vector<float> wpad((size_t)d.cin * 9 * 16, 0.f), bpad(16, 0.f);
+                    for (size_t r = 0; r < (size_t)d.cin * 9; ++r)
+                        for (int co = 0; co < d.cout; ++co) wpad[r * 16 + co] = w[r * d.cout + co];
+                    for (int co = 0; co < d.cout; ++co) bpad[co] = bias[co];
+                    c.rc.p[k] = RfbConvArgs{d.in, d.out, arena.upload(wpad), arena.upload(bpad), d.cin, d.cout, d.dil, d.relu, d.ict, d.ico, d.oct, d.oco};
+                    flops_per_frame += 2.0 * HW * d.cin * 9 * d.cout;
+                }
+                for (int k = c.n; k < 3; ++k) c.rc.p[k] = c.rc.p[0];
+                ops.push_back(c);
+            }
+            Op t{};
+            t.type = 8;
+            fold_pw(b, "conv8.ConvLinear.conv", "conv8.ConvLinear.bn", 64, 48, w2, bias2);
+            t.rt = RfbTailArgs{cat, arena.upload(w2), arena.upload(bias2), sc, out, 1.0f, B, ch, cw};
+            ops.push_back(t);
+            flops_per_frame += 2.0 * HW * 48 * 64;
+        } else {
+            const std::string p = "conv" + std::to_string(i + 2);
+            fold_dw(b, p + ".0", p + ".1", cin, w, bias);
+            fold_pw(b, p + ".3", p + ".4", cout, cin, w2, bias2);
+            ops.push_back(dwpw_op(cur, out, w, bias, w2, bias2, cin, cout, ch, cw, oh, ow, stride));
+            flops_per_frame += 2.0 * oh * ow * (9.0 * cin + (double)cin * cout);
+        }
+        cur = out;
+        ch = oh;
+        cw = ow;
+        const int lv = i == 6 ? 0 : (i == 9 ? 1 : (i == 11 ? 2 : -1));
+        if (lv >= 0) {
+            feat[lv] = cur;
+            fh[lv] = ch;
+            fw[lv] = cw;
+        }
+    }
+    {  // conv14: 1x1 256 -> 64 + bias + ReLU, then depth_conv2d(64, 256, 3, stride 2) + ReLU (a conv_dw block with biases for BN)
+        float *mid = act(64, ch, cw);
+        pw_bias(b, "conv14.0", 64, 256, w2, bias2);
+        Op o{};
+        o.type = 0;
+        o.dw = DwPwArgs{cur, mid, nullptr, nullptr, arena.upload(w2), arena.upload(bias2), nullptr, 0, 0, B, 256, ch, cw, 64, ch, cw, 1, 1,
+                        nullptr, nullptr, nullptr};
+        const std::vector<uint16_t> ph = pack_pw_split(w2, 256, 64);
+        if (!ph.empty()) o.dw.wph = reinterpret_cast<const half_t *>(arena.upload(ph));
+        ops.push_back(o);
+        flops_per_frame += 2.0 * ch * cw * 256 * 64;
+        const int oh = conv_out(ch, 2), ow = conv_out(cw, 2);
+        float *out = act(256, oh, ow);
+        dw_bias(b, "conv14.2.0", 64, w, bias);
+        pw_bias(b, "conv14.2.2", 256, 64, w2, bias2);
+        ops.push_back(dwpw_op(mid, out, w, bias, w2, bias2, 64, 256, ch, cw, oh, ow, 2));
+        flops_per_frame += 2.0 * oh * ow * (9.0 * 64 + 64.0 * 256);
+        feat[3] = out;
+        fh[3] = oh;
+        fw[3] = ow;
+    }
+    for (int k = 0; k < 4; ++k)
+        if (fh[k] != g.fh[k] || fw[k] != g.fw[k]) raise(FRT_ERR_INVALID, "detector: feature-map size mismatch");
+    const char *heads[3] = {"loc", "conf", "landm"};
+    const int per[3] = {4, 2, 10}, chan0[3] = {0, 12, 18};  // channel offsets of the three heads in the kernels' 48-channel layout
+    const int nh = has_landmarks ? 3 : 2;
+    Op ho{};
+    ho.type = 4;
+    ho.n = 3;
+    ho.sh.loc = d_loc;
+    ho.sh.conf = d_conf;
+    ho.sh.ldm = has_landmarks ? d_ldm : nullptr;
+    ho.sh.B = B;
+    ho.sh.A = g.A;
+    for (int k = 0; k < 3; ++k) {
+        const int C = SLIM_HEAD_C[k], na = SLIM_NA[k];
+        std::vector<float> wd((size_t)C * 30, 0.f), wp((size_t)C * 48, 0.f), bp(48, 0.f);
+        for (int h = 0; h < nh; ++h) {
+            const std::string p = std::string(heads[h]) + "." + std::to_string(k);
+            dw_bias(b, p + ".0", C, w, bias);
+            for (int ci = 0; ci < C; ++ci) {
+                for (int t = 0; t < 9; ++t) wd[(size_t)ci * 30 + h * 10 + t] = w[(size_t)ci * 9 + t];
+                wd[(size_t)ci * 30 + h * 10 + 9] = bias[ci];
+            }
+            const int co_n = per[h] * na;
+            pw_bias(b, p + ".2", co_n, C, w2, bias2);
+            for (int ci = 0; ci < C; ++ci)
+                for (int co = 0; co < co_n; ++co) wp[(size_t)ci * 48 + chan0[h] + co] = w2[(size_t)ci * co_n + co];
+            for (int co = 0; co < co_n; ++co) bp[chan0[h] + co] = bias2[co];
+            flops_per_frame += 2.0 * fh[k] * fw[k] * C * (9.0 + co_n);
+        }
+        ho.sh.lv[k] = SlimHeadArgs{feat[k], arena.upload(wd), arena.upload(wp), arena.upload(bp), C, fh[k], fw[k], na, g.base[k]};
+    }
+    ops.push_back(ho);
+    {  // level 3: loc / conf / landm = dense 3x3 convs 256 -> 12 / 6 / 30 (+ bias), one launch with the channels concatenated
+        const int na = SLIM_NA[3], cout = na * (has_landmarks ? 16 : 6), cpad = (cout + 15) / 16 * 16;
+        std::vector<float> wc((size_t)256 * 9 * cpad, 0.f), bc(cpad, 0.f);
+        int off = 0;
+        for (int h = 0; h < nh; ++h) {
+            const std::string p = std::string(heads[h]) + ".3";
+            const int co_n = per[h] * na;
+            const float *src = b.get(p + ".weight", (size_t)co_n * 256 * 9).data, *bs = b.get(p + ".bias", co_n).data;
+            for (int co = 0; co < co_n; ++co) {
+                for (int ci = 0; ci < 256; ++ci)
+                    for (int t = 0; t < 9; ++t) wc[((size_t)ci * 9 + t) * cpad + off + co] = src[((size_t)co * 256 + ci) * 9 + t];
+                bc[off + co] = bs[co];
+            }
+            off += co_n;
+        }
+        Op o{};
+        o.type = 5;
+        o.dh = DenseHeadArgs{feat[3], arena.upload(wc), arena.upload(bc), d_loc, d_conf, has_landmarks ? d_ldm : nullptr, B, 256, fh[3], fw[3], na, cout, cpad, g.A,
+                             g.base[3]};
+        ops.push_back(o);
+        flops_per_frame += 2.0 * fh[3] * fw[3] * 256 * 9 * cout;
+    }
+}
+
 void frt_detector::preprocess(const uint8_t *frames_dev, int n, size_t row_stride, size_t frame_stride, hipStream_t s) {
     ProfScope ps(2, "det_preprocess", (double)n * g.frame_h * g.frame_w * 3, s);
     launch_det_preprocess(frames_dev, n, g.frame_h, g.frame_w, row_stride, frame_stride, g.in_h, g.in_w, d_input, s);
@@ -436,6 +736,21 @@ void frt_detector::forward(int n, hipStream_t s, int first_op) {
         } else if (o.type == 1) {
             for (int k = 0; k < o.n; ++k) o.c3[k].B = n;
             launch_conv3x3_multi(o.c3, o.n, s);
+        } else if (o.type == 4) {
+            o.sh.B = n;
+            launch_slim_heads(o.sh, o.n, s);
+        } else if (o.type == 5) {
+            o.dh.B = n;
+            launch_dense_head(o.dh, s);
+        } else if (o.type == 6) {
+            o.rp.B = n;
+            launch_rfb_proj(o.rp, s);
+        } else if (o.type == 7) {
+            o.rc.B = n;
+            launch_rfb_conv(o.rc, o.n, s);
+        } else if (o.type == 8) {
+            o.rt.B = n;
+            launch_rfb_tail(o.rt, s);
         } else {
             for (int k = 0; k < o.n; ++k) o.hd[k].B = n;
             launch_heads_multi(o.hd, o.n, s);
@@ -468,20 +783,28 @@ int frt_detector_create(const char *weights_path, int frame_w, int frame_h, int 
         std::string err;
         const int rc = blob.load(weights_path, err);
         if (rc) raise(rc, err);
-        if (blob.kind != 1) raise(FRT_ERR_FORMAT, "detector: weight blob is not a RetinaFace-mobilenet0.25 blob");
+        const DetLayout layout = det_layout(blob);  // (host only: a malformed blob fails before any HIP call)
         use_device(device);
         std::unique_ptr<frt_detector> d(new frt_detector);
         d->device = device;
         d->max_batch = max_batch;
+        d->family = layout.family;
         DetGeom &g = d->g;
         g.in_w = in_w; g.in_h = in_h; g.frame_w = frame_w; g.frame_h = frame_h;
-        const float steps[3] = {8.f, 16.f, 32.f};
+        // the anchor table of the network's own training config: cfg_mnet, or cfg_slim / cfg_rfb (conversion/retina/config.py)
+        static const int mnet_sizes[3][DET_MAX_SIZES] = {{10, 20}, {32, 64}, {128, 256}}, mnet_n[3] = {2, 2, 2};
+        static const int slim_sizes[4][DET_MAX_SIZES] = {{10, 16, 24}, {32, 48}, {64, 96}, {128, 192, 256}}, slim_n[4] = {3, 2, 2, 3};
+        const bool mnet = layout.family == 1;
+        g.levels = layout.levels;
         int base = 0;
-        for (int k = 0; k < 3; ++k) {
-            g.fh[k] = (int)std::ceil(in_h / steps[k]);
-            g.fw[k] = (int)std::ceil(in_w / steps[k]);
+        for (int k = 0; k < g.levels; ++k) {
+            g.step[k] = (float)(8 << k);
+            g.nsz[k] = mnet ? mnet_n[k] : slim_n[k];
+            for (int l = 0; l < DET_MAX_SIZES; ++l) g.min_size[k][l] = mnet ? mnet_sizes[k][l] : slim_sizes[k][l];
+            g.fh[k] = (int)std::ceil(in_h / g.step[k]);
+            g.fw[k] = (int)std::ceil(in_w / g.step[k]);
             g.base[k] = base;
-            base += g.fh[k] * g.fw[k] * 2;
+            base += g.fh[k] * g.fw[k] * g.nsz[k];
         }
         g.A = base;
         g.scale_h = (float)in_h / frame_h;  // retinaface.cpp:21-22
@@ -502,14 +825,21 @@ int frt_detector_create(const char *weights_path, int frame_w, int frame_h, int 
         d->d_nout = d->arena.alloc<int>(B);
         d->d_dead = d->arena.alloc<uint8_t>(B * g.A);
         d->d_boxes = d->arena.alloc<frt_bbox>(B * max_faces);
-        d->d_tmp = d->arena.alloc<float>(B * 64 * (size_t)g.fh[0] * g.fw[0]);  // largest depthwise intermediate of a split conv_dw block
-        d->has_landmarks = blob.has("LandmarkHead.0.conv1x1.weight");
+        d->has_landmarks = layout.has_landmarks;
         if (d->has_landmarks) {
             d->d_ldm = d->arena.alloc<float>(B * g.A * 10);
             d->d_kept_anchor = d->arena.alloc<int>(B * max_faces);
             d->d_landmarks = d->arena.alloc<float>(B * max_faces * 10);
         }
-        d->build(blob);
+        if (mnet) d->build(blob);
+        else d->build_slim(blob, layout.family == 5);
+        // scratch of the split depthwise -> pointwise path: the largest depthwise intermediate of the built conv_dw ops
+        size_t tmp = B * 64 * (size_t)g.fh[0] * g.fw[0];
+        for (const auto &o : d->ops)
+            if (o.type == 0 && o.dw.wd) tmp = std::max(tmp, B * o.dw.Cin * (size_t)o.dw.Ho * o.dw.Wo);
+        d->d_tmp = d->arena.alloc<float>(tmp);
+        for (auto &o : d->ops)
+            if (o.type == 0 && o.dw.wd) o.dw.tmp = d->d_tmp;
         HIPCHK(hipDeviceSynchronize());
         *out = d.release();
     });
@@ -525,6 +855,20 @@ void frt_detector_destroy(frt_detector *d) {
     if (d->ev_busy) (void)hipEventDestroy(d->ev_busy);
     d->arena.release();
     delete d;
+}
+
+int frt_detector_describe(const char *weights_path, int *family, int *levels, int *has_landmarks) {
+    return guarded([&] {
+        if (!weights_path) raise(FRT_ERR_INVALID, "null argument");
+        frt::Blob blob;
+        std::string err;
+        const int rc = blob.load(weights_path, err);
+        if (rc) raise(rc, err);
+        const DetLayout layout = det_layout(blob);
+        if (family) *family = layout.family;
+        if (levels) *levels = layout.levels;
+        if (has_landmarks) *has_landmarks = layout.has_landmarks ? 1 : 0;
+    });
 }
 
 int frt_detector_num_anchors(const frt_detector *d) { return d ? d->g.A : 0; }

@@ -2,6 +2,13 @@
 #pragma once
 #include "frt_internal.hpp"
 
+struct DetLayout {
+    int family = 0;  // blob kind: 1 RetinaFace mobilenet0.25, 4 Slim, 5 RFB
+    int levels = 0;  // pyramid levels of the anchor table
+    bool has_landmarks = false;
+};
+DetLayout det_layout(const frt::Blob &b);  // throws on a blob that is no detector, or a Slim / RFB blob with a missing / misshapen / extra tensor
+
 struct frt_detector {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -23,7 +30,15 @@ struct frt_detector {
         DwPwArgs dw;
         Conv3Args c3[3];
         HeadArgs hd[3];
+        // Slim / RFB (kernels_det_slim.hip): 4 heads of levels 0-2, 5 dense head of level 3, 6 RFB projections, 7 RFB 3x3 convs (n problems),
+        // 8 RFB tail
+        SlimHeadsArgs sh;
+        DenseHeadArgs dh;
+        RfbProjArgs rp;
+        RfbConvMulti rc;
+        RfbTailArgs rt;
     };
+    int family = 1;  // blob kind: 1 mnet0.25, 4 Slim, 5 RFB
     float *d_tmp = nullptr;  // depthwise intermediate of the split conv_dw path
     float *d_wave_zeros = nullptr;  // zeros for dwpw_wave_kernel (input rows outside the image)
     std::vector<Op> ops;
@@ -41,6 +56,9 @@ struct frt_detector {
     float *d_landmarks = nullptr;  // decoded, frame coordinates [B][max_faces][10]
 
     void build(const frt::Blob &b);
+    Op dwpw_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias, const std::vector<float> &w2,
+               const std::vector<float> &bias2, int cin, int cout, int h, int w_, int oh, int ow, int stride);
+    void build_slim(const frt::Blob &b, bool rfb);  // kinds 4 / 5 (net_slim.py, net_rfb.py)
     void forward(int n, hipStream_t s, int first_op = 0);  // d_input -> d_loc/d_conf (first_op = 1: op 0 already ran)
     // preprocess + forward; when the letterbox is the identity the first conv reads the u8 frames and d_input is never written
     void forward_frames(const uint8_t *frames_dev, int n, size_t row_stride, size_t frame_stride, hipStream_t s);

@@ -96,10 +96,15 @@ bool match_screen_supported(int D);  // D the coarse kernel is instantiated for
 void launch_rows_to_half(const float *in, long row0, long n_rows, int D, half_t *g16, hipStream_t s);
 
 // ---------------------------------------------------------------- post-processing (kernels_post.hip)
-struct DetGeom {
+constexpr int DET_MAX_LEVELS = 4, DET_MAX_SIZES = 3;
+struct DetGeom {  // anchor table of one detector (mnet: 3 levels x 2 sizes; Slim / RFB: 4 levels x 3/2/2/3 sizes)
     int in_w, in_h, frame_w, frame_h;
-    int fw[3], fh[3];      // feature-map sizes per level (ceil(dim/step))
-    int base[3];           // first anchor index per level
+    int levels;
+    int fw[DET_MAX_LEVELS], fh[DET_MAX_LEVELS];  // feature-map sizes per level (ceil(dim/step))
+    int base[DET_MAX_LEVELS];                    // first anchor index per level
+    int nsz[DET_MAX_LEVELS];                     // anchor sizes per cell
+    int min_size[DET_MAX_LEVELS][DET_MAX_SIZES];
+    float step[DET_MAX_LEVELS];
     int A;                 // anchors per frame
     float scale_w, scale_h;
     float nms_thr, bbox_thr;
@@ -190,6 +195,53 @@ struct HeadArgs {
 };
 void launch_heads(const HeadArgs &a, hipStream_t s);
 void launch_heads_multi(const HeadArgs *a, int n, hipStream_t s);
+
+// ---------------------------------------------------------------- Slim / RFB detector parts (kernels_det_slim.hip), fp32 NCHW
+struct SlimHeadArgs {       // one of pyramid levels 0-2: the loc / conf / landm depth_conv2d heads (dw3x3 + bias -> ReLU -> 1x1 + bias)
+    const float *in;        // [B][C][H][W]
+    const float *wd;        // [C][3 heads][9 taps + bias]
+    const float *wp, *bp;   // [C][48], [48]: loc 4*3 | conf 2*3 | ldm 10*3 (zero beyond the level's na anchors)
+    int C, H, W, na, base;  // na anchors per cell, first anchor index of the level
+};
+struct SlimHeadsArgs {
+    SlimHeadArgs lv[3];
+    float *loc, *conf, *ldm;  // [B][A][4], [B][A][2] (softmax), [B][A][10]; ldm null: no landmark heads
+    int B, A;
+};
+void launch_slim_heads(const SlimHeadsArgs &a, int n, hipStream_t s);
+struct DenseHeadArgs {      // last level: dense 3x3 (pad 1) C -> cout = na*(4 + 2 [+ 10]) + bias, channels loc | conf | ldm
+    const float *in;        // [B][C][H][W]
+    const float *w, *b;     // [C][9][cpad] (cpad = cout rounded up to 16, zero-padded), [cpad]
+    float *loc, *conf, *ldm;
+    int B, C, H, W, na, cout, cpad, A, base;
+};
+void launch_dense_head(const DenseHeadArgs &a, hipStream_t s);
+struct RfbProjArgs {        // BasicRFB's 1x1 convs of x (64 channels): branch reductions 3 x 8 -> red [B][24], shortcut 64 -> sc [B][64]
+    const float *in;
+    const float *w, *b;     // [64][88] (24 reductions | 64 shortcut), [88]; BN folded
+    float *red, *sc;
+    int B, H, W;
+};
+void launch_rfb_proj(const RfbProjArgs &a, hipStream_t s);
+struct RfbConvArgs {        // 3x3, stride 1, dilation = padding = dil; reads channels [in_coff, +Cin) of a [B][in_ctotal] tensor
+    const float *in; float *out;
+    const float *w, *b;     // [Cin][9][16], [16] (Cout <= 16, zero-padded); BN folded
+    int Cin, Cout, dil, relu, in_ctotal, in_coff, out_ctotal, out_coff;
+};
+struct RfbConvMulti {       // up to 3 problems on the same H x W (blockIdx.z)
+    RfbConvArgs p[3];
+    int B, H, W;
+};
+void launch_rfb_conv(const RfbConvMulti &a, int n, hipStream_t s);
+struct RfbTailArgs {        // relu((ConvLinear 48 -> 64 + BN) * scale + shortcut)
+    const float *cat;       // [B][48][H][W]
+    const float *w, *b;     // [48][64], [64]
+    const float *sc;        // [B][64][H][W]
+    float *out;
+    float scale;
+    int B, H, W;
+};
+void launch_rfb_tail(const RfbTailArgs &a, hipStream_t s);
 
 // ---------------------------------------------------------------- recogniser network (kernels_arc.hip), fp16 NHWC + MFMA
 enum { EPI_PRELU = 0, EPI_BN = 1, EPI_BN_ADD_BN = 2, EPI_PARTIAL = 3, EPI_BN_SE = 4 };  // EPI_BN_SE: BN -> SE gate -> + shortcut -> BN_next (IR-SE unit tail)

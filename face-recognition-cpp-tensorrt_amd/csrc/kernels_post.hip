@@ -19,23 +19,33 @@
 namespace {
 
 constexpr int CC_STRIDE = 32;
-__constant__ int c_min_sizes[3][2] = {{10, 20}, {32, 64}, {128, 256}};
-__constant__ float c_steps[3] = {8.f, 16.f, 32.f};
+
+// level, size and cell of anchor a (order: level, row, column, size - create_anchor_retinaface's nesting)
+__device__ __forceinline__ void anchor_cell(const DetGeom &g, int a, int &k, int &l, int &i, int &j) {
+    k = 0;
+    for (int q = 1; q < g.levels; ++q)
+        if (a >= g.base[q]) k = q;
+    const int rel = a - g.base[k];
+    const int ns = g.nsz[k];
+    const int cell = rel / ns;
+    l = rel - cell * ns;
+    i = cell / g.fw[k];
+    j = cell - i * g.fw[k];
+}
 
 __device__ __forceinline__ int clipi(int v, int lo, int hi) {
     const int t = v < hi ? v : hi;
     return t > lo ? t : lo;
 }
 
-// Decode of ONE anchor (retinaface.cpp:161-187, 225-236): priors, box decode, corner truncation, un-letterbox, clip.
+// Decode of ONE anchor (retinaface.cpp:161-187, 225-236): priors, box decode, corner truncation, un-letterbox, clip.  The anchor table
+// (levels, steps, sizes) is the detector's own (DetGeom); the arithmetic is the reference's for every family.
 __device__ __forceinline__ frt_bbox decode_box(const DetGeom &g, int a, const float *__restrict__ loc_f, float score) {
-    const int k = a >= g.base[2] ? 2 : (a >= g.base[1] ? 1 : 0);
-    const int rel = a - g.base[k];
-    const int l = rel & 1, cell = rel >> 1;
-    const int i = cell / g.fw[k], j = cell - i * g.fw[k];
+    int k, l, i, j;
+    anchor_cell(g, a, k, l, i, j);
     const int w = g.in_w, h = g.in_h;
-    const float step = c_steps[k];
-    const int ms = c_min_sizes[k][l];
+    const float step = g.step[k];
+    const int ms = g.min_size[k][l];
     // priors: double arithmetic narrowed to float (retinaface.cpp:230-233)
     const float asx = (float)(ms * 1.0 / w);
     const float asy = (float)(ms * 1.0 / h);
@@ -304,12 +314,10 @@ __global__ void landmark_decode_kernel(const float *__restrict__ ldm, const int 
     float x = 0.f, y = 0.f;
     if (kbox < n_out[f]) {
         const int a = kept_anchor[(long)f * g.max_faces + kbox];
-        const int lv = a >= g.base[2] ? 2 : (a >= g.base[1] ? 1 : 0);
-        const int rel = a - g.base[lv];
-        const int l = rel & 1, cell = rel >> 1;
-        const int i = cell / g.fw[lv], j = cell - i * g.fw[lv];
-        const float step = c_steps[lv];
-        const float asx = (float)c_min_sizes[lv][l] / (float)g.in_w, asy = (float)c_min_sizes[lv][l] / (float)g.in_h;
+        int lv, l, i, j;
+        anchor_cell(g, a, lv, l, i, j);
+        const float step = g.step[lv];
+        const float asx = (float)g.min_size[lv][l] / (float)g.in_w, asy = (float)g.min_size[lv][l] / (float)g.in_h;
         const float acx = ((float)j + 0.5f) * step / (float)g.in_w, acy = ((float)i + 0.5f) * step / (float)g.in_h;
         const float *p = ldm + ((long)f * g.A + a) * 10 + 2 * k;
         x = (acx + p[0] * 0.1f * asx) * (float)g.in_w;

@@ -112,6 +112,80 @@ def retinaface_state(seed=1, class_bias=CLASS_BIAS, class_scale=1.0, bbox_scale=
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# Slim / RFB ("Face-Detector-1MB") - names as in net_slim.Slim(cfg_slim) / net_rfb.RFB(cfg_rfb) .state_dict()
+# ----------------------------------------------------------------------------------------------------------------------
+SLIM_DW = [(16, 32, 1), (32, 32, 2), (32, 32, 1), (32, 64, 2), (64, 64, 1), (64, 64, 1), (64, 64, 1), (64, 128, 2), (128, 128, 1),
+           (128, 128, 1), (128, 256, 2), (256, 256, 1)]  # conv2 - conv13: conv_dw(cin, cout, stride)
+SLIM_NA = (3, 2, 2, 3)  # anchors per cell of the four levels (cfg_slim min_sizes)
+# BasicRFB(64, 64, scale=1.0) (net_rfb.py:31-78), inter_planes 8: (branch, index, cout, cin, k)
+RFB_CONVS = [(0, 0, 8, 64, 1), (0, 1, 16, 8, 3), (0, 2, 16, 16, 3), (1, 0, 8, 64, 1), (1, 1, 16, 8, 3), (1, 2, 16, 16, 3),
+             (2, 0, 8, 64, 1), (2, 1, 12, 8, 3), (2, 2, 16, 12, 3), (2, 3, 16, 16, 3)]
+# per-level face-logit offsets, calibrated on make_frame(0..3) at 640x640 so that ~1 % of the anchors pass 0.6
+SLIM_CLASS_BIAS = (-7.6, -2.3, -6.6, -4.8)
+
+
+def slim_state(seed=5, rfb=False, class_bias=SLIM_CLASS_BIAS, bbox_scale=2.0, landmarks=True):
+    """state_dict of ``Slim(cfg_slim, 'test')`` (``net_slim.py``) or, with ``rfb=True``, ``RFB(cfg_rfb, 'test')`` (``net_rfb.py``).
+
+    ``class_bias`` (one per level, or one for all) is added to the face-class logit so that O(1 %) of anchors pass 0.6; the landmark
+    head biases form a face-like 5-point layout as in :func:`retinaface_state`.  ``landmarks=False`` leaves the ``landm.*`` heads out.
+    """
+    sd = OrderedDict()
+    _conv(sd, seed, "conv1.0.weight", 16, 3, 3, scale=1.0 / 48.0)
+    _bn(sd, seed, "conv1.1", 16)
+    for i, (cin, cout, _s) in enumerate(SLIM_DW):
+        p = "conv%d" % (i + 2)
+        if rfb and i == 6:
+            for br, j, co, ci, k in RFB_CONVS:
+                q = "conv8.branch%d.%d" % (br, j)
+                _conv(sd, seed, q + ".conv.weight", co, ci, k)
+                _bn(sd, seed, q + ".bn", co)
+            _conv(sd, seed, "conv8.ConvLinear.conv.weight", 64, 48, 1, gain=1.0)
+            _bn(sd, seed, "conv8.ConvLinear.bn", 64)
+            _conv(sd, seed, "conv8.shortcut.conv.weight", 64, 64, 1, gain=1.0)
+            _bn(sd, seed, "conv8.shortcut.bn", 64)
+            continue
+        _conv(sd, seed, p + ".0.weight", cin, 1, 3)
+        _bn(sd, seed, p + ".1", cin)
+        _conv(sd, seed, p + ".3.weight", cout, cin, 1)
+        _bn(sd, seed, p + ".4", cout)
+
+    def bias(name, n, std=0.1):
+        sd[name] = (std * _rng(seed, name).standard_normal(n)).astype(np.float32)
+
+    _conv(sd, seed, "conv14.0.weight", 64, 256, 1)
+    bias("conv14.0.bias", 64)
+    _conv(sd, seed, "conv14.2.0.weight", 64, 1, 3)
+    bias("conv14.2.0.bias", 64)
+    _conv(sd, seed, "conv14.2.2.weight", 256, 64, 1)
+    bias("conv14.2.2.bias", 256)
+    tmpl = (np.array(ARC_TEMPLATE, np.float64).reshape(5, 2) - 56.0) / 112.0 * 10.0
+    heads = [("loc", 4), ("conf", 2)] + ([("landm", 10)] if landmarks else [])
+    for h, per in heads:
+        for k, cin in enumerate((64, 128, 256, 256)):
+            co = per * SLIM_NA[k]
+            if k < 3:  # depth_conv2d(cin, co, kernel=3, pad=1)
+                p = "%s.%d" % (h, k)
+                _conv(sd, seed, p + ".0.weight", cin, 1, 3)
+                bias(p + ".0.bias", cin)
+                w, b = p + ".2.weight", p + ".2.bias"
+                _conv(sd, seed, w, co, cin, 1, gain=1.0)
+            else:  # nn.Conv2d(256, co, 3, padding=1)
+                w, b = "%s.3.weight" % h, "%s.3.bias" % h
+                _conv(sd, seed, w, co, cin, 3, gain=1.0)
+            if h == "loc":
+                sd[w] = (sd[w] * np.float32(bbox_scale)).astype(np.float32)
+            bv = 0.1 * _rng(seed, b).standard_normal(co)
+            if h == "conf":
+                bv[1::2] += class_bias[k] if hasattr(class_bias, "__len__") else class_bias  # channel 2l+1 = face logit of anchor l
+            if h == "landm":
+                sd[w] = (sd[w] * np.float32(0.6)).astype(np.float32)
+                bv += np.tile(tmpl.reshape(-1), SLIM_NA[k])
+            sd[b] = bv.astype(np.float32)
+    return sd
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # ArcFace IR-50 / IR-SE-50 - names as in model_irse.Backbone([112,112], 50, mode).state_dict()
 # ----------------------------------------------------------------------------------------------------------------------
 def ir_units(num_layers=50):

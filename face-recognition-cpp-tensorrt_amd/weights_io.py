@@ -9,7 +9,7 @@ all folding (BatchNorm), layout permutes and fp16 casts happen inside ``libfrt.s
 Layout::
 
     char[8]  magic  = b"FRTW0001"
-    u32      kind   (1 = retinaface mobilenet0.25 trimmed, 2 = arcface IR family, 3 = arcface IR-SE family)
+    u32      kind   (1 = retinaface mobilenet0.25 trimmed, 2 = arcface IR family, 3 = arcface IR-SE family, 4 = Slim, 5 = RFB)
     u32      n_tensors
     n_tensors x { u16 name_len; char name[name_len]; u8 ndim; u32 dims[ndim]; u64 offset; u64 n_elem }
     ... padding to a 64-byte boundary ...
@@ -20,6 +20,11 @@ their SE variants.  ``libfrt.so`` reads the depth from the tensors (``frt_embedd
 too and refuses a checkpoint whose tensors are another backbone::
 
     python weights_io.py backbone_ir50_asia.pth rec.frtw --kind ir50       # also: ir100, ir152, ir_se50, ir_se100, ir_se152
+
+Kinds 4 and 5 are the other two detectors ``conversion/retina/torch2trt.py --network slim | RFB`` exports (``net_slim.py``,
+``net_rfb.py``), with or without their landmark heads::
+
+    python weights_io.py slim_Final.pth det.frtw --kind slim               # also: rfb (or RFB), retinaface
 """
 import struct
 from collections import OrderedDict
@@ -30,6 +35,8 @@ MAGIC = b"FRTW0001"
 KIND_RETINAFACE_MNET025 = 1
 KIND_ARCFACE_IR50 = 2
 KIND_ARCFACE_IR_SE50 = 3
+KIND_RETINAFACE_SLIM = 4
+KIND_RETINAFACE_RFB = 5
 KIND_ARCFACE_IR = KIND_ARCFACE_IR50        # the IR family of any depth
 KIND_ARCFACE_IR_SE = KIND_ARCFACE_IR_SE50  # the IR-SE family of any depth
 # --kind -> (blob kind, layers, SE) for the recogniser backbones of model_irse.py
@@ -130,14 +137,31 @@ def arcface_layout(state):
     raise ValueError("body.0 - body.%d: stage table %s is none of %s" % (n - 1, tuple(stages), sorted(IR_STAGES.values())))
 
 
+DETECTOR_KINDS = {"retinaface": KIND_RETINAFACE_MNET025, "slim": KIND_RETINAFACE_SLIM, "rfb": KIND_RETINAFACE_RFB, "RFB": KIND_RETINAFACE_RFB}
+_DETECTOR_NAMES = {KIND_RETINAFACE_MNET025: "RetinaFace mobilenet0.25", KIND_RETINAFACE_SLIM: "Slim", KIND_RETINAFACE_RFB: "RFB"}
+
+
+def detector_family(state):
+    """Blob kind of a detector state dict by its distinctive tensors: 5 (RFB: conv8 is a BasicRFB), 4 (Slim: conv8 is a conv_dw block),
+    1 (mnet0.25: body.stage1.*); ValueError when it is none of them.  The full tensor-by-tensor check is libfrt's
+    (frt_detector_describe)."""
+    if any(k.startswith("conv8.branch0.") for k in state):
+        return KIND_RETINAFACE_RFB
+    if "conv8.0.weight" in state and "conv14.0.weight" in state:
+        return KIND_RETINAFACE_SLIM
+    if any(k.startswith("body.stage1.") for k in state):
+        return KIND_RETINAFACE_MNET025
+    raise ValueError("not a RetinaFace mobilenet0.25 / Slim / RFB state dict (no body.stage1.*, conv8.0.* or conv8.branch0.* tensors)")
+
+
 def export_pth(pth_path, out_path, kind):
     """``.pth`` -> FRTW blob; the replacement for ``conversion/*/torch2trt.py``.
 
     Strips the ``module.`` prefix and unwraps a ``state_dict`` key exactly like
     ``/root/reference/conversion/retina/torch2trt.py:41-61``.
 
-    ``kind`` is a blob kind (1, 2, 3) or a name of ``ARCFACE_KINDS``; a named recogniser kind refuses (ValueError) a checkpoint whose
-    tensors are another backbone.
+    ``kind`` is a blob kind (1 - 5), a name of ``ARCFACE_KINDS`` or of ``DETECTOR_KINDS``; a named kind refuses (ValueError) a checkpoint
+    whose tensors are another backbone / detector.
     """
     import torch
 
@@ -153,8 +177,11 @@ def export_pth(pth_path, out_path, kind):
         got = arcface_layout(clean)
         if got != (layers, se):
             raise ValueError("%s holds IR%s-%d, not the IR%s-%d asked for" % (pth_path, "-SE" if got[1] else "", got[0], "-SE" if se else "", layers))
-    elif kind == "retinaface":
-        kind = KIND_RETINAFACE_MNET025
+    elif kind in DETECTOR_KINDS:
+        kind = DETECTOR_KINDS[kind]
+        got = detector_family(clean)
+        if got != kind:
+            raise ValueError("%s holds a %s detector, not the %s asked for" % (pth_path, _DETECTOR_NAMES[got], _DETECTOR_NAMES[kind]))
     return write_blob(out_path, clean, kind)
 
 
@@ -164,6 +191,6 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser(description="Export a PyTorch .pth checkpoint to an FRTW weight blob")
     ap.add_argument("pth")
     ap.add_argument("out")
-    ap.add_argument("--kind", choices=["retinaface"] + list(ARCFACE_KINDS), required=True)
+    ap.add_argument("--kind", choices=list(DETECTOR_KINDS) + list(ARCFACE_KINDS), required=True)
     a = ap.parse_args()
     export_pth(a.pth, a.out, a.kind)

@@ -69,9 +69,15 @@ int frt_probe_sustained_mfma(int device, int mix, double seconds, double *tflops
  * ------------------------------------------------------------------------------------------------------------------ */
 
 /* RetinaFace::RetinaFace (src/retinaface.cpp:3-29) + loadEngine (:31-55) + preInference (:81-104).
- * weights_path: FRTW blob (kind 1) instead of a TensorRT engine.  in_c must be 3.  max_batch = frames per call. */
+ * weights_path: FRTW blob instead of a TensorRT engine: kind 1 (RetinaFace mobilenet0.25), 4 (Slim) or 5 (RFB) - the three
+ * networks of conversion/retina/torch2trt.py.  Each decodes with its own training anchors (cfg_mnet: 3 levels; cfg_slim / cfg_rfb: 4 levels,
+ * steps 8/16/32/64, sizes {10,16,24} {32,48} {64,96} {128,192,256}).  in_c must be 3.  max_batch = frames per call. */
 int frt_detector_create(const char *weights_path, int frame_w, int frame_h, int in_c, int in_h, int in_w, int max_batch,
                         int max_faces, float nms_threshold, float bbox_threshold, int device, frt_detector **out);
+/* The network a detector blob holds, validated as frt_detector_create does, without a device: family = blob kind (1 mnet0.25, 4 Slim,
+ * 5 RFB), levels = anchor pyramid levels (3 or 4), has_landmarks = 1 when the blob carries the landmark heads.  A missing, misshapen or
+ * unexpected tensor of a Slim / RFB blob -> FRT_ERR_FORMAT naming it (frt_last_error).  Any out pointer may be NULL. */
+int frt_detector_describe(const char *weights_path, int *family, int *levels, int *has_landmarks);
 /* RetinaFace::~RetinaFace (src/retinaface.cpp:273-280) */
 void frt_detector_destroy(frt_detector *d);
 /* m_OUTPUT_SIZE_BASE (src/retinaface.cpp:13): anchors per frame */
