@@ -11,15 +11,15 @@ cosine top-1 against a 1M x 512 fp32 gallery.  Nothing is cached between steps a
 THE MATCH STAGE IS NOT SURVEY 8(d)'s 2.048 GB fp32 scan: it is an int8-SCREENED coarse scan (0.51 GB shadow gallery, fp16 MFMA products of
 exactly widened int8 rows) + an EXACT fp32 re-rank of every 32-row block the rigorous error bound cannot exclude.  Its results
 are bit-identical to the exact scan's (tests/test_gpu_match.py), its cost depends on the queries: the default workload's queries match
-nothing in the gallery ("miss": ~ 11 candidate blocks per query); `match_legs` in the line carries the same step with the queries planted
+nothing in the gallery ("miss": ~ 11 candidate blocks per query); `match_legs` in the --full line carries the same step with the queries planted
 in the gallery ("hit") and with the screening switched off ("worst_case" = the exact fp32 scan of 8(d), frt_matcher_set_screening(m, 0)).
 
 TIMED REGION: u8 frames in PINNED HOST memory -> per-face (box, top-1 index, similarity) records back in host memory,
 through frt_pipeline_submit / frt_pipeline_wait with three batches in flight (H2D of 39 MB per step on the copy stream, D2H of the
 4.6 KB record block).  The figure with frames and results resident in HBM (frt_pipeline_run_dev) is reported beside it in
-`hbm_resident`; `--resident` makes it the primary one.  With N > 1 every rank (one process per GPU) owns a full gallery replica and
+`hbm_resident` (--full); `--resident` makes it the primary one.  With N > 1 every rank (one process per GPU) owns a full gallery replica and
 its own 32 frames (weak scaling; `--strong` splits ONE 32-frame batch over the ranks - BASELINE configs[3] as written, also reported
-as a side object of every N > 1 run).  Frames are independent, so there is NO collective on the data path; with N > 1 the per-face
+as a side object of every N > 1 --full run).  Frames are independent, so there is NO collective on the data path; with N > 1 the per-face
 result records of every step are all-gathered over RCCL on a side stream inside the timed region (configs[3]'s exchange step).
 `--sharded-gallery` runs configs[4] instead: the gallery is row-sharded over the ranks and stored as fp16, the embeddings are rounded to
 fp16 and all-gathered, every rank searches its shard for its top-k lists (global indices), the lists are all-gathered and merged on the
@@ -30,11 +30,16 @@ barrier / max-over-ranks bookkeeping.
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline      dominant kernel family = the ArcFace 3x3 implicit-GEMM convs; achieved = algorithmic FLOPs of those launches /
                 their HIP-event time, measured live on the stream they run on during one step of the timed region; peak = 2.5 PFLOP/s
-                dense fp16 MFMA (MI355X_MICROARCH.md); sustained_peak = what THIS device sustains on the kernel's instruction mix under its
-                power limit, measured in this process right after the timed region (frt_probe_sustained_mfma).
-  cpu_baseline  the oracle (reference-faithful CPU restatement, oracle/) timed on this box's host cores over bounded samples of
-                the same workload, rank 0 at N = 1 only: the full CPU pipeline and the reference's HOST-side work alone
+                dense fp16 MFMA (MI355X_MICROARCH.md); sustained_peak (--full) = what THIS device sustains on the kernel's instruction mix
+                under its power limit, measured in this process right after the timed region (frt_probe_sustained_mfma).
+  cpu_baseline  --full only (null otherwise): the oracle (reference-faithful CPU restatement, oracle/) timed on this box's host cores over
+                bounded samples of the same workload, rank 0 at N = 1 only: the full CPU pipeline and the reference's HOST-side work alone
                 (pre/post-processing + O(F*N) argmax), each with all cores and with one thread.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the line.  Everything measured beyond that takes
+runs of its own and is behind --full: the other boundary (hbm_resident / host_boundary), steady_state, sync_call_latency_ms,
+strong_scaling (N > 1), the serial roofline and roofline.stages, overlap_efficiency, match_legs, strong_scaling_proxy,
+roofline.sustained_peak and cpu_baseline.  --no-extras / --no-cpu-baseline drop parts of that set again.
 """
 import argparse
 import json
@@ -295,7 +300,10 @@ def main():
     ap.add_argument("--frame", default="640x640", help="frame size WxH (default 640x640 = the metric; 1920x1080 = BASELINE config 3's "
                                                        "video frames, letterboxed to the 640x640 detector input). Implies --no-cpu-baseline when not 640x640")
     ap.add_argument("--mode", default="ir", choices=["ir", "ir_se"], help="IR-50 (the reference's network) or IR-SE-50")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the line's own measurement, run every side measurement too (other boundary, steady "
+                                                        "state, serial roofline and stages, match legs, strong-scaling proxy, sustained peak, CPU "
+                                                        "baseline); off by default: a plain run does only what the headline figure needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--resident", action="store_true", help="primary timed region with frames/results resident in HBM (frt_pipeline_run_dev)")
     ap.add_argument("--strong", action="store_true", help="strong scaling: ONE batch of --batch frames split over the ranks (BASELINE configs[3])")
     ap.add_argument("--in-flight", type=int, default=DEPTH, help="batches in flight at the host boundary (1..11; default 3, 2 N + 2 with --pair N).  With --strong every rank "
@@ -319,7 +327,7 @@ def main():
                          "top-k lists) as DIR/<name>.npy in float32 / float64, for an output-by-output comparison of two builds")
     ap.add_argument("--stage-profile", default=None, help="write a per-stage HIP-event breakdown (extra untimed steps) to this file")
     ap.add_argument("--no-profile", action="store_true", help="do not record per-kernel HIP events in the timed region")
-    ap.add_argument("--no-extras", action="store_true", help="only the contract's timed region (no side measurements)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: no side measurements on the device (the CPU baseline stays)")
     ap.add_argument("--ab-old-lib", default=None, help="measurement only: run the timed region on an OLDER build of libfrt.so (path) for a same-box A/B "
                                                        "(tools/ab_lib.sh); symbols it lacks are skipped with a warning.  Never a reported number")
     ap.add_argument("--smi-trace", default=None, help="write the rocm-smi power/clock samples taken during the timed region to this file")
@@ -328,6 +336,8 @@ def main():
                          "(a server's request threads must not burn cores); this driver owns its core and one late wake-up is a third of a "
                          "20-step region, so it asks for 50 ms and says so in config.host_wait")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = True   # a plain run: the headline figure's own measurement only
     depth = max(1, min(11, args.in_flight))
     if args.pair and args.in_flight == DEPTH:
         depth = 2 * args.pair + 2   # grouped calls complete N at a time: two groups in the later stages + the detector's calls ahead of them

@@ -366,15 +366,16 @@ def test_config0_one_jpeg_ir_se_two_face_gallery(frt, orc, synth, blobs):
 
 
 def test_bench_line_contract():
-    """`python bench.py --gpus 1 --steps K --warmup W` (the driver's command, short): ONE JSON line with the contract's fields, the roofline
-    object of the dominant kernel (live HIP-event duration, counter traffic from profiles/) and the bounded cpu_baseline leg."""
+    """`python bench.py --gpus 1 --steps K --warmup W --full` (the driver's command, short, with every side measurement): ONE JSON line with
+    the contract's fields, the roofline object of the dominant kernel (live HIP-event duration, counter traffic from profiles/) and the bounded
+    cpu_baseline leg."""
     import json
     import subprocess
     import sys
 
     from conftest import ROOT
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2"], capture_output=True, text=True,
-                         timeout=1500, cwd=ROOT)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full"], capture_output=True,
+                         text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -391,6 +392,37 @@ def test_bench_line_contract():
     assert "conv_patchc_kernel<7" in r["kernel"] and r["launches"] == 27  # the 14x14 body convs on compact strips (the 7 at 28x28 stay on conv_patch_kernel)
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and c["cores"] >= 1 and c["unit"] == "faces/sec" and c["sample"]
+    for k in ("hbm_resident", "steady_state", "sync_call_latency_ms", "overlap_efficiency", "match_legs", "strong_scaling_proxy"):
+        assert k in d, k
+    assert "stages" in r and "serial_achieved" in r and "sustained_peak" in r
+
+
+def test_bench_plain_run_is_the_headline_only():
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: the same contract fields and the live roofline of the timed region,
+    and none of the side measurements that take runs of their own (cpu_baseline is null)."""
+    import json
+    import subprocess
+    import sys
+
+    from conftest import ROOT
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2"], capture_output=True,
+                         text=True, timeout=1500, cwd=ROOT)
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+              "config", "roofline", "cpu_baseline"):
+        assert k in d, k
+    assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["higher_is_better"] is True and d["unit"] == "faces/sec"
+    assert d["value"] > 5000 and abs(d["value"] - d["config"]["faces_per_step"] / (d["ms_per_step"] * 1e-3)) < 0.01 * d["value"]
+    r = d["roofline"]
+    assert r["bound"] == "mfma" and 0.05 < r["frac"] < 1 and r["launches"] == 27
+    assert d["cpu_baseline"] is None
+    for k in ("hbm_resident", "steady_state", "sync_call_latency_ms", "overlap_efficiency", "match_legs", "match_worst_case", "strong_scaling_proxy"):
+        assert k not in d, k
+    for k in ("stages", "serial_achieved", "sustained_peak"):
+        assert k not in r, k
 
 
 def test_bench_dump_outputs_are_the_last_timed_steps_records(frt, synth, blobs, tmp_path):

@@ -56,18 +56,18 @@ json.dump({"per_kernel": mo, "note": "rocprofv3 --pmc (one pass) over tools/prof
 PYEOF
 mkdir -p "$ROOT/profiles/${TAG:0:3}" && cp "$OUT/${TAG}_pmc_hbm.json" "$ROOT/profiles/${TAG:0:3}/" 2>/dev/null   # bench.py reads the newest profiles/*/*_pmc_hbm.json for roofline.traffic
 cd "$ROOT"
-# 3. the benchmark: driver-style line, default line (+ stage breakdown), power/clock trace over a long region
+# 3. the benchmark: driver-style line, --full line (+ stage breakdown), power/clock trace over a long region; --full wherever the side objects are wanted
 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/${TAG}_bench_driver.json" 2> "$OUT/${TAG}_bench_driver.stderr"
-python bench.py --stage-profile "$OUT/${TAG}_stages.json" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.stderr"
+python bench.py --full --stage-profile "$OUT/${TAG}_stages.json" > "$OUT/${TAG}_bench.json" 2> "$OUT/${TAG}_bench.stderr"
 python bench.py --steps 4000 --warmup 5 --no-cpu-baseline --no-extras --no-profile --smi-trace "$OUT/${TAG}_power_clock_trace.json" > "$OUT/${TAG}_bench_long.json" 2>/dev/null
-python bench.py --mode ir_se --no-cpu-baseline > "$OUT/${TAG}_bench_ir_se.json" 2>/dev/null
-python bench.py --frame 1920x1080 --no-cpu-baseline > "$OUT/${TAG}_bench_1080p.json" 2>/dev/null
-python bench.py --batch 1 --gallery 10000 --no-cpu-baseline > "$OUT/${TAG}_bench_config1.json" 2>/dev/null
-python bench.py --batch 1 --gallery 10000 --no-cpu-baseline --fp32 > "$OUT/${TAG}_bench_config1_fp32.json" 2>/dev/null   # BASELINE configs[1] as labelled: fp32 recogniser
+python bench.py --full --mode ir_se --no-cpu-baseline > "$OUT/${TAG}_bench_ir_se.json" 2>/dev/null
+python bench.py --full --frame 1920x1080 --no-cpu-baseline > "$OUT/${TAG}_bench_1080p.json" 2>/dev/null
+python bench.py --full --batch 1 --gallery 10000 --no-cpu-baseline > "$OUT/${TAG}_bench_config1.json" 2>/dev/null
+python bench.py --full --batch 1 --gallery 10000 --no-cpu-baseline --fp32 > "$OUT/${TAG}_bench_config1_fp32.json" 2>/dev/null   # BASELINE configs[1] as labelled: fp32 recogniser
 python bench.py --exact-match --no-cpu-baseline --no-extras > "$OUT/${TAG}_bench_exact_match.json" 2>/dev/null         # primary region with the exact fp32 scan (SURVEY 8(d)'s match)
-python bench.py --faces 1 --no-cpu-baseline > "$OUT/${TAG}_bench_k1.json" 2>/dev/null
-FRT_BENCH_FORCE_DIST=1 python bench.py --no-cpu-baseline 2>/dev/null | head -1 > "$OUT/${TAG}_bench_rccl_1rank.json"
-FRT_BENCH_FORCE_DIST=1 python bench.py --sharded-gallery --batch 64 --gallery 1250000 --no-cpu-baseline 2>/dev/null | head -1 > "$OUT/${TAG}_bench_sharded_1rank.json"
+python bench.py --full --faces 1 --no-cpu-baseline > "$OUT/${TAG}_bench_k1.json" 2>/dev/null
+FRT_BENCH_FORCE_DIST=1 python bench.py --full --no-cpu-baseline 2>/dev/null | head -1 > "$OUT/${TAG}_bench_rccl_1rank.json"
+FRT_BENCH_FORCE_DIST=1 python bench.py --full --sharded-gallery --batch 64 --gallery 1250000 --no-cpu-baseline 2>/dev/null | head -1 > "$OUT/${TAG}_bench_sharded_1rank.json"
 # 3b. the drop-in shells measured (src/app.cpp:304-310 through include/frt/*.h, 1 and 8 threads, N = 1M)
 python tools/dropin_bench.py --gallery 1000000 --threads 1 8 --iters 150 --out "$OUT/${TAG}_dropin_bench.json" > /dev/null 2>&1
 # 3b'. round 4: the same call sequence from 8 / 32 request threads on ONE detector + ONE recogniser with request coalescing (frt_coalescer_*)
@@ -75,8 +75,8 @@ for t in 8 32; do python tools/dropin_bench.py --gallery 1000000 --threads $t --
 python tools/dropin_bench.py --gallery 1000000 --threads 8 --iters 100 --shared --out "$OUT/${TAG}_dropin_shared_plain_t8.json" > /dev/null 2>&1
 # 3b''. round 4: one process / every visible device (tests/cpp/multi_device_pipeline.cpp); BASELINE configs[3] per-rank shape (4 frames per step)
 python tools/multi_device_bench.py --steps 100 --out "$OUT/${TAG}_multi_device.json" > /dev/null 2>&1
-python bench.py --batch 4 --no-cpu-baseline --steps 300 --resident > "$OUT/${TAG}_bench_b4_resident.json" 2>/dev/null
-python bench.py --batch 4 --no-cpu-baseline --steps 300 > "$OUT/${TAG}_bench_b4.json" 2>/dev/null
+python bench.py --full --batch 4 --no-cpu-baseline --steps 300 --resident > "$OUT/${TAG}_bench_b4_resident.json" 2>/dev/null
+python bench.py --full --batch 4 --no-cpu-baseline --steps 300 > "$OUT/${TAG}_bench_b4.json" 2>/dev/null
 # round 5: consecutive calls sharing a recogniser pass (frt_pipeline_set_pairing): pairs and groups of four, 4 frames per call and K = 1
 for g in 2 4; do python bench.py --batch 4 --no-cpu-baseline --steps 300 --no-extras --pair $g > "$OUT/${TAG}_bench_b4_pair$g.json" 2>/dev/null; done
 python bench.py --faces 1 --no-cpu-baseline --no-extras --pair 4 > "$OUT/${TAG}_bench_k1_pair4.json" 2>/dev/null

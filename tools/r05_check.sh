@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 cd "$ROOT"
 python -c "import __graft_entry__ as e; e.smoke()" 2>&1 | grep -v amdgpu.ids > "$OUT/${TAG}_smoke.txt"
 python -m pytest tests -m gpu -q 2>&1 | tail -4 > "$OUT/${TAG}_pytest_gpu.log"
-for i in 1 2; do python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/${TAG}_bench_driver_$i.json" 2>/dev/null; done
+for i in 1 2; do python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/${TAG}_bench_driver_$i.json" 2>/dev/null; done
 cd /tmp && export TMPDIR=/tmp
 for B in 32 4 1; do
   rm -rf /tmp/prof_det && mkdir -p /tmp/prof_det
