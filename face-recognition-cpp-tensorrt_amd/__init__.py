@@ -22,7 +22,7 @@ import numpy as np
 from . import dist, synth, weights_io  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("FRT_LIB") or os.path.join(_HERE, "libfrt.so")  # FRT_LIB: measurement builds (make TUNING=1), tools only
+LIB_PATH = os.environ.get("FRT_LIB") or os.path.join(_HERE, "libfrt.so")  # FRT_LIB: another build of the library (A/B runs: bench.py --ab-old-lib), tools only
 
 if not os.path.exists(LIB_PATH):
     raise ImportError("libfrt.so not built: run `python -c 'import __graft_entry__ as g; g.build()'` "

@@ -40,7 +40,7 @@ typedef std::chrono::steady_clock Clock;
 struct frt_coalescer {
     static constexpr int kBatches = 4;   // staging sets (the pipeline itself holds up to 4 batches in flight)
     static constexpr size_t kCropBytes = 112 * 112 * 3;
-    int kInflight = 3;  // batches queued on the pipeline before the dispatcher lets the open one grow (FRT_COALESCE_INFLIGHT: 1 .. 3; measured at 8 / 32 threads: 1 -> 10.2 / 19.6 k faces/s, 2 -> 12.9 / 25.8 k, 3 -> 13.9 / 27.9 k)
+    static constexpr int kInflight = 3;  // batches queued on the pipeline before the dispatcher lets the open one grow (measured at 8 / 32 threads: 1 -> 10.2 / 19.6 k faces/s, 2 -> 12.9 / 25.8 k, 3 -> 13.9 / 27.9 k)
     enum State { FREE, OPEN, CLOSED, DONE };
     struct Batch {
         uint8_t *h_frames = nullptr;
@@ -178,9 +178,6 @@ int frt_coalescer_create(frt_detector *d, frt_embedder *e, frt_matcher *m, int m
         c->max_faces = mf;
         c->fbytes = (size_t)fw * fh * 3;
         c->window_us = window_us;
-#ifdef FRT_TUNING  // (measurement builds only: batches in flight behind the coalescer)
-        if (const char *e = getenv("FRT_COALESCE_INFLIGHT")) c->kInflight = std::max(1, std::min(3, atoi(e)));
-#endif
         auto cleanup = [&] {
             for (auto &b : c->batch) {
                 frt_pinned_free(b.h_frames);

@@ -667,38 +667,6 @@ void frt_detector::forward_frames(const uint8_t *frames_dev, int n, size_t row_s
         Conv3Args c = ops[0].c3[0];
         c.B = n;
         if (ops.size() >= 3 && ops[1].type == 0 && ops[2].type == 0) {  // first conv + the first two conv_dw blocks in one kernel
-#ifdef FRT_TUNING
-            if (frt_tuning_env("FRT_DET_STEM_CHECK")) {  // debugging aid: the three layers one by one against the fused kernel, element for element
-                const size_t cnt = (size_t)n * ops[2].dw.Cout * ops[2].dw.Ho * ops[2].dw.Wo;
-                std::vector<float> ref(cnt), got(cnt);
-                (void)launch_det_conv1_u8(frames_dev, row_stride, frame_stride, c, s);
-                ops[1].dw.B = n; ops[2].dw.B = n;
-                launch_dwpw(ops[1].dw, s);
-                launch_dwpw(ops[2].dw, s);
-                HIPCHK(hipStreamSynchronize(s));
-                HIPCHK(hipMemcpy(ref.data(), ops[2].dw.out, cnt * 4, hipMemcpyDeviceToHost));
-                HIPCHK(hipMemset(ops[2].dw.out, 0xff, cnt * 4));
-                const bool ran = launch_det_stem(frames_dev, row_stride, frame_stride, c, ops[1].dw, ops[2].dw, s);
-                HIPCHK(hipStreamSynchronize(s));
-                HIPCHK(hipMemcpy(got.data(), ops[2].dw.out, cnt * 4, hipMemcpyDeviceToHost));
-                size_t bad = 0, first = cnt;
-                double maxd = 0;
-                for (size_t i = 0; i < cnt; ++i) {
-                    const double d = std::fabs((double)ref[i] - (double)got[i]);
-                    if (!(d == 0)) { if (first == cnt) first = i; ++bad; }
-                    if (d > maxd || d != d) maxd = d;
-                }
-                const int hw = ops[2].dw.Ho * ops[2].dw.Wo;
-                fprintf(stderr, "[stem check] ran %d, %zu of %zu differ, max |d| %g", (int)ran, bad, cnt, maxd);
-                if (first < cnt) fprintf(stderr, "; first at b=%zu c=%zu y=%zu x=%zu: got %g want %g", first / ((size_t)32 * hw), (first / hw) % 32, (first % hw) / ops[2].dw.Wo, first % ops[2].dw.Wo, got[first], ref[first]);
-                fprintf(stderr, "\n");
-                size_t by_c[32] = {0};
-                for (size_t i = 0; i < cnt; ++i) if (ref[i] != got[i]) ++by_c[(i / hw) % 32];
-                fprintf(stderr, "[stem check] differing by channel:");
-                for (int k = 0; k < 32; ++k) fprintf(stderr, " %zu", by_c[k]);
-                fprintf(stderr, "\n");
-            }
-#endif
             bool stem;
             {
                 ProfScope ps(2, "det_stem", (double)n * g.frame_h * g.frame_w * 3, s);
@@ -727,7 +695,7 @@ void frt_detector::forward(int n, hipStream_t s, int first_op) {
         }
         if (o.type == 3) {
             for (int k = 0; k < o.n; ++k) o.c3[k].B = n;
-            if (det_mfma_enabled() && (launch_conv3x3_split(o.c3, o.n, s) || launch_conv3x3_mfma(o.c3, o.n, s))) skip = 2;  // else: the two separate convs
+            if (launch_conv3x3_split(o.c3, o.n, s) || launch_conv3x3_mfma(o.c3, o.n, s)) skip = 2;  // else: the two separate convs
             continue;
         }
         if (o.type == 0) {

@@ -56,7 +56,6 @@ std::vector<float> vec_of(const frt::Blob &b, const std::string &name, size_t n)
 
 void frt_embedder::build(const frt::Blob &b) {
     std::vector<float> sc, bi;
-    const bool condition = !(frt_tuning_env("FRT_ARC_CONDITION") && frt_tuning_env("FRT_ARC_CONDITION")[0] == '0');  // (tuning build: the sweep's "off" leg)
     // Residual-stream conditioning of the deep IR backbones.  The fp16 stream (Y / Z / SC) adds one branch per unit: on the same
     // kind of weights IR-100 / IR-152 peak 11 / 16 times higher than IR-50 (545 / 783 vs 48), so a stream scale IR-50 holds (1e3) overflows
     // them.  Where the stream BatchNorms' running statistics say the stream is large (sigma >= 2^6), such a blob runs with the stream scaled by
@@ -66,7 +65,7 @@ void frt_embedder::build(const frt::Blob &b) {
     // every factor is a power of two, exact in binary floating point.  IR-50 (24 units) and the IR-SE family (its gates damp the branches:
     // peaks 5 / 9 / 11) are never touched.
     stream_scale = 1.0f;
-    if (condition && !se && layout.units.size() > 24) {
+    if (!se && layout.units.size() > 24) {
         double var = 0.0;
         for (size_t i = 0; i <= layout.units.size(); ++i) {
             const std::string p = i < layout.units.size() ? "body." + std::to_string(i) + ".res_layer.0" : std::string("output_layer.0");
@@ -123,35 +122,33 @@ void frt_embedder::build(const frt::Blob &b) {
             std::vector<float> w1v = vec_of(b, p + ".res_layer.1.weight", (size_t)a.depth * a.cin * 9);
             std::vector<float> w2v = vec_of(b, p + ".res_layer.3.weight", (size_t)a.depth * a.depth * 9);
             std::vector<float> dinv(a.depth, 1.f);
-            if (condition) {
-                auto pow2_inv = [](double v) {  // 2^-round(log2 v), clamped; 1 for zero / non-finite rows
-                    if (!(v > 0.0) || !std::isfinite(v)) return 1.0;
-                    const double e = std::max(-60.0, std::min(60.0, -std::nearbyint(std::log2(v))));
-                    return std::exp2(e);
-                };
-                for (int j = 0; j < a.depth; ++j) {
-                    double n2 = 0.0;
-                    float *row = &w1v[(size_t)j * a.cin * 9];
-                    for (int i = 0; i < a.cin * 9; ++i) n2 += (double)row[i] * row[i];
-                    const double c = pow2_inv(std::sqrt(n2));
-                    if (c == 1.0) continue;
-                    for (int i = 0; i < a.cin * 9; ++i) row[i] = (float)(row[i] * c);
-                    for (int k = 0; k < a.depth; ++k)
-                        for (int t = 0; t < 9; ++t) {
-                            float &v = w2v[((size_t)k * a.depth + j) * 9 + t];
-                            v = (float)(v / c);
-                        }
-                }
-                for (int k = 0; k < a.depth; ++k) {
-                    double mx = 0.0;
-                    float *row = &w2v[(size_t)k * a.depth * 9];
-                    for (int i = 0; i < a.depth * 9; ++i) mx = std::max(mx, (double)std::fabs(row[i]));
-                    double d = 1.0;
-                    if (mx > 0.0 && std::isfinite(mx) && (mx >= 2.0 || mx < 0.03125)) d = std::exp2(std::max(-60.0, std::min(60.0, -std::ceil(std::log2(mx)))));
-                    if (d == 1.0) continue;   // (entries already inside [2^-5, 2): nothing to gain, keep the trained numbers as they are)
-                    for (int i = 0; i < a.depth * 9; ++i) row[i] = (float)(row[i] * d);
-                    dinv[k] = (float)(1.0 / d);
-                }
+            auto pow2_inv = [](double v) {  // 2^-round(log2 v), clamped; 1 for zero / non-finite rows
+                if (!(v > 0.0) || !std::isfinite(v)) return 1.0;
+                const double e = std::max(-60.0, std::min(60.0, -std::nearbyint(std::log2(v))));
+                return std::exp2(e);
+            };
+            for (int j = 0; j < a.depth; ++j) {
+                double n2 = 0.0;
+                float *row = &w1v[(size_t)j * a.cin * 9];
+                for (int i = 0; i < a.cin * 9; ++i) n2 += (double)row[i] * row[i];
+                const double c = pow2_inv(std::sqrt(n2));
+                if (c == 1.0) continue;
+                for (int i = 0; i < a.cin * 9; ++i) row[i] = (float)(row[i] * c);
+                for (int k = 0; k < a.depth; ++k)
+                    for (int t = 0; t < 9; ++t) {
+                        float &v = w2v[((size_t)k * a.depth + j) * 9 + t];
+                        v = (float)(v / c);
+                    }
+            }
+            for (int k = 0; k < a.depth; ++k) {
+                double mx = 0.0;
+                float *row = &w2v[(size_t)k * a.depth * 9];
+                for (int i = 0; i < a.depth * 9; ++i) mx = std::max(mx, (double)std::fabs(row[i]));
+                double d = 1.0;
+                if (mx > 0.0 && std::isfinite(mx) && (mx >= 2.0 || mx < 0.03125)) d = std::exp2(std::max(-60.0, std::min(60.0, -std::ceil(std::log2(mx)))));
+                if (d == 1.0) continue;   // (entries already inside [2^-5, 2): nothing to gain, keep the trained numbers as they are)
+                for (int i = 0; i < a.depth * 9; ++i) row[i] = (float)(row[i] * d);
+                dinv[k] = (float)(1.0 / d);
             }
             a.w1 = reinterpret_cast<half_t *>(arena.upload(conv_w_f16(w1v.data(), a.depth, a.cin, 3)));
             {  // conv1 is always stride 1; conv2 only in the units that keep the resolution
@@ -211,10 +208,6 @@ void frt_embedder::build(const frt::Blob &b) {
         bn_b = arena.upload(bi);
         flops_per_face += 2.0 * 25088 * 512;
     }
-    {
-        const char *sf = frt_tuning_env("FRT_SC_FUSED");
-        sc_fusion = !(sf && sf[0] == '0');
-    }
     const size_t F = (size_t)max_batch;
     const size_t big = F * 112 * 112 * 64;
     d_in = arena.alloc<float>(F * 3 * 112 * 112);
@@ -232,8 +225,6 @@ void frt_embedder::build(const frt::Blob &b) {
         HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h_se_error), sizeof(int), hipHostMallocMapped));
         *h_se_error = 0;
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&d_se_error), h_se_error, 0));
-        const char *sf = frt_tuning_env("FRT_SE_FUSED");  // (tuning build; the product's switch is frt_embedder_set_se_fused)
-        se_fused = !(sf && sf[0] == '0');
     }
     fc_partial = arena.alloc<float>((size_t)FC_SPLITS * F * 512);
     d_out = arena.alloc<float>(F * 512);
@@ -416,7 +407,7 @@ void frt_embedder::forward(const float *chw_dev, int F, const int *valid_dev, fl
         // IR-50: the stride-2 strip kernel computes the 1x1 stride-2 shortcut conv itself (its input pixels are the (even, even) phase
         // plane) - no launch, no shortcut tensor.  IR-SE keeps the tensor: the gate multiplies the residual branch only.
         bool sc_fused = false;
-        if (u.wsc && u.wscf && !se && u.stride == 2 && sc_fusion) {
+        if (u.wsc && u.wscf && !se && u.stride == 2) {
             ConvMfmaArgs t{};
             t.x = T; t.w = u.w2; t.wf2 = u.w2f2;
             t.B = F; t.H = h; t.W = h; t.Cin = u.depth; t.Ho = ho; t.Wo = ho; t.Cout = u.depth; t.ks = 3; t.stride = 2; t.pad = 1;

@@ -40,9 +40,8 @@ struct frt_embedder {
     half_t *Y[2], *Z[2], *T, *SC, *RES = nullptr, *zeros = nullptr;
     float *fc_partial, *d_out, *se_pool = nullptr, *se_gate = nullptr;
     int se_epoch = 0;  // launch counter of the fused SE tails (their gate-ready flags carry the launch number)
-    bool sc_fusion = true;       // IR-50: 1x1 stride-2 shortcut convs inside the stride-2 strip kernel (tuning build: FRT_SC_FUSED=0 restores the launches)
-    bool se_fused = true;        // IR-SE: run the SE tail inside conv2's epilogue where the strip kernels allow it (FRT_SE_FUSED=0 /
-                                 // frt_embedder_set_se_fused(e, 0): always the stand-alone pool + gate + apply launches)
+    bool se_fused = true;        // IR-SE: run the SE tail inside conv2's epilogue where the strip kernels allow it
+                                 // (frt_embedder_set_se_fused(e, 0): always the stand-alone pool + gate + apply launches)
     int *h_se_error = nullptr;   // error word of the fused tail's cross-workgroup hand-over (pinned, mapped; 0 = fine)
     int *d_se_error = nullptr;   // ... its device address
     void check_se_error() {      // after a host synchronisation: a timed-out hand-over must not pass as a result

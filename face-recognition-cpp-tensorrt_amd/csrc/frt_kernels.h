@@ -11,16 +11,6 @@ typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
 
-// A/B switches of the kernels (environment variables, read once per process).  They exist for measurements
-// and are compiled in only with `make TUNING=1` (-DFRT_TUNING -DFRT_ABLATE); the default library ignores them and contains none
-// of the timing-ablation kernel variants (which produce wrong results by design).
-#ifdef FRT_TUNING
-#include <stdlib.h>
-inline const char *frt_tuning_env(const char *name) { return getenv(name); }
-#else
-inline const char *frt_tuning_env(const char *) { return nullptr; }
-#endif
-
 // One-time per-DEVICE setup of a kernel (hipFuncSetAttribute for > 64 KB of dynamic LDS is per device, not per process).
 constexpr int FRT_MAX_DEVICES = 32;
 inline bool frt_first_use_on_device(bool (&done)[FRT_MAX_DEVICES]) {
@@ -170,7 +160,6 @@ struct Conv3Args {
     float *out2;               // channels >= split go to out2 (channel co - split of a [B][out2_ctotal][Ho][Wo] tensor, + out2_coff)
     int split, out2_ctotal, out2_coff;
 };
-bool det_mfma_enabled();       // env FRT_DET_MFMA=0 switches the detector back to the scalar kernels (A/B measurements)
 void launch_conv3x3(const Conv3Args &a, hipStream_t s);
 // the detector's first three layers in one kernel (kernels_det_stem.hip); false: not applicable, run them one by one
 size_t det_stem_weight_floats();

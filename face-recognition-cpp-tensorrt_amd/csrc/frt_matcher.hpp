@@ -177,16 +177,14 @@ struct frt_matcher {
         if (old32) (void)hipFree(old32);  // (hipFree waits for the device: stages of earlier pipeline calls have finished with it)
         if (old16) (void)hipFree(old16);
         blocks = match_top1_blocks(N, 0);
-        const char *scr_env = frt_tuning_env("FRT_MATCH_SCREEN");  // (tuning build only; the product's switch is frt_matcher_set_screening)
-        screen = N >= 32768 && match_screen_supported(D) && !(scr_env && scr_env[0] == '0');
+        screen = N >= 32768 && match_screen_supported(D);
         gmax_norm = 0.f;
         if (N > 0 && (screen || store16)) {  // fp16 shadow copy (fp32 storage) + the largest row norm (rounding bound of the screening pass)
             int *d_bits = nullptr;
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_bits), sizeof(int)));
             // fp32-stored galleries of 512 columns are screened through an INT8 shadow (half the bytes of the per-call scan; kernels_match.hip);
-            // FRT_MATCH_I8=0 / FRT_MATCH_FAST=0 keep the fp16 shadow (A/B measurements, the round-2 tile-list path)
-            const char *i8_env = frt_tuning_env("FRT_MATCH_I8"), *fast_env = frt_tuning_env("FRT_MATCH_FAST");
-            const bool use_i8 = screen && !store16 && D == 512 && !(i8_env && i8_env[0] == '0') && !(fast_env && fast_env[0] == '0');
+            // other widths through an fp16 shadow
+            const bool use_i8 = screen && !store16 && D == 512;
             int *d_ebits = nullptr;
             if (store16) {
                 launch_gallery_norm16(d_g16, N, D, d_bits, stream);
@@ -244,15 +242,12 @@ struct frt_matcher {
             scr.count = scr.tile_flags + tiles;                                                           // one contiguous range to clear per call
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.tile_list), tiles * sizeof(int)));
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.segmax), (size_t)cap * 16 * sizeof(float)));
-            const char *fe = frt_tuning_env("FRT_MATCH_FAST");  // "0": the round-2 tile-list re-rank (diagnostics, tuning build)
-            if (!(fe && fe[0] == '0')) {
-                scr.pair_cap = std::max(cap * 64, 8192);  // (a multiple of the 64 sub-lists)
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.wgmax), (size_t)256 * cap * sizeof(float)));
-                HIPCHK(hipMalloc(&scr.pairs, (size_t)scr.pair_cap * 8));
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.ctl), FRT_MATCH_CTL_WORDS * sizeof(int)));
-                HIPCHK(hipMemset(scr.ctl, 0, FRT_MATCH_CTL_WORDS * sizeof(int)));
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.qkey), (size_t)cap * sizeof(unsigned long long)));
-            }
+            scr.pair_cap = std::max(cap * 64, 8192);  // (a multiple of the 64 sub-lists)
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.wgmax), (size_t)256 * cap * sizeof(float)));
+            HIPCHK(hipMalloc(&scr.pairs, (size_t)scr.pair_cap * 8));
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.ctl), FRT_MATCH_CTL_WORDS * sizeof(int)));
+            HIPCHK(hipMemset(scr.ctl, 0, FRT_MATCH_CTL_WORDS * sizeof(int)));
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.qkey), (size_t)cap * sizeof(unsigned long long)));
         }
         q_cap = cap;
     }

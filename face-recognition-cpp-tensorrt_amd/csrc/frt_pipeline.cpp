@@ -23,38 +23,21 @@ int frt_pipeline_create(frt_detector *d, frt_embedder *e, frt_matcher *m, int ma
         p->stream = nullptr;
         // the stage streams are created at the highest stream priority: ROCm keeps a separate hardware-queue pool per priority, so they
         // never share a queue with the caller's (normal priority) stream, whose queue holds the pending joins of the batches in flight
-        // (the FRT_PIPELINE_* switches below are A/B switches of measurement builds - frt_tuning_env is getenv under make TUNING=1 and nullptr in
-        //  the product; the product's switches are frt_pipeline_set_overlap / _set_graph / _check_overlap)
+        // (run-time switches: frt_pipeline_set_overlap / _set_graph / _check_overlap)
         int prio_lo = 0, prio_hi = 0;
         HIPCHK(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        {
-            const char *pe = frt_tuning_env("FRT_PIPELINE_STREAM_PRIO");
-            if (pe && pe[0] == '0') prio_hi = 0;   // "0": normal priority (stage streams share the caller's queue pool)
-        }
         // hipStreamDefault (blocking), not hipStreamNonBlocking: a gallery reload between calls (hipFree / hipMalloc / synchronous
         // hipMemcpy on the legacy default stream) is then ordered against the stages still in flight without the caller
         // synchronising anything (tests/test_gpu_pipeline.py::test_gallery_reload_between_pipelined_calls); non-blocking
         // streams also measured 1 % slower
         p->copy_prio = prio_hi;
         auto mk = [&](hipStream_t *st) { HIPCHK(hipStreamCreateWithPriority(st, hipStreamDefault, prio_hi)); };
-        {
-            // FRT_PIPELINE_DET_PRIO=lo / normal: the detector's stream below the recogniser's (A/B: does the hardware then give the recogniser -
-            // the longer stage - the CUs first and let the detector fill its gaps?)
-            const char *dp = frt_tuning_env("FRT_PIPELINE_DET_PRIO");
-            if (dp && dp[0] == 'l') HIPCHK(hipStreamCreateWithPriority(&p->det_stream, hipStreamDefault, prio_lo));
-            else if (dp && dp[0] == 'n') HIPCHK(hipStreamCreateWithPriority(&p->det_stream, hipStreamDefault, 0));
-            else mk(&p->det_stream);
-        }
+        mk(&p->det_stream);
         mk(&p->emb_stream);
         mk(&p->emb_stream2);
-        {
-            const char *de = frt_tuning_env("FRT_PIPELINE_DUAL_EMBED");
-            p->dual_embed = !(de && de[0] == '0');
-        }
-        if (p->dual_embed) {
-            e->ensure_alt();
-            p->d_chw2 = p->arena.alloc<float>((size_t)max_frames * d->g.max_faces * 3 * 112 * 112);
-        }
+        // recogniser passes of consecutive calls run on two streams with two activation sets
+        e->ensure_alt();
+        p->d_chw2 = p->arena.alloc<float>((size_t)max_frames * d->g.max_faces * 3 * 112 * 112);
         const size_t F = (size_t)p->F_cap;
         HIPCHK(hipEventCreateWithFlags(&p->ev_serial, hipEventDisableTiming));
         for (int i = 0; i < frt_pipeline::NSLOT; ++i) {
@@ -67,20 +50,11 @@ int frt_pipeline_create(frt_detector *d, frt_embedder *e, frt_matcher *m, int ma
             p->slot_nout[i] = p->arena.alloc<int>((size_t)max_frames);
             if (d->has_landmarks) p->slot_landmarks[i] = p->arena.alloc<float>(F * 10);
         }
-        {
-            const char *e = frt_tuning_env("FRT_PIPELINE_OVERLAP");
-            p->overlap = !(e && e[0] == '0');
-            const char *gph = frt_tuning_env("FRT_PIPELINE_GRAPH");
-            p->use_graphs = gph && gph[0] == '1';  // opt-in: measured no gain on this workload (see the note at run_part)
-        }
         HIPCHK(hipEventCreateWithFlags(&p->ev_input, hipEventDisableTiming));
         p->d_chw = p->arena.alloc<float>(F * 3 * 112 * 112);
         p->d_sim = p->arena.alloc<float>(F);
         p->d_idx = p->arena.alloc<int32_t>(F);
-        if (p->overlap) {  // create-time self-check of the stage streams (~1 ms)
-            const char *sc = frt_tuning_env("FRT_PIPELINE_SELFCHECK");
-            if (!(sc && sc[0] == '0')) p->self_check(false);
-        }
+        p->self_check(false);  // create-time self-check of the stage streams (~1 ms)
         *out = p.release();
     });
 }

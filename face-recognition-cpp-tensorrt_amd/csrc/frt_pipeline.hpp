@@ -15,7 +15,6 @@ struct frt_pipeline {
     // the other set's pass) - three stages with different bottlenecks (latency / MFMA+LDS / HBM) that overlap on the same CUs.  `stream` (the caller's) only joins.  Fork/join with events; boxes, embeddings and validity
     // flags of a call live in one of two slots so that a later stage of the previous call can still read them.
     hipStream_t det_stream = nullptr, emb_stream = nullptr, emb_stream2 = nullptr;
-    bool dual_embed = true;   // recogniser passes of consecutive calls on two streams with two activation sets (FRT_PIPELINE_DUAL_EMBED=0: one)
     float *d_chw2 = nullptr;
     hipEvent_t ev_serial = nullptr;  // end of the last serial (profiled) call while overlap is on
     bool serial_pending = false;
@@ -453,12 +452,6 @@ struct frt_pipeline {
         crops_req = nullptr;
         const int akey = (align ? 1 : 0) | (cur.crops ? 2 : 0);
         run_part(GraphKey{0, frames_dev, nullptr, nullptr, n, slot, akey, 0u}, ds, [&](hipStream_t st) {
-#ifdef FRT_TUNING
-            // timing build: FRT_PIPE_ABLATE bit 0 = no detector network after the first calls (post-processing re-reads the old head outputs),
-            // bit 1 = no recogniser network, bit 2 = no match: what each stage costs the pipelined step (profiles/r04/r04s_stage_ablation.txt)
-            static const int pipe_abl = getenv("FRT_PIPE_ABLATE") ? atoi(getenv("FRT_PIPE_ABLATE")) : 0;
-            if (!(pipe_abl & 1) || call < 8u)
-#endif
             det->forward_frames(frames_dev, n, (size_t)g.frame_w * 3, (size_t)g.frame_w * g.frame_h * 3, st);
             det->postprocess(n, st, slot_boxes[slot], slot_nout[slot], slot_landmarks[slot]);  // straight into this call's slot
         });
@@ -514,7 +507,7 @@ struct frt_pipeline {
             Ftot += Fc[i];
         }
         (nc >= 2 ? paired_passes : single_passes) += 1;
-        const int eset = (pipe3 && dual_embed && Ftot <= emb->max_batch) ? (int)(epass++ & 1u) : 0;  // activation set / stream of this recogniser pass
+        const int eset = (pipe3 && Ftot <= emb->max_batch) ? (int)(epass++ & 1u) : 0;  // activation set / stream of this recogniser pass
         hipStream_t es = pipe3 ? (eset ? emb_stream2 : emb_stream) : s;
         // match + pack follow the recogniser pass on ITS stream (they overlap the other set's pass and the next detector pass): a stream
         // of their own measured 0.6 % slower and is one more stream competing for the four hardware queues
@@ -546,10 +539,6 @@ struct frt_pipeline {
                 }
                 f_off += Fc[i];
             }
-#ifdef FRT_TUNING
-            static const int pipe_abl = getenv("FRT_PIPE_ABLATE") ? atoi(getenv("FRT_PIPE_ABLATE")) : 0;
-            if (!(pipe_abl & 2) || c[0].call < 8u)
-#endif
             for (int f0 = 0; f0 < Ftot; f0 += emb->max_batch) {
                 const int nf = std::min(emb->max_batch, Ftot - f0);
                 emb->forward_set(eset, chw + (size_t)f0 * 3 * 112 * 112, nf, valid + f0, emb_slot + (size_t)f0 * 512, st);
@@ -571,10 +560,6 @@ struct frt_pipeline {
         // (the serial branch too: an object-level frt_matcher_top1_dev / topk_dev on another stream shares d_partial / the pair lists with this stage)
         if (mat && mat->busy) HIPCHK(hipStreamWaitEvent(ms, mat->ev_busy, 0));
         auto stage_m = [&](hipStream_t st) {
-#ifdef FRT_TUNING
-            static const int pipe_abl = getenv("FRT_PIPE_ABLATE") ? atoi(getenv("FRT_PIPE_ABLATE")) : 0;
-            if (!(pipe_abl & 4) || c[0].call < 8u)
-#endif
             if (have_gallery) mat->top1_dev(emb_slot, Ftot, d_idx, d_sim, st);
             int f_off = 0;
             for (int i = 0; i < nc; ++i) {

@@ -8,8 +8,7 @@
 // run as an implicit GEMM on v_mfma_f32_32x32x16_f16 (M = Cout, N = B*Ho*Wo pixels, K = 9*Cin), never materialising im2col.
 //   * workgroup = 4 waves; tile = (WCO*64 couts) x (WPX*64 pixels); each wave owns a 64x64 sub-tile = 2x2 MFMA tiles;
 //   * K is walked tap-major in steps of 64 input channels (Cin % 64 == 0, so a step never straddles a tap);
-//   * both operand tiles are staged through LDS with coalesced 16-byte global loads (8 lanes = one 128-byte row segment),
-//     double-buffered with a register prefetch of step t+1 issued before the MFMAs of step t; zero padding is applied at
+//   * both operand tiles are staged through LDS (v2 below; the register-staged v1 kernel is gone); zero padding is applied at
 //     load time (out-of-image taps load zeros), which is what makes the leading BatchNorm un-foldable (see below);
 //   * LDS rows are 128 B; 16-byte chunks are XOR-swizzled with (row>>1)&7, conflict-free for ds_read_b128 lane groups;
 //   * the accumulator orientation is D[cout][pixel] (weights are the MFMA A operand): a lane then owns 4 consecutive output
@@ -28,191 +27,14 @@
 #include "frt_kernels.h"
 #include "frt_se_device.h"
 
-#include <stdlib.h>
-
 #include <type_traits>
 
 namespace {
 
 __device__ __forceinline__ int swz(int row, int chunk) { return chunk ^ ((row >> 1) & 7); }
 
-template <int WCO, int WPX>
-__global__ __launch_bounds__(256) void conv_mfma_kernel(ConvMfmaArgs p) {
-    constexpr int BCO = WCO * 64, BPX = WPX * 64;
-    constexpr int CO_CH = BCO * 8 / 256;  // 16-byte chunks per thread, weight tile
-    constexpr int PX_CH = BPX * 8 / 256;  // 16-byte chunks per thread, pixel tile
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    half_t *Ws = reinterpret_cast<half_t *>(smem);                  // [2][BCO][64]
-    half_t *Xs = reinterpret_cast<half_t *>(smem) + 2 * BCO * 64;   // [2][BPX][64]
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int r = lane & 31, hi = lane >> 5;
-    const int wco = wave / WPX, wpx = wave % WPX;
-
-    const int M = p.B * p.Ho * p.Wo;
-    const int n_co_tiles = p.Cout / BCO;
-    const int co_tile = blockIdx.x % n_co_tiles, px_tile = blockIdx.x / n_co_tiles;
-    const int co_base = co_tile * BCO, px_base = px_tile * BPX;
-
-    const int cin_steps = p.Cin >> 6;
-    const int ksteps = p.ks * p.ks * cin_steps;
-    const int per_split = (ksteps + p.splits - 1) / p.splits;
-    const int t_begin = blockIdx.z * per_split;
-    const int t_end = min(ksteps, t_begin + per_split);
-    const long Ktot = (long)p.ks * p.ks * p.Cin;
-
-    const int ld_row = tid >> 3, ld_ch = tid & 7;
-
-    // per-thread im2col row descriptors
-    int xb[PX_CH], xih0[PX_CH], xiw0[PX_CH];
-#pragma unroll
-    for (int i = 0; i < PX_CH; ++i) {
-        const int m = px_base + ld_row + 32 * i;
-        if (m < M) {
-            const int b = m / (p.Ho * p.Wo);
-            const int rem = m - b * (p.Ho * p.Wo);
-            const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
-            xb[i] = b * p.H * p.W;
-            xih0[i] = oh * p.stride - p.pad;
-            xiw0[i] = ow * p.stride - p.pad;
-        } else {
-            xb[i] = -1;
-            xih0[i] = 0;
-            xiw0[i] = 0;
-        }
-    }
-
-    half8 wreg[CO_CH], xreg[PX_CH];
-    auto load_global = [&](int t) {
-        const int tap = t / cin_steps;
-        const int c0 = (t - tap * cin_steps) << 6;
-        const int kh = tap / p.ks, kw = tap - kh * p.ks;
-#pragma unroll
-        for (int i = 0; i < CO_CH; ++i) {
-            const int co = co_base + ld_row + 32 * i;
-            wreg[i] = *reinterpret_cast<const half8 *>(p.w + (long)co * Ktot + (long)tap * p.Cin + c0 + ld_ch * 8);
-        }
-#pragma unroll
-        for (int i = 0; i < PX_CH; ++i) {
-            const int ih = xih0[i] + kh, iw = xiw0[i] + kw;
-            const bool ok = xb[i] >= 0 && ih >= 0 && ih < p.H && iw >= 0 && iw < p.W;
-            half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-            if (ok) v = *reinterpret_cast<const half8 *>(p.x + ((long)(xb[i] + ih * p.W + iw)) * p.Cin + c0 + ld_ch * 8);
-            xreg[i] = v;
-        }
-    };
-    auto store_lds = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < CO_CH; ++i) {
-            const int row = ld_row + 32 * i;
-            *reinterpret_cast<half8 *>(Ws + buf * BCO * 64 + row * 64 + swz(row, ld_ch) * 8) = wreg[i];
-        }
-#pragma unroll
-        for (int i = 0; i < PX_CH; ++i) {
-            const int row = ld_row + 32 * i;
-            *reinterpret_cast<half8 *>(Xs + buf * BPX * 64 + row * 64 + swz(row, ld_ch) * 8) = xreg[i];
-        }
-    };
-
-    floatx16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-
-    if (t_begin < t_end) {
-        load_global(t_begin);
-        store_lds(0);
-    }
-    __syncthreads();
-    int cur = 0;
-    for (int t = t_begin; t < t_end; ++t) {
-        if (t + 1 < t_end) load_global(t + 1);
-        const half_t *Wb = Ws + cur * BCO * 64;
-        const half_t *Xb = Xs + cur * BPX * 64;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int ch = kk * 2 + hi;
-            half8 af[2], bf[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int row = wco * 64 + i * 32 + r;
-                af[i] = *reinterpret_cast<const half8 *>(Wb + row * 64 + swz(row, ch) * 8);
-            }
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                const int row = wpx * 64 + j * 32 + r;
-                bf[j] = *reinterpret_cast<const half8 *>(Xb + row * 64 + swz(row, ch) * 8);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
-        }
-        if (t + 1 < t_end) store_lds(cur ^ 1);
-        __syncthreads();
-        cur ^= 1;
-    }
-
-    // ------------------------------------------------------------------ epilogue
-    // acc[i][j][e]: cout = co_base + wco*64 + i*32 + (e&3) + 8*(e>>2) + 4*hi ; pixel = px_base + wpx*64 + j*32 + r
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        const int m = px_base + wpx * 64 + j * 32 + r;
-        if (m >= M) continue;
-        long sc_off = 0;
-        if (p.mode == EPI_BN_ADD_BN) {
-            if (p.sc_stride == 1 && p.sc_h == p.Ho && p.sc_w == p.Wo) {
-                sc_off = (long)m * p.Cout;
-            } else {
-                const int b = m / (p.Ho * p.Wo);
-                const int rem = m - b * (p.Ho * p.Wo);
-                const int oh = rem / p.Wo, ow = rem - oh * p.Wo;
-                sc_off = ((long)(b * p.sc_h + oh * p.sc_stride) * p.sc_w + ow * p.sc_stride) * p.Cout;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c = co_base + wco * 64 + i * 32 + 8 * g + 4 * hi;
-                floatx4 v = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-                if (p.mode == EPI_PARTIAL) {
-                    *reinterpret_cast<floatx4 *>(p.outf + ((long)blockIdx.z * M + m) * p.Cout + c) = v;
-                    continue;
-                }
-                const floatx4 a0 = *reinterpret_cast<const floatx4 *>(p.p0 + c);
-                if (p.mode == EPI_PRELU) {
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * a0[e];
-                } else {
-                    const floatx4 a1 = *reinterpret_cast<const floatx4 *>(p.p1 + c);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] = v[e] * a0[e] + a1[e];
-                }
-                if (p.mode == EPI_BN_ADD_BN) {
-                    const half4 s4 = *reinterpret_cast<const half4 *>(p.sc + sc_off + c);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) v[e] += (float)s4[e];
-                }
-                half4 o = {(half_t)v[0], (half_t)v[1], (half_t)v[2], (half_t)v[3]};
-                *reinterpret_cast<half4 *>(p.out0 + (long)m * p.Cout + c) = o;
-                if (p.mode == EPI_BN_ADD_BN && p.out1) {
-                    const floatx4 a2 = *reinterpret_cast<const floatx4 *>(p.p2 + c);
-                    const floatx4 a3 = *reinterpret_cast<const floatx4 *>(p.p3 + c);
-                    half4 z = {(half_t)(v[0] * a2[0] + a3[0]), (half_t)(v[1] * a2[1] + a3[1]), (half_t)(v[2] * a2[2] + a3[2]),
-                               (half_t)(v[3] * a2[3] + a3[3])};
-                    *reinterpret_cast<half4 *>(p.out1 + (long)m * p.Cout + c) = z;
-                }
-            }
-        }
-    }
-}
-
 // ---------------------------------------------------------------- v2: direct global->LDS staging (LDS-DMA), N-stage ring
-// Same tiling/arithmetic as conv_mfma_kernel above, restructured around what the v1 profile showed (30 % MFMA duty):
+// Same tiling/arithmetic as the first, register-staged kernel (v1, since removed), restructured around what its profile showed (30 % MFMA duty):
 //   * both operand tiles go HBM/L2 -> LDS with global_load_lds_dwordx4 (no VGPR round trip, no ds_write_b128 issue cost).
 //     The DMA writes wave-base + lane*16, so the LDS image is lane-linear; the XOR swizzle is applied to the per-lane SOURCE
 //     address (lane L of a row fetches chunk (L&7)^f(row)) and again on the ds_read side - the same involution on both sides.
@@ -222,7 +44,7 @@ __global__ __launch_bounds__(256) void conv_mfma_kernel(ConvMfmaArgs p) {
 //   * epilogue staged through LDS: the D[cout][pixel] accumulators are transposed to pixel rows, then every lane handles 8
 //     consecutive channels of a pixel -> 16-byte coalesced shortcut loads and output stores, parameters hoisted per lane.
 //   * XCD-aware tile order: consecutive logical tiles (which share the input pixels / the weights) land on the same XCD's L2.
-template <int WCO, int WPX, int NSTAGE, int ABL = 0>  // ABL: timing ablations only (1 = no DMA in the loop, 2 = no MFMA)
+template <int WCO, int WPX, int NSTAGE>
 __global__ __launch_bounds__(256) void conv_glds_kernel(ConvMfmaArgs p) {
     constexpr int BCO = WCO * 64, BPX = WPX * 64;
     constexpr int CO_CH = BCO * 8 / 256, PX_CH = BPX * 8 / 256;
@@ -334,7 +156,7 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(ConvMfmaArgs p) {
         else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if (ABL != 1 && t + NSTAGE - 1 < t_end) issue(t + NSTAGE - 1, (STAGE + NSTAGE - 1) % NSTAGE);  // buffer of tile t-1: all its readers are past the barrier
+        if (t + NSTAGE - 1 < t_end) issue(t + NSTAGE - 1, (STAGE + NSTAGE - 1) % NSTAGE);  // buffer of tile t-1: all its readers are past the barrier
         const char *sb = smem + STAGE * STAGE_HALFS * 2;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
@@ -347,13 +169,7 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(ConvMfmaArgs p) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    if (ABL == 2) {
-                        asm volatile("" ::"v"(af[i]), "v"(bf[j]));
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
-                    }
-                }
+                for (int j = 0; j < 2; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[i], bf[j], acc[i][j], 0, 0, 0);
         }
     };
     for (int t = t_begin; t < t_end; t += NSTAGE) {
@@ -431,7 +247,7 @@ __global__ __launch_bounds__(256) void conv_glds_kernel(ConvMfmaArgs p) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) o[e] = (half_t)v[e];
             *reinterpret_cast<half8 *>(p.out0 + (long)m * p.Cout + c) = o;
-            if (p.mode == EPI_BN_ADD_BN && p.out1 && ABL != 20) {  // 20 (measurement): what would dropping the BN'd copy save?
+            if (p.mode == EPI_BN_ADD_BN && p.out1) {
                 half8 z;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) z[e] = (half_t)(v[e] * q2[e >> 2][e & 3] + q3[e >> 2][e & 3]);
@@ -471,7 +287,7 @@ __device__ __forceinline__ void se_fc_gate(const float *sp, float *shid, const f
 // images (bottom halo of one, top halo of the next), NO halo columns (they would break the one-to-one slot -> patch-row walk): the taps
 // with kw = 0 / kw = 2 point the lanes whose pixel sits in the first / last image column at a zero pixel (patch pixel 0) instead - one
 // v_cndmask on the ADDRESS per (tap, tile), masks wave-uniform in scalar registers.  R carries the patch's row count, n_img / linear unused.
-template <int PPS, int PT, int NW, bool SINGLE, int ABL, bool PAIR, int NT, int BFD, int WR, bool SEP, bool CPT>  // SEP: SE pooling + gate in the epilogue (below); WR: weight register ring depth in steps (3 or 9); NT pixel tiles per strip; PPS patch DMA pieces per thread per step during taps 0..PT-1; BFD: depth (kk-slots) of the B fragment ring
+template <int PPS, int PT, int NW, bool SINGLE, bool PAIR, int NT, int BFD, int WR, bool SEP, bool CPT>  // SEP: SE pooling + gate in the epilogue (below); WR: weight register ring depth in steps (3 or 9); NT pixel tiles per strip; PPS patch DMA pieces per thread per step during taps 0..PT-1; BFD: depth (kk-slots) of the B fragment ring
 __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, int n_img, int linear) {
     // linear != 0: pixel slots are enumerated over the PADDED row width (slot == patch row of tap (0,0), slots in the two halo
     // columns are dead).  The 32 lanes of a fragment read then touch 32 consecutive patch rows -> no LDS bank conflicts; the
@@ -596,7 +412,7 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
     constexpr int LA = WR - 1;  // weight fragments are fetched LA steps ahead
     auto load_w = [&](int c, int tap, auto slot_c) {  // wave-uniform c, tap; clamped at the tail (values unused there)
         constexpr int S = decltype(slot_c)::value;
-        const int woff = (ABL == 13) ? 0 : (c < n_chunks ? (c * 9 + tap) * (4 * 512) : 0);  // 13: every step re-reads the same fragments (cache hits)
+        const int woff = c < n_chunks ? (c * 9 + tap) * (4 * 512) : 0;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) areg[S][kk] = *reinterpret_cast<const half8 *>(wfrag + woff + kk * 512);
     };
@@ -606,7 +422,7 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
         char *pl = patch + (SINGLE ? 0 : (c & 1) * PATCH_B) + (PAIR ? (wave & 1) : wave) * 1024;
 #pragma unroll
         for (int q = Q0; q < Q0 + NQ; ++q) {
-            const half_t *src = (ABL != 14 && real && poff[q] >= 0) ? p.x + (unsigned)(poff[q] + (c << 6)) : p.zeros;  // 14: all pieces from the zero buffer
+            const half_t *src = (real && poff[q] >= 0) ? p.x + (unsigned)(poff[q] + (c << 6)) : p.zeros;
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
                                              (__attribute__((address_space(3))) void *)(pl + q * (PAIR ? 2048 : 4096)), 16, 0, 0);
         }
@@ -675,23 +491,21 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
             }
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
-                if (ABL == 2) asm volatile("" ::"v"(areg[AS][kk]), "v"(bf[cur][j]));
-                else acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(areg[AS][kk], bf[cur][j], acc[j], 0, 0, 0);
-                if (ABL == 8 || ABL == 9) {
-                } else if (kk + BFD < 4) bf[cur][j] = frag(j, std::integral_constant<int, TAP>{}, pbuf, kk + BFD);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(areg[AS][kk], bf[cur][j], acc[j], 0, 0, 0);
+                if (kk + BFD < 4) bf[cur][j] = frag(j, std::integral_constant<int, TAP>{}, pbuf, kk + BFD);
                 else bf[cur][j] = frag(j, std::integral_constant<int, NTAP>{}, pbufn, kk + BFD - 4);
                 constexpr int JL = NT > 1 ? 1 : 0;  // pixel-tile slot that carries the loads of future steps
-                if (ABL != 1 && ABL != 7 && ABL != 9 && kk == 0 && j == JL) {  // weight fragments of step t+2 into the slot step t-1 used
+                if (kk == 0 && j == JL) {  // weight fragments of step t+2 into the slot step t-1 used
                     constexpr int T2 = TAP + LA;
                     load_w(T2 < 9 ? c : c + 1, T2 % 9, std::integral_constant<int, (T2 % 9) % WR>{});
                 }
-                if (ABL != 1 && ABL != 6 && ABL != 9 && kk == 1 && j == JL && !SINGLE && TAP < PT)
+                if (kk == 1 && j == JL && !SINGLE && TAP < PT)
                     issue_patch(c + 1, std::integral_constant<int, (TAP < PT ? TAP : 0) * PPS>{}, std::integral_constant<int, PPS>{});
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
     };
-    for (int c = 0; c < (ABL == 4 ? 0 : n_chunks); ++c) {
+    for (int c = 0; c < n_chunks; ++c) {
         step(c, std::integral_constant<int, 0>{});
         step(c, std::integral_constant<int, 1>{});
         step(c, std::integral_constant<int, 2>{});
@@ -704,12 +518,6 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tail's dummy DMAs still target LDS
     __syncthreads();
-    if (ABL == 5) {  // timing ablation: keep the accumulators alive, skip the epilogue
-        float sacc = 0.f;
-        for (int j = 0; j < NT; ++j) sacc += acc[j][0];
-        if (sacc == 123.456f) p.out0[0] = (half_t)sacc;
-        return;
-    }
 
     // ------------------------------------------------------------------ epilogue (per wave: 32 couts x 7 pixel tiles) through LDS
     constexpr int EROW = 36;  // floats per pixel row (32 + 4 pad)
@@ -809,15 +617,15 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
     }
 }
 
-template <int PPS, int PT, int NW, bool SINGLE, int ABL = 0, bool PAIR = false, int NT = 7, int BFD = 2, int WR = 3, bool SEP = false>
+template <int PPS, int PT, int NW, bool SINGLE, bool PAIR = false, int NT = 7, int BFD = 2, int WR = 3, bool SEP = false>
 __global__ __launch_bounds__(256, BFD == 1 ? 2 : 1) void conv_patch_kernel(ConvMfmaArgs p, int R, int n_img, int linear) {
-    conv_patch_body<PPS, PT, NW, SINGLE, ABL, PAIR, NT, BFD, WR, SEP, false>(p, R, n_img, linear);
+    conv_patch_body<PPS, PT, NW, SINGLE, PAIR, NT, BFD, WR, SEP, false>(p, R, n_img, linear);
 }
 
 // compact strips (see CPT above): NT pixel tiles = NT*32 consecutive pixels per strip; npr = rows of the stacked-image patch window
-template <int NT, int ABL = 0>
+template <int NT>
 __global__ __launch_bounds__(256, 2) void conv_patchc_kernel(ConvMfmaArgs p, int npr) {
-    conv_patch_body<10, 1, 5, false, ABL, false, NT, 1, 3, false, true>(p, npr, 1, 0);
+    conv_patch_body<10, 1, 5, false, false, NT, 1, 3, false, true>(p, npr, 1, 0);
 }
 
 // ---------------------------------------------------------------- input layer: conv3x3 3->64 + BN + PReLU (+ unit-0 leading BN)
@@ -989,34 +797,20 @@ __global__ __launch_bounds__(256) void se_apply_kernel(SeArgs a) {
     *reinterpret_cast<half8 *>(a.z + m * a.C + c) = z8;
 }
 
-template <int WCO, int WPX>
-void launch_conv_t(const ConvMfmaArgs &a, hipStream_t s) {
-    constexpr int BCO = WCO * 64, BPX = WPX * 64;
-    const size_t lds = (size_t)2 * (BCO + BPX) * 64 * sizeof(half_t);
-    static bool attr_done[FRT_MAX_DEVICES] = {};
-    if (frt_first_use_on_device(attr_done)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_mfma_kernel<WCO, WPX>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    const int M = a.B * a.Ho * a.Wo;
-    const int px_tiles = (M + BPX - 1) / BPX;
-    dim3 grid(px_tiles * (a.Cout / BCO), 1, a.splits);
-    hipLaunchKernelGGL((conv_mfma_kernel<WCO, WPX>), grid, dim3(256), lds, s, a);
-}
-
-template <int WCO, int WPX, int NSTAGE, int ABL = 0>
+template <int WCO, int WPX, int NSTAGE>
 void launch_glds_t(const ConvMfmaArgs &a, hipStream_t s) {
     constexpr int BCO = WCO * 64, BPX = WPX * 64;
     const size_t lds = (size_t)NSTAGE * (BCO + BPX) * 64 * sizeof(half_t);
     static_assert(NSTAGE * (BCO + BPX) * 64 * 2 >= 4 * 32 * 68 * 4, "ring must hold the epilogue transpose buffer");
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_glds_kernel<WCO, WPX, NSTAGE, ABL>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_glds_kernel<WCO, WPX, NSTAGE>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
     }
     const int M = a.B * a.Ho * a.Wo;
     const int px_tiles = (M + BPX - 1) / BPX;
     dim3 grid(px_tiles * (a.Cout / BCO), 1, a.splits);
-    hipLaunchKernelGGL((conv_glds_kernel<WCO, WPX, NSTAGE, ABL>), grid, dim3(256), lds, s, a);
+    hipLaunchKernelGGL((conv_glds_kernel<WCO, WPX, NSTAGE>), grid, dim3(256), lds, s, a);
 }
 
 // strip geometry for the patch kernel; returns false when the layer is not eligible.  nt = pixel tiles per strip (1, 2, 4 or 7: the
@@ -1033,7 +827,6 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
     if ((a.mode == EPI_BN_ADD_BN || a.mode == EPI_BN_SE) && !(a.sc_stride == 1 && a.sc_h == a.Ho && a.sc_w == a.Wo)) return false;
     single = a.Cin == 64;
     const int co_tiles = pair ? 1 : a.Cout / 128;
-    static const bool small_ok = !(frt_tuning_env("FRT_CONV_SMALL_BATCH") && frt_tuning_env("FRT_CONV_SMALL_BATCH")[0] == '0');
     constexpr int kWant = 224;  // workgroups that count as "fills the 256 CUs" (128 / 64 measured at 16 / 32 / 64 faces: 0.89 / 1.20 / 1.68 ms per pass become 0.89 / 1.28 / 1.87 and 1.10 / 1.56 / 1.88, profiles/r03/r03r_kwant.txt)
     auto tiles_for = [](int px) { return px <= 32 ? 1 : (px <= 64 ? 2 : (px <= 128 ? 4 : (px <= 224 ? 7 : 0))); };
     auto slots_of = [&](int r, int ni) { return (ni * (r + 2) * (a.W + 2) * 9 + 255) / 256; };
@@ -1049,12 +842,11 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
     if (a.H * a.W <= 56) {
         // whole small images per strip: 2 images (98 pixels, 4 tiles) put 7x7x512 at 64 strips x 4 cout tiles = 256 workgroups for 128
         // faces (4 images / 7 tiles would leave 128); below 128 faces one image per strip (2 tiles)
-        static const int small_nt = frt_tuning_env("FRT_CONV_SMALL_NT") ? atoi(frt_tuning_env("FRT_CONV_SMALL_NT")) : 4;
-        for (int ni : {(small_nt * 32) / (a.H * a.W), 1}) {
+        for (int ni : {128 / (a.H * a.W), 1}) {
             if (ni < 1) continue;
             const int t = tiles_for(ni * a.H * a.W);
             if (!t || !fits(a.H, ni, t)) continue;
-            if (!R || (small_ok && ((a.B + n_img - 1) / n_img) * co_tiles < kWant)) {
+            if (!R || ((a.B + n_img - 1) / n_img) * co_tiles < kWant) {
                 R = a.H;
                 n_img = ni;
                 nt = t;
@@ -1062,11 +854,8 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
         }
         if (!R) return false;
     } else {
-        static const int lim14 = frt_tuning_env("FRT_CONV_NT4_14") ? 128 : 224;  // experiment: half-image strips (4 tiles) on the 14x14 layers
-        const int lim = a.H == 14 ? lim14 : 224;
-        static const bool ragged_ok = !(frt_tuning_env("FRT_CONV_RAGGED") && frt_tuning_env("FRT_CONV_RAGGED")[0] == '0');
         for (int d = a.H; d >= 1; --d) {  // tallest strip first
-            if (d * a.W > lim) continue;
+            if (d * a.W > 224) continue;
             const int n_str = (a.H + d - 1) / d;
             if (a.H % d) {
                 // Ragged last strip (rows past the image are padding in the patch and dead in the epilogue): only the short two-tile strips
@@ -1074,7 +863,7 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
                 // faces at ONE round of two-tile workgroups where two-row strips take two rounds of one-tile workgroups, each of which
                 // streams the same 590 KB of weights (pass of 28 / 32 / 40 / 48 / 55 faces: 1.15 / 1.22 / 1.54 / 1.60 / 1.84 -> 1.08 / 1.12 / 1.42 / 1.49 /
                 // 1.57 ms, profiles/r03/r03z_ragged.txt)
-                if (!ragged_ok || !small_ok || (n_str * d - a.H) * 7 > a.H || tiles_for(d * (a.W + 2)) != 2 || d * (a.W + 2) > 64) continue;
+                if ((n_str * d - a.H) * 7 > a.H || tiles_for(d * (a.W + 2)) != 2 || d * (a.W + 2) > 64) continue;
                 if (a.B * n_str * co_tiles < kWant) continue;  // (never the last resort: the divisor strips cover that)
             }
             // slots are enumerated over the padded row width when that still fits the same number of tiles (conflict-free LDS reads)
@@ -1084,7 +873,7 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
             if (d * a.W * 10 < t * 32 * 7) continue;  // more than 30 % dead pixel slots
             R = d;
             nt = t;
-            if (!small_ok || a.B * n_str * co_tiles >= kWant) break;  // (else: keep shortening; the shortest eligible strip stays)
+            if (a.B * n_str * co_tiles >= kWant) break;  // (else: keep shortening; the shortest eligible strip stays)
         }
         if (!R) return false;
     }
@@ -1092,19 +881,19 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
     return true;
 }
 
-template <int PPS, int PT, int NW, bool SINGLE, int ABL = 0, bool PAIR = false, int NT = 7, int BFD = 2, int WR = 3, bool SEP = false>
+template <int PPS, int PT, int NW, bool SINGLE, bool PAIR = false, int NT = 7, int BFD = 2, int WR = 3, bool SEP = false>
 void launch_patch_t(const ConvMfmaArgs &a, int R, int n_img, hipStream_t s) {
     const size_t lds = PAIR ? (size_t)2 * 34 * 2048 : (size_t)(SINGLE ? 1 : 2) * PT * PPS * 4096;  // patch buffers only (weights live in registers)
     static_assert(PAIR || ((SINGLE ? 1 : 2) * PT * PPS * 4096 <= 160 * 1024 && PT * PPS * 4096 >= 4 * 32 * 36 * 4), "LDS budget / epilogue scratch");
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patch_kernel<PPS, PT, NW, SINGLE, ABL, PAIR, NT, BFD, WR, SEP>), hipFuncAttributeMaxDynamicSharedMemorySize,
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patch_kernel<PPS, PT, NW, SINGLE, PAIR, NT, BFD, WR, SEP>), hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)lds);
     }
     const int strips = ((a.B + n_img - 1) / n_img) * ((a.H + R - 1) / R);
     dim3 grid(PAIR ? (strips + 1) / 2 : strips * (a.Cout / 128));
     const int linear = (n_img == 1 && R * (a.W + 2) <= NT * 32) ? 1 : 0;
-    hipLaunchKernelGGL((conv_patch_kernel<PPS, PT, NW, SINGLE, ABL, PAIR, NT, BFD, WR, SEP>), grid, dim3(256), lds, s, a, R, n_img, linear);
+    hipLaunchKernelGGL((conv_patch_kernel<PPS, PT, NW, SINGLE, PAIR, NT, BFD, WR, SEP>), grid, dim3(256), lds, s, a, R, n_img, linear);
 }
 
 // compact strips: rows of the stacked-image patch window the tallest strip of the launch needs (top halo + the rows its pixels touch, zero
@@ -1123,37 +912,25 @@ int compact_patch_rows(const ConvMfmaArgs &a, int nt) {
     return worst;
 }
 
-template <int NT, int ABL = 0>
+template <int NT>
 void launch_patchc_t(const ConvMfmaArgs &a, int npr, hipStream_t s) {
     constexpr size_t lds = (size_t)2 * 10 * 4096;
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done))
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patchc_kernel<NT, ABL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patchc_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const long M = (long)a.B * a.H * a.W;
     const int strips = (int)((M + NT * 32 - 1) / (NT * 32));
-    hipLaunchKernelGGL((conv_patchc_kernel<NT, ABL>), dim3(strips * (a.Cout / 128)), dim3(256), lds, s, a, npr);
-}
-
-int conv_impl() {  // FRT_CONV_IMPL: 1 = v1 register-staged, 2 = LDS-DMA 2-stage (default: 64 KB ring, 2 workgroups per CU), 3 = LDS-DMA 3-stage
-    static int impl = -1;
-    if (impl < 0) {
-        const char *e = frt_tuning_env("FRT_CONV_IMPL");
-        impl = e ? atoi(e) : 2;
-        if (impl < 1 || impl > 3) impl = 2;
-    }
-    return impl;
+    hipLaunchKernelGGL((conv_patchc_kernel<NT>), dim3(strips * (a.Cout / 128)), dim3(256), lds, s, a, npr);
 }
 
 }  // namespace
 
 // Which kernel symbol a launch resolves to (also the profiling label, so bench.py / rocprofv3 can be matched by name).
-enum { CV_V1_22, CV_V1_14, CV_G2_22, CV_G2_14, CV_G3_22, CV_G3_14, CV_P_PAIR, CV_P_SINGLE, CV_P_255, CV_P_264, CV_P_255_NT4, CV_P_NT2, CV_P_NT1, CV_PC_7, CV_PC_4 };
+enum { CV_G2_22, CV_G2_14, CV_P_PAIR, CV_P_SINGLE, CV_P_255, CV_P_264, CV_P_255_NT4, CV_P_NT2, CV_P_NT1, CV_PC_7, CV_PC_4 };
 static int conv_variant(const ConvMfmaArgs &a, int &R, int &n_img) {
-    const int impl = conv_impl();
-    static const int use_patch = frt_tuning_env("FRT_CONV_PATCH") ? atoi(frt_tuning_env("FRT_CONV_PATCH")) : 1;
     int slots, nt;
     bool single;
-    if (impl >= 2 && use_patch && patch_geometry(a, R, n_img, slots, single, nt)) {
+    if (patch_geometry(a, R, n_img, slots, single, nt)) {
         if (a.Cout == 64) return CV_P_PAIR;   // pair mode: 2 strips x 68 KB patch
         if (single) return CV_P_SINGLE;       // 15 slots (60 KB)
         if (nt == 1) return CV_P_NT1;         // short strips for small batches: 2 x 20 KB patch buffers
@@ -1161,9 +938,8 @@ static int conv_variant(const ConvMfmaArgs &a, int &R, int &n_img) {
         // compact strips (round 6) wherever the full-batch geometry leaves dead pixel slots: whole 14x14 images in 7 tiles (196 of 224 slots
         // live) -> 8 images per 7 strips; two 7x7 images in 4 tiles (98 of 128) -> 128 images per 49 strips.  Not for the fused SE tail (it
         // pools per image inside a strip) - conv_se_fused asks with the SE scratch set.
-        static const bool compact_on = !(frt_tuning_env("FRT_CONV_COMPACT") && frt_tuning_env("FRT_CONV_COMPACT")[0] == '0');
         const bool epi_ok = a.mode == EPI_PRELU || a.mode == EPI_BN || (a.mode == EPI_BN_ADD_BN && !a.se_pool);
-        if (compact_on && epi_ok && slots <= 10 && ((nt == 7 && n_img == 1 && R == a.H && a.H * a.W < 224) || (nt == 4 && n_img == 2 && 2 * a.H * a.W < 128))) {
+        if (epi_ok && slots <= 10 && ((nt == 7 && n_img == 1 && R == a.H && a.H * a.W < 224) || (nt == 4 && n_img == 2 && 2 * a.H * a.W < 128))) {
             const int npr = compact_patch_rows(a, nt);
             if (npr > 0 && (npr * a.W + 1) * 9 <= 10 * 256) {
                 R = npr;
@@ -1173,24 +949,21 @@ static int conv_variant(const ConvMfmaArgs &a, int &R, int &n_img) {
         if (nt == 4) return CV_P_255_NT4;     // 4 pixel tiles per strip (small maps)
         return slots <= 10 ? CV_P_255 : CV_P_264;  // 2 x 40 KB / 2 x 48 KB patch buffers
     }
-    const bool wide = a.Cout % 128 == 0;
-    if (impl == 1) return wide ? CV_V1_22 : CV_V1_14;
-    if (impl == 2) return wide ? CV_G2_22 : CV_G2_14;
-    return wide ? CV_G3_22 : CV_G3_14;
+    // everything else: the im2col LDS-DMA kernel with a 2-stage (64 KB) ring, 2 workgroups per CU
+    return a.Cout % 128 == 0 ? CV_G2_22 : CV_G2_14;
 }
 
 const char *conv_kernel_label(const ConvMfmaArgs &a) {
-    static const char *names[] = {"conv_mfma_kernel<2, 2>", "conv_mfma_kernel<1, 4>", "conv_glds_kernel<2, 2, 2, 0>", "conv_glds_kernel<1, 4, 2, 0>",
-                                  "conv_glds_kernel<2, 2, 3, 0>", "conv_glds_kernel<1, 4, 3, 0>", "conv_patch_kernel<3, 5, 5, true, 0, true, 7, 2, 3>",
-                                  "conv_patch_kernel<3, 5, 5, true, 0, false, 7, 1, 3>", "conv_patch_kernel<10, 1, 5, false, 0, false, 7, 1, 3>",
-                                  "conv_patch_kernel<2, 6, 4, false, 0, false, 7, 2, 3>", "conv_patch_kernel<10, 1, 5, false, 0, false, 4, 1, 3>",
-                                  "conv_patch_kernel<5, 1, 5, false, 0, false, 2, 1, 3>", "conv_patch_kernel<5, 1, 5, false, 0, false, 1, 1, 3>",
-                                  "conv_patchc_kernel<7, 0>", "conv_patchc_kernel<4, 0>"};
+    static const char *names[] = {"conv_glds_kernel<2, 2, 2>", "conv_glds_kernel<1, 4, 2>", "conv_patch_kernel<3, 5, 5, true, true, 7, 2, 3>",
+                                  "conv_patch_kernel<3, 5, 5, true, false, 7, 1, 3>", "conv_patch_kernel<10, 1, 5, false, false, 7, 1, 3>",
+                                  "conv_patch_kernel<2, 6, 4, false, false, 7, 2, 3>", "conv_patch_kernel<10, 1, 5, false, false, 4, 1, 3>",
+                                  "conv_patch_kernel<5, 1, 5, false, false, 2, 1, 3>", "conv_patch_kernel<5, 1, 5, false, false, 1, 1, 3>",
+                                  "conv_patchc_kernel<7>", "conv_patchc_kernel<4>"};
     if (conv_small_applies(a)) return a.mode == EPI_BN_ADD_BN && a.scx ? "conv_small_kernel<true>" : "conv_small_kernel<false>";
     if (conv_ks_applies(a)) return "conv_ks_kernel";
     if (const char *l2 = conv_s2_label(a)) return l2;
     if (conv64_applies(a))
-        return a.mode == EPI_PRELU ? "conv64_kernel<0, 0>" : (a.mode == EPI_BN ? "conv64_kernel<1, 0>" : "conv64_kernel<2, 0>");
+        return a.mode == EPI_PRELU ? "conv64_kernel<0>" : (a.mode == EPI_BN ? "conv64_kernel<1>" : "conv64_kernel<2>");
     int R, n_img;
     const int variant = conv_variant(a, R, n_img);
     const char *base = names[variant];
@@ -1218,11 +991,11 @@ static bool se_fused_fits_device() {
         hipDeviceProp_t prop;
         int per_cu7 = 0, per_cu4 = 0;
         const size_t lds7 = (size_t)2 * 10 * 4096, lds4 = (size_t)2 * 10 * 4096;
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patch_kernel<10, 1, 5, false, 0, false, 7, 1, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds7);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patch_kernel<10, 1, 5, false, 0, false, 4, 1, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patch_kernel<10, 1, 5, false, false, 7, 1, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds7);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patch_kernel<10, 1, 5, false, false, 4, 1, 3, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds4);
         const bool q = hipGetDeviceProperties(&prop, d) == hipSuccess &&
-                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu7, conv_patch_kernel<10, 1, 5, false, 0, false, 7, 1, 3, true>, 256, lds7) == hipSuccess &&
-                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, conv_patch_kernel<10, 1, 5, false, 0, false, 4, 1, 3, true>, 256, lds4) == hipSuccess;
+                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu7, conv_patch_kernel<10, 1, 5, false, false, 7, 1, 3, true>, 256, lds7) == hipSuccess &&
+                       hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, conv_patch_kernel<10, 1, 5, false, false, 4, 1, 3, true>, 256, lds4) == hipSuccess;
         ok[d] = (q && (long)per_cu7 * prop.multiProcessorCount >= 16 && (long)per_cu4 * prop.multiProcessorCount >= 16) ? 1 : -1;
     }
     return ok[d] > 0;
@@ -1248,98 +1021,37 @@ void launch_conv_mfma(const ConvMfmaArgs &a, hipStream_t s) {
     if (launch_conv_s2(a, s)) return;  // stride-2 strip kernel on de-interleaved phase planes (kernels_arc_s2.hip)
     int R = 0, n_img = 0;
     const int v = conv_variant(a, R, n_img);
-#ifdef FRT_ABLATE
-    static const int abl = frt_tuning_env("FRT_CONV_ABLATE") ? atoi(frt_tuning_env("FRT_CONV_ABLATE")) : 0;  // timing experiments only (make TUNING=1)
-#endif
     switch (v) {
-        case CV_P_PAIR: return launch_patch_t<3, 5, 5, true, 0, true>(a, R, n_img, s);
-        case CV_P_SINGLE: return launch_patch_t<3, 5, 5, true, 0, false, 7, 1>(a, R, n_img, s);
+        case CV_P_PAIR: return launch_patch_t<3, 5, 5, true, true>(a, R, n_img, s);
+        case CV_P_SINGLE: return launch_patch_t<3, 5, 5, true, false, 7, 1>(a, R, n_img, s);
         case CV_P_255:
-#ifdef FRT_ABLATE
-            if (abl == 1) return launch_patch_t<2, 5, 5, false, 1>(a, R, n_img, s);
-            if (abl == 2) return launch_patch_t<2, 5, 5, false, 2>(a, R, n_img, s);
-            if (abl == 4) return launch_patch_t<2, 5, 5, false, 4>(a, R, n_img, s);
-            if (abl == 5) return launch_patch_t<2, 5, 5, false, 5>(a, R, n_img, s);
-            if (abl == 6) return launch_patch_t<2, 5, 5, false, 6>(a, R, n_img, s);
-            if (abl == 7) return launch_patch_t<2, 5, 5, false, 7>(a, R, n_img, s);
-            if (abl == 8) return launch_patch_t<2, 5, 5, false, 8>(a, R, n_img, s);
-            if (abl == 9) return launch_patch_t<2, 5, 5, false, 9>(a, R, n_img, s);
-            if (abl == 18) return launch_patch_t<5, 2, 5, false, 0, false, 7, 1>(a, R, n_img, s);
-            if (abl == 13) return launch_patch_t<2, 5, 5, false, 13, false, 7, 1>(a, R, n_img, s);
-            if (abl == 14) return launch_patch_t<2, 5, 5, false, 14, false, 7, 1>(a, R, n_img, s);
-            if (abl == 15) return launch_patch_t<2, 5, 5, false, 1, false, 7, 1>(a, R, n_img, s);
-            if (abl == 12) return launch_patch_t<2, 5, 5, false, 0, false, 7, 2, 9>(a, R, n_img, s);
-            if (abl == 11) return launch_patch_t<2, 5, 5, false>(a, R, n_img, s);  // two-deep B ring, one wave per SIMD
-            if (abl == 19) return launch_patch_t<2, 5, 5, false, 0, false, 7, 1>(a, R, n_img, s);  // patch pieces spread over taps 0-4
-            if (abl == 20) return launch_patch_t<10, 1, 5, false, 20, false, 7, 1>(a, R, n_img, s);
-            if (abl == 22) return launch_patch_t<10, 1, 5, false, 2, false, 7, 1>(a, R, n_img, s);
-            if (abl == 24) return launch_patch_t<10, 1, 5, false, 4, false, 7, 1>(a, R, n_img, s);
-            if (abl == 29) return launch_patch_t<10, 1, 5, false, 9, false, 7, 1>(a, R, n_img, s);
-#endif
             if (a.mode == EPI_BN_SE)  // IR-SE conv2 with the whole SE tail in the epilogue (the caller checked conv_se_fused)
-                return launch_patch_t<10, 1, 5, false, 0, false, 7, 1, 3, true>(a, R, n_img, s);
+                return launch_patch_t<10, 1, 5, false, false, 7, 1, 3, true>(a, R, n_img, s);
             // (Round 3, built, measured and parked in tools/experiments/conv_patch2_two_cout_blocks_per_wave.hip: a wave owning TWO cout
             //  blocks x half the pixel tiles, so that a B fragment read from LDS feeds two MFMAs - half the LDS bytes per MFMA at 256
             //  registers, parity tests green.  40.9 -> 43.2 us per launch, pipelined step 3.274 -> 3.348 ms (profiles/r03/r03g_patch2_*):
             //  the 4 + 3 split of 7 tiles puts 8 MFMA slots per kk step on the critical SIMDs, and the K loop was never LDS-bound - it
             //  runs at 0.94 of the rate the part sustains for its instruction mix.)
-            return launch_patch_t<10, 1, 5, false, 0, false, 7, 1>(a, R, n_img, s);
+            return launch_patch_t<10, 1, 5, false, false, 7, 1>(a, R, n_img, s);
         case CV_P_264: return launch_patch_t<2, 6, 4, false>(a, R, n_img, s);
-        case CV_PC_7:
-#ifdef FRT_ABLATE
-            if (abl == 22) return launch_patchc_t<7, 2>(a, R, s);
-            if (abl == 24) return launch_patchc_t<7, 4>(a, R, s);
-            if (abl == 25) return launch_patchc_t<7, 5>(a, R, s);
-#endif
-            return launch_patchc_t<7>(a, R, s);
+        case CV_PC_7: return launch_patchc_t<7>(a, R, s);
         case CV_PC_4: return launch_patchc_t<4>(a, R, s);
         case CV_P_255_NT4:
-#ifdef FRT_ABLATE
-            if (abl == 11) return launch_patch_t<2, 5, 5, false, 0, false, 4>(a, R, n_img, s);
-            if (abl == 19) return launch_patch_t<2, 5, 5, false, 0, false, 4, 1>(a, R, n_img, s);
-#endif
-            if (a.mode == EPI_BN_SE) return launch_patch_t<10, 1, 5, false, 0, false, 4, 1, 3, true>(a, R, n_img, s);  // (conv_se_fused)
-            return launch_patch_t<10, 1, 5, false, 0, false, 4, 1>(a, R, n_img, s);
+            if (a.mode == EPI_BN_SE) return launch_patch_t<10, 1, 5, false, false, 4, 1, 3, true>(a, R, n_img, s);  // (conv_se_fused)
+            return launch_patch_t<10, 1, 5, false, false, 4, 1>(a, R, n_img, s);
         // (Round 3, measured and not kept: a 9-deep weight ring for these short-strip variants - 1 or 2 accumulator tiles leave the
         //  registers for it.  4 / 16 / 32 faces: 12.4 -> 12.0, 14.0 -> 13.5, 18.7 -> 18.9 us per launch, batch-1 call 1.286 -> 1.280 ms
         //  (profiles/r03/r03f_small_batch_wr.txt): a small-batch launch is prologue + four chunk hand-overs + epilogue + dispatch, not
         //  weight latency.)
-        case CV_P_NT2:
-#ifdef FRT_ABLATE
-            if (abl == 1) return launch_patch_t<5, 1, 5, false, 1, false, 2, 1>(a, R, n_img, s);
-            if (abl == 2) return launch_patch_t<5, 1, 5, false, 2, false, 2, 1>(a, R, n_img, s);
-            if (abl == 5) return launch_patch_t<5, 1, 5, false, 5, false, 2, 1>(a, R, n_img, s);
-            if (abl == 6) return launch_patch_t<5, 1, 5, false, 6, false, 2, 1>(a, R, n_img, s);
-#endif
-            return launch_patch_t<5, 1, 5, false, 0, false, 2, 1>(a, R, n_img, s);
-        case CV_P_NT1:
-#ifdef FRT_ABLATE
-            if (abl == 1) return launch_patch_t<5, 1, 5, false, 1, false, 1, 1>(a, R, n_img, s);
-            if (abl == 2) return launch_patch_t<5, 1, 5, false, 2, false, 1, 1>(a, R, n_img, s);
-            if (abl == 5) return launch_patch_t<5, 1, 5, false, 5, false, 1, 1>(a, R, n_img, s);
-            if (abl == 6) return launch_patch_t<5, 1, 5, false, 6, false, 1, 1>(a, R, n_img, s);
-#endif
-            return launch_patch_t<5, 1, 5, false, 0, false, 1, 1>(a, R, n_img, s);
-        case CV_V1_22: return launch_conv_t<2, 2>(a, s);
-        case CV_V1_14: return launch_conv_t<1, 4>(a, s);
-        case CV_G2_22:
-#ifdef FRT_ABLATE
-            if (abl == 1) return launch_glds_t<2, 2, 2, 1>(a, s);
-            if (abl == 2) return launch_glds_t<2, 2, 2, 2>(a, s);
-#endif
-            return launch_glds_t<2, 2, 2>(a, s);
-        case CV_G2_14: return launch_glds_t<1, 4, 2>(a, s);
-        case CV_G3_22: return launch_glds_t<2, 2, 3>(a, s);
-        default: return launch_glds_t<1, 4, 3>(a, s);
+        case CV_P_NT2: return launch_patch_t<5, 1, 5, false, false, 2, 1>(a, R, n_img, s);
+        case CV_P_NT1: return launch_patch_t<5, 1, 5, false, false, 1, 1>(a, R, n_img, s);
+        case CV_G2_22: return launch_glds_t<2, 2, 2>(a, s);
+        default: return launch_glds_t<1, 4, 2>(a, s);
     }
 }
 
 void launch_arc_input(const ArcInputArgs &a, hipStream_t s) {
-    static const bool use_mfma = [] {
-        const char *e = frt_tuning_env("FRT_ARC_INPUT_MFMA");
-        return !(e && e[0] == '0');
-    }();
-    if (use_mfma && launch_arc_input_mfma(a, s)) return;
+    if (launch_arc_input_mfma(a, s)) return;
     const long total = (long)a.F * a.H * a.W * 8;  // 8 lanes per pixel
     hipLaunchKernelGGL(arc_input_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a);
 }

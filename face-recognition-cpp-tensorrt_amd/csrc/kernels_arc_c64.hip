@@ -29,7 +29,7 @@ constexpr int PATCH_B = NDMA * 2 * 1024;        // 34816: whole DMA slots
 constexpr int RING = 5;                // B-fragment register ring: fragments are requested RING-1 steps (128 clk each) ahead
 constexpr int EROW = 36;               // floats per pixel row of the epilogue tile (32 + 4 pad)
 
-template <int MODE, int abl = 0>  // abl (measurement only): 1 no B reads, 2 no MFMA, 4 no epilogue
+template <int MODE>
 __global__ __launch_bounds__(128) void conv64_kernel(ConvMfmaArgs p, int n_strips) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *patch = smem;                                           // [2][PATCH_B]
@@ -160,18 +160,13 @@ __global__ __launch_bounds__(128) void conv64_kernel(ConvMfmaArgs p, int n_strip
         };
 #pragma unroll
         for (int s = 0; s < RING - 1; ++s)
-            if (!(abl & 1)) read_b(s, bf[s]);
+            read_b(s, bf[s]);
 #pragma unroll
         for (int s = 0; s < 36; ++s) {
-            if (s + RING - 1 < 36 && !(abl & 1)) read_b(s + RING - 1, bf[(s + RING - 1) % RING]);
+            if (s + RING - 1 < 36) read_b(s + RING - 1, bf[(s + RING - 1) % RING]);
             __builtin_amdgcn_sched_barrier(0);
-            if (!(abl & 2)) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[s >> 2][s & 3], bf[s % RING][t], acc[t], 0, 0, 0);
-            } else {
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[t][s & 15] += (float)bf[s % RING][t][0] * (float)wreg[s >> 2][s & 3][0];
-            }
+            for (int t = 0; t < 4; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wreg[s >> 2][s & 3], bf[s % RING][t], acc[t], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
 
@@ -179,50 +174,48 @@ __global__ __launch_bounds__(128) void conv64_kernel(ConvMfmaArgs p, int n_strip
         // output stores out of the wait
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         // ---- epilogue of this strip
-        if (!(abl & 4)) {
-            const int b = strip / strips_per_img, rem = strip - b * strips_per_img;
-            const int sy = rem / strips_x, sx = rem - sy * strips_x;
-            const long img_base = (long)b * H * W;
+        const int b = strip / strips_per_img, rem = strip - b * strips_per_img;
+        const int sy = rem / strips_x, sx = rem - sy * strips_x;
+        const long img_base = (long)b * H * W;
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                // lane (r, hi) owns pixel r of the tile and channels (e&3) + 8*(e>>2) + 4*hi of this wave's 32
+        for (int t = 0; t < 4; ++t) {
+            // lane (r, hi) owns pixel r of the tile and channels (e&3) + 8*(e>>2) + 4*hi of this wave's 32
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    floatx4 v = {acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
-                    *reinterpret_cast<floatx4 *>(et + r * EROW + 8 * g + 4 * hi) = v;
+            for (int g = 0; g < 4; ++g) {
+                floatx4 v = {acc[t][4 * g], acc[t][4 * g + 1], acc[t][4 * g + 2], acc[t][4 * g + 3]};
+                *reinterpret_cast<floatx4 *>(et + r * EROW + 8 * g + 4 * hi) = v;
+            }
+            // read back as 128 octets (32 pixels x 4), two per lane: lane -> pixel (lane >> 2) + 16 i, channel octet lane & 3
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const int px = (lane >> 2) + 16 * i;
+                const floatx4 v0 = *reinterpret_cast<const floatx4 *>(et + px * EROW + (lane & 3) * 8);
+                const floatx4 v1 = *reinterpret_cast<const floatx4 *>(et + px * EROW + (lane & 3) * 8 + 4);
+                const int q = 32 * t + px;
+                if (q >= 2 * SW) continue;
+                const int row = q / SW, col = q - row * SW;
+                const long m = img_base + (long)(sy * 2 + row) * W + sx * SW + col;
+                float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                if (MODE == EPI_PRELU) {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * q0[e];
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) v[e] = v[e] * q0[e] + q1[e];
                 }
-                // read back as 128 octets (32 pixels x 4), two per lane: lane -> pixel (lane >> 2) + 16 i, channel octet lane & 3
+                if (MODE == EPI_BN_ADD_BN) {
 #pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const int px = (lane >> 2) + 16 * i;
-                    const floatx4 v0 = *reinterpret_cast<const floatx4 *>(et + px * EROW + (lane & 3) * 8);
-                    const floatx4 v1 = *reinterpret_cast<const floatx4 *>(et + px * EROW + (lane & 3) * 8 + 4);
-                    const int q = 32 * t + px;
-                    if (q >= 2 * SW) continue;
-                    const int row = q / SW, col = q - row * SW;
-                    const long m = img_base + (long)(sy * 2 + row) * W + sx * SW + col;
-                    float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                    if (MODE == EPI_PRELU) {
+                    for (int e = 0; e < 8; ++e) v[e] += (float)scv[t][i][e];
+                }
+                half8 o;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * q0[e];
-                    } else {
+                for (int e = 0; e < 8; ++e) o[e] = (half_t)v[e];
+                *reinterpret_cast<half8 *>(p.out0 + m * 64 + ec0) = o;
+                if (MODE == EPI_BN_ADD_BN && p.out1) {
+                    half8 z;
 #pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] = v[e] * q0[e] + q1[e];
-                    }
-                    if (MODE == EPI_BN_ADD_BN) {
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) v[e] += (float)scv[t][i][e];
-                    }
-                    half8 o;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) o[e] = (half_t)v[e];
-                    *reinterpret_cast<half8 *>(p.out0 + m * 64 + ec0) = o;
-                    if (MODE == EPI_BN_ADD_BN && p.out1) {
-                        half8 z;
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) z[e] = (half_t)(v[e] * q2[e] + q3[e]);
-                        *reinterpret_cast<half8 *>(p.out1 + m * 64 + ec0) = z;
-                    }
+                    for (int e = 0; e < 8; ++e) z[e] = (half_t)(v[e] * q2[e] + q3[e]);
+                    *reinterpret_cast<half8 *>(p.out1 + m * 64 + ec0) = z;
                 }
             }
         }
@@ -255,50 +248,21 @@ __global__ __launch_bounds__(128) void conv64_kernel(ConvMfmaArgs p, int n_strip
 bool conv64_applies(const ConvMfmaArgs &a) {
     if (a.Cin != 64 || a.Cout != 64 || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W) return false;
     if ((a.H & 1) || a.W % SW || a.mode == EPI_PARTIAL) return false;
-    if (a.mode == EPI_BN_ADD_BN && !(a.sc && a.sc_stride == 1 && a.sc_h == a.H && a.sc_w == a.W)) return false;
-    static const bool off = frt_tuning_env("FRT_CONV64") && frt_tuning_env("FRT_CONV64")[0] == '0';
-    return !off;
+    return a.mode != EPI_BN_ADD_BN || (a.sc && a.sc_stride == 1 && a.sc_h == a.H && a.sc_w == a.W);
 }
 
 bool launch_conv64(const ConvMfmaArgs &a, hipStream_t s) {
     if (!conv64_applies(a)) return false;
-    if (a.Cin != 64 || a.Cout != 64 || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W) return false;
-    if ((a.H & 1) || a.W % SW || a.mode == EPI_PARTIAL) return false;
-    if (a.mode == EPI_BN_ADD_BN && !(a.sc && a.sc_stride == 1 && a.sc_h == a.H && a.sc_w == a.W)) return false;
-    static const bool off = frt_tuning_env("FRT_CONV64") && frt_tuning_env("FRT_CONV64")[0] == '0';
-    if (off) return false;
     const int n_strips = a.B * (a.H / 2) * (a.W / SW);
     int grid = 512;
     if (grid > n_strips) grid = n_strips;
     const size_t lds = 2 * PATCH_B + 2 * 32 * EROW * sizeof(float);
-#ifdef FRT_ABLATE
-    static const int abl = frt_tuning_env("FRT_C64_ABLATE") ? atoi(frt_tuning_env("FRT_C64_ABLATE")) : 0;  // measurement only: 1 no B reads, 2 no MFMA, 4 no epilogue
-#endif
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done)) {  // > 64 KB of dynamic LDS needs the opt-in
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_PRELU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_BN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_BN_ADD_BN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
-#ifdef FRT_ABLATE
-    if (abl && a.mode == EPI_PRELU) {
-        static bool ad = false;
-        if (!ad) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_PRELU, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_PRELU, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_PRELU, 4>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_PRELU, 5>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_PRELU, 7>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            ad = true;
-        }
-        if (abl == 1) hipLaunchKernelGGL((conv64_kernel<EPI_PRELU, 1>), dim3(grid), dim3(128), lds, s, a, n_strips);
-        else if (abl == 2) hipLaunchKernelGGL((conv64_kernel<EPI_PRELU, 2>), dim3(grid), dim3(128), lds, s, a, n_strips);
-        else if (abl == 4) hipLaunchKernelGGL((conv64_kernel<EPI_PRELU, 4>), dim3(grid), dim3(128), lds, s, a, n_strips);
-        else if (abl == 5) hipLaunchKernelGGL((conv64_kernel<EPI_PRELU, 5>), dim3(grid), dim3(128), lds, s, a, n_strips);
-        else hipLaunchKernelGGL((conv64_kernel<EPI_PRELU, 7>), dim3(grid), dim3(128), lds, s, a, n_strips);
-        return true;
-    }
-#endif
     switch (a.mode) {
         case EPI_PRELU: hipLaunchKernelGGL((conv64_kernel<EPI_PRELU>), dim3(grid), dim3(128), lds, s, a, n_strips); break;
         case EPI_BN: hipLaunchKernelGGL((conv64_kernel<EPI_BN>), dim3(grid), dim3(128), lds, s, a, n_strips); break;

@@ -105,7 +105,7 @@ struct Conv32 {
 //  pixel 8 x 9 times - at the ~ 11 TB/s the L2 -> CU path delivers); the 288 MFMAs of a wave 8.7 us at 30 ns each (tools/ubench/mfma_f32_chain:
 //  the dependent chain costs nothing) - and the two ADD instead of overlapping, whatever the order.  Fewer bytes need larger tiles, larger tiles
 //  leave fewer than 800 waves for 1 024 SIMDs at 4 faces: the mode stays a small-batch accuracy path.)
-template <bool PRO, int ABL = 0>  // ABL (measurement builds): 1 = no K loop, 2 = K loop without the MFMAs
+template <bool PRO>
 __global__ __launch_bounds__(256) void conv32_kernel(Conv32 a, int cb_log2) {
     constexpr int C32_R = PRO ? 3 : 4;
     __shared__ float red[4][32][33];
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void conv32_kernel(Conv32 a, int cb_log2) {
     const int co0 = blockIdx.y * 32;
     const int CB = 1 << cb_log2;            // 32-channel blocks per tap
     const int NB = a.ks * a.ks * CB;        // K blocks of the layer
-    const int NI = ABL == 1 ? 0 : (NB + 3) >> 2;           // this wave's iterations (block wave + 4 it; blocks >= NB are zero operands)
+    const int NI = (NB + 3) >> 2;           // this wave's iterations (block wave + 4 it; blocks >= NB are zero operands)
     // loader role: lane = (pixel sub-index lane >> 3, 16-byte chunk lane & 7); pixel of slot i: (lane >> 3) + 8 i.  Per pixel, once: the BYTE offset
     // of its tap (0, 0) / channel 4 ch (may be "negative": only ever used with a valid tap's offset added) and the 9 taps' validity bits
     const int lp = lane >> 3, ch = lane & 7;
@@ -208,8 +208,7 @@ __global__ __launch_bounds__(256) void conv32_kernel(Conv32 a, int cb_log2) {
         for (int q = 0; q < 4; ++q) wa[q] = wq[S][q];
         static_for<0, 16>([&](auto gc) {
             constexpr int G = decltype(gc)::value;
-            if (ABL == 2) asm volatile("" ::"v"(wa[G >> 2][G & 3]), "v"(bf[P][G >> 2][G & 3]));
-            else acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[G >> 2][G & 3], bf[P][G >> 2][G & 3], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wa[G >> 2][G & 3], bf[P][G >> 2][G & 3], acc, 0, 0, 0);
             if constexpr (G < 4) issue(it + C32_R, slot_c, std::integral_constant<int, G>{});
             else if constexpr (G < 8) from_lds(std::integral_constant<int, P ^ 1>{}, G - 4);
             else if constexpr (G >= 11 && G < 15) to_lds(std::integral_constant<int, (S + 2) % C32_R>{}, std::integral_constant<int, P>{}, G - 11);
@@ -331,11 +330,6 @@ void launch_conv32(const Conv32Args &c, hipStream_t s) {
     int lg = 0;
     while ((32 << lg) < c.Cin) ++lg;  // Cin / 32 is a power of two (64 ... 512 channels)
     const dim3 grid((unsigned)((M + 31) / 32), (unsigned)(c.Cout / 32));
-#ifdef FRT_ABLATE
-    static const int xp = frt_tuning_env("FRT_C32_ABLATE") ? atoi(frt_tuning_env("FRT_C32_ABLATE")) : 0;  // timing ablations (make TUNING=1): wrong results by design
-    if (xp == 1) { if (c.ps) hipLaunchKernelGGL((conv32_kernel<true, 1>), grid, dim3(256), 0, s, a, lg); else hipLaunchKernelGGL((conv32_kernel<false, 1>), grid, dim3(256), 0, s, a, lg); return; }
-    if (xp == 2) { if (c.ps) hipLaunchKernelGGL((conv32_kernel<true, 2>), grid, dim3(256), 0, s, a, lg); else hipLaunchKernelGGL((conv32_kernel<false, 2>), grid, dim3(256), 0, s, a, lg); return; }
-#endif
     if (c.ps) hipLaunchKernelGGL((conv32_kernel<true>), grid, dim3(256), 0, s, a, lg);
     else hipLaunchKernelGGL((conv32_kernel<false>), grid, dim3(256), 0, s, a, lg);
 }

@@ -25,7 +25,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <type_traits>
-#include <vector>
 
 #include "frt_kernels.h"
 
@@ -52,15 +51,6 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(ConvMfmaArgs p) {
     const int strip = blockIdx.x, blk = blockIdx.y;
     const int img = strip / strips_per_img, row0 = (strip - img * strips_per_img) * R;
     char *patch = smem + wave * (CPW * PATCH_B);
-#ifdef FRT_ABLATE
-    // timing build: phase stamps (100 MHz constant clock) of wave 0 of the first and the last workgroup, 8 per workgroup, into p.outf
-    unsigned long long *stamps = (p.outf && wave == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && blockIdx.y == 0)
-                                     ? reinterpret_cast<unsigned long long *>(p.outf) + (blockIdx.x ? 8 : 0) : nullptr;
-#define KS_STAMP(i) do { if (stamps && lane == 0) stamps[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define KS_STAMP(i) do { } while (0)
-#endif
-    KS_STAMP(0);
     // ---- weights: every fragment of this wave's chunks, straight into registers.  The first three taps go out before the patch pieces,
     //      the rest behind them: "at most that many loads outstanding" then means the patch and the first taps' weights have landed (VMEM
     //      retires in order) and the K loop starts under the rest of the weight stream
@@ -74,7 +64,6 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(ConvMfmaArgs p) {
     load_w(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{});
     load_w(std::integral_constant<int, 0>{}, std::integral_constant<int, 1>{});
     load_w(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{});
-    KS_STAMP(1);
     // ---- patch DMA: piece q = patch rows 7q .. 7q + 6; lane = (row within the piece) * 9 + 16-byte slot (slot 8 = the row's pad)
     if (lane < 63) {
         const int lr = lane / 9, pos = lane - lr * 9;
@@ -116,7 +105,6 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(ConvMfmaArgs p) {
     // between) says the issuing wave's covering vmcnt does order its own reads, and the round-4 symptom was a miscounted wait.  The sleep is
     // kept as margin (64 cycles once per workgroup), not as the mechanism.
     asm volatile("s_sleep 2" ::: "memory");
-    KS_STAMP(2);
 
     // ---- epilogue operands of the tiles this wave finishes (they land under the K loop)
     const int chunk8 = lane & 3;
@@ -190,9 +178,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(ConvMfmaArgs p) {
 
     // ---- the four partial sums meet in LDS (over the patches, which nobody reads any more), added in wave order
     asm volatile("" ::"v"(acc[0][0]));
-    KS_STAMP(3);
     __syncthreads();
-    KS_STAMP(4);
     float *red = reinterpret_cast<float *>(smem);
 #pragma unroll
     for (int j = 0; j < NT; ++j)
@@ -200,7 +186,6 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(ConvMfmaArgs p) {
         for (int g = 0; g < 4; ++g)
             *reinterpret_cast<floatx4 *>(red + ((((wave * NT + j) * 4 + g) * 64) + lane) * 4) = floatx4{acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]};
     __syncthreads();
-    KS_STAMP(5);
     constexpr int RED_B = 4 * NT * 4096, EP_B = 4 * 32 * EROW * 4;
     constexpr int MAIN_B = 4 * CPW * PATCH_B > RED_B ? 4 * CPW * PATCH_B : RED_B;
     constexpr int EP_OFF = RED_B + EP_B <= MAIN_B ? RED_B : MAIN_B;  // the transpose tiles sit behind the partial sums, over dead patches where they fit
@@ -248,38 +233,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(ConvMfmaArgs p) {
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    KS_STAMP(6);
 }
-
-#ifdef FRT_ABLATE
-// timing build, FRT_KS_STAMPS=1: every launch leaves its 16 stamps in the next slot of a device ring; printed at exit
-struct KsStamps {
-    unsigned long long *dev = nullptr;
-    int n = 0;
-    static constexpr int CAP = 4096;
-    int kind[CAP];
-    ~KsStamps() {
-        if (!dev || !n) return;
-        std::vector<unsigned long long> h((size_t)std::min(n, CAP) * 16);
-        if (hipMemcpy(h.data(), dev, h.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) return;
-        for (int k : {2, 4, 7}) {
-            double d[2][7] = {};
-            int cnt = 0;
-            for (int i = std::min(n, CAP) / 2; i < std::min(n, CAP); ++i) {  // second half of the run (warm)
-                if (kind[i] != k) continue;
-                ++cnt;
-                for (int b = 0; b < 2; ++b)
-                    for (int j = 1; j < 7; ++j) d[b][j] += (double)(h[(size_t)i * 16 + b * 8 + j] - h[(size_t)i * 16 + b * 8 + j - 1]) * 0.01;
-            }
-            if (!cnt) continue;
-            for (int b = 0; b < 2; ++b)
-                fprintf(stderr, "[ks stamps] NT %d %s workgroup, %d launches: dma issue %.2f | weights issued + patch landed %.2f | K loop %.2f | barrier %.2f | partials written %.2f | sum + epilogue %.2f us\n",
-                        k, b ? "last" : "first", cnt, d[b][1] / cnt, d[b][2] / cnt, d[b][3] / cnt, d[b][4] / cnt, d[b][5] / cnt, d[b][6] / cnt);
-        }
-    }
-};
-static KsStamps g_stamps;
-#endif
 
 template <int NT, int CPW, int HW, int R>
 void launch_ks_t(const ConvMfmaArgs &a, hipStream_t s) {
@@ -293,27 +247,7 @@ void launch_ks_t(const ConvMfmaArgs &a, hipStream_t s) {
     if (frt_first_use_on_device(attr_done))
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_ks_kernel<NT, CPW, HW, R>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     constexpr int spi = HW / R;
-#ifdef FRT_ABLATE
-    static const bool want_stamps = frt_tuning_env("FRT_KS_STAMPS") != nullptr;
-    if (want_stamps) {
-        if (!g_stamps.dev && hipMalloc(reinterpret_cast<void **>(&g_stamps.dev), KsStamps::CAP * 16 * 8) != hipSuccess) g_stamps.dev = nullptr;
-        if (g_stamps.dev && g_stamps.n < KsStamps::CAP) {
-            ConvMfmaArgs b = a;
-            b.outf = reinterpret_cast<float *>(g_stamps.dev + (size_t)g_stamps.n * 16);
-            g_stamps.kind[g_stamps.n++] = NT;
-            hipLaunchKernelGGL((conv_ks_kernel<NT, CPW, HW, R>), dim3(a.B * spi, a.Cout / 32), dim3(256), lds, s, b);
-            return;
-        }
-    }
-#endif
     hipLaunchKernelGGL((conv_ks_kernel<NT, CPW, HW, R>), dim3(a.B * spi, a.Cout / 32), dim3(256), lds, s, a);
-}
-
-// faces per pass this kernel takes (above: the strip kernels; conv_small_kernel is asked first and keeps the small batches)
-int ks_max_faces(int H) {
-    static const int e14 = frt_tuning_env("FRT_CONV_KS_MAX14") ? atoi(frt_tuning_env("FRT_CONV_KS_MAX14")) : 40;
-    static const int e7 = frt_tuning_env("FRT_CONV_KS_MAX7") ? atoi(frt_tuning_env("FRT_CONV_KS_MAX7")) : 40;
-    return H == 14 ? e14 : e7;
 }
 
 }  // namespace
@@ -323,7 +257,7 @@ bool conv_ks_applies(const ConvMfmaArgs &a) {
     if (!((a.H == 14 && a.Cin == 256) || (a.H == 7 && a.Cin == 512))) return false;
     if (a.mode != EPI_PRELU && a.mode != EPI_BN && a.mode != EPI_BN_ADD_BN) return false;
     if (a.mode == EPI_BN_ADD_BN && (a.scx || !a.sc || a.sc_stride != 1 || a.sc_h != a.Ho || a.sc_w != a.Wo)) return false;
-    return a.B >= 1 && a.B <= ks_max_faces(a.H);
+    return a.B >= 1 && a.B <= 40;  // faces per pass this kernel takes (above: the strip kernels; conv_small_kernel is asked first and keeps the small batches)
 }
 
 bool launch_conv_ks(const ConvMfmaArgs &a, hipStream_t s) {

@@ -57,25 +57,9 @@ __global__ __launch_bounds__(NW * 64) void conv_small_kernel(ConvMfmaArgs p, con
 
     half8 A[D][NC][4], B[D][4];
     const half8 zero8 = {0, 0, 0, 0, 0, 0, 0, 0};
-#ifdef FRT_ABLATE
-    const int abl = (int)(tap_pack >> 40) & 3;  // timing experiments (wrong results): 1 no B loads, 2 no A loads
-#endif
     auto load = [&](int i, auto dc) {
         constexpr int d = decltype(dc)::value;
         const int j = wave + NW * i;
-#ifdef FRT_ABLATE
-        if (abl) {
-            const half_t *ap = wb + (long)((j / 9) * 9 + j % 9) * 2048;
-            const half_t *bp = xf + (long)(j % 9) * Cin + (j / 9) * 64;
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-#pragma unroll
-                for (int kk = 0; kk < 4; ++kk) A[d][c][kk] = abl == 2 ? zero8 + (half_t)lane : *reinterpret_cast<const half8 *>(ap + c * wstride + kk * 512);
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) B[d][kk] = abl == 1 ? zero8 + (half_t)lane : *reinterpret_cast<const half8 *>(bp + kk * 16);
-            return;
-        }
-#endif
         if (SCF && j >= np) {
             const int c64 = j - np;
 #pragma unroll
@@ -210,14 +194,7 @@ __global__ __launch_bounds__(NW * 64) void conv_small_kernel(ConvMfmaArgs p, con
 // layer at 1 / 4 / 8 / 16 / 32 faces (profiles/r03/r03p_small_layers.txt, r03p_small_ab*.txt): stride-1 layers break even at ~ 14 000 (14x14x256
 // for 8 faces: 392 x 36; 28x28x128 and 56x56x64 for 4 faces are level from 7 000 on); the stride-2 layers - 33 - 44 us in the strip
 // kernel however small the batch - win at 30 000 (16 faces: 25 - 27 us) and lose at 60 000 (32 faces, 14 -> 7: 47 against 43).
-long small_work_limit(int stride) {
-    static const long lim = [] {
-        const char *e = frt_tuning_env("FRT_CONV_SMALL_WORK");
-        return e ? atol(e) : -1;
-    }();
-    if (lim >= 0) return lim;
-    return stride == 2 ? 40000 : 16000;
-}
+long small_work_limit(int stride) { return stride == 2 ? 40000 : 16000; }
 
 }  // namespace
 
@@ -251,11 +228,7 @@ bool launch_conv_small(const ConvMfmaArgs &a, hipStream_t s) {
     const int M = a.B * a.Ho * a.Wo;
     // tap of K step `st` in the weight array: natural order, or the stride-2 strip kernel's 0,2,6,8,4,1,7,3,5 (not for its 64 -> 64 form)
     const bool s2_order = a.stride == 2 && !(a.Cin == 64 && a.Cout == 64);
-    unsigned long long taps = s2_order ? 0x537148620ull : 0x876543210ull;
-#ifdef FRT_ABLATE
-    static const int abl = frt_tuning_env("FRT_CONV_SMALL_ABL") ? atoi(frt_tuning_env("FRT_CONV_SMALL_ABL")) : 0;
-    taps |= (unsigned long long)(abl & 3) << 40;
-#endif
+    const unsigned long long taps = s2_order ? 0x537148620ull : 0x876543210ull;
     const half_t *wfrag = a.stride == 1 ? a.wf : a.wf2;
     const bool scf = a.mode == EPI_BN_ADD_BN && a.scx;
     // Four waves, one pixel tile, ring of 3.  (Measured and not kept: 8 waves with every load of the launch in flight at once (ring of 5),
@@ -265,10 +238,8 @@ bool launch_conv_small(const ConvMfmaArgs &a, hipStream_t s) {
     // kept: the pixel operand fetched as whole 128-byte chunks of 8 pixels per load (8 cache lines per instruction instead of the gather's
     // 32) and transposed into MFMA fragments through a wave-private LDS tile, with 1 / 2 / 4 tiles per workgroup: bit-identical results,
     // 430 / 659 us (1 face), 504 / 716 us (4 faces), 16 - 32 faces 1.3 - 3.1 ms per pass (profiles/r03/r03x_small_lds.txt).)
-    static const int nc_env = frt_tuning_env("FRT_CONV_SMALL_NC") ? atoi(frt_tuning_env("FRT_CONV_SMALL_NC")) : 0;
     const int wgs = (M + 31) / 32 * (a.Cout / 32);
-    int nc = wgs > 256 && a.Cout % 64 == 0 ? 2 : 1;  // more one-block units than CUs: two cout blocks per workgroup share the pixel fragments
-    if (nc_env == 1 || (nc_env == 2 && a.Cout % 64 == 0)) nc = nc_env;
+    const int nc = wgs > 256 && a.Cout % 64 == 0 ? 2 : 1;  // more one-block units than CUs: two cout blocks per workgroup share the pixel fragments
     // (four cout blocks per workgroup, ring of 2: 8 / 12 / 16 / 32 faces 0.86 / 1.00 / 1.04 / 1.61 ms per pass against 0.73 / 0.86 / 0.91 / 1.19 -
     //  from ~ 10 faces on the strip kernels win, profiles/r03/r03z_small_nc4.txt)
     if (nc == 2) {

@@ -717,42 +717,28 @@ void launch_pw(const DwPwArgs &a, hipStream_t s) {
 
 }  // namespace
 
-bool det_mfma_enabled() {
-    static const bool use_mfma = [] {
-        const char *e = frt_tuning_env("FRT_DET_MFMA");
-        return !(e && e[0] == '0');
-    }();
-    return use_mfma;
-}
-
 void launch_dwpw(const DwPwArgs &a, hipStream_t s) {
-    if (det_mfma_enabled() && launch_dwpw_mfma(a, s)) return;  // fp32 matrix-core kernels (kernels_det_mfma.hip); scalar kernels = generic fallback
+    if (launch_dwpw_mfma(a, s)) return;  // fp32 matrix-core kernels (kernels_det_mfma.hip); scalar kernels = generic fallback
     if (!a.wd) return launch_pw(a, s);
     const long total = (long)a.B * a.Ho * a.Wo;
     const long blocks = (total + 255) / 256;
-    // stride-1 blocks whose one channel tile covers every output channel: four pixels of a row per thread
-    static const bool row4 = !(frt_tuning_env("FRT_DWPW_ROW4") && frt_tuning_env("FRT_DWPW_ROW4")[0] == '0');
     // the 32 -> 32 block at a few frames per call: thread = pixel with branch-free taps.  Measured per launch (us), dwpw_row4_kernel / this:
     // 29.3 / 12.7 at 1 frame and 29.3 / 17.4 at 2 (two 16-channel tiles over grid.y), 29.8 / 21.3 at 4 (one tile); 31 / 40 at 8 (nine dword
     // loads per pixel and channel: the texture path saturates at ~ 9 lanes per CU and clock)
-    static const bool pixs = !(frt_tuning_env("FRT_DWPW_PIXS") && frt_tuning_env("FRT_DWPW_PIXS")[0] == '0');
-    if (pixs && !a.add && a.Cout == 32 && a.Cin == 32 && blocks <= 512 && (long)a.B * a.Cin * a.H * a.W * 4 < (1L << 31)) {
+    if (!a.add && a.Cout == 32 && a.Cin == 32 && blocks <= 512 && (long)a.B * a.Cin * a.H * a.W * 4 < (1L << 31)) {
         if (blocks <= 256) hipLaunchKernelGGL((dwpw_pixs_kernel<16, 4>), dim3((unsigned)blocks, 2), dim3(256), (size_t)a.Cin * 28 * sizeof(float), s, a);
         else hipLaunchKernelGGL((dwpw_pixs_kernel<32, 2>), dim3((unsigned)blocks, 1), dim3(256), (size_t)a.Cin * 44 * sizeof(float), s, a);
         return;
     }
-    if (row4 && a.stride == 1 && !a.add && a.H == a.Ho && a.W == a.Wo && a.W % 4 == 0 && (a.Cout == 16 || a.Cout == 32) && a.Cin <= 64) {
+    // stride-1 blocks whose one channel tile covers every output channel: four pixels of a row per thread
+    if (a.stride == 1 && !a.add && a.H == a.Ho && a.W == a.Wo && a.W % 4 == 0 && (a.Cout == 16 || a.Cout == 32) && a.Cin <= 64) {
         const long threads = (long)a.B * a.H * (a.W / 4);
         const dim3 grid((unsigned)((threads + 255) / 256));
-        static const bool mf = !(frt_tuning_env("FRT_ROW4_MFMA") && frt_tuning_env("FRT_ROW4_MFMA")[0] == '0');
-        const bool use_mf = mf && a.Cout == 32 && a.Cin % 2 == 0;
+        const bool use_mf = a.Cout == 32 && a.Cin % 2 == 0;
         const size_t lds = (size_t)a.Cin * (12 + a.Cout + (use_mf ? 32 : 0)) * sizeof(float);
         // (ring depth measured on the 8 -> 16 block: 98 / 97 / 99 us with 1 / 2 / 3 channels in flight - the kernel waits on memory 60 % of
-        //  its wave cycles but not for lack of bytes in flight; default = the shallow ring, 176 registers)
-        static const int ns16 = frt_tuning_env("FRT_ROW4_NS") ? atoi(frt_tuning_env("FRT_ROW4_NS")) : 2;
-        if (a.Cout == 16 && ns16 == 4) hipLaunchKernelGGL((dwpw_row4_kernel<16, 4>), grid, dim3(256), lds, s, a);
-        else if (a.Cout == 16 && ns16 == 3) hipLaunchKernelGGL((dwpw_row4_kernel<16, 3>), grid, dim3(256), lds, s, a);
-        else if (a.Cout == 16) hipLaunchKernelGGL((dwpw_row4_kernel<16, 2>), grid, dim3(256), lds, s, a);
+        //  its wave cycles but not for lack of bytes in flight; kept: the shallow ring, 176 registers)
+        if (a.Cout == 16) hipLaunchKernelGGL((dwpw_row4_kernel<16, 2>), grid, dim3(256), lds, s, a);
         else if (use_mf) hipLaunchKernelGGL((dwpw_row4_kernel<32, 2, true>), grid, dim3(256), lds, s, a);
         else hipLaunchKernelGGL((dwpw_row4_kernel<32, 2>), grid, dim3(256), lds, s, a);
         return;
@@ -784,8 +770,8 @@ void launch_dwpw(const DwPwArgs &a, hipStream_t s) {
 }
 
 void launch_conv3x3_multi(const Conv3Args *a, int n, hipStream_t s) {
-    if (det_mfma_enabled() && launch_conv3x3_split(a, n, s)) return;  // fp16 hi/lo split on the fp16 matrix cores (kernels_det_conv3h.hip)
-    if (det_mfma_enabled() && launch_conv3x3_mfma(a, n, s)) return;  // fp32 matrix-core kernel (kernels_det_mfma.hip)
+    if (launch_conv3x3_split(a, n, s)) return;  // fp16 hi/lo split on the fp16 matrix cores (kernels_det_conv3h.hip)
+    if (launch_conv3x3_mfma(a, n, s)) return;  // fp32 matrix-core kernel (kernels_det_mfma.hip)
     Conv3Multi mm;
     long max_total = 0;
     int cout = a[0].Cout;
@@ -798,8 +784,7 @@ void launch_conv3x3_multi(const Conv3Args *a, int n, hipStream_t s) {
     const bool two_out = a[0].out2 != nullptr;  // the split must fall on a channel-tile boundary: 16-channel tiles
     // a few frames: the LDS-weight variant (bit-identical).  Measured per launch, conv3x3_kernel<16> / this: 22.4 / 10.7 us at 1 frame (8-channel
     // tiles, all 16 input channels' taps in flight), 23.4 / 16.0 at 4 frames (16-channel tiles), equal at 8, 43 / 60 at 32
-    static const int ldsw = frt_tuning_env("FRT_C3_LDSW") ? atoi(frt_tuning_env("FRT_C3_LDSW")) : 1;  // 0: off, 2: at every batch size
-    bool ldsw_ok = ldsw && cout % 16 == 0 && (ldsw == 2 || gx <= 128);
+    bool ldsw_ok = cout % 16 == 0 && gx <= 128;
     for (int i = 0; i < n; ++i) ldsw_ok = ldsw_ok && a[i].Cin == 16 && a[i].Cout == cout && !(reinterpret_cast<uintptr_t>(a[i].w) & 15);
     if (ldsw_ok) {
         if (gx <= 32) hipLaunchKernelGGL((conv3x3_ldsw_kernel<8, 16>), dim3(gx, cout / 8, n), dim3(256), (size_t)16 * 9 * 8 * sizeof(float), s, mm);
@@ -817,7 +802,7 @@ void launch_conv3x3_multi(const Conv3Args *a, int n, hipStream_t s) {
 void launch_conv3x3(const Conv3Args &a, hipStream_t s) { launch_conv3x3_multi(&a, 1, s); }
 
 bool launch_det_conv1_u8(const uint8_t *frames, size_t row_stride, size_t frame_stride, const Conv3Args &a, hipStream_t s) {
-    if (a.Cin != 3 || a.Cout != 8 || a.stride != 2 || frt_tuning_env("FRT_DET_NO_FUSED_INPUT")) return false;
+    if (a.Cin != 3 || a.Cout != 8 || a.stride != 2) return false;
     const long total = (long)a.B * a.Ho * a.Wo;
     hipLaunchKernelGGL(det_conv1_u8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, row_stride, frame_stride, a);
     return true;
@@ -831,11 +816,8 @@ void launch_heads_multi(const HeadArgs *a, int n, hipStream_t s) {
         max_total = max_total > (long)a[i].B * a[i].H * a[i].W ? max_total : (long)a[i].B * a[i].H * a[i].W;
     }
     for (int i = n; i < 3; ++i) mm.p[i] = a[0];
-    static const int unr = frt_tuning_env("FRT_HEADS_UNROLL") ? atoi(frt_tuning_env("FRT_HEADS_UNROLL")) : 16;  // (tuning build: input channels' loads in flight)
     const dim3 grid((unsigned)((max_total + 255) / 256), 1, n);
-    if (unr == 64) hipLaunchKernelGGL(heads_kernel<64>, grid, dim3(256), 0, s, mm);
-    else if (unr == 32) hipLaunchKernelGGL(heads_kernel<32>, grid, dim3(256), 0, s, mm);
-    else hipLaunchKernelGGL(heads_kernel<16>, grid, dim3(256), 0, s, mm);
+    hipLaunchKernelGGL(heads_kernel<16>, grid, dim3(256), 0, s, mm);  // 16 input channels' loads in flight
 }
 
 void launch_heads(const HeadArgs &a, hipStream_t s) { launch_heads_multi(&a, 1, s); }

@@ -298,29 +298,20 @@ bool launch_conv3x3_mfma(const Conv3Args *a, int n, hipStream_t s) {
     }
     for (int i = n; i < 4; ++i) mm.base[i] = base;  // unused levels start past the end: never selected
     const int cin = a[0].Cin, cout = a[0].Cout;
-    const int kc = cin == 16 ? 16 : 32;
     // 16 -> 16 convs: 8 MFMAs per step cannot hide a step's fixed costs (measured 51 us against 31 us for the scalar kernel)
     // (With the few tiles of ONE frame it is the other way round - 10 us against 23, profiles/r03/r03q_det_b1_switches.txt - but switching by
     //  batch size would give a frame other last bits in its scores alone than in a batch: tests/test_gpu_detector.py holds the detector to
     //  bit-identical outputs whatever the batch.)
-    if (cin == 16 && !frt_tuning_env("FRT_C3_FORCE16")) return false;
+    if (cin == 16) return false;
+    constexpr int kc = 32;
     if (cout > 64 || cout < 16 || cin % kc || a[0].wm_kc != kc) return false;
     const int cb = cout > 32 ? 2 : 1;
     if (a[0].wm_cpad != cb * 32) return false;
-    static const int wg_per_cu = [] {
-        const char *e = frt_tuning_env("FRT_C3_WG_PER_CU");
-        return e ? atoi(e) : 2;
-    }();
-    int grid = 256 * wg_per_cu;
+    int grid = 256 * 2;  // two workgroups per CU
     if (grid > base) grid = base;
     const int tiles_per_wg = (base + grid - 1) / grid;
     const size_t lds = (size_t)(2 * 180 + 3 * cb * 32) * (kc + 4) * sizeof(float);
-    if (kc == 16) {
-        if (cb == 2) hipLaunchKernelGGL((conv3x3_mfma_kernel<2, 16>), dim3(grid), dim3(256), lds, s, mm, tiles_per_wg);
-        else hipLaunchKernelGGL((conv3x3_mfma_kernel<1, 16>), dim3(grid), dim3(256), lds, s, mm, tiles_per_wg);
-    } else {
-        if (cb == 2) hipLaunchKernelGGL((conv3x3_mfma_kernel<2, 32>), dim3(grid), dim3(256), lds, s, mm, tiles_per_wg);
-        else hipLaunchKernelGGL((conv3x3_mfma_kernel<1, 32>), dim3(grid), dim3(256), lds, s, mm, tiles_per_wg);
-    }
+    if (cb == 2) hipLaunchKernelGGL((conv3x3_mfma_kernel<2, 32>), dim3(grid), dim3(256), lds, s, mm, tiles_per_wg);
+    else hipLaunchKernelGGL((conv3x3_mfma_kernel<1, 32>), dim3(grid), dim3(256), lds, s, mm, tiles_per_wg);
     return true;
 }

@@ -29,9 +29,6 @@
 
 namespace {
 
-#ifndef FRT_C3H_ABL
-#define FRT_C3H_ABL 0   // timing ablations of tools/ubench/det_conv3h_bench.hip (wrong results by design): 1 no tap loop, 2 no patch staging,
-#endif                  // 4 no weight staging, 8 no output stores, 16 no barriers
 constexpr int TS = 16;                    // tile width (output pixels); tile height 8
 constexpr int TH = 8;
 constexpr int PS = TS + 2;                // patch width
@@ -198,8 +195,8 @@ __global__ __launch_bounds__(256) void conv3x3_split_kernel(Conv3H mm) {
         // (one chunk per tile: the weights in LDS are the next step's too unless the pyramid level changes)
         const bool new_w = NCH > 1 || (v1 && lv_of(s1.t) != lv_of(s0.t));
         if (v1) {
-            if (!(FRT_C3H_ABL & 2)) fetch_patch(s1.t, s1.c);
-            if (new_w && !(FRT_C3H_ABL & 4)) fetch_weights(lv_of(s1.t), s1.c);
+            fetch_patch(s1.t, s1.c);
+            if (new_w) fetch_weights(lv_of(s1.t), s1.c);
         }
         const half_t *pb_ = pbuf + s0.pc * PATCH_H;
         auto read_frag = [&](int tap, int i, half8 &dst) {   // fragment i of a tap: 0 .. 2 NCB - 1 weights (cb, hi | lo), then b_hi, b_lo
@@ -209,13 +206,11 @@ __global__ __launch_bounds__(256) void conv3x3_split_kernel(Conv3H mm) {
             else
                 dst = *reinterpret_cast<const half8 *>(pb_ + bbase + (kh * PS + kw) * ROWH + 16 * (i - 2 * NCB));
         };
-        if (!(FRT_C3H_ABL & 1)) {
 #pragma unroll
         for (int i = 0; i < NF; ++i) read_frag(0, i, fr[0][i]);
         __builtin_amdgcn_sched_barrier(0);
-        }
 #pragma unroll
-        for (int tap = 0; tap < ((FRT_C3H_ABL & 1) ? 0 : 9); ++tap) {
+        for (int tap = 0; tap < 9; ++tap) {
             half8(&f)[NF] = fr[tap & 1];
             half8(&n)[NF] = fr[(tap + 1) & 1];
             const half8 bh = f[2 * NCB], bl = f[2 * NCB + 1];
@@ -259,17 +254,17 @@ __global__ __launch_bounds__(256) void conv3x3_split_kernel(Conv3H mm) {
                     const int co = cb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hi;
                     float v = acc[cb][e] + sb[co];
                     if (a.relu) v = fmaxf(v, 0.f);
-                    if (inside && co < cout_l && (!(FRT_C3H_ABL & 8) || v == 12345.678f)) (co < split_l ? o1 : o2)[co * HoWo] = v;
+                    if (inside && co < cout_l) (co < split_l ? o1 : o2)[co * HoWo] = v;
                     acc[cb][e] = 0.f;
                 }
         }
         if (!v1) break;
-        if (!(FRT_C3H_ABL & 2)) store_patch(pbuf + s1.pc * PATCH_H);  // the other patch buffer: its readers finished a step ago
+        store_patch(pbuf + s1.pc * PATCH_H);  // the other patch buffer: its readers finished a step ago
         if (new_w) {
-            if (!(FRT_C3H_ABL & 16)) __syncthreads();                  // everybody is done with this step's weights
-            if (!(FRT_C3H_ABL & 4)) store_weights();
+            __syncthreads();  // everybody is done with this step's weights
+            store_weights();
         }
-        if (!(FRT_C3H_ABL & 16)) __syncthreads();
+        __syncthreads();
         s0 = s1;
         s1 = advance(s1);
     }
@@ -290,8 +285,7 @@ void launch_split(const Conv3H &mm, int total, hipStream_t s, int cout_groups = 
 
 // Up to 3 same-shaped stride-1 problems with Cin == 64 or 16 in one launch.  false: shape not covered / split weights absent.
 bool launch_conv3x3_split(const Conv3Args *a, int n, hipStream_t s) {
-    static const bool off = frt_tuning_env("FRT_DET_SPLIT") && frt_tuning_env("FRT_DET_SPLIT")[0] == '0';
-    if (off || n < 1 || n > 3) return false;
+    if (n < 1 || n > 3) return false;
     Conv3H mm;
     int base = 0;
     for (int i = 0; i < 3; ++i) {
@@ -311,9 +305,8 @@ bool launch_conv3x3_split(const Conv3Args *a, int n, hipStream_t s) {
     if (a[0].Cin == 64) {
         // a few frames per call: fewer tiles than CUs - the 64 output channels as two workgroups of 32 (same accumulation order per channel:
         // bit-identical; every workgroup stages half the weights and the whole patch)
-        static const int small_tiles = frt_tuning_env("FRT_C3H_SPLIT_TILES") ? atoi(frt_tuning_env("FRT_C3H_SPLIT_TILES")) : 384;
         if (one) launch_split<4, 1>(mm, base, s);
-        else if (base <= small_tiles) launch_split<4, 1>(mm, base, s, 2);
+        else if (base <= 384) launch_split<4, 1>(mm, base, s, 2);
         else launch_split<4, 2>(mm, base, s);
     } else {
         if (one) launch_split<1, 1>(mm, base, s);

@@ -103,15 +103,7 @@ __global__ __launch_bounds__(64 * NPW * NCW) void dwpw_mfma_kernel(DwPwArgs a, i
     // ---- depthwise role: one 4-pixel segment, CH_PASS-strided channels
     const int seg = threadIdx.x % SEGS, chl = threadIdx.x / SEGS;
     const PixMap ms = map_pixel<MODE2D, TP>(lid, seg * 4, a.B, a.Ho, a.Wo, tiles_x, tiles_y);
-#ifdef FRT_ABLATE
-    // timing build, linear tiles only (tiles_x is unused there; FRT_DWPW_ABLATE): bit 0 no output stores, bit 1 every workgroup reads the
-    // first rows of image 0 (cache-resident input).  Round 4, 128 -> 128 block at 40x40, 32 frames: 45 us -> 44 (no stores) / 44 (cached
-    // input) / 38 (both) in the ablation build - the launch is not memory-bound; profiles/r04/r04o_det_ablations.txt
-    const int abl = MODE2D ? 0 : tiles_x;
-    const float *inb = a.in + (long)((ms.ok && !(abl & 2)) ? ms.b : 0) * a.Cin * HW;
-#else
     const float *inb = a.in + (long)(ms.ok ? ms.b : 0) * a.Cin * HW;
-#endif
     int roff[3];
     bool rok[3];
 #pragma unroll
@@ -119,9 +111,6 @@ __global__ __launch_bounds__(64 * NPW * NCW) void dwpw_mfma_kernel(DwPwArgs a, i
         const int iy = ms.oy * STRIDE - 1 + k;
         rok[k] = ms.ok && iy >= 0 && iy < a.H;
         roff[k] = rok[k] ? iy * a.W + ms.ox * STRIDE : 0;
-#ifdef FRT_ABLATE
-        if (abl & 2) roff[k] = rok[k] ? (iy % 3) * a.W + ms.ox * STRIDE : 0;
-#endif
     }
     const bool left_ok = ms.ox > 0;                            // column ox*STRIDE - 1 exists
     const bool right_ok = STRIDE == 1 && ms.ox + 4 < a.W;      // column ox + 4 exists (stride 1 only)
@@ -406,9 +395,6 @@ __global__ __launch_bounds__(64 * NPW * NCW) void dwpw_mfma_kernel(DwPwArgs a, i
                 const int co = co_base + cb * 32 + (e & 3) + 8 * (e >> 2) + 4 * hi;
                 float v = acc[cb][e] + bq[cb][e];
                 if (a.relu) v = fmaxf(v, 0.f);
-#ifdef FRT_ABLATE
-                if ((abl & 1) && v != 12345.678f) continue;
-#endif
                 ob[(long)co * HoWo] = v;
             }
         return;
@@ -421,9 +407,6 @@ __global__ __launch_bounds__(64 * NPW * NCW) void dwpw_mfma_kernel(DwPwArgs a, i
             if (co < a.Cout) {
                 float v = acc[cb][e] + bq[cb][e];
                 if (a.relu) v = fmaxf(v, 0.f);
-#ifdef FRT_ABLATE
-                if ((abl & 1) && v != 12345.678f) continue;
-#endif
                 ob[(long)co * HoWo] = v;
             }
         }
@@ -639,48 +622,42 @@ void launch_fused(const DwPwArgs &a, hipStream_t s) {
     } else {
         nblocks = ((long)a.B * a.Ho * a.Wo + TP - 1) / TP;
     }
-#ifdef FRT_ABLATE
-    if (!MODE2D) tiles_x = frt_tuning_env("FRT_DWPW_ABLATE") ? atoi(frt_tuning_env("FRT_DWPW_ABLATE")) : 0;
-#endif
     const unsigned cgroups = (unsigned)((a.Cout + 32 * NCW * CBW - 1) / (32 * NCW * CBW));
     const dim3 grid((unsigned)nblocks, cgroups);
-    static const bool split = !(frt_tuning_env("FRT_DET_PW_SPLIT") && frt_tuning_env("FRT_DET_PW_SPLIT")[0] == '0');
-    if constexpr (KC == 32) {  // (the 16-channel block with 128-pixel tiles measured slower split: 113 vs 108 us, scattered 2-byte LDS stores)
-        if (split && a.wph) {  // pointwise product on the fp16 matrix cores (hi/lo split, fp32-class accuracy)
-            const size_t ldsh = (size_t)2 * TP * (2 * KC + 8) * sizeof(half_t);
-            // a frame or two (every workgroup alone on its CU): PRE chunks' loads in flight.  Measured per launch at one frame: see DESIGN 3.9
-            static const int pre = frt_tuning_env("FRT_DWPW_PRE") ? atoi(frt_tuning_env("FRT_DWPW_PRE")) : 1;
-            if constexpr (!MODE2D && NPW <= 2) {
-                const int nchunk = a.Cin / KC;
-                if (pre && nblocks * cgroups <= (pre == 2 ? 100000 : 256) && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0) {
-                    if (nchunk % 4 == 0) {
-                        if (a.stride == 1)
-                            hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 1, MODE2D, true, 4>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
-                        else
-                            hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 2, MODE2D, true, 4>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
-                        return;
-                    }
-                    if (nchunk % 2 == 0) {
-                        if (a.stride == 1)
-                            hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 1, MODE2D, true, 2>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
-                        else
-                            hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 2, MODE2D, true, 2>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
-                        return;
-                    }
+    if constexpr (KC == 32) {  // pointwise product on the fp16 matrix cores (hi/lo split, fp32-class accuracy; launch_dwpw_mfma checked a.wph)
+        // (the 16-channel block with 128-pixel tiles measured slower split: 113 vs 108 us, scattered 2-byte LDS stores)
+        const size_t ldsh = (size_t)2 * TP * (2 * KC + 8) * sizeof(half_t);
+        // a frame or two (every workgroup alone on its CU): four or two chunks' loads in flight.  Measured per launch at one frame: see DESIGN 3.9
+        if constexpr (!MODE2D && NPW <= 2) {
+            const int nchunk = a.Cin / KC;
+            if (nblocks * cgroups <= 256 && (reinterpret_cast<uintptr_t>(a.in) & 15) == 0) {
+                if (nchunk % 4 == 0) {
+                    if (a.stride == 1)
+                        hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 1, MODE2D, true, 4>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
+                    else
+                        hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 2, MODE2D, true, 4>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
+                    return;
+                }
+                if (nchunk % 2 == 0) {
+                    if (a.stride == 1)
+                        hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 1, MODE2D, true, 2>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
+                    else
+                        hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 2, MODE2D, true, 2>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
+                    return;
                 }
             }
-            if (a.stride == 1)
-                hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 1, MODE2D, true>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
-            else
-                hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 2, MODE2D, true>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
-            return;
         }
+        if (a.stride == 1)
+            hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 1, MODE2D, true>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
+        else
+            hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 2, MODE2D, true>), grid, dim3(64 * NPW * NCW), ldsh, s, a, tiles_x, tiles_y);
+    } else {  // 8- and 16-channel chunks: fp32 MFMA
+        const size_t lds = (2 * (size_t)KC * TP) * sizeof(float);
+        if (a.stride == 1)
+            hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 1, MODE2D>), grid, dim3(64 * NPW * NCW), lds, s, a, tiles_x, tiles_y);
+        else
+            hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 2, MODE2D>), grid, dim3(64 * NPW * NCW), lds, s, a, tiles_x, tiles_y);
     }
-    const size_t lds = (2 * (size_t)KC * TP) * sizeof(float);
-    if (a.stride == 1)
-        hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 1, MODE2D>), grid, dim3(64 * NPW * NCW), lds, s, a, tiles_x, tiles_y);
-    else
-        hipLaunchKernelGGL((dwpw_mfma_kernel<NPW, NCW, KC, CBW, 2, MODE2D>), grid, dim3(64 * NPW * NCW), lds, s, a, tiles_x, tiles_y);
 }
 
 }  // namespace
@@ -689,7 +666,7 @@ void launch_fused(const DwPwArgs &a, hipStream_t s) {
 bool launch_dwpw_mfma(const DwPwArgs &a, hipStream_t s) {
     if ((a.Cin & 1) || a.Cout < 16) return false;
     if (!a.wd) {
-        if (a.stride != 1 || a.H != a.Ho || a.W != a.Wo) return false;
+        if (a.stride != 1 || a.H != a.Ho || a.W != a.Wo || !a.wph || a.Cin % 16) return false;  // (every 1x1 op of the detectors carries wph)
         const long total = (long)a.B * a.H * a.W;
         const int n_pix_groups = (int)((total + 31) / 32);
         // one wave covers all output channels while that still fills the chip, otherwise 32 channels per wave
@@ -700,14 +677,8 @@ bool launch_dwpw_mfma(const DwPwArgs &a, hipStream_t s) {
         // (persistent: two 256-thread workgroups per CU for the wide variant (180 registers), four for the narrow one (104))
         const unsigned cap = wide ? 3 * 256 : 4 * 256;  // (round 5: 154 / 114 registers)
         const unsigned grid = (unsigned)std::min<long>((waves + 3) / 4, cap);
-        static const bool split = !(frt_tuning_env("FRT_DET_PW_SPLIT") && frt_tuning_env("FRT_DET_PW_SPLIT")[0] == '0');
-        if (split && a.wph && a.Cin % 16 == 0) {
-            if (wide) hipLaunchKernelGGL((pw_mfma_kernel<2, true>), dim3(grid), dim3(256), 0, s, a, n_pix_groups);
-            else hipLaunchKernelGGL((pw_mfma_kernel<1, true>), dim3(grid), dim3(256), 0, s, a, n_pix_groups);
-            return true;
-        }
-        if (wide) hipLaunchKernelGGL((pw_mfma_kernel<2>), dim3(grid), dim3(256), 0, s, a, n_pix_groups);
-        else hipLaunchKernelGGL((pw_mfma_kernel<1>), dim3(grid), dim3(256), 0, s, a, n_pix_groups);
+        if (wide) hipLaunchKernelGGL((pw_mfma_kernel<2, true>), dim3(grid), dim3(256), 0, s, a, n_pix_groups);
+        else hipLaunchKernelGGL((pw_mfma_kernel<1, true>), dim3(grid), dim3(256), 0, s, a, n_pix_groups);
         return true;
     }
     if (a.add || (a.stride != 1 && a.stride != 2) || !a.wd12) return false;
@@ -720,7 +691,8 @@ bool launch_dwpw_mfma(const DwPwArgs &a, hipStream_t s) {
     // (A persistent, 3-stage software-pipelined variant of this kernel was also tried: slower on every block - fewer, fatter
     // waves hide the load latency worse than three small resident workgroups per CU do.)
     if (launch_dwpw_wave(a, s)) return true;
-    if (a.Cout <= 32 && a.Cin <= 32 && a.stride == 1 && !frt_tuning_env("FRT_DWPW_FORCE_MFMA")) return false;
+    if (a.Cout <= 32 && a.Cin <= 32 && a.stride == 1) return false;
+    if (a.Cin % 32 == 0 && !a.wph) return false;  // the 32-channel chunk kernels run split only (wph: every op with Cin % 16 == 0 has it)
     const long total = (long)a.B * a.Ho * a.Wo;
     const bool big = a.Wo >= 64 && (a.Wo % 16) == 0 && (a.Ho % 8) == 0;
     if (a.Cout <= 32) {
@@ -731,25 +703,12 @@ bool launch_dwpw_mfma(const DwPwArgs &a, hipStream_t s) {
         return true;
     }
     if (a.Cin % 32) return false;
-    if (a.Cout == 64 && total >= 128L * 512) {
-        static const int c64 = frt_tuning_env("FRT_DWPW_C64") ? atoi(frt_tuning_env("FRT_DWPW_C64")) : 1;  // measured: 64-px linear tiles, 2x2 waves: 46/60 us vs 54/71 for 8x16 tiles
-        if (c64 == 1) launch_fused<2, 2, 32, 1, false>(a, s);
-        else if (c64 == 2) launch_fused<1, 2, 32, 1, false>(a, s);
-        else if (c64 == 3) big ? launch_fused<4, 1, 16, 2, true>(a, s) : launch_fused<4, 1, 16, 2, false>(a, s);
-        else big ? launch_fused<4, 1, 32, 2, true>(a, s) : launch_fused<4, 1, 32, 2, false>(a, s);
-    } else if (a.Cout == 128 || (a.Cout == 64)) {
-        if (a.Cout == 128) {
-            static const int small = frt_tuning_env("FRT_DWPW_SMALL") ? atoi(frt_tuning_env("FRT_DWPW_SMALL")) : 1;
-            if (small == 1) launch_fused<1, 4, 32, 1, false>(a, s);  // (KC = 64, half as many rounds, measured 52 vs 46 us: registers)
-            else if (small == 2) launch_fused<1, 2, 32, 2, false>(a, s);
-            else if (small == 3) launch_fused<1, 2, 32, 1, false>(a, s);
-            else launch_fused<2, 2, 32, 2, false>(a, s);
-        }
-        else launch_fused<2, 2, 32, 1, false>(a, s);
+    if (a.Cout == 64) {
+        launch_fused<2, 2, 32, 1, false>(a, s);  // measured: 64-px linear tiles, 2x2 waves: 46/60 us vs 54/71 for 8x16 tiles
+    } else if (a.Cout == 128) {
+        launch_fused<1, 4, 32, 1, false>(a, s);  // (KC = 64, half as many rounds, measured 52 vs 46 us: registers)
     } else if (a.Cout == 256) {
-        static const int small = frt_tuning_env("FRT_DWPW_SMALL") ? atoi(frt_tuning_env("FRT_DWPW_SMALL")) : 1;
-        if (small == 2) launch_fused<1, 2, 32, 2, false>(a, s);
-        else if (small == 3 || total <= 2048) launch_fused<1, 2, 32, 1, false>(a, s);  // a frame or two: twice the workgroups (17 + 24 -> 12 + 18 us)
+        if (total <= 2048) launch_fused<1, 2, 32, 1, false>(a, s);  // a frame or two: twice the workgroups (17 + 24 -> 12 + 18 us)
         else launch_fused<1, 4, 32, 2, false>(a, s);
     } else {
         return false;

@@ -89,8 +89,8 @@ python tools/prof_match_small.py 2>/dev/null | grep queries > "$OUT/${TAG}_match
 for P in clock_probe occ_probe mfma_f32_order mfma_pk_overlap; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -w -o /tmp/$P "$ROOT/tools/ubench/$P.hip" 2>/dev/null && timeout 120 /tmp/$P > "$OUT/${TAG}_$P.txt" 2>&1
 done
-# 5. round 4: the detector alone (kernel trace of tools/prof_det.py at 32 and 4 frames), dwpw_wave_kernel against dwpw_mfma_kernel bit for bit
-#    (tuning build), and the stand-alone harness of the wave kernel on its three shapes
+# 5. round 4: the detector alone (kernel trace of tools/prof_det.py at 32 and 4 frames) and the stand-alone harness of the wave kernel on its
+#    three shapes
 cd /tmp
 for B in 32 4 1; do
   rm -rf /tmp/prof_det && mkdir -p /tmp/prof_det
@@ -98,10 +98,8 @@ for B in 32 4 1; do
   cp "$(find /tmp/prof_det -name '*kernel_stats.csv' | head -1)" "$OUT/${TAG}_det_kernel_stats_b$B.csv" 2>/dev/null
 done
 cd "$ROOT"
-python tools/dwpw_wave_check.py 2>/dev/null | grep -v amdgpu.ids > "$OUT/${TAG}_dwpw_wave_check.txt"
-FRT_LIB=$ROOT/face-recognition-cpp-tensorrt_amd/libfrt_tuning.so FRT_DET_STEM_CHECK=1 python tools/stem_check_run.py 2>&1 | grep "stem check" > "$OUT/${TAG}_stem_check.txt"
-/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -DFRT_TUNING -w -Iface-recognition-cpp-tensorrt_amd/csrc -o /tmp/dwpw_wave_bench tools/ubench/dwpw_wave_bench.hip 2>/dev/null &&
-  for A in "32" "2" "32 64 80" "2 64 80" "32 256 20" "2 256 20"; do FRT_DWPW_WAVE_ANYB=1 timeout 60 /tmp/dwpw_wave_bench $A; done > "$OUT/${TAG}_dwpw_wave_bench.txt" 2>&1
+/opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 -w -Iface-recognition-cpp-tensorrt_amd/csrc -o /tmp/dwpw_wave_bench tools/ubench/dwpw_wave_bench.hip 2>/dev/null &&
+  for A in "32" "32 64 80" "32 256 20"; do timeout 60 /tmp/dwpw_wave_bench $A; done > "$OUT/${TAG}_dwpw_wave_bench.txt" 2>&1
 # 6. round 5: detector PMC passes (waves, cycles, waits, instruction mix, HBM bytes) over the detector alone; probes and harnesses
 {
   echo "rocprofv3 --pmc (separate passes, no trace domains) over tools/prof_det.py 32 2 (detector alone, 32 frames of 640x640), medians per launch, summed over the chip."
@@ -113,18 +111,6 @@ FRT_LIB=$ROOT/face-recognition-cpp-tensorrt_amd/libfrt_tuning.so FRT_DET_STEM_CH
 [ -x tools/ubench/lds_dma_raw ] && timeout 120 tools/ubench/lds_dma_raw > "$OUT/${TAG}_lds_dma_raw.txt" 2>&1
 [ -x tools/ubench/det_conv3h_bench ] && { timeout 300 tools/ubench/det_conv3h_bench 32; timeout 120 tools/ubench/det_conv3h_bench 4; timeout 120 tools/ubench/det_conv3h_bench 1; } > "$OUT/${TAG}_det_conv3h_bench.txt" 2>&1
 [ -x tools/ubench/plane_stride ] && timeout 300 tools/ubench/plane_stride > "$OUT/${TAG}_plane_stride.txt" 2>&1
-# 7. what each stage costs the pipelined step (tuning build, FRT_PIPE_ABLATE bit 0 = no detector network, 1 = no recogniser network, 2 = no match)
-{
-  echo "bench.py --steps 60 --warmup 12 --no-cpu-baseline --no-extras, tuning build, FRT_PIPE_ABLATE (bit 0: no detector network after the first calls, bit 1: no"
-  echo "recogniser network, bit 2: no match); faces/s and ms per step; K = 4 (the metric's configuration) and K = 1"
-  for A in 0 1 2 4 5 6; do
-    for K in 4 1; do
-      printf "ablate %d  K %d  " $A $K
-      FRT_LIB=$ROOT/face-recognition-cpp-tensorrt_amd/libfrt_tuning.so FRT_PIPE_ABLATE=$A python bench.py --steps 60 --warmup 12 --faces $K --no-cpu-baseline --no-extras 2>/dev/null |
-        python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'])"
-    done
-  done
-} > "$OUT/${TAG}_stage_ablation_raw.txt" 2>&1
 for f in "$OUT"/${TAG}_det_kernel_stats_b*.csv; do echo "== $(basename $f)"; python tools/det_table.py "$f"; done > "$OUT/${TAG}_det_tables.txt" 2>&1
 # 8. round 6: the adaptive mode at 2 - 11 calls in flight (4-frame calls), the fp32 recogniser pass per layer, the two fp32-MFMA microbenchmarks
 python tools/proxy_only.py 2 3 4 5 6 8 11 2>&1 | grep depth > "$OUT/${TAG}_adaptive_depth_sweep.txt"

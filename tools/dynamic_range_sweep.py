@@ -14,7 +14,7 @@ network computes (so the fp32 oracle's embedding is the same up to rounding and 
 
 Round 5: libfrt conditions every unit's branch at load (powers of two on conv1 rows / conv2 columns + rows / the closing BatchNorm's scale, the same
 function exactly - csrc/frt_embedder.cpp), so the branch sweep is flat now (5.5e-6 from 1e-4 to 1e4, profiles/r05e_dynamic_range.json; round 3:
-4.8e-4 at 1e-4, non-finite at 1e4).  The tuning build's FRT_ARC_CONDITION=0 restores the unconditioned load for an A/B.
+4.8e-4 at 1e-4, non-finite at 1e4).  (The A/B switch back to the unconditioned load went with the tuning build)
 
     python tools/dynamic_range_sweep.py --out gpurun_out/r03_dynamic_range.json        (GPU box)
     python tools/dynamic_range_sweep.py --backbones ir100 ir_se152 --which stream --out profiles/r07/r07_deep_range.json

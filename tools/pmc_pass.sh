@@ -17,7 +17,7 @@ for disp, name, cn, val in c.execute("select dispatch_id, kernel_name, counter_n
     d[k][cn][disp] += val
 for k in d:
     import os, re
-    if re.search(os.environ.get("KFILTER", "conv_patch_kernel<2, 5, 5, false, 0, false, 7|conv64_kernel<0"), k):
+    if re.search(os.environ.get("KFILTER", "conv_patch_kernel<10, 1, 5, false, false, 7|conv64_kernel<0"), k):
         print(k, {cn: round(statistics.median(v.values())) for cn, v in d[k].items()})
 PY
 done

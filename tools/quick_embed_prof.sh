@@ -1,5 +1,5 @@
 #!/bin/bash
-# quick per-kernel table of one recogniser run under rocprofv3 (GPU box; args: env assignments to apply, e.g. FRT_CONV_ABLATE=1)
+# quick per-kernel table of one recogniser run under rocprofv3 (GPU box; args: env assignments to apply, e.g. FRT_LIB=<other libfrt.so>)
 cd /tmp && export TMPDIR=/tmp
 for E in "$@"; do
 rm -rf /tmp/pe && mkdir -p /tmp/pe

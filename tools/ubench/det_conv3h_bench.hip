@@ -13,7 +13,8 @@
 #include <vector>
 
 #include "frt_kernels.h"
-bool det_mfma_enabled() { return true; }
+// the kernels parked in tools/experiments still read A/B switches the library no longer has: always their defaults here
+static const char *frt_tuning_env(const char *) { return nullptr; }
 namespace oldk {
 #include "../experiments/det_conv3h_r04.hip"
 }

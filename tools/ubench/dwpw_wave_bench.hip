@@ -1,5 +1,5 @@
 // Stand-alone harness for dwpw_wave_kernel (kernels_det_wave.hip): the 128 -> 128 conv_dw block at 40x40 on random data, checked against a
-// plain fp32 / fp64 kernel, timed with HIP events.   hipcc -O3 -std=c++17 --offload-arch=gfx950 -DFRT_TUNING -I<csrc> dwpw_wave_bench.hip
+// plain fp32 / fp64 kernel, timed with HIP events.   hipcc -O3 -std=c++17 --offload-arch=gfx950 -I<csrc> dwpw_wave_bench.hip
 #include <hip/hip_runtime.h>
 
 #include <cmath>
