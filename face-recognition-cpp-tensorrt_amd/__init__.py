@@ -77,6 +77,11 @@ ABI = {
     "frt_matcher_gallery_append": (_i, [_vp, _vp, _i]),
     "frt_matcher_gallery_commit": (_i, [_vp]),
     "frt_matcher_num_rows": (_i, [_vp]),
+    "frt_matcher_gallery_reserve": (_i, [_vp, _i]),
+    "frt_matcher_gallery_add": (_i, [_vp, _vp, _i]),
+    "frt_matcher_gallery_add_dev": (_i, [_vp, _vp, _i]),
+    "frt_matcher_gallery_remove": (_i, [_vp, _vp, _i]),
+    "frt_matcher_edit_stats": (_i, [_vp, _vp]),
     "frt_matcher_top1_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "frt_matcher_calculate": (_i, [_vp, _vp, _i, _vp]),
     "frt_matcher_top1": (_i, [_vp, _vp, _i, _vp, _vp]),
@@ -263,6 +268,45 @@ class MatMul:
     def galleryCommit(self):
         _check(lib.frt_matcher_gallery_commit(self._h))
         self.m, self.k = int(lib.frt_matcher_num_rows(self._h)), self._pending_k
+
+    # live edits (frt_matcher_gallery_reserve / add / add_dev / remove): the gallery changes in place, no reload
+    def _edited(self):
+        self.m = int(lib.frt_matcher_num_rows(self._h))
+
+    def galleryReserve(self, rowCapacity):
+        """Room for edits up to ``rowCapacity`` rows (an add inside it allocates nothing); never shrinks."""
+        _check(lib.frt_matcher_gallery_reserve(self._h, int(rowCapacity)))
+
+    def galleryAdd(self, rows):
+        """Append float32 rows [n, numCol] (or one row); they get the indices ``m .. m + n - 1``.  Returns the first new index."""
+        a = np.ascontiguousarray(rows, np.float32).reshape(-1, self.k)
+        first = int(lib.frt_matcher_num_rows(self._h))
+        _check(lib.frt_matcher_gallery_add(self._h, _ptr(a), a.shape[0]))
+        self._edited()
+        return first
+
+    def galleryAddDev(self, rows_ptr, n):
+        """Append ``n`` fp32 rows that are resident on the device (raw address, e.g. the embeddings ``Pipeline.run_dev`` left there); the
+        rows must be complete (synchronise their producer first)."""
+        first = int(lib.frt_matcher_num_rows(self._h))
+        _check(lib.frt_matcher_gallery_add_dev(self._h, _vp(rows_ptr), int(n)))
+        self._edited()
+        return first
+
+    def galleryRemove(self, indices):
+        """Remove the rows ``indices`` (any order, duplicates count once); the rows behind them close up in order."""
+        i = np.ascontiguousarray(indices, np.int32).reshape(-1)
+        _check(lib.frt_matcher_gallery_remove(self._h, _ptr(i), i.size))
+        self._edited()
+
+    def editStats(self):
+        """Cumulative dict(rows_uploaded, rows_moved, shadow_rows_rebuilt, reallocations) of the live edits."""
+        out = (ctypes.c_long * 4)()
+        _check(lib.frt_matcher_edit_stats(self._h, out))
+        return dict(zip(("rows_uploaded", "rows_moved", "shadow_rows_rebuilt", "reallocations"), (int(v) for v in out)))
+
+    def generation(self):
+        return int(lib.frt_matcher_generation(self._h))
 
     def top1_dev(self, embeds_ptr, n, idx_ptr, sim_ptr, hip_stream=None):
         """Asynchronous, raw device addresses (queries fp32 [n][k], idx int32 [n], sim fp32 [n])."""
@@ -587,6 +631,32 @@ class ArcFaceIR50:
 
     def initMatMul(self):
         self.matmul.init(self._known[:self.classCount], self.classCount, self.outputDim)
+
+    # live enrolment (/insert/face and /delete/user without /reload): the device rows and classNames / classCount move together.  The host
+    # copy behind initKnownEmbeds / addEmbedding is not involved; a later load cycle replaces the gallery as /reload does.
+    def enrolEmbedding(self, className, embedding):
+        """One row, or rows [n, outputDim] with ``className`` a list of n names.  Returns the first new row index."""
+        e = np.ascontiguousarray(embedding, np.float32).reshape(-1, self.outputDim)
+        names = [className] if isinstance(className, (str, bytes)) or e.shape[0] == 1 and not isinstance(className, (list, tuple)) else list(className)
+        if len(names) != e.shape[0]:
+            raise ValueError("enrolEmbedding: %d names for %d rows" % (len(names), e.shape[0]))
+        if self.matmul.k == 0:  # never loaded: an empty gallery of this width first
+            self.matmul.galleryBegin(0, self.outputDim)
+            self.matmul.galleryCommit()
+        first = self.matmul.galleryAdd(e)
+        self.classNames = list(self.classNames) + names
+        self.classCount = len(self.classNames)
+        return first
+
+    def removeClass(self, className):
+        """Remove every row of ``className`` (as /delete/user does); returns how many there were."""
+        rows = [i for i, n in enumerate(self.classNames) if n == className]
+        if rows:
+            self.matmul.galleryRemove(rows)
+            gone = set(rows)
+            self.classNames = [n for i, n in enumerate(self.classNames) if i not in gone]
+            self.classCount = len(self.classNames)
+        return len(rows)
 
     def forward(self, image, outputBbox):
         image = np.ascontiguousarray(image, np.uint8)

@@ -82,8 +82,15 @@ void launch_gallery_norm16(const half_t *g16, int N, int D, int *max_norm2_bits,
 // The fp16 gallery (shadow or stored) is kept in MFMA-fragment order and padded to whole 128-row tiles (see kernels_match.hip):
 size_t gallery16_elems(int N, int D);
 bool match_screen_supported(int D);  // D the coarse kernel is instantiated for
-// fp32 rows [n_rows][D] (first row = global row row0, a multiple of 128) -> their place in the fp16 gallery (which must be zero-filled first)
+// fp32 rows [n_rows][D] (first row = global row row0) -> their place in the fp16 gallery (whose rows never written must be zero)
 void launch_rows_to_half(const float *in, long row0, long n_rows, int D, half_t *g16, hipStream_t s);
+// live gallery edits (frt_matcher_gallery_add / _remove): row-range forms of the shadow build, and the gather half of the chunked in-place
+// compaction (keys / klo / khi: frt_holes.h; the bounce buffer receives the chunk in its final layout, a copy on the same stream places it)
+void launch_gallery_shadow8_rows(const float *rows, int row0, int n_rows, uint8_t *g8, float *scale, int *max_err2_bits, int *max_norm2_bits, hipStream_t s);
+void launch_rows_norm(const float *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s);
+void launch_rows_norm16(const half_t *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s);
+void launch_gather_rows(const float *G, int D, int a, int n_rows, const int *keys, int klo, int khi, float *bounce, hipStream_t s);
+void launch_gather_rows16(const half_t *G, int D, long tile0, long n_tiles, int n_new, const int *keys, int klo, int khi, half_t *bounce, hipStream_t s);
 
 // ---------------------------------------------------------------- post-processing (kernels_post.hip)
 constexpr int DET_MAX_LEVELS = 4, DET_MAX_SIZES = 3;

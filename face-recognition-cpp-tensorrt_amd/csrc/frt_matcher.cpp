@@ -3,6 +3,220 @@
 // device every entry point that needs one fails with FRT_ERR_DEVICE.
 #include "frt_matcher.hpp"
 
+#include "frt_holes.h"
+
+// ------------------------------------------------------------------------------------------------------------- live gallery edits
+// Add and remove rows of the gallery the matcher is answering from (include/frt.h).  Every edit runs on the matcher's stream behind its
+// in-flight match stages (wait_idle), holds the object's mutex - which the pipeline takes to queue a match stage - from start to end, and
+// returns when its device work is complete: a match call sees the gallery of before or of after, never a mix.
+namespace {
+
+int round_up_tile(long rows) { return (int)((rows + 127) / 128 * 128); }
+
+void edit_checks(frt_matcher *m, const char *what) {
+    if (m->row_offset != 0) raise(FRT_ERR_INVALID, std::string(what) + ": a gallery with a row offset (a shard) is edited by reloading it");
+}
+
+// Room for `rows` rows: allocate + device copy + free (both copies exist until the copy has run).  Counts as one reallocation when there
+// were rows to carry over.
+void grow(frt_matcher *m, int rows) {
+    if (rows <= m->cap_rows) return;
+    hipStream_t s = m->stream;
+    const int N = m->N, D = m->D, cap = round_up_tile(rows);
+    const size_t cap_tiles = (size_t)cap / 128, n_tiles = ((size_t)N + 127) / 128;
+    float *new32 = nullptr;
+    half_t *new16 = nullptr, *sh16 = nullptr;
+    uint8_t *sh8 = nullptr;
+    float *sh8s = nullptr;
+    const bool shadow = !m->store16 && m->screen && m->shadow_rows > 0;  // a valid shadow moves along; a stale one is dropped
+    try {
+        if (m->store16) {
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&new16), gallery16_elems(cap, D) * sizeof(half_t)));
+            HIPCHK(hipMemsetAsync(new16 + n_tiles * 128 * D, 0, (cap_tiles - n_tiles) * 128 * D * sizeof(half_t), s));
+            if (N > 0) HIPCHK(hipMemcpyAsync(new16, m->d_g16, n_tiles * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+        } else {
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&new32), (size_t)cap * D * sizeof(float)));
+            if (N > 0) HIPCHK(hipMemcpyAsync(new32, m->d_gallery, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+            if (shadow && m->d_g8) {
+                HIPCHK(hipMalloc(reinterpret_cast<void **>(&sh8), gallery8_bytes(cap, D)));
+                HIPCHK(hipMalloc(reinterpret_cast<void **>(&sh8s), cap_tiles * 128 * sizeof(float)));
+                HIPCHK(hipMemsetAsync(sh8 + n_tiles * 128 * D, 0x80, (cap_tiles - n_tiles) * 128 * D, s));
+                HIPCHK(hipMemsetAsync(sh8s + n_tiles * 128, 0, (cap_tiles - n_tiles) * 128 * sizeof(float), s));
+                HIPCHK(hipMemcpyAsync(sh8, m->d_g8, n_tiles * 128 * D, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(sh8s, m->d_g8_scale, n_tiles * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
+            } else if (shadow) {
+                HIPCHK(hipMalloc(reinterpret_cast<void **>(&sh16), gallery16_elems(cap, D) * sizeof(half_t)));
+                HIPCHK(hipMemsetAsync(sh16 + n_tiles * 128 * D, 0, (cap_tiles - n_tiles) * 128 * D * sizeof(half_t), s));
+                HIPCHK(hipMemcpyAsync(sh16, m->d_g16, n_tiles * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+            }
+        }
+        HIPCHK(hipStreamSynchronize(s));
+    } catch (...) {
+        (void)hipStreamSynchronize(s);
+        for (void *p : {(void *)new32, (void *)new16, (void *)sh16, (void *)sh8, (void *)sh8s})
+            if (p) (void)hipFree(p);
+        throw;
+    }
+    if (m->store16) {
+        if (m->d_g16) (void)hipFree(m->d_g16);
+        m->d_g16 = new16;
+    } else {
+        if (m->d_gallery) (void)hipFree(m->d_gallery);
+        m->d_gallery = new32;
+        for (void *p : {(void *)m->d_g8, (void *)m->d_g8_scale, (void *)m->d_g16})
+            if (p) (void)hipFree(p);
+        m->d_g8 = sh8;
+        m->d_g8_scale = sh8s;
+        m->d_g16 = sh16;
+        m->shadow_rows = shadow ? cap : 0;
+    }
+    m->cap_rows = cap;
+    if (N > 0) ++m->edit_stats[3];
+}
+
+// the tail of every edit: sizes, scratch, generation; the stream is idle when this returns
+void finish_edit(frt_matcher *m, int new_n) {
+    m->N = new_n;
+    ++m->generation;
+    m->bind_scratch();
+    if (m->q_cap > 0 && new_n > 0) m->ensure_queries(m->q_cap);  // (a grown capacity, or screening that has just begun: a pipeline call that was
+                                                                  //  queued before the edit runs its match stage without passing ensure_queries again)
+    HIPCHK(hipStreamSynchronize(m->stream));
+}
+
+void add_rows(frt_matcher *m, const void *rows, int n, bool on_device) {
+    edit_checks(m, "gallery_add");
+    if (n < 0 || (n > 0 && !rows)) raise(FRT_ERR_INVALID, "gallery_add: bad argument");
+    if (m->D <= 0) raise(FRT_ERR_INVALID, "gallery_add: the number of columns is not known yet (frt_matcher_init or gallery_begin + commit first)");
+    if (n == 0) return;
+    if ((long)m->N + n > INT32_MAX - 128) raise(FRT_ERR_CAPACITY, "gallery_add: too many rows");
+    hipStream_t s = m->stream;
+    const int N = m->N, D = m->D, new_n = N + n;
+    m->wait_idle(s);
+    if (new_n > m->cap_rows) grow(m, std::max(new_n, std::max((int)std::min((long)m->cap_rows * 3 / 2, (long)INT32_MAX - 128), m->reserve_rows)));
+    const float *src32 = reinterpret_cast<const float *>(rows);  // the new rows as fp32 ON THE DEVICE (conversion source)
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    if (m->store16) {
+        if (!on_device) {
+            const size_t need = (size_t)n * D;
+            if (need > m->edit_stage_floats) {
+                if (m->d_edit_stage) (void)hipFree(m->d_edit_stage);
+                m->d_edit_stage = nullptr;
+                m->edit_stage_floats = 0;
+                HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_edit_stage), need * sizeof(float)));
+                m->edit_stage_floats = need;
+            }
+            HIPCHK(hipMemcpyAsync(m->d_edit_stage, rows, need * sizeof(float), kind, s));
+            src32 = m->d_edit_stage;
+        }
+        launch_rows_to_half(src32, N, n, D, m->d_g16, s);
+    } else {
+        HIPCHK(hipMemcpyAsync(m->d_gallery + (size_t)N * D, rows, (size_t)n * D * sizeof(float), kind, s));
+        src32 = m->d_gallery + (size_t)N * D;
+    }
+    m->edit_stats[0] += n;
+    const bool was_screen = m->screen;
+    m->screen = new_n >= frt_matcher::SCREEN_MIN_ROWS && match_screen_supported(D);
+    if (m->screen && !was_screen) {  // the gallery has grown across the screening threshold: the one add that builds the whole shadow
+        m->N = new_n;
+        try {
+            m->build_screen_data();
+        } catch (...) {
+            m->N = N;
+            m->screen = was_screen;
+            throw;
+        }
+        if (!m->store16) m->edit_stats[2] += new_n;
+    } else if (m->screen) {  // tail update: only the new rows are converted into their places
+        if (m->store16) {
+            launch_rows_norm16(m->d_g16, N, n, D, m->d_edit_bits + 1, s);
+            HIPCHK(hipMemsetAsync(m->d_edit_bits, 0, sizeof(int), s));
+        } else if (m->d_g8 && D == 512) {
+            launch_gallery_shadow8_rows(src32, N, n, m->d_g8, m->d_g8_scale, m->d_edit_bits, m->d_edit_bits + 1, s);
+            m->edit_stats[2] += n;
+        } else {
+            launch_rows_to_half(src32, N, n, D, m->d_g16, s);
+            launch_rows_norm(m->d_gallery, N, n, D, m->d_edit_bits + 1, s);
+            HIPCHK(hipMemsetAsync(m->d_edit_bits, 0, sizeof(int), s));
+            m->edit_stats[2] += n;
+        }
+        HIPCHK(hipGetLastError());
+        m->read_bounds(true);
+    }
+    HIPCHK(hipGetLastError());
+    finish_edit(m, new_n);
+}
+
+void remove_rows(frt_matcher *m, const int32_t *idx, int n_idx) {
+    edit_checks(m, "gallery_remove");
+    if (n_idx < 0 || (n_idx > 0 && !idx)) raise(FRT_ERR_INVALID, "gallery_remove: bad argument");
+    std::vector<int> keys;
+    if (!frt_hole_keys(idx, n_idx, m->N, keys)) raise(FRT_ERR_INVALID, "gallery_remove: row index out of range");
+    if (keys.empty()) return;
+    hipStream_t s = m->stream;
+    const int N = m->N, D = m->D, nk = (int)keys.size(), new_n = N - nk, r0 = keys[0];
+    const long tile0 = r0 >> 7, new_tiles = ((long)new_n + 127) / 128, old_tiles = ((long)N + 127) / 128;
+    m->wait_idle(s);
+    if (!m->d_bounce) HIPCHK(hipMalloc(&m->d_bounce, frt_matcher::BOUNCE_BYTES));
+    if (keys.size() > m->keys_cap) {
+        if (m->d_keys) (void)hipFree(m->d_keys);
+        m->d_keys = nullptr;
+        m->keys_cap = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_keys), keys.size() * sizeof(int)));
+        m->keys_cap = keys.size();
+    }
+    HIPCHK(hipMemcpyAsync(m->d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    // the keys that fall into the destination rows [a, b): those in front of them all count, those behind them never do
+    auto key_range = [&](long a, long b, int &lo, int &hi) {
+        lo = (int)(std::lower_bound(keys.begin(), keys.end(), (int)a) - keys.begin());
+        hi = (int)(std::upper_bound(keys.begin(), keys.end(), (int)(b - 1)) - keys.begin());
+    };
+    if (m->store16) {
+        // whole destination tiles from the first hole's tile on; the gather also zeroes the padding of the new last tile
+        const long chunk = std::max<long>(1, (long)(frt_matcher::BOUNCE_BYTES / ((size_t)128 * D * sizeof(half_t))));
+        half_t *bounce = reinterpret_cast<half_t *>(m->d_bounce);
+        for (long t = tile0; t < new_tiles; t += chunk) {
+            const long nt = std::min(chunk, new_tiles - t);
+            int lo, hi;
+            key_range(t * 128, (t + nt) * 128, lo, hi);
+            launch_gather_rows16(m->d_g16, D, t, nt, new_n, m->d_keys, lo, hi, bounce, s);
+            HIPCHK(hipMemcpyAsync(m->d_g16 + (size_t)t * 128 * D, bounce, (size_t)nt * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+        }
+        if (old_tiles > new_tiles) HIPCHK(hipMemsetAsync(m->d_g16 + (size_t)new_tiles * 128 * D, 0, (size_t)(old_tiles - new_tiles) * 128 * D * sizeof(half_t), s));
+    } else {
+        const long chunk = std::max<long>(1, (long)(frt_matcher::BOUNCE_BYTES / ((size_t)D * sizeof(float))));
+        float *bounce = reinterpret_cast<float *>(m->d_bounce);
+        for (long a = r0; a < new_n; a += chunk) {
+            const long nr = std::min(chunk, (long)new_n - a);
+            int lo, hi;
+            key_range(a, a + nr, lo, hi);
+            launch_gather_rows(m->d_gallery, D, (int)a, (int)nr, m->d_keys, lo, hi, bounce, s);
+            HIPCHK(hipMemcpyAsync(m->d_gallery + (size_t)a * D, bounce, (size_t)nr * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+        }
+    }
+    HIPCHK(hipGetLastError());
+    if (new_n > r0) m->edit_stats[1] += new_n - r0;
+    // Below the threshold a fresh matcher does not screen, and neither does this one (the shadow's allocation stays for the way back up).
+    m->screen = new_n >= frt_matcher::SCREEN_MIN_ROWS && match_screen_supported(D);
+    if (m->screen && !m->store16) {
+        // the shadow from the first affected tile on, with the build's arithmetic; gerr / gmax_norm stay (maxima over a subset are no larger)
+        const long first = tile0 * 128, n_re = std::max(0L, (long)new_n - first);
+        if (m->d_g8 && D == 512) {
+            HIPCHK(hipMemsetAsync(m->d_g8 + (size_t)first * D, 0x80, (size_t)(old_tiles - tile0) * 128 * D, s));
+            HIPCHK(hipMemsetAsync(m->d_g8_scale + first, 0, (size_t)(old_tiles - tile0) * 128 * sizeof(float), s));
+            launch_gallery_shadow8_rows(m->d_gallery + (size_t)first * D, (int)first, (int)n_re, m->d_g8, m->d_g8_scale, m->d_edit_bits, m->d_edit_bits + 1, s);
+        } else {
+            HIPCHK(hipMemsetAsync(m->d_g16 + (size_t)first * D, 0, (size_t)(old_tiles - tile0) * 128 * D * sizeof(half_t), s));
+            launch_rows_to_half(m->d_gallery + (size_t)first * D, first, n_re, D, m->d_g16, s);
+        }
+        HIPCHK(hipGetLastError());
+        m->edit_stats[2] += n_re;
+    }
+    finish_edit(m, new_n);
+}
+
+}  // namespace
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------------------- matcher
@@ -32,7 +246,7 @@ void frt_matcher_destroy(frt_matcher *m) {
     }
     if (m->ev_busy) (void)hipEventDestroy(m->ev_busy);
     for (void *p : {(void *)m->d_gallery, (void *)m->d_q, (void *)m->d_sim, (void *)m->d_idx, (void *)m->d_partial, (void *)m->d_full, (void *)m->d_g16, (void *)m->d_kth,
-                    (void *)m->d_g8, (void *)m->d_g8_scale})
+                    (void *)m->d_g8, (void *)m->d_g8_scale, (void *)m->d_edit_bits, (void *)m->d_edit_stage, m->d_bounce, (void *)m->d_keys})
         if (p) (void)hipFree(p);
     m->free_screen_scratch();
     delete m;
@@ -122,6 +336,56 @@ int frt_matcher_gallery_commit(frt_matcher *m) {
             m->load_abort();
             throw;
         }
+    });
+}
+
+int frt_matcher_gallery_reserve(frt_matcher *m, int row_capacity) {
+    return guarded([&] {
+        if (!m || row_capacity < 0 || row_capacity > INT32_MAX - 128) raise(FRT_ERR_INVALID, "gallery_reserve: bad argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        use_device(m->device);
+        edit_checks(m, "gallery_reserve");
+        m->reserve_rows = std::max(m->reserve_rows, row_capacity);
+        if (m->N > 0 && row_capacity > m->cap_rows) {  // a live gallery moves now; an empty matcher allocates with its first rows
+            m->wait_idle(m->stream);
+            grow(m, row_capacity);
+            finish_edit(m, m->N);
+        }
+    });
+}
+
+int frt_matcher_gallery_add(frt_matcher *m, const float *rows, int n_rows) {
+    return guarded([&] {
+        if (!m) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        use_device(m->device);
+        add_rows(m, rows, n_rows, false);
+    });
+}
+
+int frt_matcher_gallery_add_dev(frt_matcher *m, const void *rows_dev, int n_rows) {
+    return guarded([&] {
+        if (!m) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        use_device(m->device);
+        add_rows(m, rows_dev, n_rows, true);
+    });
+}
+
+int frt_matcher_gallery_remove(frt_matcher *m, const int32_t *idx, int n_idx) {
+    return guarded([&] {
+        if (!m) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        use_device(m->device);
+        remove_rows(m, idx, n_idx);
+    });
+}
+
+int frt_matcher_edit_stats(frt_matcher *m, long out[4]) {
+    return guarded([&] {
+        if (!m || !out) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        for (int i = 0; i < 4; ++i) out[i] = m->edit_stats[i];
     });
 }
 

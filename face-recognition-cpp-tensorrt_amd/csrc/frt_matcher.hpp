@@ -32,6 +32,27 @@ struct frt_matcher {
     bool screen = false;
     bool screen_on = true;     // frt_matcher_set_screening: false = every top-1 call takes the exact fp32 scan (the shadow gallery stays resident)
     ScreenScratch scr{};
+    // ---- live edits (frt_matcher_gallery_reserve / add / remove; frt_matcher.cpp).  The stored rows, the shadow and every scratch buffer
+    //      sized by rows, tiles or blocks are allocated for cap_rows >= N rows, so an add inside the capacity allocates nothing.
+    int cap_rows = 0;       // rows the stored buffer (d_gallery, or d_g16 when store16) holds
+    int shadow_rows = 0;    // rows the shadow buffers (d_g8 + d_g8_scale, or the fp16 shadow of an fp32 gallery) hold; 0 = none.  They outlive
+                            // `screen` (a gallery that fell below the threshold keeps the allocation; its contents are then stale)
+    int reserve_rows = 0;   // floor of the next allocation (frt_matcher_gallery_reserve)
+    int scratch_rows = 0;   // cap_rows when d_partial / the tile-sized screening scratch were allocated
+    long edit_stats[4] = {};  // rows_uploaded, rows_moved, shadow_rows_rebuilt, reallocations
+    int *d_edit_bits = nullptr;     // [2]: largest error norm^2 / row norm^2 of the rows an edit converted (float bit patterns)
+    float *d_edit_stage = nullptr;  // fp16 storage: fp32 landing buffer of host rows in front of the conversion kernel
+    size_t edit_stage_floats = 0;
+    void *d_bounce = nullptr;       // BOUNCE_BYTES of the chunked compaction
+    int *d_keys = nullptr;          // the hole keys of a removal (frt_holes.h)
+    size_t keys_cap = 0;
+    static constexpr size_t BOUNCE_BYTES = (size_t)32 << 20;
+    static constexpr int SCREEN_MIN_ROWS = 32768;
+    // scr.count sits behind the flags of the CURRENT tile count (they are cleared together); the buffers hold cap_rows' tiles
+    void bind_scratch() {
+        blocks = match_top1_blocks(N, 0);
+        if (scr.tile_flags) scr.count = scr.tile_flags + ((size_t)N + 127) / 128;
+    }
     void free_screen_scratch() {
         for (void *p : {(void *)scr.q16, (void *)scr.tilemax, (void *)scr.tile_flags, (void *)scr.tile_list, (void *)scr.segmax, (void *)scr.wgmax, scr.pairs,
                         (void *)scr.ctl, (void *)scr.qkey})  // scr.count lives behind tile_flags
@@ -54,6 +75,7 @@ struct frt_matcher {
         bool active = false;
         bool f16 = false;
         int cap = 0, D = 0, rows = 0, fill = 0, cur = 0;
+        int alloc = 0;  // rows allocated: cap, or the matcher's reserve_rows when that is more
         float *d_new32 = nullptr;
         half_t *d_new16 = nullptr;
         float *h_stage[NCH] = {};
@@ -101,14 +123,15 @@ struct frt_matcher {
         ld.cap = cap;
         ld.D = cols;
         ld.rows = ld.fill = ld.cur = 0;
+        ld.alloc = cap > 0 ? std::max(cap, reserve_rows) : 0;
         if (cap > 0) {
             if (ld.f16) {
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&ld.d_new16), gallery16_elems(cap, cols) * sizeof(half_t)));
-                HIPCHK(hipMemsetAsync(ld.d_new16, 0, gallery16_elems(cap, cols) * sizeof(half_t), ld.s));  // fragment order, zero pad rows
+                HIPCHK(hipMalloc(reinterpret_cast<void **>(&ld.d_new16), gallery16_elems(ld.alloc, cols) * sizeof(half_t)));
+                HIPCHK(hipMemsetAsync(ld.d_new16, 0, gallery16_elems(ld.alloc, cols) * sizeof(half_t), ld.s));  // fragment order, zero pad rows
                 for (int i = 0; i < Load::NCH; ++i)
                     if (!ld.d_stage[i]) HIPCHK(hipMalloc(reinterpret_cast<void **>(&ld.d_stage[i]), need * sizeof(float)));
             } else {
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&ld.d_new32), (size_t)cap * cols * sizeof(float)));
+                HIPCHK(hipMalloc(reinterpret_cast<void **>(&ld.d_new32), (size_t)ld.alloc * cols * sizeof(float)));
             }
         }
         ld.active = true;
@@ -160,6 +183,7 @@ struct frt_matcher {
         if (d_g8_scale) (void)hipFree(d_g8_scale);
         d_g8 = nullptr;
         d_g8_scale = nullptr;
+        shadow_rows = 0;
         gerr = 0.f;
         ++generation;
         N = ld.rows;
@@ -167,6 +191,7 @@ struct frt_matcher {
         store16 = ld.f16;
         d_gallery = ld.rows > 0 ? ld.d_new32 : nullptr;
         d_g16 = ld.rows > 0 ? ld.d_new16 : nullptr;
+        cap_rows = ld.rows > 0 ? ld.alloc : 0;
         if (ld.rows == 0) {  // empty gallery: nothing to keep
             if (ld.d_new32) (void)hipFree(ld.d_new32);
             if (ld.d_new16) (void)hipFree(ld.d_new16);
@@ -176,49 +201,76 @@ struct frt_matcher {
         ld.active = false;
         if (old32) (void)hipFree(old32);  // (hipFree waits for the device: stages of earlier pipeline calls have finished with it)
         if (old16) (void)hipFree(old16);
-        blocks = match_top1_blocks(N, 0);
-        screen = N >= 32768 && match_screen_supported(D);
+        screen = N >= SCREEN_MIN_ROWS && match_screen_supported(D);
         gmax_norm = 0.f;
-        if (N > 0 && (screen || store16)) {  // fp16 shadow copy (fp32 storage) + the largest row norm (rounding bound of the screening pass)
-            int *d_bits = nullptr;
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_bits), sizeof(int)));
-            // fp32-stored galleries of 512 columns are screened through an INT8 shadow (half the bytes of the per-call scan; kernels_match.hip);
-            // other widths through an fp16 shadow
-            const bool use_i8 = screen && !store16 && D == 512;
-            int *d_ebits = nullptr;
-            if (store16) {
-                launch_gallery_norm16(d_g16, N, D, d_bits, stream);
-            } else if (use_i8) {
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_ebits), sizeof(int)));
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_g8), gallery8_bytes(N, D)));
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_g8_scale), ((size_t)(N + 127) / 128) * 128 * sizeof(float)));
-                launch_gallery_shadow8(d_gallery, N, D, d_g8, d_g8_scale, d_ebits, d_bits, stream);
-            } else {
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_g16), gallery16_elems(N, D) * sizeof(half_t)));
-                launch_gallery_shadow(d_gallery, N, D, d_g16, d_bits, stream);
-            }
-            int bits = 0, ebits = 0;
-            HIPCHK(hipMemcpyAsync(&bits, d_bits, sizeof(int), hipMemcpyDeviceToHost, stream));
-            if (d_ebits) HIPCHK(hipMemcpyAsync(&ebits, d_ebits, sizeof(int), hipMemcpyDeviceToHost, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            (void)hipFree(d_bits);
-            if (d_ebits) (void)hipFree(d_ebits);
-            float n2, e2;
-            std::memcpy(&n2, &bits, 4);
-            std::memcpy(&e2, &ebits, 4);
-            gmax_norm = std::sqrt(n2);
-            gerr = std::sqrt(e2);
-        }
+        if (N > 0 && (screen || store16)) build_screen_data();
         q_cap = 0;  // partial scratch depends on `blocks`
         if (d_partial) {
             (void)hipFree(d_partial);
             d_partial = nullptr;
         }
+        bind_scratch();
+    }
+    // The screening data of the whole current gallery, on `stream`, synchronously: the int8 / fp16 shadow of fp32-stored rows (allocated for
+    // cap_rows; rows from N on hold the value 0) with the largest row norm and quantisation error; fp16-stored rows are their own shadow.
+    void build_screen_data() {
+        const size_t cap_tiles = ((size_t)cap_rows + 127) / 128, n_tiles = ((size_t)N + 127) / 128;
+        // fp32-stored galleries of 512 columns are screened through an INT8 shadow (half the bytes of the per-call scan; kernels_match.hip);
+        // other widths through an fp16 shadow
+        const bool use_i8 = screen && !store16 && D == 512;
+        if (!d_edit_bits) HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_edit_bits), 2 * sizeof(int)));
+        HIPCHK(hipMemsetAsync(d_edit_bits, 0, 2 * sizeof(int), stream));
+        if (store16) {
+            launch_gallery_norm16(d_g16, N, D, d_edit_bits + 1, stream);
+        } else {
+            if (shadow_rows < cap_rows) {
+                if (d_g8) (void)hipFree(d_g8);
+                if (d_g8_scale) (void)hipFree(d_g8_scale);
+                if (d_g16) (void)hipFree(d_g16);
+                d_g8 = nullptr;
+                d_g8_scale = nullptr;
+                d_g16 = nullptr;
+                shadow_rows = 0;
+                if (use_i8) {
+                    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_g8), gallery8_bytes(cap_rows, D)));
+                    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_g8_scale), cap_tiles * 128 * sizeof(float)));
+                } else {
+                    HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_g16), gallery16_elems(cap_rows, D) * sizeof(half_t)));
+                }
+                shadow_rows = (int)(cap_tiles * 128);
+            }
+            if (use_i8) {
+                launch_gallery_shadow8(d_gallery, N, D, d_g8, d_g8_scale, d_edit_bits, d_edit_bits + 1, stream);
+                if (cap_tiles > n_tiles) {  // the tiles an add will fill later
+                    HIPCHK(hipMemsetAsync(d_g8 + n_tiles * 128 * D, 0x80, (cap_tiles - n_tiles) * 128 * D, stream));
+                    HIPCHK(hipMemsetAsync(d_g8_scale + n_tiles * 128, 0, (cap_tiles - n_tiles) * 128 * sizeof(float), stream));
+                }
+            } else {
+                launch_gallery_shadow(d_gallery, N, D, d_g16, d_edit_bits + 1, stream);
+                if (cap_tiles > n_tiles) HIPCHK(hipMemsetAsync(d_g16 + n_tiles * 128 * D, 0, (cap_tiles - n_tiles) * 128 * D * sizeof(half_t), stream));
+            }
+        }
+        read_bounds(false);
+    }
+    // d_edit_bits -> gerr / gmax_norm.  merge: keep the larger of the old and the new value (an add: still upper bounds, and the exact
+    // re-rank keeps the answers exact); a NaN - the mark of a non-finite row - sticks either way.
+    void read_bounds(bool merge) {
+        int bits[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(bits, d_edit_bits, sizeof(bits), hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        float e2, n2;
+        std::memcpy(&e2, &bits[0], 4);
+        std::memcpy(&n2, &bits[1], 4);
+        const float e = std::sqrt(e2), n = std::sqrt(n2);
+        auto upper = [](float old, float nw) { return (old != old || nw <= old) ? old : nw; };
+        gerr = merge ? upper(gerr, e) : e;
+        gmax_norm = merge ? upper(gmax_norm, n) : n;
     }
 
     void ensure_queries(int F) {
-        if (F <= q_cap && d_partial) return;
-        const int cap = std::max(F, 128);
+        if (F <= q_cap && d_partial && scratch_rows >= cap_rows && (!screen || scr.q16)) return;
+        const int cap = std::max(std::max(F, q_cap), 128);
+        const int rows = std::max(cap_rows, N);
         ++generation;  // scratch buffers move
         if (d_q) (void)hipFree(d_q);
         if (d_sim) (void)hipFree(d_sim);
@@ -228,18 +280,18 @@ struct frt_matcher {
         d_q = d_sim = d_kth = nullptr;
         d_idx = nullptr;
         d_partial = nullptr;
+        free_screen_scratch();
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_q), (size_t)cap * D * sizeof(float)));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_sim), (size_t)cap * KCAP * sizeof(float)));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_idx), (size_t)cap * KCAP * sizeof(int32_t)));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_kth), (size_t)cap * sizeof(float)));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_partial), (size_t)blocks * cap * sizeof(MatchPartial)));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_partial), (size_t)match_top1_blocks(rows, 0) * cap * sizeof(MatchPartial)));  // [blocks][cap], blocks <= those of `rows`
         if (screen) {
-            const size_t tiles = ((size_t)N + 127) / 128;
-            free_screen_scratch();
+            const size_t tiles = ((size_t)rows + 127) / 128;
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.q16), (size_t)cap * D * sizeof(half_t)));
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.tilemax), (size_t)cap * tiles * 4 * sizeof(float)));  // 4 coarse entries per tile (one per wave)
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.tile_flags), (tiles + 1) * sizeof(int)));  // [tiles] flags + the candidate count:
-            scr.count = scr.tile_flags + tiles;                                                           // one contiguous range to clear per call
+                                                                                                          // one contiguous range to clear per call (bind_scratch)
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.tile_list), tiles * sizeof(int)));
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.segmax), (size_t)cap * 16 * sizeof(float)));
             scr.pair_cap = std::max(cap * 64, 8192);  // (a multiple of the 64 sub-lists)
@@ -250,6 +302,8 @@ struct frt_matcher {
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.qkey), (size_t)cap * sizeof(unsigned long long)));
         }
         q_cap = cap;
+        scratch_rows = rows;
+        bind_scratch();
     }
     // queries_dev [F][D] -> idx_dev, sim_dev (device pointers)
     void top1_dev(const float *queries_dev, int F, int32_t *idx_dev, float *sim_dev, hipStream_t s) {

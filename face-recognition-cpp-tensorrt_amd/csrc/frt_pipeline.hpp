@@ -520,6 +520,9 @@ struct frt_pipeline {
             if (pipe3 && c[i].call >= (unsigned)NSLOT) HIPCHK(hipStreamWaitEvent(es, ev_done[c[i].slot], 0));
             if (pipe3) HIPCHK(hipStreamWaitEvent(es, ev_det[c[i].slot], 0));
         }
+        // (a call that was held back or waiting for a partner reaches this point after its submit: a live gallery edit in between - the first
+        //  rows of an empty gallery above all - may have left the matcher without scratch for this pipeline; a no-op otherwise)
+        if (mat && mat->N > 0) mat->ensure_queries(F_cap);
         const bool have_gallery = mat && mat->N > 0;
         const unsigned gen = mat ? mat->generation : 0u;
         const int akey = (align ? 1 : 0) | (c[0].crops ? 2 : 0);

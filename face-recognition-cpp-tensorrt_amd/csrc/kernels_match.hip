@@ -16,6 +16,7 @@
 #include <cstdlib>
 
 #include "frt_kernels.h"
+#include "frt_holes.h"
 
 constexpr int CTL_WORDS = FRT_MATCH_CTL_WORDS;  // control words of the fast screened path (cleared by the coarse scan; layout at CTL_OVERFLOW below; frt_matcher.hpp allocates them)
 
@@ -304,10 +305,10 @@ __global__ __launch_bounds__(256) void gallery_to_half_kernel(const float *__res
     *reinterpret_cast<half8 *>(out + piece * 8) = o;
 }
 
-// max over rows of ||g||^2 (non-negative floats order like their bit patterns -> atomicMax on the int view); one wave per row
+// max over the rows [row0, N) of ||g||^2 (non-negative floats order like their bit patterns -> atomicMax on the int view); one wave per row
 template <typename GT>
-__global__ __launch_bounds__(256) void row_norm_max_kernel(const GT *__restrict__ G, int N, int D, int *__restrict__ out_bits) {
-    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+__global__ __launch_bounds__(256) void row_norm_max_kernel(const GT *__restrict__ G, int row0, int N, int D, int *__restrict__ out_bits) {
+    const int row = row0 + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     float s = 0.f;
     for (int k = lane * 4; k < D && row < N; k += 256) {
         const floatx4 v = load_g4(G, (long)row, D, k);
@@ -470,13 +471,14 @@ __device__ __forceinline__ half8 i8x8_to_half8(unsigned d0, unsigned d1) {
     return x.v;
 }
 
-// one wave per gallery row (D = 512: 8 values per lane): scale = max|g| / 127, q = rint(g / scale), error norm^2 and row norm^2 -> atomicMax
-__global__ __launch_bounds__(256) void gallery_to_i8_kernel(const float *__restrict__ in, int N, uint8_t *__restrict__ out, float *__restrict__ scale,
+// one wave per gallery row (D = 512: 8 values per lane): scale = max|g| / 127, q = rint(g / scale), error norm^2 and row norm^2 -> atomicMax.
+// Rows [g0, N) of the gallery; `in` starts at row g0 (the whole gallery at build time, the appended rows / the rows behind a removal later).
+__global__ __launch_bounds__(256) void gallery_to_i8_kernel(const float *__restrict__ in, int g0, int N, uint8_t *__restrict__ out, float *__restrict__ scale,
                                                             int *__restrict__ max_err2_bits, int *__restrict__ max_norm2_bits) {
     constexpr int D = 512;
-    const int g = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int g = g0 + blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (g >= N) return;
-    const float *row = in + (long)g * D + lane * 8;
+    const float *row = in + (long)(g - g0) * D + lane * 8;
     const floatx4 a = *reinterpret_cast<const floatx4 *>(row), b = *reinterpret_cast<const floatx4 *>(row + 4);
     const float v[8] = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
     float m = 0.f, n2 = 0.f;
@@ -1023,6 +1025,41 @@ __global__ __launch_bounds__(256) void match_unpack_kernel(unsigned long long *_
     sim_out[(long)q * out_stride] = k ? unmono_bits((unsigned)(k >> 32)) : -INFINITY;
 }
 
+// ---------------------------------------------------------------- live gallery edits: order-preserving compaction (frt_matcher_gallery_remove)
+// The rows behind the first removed one move down IN PLACE.  Source and destination ranges overlap and the workgroups of a launch run
+// in no order, so the move is never one launch: the host walks the destination in ascending chunks, each chunk is GATHERED into a bounce
+// buffer by one of these kernels and copied to its place by the next operation on the stream - stream order is the barrier.  A chunk reads
+// only rows at or behind its own first row (a source row never lies in front of its destination) and every earlier chunk wrote only in front of
+// it.  keys: frt_holes.h; [klo, khi) = the keys that fall inside this chunk (the host narrows the search; a chunk without holes searches nothing).
+// thread = one 16-byte piece.
+__global__ __launch_bounds__(256) void gather_rows_f32_kernel(const float *__restrict__ G, int D, int a, int n_rows, const int *__restrict__ keys, int klo,
+                                                              int khi, float *__restrict__ bounce) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    const int per = D >> 2;
+    const long r = t / per;
+    if (r >= n_rows) return;
+    const int c = (int)(t - r * per);
+    const long src = frt_hole_source_row(keys, klo, khi, a + (int)r);
+    *reinterpret_cast<floatx4 *>(bounce + t * 4) = *reinterpret_cast<const floatx4 *>(G + src * D + c * 4);
+}
+// fragment-ordered fp16 rows: the chunk is whole 128-row tiles [tile0, tile0 + n_tiles) of the destination, the bounce buffer holds them in
+// their final layout; rows at or behind n_new (the padding of the new last tile) become zeros
+__global__ __launch_bounds__(256) void gather_rows_h16_kernel(const half_t *__restrict__ G, int D, long tile0, long n_tiles, int n_new, const int *__restrict__ keys,
+                                                              int klo, int khi, half_t *__restrict__ bounce) {
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;  // piece index relative to the first tile of the chunk (see gallery_to_half_kernel)
+    const int KS = D >> 4;
+    if (t >= n_tiles * 4 * KS * 64) return;
+    const long piece = t + tile0 * 4 * KS * 64;
+    const long blk = piece >> 6;
+    const int lane = (int)(piece & 63), hi = lane >> 5, r = lane & 31;
+    const int ks = (int)(blk % KS);
+    const long tw = blk / KS;
+    const long g = (tw >> 2) * 128 + (tw & 3) * 32 + r;
+    half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (g < n_new) v = *reinterpret_cast<const half8 *>(G + g16_index(frt_hole_source_row(keys, klo, khi, (int)g), ks * 16 + hi * 8, D));
+    *reinterpret_cast<half8 *>(bounce + t * 8) = v;
+}
+
 template <int NQ, bool FULL, typename GT = float, bool EXCL = false>
 void launch_t(const GT *G, int N, int D, const float *E, int F, MatchPartial *partial, float *out_full, int blocks, int row_offset,
               hipStream_t s, const int *tile_list = nullptr, const int *d_num_tiles = nullptr, const float *prev_sim = nullptr,
@@ -1090,10 +1127,11 @@ bool match_screen_supported(int D) { return D == 64 || D == 128 || D == 256 || D
 
 size_t gallery16_elems(int N, int D) { return (size_t)((N + 127) / 128) * 128 * D; }  // whole 128-row tiles
 
-// fp32 rows [n_rows][D] whose first row is global row row0 (a multiple of 128) -> their place in the fragment-ordered fp16 gallery
+// fp32 rows [n_rows][D] whose first row is global row row0 -> their place in the fragment-ordered fp16 gallery (the other rows of the
+// tiles they touch are left alone: a partly filled tail tile keeps its rows and its zero padding)
 void launch_rows_to_half(const float *in, long row0, long n_rows, int D, half_t *g16, hipStream_t s) {
     if (n_rows <= 0) return;
-    const long tiles = (n_rows + 127) / 128;
+    const long tiles = ((row0 + n_rows + 127) >> 7) - (row0 >> 7);
     const long pieces = tiles * 4 * (D / 16) * 64;
     hipLaunchKernelGGL(gallery_to_half_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, in, row0, n_rows, D, g16);
 }
@@ -1102,13 +1140,13 @@ void launch_gallery_shadow(const float *gallery, int N, int D, half_t *g16, int 
     (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
     (void)hipMemsetAsync(g16, 0, gallery16_elems(N, D) * sizeof(half_t), s);  // (pad rows of the last tile stay zero)
     launch_rows_to_half(gallery, 0, N, D, g16, s);
-    hipLaunchKernelGGL(row_norm_max_kernel<float>, dim3((N + 3) / 4), dim3(256), 0, s, gallery, N, D, max_norm2_bits);
+    hipLaunchKernelGGL(row_norm_max_kernel<float>, dim3((N + 3) / 4), dim3(256), 0, s, gallery, 0, N, D, max_norm2_bits);
 }
 
 // fp16-STORED gallery (no fp32 copy on the device): only the largest row norm is needed, the stored rows are their own shadow
 void launch_gallery_norm16(const half_t *g16, int N, int D, int *max_norm2_bits, hipStream_t s) {
     (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
-    hipLaunchKernelGGL(row_norm_max_kernel<half_t>, dim3((N + 3) / 4), dim3(256), 0, s, g16, N, D, max_norm2_bits);
+    hipLaunchKernelGGL(row_norm_max_kernel<half_t>, dim3((N + 3) / 4), dim3(256), 0, s, g16, 0, N, D, max_norm2_bits);
 }
 
 size_t gallery8_bytes(int N, int D) { return (size_t)((N + 127) / 128) * 128 * D; }
@@ -1119,8 +1157,34 @@ void launch_gallery_shadow8(const float *gallery, int N, int D, uint8_t *g8, flo
     (void)hipMemsetAsync(g8, 0x80, gallery8_bytes(N, D), s);  // pad rows of the last tile: value 0
     (void)hipMemsetAsync(scale, 0, rows * sizeof(float), s);
     if (D != 512 || N <= 0) return;
-    hipLaunchKernelGGL(gallery_to_i8_kernel, dim3((N + 3) / 4), dim3(256), 0, s, gallery, N, g8, scale, max_err2_bits, max_norm2_bits);
+    hipLaunchKernelGGL(gallery_to_i8_kernel, dim3((N + 3) / 4), dim3(256), 0, s, gallery, 0, N, g8, scale, max_err2_bits, max_norm2_bits);
 }
+// ---------------------------------------------------------------- live gallery edits (host side; frt_matcher_gallery_add / _remove)
+// rows [row0, row0 + n_rows) of the int8 shadow from fp32 rows (`rows` starts at row row0): the build's quantiser, the other rows untouched
+void launch_gallery_shadow8_rows(const float *rows, int row0, int n_rows, uint8_t *g8, float *scale, int *max_err2_bits, int *max_norm2_bits, hipStream_t s) {
+    (void)hipMemsetAsync(max_err2_bits, 0, sizeof(int), s);
+    (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
+    if (n_rows <= 0) return;
+    hipLaunchKernelGGL(gallery_to_i8_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, rows, row0, row0 + n_rows, g8, scale, max_err2_bits, max_norm2_bits);
+}
+// largest squared norm of the rows [row0, row0 + n_rows) of a gallery (fp32 row-major or fragment-ordered fp16; G = the whole gallery)
+void launch_rows_norm(const float *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s) {
+    (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
+    if (n_rows > 0) hipLaunchKernelGGL(row_norm_max_kernel<float>, dim3((n_rows + 3) / 4), dim3(256), 0, s, G, row0, row0 + n_rows, D, max_norm2_bits);
+}
+void launch_rows_norm16(const half_t *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s) {
+    (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
+    if (n_rows > 0) hipLaunchKernelGGL(row_norm_max_kernel<half_t>, dim3((n_rows + 3) / 4), dim3(256), 0, s, G, row0, row0 + n_rows, D, max_norm2_bits);
+}
+void launch_gather_rows(const float *G, int D, int a, int n_rows, const int *keys, int klo, int khi, float *bounce, hipStream_t s) {
+    const long pieces = (long)n_rows * (D / 4);
+    if (pieces > 0) hipLaunchKernelGGL(gather_rows_f32_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, G, D, a, n_rows, keys, klo, khi, bounce);
+}
+void launch_gather_rows16(const half_t *G, int D, long tile0, long n_tiles, int n_new, const int *keys, int klo, int khi, half_t *bounce, hipStream_t s) {
+    const long pieces = n_tiles * 4 * (D / 16) * 64;
+    if (pieces > 0) hipLaunchKernelGGL(gather_rows_h16_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, G, D, tile0, n_tiles, n_new, keys, klo, khi, bounce);
+}
+
 
 constexpr int COARSE_WG = 256;  // persistent workgroups of the coarse scan (one per CU)
 template <int NQB>

@@ -195,6 +195,35 @@ int frt_matcher_gallery_begin(frt_matcher *m, int row_capacity, int num_col);
 int frt_matcher_gallery_append(frt_matcher *m, const void *rows, int n_rows);
 int frt_matcher_gallery_commit(frt_matcher *m);
 int frt_matcher_num_rows(const frt_matcher *m);
+/* Live gallery edits: add rows to, and remove rows from, the gallery the matcher is answering from - the reference's /insert/face and
+ * /delete/user (src/app.cpp:131-229) without the /reload (src/app.cpp:354-365) that re-reads every row.  The rows already there stay on the
+ * device, the screening data is updated only where it changed.  After any sequence of edits the matcher answers EXACTLY as a fresh matcher
+ * would that was frt_matcher_init'ed with the resulting row list in the same storage mode (indices, similarities, the first-maximum tie
+ * rule; top1 / topk / calculate / the _dev forms / the pipeline's match stage; screening on or off).
+ *   - An edit returns when its device work is complete; a call submitted after it returns is answered from the new gallery, a call in
+ *     flight wholly from the old or wholly from the new one.  frt_matcher_generation changes on every edit that changes the gallery.
+ *   - Limits: a matcher with a row offset (a shard, frt_matcher_set_row_offset != 0) is not edited - FRT_ERR_INVALID; reload the shard.  An
+ *     edit while a streamed load is open (gallery_begin without commit) acts on the live gallery; the commit then replaces it, as always.
+ *     Galleries screen from 32 768 rows on: the add that takes the gallery across builds the whole shadow (once), a remove that takes it
+ *     below stops screening (the allocation is kept for the way back) - frt_matcher_scan_bytes describes either state.
+ * gallery_reserve: room for edits up to row_capacity rows - the stored rows, the shadow, the per-row scales and the per-call scratch sized
+ *   by tiles or blocks; an add inside it allocates nothing.  Never shrinks; contents and answers are unchanged.  On a matcher without rows it
+ *   is the floor of the next allocation (init / gallery_begin / the first add).
+ * gallery_add / gallery_add_dev: append n_rows rows [n_rows][num_col] fp32 from host memory / from device memory (the embedder's output:
+ *   an enrolment never crosses PCIe twice; the rows must be complete when the call is made).  They get the indices N .. N + n_rows - 1,
+ *   existing indices do not move.  Short of capacity the gallery is moved into an allocation 1.5 x as large (at least what is needed):
+ *   allocate + device copy + free, which transiently needs BOTH copies.  num_col is that of the last init / gallery_begin (an empty
+ *   gallery: gallery_begin(m, cap, num_col) + gallery_commit with zero rows).
+ * gallery_remove: row indices in any order, duplicates count once; an index outside [0, N) is FRT_ERR_INVALID with nothing changed.
+ *   Order-preserving, like the reference after a delete + /reload (SELECT order, src/db.cpp:316-346): the surviving rows keep their order
+ *   and close up, a row behind r removed rows moves down by r.  Removing every row leaves an empty gallery (match calls: FRT_ERR_EMPTY).
+ * edit_stats: cumulative { rows_uploaded (rows taken in by add), rows_moved (rows a remove moved down), shadow_rows_rebuilt (rows converted
+ *   into the int8 / fp16 shadow by edits), reallocations (moves of a non-empty gallery into a larger allocation) }. */
+int frt_matcher_gallery_reserve(frt_matcher *m, int row_capacity);
+int frt_matcher_gallery_add(frt_matcher *m, const float *rows, int n_rows);
+int frt_matcher_gallery_add_dev(frt_matcher *m, const void *rows_dev, int n_rows);
+int frt_matcher_gallery_remove(frt_matcher *m, const int32_t *idx, int n_idx);
+int frt_matcher_edit_stats(frt_matcher *m, long out[4]);
 /* MatMul::calculate (src/matmul.cpp:36-77): outputs[i*num_row + j] = sum_k embeds[i][k] * gallery[j][k], fp32. */
 int frt_matcher_calculate(frt_matcher *m, const float *embeds, int embed_count, float *outputs);
 /* calculate and the first-maximum argmax of every row in ONE call: outputs (may be NULL: no matrix is materialised) as

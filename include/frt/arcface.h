@@ -148,6 +148,36 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         classNames.insert(classNames.end(), names.begin(), names.end());
         classCount += (int)names.size();
     }
+    // Extension: live enrolment - what /insert/face and /delete/user (src/app.cpp:131-229) need so that nobody has to post /reload
+    // (src/app.cpp:354-365).  The rows go to / leave the gallery the matcher is answering from (frt_matcher_gallery_add / _remove: the rows
+    // already there stay on the device) and classNames / classCount move with them; the next featureMatching() sees the change.  Not for
+    // use between initKnownEmbeds() and initMatMul(): a load in progress replaces the gallery at its commit.
+    void enrolEmbedding(const std::string &className, const float embedding[]) { enrolEmbeddings(std::vector<std::string>(1, className), embedding); }
+    void enrolEmbedding(const std::string &className, const std::vector<float> &embedding) {
+        assert((int)embedding.size() == m_OUTPUT_D);
+        enrolEmbedding(className, embedding.data());
+    }
+    void enrolEmbeddings(const std::vector<std::string> &names, const float *embeddings) {
+        if (matmul.numRows() == 0 && classNames.empty()) {  // never loaded (or emptied): an empty gallery of this width first
+            matmul.galleryBegin(0, m_OUTPUT_D);
+            matmul.galleryCommit();
+        }
+        matmul.galleryAdd(embeddings, (int)names.size());
+        classNames.insert(classNames.end(), names.begin(), names.end());
+        classCount += (int)names.size();
+    }
+    // every row of that name, as /delete/user removes every face of the user; the rows behind them close up in order (the order a
+    // /reload would read them in: src/db.cpp:316-346).  Returns how many there were.
+    int removeClass(const std::string &className) {
+        std::vector<int> rows;
+        for (size_t i = 0; i < classNames.size(); ++i)
+            if (classNames[i] == className) rows.push_back((int)i);
+        if (rows.empty()) return 0;
+        matmul.galleryRemove(rows.data(), (int)rows.size());
+        classNames.erase(std::remove(classNames.begin(), classNames.end(), className), classNames.end());
+        classCount -= (int)rows.size();
+        return (int)rows.size();
+    }
     void initKnownEmbeds(int num) { matmul.galleryBegin(num, m_OUTPUT_D); }  // arcface.cpp:162
     void initMatMul() { matmul.galleryCommit(); }                            // arcface.cpp:164
     void resetEmbeddings() {                                                  // arcface.cpp:233-236

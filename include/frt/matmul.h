@@ -37,6 +37,24 @@ class MatMul {
     void galleryAppend(const float *rows, int n) { checkFrtStatus(frt_matcher_gallery_append(h_, rows, n)); }
     void galleryCommit() { checkFrtStatus(frt_matcher_gallery_commit(h_)); }
     int numRows() const { return frt_matcher_num_rows(h_); }
+    // Extension: live edits of the gallery the object is answering from (frt_matcher_gallery_reserve / _add / _add_dev / _remove): no reload,
+    // the rows already on the device stay there.  galleryAdd appends (new indices numRows() ...), galleryRemove closes the gaps in order.
+    void galleryReserve(int rowCapacity) {
+        ensure();
+        checkFrtStatus(frt_matcher_gallery_reserve(h_, rowCapacity));
+    }
+    void galleryAdd(const float *rows, int n) {
+        ensure();
+        checkFrtStatus(frt_matcher_gallery_add(h_, rows, n));
+    }
+    void galleryAddDev(const void *rowsDev, int n) {
+        ensure();
+        checkFrtStatus(frt_matcher_gallery_add_dev(h_, rowsDev, n));
+    }
+    void galleryRemove(const int *rows, int n) {
+        ensure();
+        checkFrtStatus(frt_matcher_gallery_remove(h_, rows, n));
+    }
     // Extension: store the gallery rows as fp16 on the device (next init / galleryBegin); see frt_matcher_set_storage
     void setStorageFp16(bool on) {
         ensure();
