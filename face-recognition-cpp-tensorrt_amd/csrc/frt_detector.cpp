@@ -47,26 +47,38 @@ void pw_bias(const frt::Blob &b, const std::string &conv, int cout, int cin, std
         for (int ci = 0; ci < cin; ++ci) w[(size_t)ci * cout + co] = src[(size_t)co * cin + ci];
     bias.assign(bs, bs + cout);
 }
+// two 3x3 convs (+BN) of the same input as one: fold_conv3 of each, concatenated along Cout (a's channels first)
+void fold_conv3_pair(const frt::Blob &b, const std::string &a, int couta, const std::string &c, int coutc, int cin, std::vector<float> &w,
+                     std::vector<float> &bias) {
+    std::vector<float> wa, wc, bc;
+    fold_conv3(b, a + ".0", a + ".1", couta, cin, wa, bias);
+    fold_conv3(b, c + ".0", c + ".1", coutc, cin, wc, bc);
+    bias.insert(bias.end(), bc.begin(), bc.end());
+    const int cout = couta + coutc;
+    w.resize((size_t)cin * 9 * cout);
+    for (size_t row = 0; row < (size_t)cin * 9; ++row) {
+        std::copy(wa.begin() + row * couta, wa.begin() + (row + 1) * couta, w.begin() + row * cout);
+        std::copy(wc.begin() + row * coutc, wc.begin() + (row + 1) * coutc, w.begin() + row * cout + couta);
+    }
+}
 inline int conv_out(int x, int stride) { return (x + 2 - 3) / stride + 1; }
+inline float f16_to_f32(uint16_t h) {  // exact
+    _Float16 x;
+    std::memcpy(&x, &h, 2);
+    return (float)x;
+}
 // [Cin][9][Cout] fp32 -> fp16 hi/lo split [Cin/16][9][64][hi16 | lo16] (kernels_det_conv3h.hip); empty unless Cin is 64 or 16 and 16 <= Cout <= 64
 std::vector<uint16_t> pack_conv3_split(const std::vector<float> &w, int cin, int cout) {
     if ((cin != 64 && cin != 16) || cout > 64 || cout < 16) return {};
     const int nch = cin / 16;
     std::vector<uint16_t> o((size_t)nch * 9 * 64 * 32, 0);
-    auto h2f = [](uint16_t h) {  // fp16 -> fp32 (normal / subnormal / zero; no inf/nan expected in weights)
-        const uint32_t sgn = (uint32_t)(h & 0x8000) << 16, e = (h >> 10) & 31, m = h & 1023;
-        float f;
-        if (e == 0) f = std::ldexp((float)m, -24);
-        else f = std::ldexp((float)(m | 1024), (int)e - 25);
-        return sgn ? -f : f;
-    };
     for (int c = 0; c < nch; ++c)
         for (int t = 0; t < 9; ++t)
             for (int co = 0; co < cout; ++co)
                 for (int k = 0; k < 16; ++k) {
                     const float x = w[((size_t)(c * 16 + k) * 9 + t) * cout + co];
                     const uint16_t hi = frt::f32_to_f16(x);
-                    const uint16_t lo = frt::f32_to_f16(x - h2f(hi));
+                    const uint16_t lo = frt::f32_to_f16(x - f16_to_f32(hi));
                     const size_t row = (((size_t)c * 9 + t) * 64 + co) * 32;
                     o[row + k] = hi;
                     o[row + 16 + k] = lo;
@@ -76,11 +88,6 @@ std::vector<uint16_t> pack_conv3_split(const std::vector<float> &w, int cin, int
 // pointwise weights [Cin][Cout] fp32 -> fp16 hi/lo split [Cout][Cin/16][hi16 | lo16] (dwpw_mfma_kernel / pw_mfma_kernel); empty unless Cin % 16 == 0
 std::vector<uint16_t> pack_pw_split(const std::vector<float> &w, int cin, int cout) {
     if (cin % 16) return {};
-    auto h2f = [](uint16_t h) {
-        const uint32_t sgn = (uint32_t)(h & 0x8000) << 16, e = (h >> 10) & 31, m = h & 1023;
-        const float f = e == 0 ? std::ldexp((float)m, -24) : std::ldexp((float)(m | 1024), (int)e - 25);
-        return sgn ? -f : f;
-    };
     std::vector<uint16_t> o((size_t)cout * cin * 2, 0);
     for (int co = 0; co < cout; ++co)
         for (int k = 0; k < cin; ++k) {
@@ -88,22 +95,42 @@ std::vector<uint16_t> pack_pw_split(const std::vector<float> &w, int cin, int co
             const uint16_t hi = frt::f32_to_f16(x);
             const size_t row = ((size_t)co * (cin / 16) + k / 16) * 32;
             o[row + k % 16] = hi;
-            o[row + 16 + k % 16] = frt::f32_to_f16(x - h2f(hi));
+            o[row + 16 + k % 16] = frt::f32_to_f16(x - f16_to_f32(hi));
         }
     return o;
 }
-// [Cin][9][Cout] -> matrix-core layout [9][Cin/kc][cpad][kc] (kernels_det_conv3.hip); empty when the shape is not covered
-std::vector<float> pack_conv3_mfma(const std::vector<float> &w, int cin, int cout, int &kc, int &cpad) {
-    kc = cin == 16 ? 16 : 32;
-    cpad = cout > 32 ? 64 : 32;
-    if (cin % kc || cout > 64 || cout < 16) return {};
-    const int ncc = cin / kc;
-    std::vector<float> o((size_t)9 * ncc * cpad * kc, 0.f);
-    for (int t = 0; t < 9; ++t)
-        for (int cc = 0; cc < ncc; ++cc)
-            for (int co = 0; co < cout; ++co)
-                for (int k = 0; k < kc; ++k) o[(((size_t)t * ncc + cc) * cpad + co) * kc + k] = w[((size_t)(cc * kc + k) * 9 + t) * cout + co];
-    return o;
+// "set the batch, launch", once per kind of op (frt_detector::forward)
+void run(DwPwArgs &a, int n, hipStream_t s) {
+    a.B = n;
+    launch_dwpw(a, s);
+}
+void run(frt_detector::Conv3Op &o, int n, hipStream_t s) {
+    for (int k = 0; k < o.n; ++k) o.p[k].B = n;
+    launch_conv3x3_multi(o.p, o.n, s);
+}
+void run(frt_detector::HeadsOp &o, int n, hipStream_t s) {
+    for (int k = 0; k < o.n; ++k) o.p[k].B = n;
+    launch_heads_multi(o.p, o.n, s);
+}
+void run(frt_detector::SlimHeadsOp &o, int n, hipStream_t s) {
+    o.a.B = n;
+    launch_slim_heads(o.a, o.n, s);
+}
+void run(DenseHeadArgs &a, int n, hipStream_t s) {
+    a.B = n;
+    launch_dense_head(a, s);
+}
+void run(RfbProjArgs &a, int n, hipStream_t s) {
+    a.B = n;
+    launch_rfb_proj(a, s);
+}
+void run(frt_detector::RfbConvOp &o, int n, hipStream_t s) {
+    o.a.B = n;
+    launch_rfb_conv(o.a, o.n, s);
+}
+void run(RfbTailArgs &a, int n, hipStream_t s) {
+    a.B = n;
+    launch_rfb_tail(a, s);
 }
 
 // ---- Slim / RFB (conversion/retina/models/net_slim.py, net_rfb.py): the tensors of the state_dict, shapes included
@@ -201,42 +228,37 @@ DetLayout det_layout(const frt::Blob &b) {
     return L;
 }
 
-namespace {
-
-}  // namespace
-
 // one conv_dw block (dw3x3 + bias -> ReLU -> 1x1 + bias -> ReLU, BN folded) with every weight layout its kernels may use; its scratch
 // (tmp) is set once the whole op list is known (frt_detector_create: sized from the ops)
-frt_detector::Op frt_detector::dwpw_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias,
-                                       const std::vector<float> &w2, const std::vector<float> &bias2, int cin, int cout, int h, int w_, int oh,
-                                       int ow, int stride) {
+DwPwArgs frt_detector::dwpw_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias,
+                               const std::vector<float> &w2, const std::vector<float> &bias2, int cin, int cout, int h, int w_, int oh, int ow,
+                               int stride) {
     const int B = max_batch;
-    Op o{};
-    o.type = 0;
+    flops_per_frame += 2.0 * oh * ow * (9.0 * cin + (double)cin * cout);
     std::vector<float> w12((size_t)cin * 12, 0.f);
     for (int ci = 0; ci < cin; ++ci) {
         for (int t = 0; t < 9; ++t) w12[(size_t)ci * 12 + t] = w[(size_t)ci * 9 + t];
         w12[(size_t)ci * 12 + 9] = bias[ci];
     }
-    o.dw = DwPwArgs{in, out, arena.upload(w), arena.upload(bias), arena.upload(w2), arena.upload(bias2), nullptr, 0, 0,
-                    B, cin, h, w_, cout, oh, ow, stride, 1, nullptr, arena.upload(w12), nullptr};
+    DwPwArgs d{in, out, arena.upload(w), arena.upload(bias), arena.upload(w2), arena.upload(bias2), nullptr, 0, 0,
+               B, cin, h, w_, cout, oh, ow, stride, 1, nullptr, arena.upload(w12), nullptr};
     {
         const std::vector<uint16_t> ph = pack_pw_split(w2, cin, cout);
-        if (!ph.empty()) o.dw.wph = reinterpret_cast<const half_t *>(arena.upload(ph));
+        if (!ph.empty()) d.wph = reinterpret_cast<const half_t *>(arena.upload(ph));
         if (cin % 2 == 0) {  // depthwise weights of channel pairs (kernels_det_wave.hip, kernels_det_stem.hip)
             std::vector<float> wp2((size_t)cin * 10, 0.f);  // [Cin/2][10][2]: taps 0-8, bias; the channel pair interleaved
             for (int ci = 0; ci < cin; ++ci) {
                 for (int t = 0; t < 9; ++t) wp2[(size_t)(ci / 2) * 20 + 2 * t + (ci & 1)] = w[(size_t)ci * 9 + t];
                 wp2[(size_t)(ci / 2) * 20 + 18 + (ci & 1)] = bias[ci];
             }
-            o.dw.wdp = arena.upload(wp2);
+            d.wdp = arena.upload(wp2);
             if (cin <= 16) {
                 std::vector<float> wt((size_t)cin * 10, 0.f);
                 for (int ci = 0; ci < cin; ++ci) {
                     for (int t = 0; t < 9; ++t) wt[((size_t)t * (cin / 2) + ci / 2) * 2 + (ci & 1)] = w[(size_t)ci * 9 + t];
                     wt[((size_t)9 * (cin / 2) + ci / 2) * 2 + (ci & 1)] = bias[ci];
                 }
-                o.dw.wdt = arena.upload(wt);
+                d.wdt = arena.upload(wt);
             }
         }
         if (!ph.empty() && cout % 32 == 0) {  // the other operands of dwpw_wave_kernel
@@ -253,83 +275,55 @@ frt_detector::Op frt_detector::dwpw_op(const float *in, float *out, const std::v
                 d_wave_zeros = arena.alloc<float>(dwpw_wave_zero_bytes() / 4);
                 HIPCHK(hipMemset(d_wave_zeros, 0, dwpw_wave_zero_bytes()));
             }
-            o.dw.zeros = d_wave_zeros;
-            o.dw.wpf = reinterpret_cast<const half_t *>(arena.upload(pf));
+            d.zeros = d_wave_zeros;
+            d.wpf = reinterpret_cast<const half_t *>(arena.upload(pf));
         }
     }
-    return o;
+    return d;
+}
+
+// a plain 1x1 conv + bias + ReLU (BN folded), optionally adding a nearest-upsampled [B][cout][add_h][add_w] tensor behind the ReLU
+DwPwArgs frt_detector::pw_op(const float *in, float *out, const std::vector<float> &w2, const std::vector<float> &bias2, int cin, int cout, int h,
+                             int w_, const float *add, int add_h, int add_w) {
+    flops_per_frame += 2.0 * h * w_ * cin * cout;
+    DwPwArgs d{in, out, nullptr, nullptr, arena.upload(w2), arena.upload(bias2), add, add_h, add_w, max_batch, cin, h, w_, cout, h, w_, 1, 1,
+               nullptr, nullptr, nullptr};
+    const std::vector<uint16_t> ph = pack_pw_split(w2, cin, cout);
+    if (!ph.empty()) d.wph = reinterpret_cast<const half_t *>(arena.upload(ph));
+    return d;
+}
+
+// a dense 3x3 conv + bias + ReLU (w, bias: fold_conv3 / fold_conv3_pair) writing channels [coff, coff + cout) of a ctotal-channel tensor; stride 1:
+// with the split-fp16 layout where pack_conv3_split covers the shape
+Conv3Args frt_detector::conv3_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias, int cin, int cout, int h,
+                                 int w_, int stride, int ctotal, int coff) {
+    Conv3Args c{in, out, arena.upload(w), arena.upload(bias), max_batch, cin, h, w_, cout, conv_out(h, stride), conv_out(w_, stride), stride, 1, ctotal, coff};
+    flops_per_frame += 2.0 * cin * 9 * cout * c.Ho * c.Wo;
+    if (stride == 1) {
+        const std::vector<uint16_t> ph = pack_conv3_split(w, cin, cout);
+        if (!ph.empty()) c.wh = reinterpret_cast<const half_t *>(arena.upload(ph));
+    }
+    return c;
+}
+
+frt_detector::Stem frt_detector::stem() {
+    Stem st;
+    Conv3Op *c = ops.empty() ? nullptr : std::get_if<Conv3Op>(&ops[0]);
+    if (!c || c->n != 1) return st;
+    st.c = &c->p[0];
+    DwPwArgs *d1 = ops.size() >= 3 ? std::get_if<DwPwArgs>(&ops[1]) : nullptr, *d2 = d1 ? std::get_if<DwPwArgs>(&ops[2]) : nullptr;
+    if (d2) {
+        st.d1 = d1;
+        st.d2 = d2;
+    }
+    return st;
 }
 
 void frt_detector::build(const frt::Blob &b) {
-    const int B = max_batch, H = g.in_h, W = g.in_w;
+    const int H = g.in_h, W = g.in_w;
     std::vector<float> w, bias, w2, bias2;
-    auto act = [&](int c, int h, int w_) { return arena.alloc<float>((size_t)B * c * h * w_); };
-    auto add_c3 = [&](const float *in, float *out, const std::string &conv, const std::string &bn, int cin, int cout, int h, int w_, int stride,
-                      int ctotal, int coff) {
-        fold_conv3(b, conv, bn, cout, cin, w, bias);
-        Op o{};
-        o.type = 1;
-        o.n = 1;
-        o.c3[0] = Conv3Args{in, out, arena.upload(w), arena.upload(bias), B, cin, h, w_, cout, conv_out(h, stride), conv_out(w_, stride), stride, 1, ctotal, coff};
-        if (stride == 1) {
-            const std::vector<float> pk = pack_conv3_mfma(w, cin, cout, o.c3[0].wm_kc, o.c3[0].wm_cpad);
-            if (!pk.empty()) o.c3[0].wm = arena.upload(pk);
-            const std::vector<uint16_t> ph = pack_conv3_split(w, cin, cout);
-            if (!ph.empty()) o.c3[0].wh = reinterpret_cast<const half_t *>(arena.upload(ph));
-        }
-        ops.push_back(o);
-        flops_per_frame += 2.0 * cin * 9 * cout * o.c3[0].Ho * o.c3[0].Wo;
-    };
-    // the same conv on every pyramid level -> ONE launch (blockIdx.z = level)
-    auto add_c3_levels = [&](const float *const in[3], float *const out[3], const std::string &name, int cin, int cout, const int *hs, const int *ws,
-                             int ctotal, int coff) {
-        Op o{};
-        o.type = 1;
-        o.n = 3;
-        for (int k = 0; k < 3; ++k) {
-            const std::string pfx = "ssh" + std::to_string(k + 1) + "." + name;
-            fold_conv3(b, pfx + ".0", pfx + ".1", cout, cin, w, bias);
-            o.c3[k] = Conv3Args{in[k], out[k], arena.upload(w), arena.upload(bias), B, cin, hs[k], ws[k], cout, hs[k], ws[k], 1, 1, ctotal, coff};
-            const std::vector<float> pk = pack_conv3_mfma(w, cin, cout, o.c3[k].wm_kc, o.c3[k].wm_cpad);
-            if (!pk.empty()) o.c3[k].wm = arena.upload(pk);
-            const std::vector<uint16_t> ph = pack_conv3_split(w, cin, cout);
-            if (!ph.empty()) o.c3[k].wh = reinterpret_cast<const half_t *>(arena.upload(ph));
-            flops_per_frame += 2.0 * cin * 9 * cout * hs[k] * ws[k];
-        }
-        ops.push_back(o);
-    };
-    // two convs reading the same input on every level (SSH conv3X3 64->32 and conv5X5_1 64->16): ONE matrix-core launch with the
-    // output channels concatenated and a split epilogue; the two separate ops stay behind it as the scalar fallback
-    auto add_c3_pair_levels = [&](const float *const in[3], float *const outa[3], const std::string &na, int couta, int ctotala, int coffa,
-                                  float *const outb[3], const std::string &nb, int coutb, int ctotalb, int coffb, int cin, const int *hs,
-                                  const int *ws) {
-        Op o{};
-        o.type = 3;
-        o.n = 3;
-        const int cout = couta + coutb;
-        for (int k = 0; k < 3; ++k) {
-            const std::string pa = "ssh" + std::to_string(k + 1) + "." + na, pb = "ssh" + std::to_string(k + 1) + "." + nb;
-            fold_conv3(b, pa + ".0", pa + ".1", couta, cin, w, bias);
-            fold_conv3(b, pb + ".0", pb + ".1", coutb, cin, w2, bias2);
-            std::vector<float> wc((size_t)cin * 9 * cout), bc(bias);
-            bc.insert(bc.end(), bias2.begin(), bias2.end());
-            for (size_t row = 0; row < (size_t)cin * 9; ++row) {
-                std::copy(w.begin() + row * couta, w.begin() + (row + 1) * couta, wc.begin() + row * cout);
-                std::copy(w2.begin() + row * coutb, w2.begin() + (row + 1) * coutb, wc.begin() + row * cout + couta);
-            }
-            o.c3[k] = Conv3Args{in[k], outa[k], nullptr, arena.upload(bc), B, cin, hs[k], ws[k], cout, hs[k], ws[k], 1, 1, ctotala, coffa};
-            const std::vector<float> pk = pack_conv3_mfma(wc, cin, cout, o.c3[k].wm_kc, o.c3[k].wm_cpad);
-            if (pk.empty()) raise(FRT_ERR_INVALID, "detector: fused SSH conv shape not covered");
-            o.c3[k].wm = arena.upload(pk);
-            const std::vector<uint16_t> ph = pack_conv3_split(wc, cin, cout);
-            if (!ph.empty()) o.c3[k].wh = reinterpret_cast<const half_t *>(arena.upload(ph));
-            o.c3[k].out2 = outb[k];
-            o.c3[k].split = couta;
-            o.c3[k].out2_ctotal = ctotalb;
-            o.c3[k].out2_coff = coffb;
-        }
-        ops.push_back(o);
-    };
+    auto act = [&](int c, int h, int w_) { return arena.alloc<float>((size_t)max_batch * c * h * w_); };
+    const auto ssh = [](int k, const char *name) { return "ssh" + std::to_string(k + 1) + "." + name; };
     // ---- body (net.py:102-124); return layers stage1/2/3 (config.py:17)
     struct L {
         int cin, cout, stride;
@@ -350,13 +344,12 @@ void frt_detector::build(const frt::Blob &b) {
             const int oh = conv_out(ch, l.stride), ow = conv_out(cw, l.stride);
             float *out = act(l.cout, oh, ow);
             if (l.cin == 3) {
-                add_c3(cur, out, p + ".0", p + ".1", 3, l.cout, ch, cw, l.stride, l.cout, 0);
+                fold_conv3(b, p + ".0", p + ".1", l.cout, 3, w, bias);
+                ops.push_back(Conv3Op{{conv3_op(cur, out, w, bias, 3, l.cout, ch, cw, l.stride, l.cout, 0)}, 1});
             } else {
                 fold_dw(b, p + ".0", p + ".1", l.cin, w, bias);
                 fold_pw(b, p + ".3", p + ".4", l.cout, l.cin, w2, bias2);
-                Op o = dwpw_op(cur, out, w, bias, w2, bias2, l.cin, l.cout, ch, cw, oh, ow, l.stride);
-                ops.push_back(o);
-                flops_per_frame += 2.0 * oh * ow * (9.0 * l.cin + (double)l.cin * l.cout);
+                ops.push_back(dwpw_op(cur, out, w, bias, w2, bias2, l.cin, l.cout, ch, cw, oh, ow, l.stride));
             }
             cur = out;
             ch = oh;
@@ -368,12 +361,11 @@ void frt_detector::build(const frt::Blob &b) {
         ++si;
     }
     // the first three layers as one kernel (kernels_det_stem.hip): their weights gathered into one buffer
-    if (ops.size() >= 3 && ops[0].type == 1 && ops[0].n == 1 && ops[1].type == 0 && ops[2].type == 0 && ops[1].dw.wdt && ops[2].dw.wdt &&
-        ops[1].dw.Cin == 8 && ops[1].dw.Cout == 16 && ops[2].dw.Cin == 16 && ops[2].dw.Cout == 32) {
-        float *stem = arena.alloc<float>(det_stem_weight_floats());
-        det_stem_pack(ops[0].c3[0], ops[1].dw, ops[2].dw, stem, nullptr);
+    if (const Stem st = stem(); st.d1 && st.d1->wdt && st.d2->wdt && st.d1->Cin == 8 && st.d1->Cout == 16 && st.d2->Cin == 16 && st.d2->Cout == 32) {
+        float *buf = arena.alloc<float>(det_stem_weight_floats());
+        det_stem_pack(*st.c, *st.d1, *st.d2, buf, nullptr);
         HIPCHK(hipStreamSynchronize(nullptr));
-        ops[1].dw.stem = stem;
+        st.d1->stem = buf;
     }
     for (int k = 0; k < 3; ++k)
         if (fh[k] != g.fh[k] || fw[k] != g.fw[k]) raise(FRT_ERR_INVALID, "detector: feature-map size mismatch");
@@ -384,93 +376,68 @@ void frt_detector::build(const frt::Blob &b) {
         const std::string p = "fpn.output" + std::to_string(k + 1);
         fold_pw(b, p + ".0", p + ".1", 64, cins[k], w2, bias2);
         lat[k] = act(64, fh[k], fw[k]);
-        Op o{};
-        o.type = 0;
-        o.dw = DwPwArgs{feat[k], lat[k], nullptr, nullptr, arena.upload(w2), arena.upload(bias2), addsrc, ah, aw,
-                        B, cins[k], fh[k], fw[k], 64, fh[k], fw[k], 1, 1, nullptr, nullptr, nullptr};
-        {
-            const std::vector<uint16_t> ph = pack_pw_split(w2, cins[k], 64);
-            if (!ph.empty()) o.dw.wph = reinterpret_cast<const half_t *>(arena.upload(ph));
-        }
-        ops.push_back(o);
-        flops_per_frame += 2.0 * fh[k] * fw[k] * cins[k] * 64;
+        ops.push_back(pw_op(feat[k], lat[k], w2, bias2, cins[k], 64, fh[k], fw[k], addsrc, ah, aw));
+    };
+    auto add_merge = [&](int k, const float *in, float *out) {
+        const std::string p = "fpn.merge" + std::to_string(k + 1);
+        fold_conv3(b, p + ".0", p + ".1", 64, 64, w, bias);
+        ops.push_back(Conv3Op{{conv3_op(in, out, w, bias, 64, 64, fh[k], fw[k], 1, 64, 0)}, 1});
     };
     add_lat(2, nullptr, 0, 0);
     add_lat(1, lat[2], fh[2], fw[2]);
     float *p4 = act(64, fh[1], fw[1]);
-    add_c3(lat[1], p4, "fpn.merge2.0", "fpn.merge2.1", 64, 64, fh[1], fw[1], 1, 64, 0);
+    add_merge(1, lat[1], p4);
     add_lat(0, p4, fh[1], fw[1]);
     float *p3 = act(64, fh[0], fw[0]);
-    add_c3(lat[0], p3, "fpn.merge1.0", "fpn.merge1.1", 64, 64, fh[0], fw[0], 1, 64, 0);
-    float *const pyr_m[3] = {p3, p4, lat[2]};
+    add_merge(0, lat[0], p3);
     const float *const pyr[3] = {p3, p4, lat[2]};
-    (void)pyr_m;
     // ---- SSH (net.py:55-66) + heads (retinaface_trim.py:14-35).  Every SSH conv ends in a ReLU: either its own or the
-    //      ReLU applied to the concat it feeds exclusively.
+    //      ReLU applied to the concat it feeds exclusively.  The same conv on every pyramid level is ONE launch (blockIdx.z = level).
     float *cat[3], *t1[3], *t2[3];
     for (int k = 0; k < 3; ++k) {
         cat[k] = act(64, fh[k], fw[k]);
         t1[k] = act(16, fh[k], fw[k]);
         t2[k] = act(16, fh[k], fw[k]);
     }
-    add_c3_pair_levels(pyr, cat, "conv3X3", 32, 64, 0, t1, "conv5X5_1", 16, 16, 0, 64, fh, fw);  // type 3: skips the next two ops when it ran
-    add_c3_levels(pyr, cat, "conv3X3", 64, 32, fh, fw, 64, 0);
-    add_c3_levels(pyr, t1, "conv5X5_1", 64, 16, fh, fw, 16, 0);
-    {
-        // conv5X5_2 (-> cat[32:48]) and conv7X7_2 (-> t2) read the same 16-channel tensor: one launch with the output channels
-        // concatenated (two channel tiles of the scalar kernel, the second writing to t2); same weights, same summation order
-        Op o{};
-        o.type = 1;
-        o.n = 3;
+    // two convs reading the same tensor on every level: one launch with the output channels concatenated and a split epilogue (a's couta
+    // channels -> outa at coffa, c's coutc -> outc); same weights, same summation order as the two separate convs
+    auto add_c3_pair_levels = [&](const float *const in[3], int cin, const char *na, int couta, float *const outa[3], int coffa, const char *nc,
+                                  int coutc, float *const outc[3]) {
+        Conv3Op o{{}, 3};
         for (int k = 0; k < 3; ++k) {
-            const std::string pa = "ssh" + std::to_string(k + 1) + ".conv5X5_2", pb = "ssh" + std::to_string(k + 1) + ".conv7X7_2";
-            fold_conv3(b, pa + ".0", pa + ".1", 16, 16, w, bias);
-            fold_conv3(b, pb + ".0", pb + ".1", 16, 16, w2, bias2);
-            std::vector<float> wc((size_t)16 * 9 * 32), bc(bias);
-            bc.insert(bc.end(), bias2.begin(), bias2.end());
-            for (size_t row = 0; row < (size_t)16 * 9; ++row) {
-                std::copy(w.begin() + row * 16, w.begin() + (row + 1) * 16, wc.begin() + row * 32);
-                std::copy(w2.begin() + row * 16, w2.begin() + (row + 1) * 16, wc.begin() + row * 32 + 16);
-            }
-            o.c3[k] = Conv3Args{t1[k], cat[k], arena.upload(wc), arena.upload(bc), B, 16, fh[k], fw[k], 32, fh[k], fw[k], 1, 1, 64, 32};
-            {
-                const std::vector<uint16_t> ph = pack_conv3_split(wc, 16, 32);  // round 5: the 16-channel SSH convs on the split-fp16 matrix-core kernel
-                if (!ph.empty()) o.c3[k].wh = reinterpret_cast<const half_t *>(arena.upload(ph));
-            }
-            o.c3[k].out2 = t2[k];
-            o.c3[k].split = 16;
-            o.c3[k].out2_ctotal = 16;
-            o.c3[k].out2_coff = 0;
-            flops_per_frame += 2.0 * 16 * 9 * 32 * fh[k] * fw[k];
+            fold_conv3_pair(b, ssh(k, na), couta, ssh(k, nc), coutc, cin, w, bias);
+            o.p[k] = conv3_op(in[k], outa[k], w, bias, cin, couta + coutc, fh[k], fw[k], 1, 64, coffa);
+            if (!o.p[k].wh) raise(FRT_ERR_INVALID, "detector: fused SSH conv shape not covered");
+            o.p[k].out2 = outc[k];
+            o.p[k].split = couta;
+            o.p[k].out2_ctotal = 16;
+            o.p[k].out2_coff = 0;
+        }
+        ops.push_back(o);
+    };
+    add_c3_pair_levels(pyr, 64, "conv3X3", 32, cat, 0, "conv5X5_1", 16, t1);  // -> cat[0:32], t1
+    add_c3_pair_levels(t1, 16, "conv5X5_2", 16, cat, 32, "conv7X7_2", 16, t2);  // -> cat[32:48], t2
+    {
+        Conv3Op o{{}, 3};
+        for (int k = 0; k < 3; ++k) {
+            fold_conv3(b, ssh(k, "conv7x7_3") + ".0", ssh(k, "conv7x7_3") + ".1", 16, 16, w, bias);
+            o.p[k] = conv3_op(t2[k], cat[k], w, bias, 16, 16, fh[k], fw[k], 1, 64, 48);
         }
         ops.push_back(o);
     }
-    add_c3_levels(t2, cat, "conv7x7_3", 16, 16, fh, fw, 64, 48);
-    Op ho{};
-    ho.type = 2;
-    ho.n = 3;
+    HeadsOp ho{{}, 3};
     for (int k = 0; k < 3; ++k) {
-        const std::string hb = "BboxHead." + std::to_string(k) + ".conv1x1", hc = "ClassHead." + std::to_string(k) + ".conv1x1";
-        const float *wb = b.get(hb + ".weight", 8 * 64).data, *wc = b.get(hc + ".weight", 4 * 64).data;
-        std::vector<float> tb(64 * 8), tc(64 * 4);
-        for (int co = 0; co < 8; ++co)
-            for (int ci = 0; ci < 64; ++ci) tb[ci * 8 + co] = wb[co * 64 + ci];
-        for (int co = 0; co < 4; ++co)
-            for (int ci = 0; ci < 64; ++ci) tc[ci * 4 + co] = wc[co * 64 + ci];
-        std::vector<float> bb(b.get(hb + ".bias", 8).data, b.get(hb + ".bias", 8).data + 8);
-        std::vector<float> bc(b.get(hc + ".bias", 4).data, b.get(hc + ".bias", 4).data + 4);
-        ho.hd[k] = HeadArgs{cat[k], arena.upload(tb), arena.upload(bb), arena.upload(tc), arena.upload(bc), d_loc, d_conf, B, 64, fh[k], fw[k], g.A, g.base[k],
-                            nullptr, nullptr, nullptr};
+        std::vector<float> wc, bc;
+        pw_bias(b, "BboxHead." + std::to_string(k) + ".conv1x1", 8, 64, w, bias);
+        pw_bias(b, "ClassHead." + std::to_string(k) + ".conv1x1", 4, 64, wc, bc);
+        ho.p[k] = HeadArgs{cat[k], arena.upload(w), arena.upload(bias), arena.upload(wc), arena.upload(bc), d_loc, d_conf, max_batch, 64, fh[k], fw[k], g.A,
+                           g.base[k], nullptr, nullptr, nullptr};
         flops_per_frame += 2.0 * fh[k] * fw[k] * 64 * 12;
         if (has_landmarks) {
-            const std::string hl = "LandmarkHead." + std::to_string(k) + ".conv1x1";
-            const float *wl = b.get(hl + ".weight", 20 * 64).data, *bl = b.get(hl + ".bias", 20).data;
-            std::vector<float> tl(64 * 20), blv(bl, bl + 20);
-            for (int co = 0; co < 20; ++co)
-                for (int ci = 0; ci < 64; ++ci) tl[ci * 20 + co] = wl[co * 64 + ci];
-            ho.hd[k].wl = arena.upload(tl);
-            ho.hd[k].bl = arena.upload(blv);
-            ho.hd[k].ldm = d_ldm;
+            pw_bias(b, "LandmarkHead." + std::to_string(k) + ".conv1x1", 20, 64, w, bias);
+            ho.p[k].wl = arena.upload(w);
+            ho.p[k].bl = arena.upload(bias);
+            ho.p[k].ldm = d_ldm;
             flops_per_frame += 2.0 * fh[k] * fw[k] * 64 * 20;
         }
     }
@@ -487,12 +454,7 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
     float *cur = act(16, ch, cw);
     {  // conv1 = conv_bn(3, 16, 2): preprocess + the generic first conv (the fused u8 first conv covers mnet's Cout = 8 only)
         fold_conv3(b, "conv1.0", "conv1.1", 16, 3, w, bias);
-        Op o{};
-        o.type = 1;
-        o.n = 1;
-        o.c3[0] = Conv3Args{d_input, cur, arena.upload(w), arena.upload(bias), B, 3, H, W, 16, ch, cw, 2, 1, 16, 0};
-        ops.push_back(o);
-        flops_per_frame += 2.0 * 3 * 9 * 16 * ch * cw;
+        ops.push_back(Conv3Op{{conv3_op(d_input, cur, w, bias, 3, 16, H, W, 2, 16, 0)}, 1});
     }
     const float *feat[4];
     int fh[4], fw[4];
@@ -503,8 +465,6 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
         if (rfb && i == 6) {  // conv8 = BasicRFB(64, 64, scale = 1.0): 5 launches (kernels_det_slim.hip)
             const int HW = ch * cw;
             float *red = act(24, ch, cw), *sc = act(64, ch, cw), *ta = act(44, ch, cw), *tb = act(16, ch, cw), *cat = act(48, ch, cw);
-            Op o{};
-            o.type = 6;
             std::vector<float> wp((size_t)64 * 88), bp(88);
             for (int j = 0; j < 3; ++j) {
                 const std::string q = "conv8.branch" + std::to_string(j) + ".0";
@@ -517,8 +477,7 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
             for (int ci = 0; ci < 64; ++ci)
                 for (int co = 0; co < 64; ++co) wp[(size_t)ci * 88 + 24 + co] = w2[(size_t)ci * 64 + co];
             for (int co = 0; co < 64; ++co) bp[24 + co] = bias2[co];
-            o.rp = RfbProjArgs{cur, arena.upload(wp), arena.upload(bp), red, sc, B, ch, cw};
-            ops.push_back(o);
+            ops.push_back(RfbProjArgs{cur, arena.upload(wp), arena.upload(bp), red, sc, B, ch, cw});
             flops_per_frame += 2.0 * HW * 64 * 88;
             // 3x3 convs: {branch.index, cin, cout, dilation, relu, in, in_ctotal, in_coff, out, out_ctotal, out_coff}
             struct C3 {
@@ -535,12 +494,10 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
                                      {{"branch0.2", 16, 16, 2, 0, ta, 44, 0, cat, 48, 0}, {"branch1.2", 16, 16, 3, 0, ta, 44, 16, cat, 48, 16},
                                       {"branch2.3", 16, 16, 5, 0, tb, 16, 0, cat, 48, 32}}};
             for (int st = 0; st < 3; ++st) {
-                Op c{};
-                c.type = 7;
-                c.n = st == 1 ? 1 : 3;
-                c.rc.B = B;
-                c.rc.H = ch;
-                c.rc.W = cw;
+                RfbConvOp c{{}, st == 1 ? 1 : 3};
+                c.a.B = B;
+                c.a.H = ch;
+                c.a.W = cw;
                 for (int k = 0; k < c.n; ++k) {
                     const C3 &d = stages[st][k];
                     const std::string q = std::string("conv8.") + d.name;
@@ -550,24 +507,20 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
                     for (size_t r = 0; r < (size_t)d.cin * 9; ++r)
                         for (int co = 0; co < d.cout; ++co) wpad[r * 16 + co] = w[r * d.cout + co];
                     for (int co = 0; co < d.cout; ++co) bpad[co] = bias[co];
-                    c.rc.p[k] = RfbConvArgs{d.in, d.out, arena.upload(wpad), arena.upload(bpad), d.cin, d.cout, d.dil, d.relu, d.ict, d.ico, d.oct, d.oco};
+                    c.a.p[k] = RfbConvArgs{d.in, d.out, arena.upload(wpad), arena.upload(bpad), d.cin, d.cout, d.dil, d.relu, d.ict, d.ico, d.oct, d.oco};
                     flops_per_frame += 2.0 * HW * d.cin * 9 * d.cout;
                 }
-                for (int k = c.n; k < 3; ++k) c.rc.p[k] = c.rc.p[0];
+                for (int k = c.n; k < 3; ++k) c.a.p[k] = c.a.p[0];
                 ops.push_back(c);
             }
-            Op t{};
-            t.type = 8;
             fold_pw(b, "conv8.ConvLinear.conv", "conv8.ConvLinear.bn", 64, 48, w2, bias2);
-            t.rt = RfbTailArgs{cat, arena.upload(w2), arena.upload(bias2), sc, out, 1.0f, B, ch, cw};
-            ops.push_back(t);
+            ops.push_back(RfbTailArgs{cat, arena.upload(w2), arena.upload(bias2), sc, out, 1.0f, B, ch, cw});
             flops_per_frame += 2.0 * HW * 48 * 64;
         } else {
             const std::string p = "conv" + std::to_string(i + 2);
             fold_dw(b, p + ".0", p + ".1", cin, w, bias);
             fold_pw(b, p + ".3", p + ".4", cout, cin, w2, bias2);
             ops.push_back(dwpw_op(cur, out, w, bias, w2, bias2, cin, cout, ch, cw, oh, ow, stride));
-            flops_per_frame += 2.0 * oh * ow * (9.0 * cin + (double)cin * cout);
         }
         cur = out;
         ch = oh;
@@ -582,20 +535,12 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
     {  // conv14: 1x1 256 -> 64 + bias + ReLU, then depth_conv2d(64, 256, 3, stride 2) + ReLU (a conv_dw block with biases for BN)
         float *mid = act(64, ch, cw);
         pw_bias(b, "conv14.0", 64, 256, w2, bias2);
-        Op o{};
-        o.type = 0;
-        o.dw = DwPwArgs{cur, mid, nullptr, nullptr, arena.upload(w2), arena.upload(bias2), nullptr, 0, 0, B, 256, ch, cw, 64, ch, cw, 1, 1,
-                        nullptr, nullptr, nullptr};
-        const std::vector<uint16_t> ph = pack_pw_split(w2, 256, 64);
-        if (!ph.empty()) o.dw.wph = reinterpret_cast<const half_t *>(arena.upload(ph));
-        ops.push_back(o);
-        flops_per_frame += 2.0 * ch * cw * 256 * 64;
+        ops.push_back(pw_op(cur, mid, w2, bias2, 256, 64, ch, cw, nullptr, 0, 0));
         const int oh = conv_out(ch, 2), ow = conv_out(cw, 2);
         float *out = act(256, oh, ow);
         dw_bias(b, "conv14.2.0", 64, w, bias);
         pw_bias(b, "conv14.2.2", 256, 64, w2, bias2);
         ops.push_back(dwpw_op(mid, out, w, bias, w2, bias2, 64, 256, ch, cw, oh, ow, 2));
-        flops_per_frame += 2.0 * oh * ow * (9.0 * 64 + 64.0 * 256);
         feat[3] = out;
         fh[3] = oh;
         fw[3] = ow;
@@ -605,14 +550,12 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
     const char *heads[3] = {"loc", "conf", "landm"};
     const int per[3] = {4, 2, 10}, chan0[3] = {0, 12, 18};  // channel offsets of the three heads in the kernels' 48-channel layout
     const int nh = has_landmarks ? 3 : 2;
-    Op ho{};
-    ho.type = 4;
-    ho.n = 3;
-    ho.sh.loc = d_loc;
-    ho.sh.conf = d_conf;
-    ho.sh.ldm = has_landmarks ? d_ldm : nullptr;
-    ho.sh.B = B;
-    ho.sh.A = g.A;
+    SlimHeadsOp ho{{}, 3};
+    ho.a.loc = d_loc;
+    ho.a.conf = d_conf;
+    ho.a.ldm = has_landmarks ? d_ldm : nullptr;
+    ho.a.B = B;
+    ho.a.A = g.A;
     for (int k = 0; k < 3; ++k) {
         const int C = SLIM_HEAD_C[k], na = SLIM_NA[k];
         std::vector<float> wd((size_t)C * 30, 0.f), wp((size_t)C * 48, 0.f), bp(48, 0.f);
@@ -630,7 +573,7 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
             for (int co = 0; co < co_n; ++co) bp[chan0[h] + co] = bias2[co];
             flops_per_frame += 2.0 * fh[k] * fw[k] * C * (9.0 + co_n);
         }
-        ho.sh.lv[k] = SlimHeadArgs{feat[k], arena.upload(wd), arena.upload(wp), arena.upload(bp), C, fh[k], fw[k], na, g.base[k]};
+        ho.a.lv[k] = SlimHeadArgs{feat[k], arena.upload(wd), arena.upload(wp), arena.upload(bp), C, fh[k], fw[k], na, g.base[k]};
     }
     ops.push_back(ho);
     {  // level 3: loc / conf / landm = dense 3x3 convs 256 -> 12 / 6 / 30 (+ bias), one launch with the channels concatenated
@@ -648,11 +591,8 @@ void frt_detector::build_slim(const frt::Blob &b, bool rfb) {
             }
             off += co_n;
         }
-        Op o{};
-        o.type = 5;
-        o.dh = DenseHeadArgs{feat[3], arena.upload(wc), arena.upload(bc), d_loc, d_conf, has_landmarks ? d_ldm : nullptr, B, 256, fh[3], fw[3], na, cout, cpad, g.A,
-                             g.base[3]};
-        ops.push_back(o);
+        ops.push_back(DenseHeadArgs{feat[3], arena.upload(wc), arena.upload(bc), d_loc, d_conf, has_landmarks ? d_ldm : nullptr, B, 256, fh[3], fw[3], na, cout,
+                                    cpad, g.A, g.base[3]});
         flops_per_frame += 2.0 * fh[3] * fw[3] * 256 * 9 * cout;
     }
 }
@@ -663,67 +603,27 @@ void frt_detector::preprocess(const uint8_t *frames_dev, int n, size_t row_strid
 }
 
 void frt_detector::forward_frames(const uint8_t *frames_dev, int n, size_t row_stride, size_t frame_stride, hipStream_t s) {
-    if (g.frame_h == g.in_h && g.frame_w == g.in_w && !ops.empty() && ops[0].type == 1 && ops[0].n == 1) {
-        Conv3Args c = ops[0].c3[0];
+    // the one place that knows how many leading ops a fused kernel stood in for: the stem kernel for ops 0 - 2, the u8 first conv for op 0
+    int done = 0;
+    if (const Stem st = stem(); st.c && g.frame_h == g.in_h && g.frame_w == g.in_w) {
+        Conv3Args c = *st.c;
         c.B = n;
-        if (ops.size() >= 3 && ops[1].type == 0 && ops[2].type == 0) {  // first conv + the first two conv_dw blocks in one kernel
-            bool stem;
-            {
-                ProfScope ps(2, "det_stem", (double)n * g.frame_h * g.frame_w * 3, s);
-                stem = launch_det_stem(frames_dev, row_stride, frame_stride, c, ops[1].dw, ops[2].dw, s);
-            }
-            if (stem) return forward(n, s, 3);
+        if (st.d1) {  // first conv + the first two conv_dw blocks in one kernel
+            ProfScope ps(2, "det_stem", (double)n * g.frame_h * g.frame_w * 3, s);
+            if (launch_det_stem(frames_dev, row_stride, frame_stride, c, *st.d1, *st.d2, s)) done = 3;
         }
-        bool fused;
-        {
+        if (!done) {
             ProfScope ps(2, "det_preprocess", (double)n * g.frame_h * g.frame_w * 3, s);  // fused into the first conv
-            fused = launch_det_conv1_u8(frames_dev, row_stride, frame_stride, c, s);
+            if (launch_det_conv1_u8(frames_dev, row_stride, frame_stride, c, s)) done = 1;
         }
-        if (fused) return forward(n, s, 1);
     }
-    preprocess(frames_dev, n, row_stride, frame_stride, s);
-    forward(n, s);
+    if (!done) preprocess(frames_dev, n, row_stride, frame_stride, s);
+    forward(n, s, done);
 }
 
 void frt_detector::forward(int n, hipStream_t s, int first_op) {
     ProfScope ps(2, "det_network", flops_per_frame * n, s);
-    int skip = first_op;
-    for (Op &o : ops) {
-        if (skip > 0) {
-            --skip;
-            continue;
-        }
-        if (o.type == 3) {
-            for (int k = 0; k < o.n; ++k) o.c3[k].B = n;
-            if (launch_conv3x3_split(o.c3, o.n, s) || launch_conv3x3_mfma(o.c3, o.n, s)) skip = 2;  // else: the two separate convs
-            continue;
-        }
-        if (o.type == 0) {
-            o.dw.B = n;
-            launch_dwpw(o.dw, s);
-        } else if (o.type == 1) {
-            for (int k = 0; k < o.n; ++k) o.c3[k].B = n;
-            launch_conv3x3_multi(o.c3, o.n, s);
-        } else if (o.type == 4) {
-            o.sh.B = n;
-            launch_slim_heads(o.sh, o.n, s);
-        } else if (o.type == 5) {
-            o.dh.B = n;
-            launch_dense_head(o.dh, s);
-        } else if (o.type == 6) {
-            o.rp.B = n;
-            launch_rfb_proj(o.rp, s);
-        } else if (o.type == 7) {
-            o.rc.B = n;
-            launch_rfb_conv(o.rc, o.n, s);
-        } else if (o.type == 8) {
-            o.rt.B = n;
-            launch_rfb_tail(o.rt, s);
-        } else {
-            for (int k = 0; k < o.n; ++k) o.hd[k].B = n;
-            launch_heads_multi(o.hd, o.n, s);
-        }
-    }
+    for (size_t i = first_op; i < ops.size(); ++i) std::visit([&](auto &a) { run(a, n, s); }, ops[i]);
     HIPCHK(hipGetLastError());  // a failed launch (e.g. the dynamic-LDS opt-in missing on this device) must not pass silently
 }
 
@@ -737,6 +637,50 @@ void frt_detector::postprocess(int n, hipStream_t s, frt_bbox *boxes_out, int *n
     HIPCHK(hipGetLastError());
 }
 
+namespace {
+
+// frt_detector_find_faces_batch, and with landmarks_out frt_detector_find_faces_landmarks
+void find_faces(frt_detector *d, const uint8_t *bgr, int n_frames, int rows, int cols, size_t row_stride, size_t frame_stride, frt_bbox *out,
+                float *landmarks_out, int *n_out) {
+    if (!d || !bgr || !out || !n_out) raise(FRT_ERR_INVALID, "null argument");
+    if (landmarks_out && !d->has_landmarks) raise(FRT_ERR_FORMAT, "findFaceLandmarks: the detector blob has no LandmarkHead (trimmed export)");
+    if (rows != d->g.frame_h || cols != d->g.frame_w) raise(FRT_ERR_INVALID, "findFace: frame must be frameWidth x frameHeight");
+    if (n_frames < 1 || n_frames > d->max_batch) raise(FRT_ERR_CAPACITY, "findFace: more frames than det_maxBatchSize");
+    std::lock_guard<std::mutex> lk(d->mu);
+    use_device(d->device);
+    hipStream_t s = d->stream;
+    d->wait_idle(s);
+    const size_t tight = (size_t)cols * 3;
+    for (int f = 0; f < n_frames; ++f)
+        HIPCHK(hipMemcpy2DAsync(d->d_frames + (size_t)f * rows * tight, tight, bgr + (size_t)f * frame_stride, row_stride, tight, rows,
+                                hipMemcpyHostToDevice, s));
+    d->forward_frames(d->d_frames, n_frames, tight, (size_t)rows * tight, s);
+    d->postprocess(n_frames, s);
+    HIPCHK(hipMemcpyAsync(out, d->d_boxes, sizeof(frt_bbox) * n_frames * d->g.max_faces, hipMemcpyDeviceToHost, s));
+    if (landmarks_out) HIPCHK(hipMemcpyAsync(landmarks_out, d->d_landmarks, sizeof(float) * 10 * n_frames * d->g.max_faces, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(n_out, d->d_nout, sizeof(int) * n_frames, hipMemcpyDeviceToHost, s));
+    sync_stream_spinning(s);
+}
+
+// frt_detector_infer, and with ldm_out frt_detector_infer_landmarks
+void infer(frt_detector *d, const float *chw, int batch, float *loc_out, float *conf_out, float *ldm_out) {
+    if (!d || !chw || !loc_out || !conf_out) raise(FRT_ERR_INVALID, "null argument");
+    if (ldm_out && !d->has_landmarks) raise(FRT_ERR_FORMAT, "doInference: the detector blob has no LandmarkHead (trimmed export)");
+    if (batch < 1 || batch > d->max_batch) raise(FRT_ERR_CAPACITY, "doInference: batch exceeds det_maxBatchSize");
+    std::lock_guard<std::mutex> lk(d->mu);
+    use_device(d->device);
+    hipStream_t s = d->stream;
+    d->wait_idle(s);
+    const size_t in_elems = (size_t)3 * d->g.in_h * d->g.in_w;
+    HIPCHK(hipMemcpyAsync(d->d_input, chw, sizeof(float) * in_elems * batch, hipMemcpyHostToDevice, s));
+    d->forward(batch, s);
+    HIPCHK(hipMemcpyAsync(loc_out, d->d_loc, sizeof(float) * (size_t)batch * d->g.A * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(conf_out, d->d_conf, sizeof(float) * (size_t)batch * d->g.A * 2, hipMemcpyDeviceToHost, s));
+    if (ldm_out) HIPCHK(hipMemcpyAsync(ldm_out, d->d_ldm, sizeof(float) * (size_t)batch * d->g.A * 10, hipMemcpyDeviceToHost, s));
+    sync_stream_spinning(s);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -804,10 +748,10 @@ int frt_detector_create(const char *weights_path, int frame_w, int frame_h, int 
         // scratch of the split depthwise -> pointwise path: the largest depthwise intermediate of the built conv_dw ops
         size_t tmp = B * 64 * (size_t)g.fh[0] * g.fw[0];
         for (const auto &o : d->ops)
-            if (o.type == 0 && o.dw.wd) tmp = std::max(tmp, B * o.dw.Cin * (size_t)o.dw.Ho * o.dw.Wo);
+            if (const DwPwArgs *dw = std::get_if<DwPwArgs>(&o); dw && dw->wd) tmp = std::max(tmp, B * dw->Cin * (size_t)dw->Ho * dw->Wo);
         d->d_tmp = d->arena.alloc<float>(tmp);
         for (auto &o : d->ops)
-            if (o.type == 0 && o.dw.wd) o.dw.tmp = d->d_tmp;
+            if (DwPwArgs *dw = std::get_if<DwPwArgs>(&o); dw && dw->wd) dw->tmp = d->d_tmp;
         HIPCHK(hipDeviceSynchronize());
         *out = d.release();
     });
@@ -852,24 +796,7 @@ int frt_detector_geometry(const frt_detector *d, int *frame_w, int *frame_h, int
 
 int frt_detector_find_faces_batch(frt_detector *d, const uint8_t *bgr, int n_frames, int rows, int cols, size_t row_stride,
                                   size_t frame_stride, frt_bbox *out, int *n_out) {
-    return guarded([&] {
-        if (!d || !bgr || !out || !n_out) raise(FRT_ERR_INVALID, "null argument");
-        if (rows != d->g.frame_h || cols != d->g.frame_w) raise(FRT_ERR_INVALID, "findFace: frame must be frameWidth x frameHeight");
-        if (n_frames < 1 || n_frames > d->max_batch) raise(FRT_ERR_CAPACITY, "findFace: more frames than det_maxBatchSize");
-        std::lock_guard<std::mutex> lk(d->mu);
-        use_device(d->device);
-        hipStream_t s = d->stream;
-        d->wait_idle(s);
-        const size_t tight = (size_t)cols * 3;
-        for (int f = 0; f < n_frames; ++f)
-            HIPCHK(hipMemcpy2DAsync(d->d_frames + (size_t)f * rows * tight, tight, bgr + (size_t)f * frame_stride, row_stride, tight, rows,
-                                    hipMemcpyHostToDevice, s));
-        d->forward_frames(d->d_frames, n_frames, tight, (size_t)rows * tight, s);
-        d->postprocess(n_frames, s);
-        HIPCHK(hipMemcpyAsync(out, d->d_boxes, sizeof(frt_bbox) * n_frames * d->g.max_faces, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(n_out, d->d_nout, sizeof(int) * n_frames, hipMemcpyDeviceToHost, s));
-        sync_stream_spinning(s);
-    });
+    return guarded([&] { find_faces(d, bgr, n_frames, rows, cols, row_stride, frame_stride, out, nullptr, n_out); });
 }
 
 int frt_detector_find_faces(frt_detector *d, const uint8_t *bgr, int rows, int cols, size_t row_stride, frt_bbox *out, int *n_out) {
@@ -881,21 +808,8 @@ int frt_detector_has_landmarks(const frt_detector *d) { return d && d->has_landm
 int frt_detector_find_faces_landmarks(frt_detector *d, const uint8_t *bgr, int rows, int cols, size_t row_stride, frt_bbox *out,
                                       float *landmarks_out, int *n_out) {
     return guarded([&] {
-        if (!d || !bgr || !out || !n_out || !landmarks_out) raise(FRT_ERR_INVALID, "null argument");
-        if (!d->has_landmarks) raise(FRT_ERR_FORMAT, "findFaceLandmarks: the detector blob has no LandmarkHead (trimmed export)");
-        if (rows != d->g.frame_h || cols != d->g.frame_w) raise(FRT_ERR_INVALID, "findFace: frame must be frameWidth x frameHeight");
-        std::lock_guard<std::mutex> lk(d->mu);
-        use_device(d->device);
-        hipStream_t s = d->stream;
-        d->wait_idle(s);
-        const size_t tight = (size_t)cols * 3;
-        HIPCHK(hipMemcpy2DAsync(d->d_frames, tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice, s));
-        d->forward_frames(d->d_frames, 1, tight, (size_t)rows * tight, s);
-        d->postprocess(1, s);
-        HIPCHK(hipMemcpyAsync(out, d->d_boxes, sizeof(frt_bbox) * d->g.max_faces, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(landmarks_out, d->d_landmarks, sizeof(float) * 10 * d->g.max_faces, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(n_out, d->d_nout, sizeof(int), hipMemcpyDeviceToHost, s));
-        sync_stream_spinning(s);
+        if (!landmarks_out) raise(FRT_ERR_INVALID, "null argument");
+        find_faces(d, bgr, 1, rows, cols, row_stride, row_stride * (size_t)rows, out, landmarks_out, n_out);
     });
 }
 
@@ -916,38 +830,13 @@ int frt_detector_preprocess(frt_detector *d, const uint8_t *bgr, int rows, int c
 }
 
 int frt_detector_infer(frt_detector *d, const float *chw, int batch, float *loc_out, float *conf_out) {
-    return guarded([&] {
-        if (!d || !chw || !loc_out || !conf_out) raise(FRT_ERR_INVALID, "null argument");
-        if (batch < 1 || batch > d->max_batch) raise(FRT_ERR_CAPACITY, "doInference: batch exceeds det_maxBatchSize");
-        std::lock_guard<std::mutex> lk(d->mu);
-        use_device(d->device);
-        hipStream_t s = d->stream;
-        d->wait_idle(s);
-        const size_t in_elems = (size_t)3 * d->g.in_h * d->g.in_w;
-        HIPCHK(hipMemcpyAsync(d->d_input, chw, sizeof(float) * in_elems * batch, hipMemcpyHostToDevice, s));
-        d->forward(batch, s);
-        HIPCHK(hipMemcpyAsync(loc_out, d->d_loc, sizeof(float) * (size_t)batch * d->g.A * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(conf_out, d->d_conf, sizeof(float) * (size_t)batch * d->g.A * 2, hipMemcpyDeviceToHost, s));
-        sync_stream_spinning(s);
-    });
+    return guarded([&] { infer(d, chw, batch, loc_out, conf_out, nullptr); });
 }
 
 int frt_detector_infer_landmarks(frt_detector *d, const float *chw, int batch, float *loc_out, float *conf_out, float *ldm_out) {
     return guarded([&] {
-        if (!d || !chw || !loc_out || !conf_out || !ldm_out) raise(FRT_ERR_INVALID, "null argument");
-        if (!d->has_landmarks) raise(FRT_ERR_FORMAT, "doInference: the detector blob has no LandmarkHead (trimmed export)");
-        if (batch < 1 || batch > d->max_batch) raise(FRT_ERR_CAPACITY, "doInference: batch exceeds det_maxBatchSize");
-        std::lock_guard<std::mutex> lk(d->mu);
-        use_device(d->device);
-        hipStream_t s = d->stream;
-        d->wait_idle(s);
-        const size_t in_elems = (size_t)3 * d->g.in_h * d->g.in_w;
-        HIPCHK(hipMemcpyAsync(d->d_input, chw, sizeof(float) * in_elems * batch, hipMemcpyHostToDevice, s));
-        d->forward(batch, s);
-        HIPCHK(hipMemcpyAsync(loc_out, d->d_loc, sizeof(float) * (size_t)batch * d->g.A * 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(conf_out, d->d_conf, sizeof(float) * (size_t)batch * d->g.A * 2, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(ldm_out, d->d_ldm, sizeof(float) * (size_t)batch * d->g.A * 10, hipMemcpyDeviceToHost, s));
-        sync_stream_spinning(s);
+        if (!ldm_out) raise(FRT_ERR_INVALID, "null argument");
+        infer(d, chw, batch, loc_out, conf_out, ldm_out);
     });
 }
 

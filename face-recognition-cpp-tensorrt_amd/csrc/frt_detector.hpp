@@ -1,5 +1,7 @@
 // struct frt_detector: the object behind frt_detector_* (include/frt.h).  Internal header of libfrt.so.
 #pragma once
+#include <variant>
+
 #include "frt_internal.hpp"
 
 struct DetLayout {
@@ -24,20 +26,33 @@ struct frt_detector {
     Arena arena;
     DetGeom g{};
     int max_batch = 1;
-    struct Op {
-        int type;  // 0 dwpw, 1 conv3x3 (n same-shaped problems, one per pyramid level), 2 heads (n levels), 3 fused conv3x3 pair
+    // One launch of the network.  An op is the argument struct of the kernel family that runs it; the kinds that run up to three problems in
+    // one launch (one per pyramid level, or the parallel RFB branches) keep the count of live problems next to them.
+    struct Conv3Op {      // n same-shaped 3x3 convs (launch_conv3x3_multi); n == 1: a single conv
+        Conv3Args p[3];
         int n;
-        DwPwArgs dw;
-        Conv3Args c3[3];
-        HeadArgs hd[3];
-        // Slim / RFB (kernels_det_slim.hip): 4 heads of levels 0-2, 5 dense head of level 3, 6 RFB projections, 7 RFB 3x3 convs (n problems),
-        // 8 RFB tail
-        SlimHeadsArgs sh;
-        DenseHeadArgs dh;
-        RfbProjArgs rp;
-        RfbConvMulti rc;
-        RfbTailArgs rt;
     };
+    struct HeadsOp {      // mnet0.25 bbox / class / landmark heads of n levels
+        HeadArgs p[3];
+        int n;
+    };
+    struct SlimHeadsOp {  // Slim / RFB heads of levels 0 .. n-1 (kernels_det_slim.hip)
+        SlimHeadsArgs a;
+        int n;
+    };
+    struct RfbConvOp {    // n 3x3 convs of BasicRFB on the same map
+        RfbConvMulti a;
+        int n;
+    };
+    // DwPwArgs: a conv_dw block or a plain 1x1 conv; DenseHeadArgs: Slim / RFB head of level 3; RfbProjArgs / RfbTailArgs: BasicRFB's 1x1 convs
+    using Op = std::variant<DwPwArgs, Conv3Op, HeadsOp, SlimHeadsOp, DenseHeadArgs, RfbProjArgs, RfbConvOp, RfbTailArgs>;
+    // The leading ops a fused kernel may stand in for.  c: op 0 when it is a single 3x3 conv (launch_det_conv1_u8); d1, d2: ops 1 and 2 when c
+    // is set and both are DwPwArgs (launch_det_stem: ops 0 - 2).  Null otherwise.  The kernels' launchers decide from the arguments whether they apply.
+    struct Stem {
+        Conv3Args *c = nullptr;
+        DwPwArgs *d1 = nullptr, *d2 = nullptr;
+    };
+    Stem stem();
     int family = 1;  // blob kind: 1 mnet0.25, 4 Slim, 5 RFB
     float *d_tmp = nullptr;  // depthwise intermediate of the split conv_dw path
     float *d_wave_zeros = nullptr;  // zeros for dwpw_wave_kernel (input rows outside the image)
@@ -56,11 +71,16 @@ struct frt_detector {
     float *d_landmarks = nullptr;  // decoded, frame coordinates [B][max_faces][10]
 
     void build(const frt::Blob &b);
-    Op dwpw_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias, const std::vector<float> &w2,
-               const std::vector<float> &bias2, int cin, int cout, int h, int w_, int oh, int ow, int stride);
+    // the builders of one op's arguments: weights uploaded in every layout their kernels may use, flops_per_frame advanced
+    DwPwArgs dwpw_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias, const std::vector<float> &w2,
+                     const std::vector<float> &bias2, int cin, int cout, int h, int w_, int oh, int ow, int stride);
+    DwPwArgs pw_op(const float *in, float *out, const std::vector<float> &w2, const std::vector<float> &bias2, int cin, int cout, int h, int w_,
+                   const float *add, int add_h, int add_w);
+    Conv3Args conv3_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias, int cin, int cout, int h, int w_,
+                       int stride, int ctotal, int coff);
     void build_slim(const frt::Blob &b, bool rfb);  // kinds 4 / 5 (net_slim.py, net_rfb.py)
-    void forward(int n, hipStream_t s, int first_op = 0);  // d_input -> d_loc/d_conf (first_op = 1: op 0 already ran)
-    // preprocess + forward; when the letterbox is the identity the first conv reads the u8 frames and d_input is never written
+    void forward(int n, hipStream_t s, int first_op = 0);  // d_input -> d_loc/d_conf; ops before first_op already ran (forward_frames)
+    // preprocess + forward; when the letterbox is the identity the stem kernel or the first conv reads the u8 frames and d_input is never written
     void forward_frames(const uint8_t *frames_dev, int n, size_t row_stride, size_t frame_stride, hipStream_t s);
     void postprocess(int n, hipStream_t s, frt_bbox *boxes_out = nullptr, int *nout_out = nullptr, float *landmarks_out = nullptr);  // d_loc/d_conf -> boxes (default: d_boxes/d_nout/d_landmarks)
     void preprocess(const uint8_t *frames_dev, int n, size_t row_stride, size_t frame_stride, hipStream_t s);

@@ -160,10 +160,7 @@ struct Conv3Args {
     const float *w, *b;     // [Cin][9][Cout] (transposed), bias [Cout]
     int B, Cin, H, W, Cout, Ho, Wo, stride, relu;
     int out_ctotal, out_coff;  // write into channels [coff, coff+Cout) of a [B][ctotal][Ho][Wo] tensor
-    // matrix-core path (kernels_det_conv3.hip); all optional
-    const float *wm;           // host-packed weights [9][Cin/wm_kc][wm_cpad][wm_kc] (zero rows beyond Cout); null: scalar kernel only
-    int wm_kc, wm_cpad;
-    const half_t *wh;          // fp16 hi/lo split weights [Cin/16][9][64][hi16|lo16] (kernels_det_conv3h.hip, Cin == 64); null: n/a
+    const half_t *wh;          // matrix-core path, optional: fp16 hi/lo split weights [Cin/16][9][64][hi16|lo16] (kernels_det_conv3h.hip); null: scalar kernels only
     float *out2;               // channels >= split go to out2 (channel co - split of a [B][out2_ctotal][Ho][Wo] tensor, + out2_coff)
     int split, out2_ctotal, out2_coff;
 };
@@ -174,11 +171,7 @@ void det_stem_pack(const Conv3Args &c, const DwPwArgs &d1, const DwPwArgs &d2, f
 bool launch_det_stem(const uint8_t *frames, size_t row_stride, size_t frame_stride, const Conv3Args &c, const DwPwArgs &d1, const DwPwArgs &d2, hipStream_t s);
 // first detector conv fed by the u8 frames directly (only valid when the letterbox is the identity); false: not applicable
 bool launch_det_conv1_u8(const uint8_t *frames, size_t row_stride, size_t frame_stride, const Conv3Args &a, hipStream_t s);
-// (A fused "stem" kernel - first conv + the two conv_dw blocks behind it with the intermediates in LDS - was tried and removed:
-//  436-840 us against 302 us for the three separate kernels; with ~1150 weights it either spills SGPRs or hoists every LDS weight
-//  read into 290 VGPRs, and the halo recompute plus LDS traffic eat the HBM saving.)
-bool launch_conv3x3_split(const Conv3Args *a, int n, hipStream_t s);  // fp16 hi/lo split MFMA version (Cin == 64); false: n/a
-bool launch_conv3x3_mfma(const Conv3Args *a, int n, hipStream_t s);   // false: shape not covered, use the scalar kernel
+bool launch_conv3x3_split(const Conv3Args *a, int n, hipStream_t s);  // fp16 hi/lo split MFMA version (stride 1, Cin 64 or 16); false: n/a, use the scalar kernels
 void launch_conv3x3_multi(const Conv3Args *a, int n, hipStream_t s);  // up to 3 same-Cout problems in one launch
 struct HeadArgs {
     const float *in;        // [B][64][H][W]
