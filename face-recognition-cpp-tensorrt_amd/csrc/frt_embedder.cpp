@@ -52,28 +52,73 @@ std::vector<float> vec_of(const frt::Blob &b, const std::string &name, size_t n)
     return std::vector<float>(p, p + n);
 }
 
+
+// Residual-stream conditioning of the deep IR backbones.  The fp16 stream (Y / Z / SC) adds one branch per unit: on the same
+// kind of weights IR-100 / IR-152 peak 11 / 16 times higher than IR-50 (545 / 783 vs 48), so a stream scale IR-50 holds (1e3) overflows
+// them.  Where the stream BatchNorms' running statistics say the stream is large (sigma >= 2^6), such a blob runs with the stream scaled by
+// ds = 2^-4, which gives back exactly the headroom the depth costs (and no more: what overflows IR-50 still overflows them, loudly).
+// PReLU, MaxPool and the convs are positively homogeneous, so with input_layer.1 and every closing BN scale and bias * ds, every
+// shortcut BN's bias * ds and every BN that reads the stream (res_layer.0, output_layer.0) scale / ds the network computes the same function;
+// every factor is a power of two, exact in binary floating point.  IR-50 (24 units) and the IR-SE family (its gates damp the branches:
+// peaks 5 / 9 / 11) are never touched.
+float residual_stream_scale(const frt::Blob &b, const frt::ArcLayout &layout, bool se) {
+    if (se || layout.units.size() <= 24) return 1.0f;
+    double var = 0.0;
+    for (size_t i = 0; i <= layout.units.size(); ++i) {
+        const std::string p = i < layout.units.size() ? "body." + std::to_string(i) + ".res_layer.0" : std::string("output_layer.0");
+        const frt::Tensor &v = b.get(p + ".running_var", i < layout.units.size() ? layout.units[i].cin : 512);
+        for (size_t c = 0; c < v.numel; ++c) var = std::max(var, (double)v.data[c]);
+    }
+    return std::sqrt(var + 1e-5) >= 64.0 ? 0.0625f : 1.0f;
+}
+
+// Conditioning of the branch conv1 -> PReLU -> conv2 -> BN (round 5; model_irse.py:57-66).  conv1's accumulators leave as the fp16
+// tensor T and both convs multiply fp16 weights: a trained backbone (conversion/arcface/torch2trt.py:21-22 loads one nobody here
+// has seen) may keep that branch orders of magnitude away from 1 - tools/dynamic_range_sweep.py: a branch 1e-4 times smaller pushes
+// T and conv1's weights into fp16's subnormals and conv2's towards its overflow, SILENTLY (1 - cos 4.8e-4).  PReLU is positively
+// homogeneous, so for powers of two c_j, d_k > 0 the unit computes exactly the same function with
+//     conv1 row j * c_j      conv2 column j / c_j, row k * d_k      BN scale k / d_k        (every scaling exact in binary fp)
+// c_j brings conv1's row norm to ~ 1 (T = O(1) behind a normalised input), d_k conv2's largest row entry into [0.5, 1).  A branch
+// that is in range already is left bit for bit as it was (the scalings commute with every rounding).
+// Returns 1 / d_k, the factors the closing BN's scale takes.
+std::vector<float> condition_branch(std::vector<float> &w1v, std::vector<float> &w2v, int cin, int depth) {
+    std::vector<float> dinv(depth, 1.f);
+    auto pow2_inv = [](double v) {  // 2^-round(log2 v), clamped; 1 for zero / non-finite rows
+        if (!(v > 0.0) || !std::isfinite(v)) return 1.0;
+        const double e = std::max(-60.0, std::min(60.0, -std::nearbyint(std::log2(v))));
+        return std::exp2(e);
+    };
+    for (int j = 0; j < depth; ++j) {
+        double n2 = 0.0;
+        float *row = &w1v[(size_t)j * cin * 9];
+        for (int i = 0; i < cin * 9; ++i) n2 += (double)row[i] * row[i];
+        const double c = pow2_inv(std::sqrt(n2));
+        if (c == 1.0) continue;
+        for (int i = 0; i < cin * 9; ++i) row[i] = (float)(row[i] * c);
+        for (int k = 0; k < depth; ++k)
+            for (int t = 0; t < 9; ++t) {
+                float &v = w2v[((size_t)k * depth + j) * 9 + t];
+                v = (float)(v / c);
+            }
+    }
+    for (int k = 0; k < depth; ++k) {
+        double mx = 0.0;
+        float *row = &w2v[(size_t)k * depth * 9];
+        for (int i = 0; i < depth * 9; ++i) mx = std::max(mx, (double)std::fabs(row[i]));
+        double d = 1.0;
+        if (mx > 0.0 && std::isfinite(mx) && (mx >= 2.0 || mx < 0.03125)) d = std::exp2(std::max(-60.0, std::min(60.0, -std::ceil(std::log2(mx)))));
+        if (d == 1.0) continue;   // (entries already inside [2^-5, 2): nothing to gain, keep the trained numbers as they are)
+        for (int i = 0; i < depth * 9; ++i) row[i] = (float)(row[i] * d);
+        dinv[k] = (float)(1.0 / d);
+    }
+    return dinv;
+}
+
 }  // namespace
 
 void frt_embedder::build(const frt::Blob &b) {
     std::vector<float> sc, bi;
-    // Residual-stream conditioning of the deep IR backbones.  The fp16 stream (Y / Z / SC) adds one branch per unit: on the same
-    // kind of weights IR-100 / IR-152 peak 11 / 16 times higher than IR-50 (545 / 783 vs 48), so a stream scale IR-50 holds (1e3) overflows
-    // them.  Where the stream BatchNorms' running statistics say the stream is large (sigma >= 2^6), such a blob runs with the stream scaled by
-    // ds = 2^-4, which gives back exactly the headroom the depth costs (and no more: what overflows IR-50 still overflows them, loudly).
-    // PReLU, MaxPool and the convs are positively homogeneous, so with input_layer.1 and every closing BN scale and bias * ds, every
-    // shortcut BN's bias * ds and every BN that reads the stream (res_layer.0, output_layer.0) scale / ds the network computes the same function;
-    // every factor is a power of two, exact in binary floating point.  IR-50 (24 units) and the IR-SE family (its gates damp the branches:
-    // peaks 5 / 9 / 11) are never touched.
-    stream_scale = 1.0f;
-    if (!se && layout.units.size() > 24) {
-        double var = 0.0;
-        for (size_t i = 0; i <= layout.units.size(); ++i) {
-            const std::string p = i < layout.units.size() ? "body." + std::to_string(i) + ".res_layer.0" : std::string("output_layer.0");
-            const frt::Tensor &v = b.get(p + ".running_var", i < layout.units.size() ? layout.units[i].cin : 512);
-            for (size_t c = 0; c < v.numel; ++c) var = std::max(var, (double)v.data[c]);
-        }
-        if (std::sqrt(var + 1e-5) >= 64.0) stream_scale = 0.0625f;
-    }
+    stream_scale = residual_stream_scale(b, layout, se);
     const float ds = stream_scale;
     // input layer (model_irse.py:139-141)
     {
@@ -111,45 +156,9 @@ void frt_embedder::build(const frt::Blob &b) {
             a.stride = shape.stride;
             a.h_in = h;
             const std::string p = "body." + std::to_string(idx);
-            // Conditioning of the branch conv1 -> PReLU -> conv2 -> BN (round 5; model_irse.py:57-66).  conv1's accumulators leave as the fp16
-            // tensor T and both convs multiply fp16 weights: a trained backbone (conversion/arcface/torch2trt.py:21-22 loads one nobody here
-            // has seen) may keep that branch orders of magnitude away from 1 - tools/dynamic_range_sweep.py: a branch 1e-4 times smaller pushes
-            // T and conv1's weights into fp16's subnormals and conv2's towards its overflow, SILENTLY (1 - cos 4.8e-4).  PReLU is positively
-            // homogeneous, so for powers of two c_j, d_k > 0 the unit computes exactly the same function with
-            //     conv1 row j * c_j      conv2 column j / c_j, row k * d_k      BN scale k / d_k        (every scaling exact in binary fp)
-            // c_j brings conv1's row norm to ~ 1 (T = O(1) behind a normalised input), d_k conv2's largest row entry into [0.5, 1).  A branch
-            // that is in range already is left bit for bit as it was (the scalings commute with every rounding).
             std::vector<float> w1v = vec_of(b, p + ".res_layer.1.weight", (size_t)a.depth * a.cin * 9);
             std::vector<float> w2v = vec_of(b, p + ".res_layer.3.weight", (size_t)a.depth * a.depth * 9);
-            std::vector<float> dinv(a.depth, 1.f);
-            auto pow2_inv = [](double v) {  // 2^-round(log2 v), clamped; 1 for zero / non-finite rows
-                if (!(v > 0.0) || !std::isfinite(v)) return 1.0;
-                const double e = std::max(-60.0, std::min(60.0, -std::nearbyint(std::log2(v))));
-                return std::exp2(e);
-            };
-            for (int j = 0; j < a.depth; ++j) {
-                double n2 = 0.0;
-                float *row = &w1v[(size_t)j * a.cin * 9];
-                for (int i = 0; i < a.cin * 9; ++i) n2 += (double)row[i] * row[i];
-                const double c = pow2_inv(std::sqrt(n2));
-                if (c == 1.0) continue;
-                for (int i = 0; i < a.cin * 9; ++i) row[i] = (float)(row[i] * c);
-                for (int k = 0; k < a.depth; ++k)
-                    for (int t = 0; t < 9; ++t) {
-                        float &v = w2v[((size_t)k * a.depth + j) * 9 + t];
-                        v = (float)(v / c);
-                    }
-            }
-            for (int k = 0; k < a.depth; ++k) {
-                double mx = 0.0;
-                float *row = &w2v[(size_t)k * a.depth * 9];
-                for (int i = 0; i < a.depth * 9; ++i) mx = std::max(mx, (double)std::fabs(row[i]));
-                double d = 1.0;
-                if (mx > 0.0 && std::isfinite(mx) && (mx >= 2.0 || mx < 0.03125)) d = std::exp2(std::max(-60.0, std::min(60.0, -std::ceil(std::log2(mx)))));
-                if (d == 1.0) continue;   // (entries already inside [2^-5, 2): nothing to gain, keep the trained numbers as they are)
-                for (int i = 0; i < a.depth * 9; ++i) row[i] = (float)(row[i] * d);
-                dinv[k] = (float)(1.0 / d);
-            }
+            const std::vector<float> dinv = condition_branch(w1v, w2v, a.cin, a.depth);
             a.w1 = reinterpret_cast<half_t *>(arena.upload(conv_w_f16(w1v.data(), a.depth, a.cin, 3)));
             {  // conv1 is always stride 1; conv2 only in the units that keep the resolution
                 const std::vector<uint16_t> f1 = conv_w_f16_frag(w1v.data(), a.depth, a.cin);
@@ -209,24 +218,13 @@ void frt_embedder::build(const frt::Blob &b) {
         flops_per_face += 2.0 * 25088 * 512;
     }
     const size_t F = (size_t)max_batch;
-    const size_t big = F * 112 * 112 * 64;
     d_in = arena.alloc<float>(F * 3 * 112 * 112);
-    for (int i = 0; i < 2; ++i) {
-        Y[i] = arena.alloc<half_t>(big);
-        Z[i] = arena.alloc<half_t>(big);
-    }
-    T = arena.alloc<half_t>(big);
-    SC = arena.alloc<half_t>(F * 28 * 28 * 128);  // largest conv-shortcut output (56->28, 128 ch)
+    alloc_act_set(act[0]);
     if (se) {
-        RES = arena.alloc<half_t>(F * 56 * 56 * 64);
-        se_pool = arena.alloc<float>(F * 512 * 4 + 2 * F);  // SE_SPLIT partial sums per (face, channel) + per-face arrival counters + gate-ready flags
-        HIPCHK(hipMemset(se_pool + F * 512 * 4, 0, 2 * F * sizeof(int)));  // (kept at zero between launches by the kernel)
-        se_gate = arena.alloc<float>(F * 512);
         HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&h_se_error), sizeof(int), hipHostMallocMapped));
         *h_se_error = 0;
         HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&d_se_error), h_se_error, 0));
     }
-    fc_partial = arena.alloc<float>((size_t)FC_SPLITS * F * 512);
     d_out = arena.alloc<float>(F * 512);
     d_crops = arena.alloc<uint8_t>(F * 112 * 112 * 3);
     d_valid = arena.alloc<int>(F);
@@ -236,25 +234,28 @@ void frt_embedder::build(const frt::Blob &b) {
     HIPCHK(hipMemset(zeros, 0, 256 * sizeof(half_t)));
 }
 
-void frt_embedder::ensure_alt() {
-    if (has_alt) return;
+void frt_embedder::alloc_act_set(ActSet &a) {
     const size_t F = (size_t)max_batch;
     const size_t big = F * 112 * 112 * 64;
     for (int i = 0; i < 2; ++i) {
-        alt.Y[i] = arena.alloc<half_t>(big);
-        alt.Z[i] = arena.alloc<half_t>(big);
+        a.Y[i] = arena.alloc<half_t>(big);
+        a.Z[i] = arena.alloc<half_t>(big);
     }
-    alt.T = arena.alloc<half_t>(big);
-    alt.SC = arena.alloc<half_t>(F * 28 * 28 * 128);
-    alt.RES = nullptr;
-    alt.se_pool = alt.se_gate = nullptr;
+    a.T = arena.alloc<half_t>(big);
+    a.SC = arena.alloc<half_t>(F * 28 * 28 * 128);  // largest conv-shortcut output (56->28, 128 ch)
     if (se) {
-        alt.RES = arena.alloc<half_t>(F * 56 * 56 * 64);
-        alt.se_pool = arena.alloc<float>(F * 512 * 4 + 2 * F);
-        HIPCHK(hipMemset(alt.se_pool + F * 512 * 4, 0, 2 * F * sizeof(int)));
-        alt.se_gate = arena.alloc<float>(F * 512);
+        a.RES = arena.alloc<half_t>(F * 56 * 56 * 64);
+        a.se_pool = arena.alloc<float>(F * 512 * 4 + 2 * F);  // SE_SPLIT partial sums per (face, channel) + per-face arrival counters + gate-ready flags
+        a.se_counter = reinterpret_cast<int *>(a.se_pool + F * 512 * 4);
+        HIPCHK(hipMemset(a.se_counter, 0, 2 * F * sizeof(int)));  // (kept at zero between launches by the kernel)
+        a.se_gate = arena.alloc<float>(F * 512);
     }
-    alt.fc_partial = arena.alloc<float>((size_t)FC_SPLITS * F * 512);
+    a.fc_partial = arena.alloc<float>((size_t)FC_SPLITS * F * 512);
+}
+
+void frt_embedder::ensure_alt() {
+    if (has_alt) return;
+    alloc_act_set(act[1]);
     has_alt = true;
 }
 
@@ -376,127 +377,184 @@ void frt_embedder::forward_f32(const float *chw_dev, int F, const int *valid_dev
     HIPCHK(hipGetLastError());
 }
 
-void frt_embedder::forward(const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s) {
+void frt_embedder::forward(int set, const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s) {
     if (fp32_mode) return forward_f32(chw_dev, F, valid_dev, out_dev, s);
     ProfScope ps(2, "embed_network", flops_per_face * F, s);
-    ArcInputArgs ia{chw_dev, in_w, in_s0, in_b0, in_slope, in_s1, in_b1, Y[0], Z[0], F, 112, 112, in_wh};
+    const ActSet &A = act[set];
+    ArcInputArgs ia{chw_dev, in_w, in_s0, in_b0, in_slope, in_s1, in_b1, A.Y[0], A.Z[0], F, 112, 112, in_wh};
     launch_arc_input(ia, s);
     int cur = 0;
     for (const ArcUnit &u : units) {
         const int h = u.h_in, ho = h / u.stride;
         {  // conv1: BN(x) [already applied -> Z] -> conv3x3 s1 -> PReLU
             ConvMfmaArgs a{};
-            a.x = Z[cur];
+            a.x = A.Z[cur];
             a.w = u.w1;
             a.wf = u.w1f;
             a.B = F; a.H = h; a.W = h; a.Cin = u.cin; a.Ho = h; a.Wo = h; a.Cout = u.depth; a.ks = 3; a.stride = 1; a.pad = 1;
             a.mode = EPI_PRELU;
             a.p0 = u.prelu;
-            a.out0 = T;
+            a.out0 = A.T;
             a.splits = 1;
             a.zeros = zeros;
-            ProfScope pk(1, conv_kernel_label(a), 2.0 * 9 * u.cin * u.depth * (double)F * h * h, s);
-            launch_conv_mfma(a, s);
+            const ConvPlan plan = conv_plan(a);
+            ProfScope pk(1, plan.label, 2.0 * 9 * u.cin * u.depth * (double)F * h * h, s);
+            launch_conv_mfma(a, plan, s);
         }
-        const half_t *sc_t = Y[cur];
-        int sc_h = h, sc_stride = u.stride;
+        // conv2: conv3x3 stride s -> BN -> (+SE) -> + shortcut ; also emits BN_next(y).  Described once, as the plain unit tail.
+        ConvMfmaArgs a{};
+        a.x = A.T;
+        a.w = u.w2;
+        a.wf = u.w2f;
+        a.wf2 = u.w2f2;
+        a.B = F; a.H = h; a.W = h; a.Cin = u.depth; a.Ho = ho; a.Wo = ho; a.Cout = u.depth; a.ks = 3; a.stride = u.stride; a.pad = 1;
+        a.p0 = u.s2;
+        a.p1 = u.b2;
+        a.splits = 1;
+        a.zeros = zeros;
+        a.mode = EPI_BN_ADD_BN;
+        a.p2 = u.sn;
+        a.p3 = u.bn;
+        a.sc = A.Y[cur];  // identity shortcut: MaxPool2d(1, stride) of the unit's input
+        a.sc_h = h; a.sc_w = h; a.sc_stride = u.stride;
         if (&u == &units[0]) {  // the input layer already wrote its raw output at the even positions only
-            sc_h = ho;
-            sc_stride = 1;
+            a.sc_h = ho; a.sc_w = ho;
+            a.sc_stride = 1;
         }
-        // IR-50: the stride-2 strip kernel computes the 1x1 stride-2 shortcut conv itself (its input pixels are the (even, even) phase
-        // plane) - no launch, no shortcut tensor.  IR-SE keeps the tensor: the gate multiplies the residual branch only.
+        a.out0 = A.Y[cur ^ 1];
+        a.out1 = A.Z[cur ^ 1];
+        if (se) {
+            a.se_pool = A.se_pool;
+            a.se_w1 = u.se_w1;
+            a.se_w2 = u.se_w2;
+            a.se_counter = A.se_counter;
+            a.se_flag_off = max_batch;
+            a.se_error = d_se_error;
+        }
+        // IR-50: the stride-2 strip kernel (and the small-batch kernel) computes the 1x1 stride-2 shortcut conv itself (its input pixels are the
+        // (even, even) phase plane) - no launch, no shortcut tensor.  IR-SE keeps the tensor: the gate multiplies the residual branch only.
+        ConvPlan plan;
         bool sc_fused = false;
         if (u.wsc && u.wscf && !se && u.stride == 2) {
-            ConvMfmaArgs t{};
-            t.x = T; t.w = u.w2; t.wf2 = u.w2f2;
-            t.B = F; t.H = h; t.W = h; t.Cin = u.depth; t.Ho = ho; t.Wo = ho; t.Cout = u.depth; t.ks = 3; t.stride = 2; t.pad = 1;
-            t.mode = EPI_BN_ADD_BN; t.splits = 1;
-            t.scx = Y[cur]; t.wscf = u.wscf; t.psc0 = u.ssc; t.psc1 = u.bsc; t.Csc = u.cin;
-            sc_fused = conv_small_applies(t) || conv_s2_applies(t);
+            a.sc = nullptr;
+            a.scx = A.Y[cur]; a.wscf = u.wscf; a.psc0 = u.ssc; a.psc1 = u.bsc; a.Csc = u.cin;
+            plan = conv_plan(a);
+            sc_fused = plan.uses_scx;
+            if (!sc_fused) a.scx = nullptr, a.wscf = nullptr, a.psc0 = a.psc1 = nullptr, a.Csc = 0;
         }
-        if (u.wsc && !sc_fused) {  // conv1x1 stride s + BN on the raw input
-            ConvMfmaArgs a{};
-            a.x = Y[cur];
-            a.w = u.wsc;
-            a.B = F; a.H = h; a.W = h; a.Cin = u.cin; a.Ho = ho; a.Wo = ho; a.Cout = u.depth; a.ks = 1; a.stride = u.stride; a.pad = 0;
-            a.mode = EPI_BN;
-            a.p0 = u.ssc;
-            a.p1 = u.bsc;
-            a.out0 = SC;
-            a.splits = 1;
-            a.zeros = zeros;
-            launch_conv_mfma(a, s);
-            sc_t = SC;
-            sc_h = ho;
-            sc_stride = 1;
+        if (u.wsc && !sc_fused) {  // conv1x1 stride s + BN on the raw input, as a launch of its own
+            ConvMfmaArgs c{};
+            c.x = A.Y[cur];
+            c.w = u.wsc;
+            c.B = F; c.H = h; c.W = h; c.Cin = u.cin; c.Ho = ho; c.Wo = ho; c.Cout = u.depth; c.ks = 1; c.stride = u.stride; c.pad = 0;
+            c.mode = EPI_BN;
+            c.p0 = u.ssc;
+            c.p1 = u.bsc;
+            c.out0 = A.SC;
+            c.splits = 1;
+            c.zeros = zeros;
+            launch_conv_mfma(c, conv_plan(c), s);
+            a.sc = A.SC;
+            a.sc_h = ho; a.sc_w = ho;
+            a.sc_stride = 1;
         }
-        {  // conv2: conv3x3 stride s -> BN -> (+SE) -> + shortcut ; also emit BN_next(y)
-            ConvMfmaArgs a{};
-            a.x = T;
-            a.w = u.w2;
-            a.wf = u.w2f;
-            a.wf2 = u.w2f2;
-            a.B = F; a.H = h; a.W = h; a.Cin = u.depth; a.Ho = ho; a.Wo = ho; a.Cout = u.depth; a.ks = 3; a.stride = u.stride; a.pad = 1;
-            a.p0 = u.s2;
-            a.p1 = u.b2;
-            a.splits = 1;
-            a.zeros = zeros;
-            a.mode = EPI_BN_ADD_BN;
-            a.p2 = u.sn;
-            a.p3 = u.bn;
-            a.sc = sc_t;
-            a.sc_h = sc_h; a.sc_w = sc_h; a.sc_stride = sc_stride;
-            if (sc_fused) {
-                a.sc = nullptr;
-                a.scx = Y[cur]; a.wscf = u.wscf; a.psc0 = u.ssc; a.psc1 = u.bsc; a.Csc = u.cin;
-            }
-            a.out0 = Y[cur ^ 1];
-            a.out1 = Z[cur ^ 1];
-            bool se_tail = false;  // IR-SE: the SE tail as separate launches behind conv2
-            if (se) {
-                int *cnt = reinterpret_cast<int *>(se_pool + (size_t)max_batch * 512 * 4);
-                a.se_pool = se_pool;
-                a.se_w1 = u.se_w1;
-                a.se_w2 = u.se_w2;
-                a.se_counter = cnt;
-                a.se_flag_off = max_batch;
-                a.se_error = d_se_error;
-                if (se_fused && conv_se_fused(a)) {  // the strip kernel runs the whole tail in its epilogue
-                    if (se_epoch >= (1 << 30)) {  // the flags carry launch numbers: start over with clean flags (both scratch sets)
-                        HIPCHK(hipMemsetAsync(cnt + max_batch, 0, (size_t)max_batch * sizeof(int), s));
-                        if (has_alt) HIPCHK(hipMemsetAsync(reinterpret_cast<int *>(alt.se_pool + (size_t)max_batch * 512 * 4) + max_batch, 0, (size_t)max_batch * sizeof(int), s));
-                        se_epoch = 0;
-                    }
-                    a.se_epoch = ++se_epoch;
-                    a.mode = EPI_BN_SE;
-                } else {
-                    a.mode = EPI_BN;
-                    a.out0 = RES;
-                    a.out1 = nullptr;
-                    a.sc = nullptr;
-                    se_tail = true;
+        if (!sc_fused) plan = conv_plan(a);
+        bool se_tail = false;  // IR-SE: the SE tail as separate launches behind conv2
+        SeArgs sa{};
+        if (se) {
+            if (se_fused && plan.se_fused() && conv_se_fits_device()) {  // the strip kernel runs the whole tail in its epilogue
+                if (se_epoch >= (1 << 30)) {  // the flags carry launch numbers: start over with clean flags (every allocated set)
+                    for (int i = 0; i < (has_alt ? 2 : 1); ++i) HIPCHK(hipMemsetAsync(act[i].se_counter + max_batch, 0, (size_t)max_batch * sizeof(int), s));
+                    se_epoch = 0;
                 }
-            }
-            {
-                ProfScope pk(1, conv_kernel_label(a), (2.0 * 9 * u.depth * u.depth + (sc_fused ? 2.0 * u.cin * u.depth : 0.0)) * (double)F * ho * ho, s);
-                launch_conv_mfma(a, s);
-            }
-            if (se_tail) {
-                SeArgs sa{RES, u.se_w1, u.se_w2, sc_t, sc_h, sc_h, sc_stride, u.sn, u.bn, Y[cur ^ 1], Z[cur ^ 1], se_pool, se_gate, F, ho, ho, u.depth,
-                          reinterpret_cast<int *>(se_pool + (size_t)max_batch * 512 * 4)};
-                launch_se(sa, s);
+                a.se_epoch = ++se_epoch;
+                // The plan made for the EPI_BN_ADD_BN description IS the plan of this launch: the arguments are not planned again under the
+                // new mode (no planner has to treat the two modes alike) - the plan only moves to its twin instantiation, same geometry.
+                a.mode = EPI_BN_SE;
+                plan.take_se_tail();
+            } else {  // another description - conv2 + BN into RES - and so another plan
+                sa = SeArgs{A.RES, u.se_w1, u.se_w2, a.sc, a.sc_h, a.sc_w, a.sc_stride, u.sn, u.bn, a.out0, a.out1, A.se_pool, A.se_gate, F, ho, ho, u.depth, A.se_counter};
+                a.mode = EPI_BN;
+                a.out0 = A.RES;
+                a.out1 = nullptr;
+                a.sc = nullptr;
+                se_tail = true;
+                plan = conv_plan(a);
             }
         }
+        {
+            ProfScope pk(1, plan.label, (2.0 * 9 * u.depth * u.depth + (sc_fused ? 2.0 * u.cin * u.depth : 0.0)) * (double)F * ho * ho, s);
+            launch_conv_mfma(a, plan, s);
+        }
+        if (se_tail) launch_se(sa, s);
         cur ^= 1;
     }
     {  // Linear 25088 -> 512 as 49 K-slices over the NHWC-flattened BN2d output (Z), then slice sum + bias + BN1d + L2 norm
-        launch_fc_slices(Z[cur], wfc, F, fc_partial, s);
-        launch_fc_finalize(fc_partial, FC_SPLITS, F, fc_bias, bn_s, bn_b, valid_dev, out_dev, s);
+        launch_fc_slices(A.Z[cur], wfc, F, A.fc_partial, s);
+        launch_fc_finalize(A.fc_partial, FC_SPLITS, F, fc_bias, bn_s, bn_b, valid_dev, out_dev, s);
     }
     HIPCHK(hipGetLastError());
 }
 
+namespace {
+
+// One-shot crop / alignment (frt_crop_faces, frt_align_faces): frame up, `launch(arena, d_frame, tight, d_crops, d_chw, d_valid)`, crops down
+// into crops_host [n][out_h][out_w][3]; returns the validity flags.
+template <class Launch>
+std::vector<int> crops_one_shot(const uint8_t *bgr, int rows, int cols, size_t row_stride, int n, int out_h, int out_w, int device, uint8_t *crops_host,
+                                Launch launch) {
+    if (device >= 0) use_device(device);
+    Arena a;
+    struct Guard {
+        Arena &a;
+        ~Guard() { a.release(); }
+    } guard{a};
+    const size_t tight = (size_t)cols * 3, crop_bytes = (size_t)n * out_h * out_w * 3;
+    uint8_t *d_frame = a.alloc<uint8_t>((size_t)rows * tight);
+    uint8_t *d_crops = a.alloc<uint8_t>(crop_bytes);
+    float *d_chw = a.alloc<float>(crop_bytes);
+    int *d_valid = a.alloc<int>(n);
+    HIPCHK(hipMemcpy2D(d_frame, tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice));
+    launch(a, d_frame, tight, d_crops, d_chw, d_valid);
+    std::vector<int> valid(n);
+    HIPCHK(hipMemcpy(valid.data(), d_valid, sizeof(int) * n, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(crops_host, d_crops, crop_bytes, hipMemcpyDeviceToHost));
+    return valid;
+}
+
+// frt_embedder_forward / _forward_aligned: frame up once, then per pass of at most max_batch faces `stage(f0, nf, tight, stream)` (boxes or landmarks
+// up, crop or alignment into d_crops / d_in / d_valid) -> network -> embeddings (and crops) down.  Returns whether a face was invalid.
+template <class Stage>
+bool forward_frame(frt_embedder *e, const uint8_t *bgr, int rows, int cols, size_t row_stride, int n, float *embeds_out, uint8_t *crops_out, Stage stage) {
+    std::lock_guard<std::mutex> lk(e->mu);
+    use_device(e->device);
+    hipStream_t s = e->stream;
+    e->wait_idle(s);
+    const size_t tight = (size_t)cols * 3, need = (size_t)rows * tight;
+    if (need > e->frame_cap) {
+        if (e->d_frame) (void)hipFree(e->d_frame);
+        e->d_frame = nullptr;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->d_frame), need));
+        e->frame_cap = need;
+    }
+    HIPCHK(hipMemcpy2DAsync(e->d_frame, tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice, s));
+    bool bad = false;
+    for (int f0 = 0; f0 < n; f0 += e->max_batch) {
+        const int nf = std::min(e->max_batch, n - f0);
+        stage(f0, nf, tight, s);
+        e->forward(0, e->d_in, nf, e->d_valid, e->d_out, s);
+        HIPCHK(hipMemcpyAsync(embeds_out + (size_t)f0 * 512, e->d_out, sizeof(float) * 512 * nf, hipMemcpyDeviceToHost, s));
+        if (crops_out) HIPCHK(hipMemcpyAsync(crops_out + (size_t)f0 * 112 * 112 * 3, e->d_crops, (size_t)nf * 112 * 112 * 3, hipMemcpyDeviceToHost, s));
+        std::vector<int> valid(nf);
+        HIPCHK(hipMemcpyAsync(valid.data(), e->d_valid, sizeof(int) * nf, hipMemcpyDeviceToHost, s));
+        sync_stream_spinning(s);
+        e->check_se_error();
+        for (int v : valid) bad = bad || !v;
+    }
+    return bad;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -506,25 +564,13 @@ int frt_crop_faces(const uint8_t *bgr, int rows, int cols, size_t row_stride, co
     return guarded([&] {
         if (!bgr || !boxes || !crops_out || n < 0 || out_w < 1 || out_h < 1) raise(FRT_ERR_INVALID, "getCroppedFaces: bad argument");
         if (n == 0) return;
-        if (device >= 0) use_device(device);
-        Arena a;
-        struct Guard {
-            Arena &a;
-            ~Guard() { a.release(); }
-        } guard{a};
-        const size_t tight = (size_t)cols * 3;
-        uint8_t *d_frame = a.alloc<uint8_t>((size_t)rows * tight);
-        frt_bbox *d_boxes = a.alloc<frt_bbox>(n);
-        uint8_t *d_crops = a.alloc<uint8_t>((size_t)n * out_h * out_w * 3);
-        float *d_chw = a.alloc<float>((size_t)n * out_h * out_w * 3);
-        int *d_valid = a.alloc<int>(n);
-        HIPCHK(hipMemcpy2D(d_frame, tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_boxes, boxes, sizeof(frt_bbox) * n, hipMemcpyHostToDevice));
-        launch_crop_faces(d_frame, rows, cols, tight, 0, d_boxes, nullptr, 1, n, 1, out_h, out_w, d_crops, d_chw, d_valid, nullptr);
-        std::vector<int> valid(n);
-        HIPCHK(hipMemcpy(valid.data(), d_valid, sizeof(int) * n, hipMemcpyDeviceToHost));
         std::vector<uint8_t> tmp((size_t)n * out_h * out_w * 3);
-        HIPCHK(hipMemcpy(tmp.data(), d_crops, tmp.size(), hipMemcpyDeviceToHost));
+        const std::vector<int> valid = crops_one_shot(bgr, rows, cols, row_stride, n, out_h, out_w, device, tmp.data(),
+                                                      [&](Arena &a, const uint8_t *d_frame, size_t tight, uint8_t *d_crops, float *d_chw, int *d_valid) {
+            frt_bbox *d_boxes = a.alloc<frt_bbox>(n);
+            HIPCHK(hipMemcpy(d_boxes, boxes, sizeof(frt_bbox) * n, hipMemcpyHostToDevice));
+            launch_crop_faces(d_frame, rows, cols, tight, 0, d_boxes, nullptr, 1, n, 1, out_h, out_w, d_crops, d_chw, d_valid, nullptr);
+        });
         bool bad = false;
         for (int i = 0; i < n; ++i) {
             if (valid[i])
@@ -645,7 +691,7 @@ int frt_embedder_infer(frt_embedder *e, const float *chw, int batch, float *embe
         for (int f0 = 0; f0 < batch; f0 += e->max_batch) {
             const int nf = std::min(e->max_batch, batch - f0);
             HIPCHK(hipMemcpyAsync(e->d_in, chw + (size_t)f0 * in_elems, sizeof(float) * in_elems * nf, hipMemcpyHostToDevice, s));
-            e->forward(e->d_in, nf, nullptr, e->d_out, s);
+            e->forward(0, e->d_in, nf, nullptr, e->d_out, s);
             HIPCHK(hipMemcpyAsync(embeds_out + (size_t)f0 * 512, e->d_out, sizeof(float) * 512 * nf, hipMemcpyDeviceToHost, s));
             sync_stream_spinning(s);
             e->check_se_error();
@@ -658,32 +704,10 @@ int frt_embedder_forward(frt_embedder *e, const uint8_t *bgr, int rows, int cols
     return guarded([&] {
         if (!e || !bgr || !boxes || !embeds_out || n < 0 || rows < 1 || cols < 1) raise(FRT_ERR_INVALID, "forward: bad argument");
         if (n == 0) return;
-        std::lock_guard<std::mutex> lk(e->mu);
-        use_device(e->device);
-        hipStream_t s = e->stream;
-        e->wait_idle(s);
-        const size_t tight = (size_t)cols * 3, need = (size_t)rows * tight;
-        if (need > e->frame_cap) {
-            if (e->d_frame) (void)hipFree(e->d_frame);
-            e->d_frame = nullptr;
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->d_frame), need));
-            e->frame_cap = need;
-        }
-        HIPCHK(hipMemcpy2DAsync(e->d_frame, tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice, s));
-        bool bad = false;
-        for (int f0 = 0; f0 < n; f0 += e->max_batch) {
-            const int nf = std::min(e->max_batch, n - f0);
+        const bool bad = forward_frame(e, bgr, rows, cols, row_stride, n, embeds_out, crops_out, [&](int f0, int nf, size_t tight, hipStream_t s) {
             HIPCHK(hipMemcpyAsync(e->d_boxes, boxes + f0, sizeof(frt_bbox) * nf, hipMemcpyHostToDevice, s));
             launch_crop_faces(e->d_frame, rows, cols, tight, 0, e->d_boxes, nullptr, 1, nf, 1, 112, 112, e->d_crops, e->d_in, e->d_valid, s);
-            e->forward(e->d_in, nf, e->d_valid, e->d_out, s);
-            HIPCHK(hipMemcpyAsync(embeds_out + (size_t)f0 * 512, e->d_out, sizeof(float) * 512 * nf, hipMemcpyDeviceToHost, s));
-            if (crops_out) HIPCHK(hipMemcpyAsync(crops_out + (size_t)f0 * 112 * 112 * 3, e->d_crops, (size_t)nf * 112 * 112 * 3, hipMemcpyDeviceToHost, s));
-            std::vector<int> valid(nf);
-            HIPCHK(hipMemcpyAsync(valid.data(), e->d_valid, sizeof(int) * nf, hipMemcpyDeviceToHost, s));
-            sync_stream_spinning(s);
-            e->check_se_error();
-            for (int v : valid) bad = bad || !v;
-        }
+        });
         if (bad) raise(FRT_ERR_EMPTY_ROI, "forward: empty or out-of-frame ROI (embedding set to zeros)");
     });
 }
@@ -692,24 +716,12 @@ int frt_align_faces(const uint8_t *bgr, int rows, int cols, size_t row_stride, c
     return guarded([&] {
         if (!bgr || !landmarks || !crops_out || n < 0 || rows < 1 || cols < 1) raise(FRT_ERR_INVALID, "alignFaces: bad argument");
         if (n == 0) return;
-        if (device >= 0) use_device(device);
-        Arena a;
-        struct Guard {
-            Arena &a;
-            ~Guard() { a.release(); }
-        } guard{a};
-        const size_t tight = (size_t)cols * 3;
-        uint8_t *d_frame = a.alloc<uint8_t>((size_t)rows * tight);
-        float *d_lm = a.alloc<float>((size_t)n * 10);
-        uint8_t *d_crops = a.alloc<uint8_t>((size_t)n * 112 * 112 * 3);
-        float *d_chw = a.alloc<float>((size_t)n * 112 * 112 * 3);
-        int *d_valid = a.alloc<int>(n);
-        HIPCHK(hipMemcpy2D(d_frame, tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(d_lm, landmarks, sizeof(float) * 10 * n, hipMemcpyHostToDevice));
-        launch_align_faces(d_frame, rows, cols, tight, 0, d_lm, nullptr, 1, n, 1, d_crops, d_chw, d_valid, nullptr);
-        std::vector<int> valid(n);
-        HIPCHK(hipMemcpy(valid.data(), d_valid, sizeof(int) * n, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(crops_out, d_crops, (size_t)n * 112 * 112 * 3, hipMemcpyDeviceToHost));
+        const std::vector<int> valid = crops_one_shot(bgr, rows, cols, row_stride, n, 112, 112, device, crops_out,
+                                                      [&](Arena &a, const uint8_t *d_frame, size_t tight, uint8_t *d_crops, float *d_chw, int *d_valid) {
+            float *d_lm = a.alloc<float>((size_t)n * 10);
+            HIPCHK(hipMemcpy(d_lm, landmarks, sizeof(float) * 10 * n, hipMemcpyHostToDevice));
+            launch_align_faces(d_frame, rows, cols, tight, 0, d_lm, nullptr, 1, n, 1, d_crops, d_chw, d_valid, nullptr);
+        });
         for (int v : valid)
             if (!v) raise(FRT_ERR_EMPTY_ROI, "alignFaces: degenerate landmarks (crop set to zeros)");
     });
@@ -720,32 +732,10 @@ int frt_embedder_forward_aligned(frt_embedder *e, const uint8_t *bgr, int rows, 
     return guarded([&] {
         if (!e || !bgr || !landmarks || !embeds_out || n < 0 || rows < 1 || cols < 1) raise(FRT_ERR_INVALID, "forwardAligned: bad argument");
         if (n == 0) return;
-        std::lock_guard<std::mutex> lk(e->mu);
-        use_device(e->device);
-        hipStream_t s = e->stream;
-        e->wait_idle(s);
-        const size_t tight = (size_t)cols * 3, need = (size_t)rows * tight;
-        if (need > e->frame_cap) {
-            if (e->d_frame) (void)hipFree(e->d_frame);
-            e->d_frame = nullptr;
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->d_frame), need));
-            e->frame_cap = need;
-        }
-        HIPCHK(hipMemcpy2DAsync(e->d_frame, tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice, s));
-        bool bad = false;
-        for (int f0 = 0; f0 < n; f0 += e->max_batch) {
-            const int nf = std::min(e->max_batch, n - f0);
+        const bool bad = forward_frame(e, bgr, rows, cols, row_stride, n, embeds_out, crops_out, [&](int f0, int nf, size_t tight, hipStream_t s) {
             HIPCHK(hipMemcpyAsync(e->d_lm, landmarks + (size_t)f0 * 10, sizeof(float) * 10 * nf, hipMemcpyHostToDevice, s));
             launch_align_faces(e->d_frame, rows, cols, tight, 0, e->d_lm, nullptr, 1, nf, 1, e->d_crops, e->d_in, e->d_valid, s);
-            e->forward(e->d_in, nf, e->d_valid, e->d_out, s);
-            HIPCHK(hipMemcpyAsync(embeds_out + (size_t)f0 * 512, e->d_out, sizeof(float) * 512 * nf, hipMemcpyDeviceToHost, s));
-            if (crops_out) HIPCHK(hipMemcpyAsync(crops_out + (size_t)f0 * 112 * 112 * 3, e->d_crops, (size_t)nf * 112 * 112 * 3, hipMemcpyDeviceToHost, s));
-            std::vector<int> valid(nf);
-            HIPCHK(hipMemcpyAsync(valid.data(), e->d_valid, sizeof(int) * nf, hipMemcpyDeviceToHost, s));
-            sync_stream_spinning(s);
-            e->check_se_error();
-            for (int v : valid) bad = bad || !v;
-        }
+        });
         if (bad) raise(FRT_ERR_EMPTY_ROI, "forwardAligned: degenerate landmarks (embedding set to zeros)");
     });
 }

@@ -35,10 +35,20 @@ struct frt_embedder {
     half_t *in_wh = nullptr;
     half_t *wfc;
     float *fc_bias, *bn_s, *bn_b;
-    // activations
+    // activations.  Two sets: the pipeline runs the recogniser passes of two consecutive calls concurrently on two streams, one set each;
+    // everything else uses set 0.  Set 1 is allocated on demand (288 GB of HBM: 1.2 GB more is not a concern).
+    struct ActSet {
+        half_t *Y[2] = {nullptr, nullptr}, *Z[2] = {nullptr, nullptr}, *T = nullptr, *SC = nullptr, *RES = nullptr;
+        float *se_pool = nullptr;   // IR-SE: SE_SPLIT partial sums per (face, channel) ...
+        int *se_counter = nullptr;  // ... and behind them [max_batch] arrival counters + [max_batch] gate-ready flags (zero between launches)
+        float *se_gate = nullptr, *fc_partial = nullptr;
+    } act[2];
+    bool has_alt = false;  // act[1] is allocated
+    void alloc_act_set(ActSet &a);
+    void ensure_alt();
     float *d_in = nullptr;  // [max_batch][3][112][112]
-    half_t *Y[2], *Z[2], *T, *SC, *RES = nullptr, *zeros = nullptr;
-    float *fc_partial, *d_out, *se_pool = nullptr, *se_gate = nullptr;
+    float *d_out = nullptr;
+    half_t *zeros = nullptr;
     int se_epoch = 0;  // launch counter of the fused SE tails (their gate-ready flags carry the launch number)
     bool se_fused = true;        // IR-SE: run the SE tail inside conv2's epilogue where the strip kernels allow it
                                  // (frt_embedder_set_se_fused(e, 0): always the stand-alone pool + gate + apply launches)
@@ -80,30 +90,6 @@ struct frt_embedder {
     void forward_f32(const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s);
 
     void build(const frt::Blob &b);
-    // chw_dev [F][3][112][112] -> out_dev [F][512]; F <= max_batch
-    void forward(const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s);
-    // second set of activation buffers: lets the pipeline run the recogniser passes of two consecutive calls concurrently on two
-    // streams (forward_alt).  Allocated on demand (288 GB of HBM: 1.2 GB more is not a concern).
-    struct ActSet {
-        half_t *Y[2], *Z[2], *T, *SC, *RES;
-        float *fc_partial, *se_pool, *se_gate;
-    } alt{};
-    bool has_alt = false;
-    void ensure_alt();
-    void swap_alt() {
-        std::swap(Y[0], alt.Y[0]); std::swap(Y[1], alt.Y[1]); std::swap(Z[0], alt.Z[0]); std::swap(Z[1], alt.Z[1]);
-        std::swap(T, alt.T); std::swap(SC, alt.SC); std::swap(RES, alt.RES);
-        std::swap(fc_partial, alt.fc_partial); std::swap(se_pool, alt.se_pool); std::swap(se_gate, alt.se_gate);
-    }
-    void forward_set(int set, const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s) {
-        if (set) swap_alt();  // host-side pointer swap: the launches below capture the alternate buffers
-        try {
-            forward(chw_dev, F, valid_dev, out_dev, s);
-        } catch (...) {
-            if (set) swap_alt();
-            throw;
-        }
-        if (set) swap_alt();
-    }
+    // chw_dev [F][3][112][112] -> out_dev [F][512] on activation set `set`; F <= max_batch
+    void forward(int set, const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s);
 };
-

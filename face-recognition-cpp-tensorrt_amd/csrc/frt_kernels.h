@@ -253,7 +253,7 @@ struct ConvMfmaArgs {
     float *outf;       // EPI_PARTIAL: [splits][M][Cout]
     int splits;
     const half_t *zeros;  // >= 16 bytes of zeros (source of padded taps for the LDS-DMA path)
-    // IR-SE unit tail inside conv2's epilogue (mode EPI_BN_SE; only when conv_se_fused(args) - the strip kernel's main variant): y (out0) =
+    // IR-SE unit tail inside conv2's epilogue (mode EPI_BN_SE; only when the launch's ConvPlan says se_fused() - the strip kernels' main variants): y (out0) =
     // BN(conv) * gate + sc, z (out1) = y * p2 + p3, gate from the image-wide channel means through fc1 [C/16][C] / fc2 [C][C/16].
     float *se_pool;      // scratch [4][B][Cout] partial channel sums
     const float *se_w1, *se_w2;
@@ -262,19 +262,54 @@ struct ConvMfmaArgs {
     int se_epoch;        // launch number (> 0, different from every earlier launch's on this scratch): what the flags are set to
     int *se_error;       // error word in mapped host memory: set (to the launch number) when a hand-over wait timed out
 };
-bool conv_se_fused(const ConvMfmaArgs &a);  // a: the unit's conv2 described as EPI_BN_ADD_BN + the se_* scratch
-void launch_conv_mfma(const ConvMfmaArgs &a, hipStream_t s);
-bool conv_s2_applies(const ConvMfmaArgs &a);                // kernels_arc_s2.hip: 3x3 stride 2, Cout % 128 == 0 or 64 -> 64 at 112 -> 56
-bool launch_conv_s2(const ConvMfmaArgs &a, hipStream_t s);
-bool conv_s2_se_fused(const ConvMfmaArgs &a);  // IR-SE tail in the stride-2 strip kernel's epilogue (see conv_se_fused)
-const char *conv_s2_label(const ConvMfmaArgs &a);
-bool conv_small_applies(const ConvMfmaArgs &a);              // kernels_arc_small.hip: 3x3 convs of a small batch (few pixel tiles)
-bool launch_conv_small(const ConvMfmaArgs &a, hipStream_t s);
-bool conv_ks_applies(const ConvMfmaArgs &a);                 // kernels_arc_ks.hip: 3x3 stride 1 at 14x14x256 / 7x7x512, medium batches (K split over the waves)
-bool launch_conv_ks(const ConvMfmaArgs &a, hipStream_t s);
-bool conv64_applies(const ConvMfmaArgs &a);                 // kernels_arc_c64.hip: Cin = Cout = 64, 3x3, stride 1
-bool launch_conv64(const ConvMfmaArgs &a, hipStream_t s);
-const char *conv_kernel_label(const ConvMfmaArgs &a);  // kernel symbol (as rocprofv3 prints it) a launch resolves to
+// One conv launch, decided once: the instantiation that runs, the geometry its launcher needs, its label.  conv_plan() is a pure host
+// function of the arguments (no HIP call: it runs on a machine without a device) and the ONE place a recogniser kernel is registered:
+// an ordered list of families, each of which owns a table of (label, launcher) rows - one row per instantiation.
+enum ConvFamily { CONV_SMALL, CONV_KS, CONV_C64, CONV_S2, CONV_STRIP };
+struct ConvPlan {
+    int family = CONV_STRIP;   // ConvFamily
+    int row = 0;               // the instantiation: index into the family's table
+    const char *label = "";    // its kernel symbol (as rocprofv3 prints it; also the profiling label bench.py and the tests key on)
+    int R = 0, n_img = 1;      // strip families: image rows (compact strips: patch rows) and images per strip
+    int M = 0;                 // CONV_SMALL: output pixels of the launch
+    bool uses_scx = false;     // the kernel computes the fused 1x1 stride-2 shortcut conv (a.scx) itself
+    // IR-SE (a = the unit's conv2 described as EPI_BN_ADD_BN + the se_* scratch): se_row >= 0 when the launch can carry the whole SE tail in its
+    // epilogue - se_row / se_label name the twin instantiation that does (same family, same geometry).  The per-device occupancy gate
+    // (conv_se_fits_device) is not part of the plan.
+    int se_row = -1;
+    const char *se_label = nullptr;
+    bool se_fused() const { return se_row >= 0; }
+    void take_se_tail() { row = se_row; label = se_label; }  // for the launch whose mode has become EPI_BN_SE
+};
+// a family's table row: every instantiation appears once, with its label next to its launcher
+struct ConvRow {
+    const char *label;
+    void (*launch)(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s);
+    int se_row;  // the row of the twin instantiation with the SE tail in its epilogue; -1: none
+};
+inline void conv_plan_row(ConvPlan &p, int family, const ConvRow *table, int row) {
+    p.family = family;
+    p.row = row;
+    p.label = table[row].label;
+}
+// IR-SE, for a planner whose strip geometry suits the tail: the plan gets the row's SE twin when `a` is a unit's conv2 described with the SE scratch
+inline void conv_plan_se_twin(ConvPlan &p, const ConvRow *table, const ConvMfmaArgs &a) {
+    if (table[p.row].se_row < 0 || a.mode != EPI_BN_ADD_BN || !a.se_pool || !a.sc || !a.out1) return;
+    p.se_row = table[p.row].se_row;
+    p.se_label = table[p.se_row].label;
+}
+ConvPlan conv_plan(const ConvMfmaArgs &a);
+void launch_conv_mfma(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s);
+bool conv_se_fits_device();  // HIP query, once per device: enough workgroups of the SE-tail instantiations are resident together (kernels_arc.hip)
+// the families, in conv_plan's order; plan_X: false = not this family's launch (p untouched)
+bool plan_small(const ConvMfmaArgs &a, ConvPlan &p);   // kernels_arc_small.hip: 3x3 convs of a small batch (few pixel tiles)
+void launch_small(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s);
+bool plan_ks(const ConvMfmaArgs &a, ConvPlan &p);      // kernels_arc_ks.hip: 3x3 stride 1 at 14x14x256 / 7x7x512, medium batches (K split over the waves)
+void launch_ks(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s);
+bool plan_c64(const ConvMfmaArgs &a, ConvPlan &p);     // kernels_arc_c64.hip: Cin = Cout = 64, 3x3, stride 1
+void launch_c64(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s);
+bool plan_s2(const ConvMfmaArgs &a, ConvPlan &p);      // kernels_arc_s2.hip: 3x3 stride 2, Cout % 128 == 0 or 64 -> 64 at 112 -> 56
+void launch_s2(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s);
 struct ArcInputArgs {
     const float *x;       // [F][3][112][112] planar RGB
     const float *w;       // [27][64]  (k = ci*9 + kh*3 + kw)

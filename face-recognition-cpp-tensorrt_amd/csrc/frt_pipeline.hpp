@@ -544,7 +544,7 @@ struct frt_pipeline {
             }
             for (int f0 = 0; f0 < Ftot; f0 += emb->max_batch) {
                 const int nf = std::min(emb->max_batch, Ftot - f0);
-                emb->forward_set(eset, chw + (size_t)f0 * 3 * 112 * 112, nf, valid + f0, emb_slot + (size_t)f0 * 512, st);
+                emb->forward(eset, chw + (size_t)f0 * 3 * 112 * 112, nf, valid + f0, emb_slot + (size_t)f0 * 512, st);
             }
         };
         // (the fp32 pass is never captured: its single activation set is handed from pass to pass through the host-tracked event f32.done,

@@ -21,9 +21,6 @@
 //                  be folded into the conv weights exactly - it is applied here, where the value is produced)
 //   EPI_PARTIAL    outf[split][pixel][cout] = acc                                (split-K partial sums for the final Linear)
 // MaxPool2d(1, stride) shortcuts are pure indexing: the shortcut operand is sampled at (oh*stride, ow*stride).
-#include <cstdio>
-#include <cstring>
-
 #include "frt_kernels.h"
 #include "frt_se_device.h"
 
@@ -798,7 +795,7 @@ __global__ __launch_bounds__(256) void se_apply_kernel(SeArgs a) {
 }
 
 template <int WCO, int WPX, int NSTAGE>
-void launch_glds_t(const ConvMfmaArgs &a, hipStream_t s) {
+void launch_glds_t(const ConvMfmaArgs &a, const ConvPlan &, hipStream_t s) {
     constexpr int BCO = WCO * 64, BPX = WPX * 64;
     const size_t lds = (size_t)NSTAGE * (BCO + BPX) * 64 * sizeof(half_t);
     static_assert(NSTAGE * (BCO + BPX) * 64 * 2 >= 4 * 32 * 68 * 4, "ring must hold the epilogue transpose buffer");
@@ -830,7 +827,7 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
     constexpr int kWant = 224;  // workgroups that count as "fills the 256 CUs" (128 / 64 measured at 16 / 32 / 64 faces: 0.89 / 1.20 / 1.68 ms per pass become 0.89 / 1.28 / 1.87 and 1.10 / 1.56 / 1.88, profiles/r03/r03r_kwant.txt)
     auto tiles_for = [](int px) { return px <= 32 ? 1 : (px <= 64 ? 2 : (px <= 128 ? 4 : (px <= 224 ? 7 : 0))); };
     auto slots_of = [&](int r, int ni) { return (ni * (r + 2) * (a.W + 2) * 9 + 255) / 256; };
-    auto fits = [&](int r, int ni, int t) {  // LDS budget of the instantiation that serves t tiles (see launch_conv_mfma)
+    auto fits = [&](int r, int ni, int t) {  // LDS budget of the instantiation that serves t tiles (see kStrip)
         const int sl = slots_of(r, ni);
         if (pair) return t == 7 && ni * (r + 2) * (a.W + 2) * 9 <= 34 * 128;
         if (single) return t == 7 && sl <= 15;
@@ -882,7 +879,8 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
 }
 
 template <int PPS, int PT, int NW, bool SINGLE, bool PAIR = false, int NT = 7, int BFD = 2, int WR = 3, bool SEP = false>
-void launch_patch_t(const ConvMfmaArgs &a, int R, int n_img, hipStream_t s) {
+void launch_patch_t(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) {
+    const int R = p.R, n_img = p.n_img;
     const size_t lds = PAIR ? (size_t)2 * 34 * 2048 : (size_t)(SINGLE ? 1 : 2) * PT * PPS * 4096;  // patch buffers only (weights live in registers)
     static_assert(PAIR || ((SINGLE ? 1 : 2) * PT * PPS * 4096 <= 160 * 1024 && PT * PPS * 4096 >= 4 * 32 * 36 * 4), "LDS budget / epilogue scratch");
     static bool attr_done[FRT_MAX_DEVICES] = {};
@@ -913,76 +911,112 @@ int compact_patch_rows(const ConvMfmaArgs &a, int nt) {
 }
 
 template <int NT>
-void launch_patchc_t(const ConvMfmaArgs &a, int npr, hipStream_t s) {
+void launch_patchc_t(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) {
     constexpr size_t lds = (size_t)2 * 10 * 4096;
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done))
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patchc_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const long M = (long)a.B * a.H * a.W;
     const int strips = (int)((M + NT * 32 - 1) / (NT * 32));
-    hipLaunchKernelGGL((conv_patchc_kernel<NT>), dim3(strips * (a.Cout / 128)), dim3(256), lds, s, a, npr);
+    hipLaunchKernelGGL((conv_patchc_kernel<NT>), dim3(strips * (a.Cout / 128)), dim3(256), lds, s, a, p.R);  // (R carries the patch's row count)
+}
+
+// The strip kernel's instantiations and the im2col kernel's, each with its symbol (the strip kernel's carries a tenth argument: SE tail in
+// the epilogue or not).
+enum { CV_G2_22, CV_G2_14, CV_P_PAIR, CV_P_SINGLE, CV_P_255, CV_P_255_SE, CV_P_264, CV_P_255_NT4, CV_P_255_NT4_SE, CV_P_NT2, CV_P_NT1, CV_PC_7, CV_PC_4 };
+const ConvRow kStrip[] = {
+    // everything no strip kernel takes: the im2col LDS-DMA kernel with a 2-stage (64 KB) ring, 2 workgroups per CU
+    /* CV_G2_22        */ {"conv_glds_kernel<2, 2, 2>", launch_glds_t<2, 2, 2>, -1},
+    /* CV_G2_14        */ {"conv_glds_kernel<1, 4, 2>", launch_glds_t<1, 4, 2>, -1},
+    /* CV_P_PAIR       */ {"conv_patch_kernel<3, 5, 5, true, true, 7, 2, 3, false>", launch_patch_t<3, 5, 5, true, true>, -1},  // pair mode: 2 strips x 68 KB patch
+    /* CV_P_SINGLE     */ {"conv_patch_kernel<3, 5, 5, true, false, 7, 1, 3, false>", launch_patch_t<3, 5, 5, true, false, 7, 1>, -1},  // 15 slots (60 KB)
+    // 2 x 40 KB patch buffers.
+    // (Round 3, built, measured and parked in tools/experiments/conv_patch2_two_cout_blocks_per_wave.hip: a wave owning TWO cout
+    //  blocks x half the pixel tiles, so that a B fragment read from LDS feeds two MFMAs - half the LDS bytes per MFMA at 256
+    //  registers, parity tests green.  40.9 -> 43.2 us per launch, pipelined step 3.274 -> 3.348 ms (profiles/r03/r03g_patch2_*):
+    //  the 4 + 3 split of 7 tiles puts 8 MFMA slots per kk step on the critical SIMDs, and the K loop was never LDS-bound - it
+    //  runs at 0.94 of the rate the part sustains for its instruction mix.)
+    /* CV_P_255        */ {"conv_patch_kernel<10, 1, 5, false, false, 7, 1, 3, false>", launch_patch_t<10, 1, 5, false, false, 7, 1>, CV_P_255_SE},
+    /* CV_P_255_SE     */ {"conv_patch_kernel<10, 1, 5, false, false, 7, 1, 3, true>", launch_patch_t<10, 1, 5, false, false, 7, 1, 3, true>, -1},
+    /* CV_P_264        */ {"conv_patch_kernel<2, 6, 4, false, false, 7, 2, 3, false>", launch_patch_t<2, 6, 4, false>, -1},  // 2 x 48 KB patch buffers
+    // 4 pixel tiles per strip (small maps)
+    /* CV_P_255_NT4    */ {"conv_patch_kernel<10, 1, 5, false, false, 4, 1, 3, false>", launch_patch_t<10, 1, 5, false, false, 4, 1>, CV_P_255_NT4_SE},
+    /* CV_P_255_NT4_SE */ {"conv_patch_kernel<10, 1, 5, false, false, 4, 1, 3, true>", launch_patch_t<10, 1, 5, false, false, 4, 1, 3, true>, -1},
+    // short strips for small batches: 2 x 20 KB patch buffers.
+    // (Round 3, measured and not kept: a 9-deep weight ring for these short-strip variants - 1 or 2 accumulator tiles leave the
+    //  registers for it.  4 / 16 / 32 faces: 12.4 -> 12.0, 14.0 -> 13.5, 18.7 -> 18.9 us per launch, batch-1 call 1.286 -> 1.280 ms
+    //  (profiles/r03/r03f_small_batch_wr.txt): a small-batch launch is prologue + four chunk hand-overs + epilogue + dispatch, not
+    //  weight latency.)
+    /* CV_P_NT2        */ {"conv_patch_kernel<5, 1, 5, false, false, 2, 1, 3, false>", launch_patch_t<5, 1, 5, false, false, 2, 1>, -1},
+    /* CV_P_NT1        */ {"conv_patch_kernel<5, 1, 5, false, false, 1, 1, 3, false>", launch_patch_t<5, 1, 5, false, false, 1, 1>, -1},
+    /* CV_PC_7         */ {"conv_patchc_kernel<7>", launch_patchc_t<7>, -1},
+    /* CV_PC_4         */ {"conv_patchc_kernel<4>", launch_patchc_t<4>, -1},
+};
+
+int strip_variant(const ConvMfmaArgs &a, int &R, int &n_img) {
+    int slots, nt;
+    bool single;
+    if (!patch_geometry(a, R, n_img, slots, single, nt)) return a.Cout % 128 == 0 ? CV_G2_22 : CV_G2_14;
+    if (a.Cout == 64) return CV_P_PAIR;
+    if (single) return CV_P_SINGLE;
+    if (nt == 1) return CV_P_NT1;
+    if (nt == 2) return CV_P_NT2;
+    // compact strips (round 6) wherever the full-batch geometry leaves dead pixel slots: whole 14x14 images in 7 tiles (196 of 224 slots
+    // live) -> 8 images per 7 strips; two 7x7 images in 4 tiles (98 of 128) -> 128 images per 49 strips.  Not for a conv2 described with
+    // the SE scratch: the fused SE tail pools per image inside a strip.
+    const bool epi_ok = a.mode == EPI_PRELU || a.mode == EPI_BN || (a.mode == EPI_BN_ADD_BN && !a.se_pool);
+    if (epi_ok && slots <= 10 && ((nt == 7 && n_img == 1 && R == a.H && a.H * a.W < 224) || (nt == 4 && n_img == 2 && 2 * a.H * a.W < 128))) {
+        const int npr = compact_patch_rows(a, nt);
+        if (npr > 0 && (npr * a.W + 1) * 9 <= 10 * 256) {
+            R = npr;
+            return nt == 7 ? CV_PC_7 : CV_PC_4;
+        }
+    }
+    if (nt == 4) return CV_P_255_NT4;
+    return slots <= 10 ? CV_P_255 : CV_P_264;
+}
+
+// the last family: never declines
+void plan_strip(const ConvMfmaArgs &a, ConvPlan &p) {
+    int R = 0, n_img = 1;
+    const int v = strip_variant(a, R, n_img);
+    conv_plan_row(p, CONV_STRIP, kStrip, v);
+    p.R = R;
+    p.n_img = n_img;
+    // IR-SE: only the strip kernel's main variants can run the whole SE tail in their epilogue, on row ranges of one image (at most SE_SPLIT
+    // of them) or two whole small images; everything else writes the BN output and leaves the tail to launch_se.
+    if (v == CV_P_255 ? (n_img == 1 && a.H / R <= SE_SPLIT) : (v == CV_P_255_NT4 && (n_img == 2 ? R == a.H : a.H / R <= SE_SPLIT))) conv_plan_se_twin(p, kStrip, a);
 }
 
 }  // namespace
 
-// Which kernel symbol a launch resolves to (also the profiling label, so bench.py / rocprofv3 can be matched by name).
-enum { CV_G2_22, CV_G2_14, CV_P_PAIR, CV_P_SINGLE, CV_P_255, CV_P_264, CV_P_255_NT4, CV_P_NT2, CV_P_NT1, CV_PC_7, CV_PC_4 };
-static int conv_variant(const ConvMfmaArgs &a, int &R, int &n_img) {
-    int slots, nt;
-    bool single;
-    if (patch_geometry(a, R, n_img, slots, single, nt)) {
-        if (a.Cout == 64) return CV_P_PAIR;   // pair mode: 2 strips x 68 KB patch
-        if (single) return CV_P_SINGLE;       // 15 slots (60 KB)
-        if (nt == 1) return CV_P_NT1;         // short strips for small batches: 2 x 20 KB patch buffers
-        if (nt == 2) return CV_P_NT2;
-        // compact strips (round 6) wherever the full-batch geometry leaves dead pixel slots: whole 14x14 images in 7 tiles (196 of 224 slots
-        // live) -> 8 images per 7 strips; two 7x7 images in 4 tiles (98 of 128) -> 128 images per 49 strips.  Not for the fused SE tail (it
-        // pools per image inside a strip) - conv_se_fused asks with the SE scratch set.
-        const bool epi_ok = a.mode == EPI_PRELU || a.mode == EPI_BN || (a.mode == EPI_BN_ADD_BN && !a.se_pool);
-        if (epi_ok && slots <= 10 && ((nt == 7 && n_img == 1 && R == a.H && a.H * a.W < 224) || (nt == 4 && n_img == 2 && 2 * a.H * a.W < 128))) {
-            const int npr = compact_patch_rows(a, nt);
-            if (npr > 0 && (npr * a.W + 1) * 9 <= 10 * 256) {
-                R = npr;
-                return nt == 7 ? CV_PC_7 : CV_PC_4;
-            }
-        }
-        if (nt == 4) return CV_P_255_NT4;     // 4 pixel tiles per strip (small maps)
-        return slots <= 10 ? CV_P_255 : CV_P_264;  // 2 x 40 KB / 2 x 48 KB patch buffers
-    }
-    // everything else: the im2col LDS-DMA kernel with a 2-stage (64 KB) ring, 2 workgroups per CU
-    return a.Cout % 128 == 0 ? CV_G2_22 : CV_G2_14;
+// The one ordered list of kernel families: the first whose planner takes the launch owns it.  A new recogniser kernel is registered here
+// (a new family) or as a row of a family's table - nowhere else.
+ConvPlan conv_plan(const ConvMfmaArgs &a) {
+    ConvPlan p;
+    if (plan_small(a, p)) return p;  // a small batch's few pixel tiles: one (32 couts x 32 pixels) unit per workgroup (kernels_arc_small.hip)
+    if (plan_ks(a, p)) return p;     // medium batches at 14x14x256 / 7x7x512: one 32-cout block x a strip, K split over the waves (kernels_arc_ks.hip)
+    if (plan_c64(a, p)) return p;    // dedicated 64 -> 64 stride-1 kernel (kernels_arc_c64.hip)
+    if (plan_s2(a, p)) return p;     // stride-2 strip kernel on de-interleaved phase planes (kernels_arc_s2.hip)
+    plan_strip(a, p);                // stride-1 strip kernel, or the im2col kernel
+    return p;
 }
 
-const char *conv_kernel_label(const ConvMfmaArgs &a) {
-    static const char *names[] = {"conv_glds_kernel<2, 2, 2>", "conv_glds_kernel<1, 4, 2>", "conv_patch_kernel<3, 5, 5, true, true, 7, 2, 3>",
-                                  "conv_patch_kernel<3, 5, 5, true, false, 7, 1, 3>", "conv_patch_kernel<10, 1, 5, false, false, 7, 1, 3>",
-                                  "conv_patch_kernel<2, 6, 4, false, false, 7, 2, 3>", "conv_patch_kernel<10, 1, 5, false, false, 4, 1, 3>",
-                                  "conv_patch_kernel<5, 1, 5, false, false, 2, 1, 3>", "conv_patch_kernel<5, 1, 5, false, false, 1, 1, 3>",
-                                  "conv_patchc_kernel<7>", "conv_patchc_kernel<4>"};
-    if (conv_small_applies(a)) return a.mode == EPI_BN_ADD_BN && a.scx ? "conv_small_kernel<true>" : "conv_small_kernel<false>";
-    if (conv_ks_applies(a)) return "conv_ks_kernel";
-    if (const char *l2 = conv_s2_label(a)) return l2;
-    if (conv64_applies(a))
-        return a.mode == EPI_PRELU ? "conv64_kernel<0>" : (a.mode == EPI_BN ? "conv64_kernel<1>" : "conv64_kernel<2>");
-    int R, n_img;
-    const int variant = conv_variant(a, R, n_img);
-    const char *base = names[variant];
-    if (!strncmp(base, "conv_patch_kernel", 17)) {  // the strip kernel's symbol carries a tenth argument: SE tail in the epilogue or not
-        static thread_local char buf[96];
-        snprintf(buf, sizeof(buf), "%.*s, %s>", (int)strlen(base) - 1, base, a.mode == EPI_BN_SE ? "true" : "false");
-        return buf;
+void launch_conv_mfma(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) {
+    switch (p.family) {
+        case CONV_SMALL: return launch_small(a, p, s);
+        case CONV_KS: return launch_ks(a, p, s);
+        case CONV_C64: return launch_c64(a, p, s);
+        case CONV_S2: return launch_s2(a, p, s);
+        default: return kStrip[p.row].launch(a, p, s);
     }
-    return base;
 }
 
-// IR-SE: can the launch of `a` (conv2 of a unit described as EPI_BN_ADD_BN, se_* scratch set) run the whole SE tail in its epilogue
-// (mode EPI_BN_SE)?  Only the strip kernel's main variant with row-range strips of single images can; everything else writes the BN
-// output and leaves the tail to launch_se.
-// The fused tail makes the (at most SE_SPLIT x 4) workgroups of one face wait for each other inside a launch, so they must be able to be
+// The fused SE tail makes the (at most SE_SPLIT x 4) workgroups of one face wait for each other inside a launch, so they must be able to be
 // resident together whatever else runs: checked once per device from the runtime's own occupancy figures for the two strip-kernel
 // instantiations that carry the tail (a device on which fewer than 16 of their workgroups fit - a much smaller part, a broken LDS opt-in -
 // gets the stand-alone tail instead of a hand-over that could starve).
-static bool se_fused_fits_device() {
+bool conv_se_fits_device() {
     static int ok[FRT_MAX_DEVICES] = {};  // 0 unknown, 1 yes, -1 no
     int d = 0;
     (void)hipGetDevice(&d);
@@ -999,55 +1033,6 @@ static bool se_fused_fits_device() {
         ok[d] = (q && (long)per_cu7 * prop.multiProcessorCount >= 16 && (long)per_cu4 * prop.multiProcessorCount >= 16) ? 1 : -1;
     }
     return ok[d] > 0;
-}
-
-bool conv_se_fused(const ConvMfmaArgs &a0) {
-    ConvMfmaArgs a = a0;
-    a.mode = EPI_BN_ADD_BN;  // same eligibility as the plain unit tail (shortcut with the output's geometry)
-    if (!a.se_pool || !a.sc || !a.out1 || conv_small_applies(a) || conv_ks_applies(a) || conv64_applies(a)) return false;
-    if (!se_fused_fits_device()) return false;
-    if (conv_s2_applies(a)) return conv_s2_se_fused(a);
-    int R = 0, n_img = 0;
-    const int v = conv_variant(a, R, n_img);
-    if (v == CV_P_255) return n_img == 1 && a.H / R <= SE_SPLIT;               // row ranges of one image
-    if (v == CV_P_255_NT4) return n_img == 2 ? R == a.H : a.H / R <= SE_SPLIT;  // two whole small images, or row ranges of one
-    return false;
-}
-
-void launch_conv_mfma(const ConvMfmaArgs &a, hipStream_t s) {
-    if (launch_conv_small(a, s)) return;  // a small batch's few pixel tiles: one (32 couts x 32 pixels) unit per workgroup (kernels_arc_small.hip)
-    if (launch_conv_ks(a, s)) return;     // medium batches at 14x14x256 / 7x7x512: one 32-cout block x a strip, K split over the waves (kernels_arc_ks.hip)
-    if (launch_conv64(a, s)) return;  // dedicated 64 -> 64 stride-1 kernel (kernels_arc_c64.hip)
-    if (launch_conv_s2(a, s)) return;  // stride-2 strip kernel on de-interleaved phase planes (kernels_arc_s2.hip)
-    int R = 0, n_img = 0;
-    const int v = conv_variant(a, R, n_img);
-    switch (v) {
-        case CV_P_PAIR: return launch_patch_t<3, 5, 5, true, true>(a, R, n_img, s);
-        case CV_P_SINGLE: return launch_patch_t<3, 5, 5, true, false, 7, 1>(a, R, n_img, s);
-        case CV_P_255:
-            if (a.mode == EPI_BN_SE)  // IR-SE conv2 with the whole SE tail in the epilogue (the caller checked conv_se_fused)
-                return launch_patch_t<10, 1, 5, false, false, 7, 1, 3, true>(a, R, n_img, s);
-            // (Round 3, built, measured and parked in tools/experiments/conv_patch2_two_cout_blocks_per_wave.hip: a wave owning TWO cout
-            //  blocks x half the pixel tiles, so that a B fragment read from LDS feeds two MFMAs - half the LDS bytes per MFMA at 256
-            //  registers, parity tests green.  40.9 -> 43.2 us per launch, pipelined step 3.274 -> 3.348 ms (profiles/r03/r03g_patch2_*):
-            //  the 4 + 3 split of 7 tiles puts 8 MFMA slots per kk step on the critical SIMDs, and the K loop was never LDS-bound - it
-            //  runs at 0.94 of the rate the part sustains for its instruction mix.)
-            return launch_patch_t<10, 1, 5, false, false, 7, 1>(a, R, n_img, s);
-        case CV_P_264: return launch_patch_t<2, 6, 4, false>(a, R, n_img, s);
-        case CV_PC_7: return launch_patchc_t<7>(a, R, s);
-        case CV_PC_4: return launch_patchc_t<4>(a, R, s);
-        case CV_P_255_NT4:
-            if (a.mode == EPI_BN_SE) return launch_patch_t<10, 1, 5, false, false, 4, 1, 3, true>(a, R, n_img, s);  // (conv_se_fused)
-            return launch_patch_t<10, 1, 5, false, false, 4, 1>(a, R, n_img, s);
-        // (Round 3, measured and not kept: a 9-deep weight ring for these short-strip variants - 1 or 2 accumulator tiles leave the
-        //  registers for it.  4 / 16 / 32 faces: 12.4 -> 12.0, 14.0 -> 13.5, 18.7 -> 18.9 us per launch, batch-1 call 1.286 -> 1.280 ms
-        //  (profiles/r03/r03f_small_batch_wr.txt): a small-batch launch is prologue + four chunk hand-overs + epilogue + dispatch, not
-        //  weight latency.)
-        case CV_P_NT2: return launch_patch_t<5, 1, 5, false, false, 2, 1>(a, R, n_img, s);
-        case CV_P_NT1: return launch_patch_t<5, 1, 5, false, false, 1, 1>(a, R, n_img, s);
-        case CV_G2_22: return launch_glds_t<2, 2, 2>(a, s);
-        default: return launch_glds_t<1, 4, 2>(a, s);
-    }
 }
 
 void launch_arc_input(const ArcInputArgs &a, hipStream_t s) {

@@ -242,31 +242,34 @@ __global__ __launch_bounds__(128) void conv64_kernel(ConvMfmaArgs p, int n_strip
 // lane the A operands of half the MFMAs come out of the accumulator file, and the kernel can no longer share a SIMD with another
 // wave.  The kernel above stays.
 
-}  // namespace
-
-// Cin == Cout == 64, 3x3, stride 1, pad 1, H even, W a multiple of 56.  false: not this shape (use the generic kernels).
-bool conv64_applies(const ConvMfmaArgs &a) {
-    if (a.Cin != 64 || a.Cout != 64 || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W) return false;
-    if ((a.H & 1) || a.W % SW || a.mode == EPI_PARTIAL) return false;
-    return a.mode != EPI_BN_ADD_BN || (a.sc && a.sc_stride == 1 && a.sc_h == a.H && a.sc_w == a.W);
-}
-
-bool launch_conv64(const ConvMfmaArgs &a, hipStream_t s) {
-    if (!conv64_applies(a)) return false;
+template <int MODE>
+void launch_c64_t(const ConvMfmaArgs &a, const ConvPlan &, hipStream_t s) {
     const int n_strips = a.B * (a.H / 2) * (a.W / SW);
     int grid = 512;
     if (grid > n_strips) grid = n_strips;
     const size_t lds = 2 * PATCH_B + 2 * 32 * EROW * sizeof(float);
     static bool attr_done[FRT_MAX_DEVICES] = {};
-    if (frt_first_use_on_device(attr_done)) {  // > 64 KB of dynamic LDS needs the opt-in
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_PRELU>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_BN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<EPI_BN_ADD_BN>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    }
-    switch (a.mode) {
-        case EPI_PRELU: hipLaunchKernelGGL((conv64_kernel<EPI_PRELU>), dim3(grid), dim3(128), lds, s, a, n_strips); break;
-        case EPI_BN: hipLaunchKernelGGL((conv64_kernel<EPI_BN>), dim3(grid), dim3(128), lds, s, a, n_strips); break;
-        default: hipLaunchKernelGGL((conv64_kernel<EPI_BN_ADD_BN>), dim3(grid), dim3(128), lds, s, a, n_strips); break;
-    }
+    if (frt_first_use_on_device(attr_done))  // > 64 KB of dynamic LDS needs the opt-in
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv64_kernel<MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL((conv64_kernel<MODE>), dim3(grid), dim3(128), lds, s, a, n_strips);
+}
+
+// row = the epilogue: PReLU, BN, everything else the shortcut-add form
+const ConvRow kC64[] = {
+    {"conv64_kernel<0>", launch_c64_t<EPI_PRELU>, -1},
+    {"conv64_kernel<1>", launch_c64_t<EPI_BN>, -1},
+    {"conv64_kernel<2>", launch_c64_t<EPI_BN_ADD_BN>, -1},
+};
+
+}  // namespace
+
+// Cin == Cout == 64, 3x3, stride 1, pad 1, H even, W a multiple of 56.  false: not this shape (use the generic kernels).
+bool plan_c64(const ConvMfmaArgs &a, ConvPlan &p) {
+    if (a.Cin != 64 || a.Cout != 64 || a.ks != 3 || a.stride != 1 || a.pad != 1 || a.Ho != a.H || a.Wo != a.W) return false;
+    if ((a.H & 1) || a.W % SW || a.mode == EPI_PARTIAL) return false;
+    if (a.mode == EPI_BN_ADD_BN && !(a.sc && a.sc_stride == 1 && a.sc_h == a.H && a.sc_w == a.W)) return false;
+    conv_plan_row(p, CONV_C64, kC64, a.mode == EPI_PRELU ? 0 : (a.mode == EPI_BN ? 1 : 2));
     return true;
 }
+
+void launch_c64(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) { kC64[p.row].launch(a, p, s); }

@@ -236,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(ConvMfmaArgs p) {
 }
 
 template <int NT, int CPW, int HW, int R>
-void launch_ks_t(const ConvMfmaArgs &a, hipStream_t s) {
+void launch_ks_t(const ConvMfmaArgs &a, const ConvPlan &, hipStream_t s) {
     constexpr int PIECES = ((R + 2) * (HW + 2) + 6) / 7;
     constexpr int PATCH_B = PIECES * 1008, RED_B = 4 * NT * 4096, EP_B = 4 * 32 * EROW * 4;
     constexpr int MAIN_B = 4 * CPW * PATCH_B > RED_B ? 4 * CPW * PATCH_B : RED_B;
@@ -250,24 +250,22 @@ void launch_ks_t(const ConvMfmaArgs &a, hipStream_t s) {
     hipLaunchKernelGGL((conv_ks_kernel<NT, CPW, HW, R>), dim3(a.B * spi, a.Cout / 32), dim3(256), lds, s, a);
 }
 
+const ConvRow kKs[] = {
+    {"conv_ks_kernel", launch_ks_t<2, 2, 7, 7>, -1},    // whole 7x7 images: 9 x 9 patch rows -> 12 pieces per chunk, 63 slots in 2 tiles
+    {"conv_ks_kernel", launch_ks_t<4, 1, 14, 7>, -1},   // half images (7 rows): 9 x 16 patch rows -> 21 pieces, 112 slots in 4 tiles
+    {"conv_ks_kernel", launch_ks_t<7, 1, 14, 14>, -1},  // whole images: 16 x 16 patch rows -> 37 pieces, 224 slots in 7 tiles
+};
+
 }  // namespace
 
-bool conv_ks_applies(const ConvMfmaArgs &a) {
+bool plan_ks(const ConvMfmaArgs &a, ConvPlan &p) {
     if (a.ks != 3 || a.stride != 1 || a.pad != 1 || !a.wf || a.splits != 1 || a.Cout % 32 || a.H != a.W || a.Ho != a.H || a.Wo != a.W) return false;
     if (!((a.H == 14 && a.Cin == 256) || (a.H == 7 && a.Cin == 512))) return false;
     if (a.mode != EPI_PRELU && a.mode != EPI_BN && a.mode != EPI_BN_ADD_BN) return false;
     if (a.mode == EPI_BN_ADD_BN && (a.scx || !a.sc || a.sc_stride != 1 || a.sc_h != a.Ho || a.sc_w != a.Wo)) return false;
-    return a.B >= 1 && a.B <= 40;  // faces per pass this kernel takes (above: the strip kernels; conv_small_kernel is asked first and keeps the small batches)
-}
-
-bool launch_conv_ks(const ConvMfmaArgs &a, hipStream_t s) {
-    if (!conv_ks_applies(a)) return false;
-    if (a.H == 7) {
-        launch_ks_t<2, 2, 7, 7>(a, s);   // whole 7x7 images: 9 x 9 patch rows -> 12 pieces per chunk, 63 slots in 2 tiles
-    } else if (a.B * 2 * (a.Cout / 32) <= 320) {
-        launch_ks_t<4, 1, 14, 7>(a, s);  // half images (7 rows): 9 x 16 patch rows -> 21 pieces, 112 slots in 4 tiles
-    } else {
-        launch_ks_t<7, 1, 14, 14>(a, s); // whole images: 16 x 16 patch rows -> 37 pieces, 224 slots in 7 tiles
-    }
+    if (a.B < 1 || a.B > 40) return false;  // faces per pass this kernel takes (above: the strip kernels; conv_small_kernel is asked first and keeps the small batches)
+    conv_plan_row(p, CONV_KS, kKs, a.H == 7 ? 0 : (a.B * 2 * (a.Cout / 32) <= 320 ? 1 : 2));
     return true;
 }
+
+void launch_ks(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) { kKs[p.row].launch(a, p, s); }

@@ -540,15 +540,27 @@ bool s2c64_applies(const ConvMfmaArgs &a) {
 }
 
 template <int NT, int PP, bool SEP = false, bool SCF = false>
-void launch_s2_t(const ConvMfmaArgs &a, int R, int n_img, hipStream_t s) {
+void launch_s2_t(const ConvMfmaArgs &a0, const ConvPlan &p, hipStream_t s) {
     constexpr size_t lds = (size_t)4 * PP * 4096;
     static_assert(lds <= 160 * 1024 && lds >= 4 * 32 * 36 * 4, "LDS budget / epilogue scratch");
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done))
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_s2_kernel<NT, PP, SEP, SCF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    const int strips = ((a.B + n_img - 1) / n_img) * (a.Ho / R);
-    const int linear = (n_img == 1 && R * (a.Wo + 1) <= NT * 32) ? 1 : 0;
-    hipLaunchKernelGGL((conv_s2_kernel<NT, PP, SEP, SCF>), dim3(strips * (a.Cout / 128)), dim3(256), lds, s, a, R, n_img, linear);
+    ConvMfmaArgs a = a0;
+    a.wf = a0.wf2;  // the kernel streams the stride-2 step order
+    const int strips = ((a.B + p.n_img - 1) / p.n_img) * (a.Ho / p.R);
+    const int linear = (p.n_img == 1 && p.R * (a.Wo + 1) <= NT * 32) ? 1 : 0;
+    hipLaunchKernelGGL((conv_s2_kernel<NT, PP, SEP, SCF>), dim3(strips * (a.Cout / 128)), dim3(256), lds, s, a, p.R, p.n_img, linear);
+}
+
+void launch_s2c64(const ConvMfmaArgs &a0, const ConvPlan &, hipStream_t s) {
+    ConvMfmaArgs a = a0;
+    a.wf = a0.wf2;  // tap order for this kernel (the host packs wf2 in tap order when Cout == 64, frt_embedder.cpp: build())
+    static bool attr_done[FRT_MAX_DEVICES] = {};
+    if (frt_first_use_on_device(attr_done))
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_s2c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C64_LDS);
+    const int n_rows = a.B * a.Ho;
+    hipLaunchKernelGGL(conv_s2c64_kernel, dim3(n_rows < 768 ? n_rows : 768), dim3(128), C64_LDS, s, a, n_rows);
 }
 
 // strip geometry; false: not eligible (the im2col kernel takes the layer)
@@ -580,60 +592,43 @@ bool s2_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &nt, int &pp) {
     return pp <= 9;
 }
 
+// rows of one (NT, PP) sit together: shortcut tensor / no shortcut, fused shortcut conv (SCF), SE tail (SEP)
+enum { S2_C64, S2_7, S2_7_SCF, S2_7_SE, S2_4, S2_4_SCF, S2_4_SE, S2_4W, S2_4W_SCF, S2_2, S2_2_SCF };
+const ConvRow kS2[] = {
+    /* S2_C64    */ {"conv_s2c64_kernel", launch_s2c64, -1},
+    /* S2_7      */ {"conv_s2_kernel<7, 9, false, false>", launch_s2_t<7, 9>, S2_7_SE},
+    /* S2_7_SCF  */ {"conv_s2_kernel<7, 9, false, true>", launch_s2_t<7, 9, false, true>, -1},
+    /* S2_7_SE   */ {"conv_s2_kernel<7, 9, true, false>", launch_s2_t<7, 9, true>, -1},
+    /* S2_4      */ {"conv_s2_kernel<4, 5, false, false>", launch_s2_t<4, 5>, S2_4_SE},
+    /* S2_4_SCF  */ {"conv_s2_kernel<4, 5, false, true>", launch_s2_t<4, 5, false, true>, -1},
+    /* S2_4_SE   */ {"conv_s2_kernel<4, 5, true, false>", launch_s2_t<4, 5, true>, -1},
+    /* S2_4W     */ {"conv_s2_kernel<4, 9, false, false>", launch_s2_t<4, 9>, -1},
+    /* S2_4W_SCF */ {"conv_s2_kernel<4, 9, false, true>", launch_s2_t<4, 9, false, true>, -1},
+    /* S2_2      */ {"conv_s2_kernel<2, 5, false, false>", launch_s2_t<2, 5>, -1},
+    /* S2_2_SCF  */ {"conv_s2_kernel<2, 5, false, true>", launch_s2_t<2, 5, false, true>, -1},
+};
+
 }  // namespace
 
-// IR-SE: can the launch of `a` (described as EPI_BN_ADD_BN + se_* scratch) run the SE tail in its epilogue?  (row-range strips of one image)
-bool conv_s2_se_fused(const ConvMfmaArgs &a) {
-    int R, n_img, nt, pp;
-    if (s2c64_applies(a) || !s2_geometry(a, R, n_img, nt, pp)) return false;
-    if (nt == 7) return n_img == 1 && a.Ho / R <= SE_SPLIT;
-    if (nt == 4 && pp <= 5) return n_img == 2 ? R == a.Ho : (n_img == 1 && a.Ho / R <= SE_SPLIT);
-    return false;
-}
-
-bool conv_s2_applies(const ConvMfmaArgs &a) {
-    int R, n_img, nt, pp;
-    return s2c64_applies(a) || s2_geometry(a, R, n_img, nt, pp);
-}
-
-const char *conv_s2_label(const ConvMfmaArgs &a) {
-    int R, n_img, nt, pp;
-    if (s2c64_applies(a)) return "conv_s2c64_kernel";
-    if (!s2_geometry(a, R, n_img, nt, pp)) return nullptr;
-    const bool scf = a.mode == EPI_BN_ADD_BN && a.scx;
-    if (a.mode == EPI_BN_SE) return nt == 7 ? "conv_s2_kernel<7, 9, true, false>" : "conv_s2_kernel<4, 5, true, false>";
-    if (nt == 7) return scf ? "conv_s2_kernel<7, 9, false, true>" : "conv_s2_kernel<7, 9, false, false>";
-    if (nt == 4) return pp <= 5 ? (scf ? "conv_s2_kernel<4, 5, false, true>" : "conv_s2_kernel<4, 5, false, false>")
-                                : (scf ? "conv_s2_kernel<4, 9, false, true>" : "conv_s2_kernel<4, 9, false, false>");
-    return scf ? "conv_s2_kernel<2, 5, false, true>" : "conv_s2_kernel<2, 5, false, false>";
-}
-
-bool launch_conv_s2(const ConvMfmaArgs &a0, hipStream_t s) {
-    int R, n_img, nt, pp;
-    if (s2c64_applies(a0)) {
-        ConvMfmaArgs a = a0;
-        a.wf = a0.wf2;  // tap order for this kernel (the host packs wf2 in tap order when Cout == 64, frt_api.cpp)
-        static bool attr_done[FRT_MAX_DEVICES] = {};
-        if (frt_first_use_on_device(attr_done))
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_s2c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, C64_LDS);
-        const int n_rows = a.B * a.Ho;
-        hipLaunchKernelGGL(conv_s2c64_kernel, dim3(n_rows < 768 ? n_rows : 768), dim3(128), C64_LDS, s, a, n_rows);
+bool plan_s2(const ConvMfmaArgs &a, ConvPlan &p) {
+    if (s2c64_applies(a)) {
+        conv_plan_row(p, CONV_S2, kS2, S2_C64);
         return true;
     }
-    if (!s2_geometry(a0, R, n_img, nt, pp)) return false;
-    ConvMfmaArgs a = a0;
-    a.wf = a0.wf2;  // the kernel streams the stride-2 step order
+    int R, n_img, nt, pp;
+    if (!s2_geometry(a, R, n_img, nt, pp)) return false;
     const bool scf = a.mode == EPI_BN_ADD_BN && a.scx;
-    if (nt == 7 && a.mode == EPI_BN_SE) launch_s2_t<7, 9, true>(a, R, n_img, s);  // (the caller checked conv_s2_se_fused)
-    else if (nt == 7 && scf) launch_s2_t<7, 9, false, true>(a, R, n_img, s);
-    else if (nt == 7) launch_s2_t<7, 9>(a, R, n_img, s);
-    else if (nt == 4 && pp <= 5 && a.mode == EPI_BN_SE) launch_s2_t<4, 5, true>(a, R, n_img, s);
-    else if (nt == 4 && pp <= 5 && scf) launch_s2_t<4, 5, false, true>(a, R, n_img, s);
-    else if (nt == 4 && pp <= 5) launch_s2_t<4, 5>(a, R, n_img, s);
-    else if (nt == 4 && scf) launch_s2_t<4, 9, false, true>(a, R, n_img, s);
-    else if (nt == 4) launch_s2_t<4, 9>(a, R, n_img, s);
-    else if (pp <= 5 && scf) launch_s2_t<2, 5, false, true>(a, R, n_img, s);
-    else if (pp <= 5) launch_s2_t<2, 5>(a, R, n_img, s);
-    else return false;
+    // (two tiles: one whole image of at most 8 x 8 outputs, or two of at most 5 x 5 - planes of at most 81 / 72 pixels, pp <= 3: the <2, 5>
+    //  instantiation always holds them)
+    const int base = nt == 7 ? S2_7 : (nt == 4 ? (pp <= 5 ? S2_4 : S2_4W) : S2_2);
+    conv_plan_row(p, CONV_S2, kS2, base + (scf ? 1 : 0));
+    p.R = R;
+    p.n_img = n_img;
+    p.uses_scx = scf;
+    // IR-SE: the tail in the epilogue needs strips that are row ranges of one image (at most SE_SPLIT of them) or two whole small images
+    const bool se_geom = nt == 7 ? (n_img == 1 && a.Ho / R <= SE_SPLIT) : (n_img == 2 ? R == a.Ho : (n_img == 1 && a.Ho / R <= SE_SPLIT));
+    if (se_geom) conv_plan_se_twin(p, kS2, a);
     return true;
 }
+
+void launch_s2(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) { kS2[p.row].launch(a, p, s); }

@@ -196,15 +196,41 @@ __global__ __launch_bounds__(NW * 64) void conv_small_kernel(ConvMfmaArgs p, con
 // kernel however small the batch - win at 30 000 (16 faces: 25 - 27 us) and lose at 60 000 (32 faces, 14 -> 7: 47 against 43).
 long small_work_limit(int stride) { return stride == 2 ? 40000 : 16000; }
 
+// Four waves, one pixel tile, ring of 3.  (Measured and not kept: 8 waves with every load of the launch in flight at once (ring of 5),
+// and 2 / 4 PIXEL tiles per workgroup sharing the weight fragments (8 waves, rings of 3 / 2) - 1 face 412 / 404 / 720 us per pass,
+// 4 faces 500 / 547 / 800: a workgroup's time is the ~ 300 KB of operands it pulls through its CU's vector memory path, not the number
+// of round trips, and a second pixel tile doubles the gathers.  Also not
+// kept: the pixel operand fetched as whole 128-byte chunks of 8 pixels per load (8 cache lines per instruction instead of the gather's
+// 32) and transposed into MFMA fragments through a wave-private LDS tile, with 1 / 2 / 4 tiles per workgroup: bit-identical results,
+// 430 / 659 us (1 face), 504 / 716 us (4 faces), 16 - 32 faces 1.3 - 3.1 ms per pass (profiles/r03/r03x_small_lds.txt).)
+template <bool SCF, int NW, int NC, int D>
+void launch_small_t(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) {
+    // tap of K step `st` in the weight array: natural order, or the stride-2 strip kernel's 0,2,6,8,4,1,7,3,5 (not for its 64 -> 64 form)
+    const bool s2_order = a.stride == 2 && !(a.Cin == 64 && a.Cout == 64);
+    const unsigned long long taps = s2_order ? 0x537148620ull : 0x876543210ull;
+    const half_t *wfrag = a.stride == 1 ? a.wf : a.wf2;
+    const dim3 grid((p.M + 31) / 32, a.Cout / (32 * NC));
+    hipLaunchKernelGGL((conv_small_kernel<SCF, NW, NC, D>), grid, dim3(NW * 64), 0, s, a, wfrag, taps, p.M);
+}
+
+// row = SCF + 2 * (NC - 1)
+const ConvRow kSmall[] = {
+    {"conv_small_kernel<false>", launch_small_t<false, 4, 1, 3>, -1},
+    {"conv_small_kernel<true>", launch_small_t<true, 4, 1, 3>, -1},
+    {"conv_small_kernel<false>", launch_small_t<false, 4, 2, 3>, -1},
+    {"conv_small_kernel<true>", launch_small_t<true, 4, 2, 3>, -1},
+};
+
 }  // namespace
 
 // 3x3 / pad 1 / stride 1 or 2 with fragment-ordered weights, Cin % 64 == 0, Cout % 32 == 0, the unit epilogues without the SE tail
 // (PReLU; BN; BN + shortcut tensor or fused 1x1 stride-2 shortcut conv + next BN), few enough output pixels.
-bool conv_small_applies(const ConvMfmaArgs &a) {
+bool plan_small(const ConvMfmaArgs &a, ConvPlan &p) {
     if (a.ks != 3 || a.pad != 1 || (a.stride != 1 && a.stride != 2) || a.Cin % 64 || a.Cout % 32 || a.splits != 1) return false;
     if (!(a.stride == 1 ? a.wf : a.wf2)) return false;
     if (a.Ho != a.H / a.stride || a.Wo != a.W / a.stride) return false;
     if (a.mode != EPI_PRELU && a.mode != EPI_BN && a.mode != EPI_BN_ADD_BN) return false;
+    const bool scf = a.mode == EPI_BN_ADD_BN && a.scx;
     if (a.mode == EPI_BN_ADD_BN) {
         if (a.scx) {
             if (!(a.stride == 2 && a.wscf && a.psc0 && a.psc1 && a.Csc % 64 == 0)) return false;
@@ -213,41 +239,17 @@ bool conv_small_applies(const ConvMfmaArgs &a) {
         }
     }
     const long M = (long)a.B * a.Ho * a.Wo;
-    const long pairs = a.Cin / 64 * 9 + (a.mode == EPI_BN_ADD_BN && a.scx ? a.Csc / 64 : 0);
-    return (M + 31) / 32 * (a.Cout / 32) * pairs <= small_work_limit(a.stride);
-}
-
-template <bool SCF, int NW, int NC, int D>
-void launch_small_t(const ConvMfmaArgs &a, const half_t *wfrag, unsigned long long taps, int M, hipStream_t s) {
-    const dim3 grid((M + 31) / 32, a.Cout / (32 * NC));
-    hipLaunchKernelGGL((conv_small_kernel<SCF, NW, NC, D>), grid, dim3(NW * 64), 0, s, a, wfrag, taps, M);
-}
-
-bool launch_conv_small(const ConvMfmaArgs &a, hipStream_t s) {
-    if (!conv_small_applies(a)) return false;
-    const int M = a.B * a.Ho * a.Wo;
-    // tap of K step `st` in the weight array: natural order, or the stride-2 strip kernel's 0,2,6,8,4,1,7,3,5 (not for its 64 -> 64 form)
-    const bool s2_order = a.stride == 2 && !(a.Cin == 64 && a.Cout == 64);
-    const unsigned long long taps = s2_order ? 0x537148620ull : 0x876543210ull;
-    const half_t *wfrag = a.stride == 1 ? a.wf : a.wf2;
-    const bool scf = a.mode == EPI_BN_ADD_BN && a.scx;
-    // Four waves, one pixel tile, ring of 3.  (Measured and not kept: 8 waves with every load of the launch in flight at once (ring of 5),
-    // and 2 / 4 PIXEL tiles per workgroup sharing the weight fragments (8 waves, rings of 3 / 2) - 1 face 412 / 404 / 720 us per pass,
-    // 4 faces 500 / 547 / 800: a workgroup's time is the ~ 300 KB of operands it pulls through its CU's vector memory path, not the number
-    // of round trips, and a second pixel tile doubles the gathers.  Also not
-    // kept: the pixel operand fetched as whole 128-byte chunks of 8 pixels per load (8 cache lines per instruction instead of the gather's
-    // 32) and transposed into MFMA fragments through a wave-private LDS tile, with 1 / 2 / 4 tiles per workgroup: bit-identical results,
-    // 430 / 659 us (1 face), 504 / 716 us (4 faces), 16 - 32 faces 1.3 - 3.1 ms per pass (profiles/r03/r03x_small_lds.txt).)
-    const int wgs = (M + 31) / 32 * (a.Cout / 32);
-    const int nc = wgs > 256 && a.Cout % 64 == 0 ? 2 : 1;  // more one-block units than CUs: two cout blocks per workgroup share the pixel fragments
+    const long pairs = a.Cin / 64 * 9 + (scf ? a.Csc / 64 : 0);
+    const long wgs = (M + 31) / 32 * (a.Cout / 32);
+    if (wgs * pairs > small_work_limit(a.stride)) return false;
+    // more one-block units than CUs: two cout blocks per workgroup share the pixel fragments
     // (four cout blocks per workgroup, ring of 2: 8 / 12 / 16 / 32 faces 0.86 / 1.00 / 1.04 / 1.61 ms per pass against 0.73 / 0.86 / 0.91 / 1.19 -
     //  from ~ 10 faces on the strip kernels win, profiles/r03/r03z_small_nc4.txt)
-    if (nc == 2) {
-        if (scf) launch_small_t<true, 4, 2, 3>(a, wfrag, taps, M, s);
-        else launch_small_t<false, 4, 2, 3>(a, wfrag, taps, M, s);
-    } else {
-        if (scf) launch_small_t<true, 4, 1, 3>(a, wfrag, taps, M, s);
-        else launch_small_t<false, 4, 1, 3>(a, wfrag, taps, M, s);
-    }
+    const int nc = wgs > 256 && a.Cout % 64 == 0 ? 2 : 1;
+    conv_plan_row(p, CONV_SMALL, kSmall, (scf ? 1 : 0) + 2 * (nc - 1));
+    p.M = (int)M;
+    p.uses_scx = scf;
     return true;
 }
+
+void launch_small(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) { kSmall[p.row].launch(a, p, s); }

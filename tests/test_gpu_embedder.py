@@ -308,3 +308,41 @@ def test_compact_strips_at_ragged_batches(frt, synth, blobs, mode):
             # downstream (measured: 1 face of 128, 6e-6 in one element; with the stand-alone SE tail: none)
             diff = (back != e).any(1)
             assert diff.sum() <= 3 and np.abs(back - e).max() < 5e-5 and ((back * e).sum(1) > 1 - 1e-6).all(), (mode, F, int(diff.sum()))
+
+
+def conv_label_sequence(frt, path, fused, F):
+    """Profiling labels of the conv launches of ONE doInference pass of F faces on a fresh embedder (public Python surface only)."""
+    rec = frt.ArcFaceIR50(path, maxBatchSize=F)
+    if fused is not None:
+        rec.setSeFused(fused)
+    x = np.random.default_rng(F).standard_normal((F, 3, 112, 112)).astype(np.float32) * 0.5
+    frt.profile_enable(1)
+    try:
+        rec.doInference(x)
+        labels, _, _ = frt.profile_collect()
+    finally:
+        frt.profile_enable(0)
+        rec.close()
+    return labels
+
+
+CONV_LABEL_CASES = [("ir", None), ("ir_se", True), ("ir_se", False)]
+CONV_LABEL_BATCHES = (1, 12, 33, 64, 128)
+
+
+def conv_label_key(mode, fused, F):
+    return "%s%s F=%d" % (mode, "" if fused is None else (" fused" if fused else " standalone"), F)
+
+
+@pytest.mark.parametrize("F", CONV_LABEL_BATCHES)
+@pytest.mark.parametrize("mode,fused", CONV_LABEL_CASES)
+def test_conv_launch_labels_are_the_recorded_ones(frt, blobs, mode, fused, F):
+    """The kernels one pass really launches - per-device SE gate included - are the ones tests/golden/arc_conv_labels.json holds: the label
+    sequence this same code recorded on an MI355X with the library of the commit before the dispatch became conv_plan (two launches per
+    unit: conv1, conv2).  IR-50, and IR-SE-50 with the SE tail in conv2's epilogue and as launches of its own; one batch per size class."""
+    import json
+    path, _ = blobs(mode)
+    want = json.load(open(os.path.join(GOLDEN, "arc_conv_labels.json")))[conv_label_key(mode, fused, F)]
+    got = conv_label_sequence(frt, path, fused, F)
+    assert len(want) == 48
+    assert got == want

@@ -7,8 +7,9 @@
 // stores) costs what the direct kernel's whole K loop costs, and at 103 KB of LDS there is one workgroup per CU and one wave per SIMD, so
 // nothing overlaps the VALU work of transform and fold with another wave's MFMAs.  Halving the MFMAs (512 instead of 1 008 per wave) buys ~ 13 us
 // of the direct kernel's 27 us K loop; transform + fold + the 16/9 weight bytes cost more.  See DESIGN 3.15.
-// To rebuild: add kernels_arc_wino to csrc/Makefile's NAMES, declare conv_wino_applies / launch_conv_wino and ConvMfmaArgs::wu in
-// frt_kernels.h, call them from launch_conv_mfma, and give frt_api.cpp the host-side weight transform at the end of this file.
+// To rebuild: add kernels_arc_wino to csrc/Makefile's NAMES, declare ConvMfmaArgs::wu and a plan / launch pair made of conv_wino_applies /
+// launch_conv_wino in frt_kernels.h, register it as a family in conv_plan (it called them from launch_conv_mfma), and give frt_embedder.cpp the
+// host-side weight transform at the end of this file.
 //
 // ArcFace IR-50: the 256 -> 256 3x3 stride-1 convolutions at 14x14 (26 of the 48 convs; model_irse.py:58-66 in the third stage) as
 // Winograd F(2x2, 3x3): 16 multiplies per 2x2 output tile and channel pair instead of 36 - under the package power limit the pipelined
