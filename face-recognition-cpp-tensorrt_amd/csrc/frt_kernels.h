@@ -32,26 +32,29 @@ struct MatchPartial {  // one per (workgroup, query)
     float sim;
     int32_t idx;
 };
-// top-1: gallery [N][512] fp32, queries [F][512] fp32 -> idx[F], sim[F].  partial: scratch [grid][F].
-void launch_match_top1(const float *gallery, int N, int D, const float *queries, int F, MatchPartial *partial, int partial_blocks,
-                       int32_t *idx_out, float *sim_out, int row_offset, hipStream_t s);
+// Every launcher that reads gallery rows is a template on their storage type GT, instantiated for float (the reference's row-major fp32
+// layout) and half_t (the fp16-STORED gallery of BASELINE config 5, MFMA-fragment order; rows widened exactly to fp32 while they are staged).
+// top-1 by the exact scan: rows [N][D], queries [F][D] fp32 -> idx[F], sim[F].  partial: scratch [grid][F].
+template <typename GT>
+void launch_match_top1(const GT *rows, int N, int D, const float *queries, int F, MatchPartial *partial, int partial_blocks, int32_t *idx_out,
+                       float *sim_out, int row_offset, hipStream_t s);
 int match_top1_blocks(int N, int F);
-// screened top-1: fp16 shadow gallery + coarse MFMA pass + exact re-rank of the few tiles that can hold the maximum
-constexpr int FRT_MATCH_CTL_WORDS = 32 + 64 * 32;
+// full matrix: out[F][N]
+template <typename GT>
+void launch_match_full(const GT *rows, int N, int D, const float *queries, int F, float *out, hipStream_t s);
+// screened search: shadow gallery (int8 or fp16) + coarse MFMA pass + exact re-rank of the few 32-row blocks that can hold the answer.
+// What the host sizes the scratch by:
+constexpr int FRT_MATCH_COARSE_WG = 256;  // persistent workgroups of the coarse scan (one per CU), each with at least one 128-row tile
+constexpr int FRT_MATCH_SEL_SUB = 64;     // sub-lists of the candidate pair list (16 tile segments x 4 query classes), one counter each
+constexpr int FRT_MATCH_CTL_WORDS = 32 + FRT_MATCH_SEL_SUB * 32;
 struct ScreenScratch {
-    half_t *q16;       // [F][D]
-    float *tilemax;    // [F][tiles][sub], sub = 1 or 4 coarse maxima per 128-row tile
-    int *tile_flags;   // [tiles]
-    int *tile_list;    // [tiles]
-    int *count;        // [1], == tile_flags + tiles (cleared together)
-    float *segmax;     // [F][16] per-segment maxima of tilemax (selection step 1)
-    // fast top-1 path (round 3): null -> the tile-list path
-    float *wgmax;                 // [coarse workgroups][F] maxima of a workgroup's coarse entries
+    float *tilemax;               // [F][tiles][4] coarse maxima: one per 32-row block of a 128-row tile
+    float *wgmax;                 // [FRT_MATCH_COARSE_WG][F] maxima of a workgroup's coarse entries
     void *pairs;                  // (query, tile) candidate pairs
-    int pair_cap;
+    int pair_cap;                 // a multiple of FRT_MATCH_SEL_SUB
     int *ctl;                     // [FRT_MATCH_CTL_WORDS] control words: overflow flag, per-sub-list pair counts, one 128-byte line each (kernels_match.hip)
     unsigned long long *qkey;     // [F] packed (similarity, ~row) winners of the scalar re-rank
-    // int8 shadow gallery (round 4; fast path, D = 512, fp32-stored galleries): null -> the fp16 shadow is scanned
+    // int8 shadow gallery (D = 512, fp32-stored galleries): null -> the fp16 shadow is scanned
     const uint8_t *g8;            // fragment-ordered biased bytes (value + 128), gallery8_bytes(N, D)
     const float *g8_scale;        // [tiles * 128] per-row scale (row = scale * int8 row + error)
     float gerr;                   // max over rows of || row - scale * int8 row ||
@@ -60,10 +63,13 @@ size_t gallery8_bytes(int N, int D);
 // fp32 rows -> int8 shadow (+ per-row scales, largest quantisation error norm^2 and largest row norm^2 as float bit patterns, atomicMax)
 void launch_gallery_shadow8(const float *gallery, int N, int D, uint8_t *g8, float *scale, int *max_err2_bits, int *max_norm2_bits, hipStream_t s);
 void launch_gallery_shadow(const float *gallery, int N, int D, half_t *g16, int *max_norm2_bits, hipStream_t s);
-void launch_match_top1_screened(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, float gmax_norm,
-                                const ScreenScratch &w, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
-                                int row_offset, hipStream_t s);
-// exact top-k [F][k] (k passes of the top-1 search over the rows behind the previous winner; screened galleries scan coarsely once)
+// exact top-k [F][k] through the screen, k = 1 being the top-1 search: one coarse scan, then k passes of the exact re-rank over the rows
+// behind the previous winner.  The exact passes read `gallery`, or the stored fp16 rows g16 when gallery == nullptr.  Needs
+// ceil(N / 128) >= FRT_MATCH_COARSE_WG; kth_scratch [F] floats (k > 1 only).
+void launch_match_screened(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, float gmax_norm,
+                           const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
+                           int row_offset, hipStream_t s);
+// exact top-k [F][k]: screen -> launch_match_screened, else k passes of the exact scan over the rows behind the previous winner
 void launch_match_topk(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, bool screen, float gmax_norm,
                        const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
                        int row_offset, hipStream_t s);
@@ -71,24 +77,17 @@ int match_topk_max();
 void launch_half_to_float(const half_t *in, long n, float *out, hipStream_t s);
 void launch_float_to_half(const float *in, long n, half_t *out, hipStream_t s);
 void launch_merge_topk(const int32_t *idx_all, const float *sim_all, int shards, int n, int k, int32_t *idx_out, float *sim_out, hipStream_t s);
-// full matrix: out[F][N]
-void launch_match_full(const float *gallery, int N, int D, const float *queries, int F, float *out, hipStream_t s);
-// fp16-STORED gallery (BASELINE config 5): same kernels, rows widened exactly to fp32 while they are staged.  For the screened
-// top-1 pass gallery == nullptr and g16 = the stored rows.
-void launch_match_top1_h(const half_t *g16, int N, int D, const float *queries, int F, MatchPartial *partial, int partial_blocks,
-                         int32_t *idx_out, float *sim_out, int row_offset, hipStream_t s);
-void launch_match_full_h(const half_t *g16, int N, int D, const float *queries, int F, float *out, hipStream_t s);
-void launch_gallery_norm16(const half_t *g16, int N, int D, int *max_norm2_bits, hipStream_t s);
 // The fp16 gallery (shadow or stored) is kept in MFMA-fragment order and padded to whole 128-row tiles (see kernels_match.hip):
 size_t gallery16_elems(int N, int D);
 bool match_screen_supported(int D);  // D the coarse kernel is instantiated for
 // fp32 rows [n_rows][D] (first row = global row row0) -> their place in the fp16 gallery (whose rows never written must be zero)
 void launch_rows_to_half(const float *in, long row0, long n_rows, int D, half_t *g16, hipStream_t s);
+// largest squared row norm of rows [row0, row0 + n_rows) as a float bit pattern (all an fp16-stored gallery needs: it is its own shadow)
+template <typename GT>
+void launch_rows_norm(const GT *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s);
 // live gallery edits (frt_matcher_gallery_add / _remove): row-range forms of the shadow build, and the gather half of the chunked in-place
 // compaction (keys / klo / khi: frt_holes.h; the bounce buffer receives the chunk in its final layout, a copy on the same stream places it)
 void launch_gallery_shadow8_rows(const float *rows, int row0, int n_rows, uint8_t *g8, float *scale, int *max_err2_bits, int *max_norm2_bits, hipStream_t s);
-void launch_rows_norm(const float *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s);
-void launch_rows_norm16(const half_t *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s);
 void launch_gather_rows(const float *G, int D, int a, int n_rows, const int *keys, int klo, int khi, float *bounce, hipStream_t s);
 void launch_gather_rows16(const half_t *G, int D, long tile0, long n_tiles, int n_new, const int *keys, int klo, int khi, half_t *bounce, hipStream_t s);
 

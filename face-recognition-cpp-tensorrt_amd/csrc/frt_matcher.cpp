@@ -129,7 +129,7 @@ void add_rows(frt_matcher *m, const void *rows, int n, bool on_device) {
         if (!m->store16) m->edit_stats[2] += new_n;
     } else if (m->screen) {  // tail update: only the new rows are converted into their places
         if (m->store16) {
-            launch_rows_norm16(m->d_g16, N, n, D, m->d_edit_bits + 1, s);
+            launch_rows_norm(m->d_g16, N, n, D, m->d_edit_bits + 1, s);
             HIPCHK(hipMemsetAsync(m->d_edit_bits, 0, sizeof(int), s));
         } else if (m->d_g8 && D == 512) {
             launch_gallery_shadow8_rows(src32, N, n, m->d_g8, m->d_g8_scale, m->d_edit_bits, m->d_edit_bits + 1, s);
@@ -213,6 +213,46 @@ void remove_rows(frt_matcher *m, const int32_t *idx, int n_idx) {
         m->edit_stats[2] += n_re;
     }
     finish_edit(m, new_n);
+}
+
+// What every host entry point that takes queries starts with (the caller holds m->mu): the queries are in d_q, on the returned stream
+hipStream_t upload_queries(frt_matcher *m, const float *embeds, int F) {
+    if (m->N <= 0 || F <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
+    use_device(m->device);
+    hipStream_t s = m->stream;
+    m->wait_idle(s);
+    m->ensure_queries(F);
+    HIPCHK(hipMemcpyAsync(m->d_q, embeds, sizeof(float) * (size_t)F * m->D, hipMemcpyHostToDevice, s));
+    return s;
+}
+
+// the full similarity matrix of the F queries in d_q -> outputs [F][N] on the host (queued on s; grows d_full)
+void full_matrix_to_host(frt_matcher *m, int F, float *outputs, hipStream_t s) {
+    const size_t need = (size_t)F * m->N;
+    if (need > m->full_cap) {
+        if (m->d_full) (void)hipFree(m->d_full);
+        m->d_full = nullptr;
+        m->full_cap = 0;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_full), need * sizeof(float)));
+        m->full_cap = need;
+    }
+    for (int f0 = 0; f0 < F; f0 += 128)
+        m->with_rows([&](auto *g) { launch_match_full(g, m->N, m->D, m->d_q + (size_t)f0 * m->D, std::min(128, F - f0), m->d_full + (size_t)f0 * m->N, s); });
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(outputs, m->d_full, need * sizeof(float), hipMemcpyDeviceToHost, s));
+}
+
+// upload the queries, search, download k columns per query: the top-1 search (lists == false, k == 1) or the top-k lists.
+// matrix_out != nullptr: the full matrix as well (the search runs under the tail of its download).
+void search_to_host(frt_matcher *m, const float *embeds, int F, bool lists, int k, int32_t *idx_out, float *sim_out, float *matrix_out = nullptr) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    hipStream_t s = upload_queries(m, embeds, F);
+    if (matrix_out) full_matrix_to_host(m, F, matrix_out, s);
+    if (lists) m->topk_dev(m->d_q, F, k, m->d_idx, m->d_sim, s);
+    else m->top1_dev(m->d_q, F, m->d_idx, m->d_sim, s);
+    HIPCHK(hipMemcpyAsync(idx_out, m->d_idx, sizeof(int32_t) * (size_t)F * k, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sim_out, m->d_sim, sizeof(float) * (size_t)F * k, hipMemcpyDeviceToHost, s));
+    sync_stream_spinning(s);
 }
 
 }  // namespace
@@ -404,28 +444,8 @@ int frt_matcher_calculate(frt_matcher *m, const float *embeds, int embed_count, 
     return guarded([&] {
         if (!m || !embeds || !outputs) raise(FRT_ERR_INVALID, "MatMul::calculate: null argument");
         std::lock_guard<std::mutex> lk(m->mu);
-        if (m->N <= 0 || embed_count <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
-        use_device(m->device);
-        hipStream_t s = m->stream;
-        m->wait_idle(s);
-        m->ensure_queries(embed_count);
-        const size_t need = (size_t)embed_count * m->N;
-        if (need > m->full_cap) {
-            if (m->d_full) (void)hipFree(m->d_full);
-            m->d_full = nullptr;
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_full), need * sizeof(float)));
-            m->full_cap = need;
-        }
-        HIPCHK(hipMemcpyAsync(m->d_q, embeds, sizeof(float) * (size_t)embed_count * m->D, hipMemcpyHostToDevice, s));
-        for (int f0 = 0; f0 < embed_count; f0 += 128) {
-            const int nf = std::min(128, embed_count - f0);
-            if (m->store16)
-                launch_match_full_h(m->d_g16, m->N, m->D, m->d_q + (size_t)f0 * m->D, nf, m->d_full + (size_t)f0 * m->N, s);
-            else
-                launch_match_full(m->d_gallery, m->N, m->D, m->d_q + (size_t)f0 * m->D, nf, m->d_full + (size_t)f0 * m->N, s);
-        }
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(outputs, m->d_full, need * sizeof(float), hipMemcpyDeviceToHost, s));
+        hipStream_t s = upload_queries(m, embeds, embed_count);
+        full_matrix_to_host(m, embed_count, outputs, s);
         sync_stream_spinning(s);
     });
 }
@@ -433,35 +453,7 @@ int frt_matcher_calculate(frt_matcher *m, const float *embeds, int embed_count, 
 int frt_matcher_calculate_top1(frt_matcher *m, const float *embeds, int embed_count, float *outputs, int32_t *idx_out, float *sim_out) {
     return guarded([&] {
         if (!m || !embeds || !idx_out || !sim_out) raise(FRT_ERR_INVALID, "calculate_top1: null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        if (m->N <= 0 || embed_count <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
-        use_device(m->device);
-        hipStream_t s = m->stream;
-        m->wait_idle(s);
-        m->ensure_queries(embed_count);
-        HIPCHK(hipMemcpyAsync(m->d_q, embeds, sizeof(float) * (size_t)embed_count * m->D, hipMemcpyHostToDevice, s));
-        if (outputs) {
-            const size_t need = (size_t)embed_count * m->N;
-            if (need > m->full_cap) {
-                if (m->d_full) (void)hipFree(m->d_full);
-                m->d_full = nullptr;
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_full), need * sizeof(float)));
-                m->full_cap = need;
-            }
-            for (int f0 = 0; f0 < embed_count; f0 += 128) {
-                const int nf = std::min(128, embed_count - f0);
-                if (m->store16)
-                    launch_match_full_h(m->d_g16, m->N, m->D, m->d_q + (size_t)f0 * m->D, nf, m->d_full + (size_t)f0 * m->N, s);
-                else
-                    launch_match_full(m->d_gallery, m->N, m->D, m->d_q + (size_t)f0 * m->D, nf, m->d_full + (size_t)f0 * m->N, s);
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(outputs, m->d_full, need * sizeof(float), hipMemcpyDeviceToHost, s));  // (the top-1 search below runs under this copy's tail)
-        }
-        m->top1_dev(m->d_q, embed_count, m->d_idx, m->d_sim, s);
-        HIPCHK(hipMemcpyAsync(idx_out, m->d_idx, sizeof(int32_t) * embed_count, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(sim_out, m->d_sim, sizeof(float) * embed_count, hipMemcpyDeviceToHost, s));
-        sync_stream_spinning(s);
+        search_to_host(m, embeds, embed_count, false, 1, idx_out, sim_out, outputs);
     });
 }
 
@@ -481,17 +473,7 @@ void frt_pinned_free(void *p) {
 int frt_matcher_top1(frt_matcher *m, const float *embeds, int embed_count, int32_t *idx_out, float *sim_out) {
     return guarded([&] {
         if (!m || !embeds || !idx_out || !sim_out) raise(FRT_ERR_INVALID, "top1: null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        if (m->N <= 0 || embed_count <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
-        use_device(m->device);
-        hipStream_t s = m->stream;
-        m->wait_idle(s);
-        m->ensure_queries(embed_count);
-        HIPCHK(hipMemcpyAsync(m->d_q, embeds, sizeof(float) * (size_t)embed_count * m->D, hipMemcpyHostToDevice, s));
-        m->top1_dev(m->d_q, embed_count, m->d_idx, m->d_sim, s);
-        HIPCHK(hipMemcpyAsync(idx_out, m->d_idx, sizeof(int32_t) * embed_count, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(sim_out, m->d_sim, sizeof(float) * embed_count, hipMemcpyDeviceToHost, s));
-        sync_stream_spinning(s);
+        search_to_host(m, embeds, embed_count, false, 1, idx_out, sim_out);
     });
 }
 
@@ -535,17 +517,7 @@ int frt_matcher_topk(frt_matcher *m, const float *embeds, int embed_count, int k
     return guarded([&] {
         if (!m || !embeds || !idx_out || !sim_out) raise(FRT_ERR_INVALID, "topk: null argument");
         check_k(k);
-        std::lock_guard<std::mutex> lk(m->mu);
-        if (m->N <= 0 || embed_count <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
-        use_device(m->device);
-        hipStream_t s = m->stream;
-        m->wait_idle(s);
-        m->ensure_queries(embed_count);
-        HIPCHK(hipMemcpyAsync(m->d_q, embeds, sizeof(float) * (size_t)embed_count * m->D, hipMemcpyHostToDevice, s));
-        m->topk_dev(m->d_q, embed_count, k, m->d_idx, m->d_sim, s);
-        HIPCHK(hipMemcpyAsync(idx_out, m->d_idx, sizeof(int32_t) * (size_t)embed_count * k, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(sim_out, m->d_sim, sizeof(float) * (size_t)embed_count * k, hipMemcpyDeviceToHost, s));
-        sync_stream_spinning(s);
+        search_to_host(m, embeds, embed_count, true, k, idx_out, sim_out);
     });
 }
 

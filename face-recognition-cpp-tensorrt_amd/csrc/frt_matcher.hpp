@@ -20,8 +20,8 @@ struct frt_matcher {
     int q_cap = 0;
     size_t full_cap = 0;
     int blocks = 0;
-    // screened top-1 (fp16 shadow gallery; see kernels_match.hip).  Off for small galleries, for widths the coarse kernel is not
-    // instantiated for (anything but 64 / 128 / 256 / 512) and with FRT_MATCH_SCREEN=0.
+    // screened search (shadow gallery; see kernels_match.hip).  Off for small galleries and for widths the coarse kernel is not
+    // instantiated for (anything but 64 / 128 / 256 / 512).
     half_t *d_g16 = nullptr;   // fp16 shadow of d_gallery, or the fp16-STORED gallery itself
     uint8_t *d_g8 = nullptr;   // int8 shadow of d_gallery (round 4: fp32-stored galleries with 512 columns take this instead of the fp16 shadow)
     float *d_g8_scale = nullptr;
@@ -48,16 +48,26 @@ struct frt_matcher {
     size_t keys_cap = 0;
     static constexpr size_t BOUNCE_BYTES = (size_t)32 << 20;
     static constexpr int SCREEN_MIN_ROWS = 32768;
-    // scr.count sits behind the flags of the CURRENT tile count (they are cleared together); the buffers hold cap_rows' tiles
-    void bind_scratch() {
-        blocks = match_top1_blocks(N, 0);
-        if (scr.tile_flags) scr.count = scr.tile_flags + ((size_t)N + 127) / 128;
-    }
+    // the coarse scan runs one persistent workgroup per CU and each needs a tile of its own: scr.wgmax is [FRT_MATCH_COARSE_WG][F], read in full
+    static_assert(SCREEN_MIN_ROWS / 128 >= FRT_MATCH_COARSE_WG, "a screened gallery has at least one 128-row tile per coarse workgroup");
+    void bind_scratch() { blocks = match_top1_blocks(N, 0); }
     void free_screen_scratch() {
-        for (void *p : {(void *)scr.q16, (void *)scr.tilemax, (void *)scr.tile_flags, (void *)scr.tile_list, (void *)scr.segmax, (void *)scr.wgmax, scr.pairs,
-                        (void *)scr.ctl, (void *)scr.qkey})  // scr.count lives behind tile_flags
+        for (void *p : {(void *)scr.tilemax, (void *)scr.wgmax, scr.pairs, (void *)scr.ctl, (void *)scr.qkey})
             if (p) (void)hipFree(p);
         scr = ScreenScratch{};
+    }
+    // the rows the exact kernels read, typed: fn(const float *) for an fp32-stored gallery, fn(const half_t *) for an fp16-stored one
+    template <typename Fn>
+    void with_rows(Fn &&fn) const {
+        if (store16) fn(static_cast<const half_t *>(d_g16));
+        else fn(static_cast<const float *>(d_gallery));
+    }
+    ScreenScratch screen_scratch() const {  // scr + the shadow the coarse scan reads
+        ScreenScratch w = scr;
+        w.g8 = d_g8;
+        w.g8_scale = d_g8_scale;
+        w.gerr = gerr;
+        return w;
     }
     // Object-level entry points share the scratch buffers with the pipeline's match stage, which keeps running on the pipeline's
     // stream after frt_pipeline_run_dev / submit returned: order this object's stream behind it (one event wait, no host sync).
@@ -221,7 +231,7 @@ struct frt_matcher {
         if (!d_edit_bits) HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_edit_bits), 2 * sizeof(int)));
         HIPCHK(hipMemsetAsync(d_edit_bits, 0, 2 * sizeof(int), stream));
         if (store16) {
-            launch_gallery_norm16(d_g16, N, D, d_edit_bits + 1, stream);
+            launch_rows_norm(d_g16, 0, N, D, d_edit_bits + 1, stream);
         } else {
             if (shadow_rows < cap_rows) {
                 if (d_g8) (void)hipFree(d_g8);
@@ -268,7 +278,7 @@ struct frt_matcher {
     }
 
     void ensure_queries(int F) {
-        if (F <= q_cap && d_partial && scratch_rows >= cap_rows && (!screen || scr.q16)) return;
+        if (F <= q_cap && d_partial && scratch_rows >= cap_rows && (!screen || scr.tilemax)) return;
         const int cap = std::max(std::max(F, q_cap), 128);
         const int rows = std::max(cap_rows, N);
         ++generation;  // scratch buffers move
@@ -288,14 +298,9 @@ struct frt_matcher {
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_partial), (size_t)match_top1_blocks(rows, 0) * cap * sizeof(MatchPartial)));  // [blocks][cap], blocks <= those of `rows`
         if (screen) {
             const size_t tiles = ((size_t)rows + 127) / 128;
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.q16), (size_t)cap * D * sizeof(half_t)));
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.tilemax), (size_t)cap * tiles * 4 * sizeof(float)));  // 4 coarse entries per tile (one per wave)
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.tile_flags), (tiles + 1) * sizeof(int)));  // [tiles] flags + the candidate count:
-                                                                                                          // one contiguous range to clear per call (bind_scratch)
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.tile_list), tiles * sizeof(int)));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.segmax), (size_t)cap * 16 * sizeof(float)));
-            scr.pair_cap = std::max(cap * 64, 8192);  // (a multiple of the 64 sub-lists)
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.wgmax), (size_t)256 * cap * sizeof(float)));
+            scr.pair_cap = std::max(cap * FRT_MATCH_SEL_SUB, 8192);  // (a multiple of the FRT_MATCH_SEL_SUB sub-lists)
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.wgmax), (size_t)FRT_MATCH_COARSE_WG * cap * sizeof(float)));
             HIPCHK(hipMalloc(&scr.pairs, (size_t)scr.pair_cap * 8));
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&scr.ctl), FRT_MATCH_CTL_WORDS * sizeof(int)));
             HIPCHK(hipMemset(scr.ctl, 0, FRT_MATCH_CTL_WORDS * sizeof(int)));
@@ -309,27 +314,16 @@ struct frt_matcher {
     void top1_dev(const float *queries_dev, int F, int32_t *idx_dev, float *sim_dev, hipStream_t s) {
         ProfScope ps(2, "match_top1", 2.0 * D * (double)N * F, s);
         // the partial scratch is [blocks][F]
-        if (screen && screen_on) {  // (d_gallery == nullptr with fp16 storage: the exact re-rank then reads the stored fp16 rows)
-            ScreenScratch w = scr;
-            w.g8 = d_g8;
-            w.g8_scale = d_g8_scale;
-            w.gerr = gerr;
-            launch_match_top1_screened(d_gallery, d_g16, N, D, queries_dev, F, gmax_norm, w, d_partial, blocks, idx_dev, sim_dev, row_offset, s);
-        }
-        else if (store16)
-            launch_match_top1_h(d_g16, N, D, queries_dev, F, d_partial, blocks, idx_dev, sim_dev, row_offset, s);
+        if (screen && screen_on)  // (d_gallery == nullptr with fp16 storage: the exact re-rank then reads the stored fp16 rows)
+            launch_match_screened(d_gallery, d_g16, N, D, queries_dev, F, 1, gmax_norm, screen_scratch(), d_kth, d_partial, blocks, idx_dev, sim_dev, row_offset, s);
         else
-            launch_match_top1(d_gallery, N, D, queries_dev, F, d_partial, blocks, idx_dev, sim_dev, row_offset, s);
+            with_rows([&](auto *g) { launch_match_top1(g, N, D, queries_dev, F, d_partial, blocks, idx_dev, sim_dev, row_offset, s); });
         HIPCHK(hipGetLastError());
     }
     // exact top-k lists [F][k] (idx_dev / sim_dev device pointers); queries fp32 on the device
     void topk_dev(const float *queries_dev, int F, int k, int32_t *idx_dev, float *sim_dev, hipStream_t s) {
         ProfScope ps(2, "match_topk", 2.0 * D * (double)N * F, s);
-        ScreenScratch w = scr;
-        w.g8 = d_g8;
-        w.g8_scale = d_g8_scale;
-        w.gerr = gerr;
-        launch_match_topk(d_gallery, d_g16, N, D, queries_dev, F, k, screen, gmax_norm, w, d_kth, d_partial, blocks, idx_dev, sim_dev, row_offset, s);
+        launch_match_topk(d_gallery, d_g16, N, D, queries_dev, F, k, screen, gmax_norm, screen_scratch(), d_kth, d_partial, blocks, idx_dev, sim_dev, row_offset, s);
         HIPCHK(hipGetLastError());
     }
 };

@@ -14,6 +14,7 @@
 // bank row (conflict-free, MI355X LDS rules).  The k index inside a chunk is permuted consistently for both operands
 // (lane>>5 picks the chunk, the 4 MFMAs of a chunk walk its 4 floats), which leaves every dot product unchanged.
 #include <cstdlib>
+#include <type_traits>
 
 #include "frt_kernels.h"
 #include "frt_holes.h"
@@ -56,12 +57,9 @@ __device__ __forceinline__ floatx4 load_g4(const half_t *G, long g, int D, int k
 template <int NQ, bool FULL, typename GT = float, bool EXCL = false>
 __global__ __launch_bounds__(256) void match_kernel(const GT *__restrict__ G, int N, int D, const float *__restrict__ E, int F,
                                                     MatchPartial *__restrict__ partial, float *__restrict__ out_full, int num_tiles,
-                                                    int row_offset, const int *__restrict__ tile_list, const int *__restrict__ d_num_tiles,
-                                                    const float *__restrict__ prev_sim = nullptr, const int32_t *__restrict__ prev_idx = nullptr,
+                                                    int row_offset, const float *__restrict__ prev_sim = nullptr, const int32_t *__restrict__ prev_idx = nullptr,
                                                     int prev_stride = 1, const int *__restrict__ gate = nullptr) {
-    if (gate && !*gate) return;  // fast top-1 path: this launch only runs when the pair list overflowed (uniform; before any barrier)
-    // tile_list != nullptr: run only over the listed 128-row gallery tiles (num_tiles = list length): the exact re-rank pass of
-    // the screened top-1 (same code path per tile as the full scan -> bitwise-identical similarities)
+    if (gate && !*gate) return;  // screened search: this launch only runs when the pair list overflowed (uniform; before any barrier)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *As = reinterpret_cast<float *>(smem);                        // [2][BM][BK]
     float *Bs = reinterpret_cast<float *>(smem) + 2 * BM * BK;          // [2][NQ*32][BK]
@@ -72,7 +70,6 @@ __global__ __launch_bounds__(256) void match_kernel(const GT *__restrict__ G, in
     const int q0 = blockIdx.y * QT;
     const int ksteps = D / BK;
 
-    if (tile_list) num_tiles = *d_num_tiles;  // list length produced on the device by the screening pass
     const int my_tiles = num_tiles > (int)blockIdx.x ? (num_tiles - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x : 0;
     const int total = my_tiles * ksteps;
 
@@ -80,8 +77,7 @@ __global__ __launch_bounds__(256) void match_kernel(const GT *__restrict__ G, in
 
     floatx4 ga[4], qa[NQ];
     auto load_global = [&](int it) {
-        int tile = blockIdx.x + (it / ksteps) * gridDim.x;
-        if (tile_list) tile = tile_list[tile];
+        const int tile = blockIdx.x + (it / ksteps) * gridDim.x;
         const int k0 = (it % ksteps) * BK;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -164,8 +160,7 @@ __global__ __launch_bounds__(256) void match_kernel(const GT *__restrict__ G, in
         }
         if (it + 1 < total) store_lds(cur ^ 1);
         if ((it % ksteps) == ksteps - 1) {  // tile finished: epilogue
-            int tile = blockIdx.x + (it / ksteps) * gridDim.x;
-            if (tile_list) tile = tile_list[tile];
+            const int tile = blockIdx.x + (it / ksteps) * gridDim.x;
             const int gbase = tile * BM + wave * 32;
 #pragma unroll
             for (int n = 0; n < NQ; ++n) {
@@ -229,7 +224,7 @@ __global__ __launch_bounds__(256) void match_kernel(const GT *__restrict__ G, in
                 MatchPartial p;
                 p.sim = v;
                 p.idx = i == INT_MAX ? -1 : i + row_offset;
-                partial[(long)blockIdx.x * F + q] = p;  // (blocks beyond a short tile list write the empty record)
+                partial[(long)blockIdx.x * F + q] = p;
             }
         }
     }
@@ -264,7 +259,7 @@ __global__ __launch_bounds__(64) void match_reduce_kernel(const MatchPartial *__
     }
 }
 
-// ---------------------------------------------------------------- screened top-1: fp16 coarse pass + exact re-rank of a few tiles
+// ---------------------------------------------------------------- screened search: coarse pass + exact re-rank of a few 32-row blocks
 // The exact fp32 scan above is bound by the fp32 matrix rate for a 128-face batch (2*512*N*F flop at <= 157 TF/s).  Screening
 // makes the common case HBM-bound instead without changing a single result bit:
 //   1. coarse: S~[q][g] on v_mfma_f32_32x32x16_f16 from an fp16 shadow copy of the gallery (half the bytes, 16x the matrix
@@ -272,14 +267,14 @@ __global__ __launch_bounds__(64) void match_reduce_kernel(const MatchPartial *__
 //      block of a 128-row tile) is kept;
 //   2. select: with fp16-rounded inputs and fp32 accumulation |S~ - S| <= delta_q = 1.2e-3 * ||q|| * max_g ||g|| (2^-10 from the
 //      two roundings via Cauchy-Schwarz, plus accumulation slack), so every row that attains the exact maximum of query q lives
-//      in a tile whose coarse maximum is >= (best coarse maximum of q) - 2*delta_q.  Those tiles go on a list (each once);
-//   3. exact: match_kernel runs over the listed tiles only, for all queries - the same code path per tile as the full scan,
-//      so similarities are bitwise those of the full scan and the first-index tie rule is unchanged.  Extra tiles are harmless.
+//      in a block whose coarse maximum is >= (best coarse maximum of q) - 2*delta_q.  Those become (query, tile) pairs;
+//   3. exact: a scalar kernel recomputes the flagged blocks of every pair in the exact kernel's summation order, so similarities
+//      are bitwise those of the full scan and the first-index tie rule is unchanged.  Extra blocks are harmless.
+// The host side is launch_match_screened at the end of this file; galleries below FRT_MATCH_COARSE_WG tiles never get here
+// (frt_matcher.hpp: SCREEN_MIN_ROWS).
 
-// (also clears `nzero` ints at `zero`: the screened search's tile flags + candidate count, which used to be two memset launches)
-__global__ __launch_bounds__(256) void to_half_kernel(const float *__restrict__ in, half_t *__restrict__ out, long n8, int *__restrict__ zero, long nzero) {
+__global__ __launch_bounds__(256) void to_half_kernel(const float *__restrict__ in, half_t *__restrict__ out, long n8) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < nzero) zero[i] = 0;
     if (i >= n8) return;
     const floatx4 a = *reinterpret_cast<const floatx4 *>(in + i * 8), b = *reinterpret_cast<const floatx4 *>(in + i * 8 + 4);
     half8 o = {(half_t)a[0], (half_t)a[1], (half_t)a[2], (half_t)a[3], (half_t)b[0], (half_t)b[1], (half_t)b[2], (half_t)b[3]};
@@ -329,16 +324,15 @@ __global__ __launch_bounds__(256) void row_norm_max_kernel(const GT *__restrict_
 // refilled with the same k-step of the NEXT tile, i.e. every load has a full tile of MFMAs (4096 clk) to land, with 128 KB per CU in
 // flight.  LDS carries only the query fragments.  No barrier in the loop (a barrier per tile stalls the load stream - loads are only
 // issued from MFMA steps - and cost ~20 % of the bandwidth): every wave writes its own maximum, four coarse entries per tile.
-// Round 3 (fast top-1 path): Q32 != nullptr -> the fp32 queries are rounded to fp16 on their way into LDS (the separate conversion
-// launch disappears); wgmax != nullptr -> every workgroup also leaves the maximum of ALL its coarse entries per query in
-// wgmax[blockIdx.x][query] (plain stores; the selection kernel takes the maximum of those <= 256 values instead of a separate
-// pass over the 31 252 entries per query); ctl / qkey: the pair counter, the overflow flag and the packed per-query results of the
-// scalar re-rank are cleared here, i.e. in front of every kernel of this call that touches them.
+// The fp32 queries Q32 are rounded to fp16 on their way into LDS (no separate conversion launch); every workgroup also leaves the
+// maximum of ALL its coarse entries per query in wgmax[blockIdx.x][query] (plain stores; the selection kernel takes the maximum of
+// those FRT_MATCH_COARSE_WG values instead of a separate pass over the 31 252 entries per query); ctl / qkey: the pair counters, the
+// overflow flag and the packed per-query results of the scalar re-rank are cleared here, i.e. in front of every kernel of this call
+// that touches them.
 template <int D>
-__global__ __launch_bounds__(256) void match_coarse_kernel(const half_t *__restrict__ G, int N, const half_t *__restrict__ Q, int F,
-                                                           float *__restrict__ tilemax, int num_tiles, const float *__restrict__ Q32 = nullptr,
-                                                           float *__restrict__ wgmax = nullptr, int *__restrict__ ctl = nullptr,
-                                                           unsigned long long *__restrict__ qkey = nullptr) {
+__global__ __launch_bounds__(256) void match_coarse_kernel(const half_t *__restrict__ G, int N, int F, float *__restrict__ tilemax, int num_tiles,
+                                                           const float *__restrict__ Q32, float *__restrict__ wgmax, int *__restrict__ ctl,
+                                                           unsigned long long *__restrict__ qkey) {
     constexpr int KS = D / 16;   // k-steps
     constexpr int QP = D + 8;    // halves per query row in LDS
     extern __shared__ __attribute__((aligned(16))) char smem2[];
@@ -346,7 +340,7 @@ __global__ __launch_bounds__(256) void match_coarse_kernel(const half_t *__restr
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int r = lane & 31, hi = lane >> 5;
     const int q0 = blockIdx.y * 128;
-    if (ctl && blockIdx.x == 0 && blockIdx.y == 0) {
+    if (blockIdx.x == 0 && blockIdx.y == 0) {
         for (int i = tid; i < CTL_WORDS; i += 256) ctl[i] = 0;
         for (int i = tid; i < F; i += 256) qkey[i] = 0ull;
     }
@@ -354,12 +348,8 @@ __global__ __launch_bounds__(256) void match_coarse_kernel(const half_t *__restr
         const int q = i / (D / 8), c = i - q * (D / 8);
         half8 v = {0, 0, 0, 0, 0, 0, 0, 0};
         if (q0 + q < F) {
-            if (Q32) {
-                const floatx4 a = *reinterpret_cast<const floatx4 *>(Q32 + (long)(q0 + q) * D + c * 8), b = *reinterpret_cast<const floatx4 *>(Q32 + (long)(q0 + q) * D + c * 8 + 4);
-                v = half8{(half_t)a[0], (half_t)a[1], (half_t)a[2], (half_t)a[3], (half_t)b[0], (half_t)b[1], (half_t)b[2], (half_t)b[3]};
-            } else {
-                v = *reinterpret_cast<const half8 *>(Q + (long)(q0 + q) * D + c * 8);
-            }
+            const floatx4 a = *reinterpret_cast<const floatx4 *>(Q32 + (long)(q0 + q) * D + c * 8), b = *reinterpret_cast<const floatx4 *>(Q32 + (long)(q0 + q) * D + c * 8 + 4);
+            v = half8{(half_t)a[0], (half_t)a[1], (half_t)a[2], (half_t)a[3], (half_t)b[0], (half_t)b[1], (half_t)b[2], (half_t)b[3]};
         }
         *reinterpret_cast<half8 *>(Qs + q * QP + c * 8) = v;
     }
@@ -367,9 +357,8 @@ __global__ __launch_bounds__(256) void match_coarse_kernel(const half_t *__restr
     bool rnan = false;
     int tile = blockIdx.x;
     if (tile >= num_tiles) {  // (uniform per workgroup; no barrier has been executed yet)
-        if (wgmax)
-            for (int i = tid; i < 128; i += 256)
-                if (q0 + i < F) wgmax[(long)blockIdx.x * F + q0 + i] = -INFINITY;
+        for (int i = tid; i < 128; i += 256)
+            if (q0 + i < F) wgmax[(long)blockIdx.x * F + q0 + i] = -INFINITY;
         return;
     }
     auto frag_ptr = [&](int t) { return G + (((long)t * 4 + wave) * KS) * 512 + lane * 8; };  // + ks * 512 halfs (1 KB) per k-step
@@ -422,23 +411,22 @@ __global__ __launch_bounds__(256) void match_coarse_kernel(const half_t *__restr
         }
         __builtin_amdgcn_sched_barrier(0);  // keep the iterations apart (without it the scheduler's version needs 512 registers + spills)
     }
-    if (wgmax) {  // the four waves' maxima -> one value per (workgroup, query); a NaN anywhere makes it NaN (the selection then takes every tile)
-        __syncthreads();
-        float *red = reinterpret_cast<float *>(smem2);  // the query block is dead now
-        if (hi == 0) {
+    // the four waves' maxima -> one value per (workgroup, query); a NaN anywhere makes it NaN (the selection then takes every tile)
+    __syncthreads();
+    float *red = reinterpret_cast<float *>(smem2);  // the query block is dead now
+    if (hi == 0) {
 #pragma unroll
-            for (int n = 0; n < 4; ++n) red[wave * 128 + n * 32 + r] = rnan ? NAN : rmax[n];
-        }
-        __syncthreads();
-        if (tid < 128 && q0 + tid < F) {
-            float m = red[tid];
+        for (int n = 0; n < 4; ++n) red[wave * 128 + n * 32 + r] = rnan ? NAN : rmax[n];
+    }
+    __syncthreads();
+    if (tid < 128 && q0 + tid < F) {
+        float m = red[tid];
 #pragma unroll
-            for (int w = 1; w < 4; ++w) {
-                const float o = red[w * 128 + tid];
-                m = (m != m || o != o) ? NAN : fmaxf(m, o);
-            }
-            wgmax[(long)blockIdx.x * F + q0 + tid] = m;
+        for (int w = 1; w < 4; ++w) {
+            const float o = red[w * 128 + tid];
+            m = (m != m || o != o) ? NAN : fmaxf(m, o);
         }
+        wgmax[(long)blockIdx.x * F + q0 + tid] = m;
     }
 }
 
@@ -668,54 +656,7 @@ __global__ __launch_bounds__(256) void match_coarse_i8_kernel(const uint8_t *__r
 // (Measured and not kept: the same scan for a full 128-query block with a 2 x 2 wave tiling - every query fragment read from LDS and every
 //  widened gallery fragment feeding TWO MFMAs, half the LDS traffic: 179 us against 163 for the 1 x 4 tiling above.)
 
-// Tile selection in two fully parallel steps (it used to be one workgroup per query walking its 31 252 coarse entries twice: 128
-// workgroups, 80 us).  Step 1: grid (segments, queries) - maximum of a segment of the query's coarse entries.  Step 2: same grid -
-// the query's best coarse maximum from the segment maxima, ||q||, then every tile of the segment within 2*delta of the best goes on the
-// list (once, over all queries).
-constexpr int SEL_SEG = 16;  // segments per query
-
-__global__ __launch_bounds__(256) void match_segmax_kernel(const float *__restrict__ tilemax, int n_ent, float *__restrict__ segmax) {
-    __shared__ float sm[4];
-    const int q = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
-    const int e0 = (int)((long)n_ent * seg / SEL_SEG), e1 = (int)((long)n_ent * (seg + 1) / SEL_SEG);
-    const float *row = tilemax + (long)q * n_ent;
-    float m = -INFINITY;
-    for (int t = e0 + tid; t < e1; t += 256) m = fmaxf(m, row[t]);
-    for (int off = 32; off > 0; off >>= 1) m = fmaxf(m, __shfl_xor(m, off));
-    if ((tid & 63) == 0) sm[tid >> 6] = m;
-    __syncthreads();
-    if (tid == 0) segmax[q * SEL_SEG + seg] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-}
-
-// kth != nullptr (top-k): the threshold hangs on the query's k-th largest coarse entry instead of its largest.  With |S~ - S| <= delta:
-// the k-th largest coarse entry m_k is the maximum of a 32-row block, k blocks have one >= m_k, hence k distinct rows have S >= m_k -
-// delta, hence the exact k-th best similarity s_k >= m_k - delta, and every row with S >= s_k has S~ >= m_k - 2*delta: it lives in a
-// listed tile.  (k = 1 is the rule above.)
-__global__ __launch_bounds__(256) void match_select_kernel(const float *__restrict__ tilemax, int num_tiles, int sub, const float *__restrict__ segmax,
-                                                           const float *__restrict__ Q, int D, float gmax_norm, int *__restrict__ tile_flags,
-                                                           int *__restrict__ tile_list, int *__restrict__ count, const float *__restrict__ kth = nullptr) {
-    // `sub` coarse entries per 128-row tile (match_coarse_kernel writes one per wave: 4)
-    __shared__ float sm[4];
-    const int q = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
-    const int n_ent = num_tiles * sub;
-    const float *row = tilemax + (long)q * n_ent;
-    float m = -INFINITY, n2 = 0.f;
-    if (kth) m = kth[q];
-    else
-        for (int s = 0; s < SEL_SEG; ++s) m = fmaxf(m, segmax[q * SEL_SEG + s]);
-    for (int k = tid; k < D; k += 256) n2 += Q[(long)q * D + k] * Q[(long)q * D + k];
-    for (int off = 32; off > 0; off >>= 1) n2 += __shfl_xor(n2, off);
-    if ((tid & 63) == 0) sm[tid >> 6] = n2;
-    __syncthreads();
-    const float qn = sqrtf(sm[0] + sm[1] + sm[2] + sm[3]);
-    const float delta = 1.2e-3f * qn * gmax_norm;
-    // fp16 overflow / non-finite inputs: no valid bound -> take every tile (degenerates to the exact full scan)
-    // (top-k with fewer than k coarse entries: kth = -inf -> every tile)
-    const float thr = (qn < 6.0e4f && gmax_norm < 6.0e4f && m == m && m > -INFINITY && m < INFINITY) ? m - 2.f * delta : -INFINITY;
-    const int e0 = (int)((long)n_ent * seg / SEL_SEG), e1 = (int)((long)n_ent * (seg + 1) / SEL_SEG);
-    for (int t = e0 + tid; t < e1; t += 256)
-        if (!(row[t] < thr) && atomicExch(&tile_flags[t / sub], 1) == 0) tile_list[atomicAdd(count, 1)] = t / sub;
-}
+constexpr int SEL_SEG = 16;  // tile segments per query: the selection runs on a grid of (SEL_SEG, queries)
 
 // ---------------------------------------------------------------- top-k support (BASELINE configs[4]: "RCCL top-k all-gather")
 constexpr int TOPK_MAX = 16;
@@ -824,10 +765,10 @@ __global__ __launch_bounds__(64) void merge_topk_kernel(const int32_t *__restric
     }
 }
 
-// ---------------------------------------------------------------- fast screened top-1 (round 3)
-// The tile list + MFMA re-rank above recomputes ALL queries against every listed tile (128 x 128 dot products per tile where typically
-// one query asked for it) behind a per-tile barrier chain: 59 us for a few hundred tiles.  Here the selection emits (query, tile)
-// PAIRS and a scalar kernel recomputes exactly those 128 dot products per pair - one thread per gallery row walking k in the order the
+// ---------------------------------------------------------------- pair selection + exact re-rank
+// (An earlier version listed whole tiles and ran match_kernel over the list: ALL queries against every listed tile - 128 x 128 dot
+// products where typically one query asked for it - behind a per-tile barrier chain, 59 us for a few hundred tiles.)  The selection emits
+// (query, tile) PAIRS and a scalar kernel recomputes exactly those 128 dot products per pair - one thread per gallery row walking k in the order the
 // exact kernel's v_mfma_f32_32x32x2_f32 chain consumes it, so the similarities are the same bits as the full scan's (checked by
 // tools/ubench/mfma_f32_order.hip and by the bit-identity tests).  Per pair the best row (first-maximum rule) goes into the query's
 // 64-bit slot with one atomicMax: high word = the similarity mapped monotonically to an unsigned integer, low word = ~row, so a higher
@@ -841,8 +782,8 @@ constexpr int PAIR_TILE_MASK = (1 << 28) - 1;
 // entries, one per (tile segment = blockIdx.x of the selection, query & 3): 1 400 increments of ONE counter cost 35 us of atomics (queries that match
 // nothing, int8 band).  Round 4 shared them out over sixteen counters in ONE cache line - the selection still took 27 us with ~ 2 000 pairs against
 // 7 us with 128 (returning atomics on one line queue in one L2 channel whatever the address); round 6: 64 counters, each in its own 128-byte line.
-constexpr int CTL_OVERFLOW = 1, CTL_SEG0 = 32, CTL_STRIDE = 32, SEL_QSUB = 4, SEL_SUB = SEL_SEG * SEL_QSUB;
-static_assert(CTL_SEG0 + SEL_SUB * CTL_STRIDE <= CTL_WORDS, "control words");
+constexpr int CTL_OVERFLOW = 1, CTL_SEG0 = 32, CTL_STRIDE = 32, SEL_QSUB = 4, SEL_SUB = FRT_MATCH_SEL_SUB;
+static_assert(SEL_SUB == SEL_SEG * SEL_QSUB && CTL_SEG0 + SEL_SUB * CTL_STRIDE <= CTL_WORDS, "control words");
 constexpr int FB_BLOCKS = 128;  // workgroups of the gated fallback scan (it returns at once in the normal case: keep the empty launch small)
 
 __device__ __forceinline__ unsigned mono_bits(float f) {
@@ -859,7 +800,10 @@ __global__ __launch_bounds__(256) void match_select_pairs_kernel(const float *__
                                                                  float c_round = 1.2e-3f, float gerr = 0.f) {
     // c_round / gerr: |S~ - S| <= ||q|| * (c_round * max||g|| + 1.02 * gerr).  fp16 shadow: two fp16 roundings (1.2e-3), no storage error;
     // int8 shadow: one rounding (the query's: 0.7e-3) + the measured quantisation error norm of the rows
-    // kth != nullptr (top-k): the threshold hangs on the query's k-th largest coarse entry (match_kth_kernel; see match_select_kernel)
+    // kth != nullptr (top-k): the threshold hangs on the query's k-th largest coarse entry (match_kth_kernel) instead of its largest.  With
+    // |S~ - S| <= delta: the k-th largest coarse entry m_k is the maximum of a 32-row block, k blocks have one >= m_k, hence k distinct rows
+    // have S >= m_k - delta, hence the exact k-th best similarity s_k >= m_k - delta, and every row with S >= s_k has S~ >= m_k - 2*delta: it
+    // lives in a listed block.  (Fewer than k coarse entries: kth = -inf -> every tile.)
     __shared__ float sm[4], sn[4];
     __shared__ int snan[4];
     const int q = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
@@ -887,8 +831,8 @@ __global__ __launch_bounds__(256) void match_select_pairs_kernel(const float *__
     const bool anynan = snan[0] | snan[1] | snan[2] | snan[3];
     const float qn = sqrtf(sn[0] + sn[1] + sn[2] + sn[3]);
     const float delta = qn * (c_round * gmax_norm + 1.02f * gerr);
-    // same rule as match_select_kernel: fp16 overflow / non-finite inputs -> no valid bound -> every tile (which overflows the pair list
-    // and sends the call through the exact full scan)
+    // fp16 overflow / non-finite inputs: no valid bound -> every tile (which overflows the pair list and sends the call through the exact
+    // full scan)
     const float thr = (!anynan && qn < 6.0e4f && gmax_norm < 6.0e4f && gerr < 6.0e4f && m == m && m > -INFINITY && m < INFINITY) ? m - 2.f * delta : -INFINITY;
     const int t0 = (int)((long)num_tiles * seg / SEL_SEG), t1 = (int)((long)num_tiles * (seg + 1) / SEL_SEG);
     const floatx4 *row = reinterpret_cast<const floatx4 *>(tilemax + (long)q * num_tiles * 4);
@@ -1062,8 +1006,7 @@ __global__ __launch_bounds__(256) void gather_rows_h16_kernel(const half_t *__re
 
 template <int NQ, bool FULL, typename GT = float, bool EXCL = false>
 void launch_t(const GT *G, int N, int D, const float *E, int F, MatchPartial *partial, float *out_full, int blocks, int row_offset,
-              hipStream_t s, const int *tile_list = nullptr, const int *d_num_tiles = nullptr, const float *prev_sim = nullptr,
-              const int32_t *prev_idx = nullptr, int prev_stride = 1, const int *gate = nullptr) {
+              hipStream_t s, const float *prev_sim = nullptr, const int32_t *prev_idx = nullptr, int prev_stride = 1, const int *gate = nullptr) {
     const int tiles = (N + BM - 1) / BM;
     const size_t lds = (size_t)2 * (BM + NQ * 32) * BK * sizeof(float);
     static bool attr_done[FRT_MAX_DEVICES] = {};
@@ -1071,9 +1014,19 @@ void launch_t(const GT *G, int N, int D, const float *E, int F, MatchPartial *pa
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&match_kernel<NQ, FULL, GT, EXCL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     dim3 grid(blocks, (F + NQ * 32 - 1) / (NQ * 32));
-    hipLaunchKernelGGL((match_kernel<NQ, FULL, GT, EXCL>), grid, dim3(256), lds, s, G, N, D, E, F, partial, out_full, tiles, row_offset, tile_list, d_num_tiles,
-                       prev_sim, prev_idx, prev_stride, gate);
+    hipLaunchKernelGGL((match_kernel<NQ, FULL, GT, EXCL>), grid, dim3(256), lds, s, G, N, D, E, F, partial, out_full, tiles, row_offset, prev_sim, prev_idx,
+                       prev_stride, gate);
 }
+
+// The exact passes read the STORED rows: fp32 row-major (gallery), or the fragment-ordered fp16 rows when there is no fp32 copy on the
+// device (gallery == nullptr: fp16-stored gallery).  fn gets the typed pointer; rows_t names its element type.
+template <typename Fn>
+void with_stored_rows(const float *gallery, const half_t *g16, Fn &&fn) {
+    if (gallery) fn(gallery);
+    else fn(g16);
+}
+template <typename P>
+using rows_t = std::remove_const_t<std::remove_pointer_t<P>>;
 
 }  // namespace
 
@@ -1083,46 +1036,33 @@ int match_top1_blocks(int N, int F) {
     return tiles < 512 ? (tiles > 0 ? tiles : 1) : 512;
 }
 
-void launch_match_top1(const float *gallery, int N, int D, const float *queries, int F, MatchPartial *partial, int partial_blocks,
-                       int32_t *idx_out, float *sim_out, int row_offset, hipStream_t s) {
+template <typename GT>
+void launch_match_top1(const GT *rows, int N, int D, const float *queries, int F, MatchPartial *partial, int partial_blocks, int32_t *idx_out,
+                       float *sim_out, int row_offset, hipStream_t s) {
     // NOTE: with grid.y > 1 every query tile writes its own columns of `partial` ([blocks][F]).
     if (F <= 32)
-        launch_t<1, false>(gallery, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
+        launch_t<1, false>(rows, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
     else if (F <= 64)
-        launch_t<2, false>(gallery, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
+        launch_t<2, false>(rows, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
     else
-        launch_t<4, false>(gallery, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
+        launch_t<4, false>(rows, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
     hipLaunchKernelGGL(match_reduce_kernel, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out, sim_out, 1, (const int *)nullptr);
 }
+template void launch_match_top1(const float *, int, int, const float *, int, MatchPartial *, int, int32_t *, float *, int, hipStream_t);
+template void launch_match_top1(const half_t *, int, int, const float *, int, MatchPartial *, int, int32_t *, float *, int, hipStream_t);
 
-void launch_match_top1_h(const half_t *g16, int N, int D, const float *queries, int F, MatchPartial *partial, int partial_blocks,
-                         int32_t *idx_out, float *sim_out, int row_offset, hipStream_t s) {
-    if (F <= 32)
-        launch_t<1, false, half_t>(g16, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
-    else if (F <= 64)
-        launch_t<2, false, half_t>(g16, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
-    else
-        launch_t<4, false, half_t>(g16, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
-    hipLaunchKernelGGL(match_reduce_kernel, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out, sim_out, 1, (const int *)nullptr);
-}
-
-void launch_match_full_h(const half_t *g16, int N, int D, const float *queries, int F, float *out, hipStream_t s) {
+template <typename GT>
+void launch_match_full(const GT *rows, int N, int D, const float *queries, int F, float *out, hipStream_t s) {
     const int blocks = match_top1_blocks(N, F);
     if (F <= 32)
-        launch_t<1, true, half_t>(g16, N, D, queries, F, nullptr, out, blocks, 0, s);
+        launch_t<1, true>(rows, N, D, queries, F, nullptr, out, blocks, 0, s);
     else
-        launch_t<4, true, half_t>(g16, N, D, queries, F, nullptr, out, blocks, 0, s);
+        launch_t<4, true>(rows, N, D, queries, F, nullptr, out, blocks, 0, s);
 }
+template void launch_match_full(const float *, int, int, const float *, int, float *, hipStream_t);
+template void launch_match_full(const half_t *, int, int, const float *, int, float *, hipStream_t);
 
-void launch_match_full(const float *gallery, int N, int D, const float *queries, int F, float *out, hipStream_t s) {
-    const int blocks = match_top1_blocks(N, F);
-    if (F <= 32)
-        launch_t<1, true>(gallery, N, D, queries, F, nullptr, out, blocks, 0, s);
-    else
-        launch_t<4, true>(gallery, N, D, queries, F, nullptr, out, blocks, 0, s);
-}
-
-// ---------------------------------------------------------------- screened top-1 (host side)
+// ---------------------------------------------------------------- shadow galleries (host side)
 bool match_screen_supported(int D) { return D == 64 || D == 128 || D == 256 || D == 512; }  // coarse kernel instantiations (queries must fit LDS)
 
 size_t gallery16_elems(int N, int D) { return (size_t)((N + 127) / 128) * 128 * D; }  // whole 128-row tiles
@@ -1136,17 +1076,20 @@ void launch_rows_to_half(const float *in, long row0, long n_rows, int D, half_t 
     hipLaunchKernelGGL(gallery_to_half_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, in, row0, n_rows, D, g16);
 }
 
-void launch_gallery_shadow(const float *gallery, int N, int D, half_t *g16, int *max_norm2_bits, hipStream_t s) {
+// largest squared norm of the rows [row0, row0 + n_rows) of a gallery (fp32 row-major or fragment-ordered fp16; G = the whole gallery).
+// An fp16-STORED gallery needs nothing else: the stored rows are their own shadow.
+template <typename GT>
+void launch_rows_norm(const GT *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s) {
     (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
+    if (n_rows > 0) hipLaunchKernelGGL(row_norm_max_kernel<GT>, dim3((n_rows + 3) / 4), dim3(256), 0, s, G, row0, row0 + n_rows, D, max_norm2_bits);
+}
+template void launch_rows_norm(const float *, int, int, int, int *, hipStream_t);
+template void launch_rows_norm(const half_t *, int, int, int, int *, hipStream_t);
+
+void launch_gallery_shadow(const float *gallery, int N, int D, half_t *g16, int *max_norm2_bits, hipStream_t s) {
     (void)hipMemsetAsync(g16, 0, gallery16_elems(N, D) * sizeof(half_t), s);  // (pad rows of the last tile stay zero)
     launch_rows_to_half(gallery, 0, N, D, g16, s);
-    hipLaunchKernelGGL(row_norm_max_kernel<float>, dim3((N + 3) / 4), dim3(256), 0, s, gallery, 0, N, D, max_norm2_bits);
-}
-
-// fp16-STORED gallery (no fp32 copy on the device): only the largest row norm is needed, the stored rows are their own shadow
-void launch_gallery_norm16(const half_t *g16, int N, int D, int *max_norm2_bits, hipStream_t s) {
-    (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
-    hipLaunchKernelGGL(row_norm_max_kernel<half_t>, dim3((N + 3) / 4), dim3(256), 0, s, g16, 0, N, D, max_norm2_bits);
+    launch_rows_norm(gallery, 0, N, D, max_norm2_bits, s);
 }
 
 size_t gallery8_bytes(int N, int D) { return (size_t)((N + 127) / 128) * 128 * D; }
@@ -1167,15 +1110,6 @@ void launch_gallery_shadow8_rows(const float *rows, int row0, int n_rows, uint8_
     if (n_rows <= 0) return;
     hipLaunchKernelGGL(gallery_to_i8_kernel, dim3((n_rows + 3) / 4), dim3(256), 0, s, rows, row0, row0 + n_rows, g8, scale, max_err2_bits, max_norm2_bits);
 }
-// largest squared norm of the rows [row0, row0 + n_rows) of a gallery (fp32 row-major or fragment-ordered fp16; G = the whole gallery)
-void launch_rows_norm(const float *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s) {
-    (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
-    if (n_rows > 0) hipLaunchKernelGGL(row_norm_max_kernel<float>, dim3((n_rows + 3) / 4), dim3(256), 0, s, G, row0, row0 + n_rows, D, max_norm2_bits);
-}
-void launch_rows_norm16(const half_t *G, int row0, int n_rows, int D, int *max_norm2_bits, hipStream_t s) {
-    (void)hipMemsetAsync(max_norm2_bits, 0, sizeof(int), s);
-    if (n_rows > 0) hipLaunchKernelGGL(row_norm_max_kernel<half_t>, dim3((n_rows + 3) / 4), dim3(256), 0, s, G, row0, row0 + n_rows, D, max_norm2_bits);
-}
 void launch_gather_rows(const float *G, int D, int a, int n_rows, const int *keys, int klo, int khi, float *bounce, hipStream_t s) {
     const long pieces = (long)n_rows * (D / 4);
     if (pieces > 0) hipLaunchKernelGGL(gather_rows_f32_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, G, D, a, n_rows, keys, klo, khi, bounce);
@@ -1185,121 +1119,95 @@ void launch_gather_rows16(const half_t *G, int D, long tile0, long n_tiles, int 
     if (pieces > 0) hipLaunchKernelGGL(gather_rows_h16_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, G, D, tile0, n_tiles, n_new, keys, klo, khi, bounce);
 }
 
+// ---------------------------------------------------------------- screened search (host side)
+constexpr int COARSE_WG = FRT_MATCH_COARSE_WG;  // persistent workgroups of the coarse scan (one per CU); wgmax is [COARSE_WG][F]
 
-constexpr int COARSE_WG = 256;  // persistent workgroups of the coarse scan (one per CU)
+// Both coarse scans launch min(tiles, COARSE_WG) workgroups per query block (smaller query blocks leave room for several per CU); the
+// matcher only screens galleries of at least COARSE_WG tiles, so every row of wgmax is written on every call.
 template <int NQB>
 static void launch_coarse_i8_t(const ScreenScratch &w, int N, const float *q32, int F, int tiles, hipStream_t s) {
     const size_t lds = (size_t)32 * NQB * (512 + 8) * sizeof(half_t);
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done))
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&match_coarse_i8_kernel<NQB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    // wgmax is [COARSE_WG][F]: the grid never exceeds COARSE_WG workgroups per query block (smaller query blocks leave room for several per CU)
     dim3 g(tiles < COARSE_WG ? tiles : COARSE_WG, (F + 32 * NQB - 1) / (32 * NQB));
     hipLaunchKernelGGL(match_coarse_i8_kernel<NQB>, g, dim3(256), lds, s, w.g8, w.g8_scale, N, F, w.tilemax, tiles, q32, w.wgmax, w.ctl, w.qkey);
 }
-static void launch_coarse_i8(const ScreenScratch &w, int N, const float *q32, int F, int tiles, hipStream_t s) {
-    if (F <= 32) return launch_coarse_i8_t<1>(w, N, q32, F, tiles, s);
-    if (F <= 64) return launch_coarse_i8_t<2>(w, N, q32, F, tiles, s);
-    launch_coarse_i8_t<4>(w, N, q32, F, tiles, s);
-}
 
 template <int D>
-static void launch_coarse_t(const half_t *g16, int N, const half_t *q16, int F, float *tilemax, int tiles, hipStream_t s, const float *q32 = nullptr,
-                            float *wgmax = nullptr, int *ctl = nullptr, unsigned long long *qkey = nullptr) {
+static void launch_coarse_t(const half_t *g16, const ScreenScratch &w, int N, const float *q32, int F, int tiles, hipStream_t s) {
     const size_t lds = (size_t)128 * (D + 8) * sizeof(half_t);
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done))
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&match_coarse_kernel<D>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 g(tiles < COARSE_WG ? tiles : COARSE_WG, (F + 127) / 128);
-    hipLaunchKernelGGL((match_coarse_kernel<D>), g, dim3(256), lds, s, g16, N, q16, F, tilemax, tiles, q32, wgmax, ctl, qkey);
+    hipLaunchKernelGGL((match_coarse_kernel<D>), g, dim3(256), lds, s, g16, N, F, w.tilemax, tiles, q32, w.wgmax, w.ctl, w.qkey);
 }
 
-// coarse pass + tile selection: leaves the candidate tile list (w.tile_list, length *w.count on the device).  k > 1: the threshold hangs
-// on every query's k-th largest coarse entry (kth_scratch [F] floats).
-static void screen_tiles(const half_t *g16, int N, int D, const float *queries, int F, float gmax_norm, const ScreenScratch &w, int k,
-                         float *kth_scratch, hipStream_t s) {
+// The screened search: exact top-k lists idx_out / sim_out [F][k] (k = 1: the top-1 search), bit for bit what the exact scan returns.
+//   coarse scan (queries rounded on load; per-workgroup maxima; clears ctl / qkey)
+//   k > 1: every query's k-th largest coarse entry (kth_scratch [F] floats) - the selection threshold hangs on it instead of the largest
+//   (query, tile) pairs inside the rounding band
+//   k passes, pass j restricted to the rows behind winner j - 1: scalar pair re-rank (a few microseconds), the unscreened exact scan
+//   gated on the pair list's overflow flag (FB_BLOCKS workgroups that return at once in the normal case), unpack of either result
+void launch_match_screened(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, float gmax_norm,
+                           const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
+                           int row_offset, hipStream_t s) {
     const int tiles = (N + BM - 1) / BM;
-    const long q8 = (long)F * D / 8;
-    const long nzero = (long)tiles + 1;  // tile flags + the candidate count behind them (ScreenScratch: count == tile_flags + tiles)
-    const long n_thr = q8 > nzero ? q8 : nzero;
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, s, queries, w.q16, q8, w.tile_flags, nzero);
-    switch (D) {
-        case 64: launch_coarse_t<64>(g16, N, w.q16, F, w.tilemax, tiles, s); break;
-        case 128: launch_coarse_t<128>(g16, N, w.q16, F, w.tilemax, tiles, s); break;
-        case 256: launch_coarse_t<256>(g16, N, w.q16, F, w.tilemax, tiles, s); break;
-        default: launch_coarse_t<512>(g16, N, w.q16, F, w.tilemax, tiles, s); break;  // match_screen_supported() gates the callers
+    const bool i8 = w.g8 && D == 512;  // int8 shadow (fp32-stored galleries): half the bytes of the scan, same answers
+    if (i8) {
+        if (F <= 32) launch_coarse_i8_t<1>(w, N, queries, F, tiles, s);
+        else if (F <= 64) launch_coarse_i8_t<2>(w, N, queries, F, tiles, s);
+        else launch_coarse_i8_t<4>(w, N, queries, F, tiles, s);
+    } else switch (D) {
+        case 64: launch_coarse_t<64>(g16, w, N, queries, F, tiles, s); break;
+        case 128: launch_coarse_t<128>(g16, w, N, queries, F, tiles, s); break;
+        case 256: launch_coarse_t<256>(g16, w, N, queries, F, tiles, s); break;
+        default: launch_coarse_t<512>(g16, w, N, queries, F, tiles, s); break;  // match_screen_supported() gates the callers
     }
+    const float *kth = nullptr;
     if (k > 1) {
         hipLaunchKernelGGL(match_kth_kernel, dim3(F), dim3(256), 0, s, w.tilemax, tiles * 4, k, kth_scratch);
-        hipLaunchKernelGGL(match_select_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles, 4, w.segmax, queries, D, gmax_norm, w.tile_flags,
-                           w.tile_list, w.count, kth_scratch);
-    } else {
-        hipLaunchKernelGGL(match_segmax_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles * 4, w.segmax);
-        hipLaunchKernelGGL(match_select_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles, 4, w.segmax, queries, D, gmax_norm, w.tile_flags,
-                           w.tile_list, w.count, (const float *)nullptr);
+        kth = kth_scratch;
     }
+    // (with F > 128 every query block y wrote its own columns of wgmax: [COARSE_WG][F])
+    hipLaunchKernelGGL(match_select_pairs_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles, w.wgmax, COARSE_WG, F, queries, D, gmax_norm,
+                       reinterpret_cast<MatchPair *>(w.pairs), w.pair_cap, w.ctl, kth, i8 ? 0.7e-3f : 1.2e-3f, i8 ? w.gerr : 0.f);
+    const int rr_grid = 2048;  // (one pair per workgroup up to 2 048 pairs: the re-rank is one 512-long dependent fma chain per row, i.e. per-pair latency)
+    const int *gate = w.ctl + CTL_OVERFLOW;
+    const int fb = partial_blocks < FB_BLOCKS ? partial_blocks : FB_BLOCKS;
+    with_stored_rows(gallery, g16, [&](auto *G) {
+        using GT = rows_t<decltype(G)>;
+        for (int j = 0; j < k; ++j) {
+            const float *ps = j ? sim_out + (j - 1) : nullptr;
+            const int32_t *pi = j ? idx_out + (j - 1) : nullptr;
+            hipLaunchKernelGGL((match_rerank_pairs_kernel<GT>), dim3(rr_grid), dim3(128), (size_t)D * sizeof(float), s, G, N, D, queries,
+                               reinterpret_cast<const MatchPair *>(w.pairs), w.pair_cap, w.ctl, w.qkey, ps, pi, k, row_offset);
+            if (k == 1) launch_t<4, false, GT>(G, N, D, queries, F, partial, nullptr, fb, row_offset, s, nullptr, nullptr, 1, gate);
+            else launch_t<4, false, GT, true>(G, N, D, queries, F, partial, nullptr, fb, row_offset, s, ps, pi, k, gate);
+            hipLaunchKernelGGL(match_unpack_kernel, dim3((F + 255) / 256), dim3(256), 0, s, w.qkey, F, row_offset, w.ctl, idx_out + j, sim_out + j, k, partial, fb);
+        }
+    });
 }
 
 // Exact top-k: idx_out / sim_out [F][k], row j of a query = the j-th entry of its exact ranking (higher similarity first, lower global
 // index first among equal similarities; -1 / -inf when the gallery has fewer than k rows).  Pass j is the top-1 search restricted to
 // the rows that come after winner j-1 - the same accumulators, the same first-maximum rule; with a screened gallery the coarse scan
-// runs ONCE (threshold on the k-th largest coarse entry) and only the short exact re-rank is repeated.
+// runs ONCE and only the short exact re-rank is repeated (launch_match_screened).
 void launch_match_topk(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, bool screen, float gmax_norm,
                        const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
                        int row_offset, hipStream_t s) {
-    const int tiles_ = (N + BM - 1) / BM;
-    if (screen && w.pairs && w.wgmax && tiles_ >= COARSE_WG) {
-        // fast path (round 3): ONE coarse scan, (query, tile) pairs within the rounding band of the k-th largest coarse entry, then k
-        // passes of the scalar pair re-rank (a few microseconds each), pass j restricted to the rows behind winner j - 1.  With the
-        // all-gathered queries of a node (configs[4]: 2 048 of them per rank) the tile-list path would re-rank every query against every
-        // listed tile, k times.
-        const bool i8 = w.g8 && D == 512;
-        if (i8) launch_coarse_i8(w, N, queries, F, tiles_, s);
-        else switch (D) {
-            case 64: launch_coarse_t<64>(g16, N, nullptr, F, w.tilemax, tiles_, s, queries, w.wgmax, w.ctl, w.qkey); break;
-            case 128: launch_coarse_t<128>(g16, N, nullptr, F, w.tilemax, tiles_, s, queries, w.wgmax, w.ctl, w.qkey); break;
-            case 256: launch_coarse_t<256>(g16, N, nullptr, F, w.tilemax, tiles_, s, queries, w.wgmax, w.ctl, w.qkey); break;
-            default: launch_coarse_t<512>(g16, N, nullptr, F, w.tilemax, tiles_, s, queries, w.wgmax, w.ctl, w.qkey); break;
-        }
-        hipLaunchKernelGGL(match_kth_kernel, dim3(F), dim3(256), 0, s, w.tilemax, tiles_ * 4, k, kth_scratch);
-        hipLaunchKernelGGL(match_select_pairs_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles_, w.wgmax, COARSE_WG, F, queries, D, gmax_norm,
-                           reinterpret_cast<MatchPair *>(w.pairs), w.pair_cap, w.ctl, (const float *)kth_scratch, i8 ? 0.7e-3f : 1.2e-3f, i8 ? w.gerr : 0.f);
-        const int *gate = w.ctl + CTL_OVERFLOW;
+    if (screen) return launch_match_screened(gallery, g16, N, D, queries, F, k, gmax_norm, w, kth_scratch, partial, partial_blocks, idx_out, sim_out, row_offset, s);
+    with_stored_rows(gallery, g16, [&](auto *G) {
+        using GT = rows_t<decltype(G)>;
         for (int j = 0; j < k; ++j) {
             const float *ps = j ? sim_out + (j - 1) : nullptr;
             const int32_t *pi = j ? idx_out + (j - 1) : nullptr;
-            if (gallery)
-                hipLaunchKernelGGL((match_rerank_pairs_kernel<float>), dim3(2048), dim3(128), (size_t)D * sizeof(float), s, gallery, N, D, queries,
-                                   reinterpret_cast<const MatchPair *>(w.pairs), w.pair_cap, w.ctl, w.qkey, ps, pi, k, row_offset);
-            else
-                hipLaunchKernelGGL((match_rerank_pairs_kernel<half_t>), dim3(2048), dim3(128), (size_t)D * sizeof(float), s, g16, N, D, queries,
-                                   reinterpret_cast<const MatchPair *>(w.pairs), w.pair_cap, w.ctl, w.qkey, ps, pi, k, row_offset);
-            // pair-list overflow: the unscreened exact scan answers this pass instead (gated on the flag; see the top-1 path)
-            const int fb = partial_blocks < FB_BLOCKS ? partial_blocks : FB_BLOCKS;
-            if (gallery) launch_t<4, false, float, true>(gallery, N, D, queries, F, partial, nullptr, fb, row_offset, s, nullptr, nullptr, ps, pi, k, gate);
-            else launch_t<4, false, half_t, true>(g16, N, D, queries, F, partial, nullptr, fb, row_offset, s, nullptr, nullptr, ps, pi, k, gate);
-            hipLaunchKernelGGL(match_unpack_kernel, dim3((F + 255) / 256), dim3(256), 0, s, w.qkey, F, row_offset, w.ctl, idx_out + j, sim_out + j, k, partial, fb);
+            if (F <= 32) launch_t<1, false, GT, true>(G, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, ps, pi, k);
+            else launch_t<4, false, GT, true>(G, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, ps, pi, k);
+            hipLaunchKernelGGL(match_reduce_kernel, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out + j, sim_out + j, k, (const int *)nullptr);
         }
-        return;
-    }
-    if (screen) screen_tiles(g16, N, D, queries, F, gmax_norm, w, k, kth_scratch, s);
-    for (int j = 0; j < k; ++j) {
-        const float *ps = j ? sim_out + (j - 1) : nullptr;
-        const int32_t *pi = j ? idx_out + (j - 1) : nullptr;
-        if (screen) {
-            if (gallery)
-                launch_t<1, false, float, true>(gallery, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, w.tile_list, w.count, ps, pi, k);
-            else
-                launch_t<1, false, half_t, true>(g16, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, w.tile_list, w.count, ps, pi, k);
-        } else if (gallery) {
-            if (F <= 32) launch_t<1, false, float, true>(gallery, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, nullptr, nullptr, ps, pi, k);
-            else launch_t<4, false, float, true>(gallery, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, nullptr, nullptr, ps, pi, k);
-        } else {
-            if (F <= 32) launch_t<1, false, half_t, true>(g16, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, nullptr, nullptr, ps, pi, k);
-            else launch_t<4, false, half_t, true>(g16, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, nullptr, nullptr, ps, pi, k);
-        }
-        hipLaunchKernelGGL(match_reduce_kernel, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out + j, sim_out + j, k, (const int *)nullptr);
-    }
+    });
 }
 int match_topk_max() { return TOPK_MAX; }
 
@@ -1307,65 +1215,8 @@ void launch_half_to_float(const half_t *in, long n, float *out, hipStream_t s) {
     hipLaunchKernelGGL(half_to_float_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, in, out, n / 8);
 }
 void launch_float_to_half(const float *in, long n, half_t *out, hipStream_t s) {  // n % 8 == 0
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, in, out, n / 8, (int *)nullptr, 0L);
+    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, in, out, n / 8);
 }
 void launch_merge_topk(const int32_t *idx_all, const float *sim_all, int shards, int n, int k, int32_t *idx_out, float *sim_out, hipStream_t s) {
     hipLaunchKernelGGL(merge_topk_kernel, dim3((n + 63) / 64), dim3(64), 0, s, idx_all, sim_all, shards, n, k, idx_out, sim_out);
-}
-
-void launch_match_top1_screened(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, float gmax_norm,
-                                const ScreenScratch &w, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
-                                int row_offset, hipStream_t s) {
-    const int tiles = (N + BM - 1) / BM;
-    if (w.pairs && w.wgmax && tiles >= COARSE_WG) {  // fast path (round 3): coarse (queries converted on load, per-workgroup maxima) -> pairs -> scalar re-rank -> unpack
-        const int n_wg = COARSE_WG;
-        const bool i8 = w.g8 && D == 512;  // int8 shadow (fp32-stored galleries): half the bytes of the scan, same answers
-        if (i8) launch_coarse_i8(w, N, queries, F, tiles, s);
-        else switch (D) {
-            case 64: launch_coarse_t<64>(g16, N, nullptr, F, w.tilemax, tiles, s, queries, w.wgmax, w.ctl, w.qkey); break;
-            case 128: launch_coarse_t<128>(g16, N, nullptr, F, w.tilemax, tiles, s, queries, w.wgmax, w.ctl, w.qkey); break;
-            case 256: launch_coarse_t<256>(g16, N, nullptr, F, w.tilemax, tiles, s, queries, w.wgmax, w.ctl, w.qkey); break;
-            default: launch_coarse_t<512>(g16, N, nullptr, F, w.tilemax, tiles, s, queries, w.wgmax, w.ctl, w.qkey); break;
-        }
-        // (with F > 128 every query block y writes its own columns of wgmax: [n_wg][F])
-        hipLaunchKernelGGL(match_select_pairs_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles, w.wgmax, n_wg, F, queries, D, gmax_norm,
-                           reinterpret_cast<MatchPair *>(w.pairs), w.pair_cap, w.ctl, (const float *)nullptr, i8 ? 0.7e-3f : 1.2e-3f, i8 ? w.gerr : 0.f);
-        const int rr_grid = 2048;  // (one pair per workgroup up to 2 048 pairs: the re-rank is one 512-long dependent fma chain per row, i.e. per-pair latency)
-        if (gallery)
-            hipLaunchKernelGGL((match_rerank_pairs_kernel<float>), dim3(rr_grid), dim3(128), (size_t)D * sizeof(float), s, gallery, N, D, queries,
-                               reinterpret_cast<const MatchPair *>(w.pairs), w.pair_cap, w.ctl, w.qkey, (const float *)nullptr, (const int32_t *)nullptr, 1, 0);
-        else
-            hipLaunchKernelGGL((match_rerank_pairs_kernel<half_t>), dim3(rr_grid), dim3(128), (size_t)D * sizeof(float), s, g16, N, D, queries,
-                               reinterpret_cast<const MatchPair *>(w.pairs), w.pair_cap, w.ctl, w.qkey, (const float *)nullptr, (const int32_t *)nullptr, 1, 0);
-        // overflow (more candidate pairs than the list holds): the unscreened exact scan answers instead - launched always, gated on the
-        // flag (FB_BLOCKS workgroups that return at once in the normal case); the unpack kernel behind it finishes either path
-        const int *gate = w.ctl + CTL_OVERFLOW;
-        const int fb = partial_blocks < FB_BLOCKS ? partial_blocks : FB_BLOCKS;
-        if (gallery) launch_t<4, false, float>(gallery, N, D, queries, F, partial, nullptr, fb, row_offset, s, nullptr, nullptr, nullptr, nullptr, 1, gate);
-        else launch_t<4, false, half_t>(g16, N, D, queries, F, partial, nullptr, fb, row_offset, s, nullptr, nullptr, nullptr, nullptr, 1, gate);
-        hipLaunchKernelGGL(match_unpack_kernel, dim3((F + 255) / 256), dim3(256), 0, s, w.qkey, F, row_offset, w.ctl, idx_out, sim_out, 1, partial, fb);
-        return;
-    }
-    const long q8 = (long)F * D / 8;
-    const long nzero = (long)tiles + 1;  // tile flags + the candidate count behind them (ScreenScratch: count == tile_flags + tiles)
-    const long n_thr = q8 > nzero ? q8 : nzero;
-    hipLaunchKernelGGL(to_half_kernel, dim3((unsigned)((n_thr + 255) / 256)), dim3(256), 0, s, queries, w.q16, q8, w.tile_flags, nzero);
-    switch (D) {
-        case 64: launch_coarse_t<64>(g16, N, w.q16, F, w.tilemax, tiles, s); break;
-        case 128: launch_coarse_t<128>(g16, N, w.q16, F, w.tilemax, tiles, s); break;
-        case 256: launch_coarse_t<256>(g16, N, w.q16, F, w.tilemax, tiles, s); break;
-        default: launch_coarse_t<512>(g16, N, w.q16, F, w.tilemax, tiles, s); break;  // match_screen_supported() gates the callers
-    }
-    hipLaunchKernelGGL(match_segmax_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles * 4, w.segmax);
-    hipLaunchKernelGGL(match_select_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles, 4, w.segmax, queries, D, gmax_norm, w.tile_flags, w.tile_list,
-                       w.count, (const float *)nullptr);
-    // exact re-rank over the listed tiles (count lives on the device); the partial scratch is [partial_blocks][F]
-    // 32 queries per workgroup (grid.y = query blocks): the list is short (a few hundred tiles), so the pass is bound by the
-    // time ONE workgroup needs for a tile - 1024 fp32 MFMAs per wave with 128 queries (27 us), 256 with 32 (7 us).  Same
-    // per-(row, query) arithmetic as the full scan, hence still bit-identical.
-    if (gallery)
-        launch_t<1, false>(gallery, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, w.tile_list, w.count);
-    else  // fp16-stored gallery: the exact pass widens the stored rows (same per-tile code path as launch_match_top1_h's full scan)
-        launch_t<1, false, half_t>(g16, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, w.tile_list, w.count);
-    hipLaunchKernelGGL(match_reduce_kernel, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out, sim_out, 1, (const int *)nullptr);
 }

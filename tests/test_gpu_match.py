@@ -382,3 +382,74 @@ def test_int8_shadow_screening_is_exact_whatever_the_rows_look_like(frt, synth):
     want = np.array([np.nanargmax(np.where(np.isnan(r), -np.inf, r)) for r in full2], np.int32)
     assert np.array_equal(i2, want)
     m.close()
+
+
+# ---- one screened search (top-1 = its k == 1 case): the smallest screened galleries, against the matcher's own exact scan
+SCREEN_MIN_ROWS = 32768  # frt_matcher.hpp; / 128 = the coarse scan's 256 workgroups
+
+
+def _smallest_screened_case(synth):
+    """N = SCREEN_MIN_ROWS exactly, D = 512 (int8 shadow): 256 tiles, one per coarse workgroup.  Query 0 is row 77, whose exact duplicate
+    sits at row 30000 (first index wins; both head its top-k list); then noisy copies, tile edges included, and unrelated queries."""
+    N = SCREEN_MIN_ROWS
+    g = synth.make_gallery(N, seed=21)
+    g[30000] = g[77]
+    r = np.random.Generator(np.random.PCG64(22))
+    q = np.concatenate([g[[77]], synth.make_queries(g, [30000, 0, 127, 128, N - 1, 16383, 5000], noise=0.05, seed=23),
+                        r.standard_normal((120, 512)).astype(np.float32)])
+    return g, q, (77, 30000)
+
+
+def _ragged_fp16_shadow_case():
+    """N = SCREEN_MIN_ROWS + 77, D = 128 (fp16 shadow, ragged last tile), 40 queries.  Query 0 is row N - 300, duplicated into the last row."""
+    N, D = SCREEN_MIN_ROWS + 77, 128
+    r = np.random.Generator(np.random.PCG64(31))
+    g = r.standard_normal((N, D)).astype(np.float32)
+    g /= np.linalg.norm(g, axis=1, keepdims=True)
+    g[N - 1] = g[N - 300]
+    q = np.concatenate([g[[N - 300]], g[[N - 1, 0, 32767, 32768, N - 2]] + np.float32(0.03) * r.standard_normal((5, D)).astype(np.float32),
+                        r.standard_normal((34, D)).astype(np.float32)])
+    return g, q, (N - 300, N - 1)
+
+
+def _check_screened_against_exact_scan(frt, g, q, ks, dup):
+    """top1 and topk(k) for every k of `ks`, bit for bit against the ranking of the calculate() matrix ("higher similarity first, lower
+    index first"); then the same top1 with the screen switched off."""
+    m = frt.MatMul(0)
+    m.init(g)
+    full = m.calculate(q)
+    order = np.argsort(-full, axis=1, kind="stable")[:, :max(ks)].astype(np.int32)
+    sims = np.take_along_axis(full, order, 1)
+    i, s = m.top1(q)
+    assert np.array_equal(i, full.argmax(1).astype(np.int32)) and np.array_equal(s, full.max(1))
+    assert i[0] == dup[0] and full[0, dup[0]] == full[0, dup[1]]
+    for k in ks:
+        ti, ts = m.topk(q, k)
+        assert np.array_equal(ti[:, 0], i) and np.array_equal(ts[:, 0], s)
+        assert np.array_equal(ti, order[:, :k]) and np.array_equal(ts, sims[:, :k])
+        if k > 1:
+            assert ti[0, :2].tolist() == list(dup)
+    m.setScreening(False)
+    i0, s0 = m.top1(q)
+    assert np.array_equal(i0, i) and np.array_equal(s0, s)
+    m.close()
+
+
+@pytest.fixture(scope="module")
+def smallest_screened(synth):
+    return _smallest_screened_case(synth)
+
+
+@pytest.mark.parametrize("F", [1, 33, 128])
+def test_smallest_screened_gallery_one_tile_per_coarse_workgroup(frt, smallest_screened, F):
+    """tiles == the coarse scan's workgroup count: every workgroup owns exactly one tile.  1, 33 and 128 queries take the int8 coarse
+    kernel's 1 / 2 / 4 query-block instantiations; topk(1) takes the top-1 sequence, topk(4) the int8-shadow top-k on an fp32-stored
+    gallery.  (Seeds checked in float64: apart from the planted duplicate no query has two rows closer than 1.8e-5 relative among its
+    first five places, so the ranking of the calculate() matrix is unambiguous.)"""
+    g, q, dup = smallest_screened
+    _check_screened_against_exact_scan(frt, g, q[:F], (1, 4), dup)
+
+
+def test_screened_fp16_shadow_with_a_ragged_last_tile(frt):
+    g, q, dup = _ragged_fp16_shadow_case()
+    _check_screened_against_exact_scan(frt, g, q, (3,), dup)
