@@ -93,6 +93,14 @@ ABI = {
     "frt_matcher_topk_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "frt_merge_topk": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "frt_merge_topk_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "frt_matcher_set_labels": (_i, [_vp, _vp, _i]),
+    "frt_matcher_labels_info": (_i, [_vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "frt_matcher_gallery_add_labeled": (_i, [_vp, _vp, _vp, _i]),
+    "frt_matcher_gallery_add_labeled_dev": (_i, [_vp, _vp, _vp, _i]),
+    "frt_matcher_topk_labels": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "frt_matcher_topk_labels_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "frt_merge_topk_labels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frt_merge_topk_labels_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_embeds_to_half_dev": (_i, [_vp, _sz, _vp, _vp]),
     "frt_comm_get_unique_id": (_i, [_vp]),
     "frt_comm_set_bootstrap_timeout": (ctypes.c_double, [ctypes.c_double]),
@@ -325,6 +333,53 @@ class MatMul:
         _check(lib.frt_matcher_topk_dev(self._h, _vp(embeds_ptr), 1 if fp16 else 0, int(n), int(k), _vp(idx_ptr), _vp(sim_ptr),
                                         _vp(hip_stream) if hip_stream else None))
 
+    # identities (frt_matcher_set_labels / labels_info / gallery_add_labeled / topk_labels): one int32 label >= 0 per row; the ranked search
+    # then returns the k best IDENTITIES, each with its best row
+    def set_labels(self, labels):
+        """One label per gallery row (``None`` or an empty list clears them).  ``init`` / ``galleryCommit`` drop the labels."""
+        l = np.ascontiguousarray([] if labels is None else labels, np.int32).reshape(-1)
+        _check(lib.frt_matcher_set_labels(self._h, _ptr(l) if l.size else None, l.size))
+
+    def labels_info(self):
+        """(number of identities, upper bound of the rows one label has); (0, 0) for an unlabelled gallery."""
+        n, m = _i(), _i()
+        _check(lib.frt_matcher_labels_info(self._h, ctypes.byref(n), ctypes.byref(m)))
+        return n.value, m.value
+
+    def gallery_add_labeled(self, rows, labels):
+        """``galleryAdd`` for a labelled gallery: one label per new row.  Returns the first new index."""
+        a = np.ascontiguousarray(rows, np.float32).reshape(-1, self.k)
+        l = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        if l.size != a.shape[0]:
+            raise ValueError("gallery_add_labeled: one label per row")
+        first = int(lib.frt_matcher_num_rows(self._h))
+        _check(lib.frt_matcher_gallery_add_labeled(self._h, _ptr(a), _ptr(l), a.shape[0]))
+        self._edited()
+        return first
+
+    def gallery_add_labeled_dev(self, rows_ptr, labels):
+        """``galleryAddDev`` for a labelled gallery: rows on the device (raw address), labels on the host."""
+        l = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        first = int(lib.frt_matcher_num_rows(self._h))
+        _check(lib.frt_matcher_gallery_add_labeled_dev(self._h, _vp(rows_ptr), _ptr(l), l.size))
+        self._edited()
+        return first
+
+    def topk_labels(self, embeds, k):
+        """The k best identities per query -> (label, idx, sim), each [n, k]: entry j is the best row of the j-th best identity (entry 0 ==
+        top1; -1 / -1 / -inf when the gallery has fewer than k identities)."""
+        e = np.ascontiguousarray(embeds, np.float32).reshape(-1, self.k)
+        lab = np.empty((e.shape[0], int(k)), np.int32)
+        idx = np.empty((e.shape[0], int(k)), np.int32)
+        sim = np.empty((e.shape[0], int(k)), np.float32)
+        _check(lib.frt_matcher_topk_labels(self._h, _ptr(e), e.shape[0], int(k), _ptr(lab), _ptr(idx), _ptr(sim)))
+        return lab, idx, sim
+
+    def topk_labels_dev(self, embeds_ptr, n, k, label_ptr, idx_ptr, sim_ptr, hip_stream=None, fp16=False):
+        """Asynchronous, raw device addresses: queries as ``topk_dev``; label int32 [n][k], idx int32 [n][k], sim fp32 [n][k]."""
+        _check(lib.frt_matcher_topk_labels_dev(self._h, _vp(embeds_ptr), 1 if fp16 else 0, int(n), int(k), _vp(label_ptr), _vp(idx_ptr), _vp(sim_ptr),
+                                               _vp(hip_stream) if hip_stream else None))
+
     def setRowOffset(self, row_offset):
         """Sharded gallery: local row 0 is global row ``row_offset`` (top-1 indices become global)."""
         _check(lib.frt_matcher_set_row_offset(self._h, int(row_offset)))
@@ -386,6 +441,25 @@ def merge_topk(idx_all, sim_all):
 def merge_topk_dev(shards, n, k, idx_all_ptr, sim_all_ptr, idx_out_ptr, sim_out_ptr, hip_stream=None):
     _check(lib.frt_merge_topk_dev(int(shards), int(n), int(k), _vp(idx_all_ptr), _vp(sim_all_ptr), _vp(idx_out_ptr), _vp(sim_out_ptr),
                                   _vp(hip_stream) if hip_stream else None))
+
+
+def merge_topk_labels(label_all, idx_all, sim_all):
+    """Host merge of per-shard identity lists [shards, n, k] with global indices -> (label, idx, sim), each [n, k]; an identity present in
+    several shards counts once, with its best row."""
+    la = np.ascontiguousarray(label_all, np.int32)
+    ia = np.ascontiguousarray(idx_all, np.int32)
+    sa = np.ascontiguousarray(sim_all, np.float32)
+    shards, n, k = ia.shape
+    if la.shape != ia.shape or sa.shape != ia.shape:
+        raise ValueError("merge_topk_labels: label, idx and sim lists differ in shape")
+    lo, io, so = np.empty((n, k), np.int32), np.empty((n, k), np.int32), np.empty((n, k), np.float32)
+    _check(lib.frt_merge_topk_labels(shards, n, k, _ptr(la), _ptr(ia), _ptr(sa), _ptr(lo), _ptr(io), _ptr(so)))
+    return lo, io, so
+
+
+def merge_topk_labels_dev(shards, n, k, label_all_ptr, idx_all_ptr, sim_all_ptr, label_out_ptr, idx_out_ptr, sim_out_ptr, hip_stream=None):
+    _check(lib.frt_merge_topk_labels_dev(int(shards), int(n), int(k), _vp(label_all_ptr), _vp(idx_all_ptr), _vp(sim_all_ptr), _vp(label_out_ptr),
+                                         _vp(idx_out_ptr), _vp(sim_out_ptr), _vp(hip_stream) if hip_stream else None))
 
 
 def embeds_to_half_dev(src_ptr, n_values, dst_ptr, hip_stream=None):

@@ -74,9 +74,16 @@ void launch_match_topk(const float *gallery, const half_t *g16, int N, int D, co
                        const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
                        int row_offset, hipStream_t s);
 int match_topk_max();
+// exact top-k over identities [F][k] (labels [N]: one int32 >= 0 per local row): kth_count > 0 -> one screened search whose selection hangs on
+// the kth_count-th largest coarse entry (<= match_topk_max()), then k label-excluded re-rank passes; 0 -> k label-excluded exact scans
+void launch_match_topk_labels(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, int kth_count, float gmax_norm,
+                              const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, const int32_t *labels,
+                              int32_t *label_out, int32_t *idx_out, float *sim_out, int row_offset, hipStream_t s);
 void launch_half_to_float(const half_t *in, long n, float *out, hipStream_t s);
 void launch_float_to_half(const float *in, long n, half_t *out, hipStream_t s);
 void launch_merge_topk(const int32_t *idx_all, const float *sim_all, int shards, int n, int k, int32_t *idx_out, float *sim_out, hipStream_t s);
+void launch_merge_topk_labels(const int32_t *label_all, const int32_t *idx_all, const float *sim_all, int shards, int n, int k, int32_t *label_out,
+                              int32_t *idx_out, float *sim_out, hipStream_t s);
 // The fp16 gallery (shadow or stored) is kept in MFMA-fragment order and padded to whole 128-row tiles (see kernels_match.hip):
 size_t gallery16_elems(int N, int D);
 bool match_screen_supported(int D);  // D the coarse kernel is instantiated for

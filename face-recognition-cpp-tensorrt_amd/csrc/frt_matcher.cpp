@@ -29,6 +29,7 @@ void grow(frt_matcher *m, int rows) {
     uint8_t *sh8 = nullptr;
     float *sh8s = nullptr;
     const bool shadow = !m->store16 && m->screen && m->shadow_rows > 0;  // a valid shadow moves along; a stale one is dropped
+    if (m->labelled) m->ensure_label_room(cap, N, s);                    // the labels move with the rows
     try {
         if (m->store16) {
             HIPCHK(hipMalloc(reinterpret_cast<void **>(&new16), gallery16_elems(cap, D) * sizeof(half_t)));
@@ -84,16 +85,29 @@ void finish_edit(frt_matcher *m, int new_n) {
     HIPCHK(hipStreamSynchronize(m->stream));
 }
 
-void add_rows(frt_matcher *m, const void *rows, int n, bool on_device) {
+// labels: one per new row (host memory) for the labelled form, nullptr for the plain one.  A gallery with rows takes only the form that
+// matches its state; an empty one takes either and becomes labelled or unlabelled by it.
+void add_rows(frt_matcher *m, const void *rows, int n, bool on_device, const int32_t *labels = nullptr, bool labelled_form = false) {
     edit_checks(m, "gallery_add");
-    if (n < 0 || (n > 0 && !rows)) raise(FRT_ERR_INVALID, "gallery_add: bad argument");
+    if (n < 0 || (n > 0 && !rows) || (labelled_form && n > 0 && !labels)) raise(FRT_ERR_INVALID, "gallery_add: bad argument");
     if (m->D <= 0) raise(FRT_ERR_INVALID, "gallery_add: the number of columns is not known yet (frt_matcher_init or gallery_begin + commit first)");
+    if (m->N > 0 && m->labelled != labelled_form)
+        raise(FRT_ERR_INVALID, m->labelled ? "gallery_add: the gallery is labelled (frt_matcher_gallery_add_labeled)"
+                                           : "gallery_add_labeled: the gallery has no labels (frt_matcher_set_labels first)");
+    for (int i = 0; labelled_form && i < n; ++i)
+        if (labels[i] < 0) raise(FRT_ERR_INVALID, "gallery_add_labeled: negative label");
     if (n == 0) return;
     if ((long)m->N + n > INT32_MAX - 128) raise(FRT_ERR_CAPACITY, "gallery_add: too many rows");
     hipStream_t s = m->stream;
     const int N = m->N, D = m->D, new_n = N + n;
     m->wait_idle(s);
+    if (N == 0) m->drop_labels();  // (rows == 0: whatever labels the emptied gallery had are gone; grow then moves none)
     if (new_n > m->cap_rows) grow(m, std::max(new_n, std::max((int)std::min((long)m->cap_rows * 3 / 2, (long)INT32_MAX - 128), m->reserve_rows)));
+    if (labelled_form) {
+        m->ensure_label_room(m->cap_rows, N, s);
+        HIPCHK(hipMemcpyAsync(m->d_labels + N, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));  // (complete before finish_edit returns)
+        m->h_labels.reserve((size_t)m->cap_rows);
+    }
     const float *src32 = reinterpret_cast<const float *>(rows);  // the new rows as fp32 ON THE DEVICE (conversion source)
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (m->store16) {
@@ -144,6 +158,11 @@ void add_rows(frt_matcher *m, const void *rows, int n, bool on_device) {
         m->read_bounds(true);
     }
     HIPCHK(hipGetLastError());
+    if (labelled_form) {
+        m->labelled = true;
+        m->h_labels.insert(m->h_labels.end(), labels, labels + n);
+        m->count_labels(labels, n);
+    }
     finish_edit(m, new_n);
 }
 
@@ -212,6 +231,17 @@ void remove_rows(frt_matcher *m, const int32_t *idx, int n_idx) {
         HIPCHK(hipGetLastError());
         m->edit_stats[2] += n_re;
     }
+    if (m->labelled) {  // the labels close up with the rows: on the host mirror, then the moved tail goes back to the device
+        for (int i = 0; i < nk; ++i) {
+            auto it = m->label_rows.find(m->h_labels[(size_t)(keys[(size_t)i] + i)]);
+            if (it != m->label_rows.end() && --it->second == 0) m->label_rows.erase(it);
+        }
+        for (int j = r0; j < new_n; ++j) m->h_labels[(size_t)j] = m->h_labels[(size_t)frt_hole_source_row(keys.data(), 0, nk, j)];
+        m->h_labels.resize((size_t)new_n);
+        if (new_n > r0)
+            HIPCHK(hipMemcpyAsync(m->d_labels + r0, m->h_labels.data() + r0, (size_t)(new_n - r0) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        // max_rows_per_label stays: the true maximum cannot have grown, and an over-estimate only makes fewer calls screen
+    }
     finish_edit(m, new_n);
 }
 
@@ -243,12 +273,22 @@ void full_matrix_to_host(frt_matcher *m, int F, float *outputs, hipStream_t s) {
 }
 
 // upload the queries, search, download k columns per query: the top-1 search (lists == false, k == 1) or the top-k lists.
-// matrix_out != nullptr: the full matrix as well (the search runs under the tail of its download).
-void search_to_host(frt_matcher *m, const float *embeds, int F, bool lists, int k, int32_t *idx_out, float *sim_out, float *matrix_out = nullptr) {
+// matrix_out != nullptr: the full matrix as well (the search runs under the tail of its download).  label_out != nullptr: the lists rank
+// identities (frt_matcher_topk_labels) and their labels come back too.
+void check_labelled(frt_matcher *m) {
+    if (m->N > 0 && !m->labelled) raise(FRT_ERR_INVALID, "topk_labels: the gallery has no labels (frt_matcher_set_labels)");
+}
+
+void search_to_host(frt_matcher *m, const float *embeds, int F, bool lists, int k, int32_t *idx_out, float *sim_out, float *matrix_out = nullptr,
+                    int32_t *label_out = nullptr) {
     std::lock_guard<std::mutex> lk(m->mu);
+    if (label_out) check_labelled(m);
     hipStream_t s = upload_queries(m, embeds, F);
     if (matrix_out) full_matrix_to_host(m, F, matrix_out, s);
-    if (lists) m->topk_dev(m->d_q, F, k, m->d_idx, m->d_sim, s);
+    if (label_out) {
+        m->topk_labels_dev(m->d_q, F, k, m->d_lab, m->d_idx, m->d_sim, s);
+        HIPCHK(hipMemcpyAsync(label_out, m->d_lab, sizeof(int32_t) * (size_t)F * k, hipMemcpyDeviceToHost, s));
+    } else if (lists) m->topk_dev(m->d_q, F, k, m->d_idx, m->d_sim, s);
     else m->top1_dev(m->d_q, F, m->d_idx, m->d_sim, s);
     HIPCHK(hipMemcpyAsync(idx_out, m->d_idx, sizeof(int32_t) * (size_t)F * k, hipMemcpyDeviceToHost, s));
     HIPCHK(hipMemcpyAsync(sim_out, m->d_sim, sizeof(float) * (size_t)F * k, hipMemcpyDeviceToHost, s));
@@ -285,7 +325,7 @@ void frt_matcher_destroy(frt_matcher *m) {
         (void)hipStreamDestroy(m->stream);
     }
     if (m->ev_busy) (void)hipEventDestroy(m->ev_busy);
-    for (void *p : {(void *)m->d_gallery, (void *)m->d_q, (void *)m->d_sim, (void *)m->d_idx, (void *)m->d_partial, (void *)m->d_full, (void *)m->d_g16, (void *)m->d_kth,
+    for (void *p : {(void *)m->d_gallery, (void *)m->d_q, (void *)m->d_sim, (void *)m->d_idx, (void *)m->d_partial, (void *)m->d_full, (void *)m->d_g16, (void *)m->d_kth, (void *)m->d_labels, (void *)m->d_lab,
                     (void *)m->d_g8, (void *)m->d_g8_scale, (void *)m->d_edit_bits, (void *)m->d_edit_stage, m->d_bounce, (void *)m->d_keys})
         if (p) (void)hipFree(p);
     m->free_screen_scratch();
@@ -409,6 +449,62 @@ int frt_matcher_gallery_add_dev(frt_matcher *m, const void *rows_dev, int n_rows
         std::lock_guard<std::mutex> lk(m->mu);
         use_device(m->device);
         add_rows(m, rows_dev, n_rows, true);
+    });
+}
+
+int frt_matcher_gallery_add_labeled(frt_matcher *m, const float *rows, const int32_t *labels, int n_rows) {
+    return guarded([&] {
+        if (!m) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        use_device(m->device);
+        add_rows(m, rows, n_rows, false, labels, true);
+    });
+}
+
+int frt_matcher_gallery_add_labeled_dev(frt_matcher *m, const void *rows_dev, const int32_t *labels, int n_rows) {
+    return guarded([&] {
+        if (!m) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        use_device(m->device);
+        add_rows(m, rows_dev, n_rows, true, labels, true);
+    });
+}
+
+int frt_matcher_set_labels(frt_matcher *m, const int32_t *labels, int n) {
+    return guarded([&] {
+        if (!m || n < 0 || (n > 0 && !labels)) raise(FRT_ERR_INVALID, "set_labels: bad argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        if (n == 0) {  // clear
+            if (m->labelled) ++m->generation;
+            m->drop_labels();
+            return;
+        }
+        if (n != m->N) raise(FRT_ERR_INVALID, "set_labels: one label per gallery row");
+        for (int i = 0; i < n; ++i)
+            if (labels[i] < 0) raise(FRT_ERR_INVALID, "set_labels: negative label");
+        use_device(m->device);
+        hipStream_t s = m->stream;
+        m->wait_idle(s);  // a match stage in flight may be reading the old labels
+        HIPCHK(hipStreamSynchronize(s));
+        if (m->busy) HIPCHK(hipEventSynchronize(m->ev_busy));
+        m->ensure_label_room(std::max(m->cap_rows, n), 0, s);
+        HIPCHK(hipMemcpyAsync(m->d_labels, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        HIPCHK(hipStreamSynchronize(s));
+        m->drop_labels();
+        m->labelled = true;
+        m->h_labels.reserve((size_t)std::max(m->cap_rows, n));
+        m->h_labels.assign(labels, labels + n);
+        m->count_labels(labels, n);
+        ++m->generation;
+    });
+}
+
+int frt_matcher_labels_info(frt_matcher *m, int *n_identities, int *max_rows_per_label) {
+    return guarded([&] {
+        if (!m || !n_identities || !max_rows_per_label) raise(FRT_ERR_INVALID, "labels_info: null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        *n_identities = m->labelled ? (int)m->label_rows.size() : 0;
+        *max_rows_per_label = m->labelled ? m->max_rows_per_label : 0;
     });
 }
 
@@ -539,6 +635,84 @@ int frt_matcher_topk_dev(frt_matcher *m, const void *embeds_dev, int embeds_fp16
         m->topk_dev(q, embed_count, k, reinterpret_cast<int32_t *>(idx_dev), reinterpret_cast<float *>(sim_dev), s);
         HIPCHK(hipEventRecord(m->ev_busy, s));  // the scratch stays in use until this call has run
         m->busy = true;
+    });
+}
+
+int frt_matcher_topk_labels(frt_matcher *m, const float *embeds, int embed_count, int k, int32_t *label_out, int32_t *idx_out, float *sim_out) {
+    return guarded([&] {
+        if (!m || !embeds || !label_out || !idx_out || !sim_out) raise(FRT_ERR_INVALID, "topk_labels: null argument");
+        check_k(k);
+        search_to_host(m, embeds, embed_count, true, k, idx_out, sim_out, nullptr, label_out);
+    });
+}
+
+int frt_matcher_topk_labels_dev(frt_matcher *m, const void *embeds_dev, int embeds_fp16, int embed_count, int k, void *label_dev, void *idx_dev, void *sim_dev,
+                                void *hip_stream) {
+    return guarded([&] {
+        if (!m || !embeds_dev || !label_dev || !idx_dev || !sim_dev) raise(FRT_ERR_INVALID, "topk_labels_dev: null argument");
+        check_k(k);
+        std::lock_guard<std::mutex> lk(m->mu);
+        check_labelled(m);
+        if (m->N <= 0 || embed_count <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
+        use_device(m->device);
+        hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+        m->wait_idle(s);
+        m->ensure_queries(embed_count);
+        const float *q = reinterpret_cast<const float *>(embeds_dev);
+        if (embeds_fp16) {  // exact widening into the query scratch
+            launch_half_to_float(reinterpret_cast<const half_t *>(embeds_dev), (long)embed_count * m->D, m->d_q, s);
+            q = m->d_q;
+        }
+        m->topk_labels_dev(q, embed_count, k, reinterpret_cast<int32_t *>(label_dev), reinterpret_cast<int32_t *>(idx_dev), reinterpret_cast<float *>(sim_dev), s);
+        HIPCHK(hipEventRecord(m->ev_busy, s));  // the scratch stays in use until this call has run
+        m->busy = true;
+    });
+}
+
+int frt_merge_topk_labels(int shards, int n, int k, const int32_t *label_all, const int32_t *idx_all, const float *sim_all, int32_t *label_out,
+                          int32_t *idx_out, float *sim_out) {
+    return guarded([&] {
+        if (shards < 1 || n < 0 || k < 1 || !label_all || !idx_all || !sim_all || !label_out || !idx_out || !sim_out)
+            raise(FRT_ERR_INVALID, "merge_topk_labels: bad argument");
+        std::vector<size_t> ent;  // the query's occupied entries in the result order; the first of every label is kept
+        for (int q = 0; q < n; ++q) {
+            ent.clear();
+            for (int sh = 0; sh < shards; ++sh)
+                for (int j = 0; j < k; ++j) {
+                    const size_t e = ((size_t)sh * n + q) * k + j;
+                    if (idx_all[e] >= 0) ent.push_back(e);
+                }
+            std::sort(ent.begin(), ent.end(), [&](size_t a, size_t b) { return sim_all[a] > sim_all[b] || (sim_all[a] == sim_all[b] && idx_all[a] < idx_all[b]); });
+            int o = 0;
+            for (size_t e : ent) {
+                if (o == k) break;
+                bool taken = false;
+                for (int t = 0; t < o; ++t) taken = taken || label_out[(size_t)q * k + t] == label_all[e];
+                if (taken) continue;
+                label_out[(size_t)q * k + o] = label_all[e];
+                idx_out[(size_t)q * k + o] = idx_all[e];
+                sim_out[(size_t)q * k + o] = sim_all[e];
+                ++o;
+            }
+            for (; o < k; ++o) {
+                label_out[(size_t)q * k + o] = -1;
+                idx_out[(size_t)q * k + o] = -1;
+                sim_out[(size_t)q * k + o] = -INFINITY;
+            }
+        }
+    });
+}
+
+int frt_merge_topk_labels_dev(int shards, int n, int k, const void *label_all_dev, const void *idx_all_dev, const void *sim_all_dev, void *label_out_dev,
+                              void *idx_out_dev, void *sim_out_dev, void *hip_stream) {
+    return guarded([&] {
+        if (shards < 1 || n < 0 || k < 1 || !label_all_dev || !idx_all_dev || !sim_all_dev || !label_out_dev || !idx_out_dev || !sim_out_dev)
+            raise(FRT_ERR_INVALID, "merge_topk_labels_dev: bad argument");
+        if (n == 0) return;
+        launch_merge_topk_labels(reinterpret_cast<const int32_t *>(label_all_dev), reinterpret_cast<const int32_t *>(idx_all_dev),
+                                 reinterpret_cast<const float *>(sim_all_dev), shards, n, k, reinterpret_cast<int32_t *>(label_out_dev),
+                                 reinterpret_cast<int32_t *>(idx_out_dev), reinterpret_cast<float *>(sim_out_dev), reinterpret_cast<hipStream_t>(hip_stream));
+        HIPCHK(hipGetLastError());
     });
 }
 

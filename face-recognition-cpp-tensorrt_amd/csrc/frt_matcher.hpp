@@ -2,6 +2,8 @@
 #pragma once
 #include "frt_internal.hpp"
 
+#include <unordered_map>
+
 struct frt_matcher {
     unsigned generation = 0;  // bumped whenever gallery pointers / sizes / offsets change (invalidates captured graphs)
     int device = 0;
@@ -46,11 +48,47 @@ struct frt_matcher {
     void *d_bounce = nullptr;       // BOUNCE_BYTES of the chunked compaction
     int *d_keys = nullptr;          // the hole keys of a removal (frt_holes.h)
     size_t keys_cap = 0;
+    // ---- identities (frt_matcher_set_labels / gallery_add_labeled / topk_labels): one int32 label >= 0 per row, on the device for the label
+    //      test of the identity passes and mirrored on the host, where the edits and the per-label row counts are kept.
+    bool labelled = false;
+    int32_t *d_labels = nullptr;  // [labels_cap], allocated for cap_rows like the rows: a labelled add inside the capacity allocates nothing
+    int labels_cap = 0;
+    std::vector<int32_t> h_labels;               // [N] while labelled
+    std::unordered_map<int32_t, int> label_rows;  // label -> rows that carry it (its size = number of identities)
+    int max_rows_per_label = 0;   // M of the screening bound: never below the true maximum; a remove leaves it alone (an over-estimate is only slower)
+    int32_t *d_lab = nullptr;     // [q_cap][KCAP] label lists of the host entry point (allocated with d_idx / d_sim)
     static constexpr size_t BOUNCE_BYTES = (size_t)32 << 20;
     static constexpr int SCREEN_MIN_ROWS = 32768;
     // the coarse scan runs one persistent workgroup per CU and each needs a tile of its own: scr.wgmax is [FRT_MATCH_COARSE_WG][F], read in full
     static_assert(SCREEN_MIN_ROWS / 128 >= FRT_MATCH_COARSE_WG, "a screened gallery has at least one 128-row tile per coarse workgroup");
     void bind_scratch() { blocks = match_top1_blocks(N, 0); }
+    void drop_labels() {  // back to an unlabelled gallery (the device allocation is kept for the next labels)
+        labelled = false;
+        h_labels.clear();
+        label_rows.clear();
+        max_rows_per_label = 0;
+    }
+    // d_labels holds at least `rows` labels; the first `keep` survive a move
+    void ensure_label_room(int rows, int keep, hipStream_t s) {
+        if (rows <= labels_cap) return;
+        int32_t *nl = nullptr;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&nl), (size_t)rows * sizeof(int32_t)));
+        if (keep > 0 && d_labels) {
+            hipError_t e = hipMemcpyAsync(nl, d_labels, (size_t)keep * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+            if (e == hipSuccess) e = hipStreamSynchronize(s);
+            if (e != hipSuccess) {
+                (void)hipFree(nl);
+                HIPCHK(e);
+            }
+        }
+        if (d_labels) (void)hipFree(d_labels);
+        d_labels = nl;
+        labels_cap = rows;
+    }
+    // count `n` more labels into label_rows / max_rows_per_label
+    void count_labels(const int32_t *l, int n) {
+        for (int i = 0; i < n; ++i) max_rows_per_label = std::max(max_rows_per_label, ++label_rows[l[i]]);
+    }
     void free_screen_scratch() {
         for (void *p : {(void *)scr.tilemax, (void *)scr.wgmax, scr.pairs, (void *)scr.ctl, (void *)scr.qkey})
             if (p) (void)hipFree(p);
@@ -195,6 +233,7 @@ struct frt_matcher {
         d_g8_scale = nullptr;
         shadow_rows = 0;
         gerr = 0.f;
+        drop_labels();  // a new gallery: its rows have no labels until frt_matcher_set_labels
         ++generation;
         N = ld.rows;
         D = ld.D;
@@ -285,15 +324,17 @@ struct frt_matcher {
         if (d_q) (void)hipFree(d_q);
         if (d_sim) (void)hipFree(d_sim);
         if (d_idx) (void)hipFree(d_idx);
+        if (d_lab) (void)hipFree(d_lab);
         if (d_kth) (void)hipFree(d_kth);
         if (d_partial) (void)hipFree(d_partial);
         d_q = d_sim = d_kth = nullptr;
-        d_idx = nullptr;
+        d_idx = d_lab = nullptr;
         d_partial = nullptr;
         free_screen_scratch();
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_q), (size_t)cap * D * sizeof(float)));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_sim), (size_t)cap * KCAP * sizeof(float)));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_idx), (size_t)cap * KCAP * sizeof(int32_t)));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_lab), (size_t)cap * KCAP * sizeof(int32_t)));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_kth), (size_t)cap * sizeof(float)));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&d_partial), (size_t)match_top1_blocks(rows, 0) * cap * sizeof(MatchPartial)));  // [blocks][cap], blocks <= those of `rows`
         if (screen) {
@@ -324,6 +365,21 @@ struct frt_matcher {
     void topk_dev(const float *queries_dev, int F, int k, int32_t *idx_dev, float *sim_dev, hipStream_t s) {
         ProfScope ps(2, "match_topk", 2.0 * D * (double)N * F, s);
         launch_match_topk(d_gallery, d_g16, N, D, queries_dev, F, k, screen, gmax_norm, screen_scratch(), d_kth, d_partial, blocks, idx_dev, sim_dev, row_offset, s);
+        HIPCHK(hipGetLastError());
+    }
+    // The selection count of a screened identity search, 0 = take the exact passes.  With at most M rows per label the best (k - 1) * M + 1
+    // rows hold k identities, so the ((k - 1) * M + 1)-th largest coarse entry bounds the k-th identity's similarity the way the k-th largest
+    // bounds the k-th row's; the kth kernel ranks up to match_topk_max() entries.
+    int identity_kth_count(int k) const {
+        if (!(screen && screen_on)) return 0;
+        const long c = (long)(k - 1) * max_rows_per_label + 1;
+        return c <= match_topk_max() ? (int)c : 0;
+    }
+    // exact top-k over identities [F][k] (label_dev / idx_dev / sim_dev device pointers); queries fp32 on the device
+    void topk_labels_dev(const float *queries_dev, int F, int k, int32_t *label_dev, int32_t *idx_dev, float *sim_dev, hipStream_t s) {
+        ProfScope ps(2, "match_topk_labels", 2.0 * D * (double)N * F, s);
+        launch_match_topk_labels(d_gallery, d_g16, N, D, queries_dev, F, k, identity_kth_count(k), gmax_norm, screen_scratch(), d_kth, d_partial, blocks,
+                                 d_labels, label_dev, idx_dev, sim_dev, row_offset, s);
         HIPCHK(hipGetLastError());
     }
 };

@@ -54,11 +54,23 @@ __device__ __forceinline__ floatx4 load_g4(const half_t *G, long g, int D, int k
 // EXCL (top-k passes): only rows that come strictly AFTER the query's previous winner (prev_sim, prev_idx = its GLOBAL index) in the
 // result order "higher similarity first, lower index first on ties" take part; prev_sim == nullptr: no previous winner (first pass).
 // The similarities are the same accumulators either way, so pass j of a top-k search returns the j-th entry of the exact ranking.
-template <int NQ, bool FULL, typename GT = float, bool EXCL = false>
+// LAB (identity top-k passes, with EXCL): labels[g] is the identity of LOCAL row g, and a row only takes part when its label is none of the
+// n_taken labels already reported for its query (taken[q * prev_stride + 0 .. n_taken), the query's row of label_out).  The label is looked up
+// only for a row that would otherwise become the lane's running best, so the test costs two dependent loads on a rare path.  The cursor of
+// EXCL stays as a first filter: a row ranked before winner j - 1 that is not itself a winner carries a taken label.
+__device__ __forceinline__ bool label_taken(int lab, const int32_t *__restrict__ taken, int n_taken) {
+    bool hit = false;
+    for (int t = 0; t < n_taken; ++t) hit = hit || taken[t] == lab;
+    return hit;
+}
+
+template <int NQ, bool FULL, typename GT = float, bool EXCL = false, bool LAB = false>
 __global__ __launch_bounds__(256) void match_kernel(const GT *__restrict__ G, int N, int D, const float *__restrict__ E, int F,
                                                     MatchPartial *__restrict__ partial, float *__restrict__ out_full, int num_tiles,
                                                     int row_offset, const float *__restrict__ prev_sim = nullptr, const int32_t *__restrict__ prev_idx = nullptr,
-                                                    int prev_stride = 1, const int *__restrict__ gate = nullptr) {
+                                                    int prev_stride = 1, const int *__restrict__ gate = nullptr, const int32_t *__restrict__ labels = nullptr,
+                                                    const int32_t *__restrict__ taken = nullptr, int n_taken = 0) {
+    static_assert(!LAB || (EXCL && !FULL), "the label test is part of the top-k passes");
     if (gate && !*gate) return;  // screened search: this launch only runs when the pair list overflowed (uniform; before any barrier)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *As = reinterpret_cast<float *>(smem);                        // [2][BM][BK]
@@ -176,7 +188,12 @@ __global__ __launch_bounds__(256) void match_kernel(const GT *__restrict__ G, in
                         const float v = acc[n][e];
                         bool ok = g < N;
                         if (EXCL) ok = ok && ((v < ps[n]) || (v == ps[n] && g + row_offset > pi[n]));
-                        if (ok && better(v, g, bv[n], bi[n])) {
+                        ok = ok && better(v, g, bv[n], bi[n]);
+                        if (LAB) {
+                            const int q = q0 + n * 32 + r;
+                            if (ok && q < F) ok = !label_taken(labels[g], taken + (long)q * prev_stride, n_taken);
+                        }
+                        if (ok) {
                             bv[n] = v;
                             bi[n] = g;
                         }
@@ -231,9 +248,12 @@ __global__ __launch_bounds__(256) void match_kernel(const GT *__restrict__ G, in
 }
 
 // one wave per query: lanes stride over the workgroup partials, then a butterfly with the same first-maximum rule
+// LAB: the winner's label as well (labels of LOCAL rows; the partial indices are global), -1 with no winner
+template <bool LAB = false>
 __global__ __launch_bounds__(64) void match_reduce_kernel(const MatchPartial *__restrict__ partial, int blocks, int F,
                                                           int32_t *__restrict__ idx_out, float *__restrict__ sim_out, int out_stride = 1,
-                                                          const int *__restrict__ gate = nullptr) {
+                                                          const int *__restrict__ gate = nullptr, const int32_t *__restrict__ labels = nullptr,
+                                                          int32_t *__restrict__ label_out = nullptr, int row_offset = 0) {
     if (gate && !*gate) return;
     const int q = blockIdx.x;
     float v = -INFINITY;
@@ -256,6 +276,7 @@ __global__ __launch_bounds__(64) void match_reduce_kernel(const MatchPartial *__
     if (threadIdx.x == 0) {
         idx_out[(long)q * out_stride] = i == INT_MAX ? -1 : i;
         sim_out[(long)q * out_stride] = v;
+        if (LAB) label_out[(long)q * out_stride] = i == INT_MAX ? -1 : labels[i - row_offset];
     }
 }
 
@@ -765,6 +786,49 @@ __global__ __launch_bounds__(64) void merge_topk_kernel(const int32_t *__restric
     }
 }
 
+// The labelled sibling: label_all [shards][n][k] names the identity of every entry, and an identity counts once, with its best entry
+// (higher similarity, lower global index on a tie).  Entry o is the best entry behind winner o - 1 whose label is none of the o labels
+// already written for the query (an entry in front of the cursor that did not win carries a taken label); label_out doubles as that list.
+__global__ __launch_bounds__(64) void merge_topk_labels_kernel(const int32_t *__restrict__ label_all, const int32_t *__restrict__ idx_all,
+                                                               const float *__restrict__ sim_all, int shards, int n, int k, int32_t *__restrict__ label_out,
+                                                               int32_t *__restrict__ idx_out, float *__restrict__ sim_out) {
+    const int q = blockIdx.x * 64 + threadIdx.x;
+    if (q >= n) return;
+    float lv = INFINITY;
+    int li = -1;
+    for (int o = 0; o < k; ++o) {
+        float bv = -INFINITY;
+        int bi = INT_MAX, bl = -1;
+        for (int s = 0; s < shards; ++s)
+            for (int j = 0; j < k; ++j) {
+                const long e = ((long)s * n + q) * k + j;
+                const int i = idx_all[e];
+                const float v = sim_all[e];
+                if (i < 0) continue;
+                if (!((v < lv) || (v == lv && i > li))) continue;
+                if (!better(v, i, bv, bi)) continue;
+                const int l = label_all[e];
+                if (label_taken(l, label_out + (long)q * k, o)) continue;
+                bv = v;
+                bi = i;
+                bl = l;
+            }
+        if (bi == INT_MAX) {  // exhausted: this and the remaining slots are empty
+            for (int o2 = o; o2 < k; ++o2) {
+                label_out[(long)q * k + o2] = -1;
+                idx_out[(long)q * k + o2] = -1;
+                sim_out[(long)q * k + o2] = -INFINITY;
+            }
+            return;
+        }
+        label_out[(long)q * k + o] = bl;
+        idx_out[(long)q * k + o] = bi;
+        sim_out[(long)q * k + o] = bv;
+        lv = bv;
+        li = bi;
+    }
+}
+
 // ---------------------------------------------------------------- pair selection + exact re-rank
 // (An earlier version listed whole tiles and ran match_kernel over the list: ALL queries against every listed tile - 128 x 128 dot
 // products where typically one query asked for it - behind a per-tile barrier chain, 59 us for a few hundred tiles.)  The selection emits
@@ -864,11 +928,13 @@ __global__ __launch_bounds__(256) void match_select_pairs_kernel(const float *__
 }
 
 // one workgroup (128 threads = the tile's 128 rows) per pair, pairs dealt round-robin over the grid
-template <typename GT>
+// LAB: the identity passes - a row whose label is one of the n_taken labels already reported for the pair's query takes no part either
+template <typename GT, bool LAB = false>
 __global__ __launch_bounds__(128) void match_rerank_pairs_kernel(const GT *__restrict__ G, int N, int D, const float *__restrict__ E, const MatchPair *__restrict__ pairs,
                                                                  int pair_cap, const int *__restrict__ ctl, unsigned long long *__restrict__ qkey,
                                                                  const float *__restrict__ prev_sim = nullptr, const int32_t *__restrict__ prev_idx = nullptr,
-                                                                 int prev_stride = 1, int row_offset = 0) {
+                                                                 int prev_stride = 1, int row_offset = 0, const int32_t *__restrict__ labels = nullptr,
+                                                                 const int32_t *__restrict__ taken = nullptr, int n_taken = 0) {
     // prev_sim != nullptr (top-k pass j > 0): only rows strictly AFTER the query's previous winner (its similarity, its GLOBAL index) in the
     // result order take part - the EXCL rule of match_kernel
     extern __shared__ __attribute__((aligned(16))) char smem3[];
@@ -914,6 +980,12 @@ __global__ __launch_bounds__(128) void match_rerank_pairs_kernel(const GT *__res
                 i = INT_MAX;
             }
         }
+        if (LAB) {
+            if (i != INT_MAX && label_taken(labels[i], taken + (long)pr.q * prev_stride, n_taken)) {
+                v = -INFINITY;
+                i = INT_MAX;
+            }
+        }
         if (v != v) {  // NaN never wins (std::max_element with operator<: a NaN is never greater)
             v = -INFINITY;
             i = INT_MAX;
@@ -943,9 +1015,12 @@ __global__ __launch_bounds__(128) void match_rerank_pairs_kernel(const GT *__res
 
 // Last kernel of a pass.  Normal case: the packed winners of the pair re-rank.  Overflow case: the gated exact scan ran in front of this
 // kernel (fb_blocks workgroups); its per-workgroup partials are reduced here, one thread per query, with the same first-maximum rule.
+// LAB: the winner's label as well (labels of LOCAL rows), -1 with no winner.
+template <bool LAB = false>
 __global__ __launch_bounds__(256) void match_unpack_kernel(unsigned long long *__restrict__ qkey, int F, int row_offset, const int *__restrict__ ctl,
                                                            int32_t *__restrict__ idx_out, float *__restrict__ sim_out, int out_stride,
-                                                           const MatchPartial *__restrict__ fb_partial, int fb_blocks) {
+                                                           const MatchPartial *__restrict__ fb_partial, int fb_blocks,
+                                                           const int32_t *__restrict__ labels = nullptr, int32_t *__restrict__ label_out = nullptr) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= F) return;
     if (ctl[CTL_OVERFLOW]) {
@@ -961,12 +1036,14 @@ __global__ __launch_bounds__(256) void match_unpack_kernel(unsigned long long *_
         qkey[q] = 0ull;
         idx_out[(long)q * out_stride] = i == INT_MAX ? -1 : i;  // (the scan's partial indices already carry the row offset)
         sim_out[(long)q * out_stride] = v;
+        if (LAB) label_out[(long)q * out_stride] = i == INT_MAX ? -1 : labels[i - row_offset];
         return;
     }
     const unsigned long long k = qkey[q];
     qkey[q] = 0ull;  // ready for the next top-k pass of this call
     idx_out[(long)q * out_stride] = k ? (int)(~(unsigned)(k & 0xffffffffull)) + row_offset : -1;
     sim_out[(long)q * out_stride] = k ? unmono_bits((unsigned)(k >> 32)) : -INFINITY;
+    if (LAB) label_out[(long)q * out_stride] = k ? labels[(int)(~(unsigned)(k & 0xffffffffull))] : -1;
 }
 
 // ---------------------------------------------------------------- live gallery edits: order-preserving compaction (frt_matcher_gallery_remove)
@@ -1004,18 +1081,19 @@ __global__ __launch_bounds__(256) void gather_rows_h16_kernel(const half_t *__re
     *reinterpret_cast<half8 *>(bounce + t * 8) = v;
 }
 
-template <int NQ, bool FULL, typename GT = float, bool EXCL = false>
+template <int NQ, bool FULL, typename GT = float, bool EXCL = false, bool LAB = false>
 void launch_t(const GT *G, int N, int D, const float *E, int F, MatchPartial *partial, float *out_full, int blocks, int row_offset,
-              hipStream_t s, const float *prev_sim = nullptr, const int32_t *prev_idx = nullptr, int prev_stride = 1, const int *gate = nullptr) {
+              hipStream_t s, const float *prev_sim = nullptr, const int32_t *prev_idx = nullptr, int prev_stride = 1, const int *gate = nullptr,
+              const int32_t *labels = nullptr, const int32_t *taken = nullptr, int n_taken = 0) {
     const int tiles = (N + BM - 1) / BM;
     const size_t lds = (size_t)2 * (BM + NQ * 32) * BK * sizeof(float);
     static bool attr_done[FRT_MAX_DEVICES] = {};
     if (frt_first_use_on_device(attr_done)) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&match_kernel<NQ, FULL, GT, EXCL>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&match_kernel<NQ, FULL, GT, EXCL, LAB>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }
     dim3 grid(blocks, (F + NQ * 32 - 1) / (NQ * 32));
-    hipLaunchKernelGGL((match_kernel<NQ, FULL, GT, EXCL>), grid, dim3(256), lds, s, G, N, D, E, F, partial, out_full, tiles, row_offset, prev_sim, prev_idx,
-                       prev_stride, gate);
+    hipLaunchKernelGGL((match_kernel<NQ, FULL, GT, EXCL, LAB>), grid, dim3(256), lds, s, G, N, D, E, F, partial, out_full, tiles, row_offset, prev_sim, prev_idx,
+                       prev_stride, gate, labels, taken, n_taken);
 }
 
 // The exact passes read the STORED rows: fp32 row-major (gallery), or the fragment-ordered fp16 rows when there is no fp32 copy on the
@@ -1046,7 +1124,7 @@ void launch_match_top1(const GT *rows, int N, int D, const float *queries, int F
         launch_t<2, false>(rows, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
     else
         launch_t<4, false>(rows, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s);
-    hipLaunchKernelGGL(match_reduce_kernel, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out, sim_out, 1, (const int *)nullptr);
+    hipLaunchKernelGGL(match_reduce_kernel<false>, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out, sim_out, 1, (const int *)nullptr);
 }
 template void launch_match_top1(const float *, int, int, const float *, int, MatchPartial *, int, int32_t *, float *, int, hipStream_t);
 template void launch_match_top1(const half_t *, int, int, const float *, int, MatchPartial *, int, int32_t *, float *, int, hipStream_t);
@@ -1144,15 +1222,10 @@ static void launch_coarse_t(const half_t *g16, const ScreenScratch &w, int N, co
     hipLaunchKernelGGL((match_coarse_kernel<D>), g, dim3(256), lds, s, g16, N, F, w.tilemax, tiles, q32, w.wgmax, w.ctl, w.qkey);
 }
 
-// The screened search: exact top-k lists idx_out / sim_out [F][k] (k = 1: the top-1 search), bit for bit what the exact scan returns.
-//   coarse scan (queries rounded on load; per-workgroup maxima; clears ctl / qkey)
-//   k > 1: every query's k-th largest coarse entry (kth_scratch [F] floats) - the selection threshold hangs on it instead of the largest
-//   (query, tile) pairs inside the rounding band
-//   k passes, pass j restricted to the rows behind winner j - 1: scalar pair re-rank (a few microseconds), the unscreened exact scan
-//   gated on the pair list's overflow flag (FB_BLOCKS workgroups that return at once in the normal case), unpack of either result
-void launch_match_screened(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, float gmax_norm,
-                           const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
-                           int row_offset, hipStream_t s) {
+// The front of every screened call: coarse scan, then the (query, tile) pairs inside the band under the query's kth_count-th largest coarse
+// entry (kth_count == 1: its largest, taken from the per-workgroup maxima).
+static void launch_coarse_select(const half_t *g16, int N, int D, const float *queries, int F, int kth_count, float gmax_norm, const ScreenScratch &w,
+                                 float *kth_scratch, hipStream_t s) {
     const int tiles = (N + BM - 1) / BM;
     const bool i8 = w.g8 && D == 512;  // int8 shadow (fp32-stored galleries): half the bytes of the scan, same answers
     if (i8) {
@@ -1166,13 +1239,25 @@ void launch_match_screened(const float *gallery, const half_t *g16, int N, int D
         default: launch_coarse_t<512>(g16, w, N, queries, F, tiles, s); break;  // match_screen_supported() gates the callers
     }
     const float *kth = nullptr;
-    if (k > 1) {
-        hipLaunchKernelGGL(match_kth_kernel, dim3(F), dim3(256), 0, s, w.tilemax, tiles * 4, k, kth_scratch);
+    if (kth_count > 1) {
+        hipLaunchKernelGGL(match_kth_kernel, dim3(F), dim3(256), 0, s, w.tilemax, tiles * 4, kth_count, kth_scratch);
         kth = kth_scratch;
     }
     // (with F > 128 every query block y wrote its own columns of wgmax: [COARSE_WG][F])
     hipLaunchKernelGGL(match_select_pairs_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles, w.wgmax, COARSE_WG, F, queries, D, gmax_norm,
                        reinterpret_cast<MatchPair *>(w.pairs), w.pair_cap, w.ctl, kth, i8 ? 0.7e-3f : 1.2e-3f, i8 ? w.gerr : 0.f);
+}
+
+// The screened search: exact top-k lists idx_out / sim_out [F][k] (k = 1: the top-1 search), bit for bit what the exact scan returns.
+//   coarse scan (queries rounded on load; per-workgroup maxima; clears ctl / qkey)
+//   k > 1: every query's k-th largest coarse entry (kth_scratch [F] floats) - the selection threshold hangs on it instead of the largest
+//   (query, tile) pairs inside the rounding band
+//   k passes, pass j restricted to the rows behind winner j - 1: scalar pair re-rank (a few microseconds), the unscreened exact scan
+//   gated on the pair list's overflow flag (FB_BLOCKS workgroups that return at once in the normal case), unpack of either result
+void launch_match_screened(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, float gmax_norm,
+                           const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
+                           int row_offset, hipStream_t s) {
+    launch_coarse_select(g16, N, D, queries, F, k, gmax_norm, w, kth_scratch, s);
     const int rr_grid = 2048;  // (one pair per workgroup up to 2 048 pairs: the re-rank is one 512-long dependent fma chain per row, i.e. per-pair latency)
     const int *gate = w.ctl + CTL_OVERFLOW;
     const int fb = partial_blocks < FB_BLOCKS ? partial_blocks : FB_BLOCKS;
@@ -1185,7 +1270,7 @@ void launch_match_screened(const float *gallery, const half_t *g16, int N, int D
                                reinterpret_cast<const MatchPair *>(w.pairs), w.pair_cap, w.ctl, w.qkey, ps, pi, k, row_offset);
             if (k == 1) launch_t<4, false, GT>(G, N, D, queries, F, partial, nullptr, fb, row_offset, s, nullptr, nullptr, 1, gate);
             else launch_t<4, false, GT, true>(G, N, D, queries, F, partial, nullptr, fb, row_offset, s, ps, pi, k, gate);
-            hipLaunchKernelGGL(match_unpack_kernel, dim3((F + 255) / 256), dim3(256), 0, s, w.qkey, F, row_offset, w.ctl, idx_out + j, sim_out + j, k, partial, fb);
+            hipLaunchKernelGGL(match_unpack_kernel<false>, dim3((F + 255) / 256), dim3(256), 0, s, w.qkey, F, row_offset, w.ctl, idx_out + j, sim_out + j, k, partial, fb);
         }
     });
 }
@@ -1205,11 +1290,43 @@ void launch_match_topk(const float *gallery, const half_t *g16, int N, int D, co
             const int32_t *pi = j ? idx_out + (j - 1) : nullptr;
             if (F <= 32) launch_t<1, false, GT, true>(G, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, ps, pi, k);
             else launch_t<4, false, GT, true>(G, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, ps, pi, k);
-            hipLaunchKernelGGL(match_reduce_kernel, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out + j, sim_out + j, k, (const int *)nullptr);
+            hipLaunchKernelGGL(match_reduce_kernel<false>, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out + j, sim_out + j, k, (const int *)nullptr);
         }
     });
 }
 int match_topk_max() { return TOPK_MAX; }
+
+// Exact top-k over IDENTITIES: label_out / idx_out / sim_out [F][k], entry j = (label, global row, similarity) of the best row of the
+// query's j-th best identity; labels [N] = the identity of every local row.  k passes of the top-1 search; pass j leaves out the rows whose
+// label is one of label_out[q][0 .. j) (and, as a first filter, those in front of winner j - 1).  kth_count > 0: through the screen - ONE
+// coarse scan, pairs under the kth_count-th largest coarse entry (the caller's bound: the best kth_count rows hold k identities), then
+// k passes of the pair re-rank with the gated exact scan behind the overflow flag.  kth_count == 0: k exact scans of the stored rows.
+void launch_match_topk_labels(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, int kth_count, float gmax_norm,
+                              const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, const int32_t *labels,
+                              int32_t *label_out, int32_t *idx_out, float *sim_out, int row_offset, hipStream_t s) {
+    if (kth_count > 0) launch_coarse_select(g16, N, D, queries, F, kth_count, gmax_norm, w, kth_scratch, s);
+    const int *gate = w.ctl + CTL_OVERFLOW;
+    const int fb = partial_blocks < FB_BLOCKS ? partial_blocks : FB_BLOCKS;
+    with_stored_rows(gallery, g16, [&](auto *G) {
+        using GT = rows_t<decltype(G)>;
+        for (int j = 0; j < k; ++j) {
+            const float *ps = j ? sim_out + (j - 1) : nullptr;
+            const int32_t *pi = j ? idx_out + (j - 1) : nullptr;
+            if (kth_count > 0) {
+                hipLaunchKernelGGL((match_rerank_pairs_kernel<GT, true>), dim3(2048), dim3(128), (size_t)D * sizeof(float), s, G, N, D, queries,
+                                   reinterpret_cast<const MatchPair *>(w.pairs), w.pair_cap, w.ctl, w.qkey, ps, pi, k, row_offset, labels, label_out, j);
+                launch_t<4, false, GT, true, true>(G, N, D, queries, F, partial, nullptr, fb, row_offset, s, ps, pi, k, gate, labels, label_out, j);
+                hipLaunchKernelGGL(match_unpack_kernel<true>, dim3((F + 255) / 256), dim3(256), 0, s, w.qkey, F, row_offset, w.ctl, idx_out + j, sim_out + j, k,
+                                   partial, fb, labels, label_out + j);
+            } else {
+                if (F <= 32) launch_t<1, false, GT, true, true>(G, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, ps, pi, k, nullptr, labels, label_out, j);
+                else launch_t<4, false, GT, true, true>(G, N, D, queries, F, partial, nullptr, partial_blocks, row_offset, s, ps, pi, k, nullptr, labels, label_out, j);
+                hipLaunchKernelGGL(match_reduce_kernel<true>, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out + j, sim_out + j, k, (const int *)nullptr,
+                                   labels, label_out + j, row_offset);
+            }
+        }
+    });
+}
 
 void launch_half_to_float(const half_t *in, long n, float *out, hipStream_t s) {  // n % 8 == 0
     hipLaunchKernelGGL(half_to_float_kernel, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, in, out, n / 8);
@@ -1219,4 +1336,8 @@ void launch_float_to_half(const float *in, long n, half_t *out, hipStream_t s) {
 }
 void launch_merge_topk(const int32_t *idx_all, const float *sim_all, int shards, int n, int k, int32_t *idx_out, float *sim_out, hipStream_t s) {
     hipLaunchKernelGGL(merge_topk_kernel, dim3((n + 63) / 64), dim3(64), 0, s, idx_all, sim_all, shards, n, k, idx_out, sim_out);
+}
+void launch_merge_topk_labels(const int32_t *label_all, const int32_t *idx_all, const float *sim_all, int shards, int n, int k, int32_t *label_out,
+                              int32_t *idx_out, float *sim_out, hipStream_t s) {
+    hipLaunchKernelGGL(merge_topk_labels_kernel, dim3((n + 63) / 64), dim3(64), 0, s, label_all, idx_all, sim_all, shards, n, k, label_out, idx_out, sim_out);
 }

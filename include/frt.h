@@ -267,6 +267,47 @@ int frt_merge_topk_dev(int shards, int n, int k, const void *idx_all_dev, const 
 /* fp32 -> IEEE fp16 (round to nearest even) of n_values (a multiple of 8) device floats: the embeddings before they are exchanged. */
 int frt_embeds_to_half_dev(const void *embeds_dev, size_t n_values, void *half_out_dev, void *hip_stream);
 
+/* Top-k over IDENTITIES.  The reference's gallery holds several rows per person (USER 1-N FACE; addEmbedding(userId, blob) once per face), so
+ * the k best ROWS can be one person k times.  A labelled gallery has one int32 label >= 0 per row, and the ranked search then ranks labels:
+ *   similarities - those frt_matcher_calculate returns, the same accumulators bit for bit (fp16 storage: the fp16-row similarities above);
+ *   row order    - higher similarity first, lower global index first among equals (the order of frt_matcher_topk);
+ *   ranking      - walk the rows in that order, keep a row if no kept row has its label; the first k kept rows are the answer.  Entry j
+ *                  reports (label, global row index, similarity) of the best row of the j-th best identity.
+ * So entry 0 is frt_matcher_top1's answer bit for bit, all labels distinct gives frt_matcher_topk's lists, and with fewer than k identities
+ * the unused slots hold label -1, idx -1, sim -inf.  1 <= k <= 16.  A matcher that never gets labels behaves exactly as before.
+ * set_labels: labels[n], n == frt_matcher_num_rows; they are copied to the device and move with later edits.  labels == NULL, n == 0 clears
+ *   them.  A negative label or a wrong n: FRT_ERR_INVALID, nothing changed.  frt_matcher_init and frt_matcher_gallery_commit REPLACE the
+ *   gallery and therefore drop the labels: set them again after a reload.  frt_matcher_generation changes whenever the labels change.
+ * labels_info: the number of distinct labels and an upper bound M of the rows any one label has (exact after set_labels and adds; a remove
+ *   leaves it alone, so it may over-state but never under-states).  0, 0 for an unlabelled gallery.
+ * gallery_add_labeled / _dev: frt_matcher_gallery_add / _add_dev with one label per new row (labels in HOST memory in both forms).  A
+ *   gallery with rows takes only the form that matches it - the plain add on a labelled gallery and the labelled add on an unlabelled one
+ *   are FRT_ERR_INVALID - an empty one takes either and becomes labelled or unlabelled by it.  frt_matcher_gallery_remove closes the labels
+ *   up with the rows, frt_matcher_gallery_reserve makes room for them too.  After any edit sequence the identity answers equal those of a
+ *   fresh matcher initialised with the resulting rows and labels.
+ * topk_labels / _dev: label_out, idx_out, sim_out are [embed_count][k]; row offset, fp16 queries and stream semantics as frt_matcher_topk /
+ *   _dev.  An unlabelled gallery: FRT_ERR_INVALID; an empty one: FRT_ERR_EMPTY.
+ *   Cost: k exact scans of the stored rows per call (pass j is the top-1 search without the rows of the j labels already reported).  A
+ *   screened gallery (>= 32 768 rows, screening on) with (k - 1) * M + 1 <= 16 instead runs ONE coarse scan and k short re-rank passes: with
+ *   at most M rows per label the best (k - 1) * M + 1 rows hold k identities, which bounds the selection.  Same bits either way;
+ *   frt_matcher_set_screening(m, 0) forces the exact passes. */
+int frt_matcher_set_labels(frt_matcher *m, const int32_t *labels, int n);
+int frt_matcher_labels_info(frt_matcher *m, int *n_identities, int *max_rows_per_label);
+int frt_matcher_gallery_add_labeled(frt_matcher *m, const float *rows, const int32_t *labels, int n_rows);
+int frt_matcher_gallery_add_labeled_dev(frt_matcher *m, const void *rows_dev, const int32_t *labels /* host */, int n_rows);
+int frt_matcher_topk_labels(frt_matcher *m, const float *embeds, int embed_count, int k, int32_t *label_out, int32_t *idx_out, float *sim_out);
+int frt_matcher_topk_labels_dev(frt_matcher *m, const void *embeds_dev, int embeds_fp16, int embed_count, int k, void *label_dev, void *idx_dev, void *sim_dev,
+                                void *hip_stream);
+/* frt_merge_topk for identity lists: label_all / idx_all / sim_all [shards][n][k] with global indices -> [n][k] by the ranking above.  An
+ * identity that appears in several shards (one user's photos may sit on different shards) counts once, with its best row: higher
+ * similarity, lower global index on a tie.  idx < 0 = empty slot.  Exact: an identity of the global top-k is in the top-k of distinct
+ * identities of the shard that holds its best row, because every identity ahead of it there is ahead of it globally.  The host form needs
+ * no device. */
+int frt_merge_topk_labels(int shards, int n, int k, const int32_t *label_all, const int32_t *idx_all, const float *sim_all, int32_t *label_out,
+                          int32_t *idx_out, float *sim_out);
+int frt_merge_topk_labels_dev(int shards, int n, int k, const void *label_all_dev, const void *idx_all_dev, const void *sim_all_dev, void *label_out_dev,
+                              void *idx_out_dev, void *sim_out_dev, void *hip_stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU exchange.  The reference is one single-GPU C++ process (src/app.cpp:52-57, 367); north_star shards whole
  * frames over the GPUs of a node with an RCCL all-gather as the only exchange step.  These calls are that step for a C++ host: RCCL

@@ -13,11 +13,13 @@
 #include <cassert>
 #include <cstring>
 #include <iterator>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 #include <tuple>
+#include <utility>
 
 #include "coalesce.h"
 #include "common.h"
@@ -162,7 +164,14 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
             matmul.galleryBegin(0, m_OUTPUT_D);
             matmul.galleryCommit();
         }
-        matmul.galleryAdd(embeddings, (int)names.size());
+        if (m_labelsSet && matmul.numRows() > 0) {  // the matcher carries labels (matchTopIdentities was used): the new rows bring theirs
+            std::vector<int> labels;
+            for (size_t i = 0; i < names.size(); ++i) labels.push_back(internLabel(names[i]));
+            matmul.galleryAddLabeled(embeddings, labels.data(), (int)names.size());
+        } else {
+            matmul.galleryAdd(embeddings, (int)names.size());
+            m_labelsSet = false;  // (an emptied gallery became unlabelled by the plain add)
+        }
         classNames.insert(classNames.end(), names.begin(), names.end());
         classCount += (int)names.size();
     }
@@ -179,10 +188,14 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         return (int)rows.size();
     }
     void initKnownEmbeds(int num) { matmul.galleryBegin(num, m_OUTPUT_D); }  // arcface.cpp:162
-    void initMatMul() { matmul.galleryCommit(); }                            // arcface.cpp:164
+    void initMatMul() {                                                       // arcface.cpp:164
+        matmul.galleryCommit();
+        forgetLabels();  // the commit replaced the gallery; matchTopIdentities sets the labels of the new one when it is next used
+    }
     void resetEmbeddings() {                                                  // arcface.cpp:233-236
         classCount = 0;
         classNames.clear();
+        forgetLabels();
     }
 
     // src/arcface.cpp:166-187
@@ -323,6 +336,27 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         }
         return std::make_tuple(names, sims);
     }
+    // Extension: the k best IDENTITIES per cropped face of the calling thread - up to k (className, similarity) pairs, best first, every
+    // class at most once with the similarity of its best row (the reference's gallery holds one row per FACE of a user: USER 1-N FACE,
+    // src/db.cpp:316-346, so the k best rows can be one user k times).  Entry 0 is matchTop1's answer.  classNames are interned into labels
+    // in first-appearance order and handed to the matcher on first use - a process that never asks pays nothing - and enrolEmbedding(s) /
+    // removeClass / initMatMul keep them in step from then on.  1 <= k <= 16; k exact scans per call, or one screened search (frt.h).
+    std::vector<std::vector<std::pair<std::string, float>>> matchTopIdentities(int k) {
+        State &s = st();
+        if (classNames.empty() || s.croppedFaces.empty()) throw "Feature matching: No faces in database or no faces found";
+        const int n = (int)s.croppedFaces.size();
+        ensureLabels();
+        std::vector<int> labels((size_t)n * k), idx((size_t)n * k);
+        std::vector<float> sims((size_t)n * k);
+        matmul.topkLabels(s.embeds.data(), n, k, labels.data(), idx.data(), sims.data());
+        std::vector<std::vector<std::pair<std::string, float>>> out((size_t)n);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < k; ++j) {
+                const int l = labels[(size_t)i * k + j];
+                if (l >= 0 && (size_t)l < m_labelNames.size()) out[(size_t)i].push_back(std::make_pair(m_labelNames[(size_t)l], sims[(size_t)i * k + j]));
+            }
+        return out;
+    }
     // src/arcface.cpp:219-231: drawing only, not on the hot path (not even called by app.cpp); real OpenCV required.
     void visualize(cv::Mat &image, std::vector<std::string> names, std::vector<float> sims) {
 #ifdef FRT_HAVE_OPENCV
@@ -350,6 +384,32 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
   private:
     // What a call leaves behind for the next call of the same request - per calling THREAD (include/frt/coalesce.h): the reference keeps
     // it in the object and shares the object between its server's threads.
+    // labels of matchTopIdentities: className <-> label, in first-appearance order; m_labelsSet: the matcher holds the labels of classNames
+    int internLabel(const std::string &name) {
+        std::map<std::string, int>::iterator it = m_labelOf.find(name);
+        if (it != m_labelOf.end()) return it->second;
+        const int l = (int)m_labelNames.size();
+        m_labelOf[name] = l;
+        m_labelNames.push_back(name);
+        return l;
+    }
+    void forgetLabels() {
+        m_labelsSet = false;
+        m_labelOf.clear();
+        m_labelNames.clear();
+    }
+    void ensureLabels() {
+        if (m_labelsSet) return;
+        forgetLabels();
+        std::vector<int> labels;
+        for (size_t i = 0; i < classNames.size(); ++i) labels.push_back(internLabel(classNames[i]));
+        matmul.setLabels(labels.data(), (int)labels.size());
+        m_labelsSet = true;
+    }
+    bool m_labelsSet = false;
+    std::map<std::string, int> m_labelOf;
+    std::vector<std::string> m_labelNames;
+
     struct State {
         std::vector<struct CroppedFace> croppedFaces;
         std::vector<float> embeds;

@@ -55,6 +55,29 @@ class MatMul {
         ensure();
         checkFrtStatus(frt_matcher_gallery_remove(h_, rows, n));
     }
+    // Extension: identities (frt.h "Top-k over IDENTITIES").  One label >= 0 per row; topkLabels then returns, per query, the k best
+    // IDENTITIES with the best row of each: labels / idx / sim are [embedCount x k], unused slots -1 / -1 / -inf.  init and galleryCommit
+    // drop the labels; galleryRemove closes them up with the rows; a labelled gallery grows through galleryAddLabeled[Dev] only.
+    void setLabels(const int *labels, int n) {
+        ensure();
+        checkFrtStatus(frt_matcher_set_labels(h_, labels, n));
+    }
+    void labelsInfo(int &identities, int &maxRowsPerLabel) {
+        ensure();
+        checkFrtStatus(frt_matcher_labels_info(h_, &identities, &maxRowsPerLabel));
+    }
+    void galleryAddLabeled(const float *rows, const int *labels, int n) {
+        ensure();
+        checkFrtStatus(frt_matcher_gallery_add_labeled(h_, rows, labels, n));
+    }
+    void galleryAddLabeledDev(const void *rowsDev, const int *labels, int n) {
+        ensure();
+        checkFrtStatus(frt_matcher_gallery_add_labeled_dev(h_, rowsDev, labels, n));
+    }
+    void topkLabels(const float *embeds, int embedCount, int k, int *labels, int *idx, float *sim) {
+        ensure();
+        checkFrtStatus(frt_matcher_topk_labels(h_, embeds, embedCount, k, labels, idx, sim));
+    }
     // Extension: store the gallery rows as fp16 on the device (next init / galleryBegin); see frt_matcher_set_storage
     void setStorageFp16(bool on) {
         ensure();
