@@ -7,7 +7,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 # ---- a deterministic "backed-up" pipeline (adaptive mode, frt_pipeline_set_pairing(p, -1)).  Whether a submit is held, merged with the next
-#      ones or shares a recogniser pass depends on event queries (frt_pipeline::backed_up / tickets_running / recogniser_busy).  Behind a closed
+#      ones or shares a recogniser pass depends on event queries (frt_pipeline::held_must_go / tickets_running / recogniser_busy).  Behind a closed
 #      gate - a spin kernel on the pipeline stream with frt_pipeline_set_input_sync on, so that every stage of the window waits for it - every
 #      query answers "still running", and the hold / merge decisions follow from the host rules alone; predict_window restates them.
 NBUF, NSLOT, MAXSUB, MAXG, HOLD_MIN = 12, 10, 4, 4, 5  # frt_pipeline.hpp
@@ -16,8 +16,8 @@ GATE_CYCLES = 200_000_000                            # ~0.1 s of device time (te
 
 def predict_window(sizes, max_frames, K, max_batch):
     """Calls and recogniser passes of one gated window: ``sizes[t]`` frames per submit ticket, submitted back to back while the gate holds,
-    then frt_pipeline_sync.  -> (calls, passes): a call is the list of its tickets, a pass the list of its calls.  The rules are
-    pipeline_submit_impl / pipeline_start_held (frt_pipeline.cpp) and run() / later_stages() (frt_pipeline.hpp): a ticket is held only when
+    then frt_pipeline_sync.  -> (calls, passes): a call is the list of its tickets, a pass the list of its calls.  The rules are frt_pipeline's
+    can_join / may_hold / held_must_go (frt_pipeline.hpp) as submit() and run() apply them (frt_pipeline.cpp): a ticket is held only when
     2 * n <= max_frames and at least HOLD_MIN tickets have their later stages queued; the next tickets join the held call while it has room
     and it goes out at MAXSUB tickets or once 2 * n > max_frames; a call of n frames waits for a partner pass while its faces fit twice
     (gcap >= 2), for up to gcap calls of the same n."""
@@ -566,6 +566,64 @@ def test_run_dev_orders_behind_the_callers_producer(frt, synth, blobs):
     for i in range(4):
         assert np.array_equal(np.frombuffer(d_res[i].cpu().numpy().tobytes(), frt.RESULT_DTYPE), want[i]), i
     pipe.set_input_sync(False)
+    pipe.set_stream(None)
+    pipe.close()
+    det.close()
+    rec.close()
+
+
+def test_refused_run_dev_leaves_nothing_for_the_next_call(frt, synth, blobs):
+    """A device-resident call that is refused (more frames than max_frames; with and without a ready event) has described itself in its own
+    request only: its buffers stay untouched, and the calls after it - device-resident, and through submit with embeddings and crops - give
+    what one ticket at a time with pairing off gives: boxes, rows and validity exactly, similarity within 2e-4 (the embedding's rounding)."""
+    import torch
+    dpath, _ = blobs("det")
+    rpath, _ = blobs("ir")
+    B, K, H, W = 4, 4, 320, 320
+    det = frt.RetinaFace(dpath, W, H, (3, H, W), B, K, 0.4, 0.6)
+    rec = frt.ArcFaceIR50(rpath, W, H, maxBatchSize=B * K, maxFacesPerScene=K)
+    rec.setGallery(synth.make_gallery(3000))
+    rec.initMatMul()
+    pipe = frt.Pipeline(det, rec, B)
+    batches = [torch.from_numpy(synth.make_frames(B, H, W, start=7 * i)).pin_memory() for i in range(2)]
+
+    def through_submit(i):
+        res = torch.zeros(B * K * frt.RESULT_DTYPE.itemsize, dtype=torch.uint8).pin_memory()
+        emb = torch.zeros(B * K, 512).pin_memory()
+        crops = torch.zeros(B * K, 112, 112, 3, dtype=torch.uint8).pin_memory()
+        pipe.wait(pipe.submit(batches[i].numpy(), res.numpy().view(frt.RESULT_DTYPE), emb.numpy(), crops.numpy()))
+        return res.numpy().view(frt.RESULT_DTYPE).copy(), emb.numpy().copy(), crops.numpy().copy()
+
+    def same(got, want):
+        return all(np.array_equal(got[k], want[k]) for k in ("x1", "y1", "x2", "y2", "frame", "match_idx", "valid")) and \
+            float(np.abs(got["match_sim"] - want["match_sim"]).max()) < 2e-4
+
+    pipe.set_pairing(0)
+    want = [through_submit(i) for i in range(2)]
+    assert sum(int(w[0]["valid"].sum()) for w in want) > 0
+    pipe.set_pairing(-1)
+    st = torch.cuda.Stream()
+    pipe.set_stream(st.cuda_stream)
+    d_big = torch.zeros(B + 1, H, W, 3, dtype=torch.uint8, device="cuda")
+    d_res_big = torch.zeros((B + 1) * K * frt.RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    ev = torch.cuda.Event()
+    ev.record(st)
+    for ready in (ev.cuda_event, None):
+        with pytest.raises(frt.FrtError) as e:
+            pipe.run_dev(d_big.data_ptr(), B + 1, d_res_big.data_ptr(), None, ready_event=ready)
+        assert e.value.code == frt.FRT_ERR_CAPACITY
+    d_frames = batches[0].cuda()
+    d_res = torch.zeros(B * K * frt.RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    pipe.run_dev(d_frames.data_ptr(), B, d_res.data_ptr(), None)
+    got = through_submit(1)
+    pipe.sync()
+    assert same(np.frombuffer(d_res.cpu().numpy().tobytes(), frt.RESULT_DTYPE), want[0][0])
+    assert not d_res_big.any()
+    assert same(got[0], want[1][0])
+    real = np.linalg.norm(want[1][1], axis=1) > 0.5
+    assert np.array_equal(got[1][~real], want[1][1][~real]) and float((got[1][real] * want[1][1][real]).sum(1).min(initial=1.0)) > 1 - 1e-5
+    assert np.array_equal(got[2], want[1][2])
     pipe.set_stream(None)
     pipe.close()
     det.close()
