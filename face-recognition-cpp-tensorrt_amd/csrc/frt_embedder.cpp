@@ -2,50 +2,15 @@
 // All device work is hand-written HIP (kernels_*.hip); there is no CPU fallback anywhere in this file: without a HIP
 // device every entry point that needs one fails with FRT_ERR_DEVICE.
 #include "frt_embedder.hpp"
+#include "frt_arc_pack.hpp"
 
 namespace {
 
-std::vector<uint16_t> conv_w_f16(const float *src, int cout, int cin, int ks) {
-    // [Cout][Cin][kh][kw] fp32 -> [Cout][kh][kw][Cin] fp16 (K index = tap*Cin + ci)
-    std::vector<uint16_t> w((size_t)cout * cin * ks * ks);
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < ks * ks; ++t) w[((size_t)co * ks * ks + t) * cin + ci] = frt::f32_to_f16(src[((size_t)co * cin + ci) * ks * ks + t]);
-    return w;
-}
+using frt::conv_w_f16;
+using frt::conv_w_f16_frag;
+using frt::conv1x1_w_f16_frag;
 std::vector<uint16_t> conv_w_f16(const frt::Blob &b, const std::string &name, int cout, int cin, int ks) {
     return conv_w_f16(b.get(name, (size_t)cout * cin * ks * ks).data, cout, cin, ks);
-}
-// 3x3 weights in the order the strip kernel's MFMA A fragments consume them: [Cout/32][Cin/64][tap][kk][lane = (k half, cout row)][8]
-// (kernels_arc.hip: conv_patch_kernel); a wave's load of one fragment is then one contiguous kilobyte.  Empty unless Cin % 64 == 0.
-// stride2: taps in the step order of the stride-2 strip kernel (kernels_arc_s2.hip: phase planes (odd,odd) (even,even) (odd,even) (even,odd)).
-std::vector<uint16_t> conv_w_f16_frag(const float *src, int cout, int cin, bool stride2 = false) {
-    if (cin % 64 || cout % 32) return {};
-    static const int s2_step_of_tap[9] = {0, 5, 1, 7, 4, 8, 2, 6, 3};  // inverse of the step -> tap table 0,2,6,8,4,1,7,3,5
-    std::vector<uint16_t> w((size_t)cout * cin * 9);
-    const int nch = cin / 64;
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci)
-            for (int t = 0; t < 9; ++t) {
-                const int blk = co >> 5, r = co & 31, ch = ci >> 6, kk = (ci & 63) >> 4, hi = (ci & 15) >> 3, e = ci & 7;
-                const int st = stride2 ? s2_step_of_tap[t] : t;
-                const size_t off = (((((size_t)blk * nch + ch) * 9 + st) * 4 + kk) * 64 + hi * 32 + r) * 8 + e;
-                w[off] = frt::f32_to_f16(src[((size_t)co * cin + ci) * 9 + t]);
-            }
-    return w;
-}
-// 1x1 shortcut weights [Cout][Cin] in the stride-2 strip kernel's fragment order [Cout/32][Cin/64][kk][lane = (k half, cout row)][8]
-std::vector<uint16_t> conv1x1_w_f16_frag(const frt::Blob &b, const std::string &name, int cout, int cin) {
-    if (cin % 64 || cout % 32) return {};
-    const float *src = b.get(name, (size_t)cout * cin).data;
-    std::vector<uint16_t> w((size_t)cout * cin);
-    const int nch = cin / 64;
-    for (int co = 0; co < cout; ++co)
-        for (int ci = 0; ci < cin; ++ci) {
-            const int blk = co >> 5, r = co & 31, ch = ci >> 6, kk = (ci & 63) >> 4, hi = (ci & 15) >> 3, e = ci & 7;
-            w[(((((size_t)blk * nch + ch) * 4 + kk) * 64) + hi * 32 + r) * 8 + e] = frt::f32_to_f16(src[(size_t)co * cin + ci]);
-        }
-    return w;
 }
 std::vector<float> vec_of(const frt::Blob &b, const std::string &name, size_t n) {
     const float *p = b.get(name, n).data;
@@ -131,11 +96,7 @@ void frt_embedder::build(const frt::Blob &b) {
         for (int co = 0; co < 64; ++co) sc[co] *= ds, bi[co] *= ds;
         in_s0 = arena.upload(sc);
         in_b0 = arena.upload(bi);
-        std::vector<uint16_t> wh(64 * 32, 0);  // matrix-core layout (kernels_arc_input.hip): BN folded, bias in tap slot 27
-        for (int co = 0; co < 64; ++co) {
-            for (int k = 0; k < 27; ++k) wh[co * 32 + k] = frt::f32_to_f16(src[co * 27 + k] * sc[co]);
-            wh[co * 32 + 27] = frt::f32_to_f16(bi[co]);
-        }
+        const std::vector<uint16_t> wh = frt::arc_input_w_f16(src, sc.data(), bi.data());  // matrix-core layout: BN folded
         in_wh = reinterpret_cast<half_t *>(arena.upload(wh));
         in_slope = arena.upload(vec_of(b, "input_layer.2.weight", 64));
         frt::bn_fold(b, "body.0.res_layer.0", 64, sc, bi);
@@ -177,7 +138,7 @@ void frt_embedder::build(const frt::Blob &b) {
             a.b2 = arena.upload(bi);
             if (a.cin != a.depth) {
                 a.wsc = reinterpret_cast<half_t *>(arena.upload(conv_w_f16(b, p + ".shortcut_layer.0.weight", a.depth, a.cin, 1)));
-                const std::vector<uint16_t> fs = conv1x1_w_f16_frag(b, p + ".shortcut_layer.0.weight", a.depth, a.cin);
+                const std::vector<uint16_t> fs = conv1x1_w_f16_frag(b.get(p + ".shortcut_layer.0.weight", (size_t)a.depth * a.cin).data, a.depth, a.cin);
                 if (!fs.empty()) a.wscf = reinterpret_cast<half_t *>(arena.upload(fs));
                 frt::bn_fold(b, p + ".shortcut_layer.1", a.depth, sc, bi);
                 for (int k = 0; k < a.depth; ++k) bi[k] *= ds;
@@ -201,16 +162,8 @@ void frt_embedder::build(const frt::Blob &b) {
     // output layer (model_irse.py:143-147): Linear over the NCHW flatten (index c*49 + hw) re-ordered to NHWC (hw*512 + c)
     {
         const float *src = b.get("output_layer.3.weight", (size_t)512 * 25088).data;
-        // ... and packed in MFMA-fragment order for kernels_arc_fc.hip: [output block o / 32][k step k / 16][lane = (k half, o % 32)][8]
-        std::vector<uint16_t> w((size_t)512 * 25088);
-        for (int o = 0; o < 512; ++o)
-            for (int c = 0; c < 512; ++c)
-                for (int hw = 0; hw < 49; ++hw) {
-                    const size_t k = (size_t)hw * 512 + c;
-                    const size_t off = ((((size_t)(o >> 5) * (25088 / 16) + (k >> 4)) * 64) + ((k >> 3) & 1) * 32 + (o & 31)) * 8 + (k & 7);
-                    w[off] = frt::f32_to_f16(src[(size_t)o * 25088 + (size_t)c * 49 + hw]);
-                }
-        wfc = reinterpret_cast<half_t *>(arena.upload(w));
+        // ... and packed in MFMA-fragment order for kernels_arc_fc.hip (frt_arc_pack.hpp)
+        wfc = reinterpret_cast<half_t *>(arena.upload(frt::fc_w_f16_frag(src)));
         fc_bias = arena.upload(vec_of(b, "output_layer.3.bias", 512));
         frt::bn_fold(b, "output_layer.4", 512, sc, bi);
         bn_s = arena.upload(sc);

@@ -1,0 +1,502 @@
+"""Cases and float64 reference for the recogniser's conv launches run one at a time (tests/cpp/arc_launch_check.cpp).  A generator and a
+reference, not a test: tests/test_arc_launch_cases.py (no GPU) and tests/test_gpu_arc_launches.py use it.
+
+Cases.  Every line of tests/golden/arc_conv_plan.txt whose description is conv1, conv2, conv2_scx, conv2_res or shortcut1x1 is run at the
+first batch size F of its range and, where the range has it, at first + 1: the smallest batches that select each instantiation, the second
+leaving the last strip ragged (an odd image for two-image strips, 113 faces for the 8-image groups of the compact 14x14 strips, 111 / 112 for
+the 7x7 ones).  The reference sees plain [Cout][Cin][ks][ks] weights and [F][H][W][C] tensors only; the harness packs with the product's
+packers, so a packing bug fails the same comparison.
+
+The operation (csrc/kernels_arc.hip, "Fused epilogues"), restated here in float64:
+    acc  = conv(x, w)                                  zero padding, stride and kernel size of the description
+    conv1        out0 = fp16(acc > 0 ? acc : acc * slope[c])
+    shortcut1x1  out0 = fp16(acc * s[c] + b[c])
+    conv2_res    out0 = fp16(acc * s[c] + b[c])
+    conv2        y = acc * s[c] + b[c] + sc[f][oh * sc_stride][ow * sc_stride][c];  out0 = fp16(y);  out1 = fp16(y * s'[c] + b'[c])
+    conv2_scx    y = acc * s[c] + b[c] + (conv1x1_stride2(scx, wsc) * ssc[c] + bsc[c]);  out0, out1 as above
+out1 is computed from the unrounded y.
+
+Class A, exact (every case).  x, the shortcut and w take values in {-1, 0, 1}, each non-zero with probability 1/4; BN scales come from
++-{1/2, 1/4, 1/8}, BN biases are distinct multiples of 1/4, PReLU slopes come from {1/2, 1/4, 1/8, 0, -1/4}, the next BN has scales in
++-{1/2, 1} and biases in multiples of 1/4.  Every product and partial sum is a small integer, exact in fp32 in any summation order and
+under any K split; every epilogue value is a multiple of 2^-4 below 2^7 in magnitude, exact in fp32 (with or without FMA contraction) and
+in fp16.  So out0 and out1 must equal the float64 reference BIT FOR BIT.  exact_case() asserts the premises on the reference: |acc| <
+2^24, power-of-two scales and quarter biases, epilogue magnitudes far below 2^20, every output unchanged by astype(float16).
+
+Class B, realistic (once per distinct (label, description) at first F + 1).  x ~ 0.5 N(0,1) rounded to fp16, w ~ N(0,1) / sqrt(K) in fp32
+(the packer rounds it; the reference rounds it with NumPy's round-to-nearest-even astype(float16)), BN / PReLU / shortcut values of the
+size the synthetic blobs have.  The tolerance is a running error bound carried through the reference, u = 2^-24:
+  * the sum: products of two fp16 numbers are exact in fp32 (22 significand bits), and K fp32 additions in ANY order (any K split, tap
+    order or tree) err by at most (K - 1) u sum|w||x| + O(u^2); the bound uses  e_acc = K u sum|w||x|.
+  * conv1: y = acc or acc * slope.  If the computed accumulator has the other sign both are within e_acc of zero, so
+    e_y = max(1, |slope|) e_acc + u |y|  (one fp32 multiplication).
+  * the BN epilogues add n terms (acc s, b, the shortcut, and for conv2_scx accsc ssc and bsc) with one fp32 rounding per operation, each
+    at most u times the magnitude of its result, which never exceeds  mag = sum of |term| + the propagated error
+    prop = e_acc |s| (+ e_accsc |ssc|).  So  e_y = prop + n_ops u mag  with n_ops = 2 (BN), 3 (+ shortcut), 5 (+ the shortcut conv's BN);
+    a contracted FMA only removes a rounding.
+  * out1: e_z = e_y |s'| + 2 u (|y s'| + |b'| + e_y |s'|).
+  * the store: rounding to fp16 adds half an fp16 ulp of the computed value, whose magnitude is at most |ref| + e:
+    half_ulp(v) = 2^(floor(log2 v) - 11), 2^-25 below 2^-14.
+The test asserts |kernel - fp16-unrounded reference| <= bound per element and prints max(err / bound); the ratios measured on the MI355X
+are recorded in DESIGN.md, not asserted."""
+import collections
+import os
+import zlib
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PLAN = os.path.join(ROOT, "tests", "golden", "arc_conv_plan.txt")
+
+SHAPES = [(64, 64, 112, 2), (64, 64, 56, 1), (64, 128, 56, 2), (128, 128, 28, 1), (128, 256, 28, 2), (256, 256, 14, 1), (256, 512, 14, 2), (512, 512, 7, 1)]
+DESC = ["conv1", "conv2", "conv2_scx", "conv2_se", "conv2_res", "shortcut1x1"]
+SELECTED = ("conv1", "conv2", "conv2_scx", "conv2_res", "shortcut1x1")
+U = 2.0 ** -24
+
+PlanLine = collections.namedtuple("PlanLine", "shape desc first last label")
+Case = collections.namedtuple("Case", "id shape desc F cls label")
+Geometry = collections.namedtuple("Geometry", "H Cin Ho Cout ks stride mode sc_kind sc_h sc_stride Csc")
+
+
+def plan_lines():
+    """The selected lines of the plan golden, in file order."""
+    out = []
+    for line in open(PLAN).read().splitlines():
+        chans, hw, s, desc, rng, rest = line.split(" ", 5)
+        cin, depth = (int(v) for v in chans.split("->"))
+        shape = SHAPES.index((cin, depth, int(hw.split("x")[0]), int(s[1:])))
+        label = rest[:rest.rindex(" scx=")]
+        first, last = (int(v) for v in rng[2:].split(".."))
+        if desc in SELECTED:
+            assert rest.endswith("se=0"), line  # the fused SE epilogue is never run alone
+            out.append(PlanLine(shape, desc, first, last, label))
+    return out
+
+
+def cases():
+    """Class A at the first F (and first + 1) of every selected line; class B once per distinct (label, description) at first + 1."""
+    out, seen = [], set()
+    for ln in plan_lines():
+        fs = [ln.first] + ([ln.first + 1] if ln.first + 1 <= ln.last else [])
+        for F in fs:
+            out.append(Case("s%d_%s_F%d_A" % (ln.shape, ln.desc, F), ln.shape, ln.desc, F, "A", ln.label))
+        if (ln.label, ln.desc) not in seen:
+            seen.add((ln.label, ln.desc))
+            out.append(Case("s%d_%s_F%d_B" % (ln.shape, ln.desc, fs[-1]), ln.shape, ln.desc, fs[-1], "B", ln.label))
+    return out
+
+
+def geometry(shape, desc):
+    """The launch description as frt_embedder::forward() fills it (tests/cpp/arc_conv_describe.hpp), for the reference."""
+    cin, depth, h, stride = SHAPES[shape]
+    ho = h // stride
+    has_sc_conv = cin != depth
+    if desc == "conv1":
+        return Geometry(h, cin, h, depth, 3, 1, "prelu", None, 0, 0, 0)
+    if desc == "shortcut1x1":
+        return Geometry(h, cin, ho, depth, 1, stride, "bn", None, 0, 0, 0)
+    if desc == "conv2_res":
+        return Geometry(h, depth, ho, depth, 3, stride, "bn", None, 0, 0, 0)
+    if desc == "conv2_scx":
+        return Geometry(h, depth, ho, depth, 3, stride, "add", "scx", h, 2, cin)
+    assert desc == "conv2"
+    if shape == 0 or has_sc_conv:  # the input layer wrote the even positions only / the 1x1 launch's output
+        return Geometry(h, depth, ho, depth, 3, stride, "add", "sc", ho, 1, 0)
+    return Geometry(h, depth, ho, depth, 3, stride, "add", "sc", h, stride, 0)
+
+
+def _rng(case_id, what):
+    return np.random.default_rng([zlib.crc32(case_id.encode()), zlib.crc32(what.encode())])
+
+
+def _ternary(r, shape):
+    v = r.integers(0, 8, size=shape, dtype=np.int8)
+    return ((v == 0).astype(np.int8) - (v == 1).astype(np.int8)).astype(np.float16)
+
+
+def inputs(case):
+    """dict of the arrays the harness reads: x, sc (fp16), w, wsc (fp32), p [6][Cout] (fp32: p0 p1 p2 p3 psc0 psc1)."""
+    g = geometry(case.shape, case.desc)
+    F, C = case.F, g.Cout
+    K = g.ks * g.ks * g.Cin
+    d = {}
+    p = np.zeros((6, C), np.float32)
+    r = lambda what: _rng(case.id, what)
+    if case.cls == "A":
+        d["x"] = _ternary(r("x"), (F, g.H, g.H, g.Cin))
+        d["w"] = _ternary(r("w"), (C, g.Cin, g.ks, g.ks)).astype(np.float32)
+        pow2 = lambda what, exps: (r(what).choice([-1.0, 1.0], C) * 2.0 ** r(what + "e").choice(exps, C)).astype(np.float32)
+        if g.mode == "prelu":
+            p[0] = r("slope").choice([0.5, 0.25, 0.125, 0.0, -0.25], C)
+        else:
+            p[0] = pow2("s", [-1, -2, -3])
+            p[1] = (r("b").permutation(C) - C // 2) / 4.0  # distinct: a vector shifted by a channel (or an octet) moves every value
+        if g.mode == "add":
+            p[2] = pow2("s2", [-1, 0])
+            p[3] = (r("b2").permutation(C) % 33 - 16) / 4.0
+        if g.sc_kind == "sc":
+            d["sc"] = _ternary(r("sc"), (F, g.sc_h, g.sc_h, C))
+        if g.sc_kind == "scx":
+            d["sc"] = _ternary(r("sc"), (F, g.H, g.H, g.Csc))
+            d["wsc"] = _ternary(r("wsc"), (C, g.Csc)).astype(np.float32)
+            p[4] = pow2("ssc", [-1, -2, -3])
+            p[5] = (r("bsc").permutation(C) % 65 - 32) / 4.0
+    else:
+        d["x"] = (0.5 * r("x").standard_normal((F, g.H, g.H, g.Cin), dtype=np.float32)).astype(np.float16)
+        d["w"] = (r("w").standard_normal((C, g.Cin, g.ks, g.ks), dtype=np.float32) / np.float32(np.sqrt(K))).astype(np.float32)
+        if g.mode == "prelu":
+            p[0] = 0.25 + 0.1 * r("slope").standard_normal(C)
+        else:
+            p[0] = r("s").uniform(0.5, 1.5, C) * r("sg").choice([-1.0, 1.0], C)
+            p[1] = 0.1 * r("b").standard_normal(C)
+        if g.mode == "add":
+            p[2] = r("s2").uniform(0.5, 1.5, C)
+            p[3] = 0.1 * r("b2").standard_normal(C)
+        if g.sc_kind == "sc":
+            d["sc"] = r("sc").standard_normal((F, g.sc_h, g.sc_h, C), dtype=np.float32).astype(np.float16)
+        if g.sc_kind == "scx":
+            d["sc"] = r("sc").standard_normal((F, g.H, g.H, g.Csc), dtype=np.float32).astype(np.float16)
+            d["wsc"] = (r("wsc").standard_normal((C, g.Csc), dtype=np.float32) / np.float32(np.sqrt(g.Csc))).astype(np.float32)
+            p[4] = r("ssc").uniform(0.5, 1.5, C)
+            p[5] = 0.1 * r("bsc").standard_normal(C)
+    d["p"] = p
+    return d
+
+
+def conv64(x, w, stride, pad, absolute=False, dtype=np.float64):
+    """Convolution of fp16-representable operands: x [F][H][W][Cin], w [Cout][Cin][ks][ks] -> float64 [F][Ho][Wo][Cout] (zero padding), as ks*ks
+    matrix products.  absolute: sum |w||x| instead.  dtype float32 is for the two uses that lose nothing by it: operands in {-1, 0, 1},
+    whose every partial sum is an integer of magnitude <= K < 2^24 and so exact in fp32 in any order (asserted here: the result IS the
+    float64 one), and the sum |w||x| of an error bound, which reference() widens by the 2^-10 this can cost."""
+    x = np.asarray(x, dtype)
+    w = np.asarray(w, dtype)
+    if dtype == np.float32 and not absolute:
+        assert all(np.abs(v).max() <= 1 and np.array_equal(v, np.rint(v)) for v in (x, w)) and w[0].size < 2 ** 24
+    if absolute:
+        x, w = np.abs(x), np.abs(w)
+    F, H, W, Cin = x.shape
+    Cout, _, ks, _ = w.shape
+    Ho, Wo = (H + 2 * pad - ks) // stride + 1, (W + 2 * pad - ks) // stride + 1
+    xp = np.zeros((F, H + 2 * pad, W + 2 * pad, Cin), dtype) if pad else x
+    if pad:
+        xp[:, pad:-pad, pad:-pad] = x
+    acc = np.zeros((F * Ho * Wo, Cout), dtype)
+    for kh in range(ks):
+        for kw in range(ks):
+            tap = xp[:, kh:kh + (Ho - 1) * stride + 1:stride, kw:kw + (Wo - 1) * stride + 1:stride]
+            acc += np.ascontiguousarray(tap).reshape(-1, Cin) @ np.ascontiguousarray(w[:, :, kh, kw].T)
+    return acc.reshape(F, Ho, Wo, Cout).astype(np.float64)
+
+
+def half_ulp16(v):
+    """Half an fp16 ulp at magnitude v (elementwise)."""
+    v = np.maximum(np.asarray(v, np.float64), 2.0 ** -14)
+    return 2.0 ** (np.floor(np.log2(v)) - 11)
+
+
+def reference(case, d, bound=False):
+    """float64 reference of one launch: dict with out0 (and out1), unrounded, plus 'acc' (and 'accsc'); bound=True adds 'bound0' / 'bound1', the
+    derived per-element error bounds of the fp16 results (module docstring)."""
+    g = geometry(case.shape, case.desc)
+    pad = 1 if g.ks == 3 else 0
+    w16 = d["w"].astype(np.float16)  # round-to-nearest-even, as the packer's conversion
+    p = d["p"].astype(np.float64)
+    gemm = np.float32 if case.cls == "A" else np.float64  # class A: exact either way (conv64)
+    acc = conv64(d["x"], w16, g.stride, pad, dtype=gemm)
+    out = {"acc": acc}
+    wide = 1 + 2.0 ** -10
+    if bound:
+        e_acc = g.ks * g.ks * g.Cin * U * wide * conv64(d["x"], w16, g.stride, pad, absolute=True, dtype=np.float32)
+    if g.mode == "prelu":
+        y = np.where(acc > 0, acc, acc * p[0])
+        out["out0"] = y
+        if bound:
+            e_y = np.maximum(1.0, np.abs(p[0])) * e_acc + U * np.abs(y)
+            out["bound0"] = e_y + half_ulp16(np.abs(y) + e_y)
+        return out
+    terms = [acc * p[0], np.broadcast_to(p[1], acc.shape)]
+    prop = e_acc * np.abs(p[0]) if bound else None
+    n_ops = 2
+    if g.sc_kind == "sc":
+        sc = np.asarray(d["sc"], np.float64)
+        n = (g.Ho - 1) * g.sc_stride + 1
+        terms.append(sc[:, 0:n:g.sc_stride, 0:n:g.sc_stride])
+        n_ops = 3
+    elif g.sc_kind == "scx":
+        wsc16 = d["wsc"].astype(np.float16)[:, :, None, None]
+        accsc = conv64(d["sc"], wsc16, 2, 0, dtype=gemm)
+        out["accsc"] = accsc
+        terms += [accsc * p[4], np.broadcast_to(p[5], acc.shape)]
+        n_ops = 5
+        if bound:
+            prop = prop + g.Csc * U * wide * conv64(d["sc"], wsc16, 2, 0, absolute=True, dtype=np.float32) * np.abs(p[4])
+    y = sum(terms)
+    out["terms"] = terms
+    out["out0"] = y
+    if bound:
+        e_y = prop + n_ops * U * (sum(np.abs(t) for t in terms) + prop)
+        out["bound0"] = e_y + half_ulp16(np.abs(y) + e_y)
+    if g.mode == "add":
+        z = y * p[2] + p[3]
+        out["out1"] = z
+        if bound:
+            e_z = e_y * np.abs(p[2]) + 2 * U * (np.abs(y * p[2]) + np.abs(p[3]) + e_y * np.abs(p[2]))
+            out["bound1"] = e_z + half_ulp16(np.abs(z) + e_z)
+    return out
+
+
+def exact_case(case, d, ref):
+    """The premises of class A, asserted on the reference alone; returns the outputs as fp16 arrays.  The accumulators are integers below 2^24
+    (conv64 asserted the operands).  Every scale is a power of two, so every epilogue product is exact, and every partial sum of the
+    epilogue, in any order, is a multiple of 2^-4 no larger than the sum of the terms' magnitudes: exact in fp32 while that stays below
+    2^20.  What is left is the store: every output must survive a conversion to fp16 unchanged."""
+    assert case.cls == "A"
+    p = d["p"].astype(np.float64)
+    for k in ("acc", "accsc"):
+        if k in ref:
+            assert np.abs(ref[k]).max() < 2 ** 24, (case.id, k)
+    for k in (0, 2, 4):
+        nz = np.abs(p[k][p[k] != 0])
+        assert np.array_equal(np.log2(nz), np.rint(np.log2(nz))) and (nz >= 2.0 ** -3).all(), (case.id, k)
+    for k in (1, 3, 5):
+        assert np.array_equal(p[k] * 4, np.rint(p[k] * 4)), (case.id, k)
+    mag = sum(np.abs(t).max() for t in ref.get("terms", [ref["acc"]]))
+    assert (mag + 1) * (np.abs(p[2]).max() + 1) + np.abs(p[3]).max() < 2 ** 20, case.id
+    out = {}
+    for k in ("out0", "out1"):
+        if k in ref:
+            out[k] = ref[k].astype(np.float16)
+            assert np.array_equal(out[k], ref[k]), (case.id, k, np.abs(ref[k]).max())
+    return out
+
+
+def write_case(dirname, case, d):
+    for k in ("x", "sc", "w", "wsc", "p"):
+        if k in d:
+            want = np.float16 if k in ("x", "sc") else np.float32
+            assert d[k].dtype == want, (k, d[k].dtype)
+            np.ascontiguousarray(d[k]).tofile(os.path.join(dirname, "%s.%s" % (case.id, k)))
+
+
+def write_manifest(dirname, case_list):
+    with open(os.path.join(dirname, "cases.txt"), "w") as f:
+        for c in case_list:
+            f.write("conv %s %d %d %d\n" % (c.id, c.shape, DESC.index(c.desc), c.F))
+
+
+def read_outputs(dirname, case):
+    """(dict out0 / out1 as fp16 arrays [F][Ho][Wo][Cout], changed slack halves, planned label) or None when the harness did not reach the case."""
+    res = {}
+    path = os.path.join(dirname, "results.txt")
+    if os.path.exists(path):
+        for line in open(path).read().splitlines():
+            cid, changed, label = line.split("\t")
+            res[cid] = (int(changed), label)
+    if case.id not in res:
+        return None
+    g = geometry(case.shape, case.desc)
+    outs = {}
+    for k in ("out0", "out1"):
+        f = os.path.join(dirname, "%s.%s" % (case.id, k))
+        if os.path.exists(f):
+            outs[k] = np.fromfile(f, np.float16).reshape(case.F, g.Ho, g.Ho, g.Cout)
+    return outs, res[case.id][0], res[case.id][1]
+
+
+def build_harness(outdir):
+    """Compiles tests/cpp/arc_launch_check.cpp (host C++ against libfrt.so, the way test_conv_plan.py compiles conv_plan_dump); returns the path."""
+    import subprocess
+    pkg = os.path.join(ROOT, "face-recognition-cpp-tensorrt_amd")
+    exe = os.path.join(str(outdir), "arc_launch_check")
+    # host side only, but with hipcc: frt_kernels.h uses clang's vector types
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", os.path.join(pkg, "csrc"),
+                           "-x", "c++", os.path.join(ROOT, "tests", "cpp", "arc_launch_check.cpp"), "-x", "none", "-o", exe, os.path.join(pkg, "libfrt.so"),
+                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib"])
+    return exe
+
+
+# ------------------------------------------------------------------------------------------------ the three small launches
+# Input layer (launch_arc_input), F = 1, 2, 3, on what the product feeds: (u8 - 127.5) * 2^-7, exact in fp16.  The kernel multiplies fp16
+# weights w * s0 (rounded once, by the packer) and adds the fp16-rounded bias as a 28th product, so with K = 28
+#     e_acc = K u (sum|wh||x| + |bh|),   v = prelu(acc): e_v = max(1, |slope|) e_acc + u |v|,   y = fp16(v),   z = fp16(v s1 + b1) as out1 above.
+# Output Linear (launch_fc_slices + launch_fc_finalize), F = 1, 2, 33, 129: z and w in {-1, 0, 1} make every slice sum an integer, exact in
+# fp32 - the 49 slice sums are compared bit for bit - and their sum `pre` exact.  What remains is fp32: t = pre + bias, m = t s, v = m + b
+# (three roundings: e_v = u (2 |t s| + |v|)), tot = sum v^2 over 512 outputs (one rounding per square, a tree of depth <= 16:
+# e_tot = sum(2 |v| e_v + e_v^2) + 17 u tot), nrm = sqrt(tot) (relative e_tot / (2 tot) + 2 u, allowing a one-ulp root), out = v / nrm (2 u,
+# allowing a one-ulp quotient):  e_out = e_v / nrm + |out| (e_tot / (2 tot) + 4 u).  About ten fp32 operations per value.  The row with
+# valid == 0 must be zeros.
+# Stand-alone SE tail (launch_se) at 56x56x64 and 7x7x512, F = 1 and 3, shortcut sampled at stride 1 and 2.  Class A: w2 = 0 makes every
+# gate exactly 1/2 (expf(-0) = 1), so with res and the shortcut in {-1, 0, 1}, s1 in +-{1/2, 1} and b1 in multiples of 1/4, y and z are
+# bit-exact.  Class B (real weights): the gate scratch [F][C] against float64, u = 2^-24:
+#     mean: se_pool_gate_kernel adds a pixel lane's share of a quarter image, then the NP = 2048 / C lanes, then the 4 quarters: no value
+#       passes more than D = ceil(ceil(HW / 4) / NP) + NP + 4 additions; one division     e_mean = u (D sum|res| / HW + |mean|)
+#     fc1 (se_fc1: `per` = C / (4096 / C) fmas per thread + a shuffle tree of log2(4096 / C)), ReLU (1-Lipschitz)
+#                                                            e_h = sum|w1| e_mean + (per + log2(4096 / C) + 1) u sum|w1||mean|
+#     fc2 (C/16 fmas)                                        e_o = sum|w2| e_h + (C/16 + 1) u sum|w2||h|
+#     sigmoid (slope <= 1/4) through the device's expf, an addition and a division: |gate - ref| <= e_o / 4 + SE_GATE_ALLOW
+# SE_GATE_ALLOW is not derived: it is 4 x the largest |gate - ref| seen on an MI355X over these cases (SE_GATE_SEEN = 4.1e-7, so 1.64e-6).  y and z of class B
+# are checked against res * (the gate the device wrote) + shortcut, two fp32 roundings and the store, so an error in the gate cannot hide an
+# error in the apply pass.  The arrival counters must be back at zero.
+SE_GATE_SEEN = 4.1e-7  # 7x7x512, F = 3; 6.7e-8 at 56x56x64
+SE_GATE_ALLOW = 4 * SE_GATE_SEEN
+WIDE = 1 + 2.0 ** -10
+
+Small = collections.namedtuple("Small", "kind id F H C sc_stride cls")
+
+
+def small_cases(kind):
+    if kind == "input":
+        return [Small("input", "input_F%d" % F, F, 112, 64, 0, "B") for F in (1, 2, 3)]
+    if kind == "fc":
+        return [Small("fc", "fc_F%d" % F, F, 7, 512, 0, "A") for F in (1, 2, 33, 129)]
+    assert kind == "se"
+    return [Small("se", "se_%dx%d_F%d_s%d_%s" % (H, C, F, st, cls), F, H, C, st, cls)
+            for H, C in ((56, 64), (7, 512)) for F in (1, 3) for st in (1, 2) for cls in ("A", "B")]
+
+
+def _bn_like(r, what, C):
+    return r(what + "s").uniform(0.5, 1.5, C) * r(what + "g").choice([-1.0, 1.0], C), 0.1 * r(what + "b").standard_normal(C)
+
+
+def small_inputs(c):
+    r = lambda what: _rng(c.id, what)
+    d = {}
+    if c.kind == "input":
+        u8 = r("x").integers(0, 256, size=(c.F, 3, 112, 112))
+        d["x"] = ((u8 - 127.5) * 2.0 ** -7).astype(np.float32)
+        d["w"] = (r("w").standard_normal((64, 27)) * np.sqrt(2.0 / 27)).astype(np.float32)
+        p = np.zeros((5, 64), np.float32)
+        p[0], p[1] = _bn_like(r, "bn0", 64)
+        p[2] = 0.25 + 0.1 * r("slope").standard_normal(64)
+        p[3], p[4] = _bn_like(r, "bn1", 64)
+        d["p"] = p
+    elif c.kind == "fc":
+        d["x"] = _ternary(r("x"), (c.F, 25088))
+        d["w"] = _ternary(_rng("fc", "w"), (512, 25088)).astype(np.float32)  # one matrix for all four batches
+        p = np.zeros((3, 512), np.float32)
+        p[0] = 0.05 * r("bias").standard_normal(512)
+        p[1], p[2] = _bn_like(r, "bn", 512)
+        d["p"] = p
+        d["valid"] = np.ones(c.F, np.int32)
+        if c.F > 1:
+            d["valid"][c.F - 1] = 0  # the last row: alone in its 32-face fragment at 33, alone in the second 128-face block at 129
+    else:
+        sh = c.H * c.sc_stride
+        R_ = c.C // 16
+        p = np.zeros((2, c.C), np.float32)
+        w1 = (r("w1").standard_normal((R_, c.C)) / np.sqrt(c.C)).astype(np.float32)
+        if c.cls == "A":
+            d["x"] = _ternary(r("x"), (c.F, c.H, c.H, c.C))
+            d["sc"] = _ternary(r("sc"), (c.F, sh, sh, c.C))
+            w2 = np.zeros((c.C, R_), np.float32)
+            p[0] = r("s1").choice([-1.0, 1.0], c.C) * 2.0 ** r("s1e").choice([-1, 0], c.C)
+            p[1] = (r("b1").permutation(c.C) - c.C // 2) / 4.0
+        else:
+            d["x"] = r("x").standard_normal((c.F, c.H, c.H, c.C), dtype=np.float32).astype(np.float16)
+            d["sc"] = r("sc").standard_normal((c.F, sh, sh, c.C), dtype=np.float32).astype(np.float16)
+            w1 *= 8  # pooled means of N(0,1) maps are small: keep the hidden layer and the gates away from 1/2
+            w2 = (r("w2").standard_normal((c.C, R_)) * 4 / np.sqrt(R_)).astype(np.float32)
+            p[0], p[1] = _bn_like(r, "bn", c.C)
+        d["w"] = np.concatenate([w1.reshape(-1), w2.reshape(-1)])
+        d["p"] = p
+    return d
+
+
+def _store_bound(ref, e):
+    return e + half_ulp16(np.abs(ref) + e)
+
+
+def small_reference(c, d, gate_dev=None):
+    """dict name -> (float64 reference, bound); bound None: bit for bit (compare with astype of the output's type)."""
+    p = d["p"].astype(np.float64)
+    if c.kind == "input":
+        wh = (d["w"] * d["p"][0][:, None]).astype(np.float16).reshape(64, 3, 3, 3)  # fp32 product, one rounding: the packer's
+        bh = d["p"][1].astype(np.float16).astype(np.float64)
+        x = np.ascontiguousarray(d["x"].transpose(0, 2, 3, 1)).astype(np.float16)
+        assert np.array_equal(x.astype(np.float32).transpose(0, 3, 1, 2), d["x"])
+        acc = conv64(x, wh, 1, 1) + bh
+        e_acc = 28 * U * WIDE * (conv64(x, wh, 1, 1, absolute=True, dtype=np.float32) + np.abs(bh))
+        v = np.where(acc > 0, acc, acc * p[2])
+        e_v = np.maximum(1.0, np.abs(p[2])) * e_acc + U * np.abs(v)
+        z = v * p[3] + p[4]
+        e_z = e_v * np.abs(p[3]) + 2 * U * (np.abs(v * p[3]) + np.abs(p[4]) + e_v * np.abs(p[3]))
+        return {"out0": (z, _store_bound(z, e_z)), "out1": (v[:, ::2, ::2], _store_bound(v, e_v)[:, ::2, ::2])}
+    if c.kind == "fc":
+        wn = d["w"].reshape(512, 512, 49).transpose(2, 1, 0)  # [hw][c][o]: the NHWC flatten the activations have
+        parts = np.matmul(d["x"].astype(np.float32).reshape(c.F, 49, 512).transpose(1, 0, 2), np.ascontiguousarray(wn))  # integers <= 512: exact
+        pre = parts.astype(np.float64).sum(0)
+        t = pre + p[0]
+        v = t * p[1] + p[2]
+        e_v = WIDE * U * (2 * np.abs(t * p[1]) + np.abs(v))
+        tot = (v * v).sum(1, keepdims=True)
+        e_tot = (2 * np.abs(v) * e_v + e_v * e_v).sum(1, keepdims=True) + 17 * U * tot
+        out = v / np.sqrt(tot)
+        e_out = WIDE * (e_v / np.sqrt(tot) + np.abs(out) * (e_tot / (2 * tot) + 4 * U))
+        out[d["valid"] == 0] = 0
+        e_out[d["valid"] == 0] = 0
+        return {"out0": (out, e_out), "out1": (parts.astype(np.float64), None)}
+    C, R_, HW = c.C, c.C // 16, c.H * c.H
+    res = d["x"].astype(np.float64)
+    n = (c.H - 1) * c.sc_stride + 1
+    sc = d["sc"].astype(np.float64)[:, 0:n:c.sc_stride, 0:n:c.sc_stride]
+    w1 = d["w"][:R_ * C].astype(np.float64).reshape(R_, C)
+    w2 = d["w"][R_ * C:].astype(np.float64).reshape(C, R_)
+    mean = res.reshape(c.F, HW, C).mean(1)
+    h = np.maximum(mean @ w1.T, 0)
+    gate = 1 / (1 + np.exp(-(h @ w2.T)))
+    NP, G = 2048 // C, 4096 // C
+    depth = -(-(-(-HW // 4)) // NP) + NP + 4
+    e_mean = WIDE * U * (depth * np.abs(res).reshape(c.F, HW, C).sum(1) / HW + np.abs(mean))
+    e_h = e_mean @ np.abs(w1).T + (max(C // G, 1) + int(np.log2(G)) + 1) * U * (np.abs(mean) @ np.abs(w1).T)
+    e_o = e_h @ np.abs(w2).T + (R_ + 1) * U * (h @ np.abs(w2).T)
+    out = {"gate": (gate, e_o / 4 + SE_GATE_ALLOW if c.cls == "B" else None)}
+    g = (gate if gate_dev is None else gate_dev.astype(np.float64))[:, None, None, :]
+    y = res * g + sc
+    z = y * p[0] + p[1]
+    if c.cls == "A":
+        assert np.all(gate == 0.5)
+        assert np.array_equal(y.astype(np.float16), y) and np.array_equal(z.astype(np.float16), z) and np.abs(y * p[0]).max() < 2 ** 11
+        out.update(out0=(y, None), out1=(z, None))
+    else:
+        e_y = WIDE * 2 * U * (np.abs(res * g) + np.abs(sc))
+        e_z = e_y * np.abs(p[0]) + 2 * U * (np.abs(y * p[0]) + np.abs(p[1]) + e_y * np.abs(p[0]))
+        out.update(out0=(y, _store_bound(y, e_y)), out1=(z, _store_bound(z, e_z)))
+    return out
+
+
+def write_small(dirname, c, d):
+    for k, v in d.items():
+        path = os.path.join(dirname, "%s.%s" % (c.id, k))
+        shared = os.path.join(dirname, "fc.w")
+        if c.kind == "fc" and k == "w":  # 51 MB, the same for every batch: written once, linked
+            if not os.path.exists(shared):
+                np.ascontiguousarray(v).tofile(shared)
+            os.link(shared, path)
+        else:
+            np.ascontiguousarray(v).tofile(path)
+
+
+def write_small_manifest(dirname, case_list):
+    with open(os.path.join(dirname, "cases.txt"), "w") as f:
+        for c in case_list:
+            f.write({"input": "input %s %d\n" % (c.id, c.F), "fc": "fc %s %d\n" % (c.id, c.F),
+                     "se": "se %s %d %d %d %d\n" % (c.id, c.H, c.C, c.F, c.sc_stride)}[c.kind])
+
+
+def read_small_outputs(dirname, c):
+    """(dict of output arrays, changed slack elements / counters, launcher name) or None when the harness did not reach the case."""
+    res = {}
+    path = os.path.join(dirname, "results.txt")
+    if os.path.exists(path):
+        res = {ln.split("\t")[0]: ln.split("\t") for ln in open(path).read().splitlines()}
+    if c.id not in res:
+        return None
+    rd = lambda k, t, shape: np.fromfile(os.path.join(dirname, "%s.%s" % (c.id, k)), t).reshape(shape)
+    if c.kind == "input":
+        outs = {"out0": rd("out0", np.float16, (c.F, 112, 112, 64)), "out1": rd("out1", np.float16, (c.F, 56, 56, 64))}
+    elif c.kind == "fc":
+        outs = {"out0": rd("out0", np.float32, (c.F, 512)), "out1": rd("out1", np.float32, (49, c.F, 512))}
+    else:
+        outs = {k: rd(k, np.float16, (c.F, c.H, c.H, c.C)) for k in ("out0", "out1")}
+        outs["gate"] = rd("gate", np.float32, (c.F, c.C))
+    return outs, int(res[c.id][1]), res[c.id][2]

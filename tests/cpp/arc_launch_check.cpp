@@ -1,0 +1,332 @@
+// Runs the recogniser's launches ONE AT A TIME, outside any network.  Convs: for each case of a list written by tests/arc_launch_ref.py it fills
+// ConvMfmaArgs through the same describe() the plan golden is enumerated with (arc_conv_describe.hpp), packs the case's plain fp32 weights with
+// the product's own packers (csrc/frt_arc_pack.hpp), calls conv_plan() and launch_conv_mfma() once and writes out0 / out1 and the planned label
+// back.  tests/test_gpu_arc_launches.py compares them with a float64 restatement of the operation that only ever sees [Cout][Cin][3][3]
+// weights.
+//
+//   arc_launch_check DIR          run every case of DIR/cases.txt on the current device; stops at the first HIP error (exit 1)
+//   arc_launch_check --plan DIR   print "<id>\t<label>" per case; no HIP call (runs on a machine without a device)
+//
+// DIR/cases.txt: one line per case.  "conv <id> <unit shape 0..7> <description 0..5> <F>" is a conv launch, with the little-endian arrays
+//   <id>.x    fp16 [F][H][W][Cin]                   <id>.w    fp32 [Cout][Cin][ks][ks]
+//   <id>.sc   fp16 shortcut tensor, or the raw unit input of the fused 1x1 shortcut conv (absent: the launch has none)
+//   <id>.wsc  fp32 [Cout][Csc] (fused shortcut conv only)
+//   <id>.p    fp32 [6][Cout]: p0 p1 p2 p3 psc0 psc1
+// Written: <id>.out0 / <id>.out1 (fp16, the logical tensors) and one line "<id>\t<changed slack elements>\t<label>" in DIR/results.txt.
+// The three small launches go through the same buffers and checks (label: the launcher's name):
+//   "input <id> <F>"                   launch_arc_input: <id>.x fp32 [F][3][112][112], <id>.w fp32 [64][27], <id>.p fp32 [5][64] s0 b0 slope s1 b1
+//                                      -> out0 = z [F][112][112][64], out1 = y [F][56][56][64] (the even positions)
+//   "fc <id> <F>"                      launch_fc_slices + launch_fc_finalize: <id>.x fp16 [F][25088] (NHWC flatten), <id>.w fp32 [512][25088] (NCHW
+//                                      flatten, as the blob has it), <id>.p fp32 [3][512] bias s b, <id>.valid int32 [F]
+//                                      -> out0 = fp32 [F][512], out1 = the slice sums fp32 [49][F][512]
+//   "se <id> <H> <C> <F> <sc_stride>"  launch_se: <id>.x fp16 res [F][H][H][C], <id>.sc fp16 [F][H*sc_stride][H*sc_stride][C], <id>.w fp32 w1 [C/16][C]
+//                                      then w2 [C][C/16], <id>.p fp32 [2][C] s1 b1 -> out0 = y, out1 = z, <id>.gate fp32 [F][C]; arrival counters
+//                                      that are not back at zero count as changed slack
+//
+// Buffers are sized the way frt_embedder::alloc_act_set sizes them for max_batch = F (the kernels were written against that sizing: compact
+// strips compute pixel slots of images that do not exist), each with 1 MiB in front.  Inputs are filled with a large finite fp16 value outside
+// the logical tensor - a kernel that accumulated slack into a stored value cannot pass the comparison - and outputs with a fixed bit pattern,
+// which must still be there after the launch everywhere outside the logical tensor.
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "arc_conv_describe.hpp"
+#include "frt_arc_pack.hpp"
+#include "frt_kernels.h"
+
+namespace {
+
+using namespace arc_describe;
+
+constexpr size_t kMarginBytes = (size_t)1 << 20;  // in front of every activation buffer
+constexpr uint16_t kInFill = 0x7800;              // 32768.0: large, finite
+constexpr uint16_t kOutFill = 0x5a5a;
+constexpr uint32_t kInFill32 = 0x7149f2ca;        // 1e30f
+constexpr uint32_t kOutFill32 = 0x5a5a5a5a;
+
+[[noreturn]] void die(const std::string &msg) {
+    fprintf(stderr, "arc_launch_check: %s\n", msg.c_str());
+    exit(1);
+}
+void hipchk(hipError_t e, const char *what, const std::string &id) {
+    if (e != hipSuccess) die("case " + id + ": " + what + ": " + hipGetErrorString(e));
+}
+#define HIPCHK(x) hipchk((x), #x, id)
+
+template <class T>
+std::vector<T> read_file(const std::string &path, size_t n, bool optional = false) {
+    FILE *f = fopen(path.c_str(), "rb");
+    if (!f) {
+        if (optional) return {};
+        die("cannot open " + path);
+    }
+    std::vector<T> v(n);
+    const size_t got = fread(v.data(), sizeof(T), n, f);
+    char extra;
+    const bool more = fread(&extra, 1, 1, f) == 1;
+    fclose(f);
+    if (got != n || more) die(path + ": expected " + std::to_string(n) + " elements");
+    return v;
+}
+void write_file(const std::string &path, const void *p, size_t bytes) {
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f || fwrite(p, 1, bytes, f) != bytes) die("cannot write " + path);
+    fclose(f);
+}
+
+struct Case {
+    std::string kind, id;
+    int shape = 0, d = 0, F = 0, H = 0, C = 0, sc_stride = 0;
+};
+std::vector<Case> read_cases(const std::string &dir) {
+    FILE *f = fopen((dir + "/cases.txt").c_str(), "r");
+    if (!f) die("cannot open " + dir + "/cases.txt");
+    std::vector<Case> cs;
+    char kind[32], id[256];
+    while (fscanf(f, "%31s %255s", kind, id) == 2) {
+        Case c;
+        c.kind = kind;
+        c.id = id;
+        bool ok = false;
+        if (c.kind == "conv")
+            ok = fscanf(f, "%d %d %d", &c.shape, &c.d, &c.F) == 3 && c.shape >= 0 && c.shape < kNumShapes && c.d >= 0 && c.d < kNumDesc;
+        else if (c.kind == "input" || c.kind == "fc")
+            ok = fscanf(f, "%d", &c.F) == 1;
+        else if (c.kind == "se")
+            ok = fscanf(f, "%d %d %d %d", &c.H, &c.C, &c.F, &c.sc_stride) == 4 && c.H >= 1 && c.H <= 56 && c.C >= 64 && c.C <= 512 && c.C % 64 == 0 &&
+                 (size_t)c.H * c.H * c.C <= 56 * 56 * 64 && (c.sc_stride == 1 || c.sc_stride == 2);
+        if (!ok || c.F < 1 || c.F > 256) die("bad case line for " + c.id);
+        cs.push_back(c);
+    }
+    fclose(f);
+    return cs;
+}
+
+// a buffer of `cap` elements (T = uint16_t: halves, uint32_t: floats / ints) behind the margin, filled with `fill`, its first `logical` elements being the tensor
+template <class T>
+struct Buf {
+    T *base = nullptr;
+    size_t cap = 0, logical = 0;
+    T fill = 0;
+    static constexpr size_t margin = kMarginBytes / sizeof(T);
+    template <class P>
+    P *ptr() const { return reinterpret_cast<P *>(base + margin); }
+};
+typedef Buf<uint16_t> ActBuf;
+
+struct DeviceCase {
+    std::string id;
+    std::vector<void *> owned;
+    ~DeviceCase() {
+        for (void *p : owned) (void)hipFree(p);
+    }
+    template <class T>
+    Buf<T> buf(size_t cap, size_t logical, T fill, const void *init) {
+        if (logical > cap) die("case " + id + ": a tensor of " + std::to_string(logical) + " elements does not fit the product's buffer of " + std::to_string(cap));
+        Buf<T> b;
+        b.cap = cap;
+        b.logical = logical;
+        b.fill = fill;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&b.base), (b.margin + cap) * sizeof(T)));
+        owned.push_back(b.base);
+        if (sizeof(T) == 2)
+            HIPCHK(hipMemsetD16(reinterpret_cast<hipDeviceptr_t>(b.base), (unsigned short)fill, b.margin + cap));
+        else
+            HIPCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b.base), (int)fill, b.margin + cap));
+        if (init) HIPCHK(hipMemcpy(b.base + b.margin, init, logical * sizeof(T), hipMemcpyHostToDevice));
+        return b;
+    }
+    ActBuf act(size_t cap, size_t logical, uint16_t fill, const std::vector<uint16_t> *init) { return buf<uint16_t>(cap, logical, fill, init ? init->data() : nullptr); }
+    template <class T>
+    T *upload(const std::vector<T> &v) {
+        T *d = nullptr;
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), v.size() * sizeof(T)));
+        owned.push_back(d);
+        HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+        return d;
+    }
+    // the logical tensor -> `path` (empty: not kept); returns the number of elements outside it that no longer hold the fill pattern
+    template <class T>
+    size_t download(const Buf<T> &b, const std::string &path) {
+        std::vector<T> h(b.margin + b.cap);
+        HIPCHK(hipMemcpy(h.data(), b.base, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+        if (!path.empty()) write_file(path, h.data() + b.margin, b.logical * sizeof(T));
+        size_t changed = 0;
+        for (size_t i = 0; i < b.margin; ++i) changed += h[i] != b.fill;
+        for (size_t i = b.margin + b.logical; i < h.size(); ++i) changed += h[i] != b.fill;
+        return changed;
+    }
+};
+
+void run_conv(const std::string &dir, const Case &c, FILE *results) {
+    const Shape &u = kShapes[c.shape];
+    ConvMfmaArgs a;
+    if (!describe(u, c.shape == 0, c.d, c.F, a)) die("case " + c.id + ": the unit has no such launch");
+    if (c.d == 3) die("case " + c.id + ": the fused SE epilogue is not run alone");
+    const std::string pre = dir + "/" + c.id;
+    DeviceCase dc;
+    dc.id = c.id;
+    const std::string &id = c.id;
+    const size_t F = (size_t)c.F, big = F * 112 * 112 * 64, sc_cap = F * 28 * 28 * 128;  // alloc_act_set: Y / Z / T, and SC
+    const bool has_sc_conv = u.cin != u.depth;
+
+    const size_t nx = F * a.H * a.W * a.Cin, nout = F * a.Ho * a.Wo * a.Cout, nw = (size_t)a.Cout * a.Cin * a.ks * a.ks;
+    const std::vector<uint16_t> x = read_file<uint16_t>(pre + ".x", nx);
+    const std::vector<float> w = read_file<float>(pre + ".w", nw);
+    const std::vector<float> par = read_file<float>(pre + ".p", (size_t)6 * a.Cout);
+    a.x = dc.act(big, nx, kInFill, &x).ptr<half_t>();
+    a.w = reinterpret_cast<half_t *>(dc.upload(frt::conv_w_f16(w.data(), a.Cout, a.Cin, a.ks)));
+    if (a.wf) a.wf = reinterpret_cast<half_t *>(dc.upload(frt::conv_w_f16_frag(w.data(), a.Cout, a.Cin)));
+    // build(): the 64 -> 64 stride-2 layer's kernel walks the taps in tap order
+    if (a.wf2) a.wf2 = reinterpret_cast<half_t *>(dc.upload(frt::conv_w_f16_frag(w.data(), a.Cout, a.Cin, u.depth != 64)));
+    float *dpar = dc.upload(par);
+    if (a.p0) a.p0 = dpar;
+    if (a.p1) a.p1 = dpar + a.Cout;
+    if (a.p2) a.p2 = dpar + 2 * a.Cout;
+    if (a.p3) a.p3 = dpar + 3 * a.Cout;
+    if (a.sc) {  // the unit's input (Y), or the 1x1 launch's output (SC) in the units that have a shortcut conv
+        const size_t nsc = F * a.sc_h * a.sc_w * a.Cout;
+        const std::vector<uint16_t> sc = read_file<uint16_t>(pre + ".sc", nsc);
+        a.sc = dc.act(has_sc_conv ? sc_cap : big, nsc, kInFill, &sc).ptr<half_t>();
+    }
+    if (a.scx) {
+        const size_t nsc = F * a.H * a.W * a.Csc;
+        const std::vector<uint16_t> sc = read_file<uint16_t>(pre + ".sc", nsc);
+        const std::vector<float> wsc = read_file<float>(pre + ".wsc", (size_t)a.Cout * a.Csc);
+        a.scx = dc.act(big, nsc, kInFill, &sc).ptr<half_t>();
+        a.wscf = reinterpret_cast<half_t *>(dc.upload(frt::conv1x1_w_f16_frag(wsc.data(), a.Cout, a.Csc)));
+        a.psc0 = dpar + 4 * a.Cout;
+        a.psc1 = dpar + 5 * a.Cout;
+    }
+    a.zeros = reinterpret_cast<half_t *>(dc.upload(std::vector<uint16_t>(256, 0)));
+    if (a.se_pool) {  // conv2_res is described with the embedder's SE scratch: real memory, sized as alloc_act_set sizes it
+        float *pool = dc.upload(std::vector<float>(F * 512 * 4 + 2 * F, 0.f));
+        a.se_pool = pool;
+        a.se_counter = reinterpret_cast<int *>(pool + F * 512 * 4);
+        a.se_flag_off = c.F;
+        a.se_w1 = dc.upload(std::vector<float>((size_t)a.Cout / 16 * a.Cout, 0.f));
+        a.se_w2 = dc.upload(std::vector<float>((size_t)a.Cout * (a.Cout / 16), 0.f));
+        a.se_error = dc.upload(std::vector<int>(1, 0));
+    }
+    ActBuf o0, o1;
+    o0 = dc.act(c.d == 5 ? sc_cap : big, nout, kOutFill, nullptr);
+    a.out0 = o0.ptr<half_t>();
+    if (a.out1) {
+        o1 = dc.act(big, nout, kOutFill, nullptr);
+        a.out1 = o1.ptr<half_t>();
+    }
+
+    const ConvPlan plan = conv_plan(a);
+    launch_conv_mfma(a, plan, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipGetLastError());
+    size_t changed = dc.download(o0, pre + ".out0");
+    if (o1.base) changed += dc.download(o1, pre + ".out1");
+    fprintf(results, "%s\t%zu\t%s\n", c.id.c_str(), changed, plan.label);
+}
+
+
+void finish(DeviceCase &dc, const std::string &id) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipGetLastError());
+}
+
+void run_input(const std::string &dir, const Case &c, FILE *results) {
+    const std::string pre = dir + "/" + c.id, &id = c.id;
+    DeviceCase dc;
+    dc.id = c.id;
+    const size_t F = (size_t)c.F, big = F * 112 * 112 * 64;
+    const std::vector<float> x = read_file<float>(pre + ".x", F * 3 * 112 * 112), w = read_file<float>(pre + ".w", 64 * 27), par = read_file<float>(pre + ".p", 5 * 64);
+    std::vector<float> wt(27 * 64);  // build(): [27][64] for the scalar kernel
+    for (int co = 0; co < 64; ++co)
+        for (int k = 0; k < 27; ++k) wt[k * 64 + co] = w[co * 27 + k];
+    const Buf<uint32_t> dx = dc.buf<uint32_t>(x.size(), x.size(), kInFill32, x.data());  // d_in has no slack
+    float *dpar = dc.upload(par);
+    const ActBuf z = dc.act(big, big, kOutFill, nullptr), y = dc.act(big, big / 4, kOutFill, nullptr);  // Z[0], Y[0]
+    ArcInputArgs a{dx.ptr<float>(), dc.upload(wt), dpar, dpar + 64, dpar + 128, dpar + 192, dpar + 256, y.ptr<half_t>(), z.ptr<half_t>(), c.F, 112, 112,
+                   reinterpret_cast<half_t *>(dc.upload(frt::arc_input_w_f16(w.data(), par.data(), par.data() + 64)))};
+    launch_arc_input(a, nullptr);
+    finish(dc, id);
+    const size_t changed = dc.download(z, pre + ".out0") + dc.download(y, pre + ".out1");
+    fprintf(results, "%s\t%zu\tlaunch_arc_input\n", c.id.c_str(), changed);
+}
+
+void run_fc(const std::string &dir, const Case &c, FILE *results) {
+    const std::string pre = dir + "/" + c.id, &id = c.id;
+    DeviceCase dc;
+    dc.id = c.id;
+    const size_t F = (size_t)c.F;
+    const std::vector<uint16_t> zin = read_file<uint16_t>(pre + ".x", F * 25088);
+    const std::vector<float> w = read_file<float>(pre + ".w", (size_t)512 * 25088), par = read_file<float>(pre + ".p", 3 * 512);
+    const std::vector<int> valid = read_file<int>(pre + ".valid", F);
+    const ActBuf z = dc.act(F * 112 * 112 * 64, zin.size(), kInFill, &zin);
+    const Buf<uint32_t> partial = dc.buf<uint32_t>(49 * F * 512, 49 * F * 512, kOutFill32, nullptr), out = dc.buf<uint32_t>(F * 512, F * 512, kOutFill32, nullptr);
+    float *dpar = dc.upload(par);
+    launch_fc_slices(z.ptr<half_t>(), reinterpret_cast<half_t *>(dc.upload(frt::fc_w_f16_frag(w.data()))), c.F, partial.ptr<float>(), nullptr);
+    launch_fc_finalize(partial.ptr<float>(), 49, c.F, dpar, dpar + 512, dpar + 1024, dc.upload(valid), out.ptr<float>(), nullptr);
+    finish(dc, id);
+    const size_t changed = dc.download(out, pre + ".out0") + dc.download(partial, pre + ".out1");
+    fprintf(results, "%s\t%zu\tlaunch_fc\n", c.id.c_str(), changed);
+}
+
+void run_se(const std::string &dir, const Case &c, FILE *results) {
+    const std::string pre = dir + "/" + c.id, &id = c.id;
+    DeviceCase dc;
+    dc.id = c.id;
+    const size_t F = (size_t)c.F, C = c.C, n = F * c.H * c.H * C, big = F * 112 * 112 * 64, sh = (size_t)c.H * c.sc_stride;
+    const std::vector<uint16_t> res = read_file<uint16_t>(pre + ".x", n), sc = read_file<uint16_t>(pre + ".sc", F * sh * sh * C);
+    const std::vector<float> w = read_file<float>(pre + ".w", 2 * (C / 16) * C), par = read_file<float>(pre + ".p", 2 * C);
+    // alloc_act_set: RES, Y (the shortcut), Y / Z of the other parity, se_pool with the arrival counters and flags behind it, se_gate
+    const ActBuf dres = dc.act(F * 56 * 56 * 64, n, kInFill, &res), dsc = dc.act(big, sc.size(), kInFill, &sc);
+    const ActBuf y = dc.act(big, n, kOutFill, nullptr), z = dc.act(big, n, kOutFill, nullptr);
+    const Buf<uint32_t> gate = dc.buf<uint32_t>(F * 512, F * C, kOutFill32, nullptr);
+    float *pool = dc.upload(std::vector<float>(F * 512 * 4 + 2 * F, 0.f));
+    int *counter = reinterpret_cast<int *>(pool + F * 512 * 4);
+    float *dw = dc.upload(w), *dpar = dc.upload(par);
+    SeArgs a{dres.ptr<half_t>(), dw, dw + (C / 16) * C, dsc.ptr<half_t>(), (int)sh, (int)sh, c.sc_stride, dpar, dpar + C, y.ptr<half_t>(), z.ptr<half_t>(), pool, gate.ptr<float>(),
+             c.F, c.H, c.H, c.C, counter};
+    launch_se(a, nullptr);
+    finish(dc, id);
+    size_t changed = dc.download(y, pre + ".out0") + dc.download(z, pre + ".out1") + dc.download(gate, pre + ".gate");
+    std::vector<int> cnt(2 * F);
+    HIPCHK(hipMemcpy(cnt.data(), counter, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
+    for (int v : cnt) changed += v != 0;  // the next launch on this scratch counts from zero
+    fprintf(results, "%s\t%zu\tlaunch_se\n", c.id.c_str(), changed);
+}
+
+void run_case(const std::string &dir, const Case &c, FILE *results) {
+    if (c.kind == "conv") run_conv(dir, c, results);
+    if (c.kind == "input") run_input(dir, c, results);
+    if (c.kind == "fc") run_fc(dir, c, results);
+    if (c.kind == "se") run_se(dir, c, results);
+    fflush(results);
+}
+
+}  // namespace
+
+int main(int argc, char **argv) {
+    const bool plan_only = argc == 3 && std::string(argv[1]) == "--plan";
+    if (argc != 2 && !plan_only) die("usage: arc_launch_check [--plan] DIR");
+    const std::string dir = argv[argc - 1];
+    const std::vector<Case> cases = read_cases(dir);
+    if (plan_only) {
+        for (const Case &c : cases) {
+            ConvMfmaArgs a;
+            if (c.kind != "conv") continue;  // only the convs are planned
+            if (!describe(kShapes[c.shape], c.shape == 0, c.d, c.F, a)) die("case " + c.id + ": the unit has no such launch");
+            printf("%s\t%s\n", c.id.c_str(), conv_plan(a).label);
+        }
+        return 0;
+    }
+    FILE *results = fopen((dir + "/results.txt").c_str(), "w");
+    if (!results) die("cannot write " + dir + "/results.txt");
+    for (const Case &c : cases) run_case(dir, c, results);
+    fclose(results);
+    return 0;
+}
