@@ -155,6 +155,9 @@ ABI = {
     "frt_jpeg_encode_batch": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "frt_jpeg_write_jfif": (_i, [_i, _i, _i, _vp, _vp, _sz, _vp]),
     "frt_base64_encode": (_sz, [_vp, _sz, _vp, _sz]),
+    "frt_preprocess_faces": (_i, [_vp, _i, _vp, _vp, _i]),
+    "frt_embedder_embed_faces": (_i, [_vp, _vp, _i, _vp, _vp]),
+    "frt_embedder_enrol_faces": (_i, [_vp, _vp, _vp, _i, _vp, _vp, ctypes.POINTER(_i)]),
     "frt_profile_enable": (_i, [_i]),
     "frt_profile_collect": (_i, [_vp, _sz, _vp, _vp, _i]),
 }
@@ -624,6 +627,41 @@ def alignFaces(frame, landmarks, device=0):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# face images instead of frames (frt_preprocess_faces / frt_embedder_embed_faces / frt_embedder_enrol_faces)
+# ----------------------------------------------------------------------------------------------------------------------
+class FaceImage(ctypes.Structure):  # == frt_face_image
+    _fields_ = [("bgr", _vp), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32), ("row_stride", _sz)]
+
+
+def _face_images(faces):
+    """list of H x W x 3 u8 arrays -> (frt_face_image array, the arrays it points into).  A view whose pixels are contiguous within a row is
+    passed with its row stride, not copied."""
+    keep = []
+    for f in faces:
+        a = np.asarray(f)
+        if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+            raise ValueError("face images are H x W x 3 uint8 arrays")
+        if a.shape[0] and a.shape[1] and (a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < a.shape[1] * 3):
+            a = np.ascontiguousarray(a)
+        keep.append(a)
+    arr = (FaceImage * max(len(keep), 1))()
+    for i, a in enumerate(keep):
+        arr[i] = FaceImage(a.ctypes.data, a.shape[0], a.shape[1], a.strides[0])
+    return arr, keep
+
+
+def preprocessFaces(faces, device=0):
+    """``cv::resize(face, face, Size(112, 112))`` where the size differs (src/app.cpp:84-87, :152-155, :255-258: default INTER_LINEAR) +
+    ``preprocessFace`` for a list of face images of any sizes, one launch -> (u8 BGR [n][112][112][3], float32 planar RGB [n][3][112][112])."""
+    arr, keep = _face_images(faces)
+    n = len(keep)
+    crops = np.zeros((n, 112, 112, 3), np.uint8)
+    chw = np.zeros((n, 3, 112, 112), np.float32)
+    _check(lib.frt_preprocess_faces(arr, n, _ptr(crops), _ptr(chw), device))
+    return crops, chw
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # class ArcFaceIR50 (src/arcface.h)
 # ----------------------------------------------------------------------------------------------------------------------
 class ArcFaceIR50:
@@ -760,6 +798,44 @@ class ArcFaceIR50:
         self._embeds = embeds
         self.croppedFaces = [dict(face=crops[i], x1=int(b["x1"]), y1=int(b["y1"]), x2=int(b["x2"]), y2=int(b["y2"])) for i, b in enumerate(boxes)]
         return embeds
+
+    # face images instead of frames: /recognize (src/app.cpp:243-287), /insert/face with api_imgIsCropped (:148-162), gen (:69-99)
+    def forwardFaces(self, faces):
+        """``forward`` for pre-cropped face images (a list of H x W x 3 u8 arrays of any sizes): resize to 112 x 112 + preprocessFace on the
+        device, full recogniser passes while the next images upload.  Leaves what ``forward`` leaves: the embeddings, and ``croppedFaces``
+        with the resized face and the box 0, 0, 112, 112 that /recognize builds (src/app.cpp:266-267)."""
+        arr, keep = _face_images(faces)
+        n = len(keep)
+        embeds = np.zeros((n, self.outputDim), np.float32)
+        crops = np.zeros((n, 112, 112, 3), np.uint8)
+        _check(lib.frt_embedder_embed_faces(self._h, arr, n, _ptr(embeds), _ptr(crops)))
+        self._embeds = embeds
+        self.croppedFaces = [dict(face=crops[i], x1=0, y1=0, x2=112, y2=112) for i in range(n)]
+        return embeds
+
+    def enrolFaces(self, classNames, faces, labels=None):
+        """``enrolEmbedding`` from the face images themselves: embeds them and appends the rows to the live gallery in one edit, device to
+        device.  ``labels``: one int per image for a labelled gallery (``MatMul.set_labels``).  Returns (first new row index, embeddings)."""
+        arr, keep = _face_images(faces)
+        names = list(classNames)
+        n = len(keep)
+        if len(names) != n:
+            raise ValueError("enrolFaces: %d names for %d images" % (len(names), n))
+        l = None
+        if labels is not None:
+            l = np.ascontiguousarray(labels, np.int32).reshape(-1)
+            if l.size != n:
+                raise ValueError("enrolFaces: one label per image")
+        if self.matmul.k == 0:  # never loaded: an empty gallery of this width first
+            self.matmul.galleryBegin(0, self.outputDim)
+            self.matmul.galleryCommit()
+        embeds = np.zeros((n, self.outputDim), np.float32)
+        first = _i(0)
+        _check(lib.frt_embedder_enrol_faces(self._h, self.matmul._h, arr, n, _ptr(l), _ptr(embeds), ctypes.byref(first)))
+        self.matmul._edited()
+        self.classNames = list(self.classNames) + names
+        self.classCount = len(self.classNames)
+        return first.value, embeds
 
     def featureMatching(self):
         if not len(self.classNames) or not self.croppedFaces:

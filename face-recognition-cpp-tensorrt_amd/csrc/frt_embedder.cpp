@@ -3,6 +3,7 @@
 // device every entry point that needs one fails with FRT_ERR_DEVICE.
 #include "frt_embedder.hpp"
 #include "frt_arc_pack.hpp"
+#include "frt_matcher.hpp"
 
 namespace {
 
@@ -507,6 +508,113 @@ bool forward_frame(frt_embedder *e, const uint8_t *bgr, int rows, int cols, size
     return bad;
 }
 
+// ---- face images instead of frames (include/frt.h "Face images instead of frames")
+// every argument of a face-image entry point that can be checked on the host, before any device work
+void check_face_images(const frt_face_image *faces, int n, const char *what) {
+    if (n < 0) raise(FRT_ERR_INVALID, std::string(what) + ": n < 0");
+    if (n > 0 && !faces) raise(FRT_ERR_INVALID, std::string(what) + ": null image list");
+    for (int i = 0; i < n; ++i) {
+        const frt_face_image &f = faces[i];
+        const char *why = !f.bgr ? "null pixel pointer"
+                          : f.rows < 1 || f.cols < 1 ? "rows < 1 or cols < 1"
+                          : f.cols > INT32_MAX / 3 ? "more columns than a row of int32 bytes holds"
+                          : f.row_stride < (size_t)f.cols * 3 ? "row_stride < cols * 3"
+                                                              : nullptr;
+        if (why) raise(FRT_ERR_INVALID, std::string(what) + ": image " + std::to_string(i) + ": " + why);
+    }
+}
+
+// images [first, first + count) with their row strides removed, each at its descriptor's offset behind `arena`
+void pack_face_images(const frt_face_image *faces, const frt_face_desc *desc, int first, int count, uint8_t *arena) {
+    for (int i = first; i < first + count; ++i) {
+        const frt_face_image &f = faces[i];
+        const size_t tight = (size_t)f.cols * 3;
+        uint8_t *dst = arena + desc[i].offset;
+        if (f.row_stride == tight) {
+            std::memcpy(dst, f.bgr, tight * f.rows);
+        } else {
+            for (int r = 0; r < f.rows; ++r) std::memcpy(dst + (size_t)r * tight, f.bgr + (size_t)r * f.row_stride, tight);
+        }
+    }
+}
+
+std::vector<frt_face_desc> face_descs(const frt_face_image *faces, int n) {
+    std::vector<frt_face_desc> desc((size_t)n);
+    for (int i = 0; i < n; ++i) desc[(size_t)i] = frt_face_desc{0, faces[i].rows, faces[i].cols};
+    return desc;
+}
+
+// The loop of gen / /insert/face / /recognize (app.cpp:69-99, :148-162, :243-287) for n images, under e->mu: chunk i + 1 is packed and
+// uploaded on the copy stream while chunk i's prepare kernel and network pass run on e->stream.  Embeddings go to embeds_out (host, may be
+// null) per chunk and, when `collect` (device, [n][512]) is given, are written there by the network pass itself.
+void embed_face_images(frt_embedder *e, const frt_face_image *faces, int n, float *embeds_out, uint8_t *crops_out, float *collect) {
+    frt_embedder::FaceStage &fs = e->faces;
+    hipStream_t s = e->stream;
+    std::vector<frt_face_desc> desc = face_descs(faces, n);
+    const std::vector<frt_face_chunk> chunks = frt_plan_face_chunks(desc.data(), n, e->max_batch, FRT_FACES_STAGE_CAP);
+    const size_t hdr = ((size_t)e->max_batch * sizeof(frt_face_desc) + 255) & ~(size_t)255;  // descriptor table in front of the arena: one upload
+    size_t need = 0;
+    for (const frt_face_chunk &c : chunks) need = std::max(need, c.bytes);
+    if (!fs.copy) {
+        HIPCHK(hipStreamCreateWithFlags(&fs.copy, hipStreamNonBlocking));
+        for (int b = 0; b < 2; ++b) {
+            HIPCHK(hipEventCreateWithFlags(&fs.uploaded[b], hipEventDisableTiming));
+            HIPCHK(hipEventCreateWithFlags(&fs.read[b], hipEventDisableTiming));
+        }
+    }
+    for (int b = 0; b < 2; ++b) {  // (both idle: every call ends with its streams drained)
+        if (fs.cap[b] >= need && fs.h_pack[b]) continue;
+        const size_t cap = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);  // grows to fit, as frame_cap does
+        if (fs.h_pack[b]) (void)hipHostFree(fs.h_pack[b]);
+        if (fs.d_pack[b]) (void)hipFree(fs.d_pack[b]);
+        fs.h_pack[b] = fs.d_pack[b] = nullptr;
+        fs.cap[b] = 0;
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&fs.h_pack[b]), hdr + cap, hipHostMallocDefault));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&fs.d_pack[b]), hdr + cap));
+        fs.cap[b] = cap;
+    }
+    e->wait_idle(s);
+    bool used[2] = {false, false};
+    auto stage = [&](size_t ci) {
+        const int b = (int)(ci & 1);
+        const frt_face_chunk &c = chunks[ci];
+        if (used[b]) wait_event_spinning(fs.uploaded[b]);  // the pinned buffer is rewritten only after its upload
+        std::memcpy(fs.h_pack[b], &desc[(size_t)c.first], (size_t)c.count * sizeof(frt_face_desc));
+        pack_face_images(faces, desc.data(), c.first, c.count, fs.h_pack[b] + hdr);
+        if (used[b]) HIPCHK(hipStreamWaitEvent(fs.copy, fs.read[b], 0));  // the arena only after the prepare kernel that read it
+        HIPCHK(hipMemcpyAsync(fs.d_pack[b], fs.h_pack[b], hdr + c.bytes, hipMemcpyHostToDevice, fs.copy));
+        HIPCHK(hipEventRecord(fs.uploaded[b], fs.copy));
+        used[b] = true;
+    };
+    try {
+        stage(0);
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            if (ci + 1 < chunks.size()) stage(ci + 1);  // (before this chunk's downloads: a copy into pageable memory holds the host)
+            const int b = (int)(ci & 1);
+            const frt_face_chunk &c = chunks[ci];
+            HIPCHK(hipStreamWaitEvent(s, fs.uploaded[b], 0));
+            {
+                ProfScope ps(2, "faces_prepare", (double)c.count * 112 * 112, s);
+                ProfScope pk(1, "faces_prepare_kernel", (double)c.count * 112 * 112, s);
+                launch_faces_prepare(fs.d_pack[b] + hdr, reinterpret_cast<const frt_face_desc *>(fs.d_pack[b]), c.count,
+                                     crops_out ? e->d_crops : nullptr, e->d_in, s);  // (d_in is shared: behind the previous chunk's pass on s)
+            }
+            HIPCHK(hipEventRecord(fs.read[b], s));
+            float *out = collect ? collect + (size_t)c.first * 512 : e->d_out;
+            e->forward(0, e->d_in, c.count, nullptr, out, s);
+            if (embeds_out) HIPCHK(hipMemcpyAsync(embeds_out + (size_t)c.first * 512, out, sizeof(float) * 512 * c.count, hipMemcpyDeviceToHost, s));
+            if (crops_out)
+                HIPCHK(hipMemcpyAsync(crops_out + (size_t)c.first * 112 * 112 * 3, e->d_crops, (size_t)c.count * 112 * 112 * 3, hipMemcpyDeviceToHost, s));
+        }
+        sync_stream_spinning(s);
+    } catch (...) {  // leave nothing in flight that reads the staging of a call that has returned
+        (void)hipStreamSynchronize(fs.copy);
+        (void)hipStreamSynchronize(s);
+        throw;
+    }
+    e->check_se_error();
+}
+
 }  // namespace
 
 extern "C" {
@@ -588,6 +696,17 @@ void frt_embedder_destroy(frt_embedder *e) {
         (void)hipStreamDestroy(e->stream);
     }
     if (e->d_frame) (void)hipFree(e->d_frame);
+    if (e->faces.copy) {
+        (void)hipStreamSynchronize(e->faces.copy);
+        (void)hipStreamDestroy(e->faces.copy);
+    }
+    for (int b = 0; b < 2; ++b) {
+        if (e->faces.h_pack[b]) (void)hipHostFree(e->faces.h_pack[b]);
+        if (e->faces.d_pack[b]) (void)hipFree(e->faces.d_pack[b]);
+        if (e->faces.uploaded[b]) (void)hipEventDestroy(e->faces.uploaded[b]);
+        if (e->faces.read[b]) (void)hipEventDestroy(e->faces.read[b]);
+    }
+    if (e->faces.d_embeds) (void)hipFree(e->faces.d_embeds);
     for (void *p : e->f32.owned) (void)hipFree(p);
     if (e->f32.done) (void)hipEventDestroy(e->f32.done);
     if (e->h_se_error) (void)hipHostFree(e->h_se_error);
@@ -690,6 +809,86 @@ int frt_embedder_forward_aligned(frt_embedder *e, const uint8_t *bgr, int rows, 
             launch_align_faces(e->d_frame, rows, cols, tight, 0, e->d_lm, nullptr, 1, nf, 1, e->d_crops, e->d_in, e->d_valid, s);
         });
         if (bad) raise(FRT_ERR_EMPTY_ROI, "forwardAligned: degenerate landmarks (embedding set to zeros)");
+    });
+}
+
+// ---------------------------------------------------------------------------------------------- face images instead of frames
+int frt_preprocess_faces(const frt_face_image *faces, int n, uint8_t *crops_out, float *chw_out, int device) {
+    return guarded([&] {
+        check_face_images(faces, n, "preprocessFaces");
+        if (n == 0 || (!crops_out && !chw_out)) return;
+        std::vector<frt_face_desc> desc = face_descs(faces, n);
+        const std::vector<frt_face_chunk> chunks = frt_plan_face_chunks(desc.data(), n, n, SIZE_MAX);  // one chunk: one arena, one launch
+        const size_t hdr = ((size_t)n * sizeof(frt_face_desc) + 255) & ~(size_t)255, px = (size_t)n * 112 * 112 * 3;
+        std::vector<uint8_t> pack(hdr + chunks[0].bytes);
+        std::memcpy(pack.data(), desc.data(), (size_t)n * sizeof(frt_face_desc));
+        pack_face_images(faces, desc.data(), 0, n, pack.data() + hdr);
+        if (device >= 0) use_device(device);
+        Arena a;
+        struct Guard {
+            Arena &a;
+            ~Guard() { a.release(); }
+        } guard{a};
+        uint8_t *d_pack = a.alloc<uint8_t>(pack.size());
+        uint8_t *d_crops = crops_out ? a.alloc<uint8_t>(px) : nullptr;
+        float *d_chw = chw_out ? a.alloc<float>(px) : nullptr;
+        HIPCHK(hipMemcpy(d_pack, pack.data(), pack.size(), hipMemcpyHostToDevice));
+        launch_faces_prepare(d_pack + hdr, reinterpret_cast<const frt_face_desc *>(d_pack), n, d_crops, d_chw, nullptr);
+        HIPCHK(hipGetLastError());
+        if (crops_out) HIPCHK(hipMemcpy(crops_out, d_crops, px, hipMemcpyDeviceToHost));
+        if (chw_out) HIPCHK(hipMemcpy(chw_out, d_chw, px * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+
+int frt_embedder_embed_faces(frt_embedder *e, const frt_face_image *faces, int n, float *embeds_out, uint8_t *crops_out) {
+    return guarded([&] {
+        if (!e) raise(FRT_ERR_INVALID, "embedFaces: null argument");
+        check_face_images(faces, n, "embedFaces");
+        if (n > 0 && !embeds_out) raise(FRT_ERR_INVALID, "embedFaces: null argument");
+        if (n == 0) return;
+        std::lock_guard<std::mutex> lk(e->mu);
+        use_device(e->device);
+        embed_face_images(e, faces, n, embeds_out, crops_out, nullptr);
+    });
+}
+
+int frt_embedder_enrol_faces(frt_embedder *e, frt_matcher *m, const frt_face_image *faces, int n, const int32_t *labels, float *embeds_out,
+                             int *first_row_out) {
+    return guarded([&] {
+        if (!e || !m) raise(FRT_ERR_INVALID, "enrolFaces: null argument");
+        check_face_images(faces, n, "enrolFaces");
+        if (n > 65536) raise(FRT_ERR_CAPACITY, "enrolFaces: more than 65536 images in one call");
+        if (e->device != m->device) raise(FRT_ERR_INVALID, "enrolFaces: the embedder and the matcher live on different devices");
+        for (int i = 0; labels && i < n; ++i)
+            if (labels[i] < 0) raise(FRT_ERR_INVALID, "enrolFaces: image " + std::to_string(i) + ": negative label");
+        std::lock_guard<std::mutex> lk(e->mu);  // lock order: embedder, then matcher
+        int rows = 0;
+        {  // what the edit will refuse is refused before the images are embedded (the add below checks again: the gallery may change in between)
+            std::lock_guard<std::mutex> lm(m->mu);
+            rows = m->N;
+            if (m->D != 512) raise(FRT_ERR_INVALID, "enrolFaces: the gallery does not hold 512-column rows (frt_matcher_init or gallery_begin + commit first)");
+            if (m->N > 0 && m->labelled != (labels != nullptr))
+                raise(FRT_ERR_INVALID, m->labelled ? "enrolFaces: the gallery is labelled (one label per image)"
+                                                   : "enrolFaces: the gallery has no labels (frt_matcher_set_labels first)");
+        }
+        if (n == 0) {
+            if (first_row_out) *first_row_out = rows;
+            return;
+        }
+        use_device(e->device);
+        frt_embedder::FaceStage &fs = e->faces;
+        if ((size_t)n > fs.embeds_cap) {
+            if (fs.d_embeds) (void)hipFree(fs.d_embeds);
+            fs.d_embeds = nullptr;
+            fs.embeds_cap = 0;
+            HIPCHK(hipMalloc(reinterpret_cast<void **>(&fs.d_embeds), (size_t)n * 512 * sizeof(float)));
+            fs.embeds_cap = (size_t)n;
+        }
+        embed_face_images(e, faces, n, embeds_out, nullptr, fs.d_embeds);
+        // one edit: all n rows or none (it takes the matcher's lock itself and checks the gallery's state again)
+        const int rc = labels ? frt_matcher_gallery_add_labeled_dev(m, fs.d_embeds, labels, n) : frt_matcher_gallery_add_dev(m, fs.d_embeds, n);
+        if (rc != FRT_OK) raise(rc, std::string(frthost::last_error()));
+        if (first_row_out) *first_row_out = frt_matcher_num_rows(m) - n;
     });
 }
 

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/frt.h"
+#include "frt_faces.hpp"
 
 typedef _Float16 half_t;
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -139,6 +140,9 @@ void launch_crop_faces(const uint8_t *frames, int frame_h, int frame_w, size_t r
 void launch_resize_linear(const uint8_t *src, int n, int sh, int sw, size_t sstride, size_t sframe, uint8_t *dst, int dh, int dw, size_t dstride,
                           size_t dframe, hipStream_t s);
 void launch_face_normalize(const uint8_t *crops, int F, int oh, int ow, float *chw, hipStream_t s);
+// F face images of any size, tightly packed in `arena` at desc[f] (frt_faces.hpp) -> cv::resize INTER_LINEAR to 112x112 + preprocessFace:
+// u8 BGR crops [F][112][112][3] and fp32 planar RGB [F][3][112][112], either may be null
+void launch_faces_prepare(const uint8_t *arena, const frt_face_desc *desc, int F, uint8_t *crops, float *chw, hipStream_t s);
 
 // ---------------------------------------------------------------- detector network (kernels_det.hip), fp32 NCHW
 struct DwPwArgs {

@@ -205,6 +205,69 @@ __global__ void face_normalize_kernel(const uint8_t *__restrict__ crops, int hw,
     for (int c = 0; c < 3; ++c) o[(size_t)c * hw] = ((float)s[2 - c] - 127.5f) * 0.0078125f;
 }
 
+// ---------------------------------------------------------------- face images instead of frames: cv::resize(face, face, Size(112, 112))
+// when the size differs (app.cpp:84-87, :152-155, :255-258: default INTER_LINEAR) + preprocessFace (arcface.cpp:105-114), for a ragged
+// batch.  arena holds the faces' tightly packed u8 BGR images, desc[f] says where face f lies and how large it is.  The resize is
+// resize_linear_u8_kernel's arithmetic, statement for statement (a 112x112 source is a copy; the exact-2x case has the same values).
+__global__ void faces_prepare_kernel(const uint8_t *__restrict__ arena, const frt_face_desc *__restrict__ desc, uint8_t *__restrict__ crops,
+                                     float *__restrict__ chw) {
+    constexpr int dh = 112, dw = 112;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t f = blockIdx.y;
+    if (p >= dh * dw) return;
+    const int dy = p / dw, dx = p - dy * dw;
+    const frt_face_desc d = desc[f];
+    const int sh = d.rows, sw = d.cols;
+    const size_t sstride = (size_t)sw * 3;
+    const uint8_t *s = arena + d.offset;
+    int v[3];
+    if (sh == dh && sw == dw) {
+        const uint8_t *q = s + (size_t)dy * sstride + (size_t)dx * 3;
+        v[0] = q[0];
+        v[1] = q[1];
+        v[2] = q[2];
+    } else {
+        const double scale_x = (double)sw / dw, scale_y = (double)sh / dh;
+        float fx = (float)((dx + 0.5) * scale_x - 0.5);
+        int sx = floor_i(fx);
+        fx -= sx;
+        if (sx < 0) {
+            fx = 0;
+            sx = 0;
+        }
+        if (sx >= sw - 1) {
+            fx = 0;
+            sx = sw - 1;
+        }
+        const int a0 = sat_short_round((1.f - fx) * COEF_SCALE), a1 = sat_short_round(fx * COEF_SCALE);
+        float fy = (float)((dy + 0.5) * scale_y - 0.5);
+        const int sy = floor_i(fy);
+        fy -= sy;
+        const int b0 = sat_short_round((1.f - fy) * COEF_SCALE), b1 = sat_short_round(fy * COEF_SCALE);
+        const int y0 = clampi(sy, 0, sh - 1), y1 = clampi(sy + 1, 0, sh - 1);
+        const int sx1 = sx + 1 < sw ? sx + 1 : sw - 1;
+        const uint8_t *s0 = s + (size_t)y0 * sstride + (size_t)sx * 3, *s1 = s + (size_t)y1 * sstride + (size_t)sx * 3;
+        const size_t step = (size_t)(sx1 - sx) * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int r0 = s0[c] * a0 + s0[step + c] * a1;
+            const int r1 = s1[c] * a0 + s1[step + c] * a1;
+            v[c] = ((((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2) & 255;
+        }
+    }
+    if (crops) {
+        uint8_t *o = crops + (f * dh * dw + p) * 3;
+        o[0] = (uint8_t)v[0];
+        o[1] = (uint8_t)v[1];
+        o[2] = (uint8_t)v[2];
+    }
+    if (chw) {
+        float *o = chw + f * 3 * dh * dw + p;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[(size_t)c * dh * dw] = ((float)v[2 - c] - 127.5f) * 0.0078125f;
+    }
+}
+
 }  // namespace
 
 void launch_det_preprocess(const uint8_t *frames, int n, int frame_h, int frame_w, size_t row_stride, size_t frame_stride, int in_h,
@@ -326,6 +389,15 @@ void launch_align_faces(const uint8_t *frames, int frame_h, int frame_w, size_t 
     dim3 grid((112 * 112 + 255) / 256, F);
     hipLaunchKernelGGL(align_faces_kernel, grid, dim3(256), 0, s, frames, frame_h, frame_w, row_stride, frame_stride, landmarks, n_boxes, max_faces,
                        frames_shared, crops, chw, valid);
+}
+
+void launch_faces_prepare(const uint8_t *arena, const frt_face_desc *desc, int F, uint8_t *crops, float *chw, hipStream_t s) {
+    constexpr int ROWS = 65535;  // faces per launch: gridDim.y
+    for (int f0 = 0; f0 < F; f0 += ROWS) {
+        dim3 grid((112 * 112 + 255) / 256, F - f0 < ROWS ? F - f0 : ROWS);
+        hipLaunchKernelGGL(faces_prepare_kernel, grid, dim3(256), 0, s, arena, desc + f0, crops ? crops + (size_t)f0 * 112 * 112 * 3 : nullptr,
+                           chw ? chw + (size_t)f0 * 3 * 112 * 112 : nullptr);
+    }
 }
 
 void launch_face_normalize(const uint8_t *crops, int F, int oh, int ow, float *chw, hipStream_t s) {

@@ -545,6 +545,27 @@ int frt_embedder_forward_aligned(frt_embedder *e, const uint8_t *bgr, int rows, 
 int frt_pipeline_set_align(frt_pipeline *p, int enable);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Face images instead of frames.  The reference takes a pre-cropped face in three places - /recognize (src/app.cpp:243-287),
+ * /insert/face with api_imgIsCropped (src/app.cpp:148-162) and the `gen` start-up mode that builds the database from a folder of face
+ * images (src/app.cpp:69-99) - and does the same per image in all of them: cv::resize to 112x112 when the size differs (default
+ * INTER_LINEAR), preprocessFace, one recogniser inference.  These entry points take a ragged batch of such images, of any sizes: the u8
+ * bytes go up once (a quarter of the fp32 tensor's), resize + preprocessFace are one kernel, the recogniser runs full passes of
+ * max_batch faces while the next images upload, and the embeddings go to the host or straight into the live gallery.
+ *   All arguments are checked before any device work: a NULL image pointer, rows < 1, cols < 1, row_stride < cols * 3 or n < 0 is
+ *   FRT_ERR_INVALID with the image's index in frt_last_error(), nothing written, nothing changed.  n == 0 succeeds and does nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct frt_face_image { const uint8_t *bgr; int32_t rows, cols; size_t row_stride; } frt_face_image;
+/* cv::resize(112x112) + preprocessFace for n images in one launch; crops_out u8 [n][112][112][3] and chw_out fp32 [n][3][112][112], either may be NULL */
+int frt_preprocess_faces(const frt_face_image *faces, int n, uint8_t *crops_out, float *chw_out, int device);
+/* the loop of gen / /insert/face / /recognize for n images: embeds_out [n][512] L2-normalised, crops_out may be NULL */
+int frt_embedder_embed_faces(frt_embedder *e, const frt_face_image *faces, int n, float *embeds_out, uint8_t *crops_out);
+/* embed n images and append their embeddings to the live gallery as ONE edit, device to device: labels NULL for an unlabelled gallery, else
+ * [n] (host) as frt_matcher_gallery_add_labeled; embeds_out (may be NULL) also returns them; first_row_out <- index of the first new row.
+ * At most 65536 images per call (FRT_ERR_CAPACITY, nothing done); the gallery gets all n rows or none; a labelled call on an unlabelled
+ * gallery with rows (or the reverse) is FRT_ERR_INVALID.  Takes the embedder's lock, then the matcher's; both objects on one device. */
+int frt_embedder_enrol_faces(frt_embedder *e, frt_matcher *m, const frt_face_image *faces, int n, const int32_t *labels, float *embeds_out, int *first_row_out);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).
  * ------------------------------------------------------------------------------------------------------------------ */
 /* kinds: 0 = off (drops the records), 1 = time every launch of the dominant kernel family (conv3x3 MFMA), 2 = time every stage,

@@ -175,6 +175,26 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         classNames.insert(classNames.end(), names.begin(), names.end());
         classCount += (int)names.size();
     }
+    // Extension: enrolEmbeddings from the face images themselves - /insert/face with api_imgIsCropped (src/app.cpp:148-162) and the gen
+    // loop (src/app.cpp:79-97) for n images of any sizes (8UC3) in one call: resize + preprocessFace + inference on the device, and the
+    // embeddings go into the live gallery device to device, as ONE edit (frt_embedder_enrol_faces).  classNames / classCount / labels move
+    // as in enrolEmbeddings.  embeddingsOut (may be null): [n x outputDim], what db.insertFace stores.  At most 65536 images per call.
+    void enrolFaces(const std::vector<std::string> &names, const std::vector<cv::Mat> &faces, float *embeddingsOut = nullptr) {
+        assert(names.size() == faces.size());
+        if (matmul.numRows() == 0 && classNames.empty()) {
+            matmul.galleryBegin(0, m_OUTPUT_D);
+            matmul.galleryCommit();
+        }
+        const std::vector<frt_face_image> imgs = faceImages(faces);
+        const bool labelled = m_labelsSet && matmul.numRows() > 0;
+        std::vector<int> labels;
+        for (size_t i = 0; labelled && i < names.size(); ++i) labels.push_back(internLabel(names[i]));
+        int first = 0;
+        checkFrtStatus(frt_embedder_enrol_faces(h_, matmul.handle(), imgs.data(), (int)imgs.size(), labelled ? labels.data() : nullptr, embeddingsOut, &first));
+        if (!labelled) m_labelsSet = false;
+        classNames.insert(classNames.end(), names.begin(), names.end());
+        classCount += (int)names.size();
+    }
     // every row of that name, as /delete/user removes every face of the user; the rows behind them close up in order (the order a
     // /reload would read them in: src/db.cpp:316-346).  Returns how many there were.
     int removeClass(const std::string &className) {
@@ -243,6 +263,38 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
                 c.x2 = outputBbox[(size_t)i].x2;
                 c.y2 = outputBbox[(size_t)i].y2;
             }
+            croppedFaces.push_back(c);
+        }
+    }
+    // Extension: forward() for face images instead of a frame and boxes - what /recognize does for one pre-cropped face (src/app.cpp:254-267:
+    // cv::resize to 112x112 when the size differs, the box 0,0,112,112, forward), for n images of any sizes (8UC3) in one call
+    // (frt_embedder_embed_faces: resize + preprocessFace in one kernel, recogniser passes of maxBatchSize faces while the next images
+    // upload).  Leaves what forward() leaves - embeddings and croppedFaces with the resized face - so featureMatching / getOutputs /
+    // matchTop1 / matchTopIdentities follow unchanged.
+    void forwardFaces(const std::vector<cv::Mat> &faces) {
+        const int n = (int)faces.size();
+        State &s = st();
+        s.croppedFaces.clear();
+        s.top_valid = s.from_record = false;
+        s.embeds.assign((size_t)std::max(n, 1) * m_OUTPUT_D, 0.f);
+        if (!n) return;
+        const std::vector<frt_face_image> imgs = faceImages(faces);
+        const size_t px = (size_t)m_INPUT_H * m_INPUT_W;
+        std::vector<unsigned char> crops((size_t)n * px * 3);
+        checkFrtStatus(frt_embedder_embed_faces(h_, imgs.data(), n, s.embeds.data(), crops.data()));
+        for (int i = 0; i < n; ++i) {
+            CroppedFace c;
+            c.face = cv::Mat(m_INPUT_H, m_INPUT_W, CV_8UC3, &crops[(size_t)i * px * 3]).clone();
+            // faceMat as preprocessFace() leaves it; both steps are exact in binary floating point, so this loop is the device kernel's output
+            c.faceMat = cv::Mat(3 * m_INPUT_H, m_INPUT_W, CV_32FC1);
+            float *t = c.faceMat.ptr<float>(0);
+            const unsigned char *p = c.face.data;
+            for (size_t k = 0; k < px; ++k)
+                for (int ch = 0; ch < 3; ++ch) t[(size_t)ch * px + k] = ((float)p[k * 3 + (size_t)(2 - ch)] - 127.5f) * 0.0078125f;
+            c.x1 = 0;
+            c.y1 = 0;
+            c.x2 = m_INPUT_H;  // bbox.x2 = recInputShape[1], bbox.y2 = recInputShape[2] (src/app.cpp:263-264)
+            c.y2 = m_INPUT_W;
             croppedFaces.push_back(c);
         }
     }
@@ -385,6 +437,16 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     // What a call leaves behind for the next call of the same request - per calling THREAD (include/frt/coalesce.h): the reference keeps
     // it in the object and shares the object between its server's threads.
     // labels of matchTopIdentities: className <-> label, in first-appearance order; m_labelsSet: the matcher holds the labels of classNames
+    static std::vector<frt_face_image> faceImages(const std::vector<cv::Mat> &faces) {  // row-strided Mats (ROIs) go as they are, not copied
+        std::vector<frt_face_image> imgs(faces.size());
+        for (size_t i = 0; i < faces.size(); ++i) {
+            imgs[i].bgr = faces[i].data;
+            imgs[i].rows = faces[i].rows;
+            imgs[i].cols = faces[i].cols;
+            imgs[i].row_stride = (size_t)faces[i].step;
+        }
+        return imgs;
+    }
     int internLabel(const std::string &name) {
         std::map<std::string, int>::iterator it = m_labelOf.find(name);
         if (it != m_labelOf.end()) return it->second;
