@@ -34,6 +34,7 @@ lib = ctypes.CDLL(LIB_PATH)
 # C ABI declarations (include/frt.h)
 # ----------------------------------------------------------------------------------------------------------------------
 FRT_OK, FRT_ERR_INVALID, FRT_ERR_NOT_FOUND, FRT_ERR_FORMAT, FRT_ERR_DEVICE, FRT_ERR_EMPTY, FRT_ERR_EMPTY_ROI, FRT_ERR_CAPACITY = range(8)
+FRT_ENROL_OK, FRT_ENROL_MANY, FRT_ENROL_NONE, FRT_ENROL_EMPTY_ROI = 1, 2, 3, 4  # frt_enrol_status: the "exactly one face" rule of /insert/face
 
 BBOX_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("score", "<f4")])  # == struct Bbox, common.h:13-16
 RESULT_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("score", "<f4"), ("frame", "<i4"),
@@ -158,6 +159,10 @@ ABI = {
     "frt_preprocess_faces": (_i, [_vp, _i, _vp, _vp, _i]),
     "frt_embedder_embed_faces": (_i, [_vp, _vp, _i, _vp, _vp]),
     "frt_embedder_enrol_faces": (_i, [_vp, _vp, _vp, _i, _vp, _vp, ctypes.POINTER(_i)]),
+    "frt_resize_images": (_i, [_vp, _i, _vp, _i, _i, _i]),
+    "frt_enrol_select_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "frt_pipeline_run_images": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "frt_pipeline_enrol_images": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "frt_profile_enable": (_i, [_i]),
     "frt_profile_collect": (_i, [_vp, _sz, _vp, _vp, _i]),
 }
@@ -661,6 +666,21 @@ def preprocessFaces(faces, device=0):
     return crops, chw
 
 
+def resizeImages(images, width, height, device=0):
+    """``resizeFrame`` for a list of H x W x 3 u8 images of any sizes, one launch (frt_resize_images) -> u8 [n][height][width][3]."""
+    arr, keep = _face_images(images)
+    n = len(keep)
+    out = np.zeros((n, int(height), int(width), 3), np.uint8)
+    _check(lib.frt_resize_images(arr, n, _ptr(out), int(height), int(width), device))
+    return out
+
+
+def enrol_select_dev(results_ptr, embeds_ptr, n_frames, max_faces, status_ptr, face_ptr, rows_ptr, count_ptr, hip_stream=None):
+    """frt_enrol_select_dev: the "exactly one face" rule on device-resident pipeline records; raw device addresses, asynchronous."""
+    _check(lib.frt_enrol_select_dev(_vp(results_ptr), _vp(embeds_ptr), int(n_frames), int(max_faces), _vp(status_ptr), _vp(face_ptr) if face_ptr else None,
+                                    _vp(rows_ptr), _vp(count_ptr), _vp(hip_stream) if hip_stream else None))
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # class ArcFaceIR50 (src/arcface.h)
 # ----------------------------------------------------------------------------------------------------------------------
@@ -919,6 +939,7 @@ class Pipeline:
         self.det, self.rec = detector, recognizer
         self.max_frames = int(max_frames)
         self.max_faces = detector.maxFacesPerScene
+        self._match = bool(match)
         _check(lib.frt_pipeline_create(detector._h, recognizer._h, recognizer.matmul._h if match else None, self.max_frames, ctypes.byref(self._h)))
 
     def run(self, frames, want_embeds=True):
@@ -928,6 +949,50 @@ class Pipeline:
         emb = np.zeros((n * self.max_faces, 512), np.float32) if want_embeds else None
         _check(lib.frt_pipeline_run(self._h, _ptr(frames), n, _ptr(res), _ptr(emb)))
         return res, emb
+
+    # whole photos of any sizes: the head of /inference (src/app.cpp:296-301) and /insert/face without api_imgIsCropped (:163-187)
+    def runImages(self, images, want_embeds=True, want_crops=False):
+        """``run`` for a list of H x W x 3 u8 images of any sizes: each is stretched to the detector's frame size on the device (cv::resize,
+        INTER_LINEAR) and the chunks of ``max_frames`` images run back to back -> (records [n * max_faces], ``frame`` = index of the image,
+        embeddings [n * max_faces, 512] or None[, u8 crops [n * max_faces, 112, 112, 3]])."""
+        arr, keep = _face_images(images)
+        n = len(keep)
+        res = np.zeros(n * self.max_faces, RESULT_DTYPE)
+        emb = np.zeros((n * self.max_faces, 512), np.float32) if want_embeds else None
+        crops = np.zeros((n * self.max_faces, 112, 112, 3), np.uint8) if want_crops else None
+        _check(lib.frt_pipeline_run_images(self._h, arr, n, _ptr(res), _ptr(emb), _ptr(crops)))
+        return (res, emb, crops) if want_crops else (res, emb)
+
+    def enrolImages(self, classNames, images, labels=None):
+        """/insert/face for whole photos: detect, require exactly one face, embed, and append the accepted photos' rows to the live gallery as
+        ONE edit, device to device.  ``labels``: one int per image for a labelled gallery.  Returns (status [n] of FRT_ENROL_*, first new
+        row index, embeddings [n_enrolled, 512] - exactly the rows added, faces [n] records with the match against the gallery as it was
+        before the call).  The recogniser's ``classNames`` / ``classCount`` grow by the accepted names only."""
+        arr, keep = _face_images(images)
+        names = list(classNames)
+        n = len(keep)
+        if len(names) != n:
+            raise ValueError("enrolImages: %d names for %d images" % (len(names), n))
+        l = None
+        if labels is not None:
+            l = np.ascontiguousarray(labels, np.int32).reshape(-1)
+            if l.size != n:
+                raise ValueError("enrolImages: one label per image")
+        mm = self.rec.matmul
+        if not self._match:  # (refused before the recogniser's matcher is touched)
+            raise FrtError(FRT_ERR_INVALID, "enrolImages: the pipeline has no matcher")
+        if mm.k == 0:  # never loaded: an empty gallery of this width first
+            mm.galleryBegin(0, self.rec.outputDim)
+            mm.galleryCommit()
+        status = np.zeros(n, np.int32)
+        faces = np.zeros(n, RESULT_DTYPE)
+        embeds = np.zeros((n, 512), np.float32)
+        first, count = _i(0), _i(0)
+        _check(lib.frt_pipeline_enrol_images(self._h, arr, n, _ptr(l), _ptr(status), _ptr(faces), _ptr(embeds), ctypes.byref(first), ctypes.byref(count)))
+        mm._edited()
+        self.rec.classNames = list(self.rec.classNames) + [nm for nm, st in zip(names, status) if st == FRT_ENROL_OK]
+        self.rec.classCount = len(self.rec.classNames)
+        return status, first.value, embeds[:count.value].copy(), faces
 
     def submit(self, frames, results, embeds=None, crops=None):
         """Asynchronous host boundary: queue one batch (``frames`` u8 [n, H, W, 3], ``results`` a RESULT_DTYPE array of

@@ -508,6 +508,8 @@ bool forward_frame(frt_embedder *e, const uint8_t *bgr, int rows, int cols, size
     return bad;
 }
 
+}  // namespace
+
 // ---- face images instead of frames (include/frt.h "Face images instead of frames")
 // every argument of a face-image entry point that can be checked on the host, before any device work
 void check_face_images(const frt_face_image *faces, int n, const char *what) {
@@ -543,6 +545,8 @@ std::vector<frt_face_desc> face_descs(const frt_face_image *faces, int n) {
     for (int i = 0; i < n; ++i) desc[(size_t)i] = frt_face_desc{0, faces[i].rows, faces[i].cols};
     return desc;
 }
+
+namespace {
 
 // The loop of gen / /insert/face / /recognize (app.cpp:69-99, :148-162, :243-287) for n images, under e->mu: chunk i + 1 is packed and
 // uploaded on the copy stream while chunk i's prepare kernel and network pass run on e->stream.  Embeddings go to embeds_out (host, may be

@@ -105,3 +105,9 @@ struct frt_embedder {
     // chw_dev [F][3][112][112] -> out_dev [F][512] on activation set `set`; F <= max_batch
     void forward(int set, const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s);
 };
+
+// every argument of a face-image / photo entry point that can be checked on the host, before any device work; the images' descriptors;
+// images [first, first + count) packed behind `arena` at their descriptors' offsets (frt_embedder.cpp; shared with frt_images.cpp)
+void check_face_images(const frt_face_image *faces, int n, const char *what);
+std::vector<frt_face_desc> face_descs(const frt_face_image *faces, int n);
+void pack_face_images(const frt_face_image *faces, const frt_face_desc *desc, int first, int count, uint8_t *arena);

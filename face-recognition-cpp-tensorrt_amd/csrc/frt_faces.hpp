@@ -7,7 +7,7 @@
 
 #include <vector>
 
-// one face of the arena: tightly packed u8 BGR [rows][cols][3] at byte `offset` (what faces_prepare_kernel reads per grid row)
+// one face of the arena: tightly packed u8 BGR [rows][cols][3] at byte `offset` (what ragged_resize_kernel reads per grid row)
 struct frt_face_desc {
     uint64_t offset;
     int32_t rows, cols;

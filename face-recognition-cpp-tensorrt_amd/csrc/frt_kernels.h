@@ -143,6 +143,14 @@ void launch_face_normalize(const uint8_t *crops, int F, int oh, int ow, float *c
 // F face images of any size, tightly packed in `arena` at desc[f] (frt_faces.hpp) -> cv::resize INTER_LINEAR to 112x112 + preprocessFace:
 // u8 BGR crops [F][112][112][3] and fp32 planar RGB [F][3][112][112], either may be null
 void launch_faces_prepare(const uint8_t *arena, const frt_face_desc *desc, int F, uint8_t *crops, float *chw, hipStream_t s);
+// the same kernel for whole photos: n images of any size at desc[i] of `arena` -> cv::resize INTER_LINEAR to dh x dw, u8 BGR [n][dh][dw][3]
+void launch_images_resize(const uint8_t *arena, const frt_face_desc *desc, int n, int dh, int dw, uint8_t *out, hipStream_t s);
+
+// ---------------------------------------------------------------- the "exactly one face" rule of /insert/face (kernels_enrol.hip)
+// results [n_frames][max_faces], embeds [n_frames][max_faces][512] -> status [n_frames] (frt_enrol_status), face_out [n_frames] (may be
+// null), the OK frames' embeddings to rows[*count ...], *count advanced; one workgroup
+void launch_enrol_select(const frt_face_result *results, const float *embeds, int n_frames, int max_faces, int32_t *status, frt_face_result *face_out,
+                         float *rows, int32_t *count, hipStream_t s);
 
 // ---------------------------------------------------------------- detector network (kernels_det.hip), fp32 NCHW
 struct DwPwArgs {

@@ -297,6 +297,16 @@ void search_to_host(frt_matcher *m, const float *embeds, int F, bool lists, int 
 
 }  // namespace
 
+// frt_matcher_gallery_add_dev / _add_labeled_dev (labels != nullptr) for callers inside the library that need the index of the first new
+// row from the edit itself (another thread's edit may follow before they could ask): takes m->mu; raises like the entry points
+int matcher_add_rows_dev(frt_matcher *m, const void *rows_dev, const int32_t *labels, int n_rows) {
+    std::lock_guard<std::mutex> lk(m->mu);
+    use_device(m->device);
+    const int first = m->N;
+    add_rows(m, rows_dev, n_rows, true, labels, labels != nullptr);
+    return first;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------------------------------------------------- matcher

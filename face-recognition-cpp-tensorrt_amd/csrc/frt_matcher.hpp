@@ -384,3 +384,5 @@ struct frt_matcher {
     }
 };
 
+// gallery_add_dev / gallery_add_labeled_dev (labels != nullptr) returning the index of the first new row (frt_matcher.cpp)
+int matcher_add_rows_dev(frt_matcher *m, const void *rows_dev, const int32_t *labels, int n_rows);

@@ -483,6 +483,7 @@ void frt_pipeline_destroy(frt_pipeline *p) {
     }
     p->drain(false);
     p->drop_graphs();
+    p->release_images();
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
     if (p->det_stream) (void)hipStreamDestroy(p->det_stream);
     if (p->emb_stream) (void)hipStreamDestroy(p->emb_stream);

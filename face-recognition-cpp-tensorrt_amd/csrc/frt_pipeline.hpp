@@ -183,6 +183,33 @@ struct frt_pipeline {
         }
     }
 
+    // ---- whole photos of any sizes (frt_pipeline_run_images / _enrol_images, frt_images.cpp), allocated on first use.  A call's chunks go
+    //      through run_dev one after the other; two staging sets, so that chunk i + 1 is packed, uploaded and resized on `ingest` while
+    //      chunk i runs and chunk i - 1's results are copied out of pinned memory.  images_mu serialises these calls among themselves and
+    //      is taken BEFORE run_mu (which they take per chunk, never async_mu): images_mu -> run_mu -> object mutexes.
+    struct ImageStage {
+        static constexpr int NSET = 2;
+        bool built = false;                                  // the fixed-size part below exists, all of it
+        hipStream_t ingest = nullptr;                        // upload + resize kernel of a chunk
+        uint8_t *h_pack[NSET] = {}, *d_pack[NSET] = {};      // pinned / device: [max_frames] descriptors, then the chunk's photos, row strides removed
+        size_t cap[NSET] = {};                               // photo bytes either of a pair holds (they grow together)
+        hipEvent_t uploaded[NSET] = {};                      // h_pack[b] may be rewritten
+        hipEvent_t ready[NSET] = {};                         // d_frames[b] holds the chunk's resized frames (Request::after)
+        hipEvent_t done[NSET] = {};                          // the chunk's stages and downloads are complete on the pipeline stream
+        uint8_t *d_frames[NSET] = {};                        // [max_frames][frame_h][frame_w][3]
+        frt_face_result *d_results[NSET] = {}, *h_results[NSET] = {};  // [F_cap] device / pinned
+        float *d_embeds[NSET] = {}, *h_embeds[NSET] = {};              // [F_cap][512]
+        uint8_t *d_crops[NSET] = {}, *h_crops[NSET] = {};              // [F_cap][112][112][3] (first call that asks for crops)
+        // one enrolment call: the dense rows of the accepted photos, status word and face per photo, the row count
+        float *d_rows = nullptr;
+        int32_t *d_status = nullptr, *h_status = nullptr, *d_count = nullptr, *h_count = nullptr;  // (h_*: pinned)
+        frt_face_result *d_face = nullptr, *h_face = nullptr;
+        size_t enrol_cap = 0;
+        hipEvent_t finished = nullptr;
+    } images;
+    std::mutex images_mu;
+    void release_images();  // (frt_pipeline_destroy)
+
     // ---- hipGraph replay.  A step is ~150 dependent launches; eager dispatch costs 3.1 us per dependent kernel on this part,
     //      a graph replay 1.8 us (tools/ubench/launch_gap.hip).  Each call is two graphs - the detector part on det_stream, the
     //      rest on `stream` - so the cross-call overlap of the two streams survives; the fork/join events stay ordinary stream

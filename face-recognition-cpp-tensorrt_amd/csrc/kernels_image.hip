@@ -205,13 +205,16 @@ __global__ void face_normalize_kernel(const uint8_t *__restrict__ crops, int hw,
     for (int c = 0; c < 3; ++c) o[(size_t)c * hw] = ((float)s[2 - c] - 127.5f) * 0.0078125f;
 }
 
-// ---------------------------------------------------------------- face images instead of frames: cv::resize(face, face, Size(112, 112))
-// when the size differs (app.cpp:84-87, :152-155, :255-258: default INTER_LINEAR) + preprocessFace (arcface.cpp:105-114), for a ragged
-// batch.  arena holds the faces' tightly packed u8 BGR images, desc[f] says where face f lies and how large it is.  The resize is
-// resize_linear_u8_kernel's arithmetic, statement for statement (a 112x112 source is a copy; the exact-2x case has the same values).
-__global__ void faces_prepare_kernel(const uint8_t *__restrict__ arena, const frt_face_desc *__restrict__ desc, uint8_t *__restrict__ crops,
-                                     float *__restrict__ chw) {
-    constexpr int dh = 112, dw = 112;
+// ---------------------------------------------------------------- ragged batches: images of any sizes -> one fixed size
+// arena holds the images' tightly packed u8 BGR bytes, desc[f] says where image f lies and how large it is; every image is resized to
+// dh x dw with resize_linear_u8_kernel's arithmetic, statement for statement (a dh x dw source is a copy; the exact-2x case has the same
+// values).  Two callers, one kernel:
+//   faces  - cv::resize(face, face, Size(112, 112)) when the size differs (app.cpp:84-87, :152-155, :255-258: default INTER_LINEAR) +
+//            preprocessFace (arcface.cpp:105-114): dh = dw = 112, u8 and / or fp32 planar out;
+//   frames - cv::resize(img, img, Size(frameWidth, frameHeight)) of whole photos (app.cpp:166, :301): u8 out only (chw null).
+// All offsets are 64-bit: the arena of a chunk is up to 64 MiB and more when one image alone is larger.
+__global__ void ragged_resize_kernel(const uint8_t *__restrict__ arena, const frt_face_desc *__restrict__ desc, int dh, int dw,
+                                     uint8_t *__restrict__ crops, float *__restrict__ chw) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     const size_t f = blockIdx.y;
     if (p >= dh * dw) return;
@@ -256,15 +259,16 @@ __global__ void faces_prepare_kernel(const uint8_t *__restrict__ arena, const fr
         }
     }
     if (crops) {
-        uint8_t *o = crops + (f * dh * dw + p) * 3;
+        uint8_t *o = crops + (f * dh * dw + (size_t)p) * 3;
         o[0] = (uint8_t)v[0];
         o[1] = (uint8_t)v[1];
         o[2] = (uint8_t)v[2];
     }
     if (chw) {
-        float *o = chw + f * 3 * dh * dw + p;
+        const size_t plane = (size_t)dh * dw;
+        float *o = chw + f * 3 * plane + p;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) o[(size_t)c * dh * dw] = ((float)v[2 - c] - 127.5f) * 0.0078125f;
+        for (int c = 0; c < 3; ++c) o[(size_t)c * plane] = ((float)v[2 - c] - 127.5f) * 0.0078125f;
     }
 }
 
@@ -395,8 +399,17 @@ void launch_faces_prepare(const uint8_t *arena, const frt_face_desc *desc, int F
     constexpr int ROWS = 65535;  // faces per launch: gridDim.y
     for (int f0 = 0; f0 < F; f0 += ROWS) {
         dim3 grid((112 * 112 + 255) / 256, F - f0 < ROWS ? F - f0 : ROWS);
-        hipLaunchKernelGGL(faces_prepare_kernel, grid, dim3(256), 0, s, arena, desc + f0, crops ? crops + (size_t)f0 * 112 * 112 * 3 : nullptr,
+        hipLaunchKernelGGL(ragged_resize_kernel, grid, dim3(256), 0, s, arena, desc + f0, 112, 112, crops ? crops + (size_t)f0 * 112 * 112 * 3 : nullptr,
                            chw ? chw + (size_t)f0 * 3 * 112 * 112 : nullptr);
+    }
+}
+
+void launch_images_resize(const uint8_t *arena, const frt_face_desc *desc, int n, int dh, int dw, uint8_t *out, hipStream_t s) {
+    constexpr int ROWS = 65535;  // images per launch: gridDim.y
+    const size_t frame = (size_t)dh * dw * 3;
+    for (int f0 = 0; f0 < n; f0 += ROWS) {
+        dim3 grid((unsigned)(((size_t)dh * dw + 255) / 256), n - f0 < ROWS ? n - f0 : ROWS);
+        hipLaunchKernelGGL(ragged_resize_kernel, grid, dim3(256), 0, s, arena, desc + f0, dh, dw, out + (size_t)f0 * frame, nullptr);
     }
 }
 

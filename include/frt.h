@@ -566,6 +566,56 @@ int frt_embedder_embed_faces(frt_embedder *e, const frt_face_image *faces, int n
 int frt_embedder_enrol_faces(frt_embedder *e, frt_matcher *m, const frt_face_image *faces, int n, const int32_t *labels, float *embeds_out, int *first_row_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Whole photos of any sizes.  The other half of /insert/face - the default, api_imgIsCropped false (src/app.cpp:163-187) - and the head of
+ * /inference (src/app.cpp:296-301) take a photo of any size: cv::resize it to frameWidth x frameHeight (default INTER_LINEAR, aspect not
+ * kept), findFace, getCroppedFaces; /insert/face then requires exactly one face (ret = 2 for more than one, :172-174; ret = 3 for none,
+ * :175-177), embeds it and stores it.  These entry points do that for a ragged batch: the photos' bytes go up once per chunk, ONE kernel
+ * resizes a chunk into the pipeline's frame buffer (the arithmetic of frt_resize_frame, bit for bit), the chunks run through the
+ * three-stage pipeline back to back while the next one uploads, and the "exactly one face" rule and the gallery edit stay on the device.
+ *   Argument checks are frt_embedder_embed_faces's, made before any device work (and before the pipeline handle is looked at): a NULL image
+ *   pointer, rows < 1, cols < 1, row_stride < cols * 3 or n < 0 is FRT_ERR_INVALID with the image's index in frt_last_error().  n == 0
+ *   succeeds and does nothing.  Images are cut into chunks of at most the pipeline's max_frames photos and 64 MiB of pixels.
+ *   Both pipeline calls may run beside frt_pipeline_submit / wait / run of other threads (lock order: the pipeline's image-stage mutex, then
+ *   per chunk run_mu -> object mutexes; the matcher's for the edit last).  Every chunk is queued in full when it is handed over: in a pairing
+ *   mode that holds frt_pipeline_run_dev calls (frt_pipeline_set_pairing 1 .. 4, -2) whatever is held or pending is flushed behind each chunk,
+ *   so the answers are those of pairing off.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef enum frt_enrol_status {
+    FRT_ENROL_OK = 1,        /* one box and valid != 0: the photo is (or would be) enrolled                                         */
+    FRT_ENROL_MANY = 2,      /* more than one box (src/app.cpp:172-174).  With maxFacesPerScene == 1 the cap behind NMS leaves at most
+                              * one box, so this status cannot occur - the reference behaves the same                               */
+    FRT_ENROL_NONE = 3,      /* no box (src/app.cpp:175-177)                                                                        */
+    FRT_ENROL_EMPTY_ROI = 4  /* one box whose ROI is empty (valid == 0, score > 0): OpenCV would throw there                       */
+} frt_enrol_status;
+/* ragged counterpart of frt_resize_frame: n images of any sizes -> out u8 [n][out_rows][out_cols][3], one launch */
+int frt_resize_images(const frt_face_image *images, int n, uint8_t *out, int out_rows, int out_cols, int device);
+/* device building block for callers whose frames are already on the device (frt_jpeg_decode_batch_dev + frt_pipeline_run_dev_after):
+ * results_dev frt_face_result [n_frames][max_faces] and embeds_dev float [n_frames][max_faces][512] as the pipeline leaves them (a frame's
+ * boxes fill its slots from slot 0; an unused slot has score 0); status_dev int32[n_frames] <- frt_enrol_status, face_dev
+ * frt_face_result[n_frames] (may be NULL) <- slot 0's record for OK / EMPTY_ROI, zeros otherwise, `frame` kept; rows_dev float
+ * [>= *count + n_frames][512] <- the embeddings of the OK frames, dense, in frame order, from row *count on; count_dev int32 (read as base,
+ * advanced by the number of OK frames).  One workgroup, asynchronous on hip_stream (the current device's; NULL = default stream): calls on
+ * one stream append.  embeds_dev and rows_dev must be 16-byte aligned.  n_frames == 0 does nothing. */
+int frt_enrol_select_dev(const void *results_dev, const void *embeds_dev, int n_frames, int max_faces, void *status_dev, void *face_dev,
+                         void *rows_dev, void *count_dev, void *hip_stream);
+/* /inference for n images of any sizes: results [n][max_faces] (frame = index of the image IN THE CALL; boxes in the resized
+ * frame_w x frame_h frame, as the reference's), embeds_out [n][max_faces][512] and crops_out [n][max_faces][112][112][3] may be NULL */
+int frt_pipeline_run_images(frt_pipeline *p, const frt_face_image *images, int n, frt_face_result *results, float *embeds_out, uint8_t *crops_out);
+/* /insert/face without api_imgIsCropped for n photos, ONE gallery edit.  Needs a pipeline with a matcher whose gallery holds 512-column rows
+ * (FRT_ERR_INVALID otherwise; an empty gallery: gallery_begin(m, cap, 512) + commit first).  At most 65536 images per call
+ * (FRT_ERR_CAPACITY, nothing done).  labels: NULL for an unlabelled gallery, else [n] on the host, one per IMAGE (those of the accepted
+ * images go to frt_matcher_gallery_add_labeled_dev); a negative label or the wrong form for a gallery with rows is FRT_ERR_INVALID before
+ * any device work.  status_out [n] <- frt_enrol_status, always written on success.  faces_out [n] (may be NULL) <- the photo's face
+ * (frame = index of the image in the call) with match_idx / match_sim against the gallery AS IT WAS BEFORE THE CALL: every chunk is matched
+ * before the edit, photos of one call do not see each other; the match is reported, not acted on.  The rows of the FRT_ENROL_OK photos are
+ * appended in image order as ONE edit - all of them or none; one step of frt_matcher_generation when the rows fit the reserved capacity
+ * (an add that has to move the gallery also moves the scratch of a matcher bound to a pipeline, a step of its own); none accepted: no edit.  embeds_out (may be NULL, room
+ * for [n][512]) <- [n_enrolled][512], exactly the rows added (what db.insertFace stores); first_row_out <- index of the first new row; n_enrolled_out <-
+ * rows added.  On any error the gallery is unchanged. */
+int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int n, const int32_t *labels, int32_t *status_out,
+                              frt_face_result *faces_out, float *embeds_out, int *first_row_out, int *n_enrolled_out);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).
  * ------------------------------------------------------------------------------------------------------------------ */
 /* kinds: 0 = off (drops the records), 1 = time every launch of the dominant kernel family (conv3x3 MFMA), 2 = time every stage,

@@ -100,6 +100,7 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     ~ArcFaceIR50() {
         frtdetail::autoUnlink(false, &m_link);
         if (std::shared_ptr<frtdetail::CoalesceLink> l = link()) l->shutdown();  // the coalescer borrows this object's embedder and matcher (waits for calls inside it)
+        if (m_photoPipe) frt_pipeline_destroy(m_photoPipe);  // (enrolImages' pipeline borrows them too)
         frt_embedder_destroy(h_);
         frtdetail::retireObject(m_id);  // every thread drops its per-thread state of this object (page-locked similarity buffers) on its next access
     }
@@ -194,6 +195,49 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         if (!labelled) m_labelsSet = false;
         classNames.insert(classNames.end(), names.begin(), names.end());
         classCount += (int)names.size();
+    }
+    // Extension: /insert/face WITHOUT api_imgIsCropped (src/app.cpp:163-187) for n whole photos of any sizes (8UC3) in one call: each photo is
+    // stretched to the frame size (cv::resize, INTER_LINEAR), detected and cropped on the device; a photo with exactly one face is embedded
+    // and enrolled, the others are refused as the handler refuses them - status[i] = FRT_ENROL_OK (1), FRT_ENROL_MANY (2: ret = 2),
+    // FRT_ENROL_NONE (3: ret = 3) or FRT_ENROL_EMPTY_ROI (4).  The accepted rows enter the live gallery device to device as ONE edit
+    // (frt_pipeline_enrol_images); classNames / classCount / labels move as in enrolFaces, by the accepted names only.  embeddingsOut (may be
+    // null; room for [n x outputDim]): the rows added, in image order - what db.insertFace stores.  The object keeps one pipeline, created at
+    // the first call for the detector's maxBatchSize frames (the recogniser needs maxBatchSize >= that x maxFacesPerScene for one pass per
+    // chunk; smaller works, in several passes); the detector must outlive this object or the next call with another detector.
+    // With labels in use (matchTopIdentities) every name is interned before the call, as enrolFaces does - the labels must exist when the
+    // photos go in - so the name of a refused photo keeps a label that no row carries yet; answers do not change, a later enrolment of that
+    // name reuses it.
+    template <class Detector>
+    void enrolImages(Detector &detector, const std::vector<std::string> &names, const std::vector<cv::Mat> &images, std::vector<int> &status,
+                     float *embeddingsOut = nullptr) {
+        assert(names.size() == images.size());
+        if (matmul.numRows() == 0 && classNames.empty()) {
+            matmul.galleryBegin(0, m_OUTPUT_D);
+            matmul.galleryCommit();
+        }
+        if (m_photoPipe && m_photoDet != detector.handle()) {
+            frt_pipeline_destroy(m_photoPipe);
+            m_photoPipe = nullptr;
+        }
+        if (!m_photoPipe) {
+            int maxBatch = 1;
+            checkFrtStatus(frt_detector_geometry(detector.handle(), nullptr, nullptr, &maxBatch, nullptr, nullptr));
+            checkFrtStatus(frt_pipeline_create(detector.handle(), h_, matmul.handle(), maxBatch, &m_photoPipe));
+            m_photoDet = detector.handle();
+        }
+        const std::vector<frt_face_image> imgs = faceImages(images);
+        const bool labelled = m_labelsSet && matmul.numRows() > 0;
+        std::vector<int> labels;
+        for (size_t i = 0; labelled && i < names.size(); ++i) labels.push_back(internLabel(names[i]));
+        std::vector<int32_t> st(images.size(), 0);
+        int first = 0, enrolled = 0;
+        checkFrtStatus(frt_pipeline_enrol_images(m_photoPipe, imgs.data(), (int)imgs.size(), labelled ? labels.data() : nullptr, st.data(), nullptr,
+                                                 embeddingsOut, &first, &enrolled));
+        status.assign(st.begin(), st.end());
+        if (!labelled && enrolled > 0) m_labelsSet = false;
+        for (size_t i = 0; i < names.size(); ++i)
+            if (st[i] == FRT_ENROL_OK) classNames.push_back(names[i]);
+        classCount += enrolled;
     }
     // every row of that name, as /delete/user removes every face of the user; the rows behind them close up in order (the order a
     // /reload would read them in: src/db.cpp:316-346).  Returns how many there were.
@@ -468,6 +512,8 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         matmul.setLabels(labels.data(), (int)labels.size());
         m_labelsSet = true;
     }
+    frt_pipeline *m_photoPipe = nullptr;  // enrolImages: created at its first call, for m_photoDet
+    frt_detector *m_photoDet = nullptr;
     bool m_labelsSet = false;
     std::map<std::string, int> m_labelOf;
     std::vector<std::string> m_labelNames;
