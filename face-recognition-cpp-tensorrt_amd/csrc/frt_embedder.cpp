@@ -186,6 +186,46 @@ void frt_embedder::build(const frt::Blob &b) {
     d_lm = arena.alloc<float>((size_t)F * 10);
     zeros = arena.alloc<half_t>(256);
     HIPCHK(hipMemset(zeros, 0, 256 * sizeof(half_t)));
+    warm_strip_tables();
+}
+
+// The strip kernels read per-geometry tables whose first use on a device allocates and copies (kernels_arc.hip).  Every launch description
+// forward() can fill is planned here for every batch up to max_batch, so that first use happens now: never in steady state, never inside a
+// captured graph.  Only the strip family reads tables and it takes stride-1 3x3 convs only, so the launches that matter are conv1, a stride-1
+// conv2 as the plain unit tail (with its SE twin) and, for IR-SE, conv2 + BN into RES; the stride-2 descriptions (fused shortcut conv included)
+// and the 1x1 shortcut launch never reach it and are planned here only as far as they share these lines.  A description this list misses
+// would still run - its first launch makes the table - except on a stream that is being captured, where that launch is refused with a message.
+void frt_embedder::warm_strip_tables() {
+    const ActSet &A = act[0];
+    for (const ArcUnit &u : units) {
+        const int h = u.h_in, ho = h / u.stride;
+        for (int F = 1; F <= max_batch; ++F) {
+            ConvMfmaArgs a{};
+            a.x = A.Z[0]; a.w = u.w1; a.wf = u.w1f;
+            a.B = F; a.H = h; a.W = h; a.Cin = u.cin; a.Ho = h; a.Wo = h; a.Cout = u.depth; a.ks = 3; a.stride = 1; a.pad = 1;
+            a.mode = EPI_PRELU;
+            a.out0 = A.T;
+            a.splits = 1;
+            conv_strip_tables_warm(a, conv_plan(a));
+            ConvMfmaArgs c{};
+            c.x = A.T; c.w = u.w2; c.wf = u.w2f; c.wf2 = u.w2f2;
+            c.B = F; c.H = h; c.W = h; c.Cin = u.depth; c.Ho = ho; c.Wo = ho; c.Cout = u.depth; c.ks = 3; c.stride = u.stride; c.pad = 1;
+            c.splits = 1;
+            c.mode = EPI_BN_ADD_BN;
+            c.sc = A.Y[0];
+            c.sc_h = h; c.sc_w = h; c.sc_stride = u.stride;
+            if (&u == &units[0] || u.wsc) c.sc_h = ho, c.sc_w = ho, c.sc_stride = 1;
+            c.out0 = A.Y[1]; c.out1 = A.Z[1];
+            if (se) c.se_pool = A.se_pool, c.se_w1 = u.se_w1, c.se_w2 = u.se_w2, c.se_counter = A.se_counter;
+            conv_strip_tables_warm(c, conv_plan(c));  // (with its SE twin, when the plan has one)
+            if (se) {  // conv2 + BN into RES, the SE tail as launches of its own
+                ConvMfmaArgs f = c;
+                f.mode = EPI_BN;
+                f.out0 = A.RES; f.out1 = nullptr; f.sc = nullptr;
+                conv_strip_tables_warm(f, conv_plan(f));
+            }
+        }
+    }
 }
 
 void frt_embedder::alloc_act_set(ActSet &a) {

@@ -102,6 +102,7 @@ struct frt_embedder {
     void forward_f32(const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s);
 
     void build(const frt::Blob &b);
+    void warm_strip_tables();
     // chw_dev [F][3][112][112] -> out_dev [F][512] on activation set `set`; F <= max_batch
     void forward(int set, const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s);
 };

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/frt.h"
 #include "frt_faces.hpp"
 
@@ -283,7 +285,39 @@ struct ConvMfmaArgs {
     int se_flag_off;
     int se_epoch;        // launch number (> 0, different from every earlier launch's on this scratch): what the flags are set to
     int *se_error;       // error word in mapped host memory: set (to the launch number) when a hand-over wait timed out
+    // strip family only, attached by its launchers (never by a caller; null when value-initialised): the device copy of the launch
+    // geometry's strip tables (strip_tables below), its period in strips and the pixels one period covers
+    const int *strip_tab;
+    int strip_period, strip_ppx;
 };
+// Strip tables: everything conv_patch_body (kernels_arc.hip) needs per thread that depends only on the strip geometry and on the strip's
+// position in its period - never on the tensors, the weights, the cout tile, Cin or the batch.  One block of `stride` ints per position:
+//   [0, nslot * threads)   poff[q][t]: the input pixel, relative to the period's first pixel, that DMA slot q of thread t copies one
+//                          16-byte piece of; -1 where the slot is structurally dead (halo, separator row, padding piece, past the patch)
+//   [.., + nt * 64)        pbase[j][lane]: LDS byte offset of the B fragment of pixel tile j for tap (0, 0)
+//   compact strips:        [nt][2] 64-bit lane masks: the lanes of tile j whose pixel sits in the first / last image column
+//   padded strips:         eoff[nt * 32]: pixel slot -> output pixel relative to the period's first pixel, -1 for dead slots
+// Periods: a compact strip is nt * 32 consecutive pixels, so the (image, row) phase repeats every lcm(H * W, nt * 32) pixels (14x14 in 7 tiles:
+// 7 strips = 8 images; 7x7 in 4 tiles: 49 strips = 128 images); a padded strip repeats with the strips of one image group.
+struct StripGeometry {
+    int H, W;
+    int compact;  // conv_patchc_kernel: consecutive pixels of the stacked images; else rows of n_img images with halo columns
+    int linear;   // padded strips: slots enumerated over the padded row width
+    int nt;       // pixel tiles per strip
+    int R;        // image rows per strip (compact: rows of the patch window)
+    int n_img;    // images per strip (padded strips)
+    int nslot;    // DMA slots per thread
+    int threads;  // threads that stage one patch: 256, or 128 in pair mode
+};
+struct StripTables {
+    int period = 0;  // strips
+    int ppx = 0;     // pixels per period
+    int stride = 0;  // ints per strip position
+    std::vector<int> data;  // [period][stride]
+};
+constexpr int strip_table_stride(const StripGeometry &g) { return g.nslot * g.threads + g.nt * 64 + (g.compact ? g.nt * 4 : g.nt * 32); }
+// pure host function (no HIP call), exact integer division throughout
+StripTables strip_tables(const StripGeometry &g);
 // One conv launch, decided once: the instantiation that runs, the geometry its launcher needs, its label.  conv_plan() is a pure host
 // function of the arguments (no HIP call: it runs on a machine without a device) and the ONE place a recogniser kernel is registered:
 // an ordered list of families, each of which owns a table of (label, launcher) rows - one row per instantiation.
@@ -321,6 +355,11 @@ inline void conv_plan_se_twin(ConvPlan &p, const ConvRow *table, const ConvMfmaA
     p.se_label = table[p.se_row].label;
 }
 ConvPlan conv_plan(const ConvMfmaArgs &a);
+// the strip geometry of a planned launch; false: the plan's kernel reads no table (another family, the im2col kernel)
+bool conv_strip_geometry(const ConvMfmaArgs &a, const ConvPlan &p, StripGeometry &g);
+// first use of the launch's geometry on the current device: checks every entry, allocates and copies (so synchronises); frt_embedder::build()
+// calls it for every plan it can reach, so that no launch allocates in steady state or inside a captured graph
+void conv_strip_tables_warm(const ConvMfmaArgs &a, const ConvPlan &p);
 void launch_conv_mfma(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s);
 bool conv_se_fits_device();  // HIP query, once per device: enough workgroups of the SE-tail instantiations are resident together (kernels_arc.hip)
 // the families, in conv_plan's order; plan_X: false = not this family's launch (p untouched)

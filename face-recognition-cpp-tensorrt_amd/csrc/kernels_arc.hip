@@ -24,7 +24,14 @@
 #include "frt_kernels.h"
 #include "frt_se_device.h"
 
+#include <array>
+#include <map>
+#include <mutex>
+#include <stdexcept>
+#include <string>
 #include <type_traits>
+#include <utility>
+#include <vector>
 
 namespace {
 
@@ -299,9 +306,6 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
     char *patch = smem + (PAIR ? (wave >> 1) * PATCH_B : 0);  // LDS holds ONLY patches; weights go L2 -> registers
     const int r = lane & 31, hi = lane >> 5;
     const int H = p.H, W = p.W, Wp = CPT ? W : W + 2;
-    const int NP = CPT ? R * W + 1 : n_img * (R + 2) * Wp;
-    const int strips_per_img = (H + R - 1) / R;  // (the last strip of an image may be ragged - linear enumeration only, see patch_geometry)
-    const int n_valid = n_img * R * W;
 
     const int n_co_tiles = PAIR ? 1 : p.Cout >> 7;
     const int nblk = gridDim.x, bq = nblk >> 3, brem = nblk & 7;
@@ -311,54 +315,21 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
     const int strip = PAIR ? (lid / n_co_tiles) * 2 + (wave >> 1) : lid / n_co_tiles;
     const int co_base = PAIR ? 0 : co_tile * 128;
     const int cow = PAIR ? (wave & 1) * 32 : wave * 32;  // this wave's cout rows inside the tile
+    // ---- the strip's place in its period (frt_kernels.h, "Strip tables"): everything below that depends only on the geometry, the strip and the
+    //      thread comes from the table block of position sp; the period's first pixel enters as one wave-uniform offset
+    const int per_idx = strip / p.strip_period, sp = strip - per_idx * p.strip_period;
+    const int pix_off = per_idx * p.strip_ppx;
+    const int Mpix = p.B * H * W;
+    const int img0 = CPT ? 0 : per_idx * n_img;
     const int c_mlo = strip * (NT * 32);  // compact: first pixel of the strip
-    const bool strip_ok = CPT ? c_mlo < p.B * H * W : strip < ((p.B + n_img - 1) / n_img) * strips_per_img;
-    const int img0 = CPT ? 0 : (strip / strips_per_img) * n_img;
-    const int row0 = CPT ? 0 : (strip % strips_per_img) * R;
-    // compact: image / in-image offset of the first pixel, and the STACKED row (image b occupies rows b*(H+1) .. b*(H+1)+H-1, row b*(H+1)+H is
-    // the zero separator) of patch row 0 = one above the first pixel's (wave-uniform divisions, once)
-    const int c_img_lo = CPT ? c_mlo / (H * W) : 0;
-    const int c_rem_lo = CPT ? c_mlo - c_img_lo * (H * W) : 0;
-    const int c_top = CPT ? c_img_lo * (H + 1) + c_rem_lo / W - 1 : 0;
+    const bool strip_ok = CPT ? c_mlo < Mpix : pix_off < Mpix;
+    constexpr int TTHR = PAIR ? 128 : 256;
+    constexpr int T_PBASE = NSLOT * TTHR, T_TAIL = T_PBASE + NT * 64, T_STRIDE = T_TAIL + (CPT ? NT * 4 : NT * 32);
+    const int *__restrict__ tab = p.strip_tab + sp * T_STRIDE;
+    const int tt = PAIR ? (wave & 1) * 64 + lane : tid;  // this thread among those that stage its patch
 
     const int n_chunks = p.Cin >> 6;
 
-    // ---- patch DMA descriptors: slot q of this lane covers 16-byte chunk g = (q*4 + wave)*64 + lane of the patch image
-    //      (round 5: the two divisions by run-time values per descriptor are reciprocal multiplies with one correction step - integer division
-    //      is ~ 40 instructions on this ISA, and conv_s2_kernel's phase stamps had shown 12 us of such arithmetic in front of its first DMA)
-    int poff[NSLOT];
-    {
-        const int patch_px = (R + 2) * Wp;
-        const float inv_patch = 1.0f / (float)patch_px, inv_wp = 1.0f / (float)Wp;
-#pragma unroll
-        for (int q = 0; q < NSLOT; ++q) {
-            const int g = PAIR ? (q * 2 + (wave & 1)) * 64 + lane : (q * 4 + wave) * 64 + lane;
-            const int prow = g / 9, pos = g - prow * 9;
-            if constexpr (CPT) {
-                const int pp = prow - 1;  // patch pixel 0 is the zero pixel
-                const float inv_w = 1.0f / (float)W, inv_h1 = 1.0f / (float)(H + 1);
-                int pr = (int)(((float)pp + 0.5f) * inv_w);
-                int pc = pp - pr * W;
-                if (pc < 0) { --pr; pc += W; } else if (pc >= W) { ++pr; pc -= W; }
-                const int sr = c_top + pr;
-                int b = (int)(((float)sr + 0.5f) * inv_h1);
-                int iy = sr - b * (H + 1);
-                if (iy < 0) { --b; iy += H + 1; } else if (iy > H) { ++b; iy -= H + 1; }
-                const bool live = pos < 8 && pp >= 0 && pr < R && strip_ok && sr >= 0 && b < p.B && iy < H;
-                poff[q] = live ? ((b * H + iy) * W + pc) * p.Cin + pos * 8 : -1;
-                continue;
-            }
-            int il = (int)(((float)prow + 0.5f) * inv_patch);
-            int rem = prow - il * patch_px;
-            if (rem < 0) { --il; rem += patch_px; } else if (rem >= patch_px) { ++il; rem -= patch_px; }
-            int pr = (int)(((float)rem + 0.5f) * inv_wp);
-            int pc = rem - pr * Wp;
-            if (pc < 0) { --pr; pc += Wp; } else if (pc >= Wp) { ++pr; pc -= Wp; }
-            const int iy = row0 + pr - 1, ix = pc - 1, b = img0 + il;
-            const bool live = pos < 8 && prow < NP && strip_ok && b < p.B && iy >= 0 && iy < H && ix >= 0 && ix < W;
-            poff[q] = live ? ((b * H + iy) * W + ix) * p.Cin + pos * 8 : -1;
-        }
-    }
     // ---- weights: each wave consumes only its own 32 cout rows, so the A fragments never touch LDS: lane (r, hi) loads its
     //      four 16-byte fragments (kk = 0..3) of W[co_base + wave*32 + r][tap][chunk*64 + (kk*2+hi)*8 ..] straight from L2 into
     //      registers, two steps ahead (register ring of 3 steps, index = tap % 3 at compile time).  This removes the weight
@@ -368,42 +339,13 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
     //      wave walks its 32 couts' weights as one sequential stream (row-major rows made every load touch 32 different 128-byte lines,
     //      32 bytes of each: four times the address/tag work for the same bytes).
     const half_t *wfrag = p.wf + ((long)((co_base + cow) >> 5) * n_chunks) * (9 * 4 * 512) + lane * 8;
+    // ---- patch DMA descriptors: slot q of this lane covers 16-byte chunk g = q * TTHR + tt of the patch image (piece pos = g % 9 of patch
+    //      pixel g / 9); the table holds the input pixel, the kernel supplies * Cin + pos * 8 and the chunk offset
+    int poff[NSLOT];
     // ---- B-fragment base addresses: pixel slot -> patch row of tap (0,0)
     int pbase[NT];
     unsigned long long mL[CPT ? NT : 1], mR[CPT ? NT : 1];  // compact: lanes whose pixel sits in the first / last image column (wave-uniform masks)
     const int zoff = hi * 16;                               // ... and where those lanes read instead for kw = 0 / kw = 2: the zero pixel
-#pragma unroll
-    for (int j = 0; j < NT; ++j) {
-        const int sl = j * 32 + r;
-        int pidx = 0;
-        if constexpr (CPT) {
-            const int u = c_rem_lo + sl;  // < H*W + NT*32
-            const int per = H * W;
-            int il = (int)(((float)u + 0.5f) * (1.0f / (float)per));
-            int rem = u - il * per;
-            if (rem < 0) { --il; rem += per; } else if (rem >= per) { ++il; rem -= per; }
-            int rr = (int)(((float)rem + 0.5f) * (1.0f / (float)W));
-            int cc = rem - rr * W;
-            if (cc < 0) { --rr; cc += W; } else if (cc >= W) { ++rr; cc -= W; }
-            const bool in = c_mlo + sl < p.B * per;
-            // own input pixel = patch pixel 1 + (stacked row - c_top) * W + cc; tap (kh, kw) reads that + (kh - 1) * W + (kw - 1)
-            pidx = in ? ((c_img_lo + il) * (H + 1) + rr - c_top) * W + cc - W : 0;
-            mL[j] = __builtin_amdgcn_ballot_w64(cc == 0);
-            mR[j] = __builtin_amdgcn_ballot_w64(cc == W - 1);
-        } else if (linear) {
-            pidx = sl < R * Wp ? sl : 0;
-        } else if (sl < n_valid) {
-            const int per = R * W;
-            int il = (int)(((float)sl + 0.5f) * (1.0f / (float)per));
-            int rem = sl - il * per;
-            if (rem < 0) { --il; rem += per; } else if (rem >= per) { ++il; rem -= per; }
-            int rr = (int)(((float)rem + 0.5f) * (1.0f / (float)W));
-            int cc = rem - rr * W;
-            if (cc < 0) { --rr; cc += W; } else if (cc >= W) { ++rr; cc -= W; }
-            pidx = (il * (R + 2) + rr) * Wp + cc;
-        }
-        pbase[j] = pidx * PROW + hi * 16;
-    }
 
     half8 areg[WR][4];
     constexpr int LA = WR - 1;  // weight fragments are fetched LA steps ahead
@@ -431,8 +373,8 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[j][e] = 0.f;
 
-    // prologue: patch(0) completely, then the weight fragments of steps 0 and 1
-    issue_patch(0, std::integral_constant<int, 0>{}, std::integral_constant<int, NSLOT>{});
+    // prologue: the weight fragments of the first steps go out first - they need nothing but wfrag - then the table entries (coalesced
+    // kilobyte loads), the one liveness test that depends on the batch, and patch(0) completely
     load_w(0, 0, std::integral_constant<int, 0>{});
     load_w(0, 1, std::integral_constant<int, 1>{});
     if constexpr (WR == 9) {
@@ -443,6 +385,33 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
         load_w(0, 6, std::integral_constant<int, 6>{});
         load_w(0, 7, std::integral_constant<int, 7>{});
     }
+    {
+#pragma unroll
+        for (int q = 0; q < NSLOT; ++q) poff[q] = tab[q * TTHR + tt];
+#pragma unroll
+        for (int j = 0; j < NT; ++j) pbase[j] = tab[T_PBASE + j * 64 + lane];
+        if constexpr (CPT) {
+            const unsigned long long *__restrict__ tm = reinterpret_cast<const unsigned long long *>(tab + T_TAIL);
+#pragma unroll
+            for (int j = 0; j < NT; ++j) {
+                mL[j] = tm[2 * j];
+                mR[j] = tm[2 * j + 1];
+            }
+        }
+        const int t9 = tt % 9;
+#pragma unroll
+        for (int q = 0; q < NSLOT; ++q) {
+            int pos = t9 + (q * TTHR) % 9;
+            pos = pos >= 9 ? pos - 9 : pos;
+            const int px = poff[q] + pix_off;
+            poff[q] = (poff[q] >= 0 && strip_ok && px < Mpix) ? px * p.Cin + pos * 8 : -1;
+        }
+        if constexpr (CPT) {  // pixel slots behind the batch read the zero pixel
+#pragma unroll
+            for (int j = 0; j < NT; ++j) pbase[j] = c_mlo + j * 32 + r < Mpix ? pbase[j] : zoff;
+        }
+    }
+    issue_patch(0, std::integral_constant<int, 0>{}, std::integral_constant<int, NSLOT>{});
 
     // (An L2 warm-up - every workgroup of an XCD pulling a different slice of the cout tile's weights through L2 at kernel start,
     //  LDS-DMA into the still unused second patch buffer - measured 45.1 us against 44.4 us without: not kept.)
@@ -461,7 +430,7 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
         if constexpr (CPT && T % 3 == 2) a = __builtin_amdgcn_inverse_ballot_w64(mR[j]) ? zoff + bufoff : a;
         return *reinterpret_cast<const half8 *>(patch + a + kko * 32);
     };
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * LA) : "memory");  // this wave's patch(0) pieces have landed (younger: the 4*LA fragment loads)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's patch(0) pieces have landed (they are the youngest requests)
     __builtin_amdgcn_s_barrier();                     // ... and everybody else's
 #pragma unroll
     for (int k2 = 0; k2 < BFD; ++k2)
@@ -513,11 +482,28 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
         step(c, std::integral_constant<int, 7>{});
         step(c, std::integral_constant<int, 8>{});
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tail's dummy DMAs still target LDS
-    __syncthreads();
-
     // ------------------------------------------------------------------ epilogue (per wave: 32 couts x 7 pixel tiles) through LDS
     constexpr int EROW = 36;  // floats per pixel row (32 + 4 pad)
+    // padded strips: the slot -> output pixel map of this strip position (relative to the period's first pixel, -1 for dead slots) is requested
+    // here, lands under the last barrier and is parked in LDS behind the transpose tiles and the SE tail's scratch
+    constexpr int ESLOTS = (NT * 32 + TTHR - 1) / TTHR;
+    int *eL = reinterpret_cast<int *>(smem + 4 * 32 * EROW * 4 + (576 + 2 * 128) * 4) + (PAIR ? (wave >> 1) * (NT * 32) : 0);
+    static_assert(4 * 32 * EROW * 4 + (576 + 2 * 128) * 4 + 2 * 7 * 32 * 4 <= 2 * 5 * 4096, "slot map behind the epilogue scratch of the smallest patch buffer pair");
+    int ev[ESLOTS];
+    (void)ev;
+    if constexpr (!CPT) {
+#pragma unroll
+        for (int i = 0; i < ESLOTS; ++i) ev[i] = tt + i * TTHR < NT * 32 ? tab[T_TAIL + tt + i * TTHR] : -1;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the tail's dummy DMAs still target LDS
+    __syncthreads();
+    if constexpr (!CPT) {
+#pragma unroll
+        for (int i = 0; i < ESLOTS; ++i)
+            if (tt + i * TTHR < NT * 32) eL[tt + i * TTHR] = ev[i];
+        __syncthreads();
+    }
+
     float *ep = reinterpret_cast<float *>(smem) + wave * (32 * EROW);
     const int chunk = lane & 3;
     const int cch = co_base + cow + chunk * 8;
@@ -534,84 +520,98 @@ __device__ __forceinline__ void conv_patch_body(const ConvMfmaArgs &p, int R, in
         q3[0] = *reinterpret_cast<const floatx4 *>(p.p3 + cch);
         q3[1] = *reinterpret_cast<const floatx4 *>(p.p3 + cch + 4);
     }
-    // pixel slots of a strip are CONTIGUOUS in the flattened (image, row, column) index: m = m0 + slot (no divisions)
-    const long m0 = CPT ? (long)c_mlo : ((long)img0 * H + row0) * W;
-    const long Mtot = (long)p.B * H * W;
-    const float inv_wp = 1.0f / (float)Wp;
-    auto slot_pixel = [&](int sl, long &m) -> bool {  // pixel slot -> flattened output pixel index; false for dead slots
+    // Output pixels are addressed from the wave-uniform pixel mbase: the strip's first pixel (compact: slot sl is pixel mbase + sl) or the
+    // period's (padded: mbase + the slot map's entry).  The bounds test against the batch is taken once: a strip whose pixels (whose image
+    // group) all lie inside the batch is the wave-uniform case `full`; only the one ragged strip of a launch tests per pixel.
+    const int mbase = CPT ? c_mlo : pix_off;
+    const bool full = CPT ? c_mlo + NT * 32 <= Mpix : pix_off + p.strip_ppx <= Mpix;
+    auto slot_rel = [&](int sl, auto full_c, int &rel) -> bool {  // pixel slot -> output pixel - mbase; false for dead slots
+        constexpr bool FULL = decltype(full_c)::value;
         if constexpr (CPT) {
-            m = m0 + sl;
-            return m < Mtot;
+            rel = sl;
+            return FULL || mbase + rel < Mpix;
         }
-        if (linear) {
-            const int rr = (int)(((float)sl + 0.5f) * inv_wp);  // exact for sl < 2^20
-            const int cc = sl - rr * Wp;
-            m = m0 + rr * W + cc;
-            return strip_ok && rr < R && row0 + rr < H && cc < W && m < Mtot;
-        }
-        m = m0 + sl;
-        return strip_ok && sl < n_valid && m < Mtot;
+        rel = eL[sl];
+        return rel >= 0 && (FULL || mbase + rel < Mpix);
     };
     if constexpr (SEP) {  // IR-SE: the whole SE tail here (frt_se_device.h)
         const int per_img = R * W;  // (compact slot enumeration when the strip holds more than one image)
-        se_tail_epilogue<NT, (NT == 4 ? 2 : 1)>(p, acc, ep, reinterpret_cast<float *>(smem + 4 * 32 * EROW * 4), strip % strips_per_img, strips_per_img,
+        se_tail_epilogue<NT, (NT == 4 ? 2 : 1)>(p, acc, ep, reinterpret_cast<float *>(smem + 4 * 32 * EROW * 4), sp, p.strip_period,
                                                n_co_tiles, img0, n_img, H * W, co_base, cow, [&](int sl, long &m, int &il) -> bool {
                                                    il = (NT == 4 && !linear && sl >= per_img) ? 1 : 0;
-                                                   return slot_pixel(sl, m);
+                                                   int rel;
+                                                   const bool ok = slot_rel(sl, std::false_type{}, rel);
+                                                   m = (long)mbase + rel;
+                                                   return ok;
                                                });
         return;
     }
-    half8 sc8[NT][2];
-    if (p.mode == EPI_BN_ADD_BN) {  // stride 1: the shortcut has the output's geometry; all 14 loads in flight before the transposes
+    // one 64-bit base per wave and tensor, 32-bit offsets per store: compile-time multiples of the wave-uniform Cout plus one lane term
+    const size_t wbase = (size_t)mbase * p.Cout;
+    half_t *const o0 = p.out0 + wbase;
+    half_t *const o1 = p.out1 ? p.out1 + wbase : nullptr;
+    const half_t *const scw = p.mode == EPI_BN_ADD_BN ? p.sc + wbase : nullptr;
+    const unsigned lane_off = (unsigned)((lane >> 2) * p.Cout + cch);
+    auto write_out = [&](auto full_c) {
+        constexpr bool FULL = decltype(full_c)::value;
+        auto offset_of = [&](int j, int it, int rel) -> unsigned {
+            if constexpr (CPT) return (unsigned)((j * 32 + 16 * it) * p.Cout) + lane_off;
+            return (unsigned)(rel * p.Cout + cch);
+        };
+        half8 sc8[NT][2];
+        if (p.mode == EPI_BN_ADD_BN) {  // stride 1: the shortcut has the output's geometry; all 14 loads in flight before the transposes
 #pragma unroll
-        for (int j = 0; j < NT; ++j)
+            for (int j = 0; j < NT; ++j)
+#pragma unroll
+                for (int it = 0; it < 2; ++it) {
+                    int rel;
+                    const bool ok = slot_rel(j * 32 + (lane >> 2) + 16 * it, full_c, rel);
+                    if constexpr (CPT && FULL) sc8[j][it] = *reinterpret_cast<const half8 *>(scw + offset_of(j, it, rel));
+                    else sc8[j][it] = *reinterpret_cast<const half8 *>(ok ? scw + offset_of(j, it, rel) : p.sc + cch);
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const floatx4 v = {acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]};
+                *reinterpret_cast<floatx4 *>(ep + r * EROW + 8 * g + 4 * hi) = v;
+            }
 #pragma unroll
             for (int it = 0; it < 2; ++it) {
-                const int sl = j * 32 + (lane >> 2) + 16 * it;
-                long m;
-                const bool ok = slot_pixel(sl, m);
-                sc8[j][it] = *reinterpret_cast<const half8 *>(p.sc + (ok ? m : 0) * p.Cout + cch);
-            }
-    }
+                const int px = (lane >> 2) + 16 * it;
+                const floatx4 v0 = *reinterpret_cast<const floatx4 *>(ep + px * EROW + chunk * 8);
+                const floatx4 v1 = *reinterpret_cast<const floatx4 *>(ep + px * EROW + chunk * 8 + 4);
+                int rel;
+                if (!slot_rel(j * 32 + px, full_c, rel)) continue;
+                const unsigned off = offset_of(j, it, rel);
+                float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                if (p.mode == EPI_PRELU) {
 #pragma unroll
-    for (int j = 0; j < NT; ++j) {
+                    for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * q0[e >> 2][e & 3];
+                } else {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const floatx4 v = {acc[j][4 * g], acc[j][4 * g + 1], acc[j][4 * g + 2], acc[j][4 * g + 3]};
-            *reinterpret_cast<floatx4 *>(ep + r * EROW + 8 * g + 4 * hi) = v;
-        }
+                    for (int e = 0; e < 8; ++e) v[e] = v[e] * q0[e >> 2][e & 3] + q1[e >> 2][e & 3];
+                }
+                if (p.mode == EPI_BN_ADD_BN) {
 #pragma unroll
-        for (int it = 0; it < 2; ++it) {
-            const int px = (lane >> 2) + 16 * it;
-            const floatx4 v0 = *reinterpret_cast<const floatx4 *>(ep + px * EROW + chunk * 8);
-            const floatx4 v1 = *reinterpret_cast<const floatx4 *>(ep + px * EROW + chunk * 8 + 4);
-            const int sl = j * 32 + px;
-            long m;
-            if (!slot_pixel(sl, m)) continue;
-            float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-            if (p.mode == EPI_PRELU) {
+                    for (int e = 0; e < 8; ++e) v[e] += (float)sc8[j][it][e];
+                }
+                half8 o;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = v[e] > 0.f ? v[e] : v[e] * q0[e >> 2][e & 3];
-            } else {
+                for (int e = 0; e < 8; ++e) o[e] = (half_t)v[e];
+                *reinterpret_cast<half8 *>(o0 + off) = o;
+                if (p.mode == EPI_BN_ADD_BN && p.out1) {
+                    half8 z;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] = v[e] * q0[e >> 2][e & 3] + q1[e >> 2][e & 3];
-            }
-            if (p.mode == EPI_BN_ADD_BN) {
-#pragma unroll
-                for (int e = 0; e < 8; ++e) v[e] += (float)sc8[j][it][e];
-            }
-            half8 o;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) o[e] = (half_t)v[e];
-            *reinterpret_cast<half8 *>(p.out0 + m * p.Cout + cch) = o;
-            if (p.mode == EPI_BN_ADD_BN && p.out1) {
-                half8 z;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) z[e] = (half_t)(v[e] * q2[e >> 2][e & 3] + q3[e >> 2][e & 3]);
-                *reinterpret_cast<half8 *>(p.out1 + m * p.Cout + cch) = z;
+                    for (int e = 0; e < 8; ++e) z[e] = (half_t)(v[e] * q2[e >> 2][e & 3] + q3[e >> 2][e & 3]);
+                    *reinterpret_cast<half8 *>(o1 + off) = z;
+                }
             }
         }
-    }
+    };
+    if (full) write_out(std::true_type{});
+    else write_out(std::false_type{});
 }
 
 template <int PPS, int PT, int NW, bool SINGLE, bool PAIR = false, int NT = 7, int BFD = 2, int WR = 3, bool SEP = false>
@@ -878,6 +878,58 @@ bool patch_geometry(const ConvMfmaArgs &a, int &R, int &n_img, int &pps, bool &s
     return true;
 }
 
+// ---- strip tables on the device: one copy per (device, geometry), made on first use (frt_embedder::build() warms every geometry its plans reach)
+struct StripTabDev {
+    const int *dev;
+    int period, ppx;
+};
+// s: the stream of the launch that asks (null: the warm-up).  A thread finds the geometries it has launched before in a list of its own - no
+// lock on the steady-state path; a first use on a stream that is being captured is refused, since the allocation would break the capture.
+StripTabDev strip_tab_device(const StripGeometry &g, hipStream_t s = nullptr) {
+    static std::mutex mu;
+    static std::map<std::array<int, 10>, StripTabDev> cache;
+    thread_local std::vector<std::pair<std::array<int, 10>, StripTabDev>> mine;
+    int d = 0;
+    (void)hipGetDevice(&d);
+    const std::array<int, 10> key = {d, g.H, g.W, g.compact, g.linear, g.nt, g.R, g.n_img, g.nslot, g.threads};
+    for (const auto &e : mine)
+        if (e.first == key) return e.second;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = cache.find(key);
+    if (it == cache.end()) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone)
+            throw std::runtime_error("strip tables: first use of a strip geometry inside a stream capture (frt_embedder::build() warms every geometry it plans)");
+        const StripTables t = strip_tables(g);  // (throws when an entry fails its range check: nothing wrong reaches the device)
+        int *dev = nullptr;
+        if (hipMalloc(reinterpret_cast<void **>(&dev), t.data.size() * sizeof(int)) != hipSuccess ||
+            hipMemcpy(dev, t.data.data(), t.data.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+            throw std::runtime_error("strip tables: device allocation or copy failed");
+        it = cache.emplace(key, StripTabDev{dev, t.period, t.ppx}).first;
+    }
+    mine.emplace_back(key, it->second);
+    return it->second;
+}
+// what every launcher of the strip family does to its arguments: the pointers come from here, never from the caller
+ConvMfmaArgs with_strip_tables(const ConvMfmaArgs &a, const StripGeometry &g, hipStream_t s) {
+    if ((long)a.B * a.H * a.W * a.Cin >= (1L << 31)) throw std::runtime_error("strip kernel: the input tensor exceeds 32-bit element offsets");
+    const StripTabDev t = strip_tab_device(g, s);
+    ConvMfmaArgs b = a;
+    b.strip_tab = t.dev;
+    b.strip_period = t.period;
+    b.strip_ppx = t.ppx;
+    return b;
+}
+template <int PPS, int PT, bool PAIR, int NT>
+StripGeometry patch_strip_geometry(const ConvMfmaArgs &a, const ConvPlan &p) {
+    const int linear = (p.n_img == 1 && p.R * (a.W + 2) <= NT * 32) ? 1 : 0;
+    return StripGeometry{a.H, a.W, 0, linear, NT, p.R, p.n_img, PAIR ? 34 : PT * PPS, PAIR ? 128 : 256};
+}
+template <int NT>
+StripGeometry patchc_strip_geometry(const ConvMfmaArgs &a, const ConvPlan &p) {
+    return StripGeometry{a.H, a.W, 1, 0, NT, p.R, 1, 10, 256};
+}
+
 template <int PPS, int PT, int NW, bool SINGLE, bool PAIR = false, int NT = 7, int BFD = 2, int WR = 3, bool SEP = false>
 void launch_patch_t(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) {
     const int R = p.R, n_img = p.n_img;
@@ -890,8 +942,8 @@ void launch_patch_t(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) {
     }
     const int strips = ((a.B + n_img - 1) / n_img) * ((a.H + R - 1) / R);
     dim3 grid(PAIR ? (strips + 1) / 2 : strips * (a.Cout / 128));
-    const int linear = (n_img == 1 && R * (a.W + 2) <= NT * 32) ? 1 : 0;
-    hipLaunchKernelGGL((conv_patch_kernel<PPS, PT, NW, SINGLE, PAIR, NT, BFD, WR, SEP>), grid, dim3(256), lds, s, a, R, n_img, linear);
+    const StripGeometry g = patch_strip_geometry<PPS, PT, PAIR, NT>(a, p);
+    hipLaunchKernelGGL((conv_patch_kernel<PPS, PT, NW, SINGLE, PAIR, NT, BFD, WR, SEP>), grid, dim3(256), lds, s, with_strip_tables(a, g, s), R, n_img, g.linear);
 }
 
 // compact strips: rows of the stacked-image patch window the tallest strip of the launch needs (top halo + the rows its pixels touch, zero
@@ -918,7 +970,7 @@ void launch_patchc_t(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&conv_patchc_kernel<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     const long M = (long)a.B * a.H * a.W;
     const int strips = (int)((M + NT * 32 - 1) / (NT * 32));
-    hipLaunchKernelGGL((conv_patchc_kernel<NT>), dim3(strips * (a.Cout / 128)), dim3(256), lds, s, a, p.R);  // (R carries the patch's row count)
+    hipLaunchKernelGGL((conv_patchc_kernel<NT>), dim3(strips * (a.Cout / 128)), dim3(256), lds, s, with_strip_tables(a, patchc_strip_geometry<NT>(a, p), s), p.R);  // (R carries the patch's row count)
 }
 
 // The strip kernel's instantiations and the im2col kernel's, each with its symbol (the strip kernel's carries a tenth argument: SE tail in
@@ -952,6 +1004,25 @@ const ConvRow kStrip[] = {
     /* CV_PC_7         */ {"conv_patchc_kernel<7>", launch_patchc_t<7>, -1},
     /* CV_PC_4         */ {"conv_patchc_kernel<4>", launch_patchc_t<4>, -1},
 };
+
+// the same rows' strip geometries, for whoever holds a plan and not a launcher (conv_strip_geometry)
+typedef StripGeometry (*StripGeometryFn)(const ConvMfmaArgs &, const ConvPlan &);
+const StripGeometryFn kStripGeometry[] = {
+    /* CV_G2_22        */ nullptr,
+    /* CV_G2_14        */ nullptr,
+    /* CV_P_PAIR       */ patch_strip_geometry<3, 5, true, 7>,
+    /* CV_P_SINGLE     */ patch_strip_geometry<3, 5, false, 7>,
+    /* CV_P_255        */ patch_strip_geometry<10, 1, false, 7>,
+    /* CV_P_255_SE     */ patch_strip_geometry<10, 1, false, 7>,
+    /* CV_P_264        */ patch_strip_geometry<2, 6, false, 7>,
+    /* CV_P_255_NT4    */ patch_strip_geometry<10, 1, false, 4>,
+    /* CV_P_255_NT4_SE */ patch_strip_geometry<10, 1, false, 4>,
+    /* CV_P_NT2        */ patch_strip_geometry<5, 1, false, 2>,
+    /* CV_P_NT1        */ patch_strip_geometry<5, 1, false, 1>,
+    /* CV_PC_7         */ patchc_strip_geometry<7>,
+    /* CV_PC_4         */ patchc_strip_geometry<4>,
+};
+static_assert(sizeof(kStripGeometry) / sizeof(kStripGeometry[0]) == sizeof(kStrip) / sizeof(kStrip[0]), "one geometry per row");
 
 int strip_variant(const ConvMfmaArgs &a, int &R, int &n_img) {
     int slots, nt;
@@ -1000,6 +1071,122 @@ ConvPlan conv_plan(const ConvMfmaArgs &a) {
     if (plan_s2(a, p)) return p;     // stride-2 strip kernel on de-interleaved phase planes (kernels_arc_s2.hip)
     plan_strip(a, p);                // stride-1 strip kernel, or the im2col kernel
     return p;
+}
+
+bool conv_strip_geometry(const ConvMfmaArgs &a, const ConvPlan &p, StripGeometry &g) {
+    if (p.family != CONV_STRIP || !kStripGeometry[p.row]) return false;
+    g = kStripGeometry[p.row](a, p);
+    return true;
+}
+
+void conv_strip_tables_warm(const ConvMfmaArgs &a, const ConvPlan &p) {
+    StripGeometry g;
+    if (conv_strip_geometry(a, p, g)) (void)strip_tab_device(g);
+    if (p.se_fused()) {  // the twin with the SE tail has the row's geometry; asked for all the same
+        ConvPlan q = p;
+        q.take_se_tail();
+        if (conv_strip_geometry(a, q, g)) (void)strip_tab_device(g);
+    }
+}
+
+// Strip tables (frt_kernels.h), with exact integer division.  A wrong entry would be an out-of-bounds DMA or LDS read, so every entry is checked
+// against what its consumer can address before the tables are returned: input pixels inside one period (plus a compact window's height), every B-fragment read of every
+// tap inside the patch buffer, every mask bit on a lane whose pixel sits in that column, every output pixel inside the period.
+StripTables strip_tables(const StripGeometry &g) {
+    const int H = g.H, W = g.W, NT = g.nt, R = g.R, T = g.threads, P = H * W, S = NT * 32;
+    auto bad = [](const char *what) { throw std::runtime_error(std::string("strip tables: ") + what); };
+    if (H < 1 || W < 1 || NT < 1 || R < 1 || g.n_img < 1 || g.nslot < 1 || (T != 128 && T != 256)) bad("geometry");
+    StripTables t;
+    t.stride = strip_table_stride(g);
+    const int o_pbase = g.nslot * T, o_tail = o_pbase + NT * 64;
+    const int patch_bytes = g.nslot * T * 16, PROW = 144;
+    const int Wp = g.compact ? W : W + 2;
+    if (g.compact) {
+        int a = P, b = S;
+        while (b) { const int c = a % b; a = b; b = c; }
+        t.period = P / a;  // lcm(P, S) / S
+        t.ppx = t.period * S;
+    } else {
+        t.period = (H + R - 1) / R;
+        t.ppx = g.n_img * P;
+    }
+    t.data.assign((size_t)t.period * t.stride, -1);
+    for (int sp = 0; sp < t.period; ++sp) {
+        int *blk = t.data.data() + (size_t)sp * t.stride;
+        const int mlo = sp * S, img_lo = mlo / P, rem_lo = mlo % P;  // compact: the strip's first pixel, in the period
+        const int top = img_lo * (H + 1) + rem_lo / W - 1;           // ... and the stacked row (H rows + one separator per image) of patch row 0
+        const int row0 = sp * R;                                     // padded: the strip's first image row
+        const int patch_px = (R + 2) * Wp;
+        for (int q = 0; q < g.nslot; ++q)
+            for (int tt = 0; tt < T; ++tt) {
+                const int piece = q * T + tt, prow = piece / 9, pos = piece % 9;
+                int e = -1;
+                if (g.compact) {
+                    const int pp = prow - 1;  // patch pixel 0 is the zero pixel
+                    if (pos < 8 && pp >= 0 && pp / W < R && top + pp / W >= 0) {
+                        const int sr = top + pp / W, b = sr / (H + 1), iy = sr % (H + 1);
+                        if (iy < H) e = (b * H + iy) * W + pp % W;
+                    }
+                } else if (pos < 8 && prow < g.n_img * patch_px) {
+                    const int il = prow / patch_px, rem = prow % patch_px;
+                    const int iy = row0 + rem / Wp - 1, ix = rem % Wp - 1;
+                    if (iy >= 0 && iy < H && ix >= 0 && ix < W) e = (il * H + iy) * W + ix;
+                }
+                // (a compact window is as tall as the launch's tallest strip needs: the last strips of a period reach into the next one's first rows)
+                if (e < -1 || e >= t.ppx + (g.compact ? R * W : 0)) bad("input pixel outside the period");
+                blk[q * T + tt] = e;
+            }
+        for (int j = 0; j < NT; ++j) {
+            unsigned long long mL = 0, mR = 0;
+            for (int lane = 0; lane < 64; ++lane) {
+                const int r = lane & 31, hi = lane >> 5, sl = j * 32 + r;
+                int pidx = 0;
+                bool first = false, last = false;
+                if (g.compact) {
+                    const int u = rem_lo + sl, il = u / P, rem = u % P, rr = rem / W, cc = rem % W;
+                    // own input pixel = patch pixel 1 + (stacked row - top) * W + cc; tap (kh, kw) reads that + (kh - 1) * W + (kw - 1)
+                    pidx = ((img_lo + il) * (H + 1) + rr - top) * W + cc - W;
+                    first = cc == 0;
+                    last = cc == W - 1;
+                    if ((mlo + sl) % P % W != cc) bad("column of a compact slot");
+                } else if (g.linear) {
+                    pidx = sl < R * Wp ? sl : 0;
+                } else if (sl < g.n_img * R * W) {
+                    const int per = R * W, il = sl / per, rem = sl % per;
+                    pidx = (il * (R + 2) + rem / W) * Wp + rem % W;
+                }
+                const int pb = pidx * PROW + hi * 16;
+                for (int tap = 0; tap < 9; ++tap) {  // the reads of the lanes the masks do not redirect: kk slots 0..3 of 16 bytes each side
+                    if ((tap % 3 == 0 && first) || (tap % 3 == 2 && last)) continue;
+                    const int at = pb + ((tap / 3) * Wp + tap % 3) * PROW;
+                    if (at < 0 || at + 3 * 32 + 16 > patch_bytes) bad("B fragment outside the patch buffer");
+                }
+                blk[o_pbase + j * 64 + lane] = pb;
+                if (first) mL |= 1ull << lane;
+                if (last) mR |= 1ull << lane;
+            }
+            if (g.compact) {
+                if ((mL >> 32) != (mL & 0xffffffffull) || (mR >> 32) != (mR & 0xffffffffull)) bad("mask halves differ");
+                blk[o_tail + 4 * j + 0] = (int)(mL & 0xffffffffull);
+                blk[o_tail + 4 * j + 1] = (int)(mL >> 32);
+                blk[o_tail + 4 * j + 2] = (int)(mR & 0xffffffffull);
+                blk[o_tail + 4 * j + 3] = (int)(mR >> 32);
+            }
+        }
+        if (!g.compact)
+            for (int sl = 0; sl < S; ++sl) {
+                int e = -1;
+                if (g.linear) {
+                    const int rr = sl / Wp, cc = sl % Wp;
+                    if (rr < R && row0 + rr < H && cc < W) e = (row0 + rr) * W + cc;
+                } else if (sl < g.n_img * R * W) {
+                    e = row0 * W + sl;
+                }
+                if (e < -1 || e >= t.ppx) bad("output pixel outside the period");
+                blk[o_tail + sl] = e;
+            }
+    }
+    return t;
 }
 
 void launch_conv_mfma(const ConvMfmaArgs &a, const ConvPlan &p, hipStream_t s) {
