@@ -1,6 +1,9 @@
 // libfrt.so: the recogniser object (weights, fp16 and fp32 networks) and its C ABI (frt_embedder_*, frt_crop_faces, frt_align_faces).
 // All device work is hand-written HIP (kernels_*.hip); there is no CPU fallback anywhere in this file: without a HIP
 // device every entry point that needs one fails with FRT_ERR_DEVICE.
+#include <array>
+#include <set>
+
 #include "frt_embedder.hpp"
 #include "frt_arc_pack.hpp"
 #include "frt_matcher.hpp"
@@ -122,13 +125,11 @@ void frt_embedder::build(const frt::Blob &b) {
             std::vector<float> w2v = vec_of(b, p + ".res_layer.3.weight", (size_t)a.depth * a.depth * 9);
             const std::vector<float> dinv = condition_branch(w1v, w2v, a.cin, a.depth);
             a.w1 = reinterpret_cast<half_t *>(arena.upload(conv_w_f16(w1v.data(), a.depth, a.cin, 3)));
-            {  // conv1 is always stride 1; conv2 only in the units that keep the resolution
-                const std::vector<uint16_t> f1 = conv_w_f16_frag(w1v.data(), a.depth, a.cin);
-                if (!f1.empty()) a.w1f = reinterpret_cast<half_t *>(arena.upload(f1));
-                // the 64 -> 64 stride-2 layer has its own kernel that stages rows in natural order and walks the taps in tap order
-                const std::vector<uint16_t> f2 = conv_w_f16_frag(w2v.data(), a.depth, a.depth, a.stride == 2 && a.depth != 64);
-                if (!f2.empty()) (a.stride == 1 ? a.w2f : a.w2f2) = reinterpret_cast<half_t *>(arena.upload(f2));
-            }
+            const ArcUnitCopies copies = arc_unit_copies(a.cin, a.depth, a.stride);  // (arc_layout's widths are multiples of 64: no packer declines)
+            if (copies.w1f) a.w1f = reinterpret_cast<half_t *>(arena.upload(conv_w_f16_frag(w1v.data(), a.depth, a.cin)));
+            if (copies.w2f) a.w2f = reinterpret_cast<half_t *>(arena.upload(conv_w_f16_frag(w2v.data(), a.depth, a.depth)));
+            // the 64 -> 64 stride-2 layer has its own kernel that stages rows in natural order and walks the taps in tap order
+            if (copies.w2f2) a.w2f2 = reinterpret_cast<half_t *>(arena.upload(conv_w_f16_frag(w2v.data(), a.depth, a.depth, a.depth != 64)));
             a.prelu = arena.upload(vec_of(b, p + ".res_layer.2.weight", a.depth));
             a.w2 = reinterpret_cast<half_t *>(arena.upload(conv_w_f16(w2v.data(), a.depth, a.depth, 3)));
             frt::bn_fold(b, p + ".res_layer.4", a.depth, sc, bi);
@@ -137,10 +138,9 @@ void frt_embedder::build(const frt::Blob &b) {
             for (int k = 0; k < a.depth; ++k) sc[k] *= dinv[k];
             a.s2 = arena.upload(sc);
             a.b2 = arena.upload(bi);
-            if (a.cin != a.depth) {
+            if (copies.wsc) {
                 a.wsc = reinterpret_cast<half_t *>(arena.upload(conv_w_f16(b, p + ".shortcut_layer.0.weight", a.depth, a.cin, 1)));
-                const std::vector<uint16_t> fs = conv1x1_w_f16_frag(b.get(p + ".shortcut_layer.0.weight", (size_t)a.depth * a.cin).data, a.depth, a.cin);
-                if (!fs.empty()) a.wscf = reinterpret_cast<half_t *>(arena.upload(fs));
+                a.wscf = reinterpret_cast<half_t *>(arena.upload(conv1x1_w_f16_frag(b.get(p + ".shortcut_layer.0.weight", (size_t)a.depth * a.cin).data, a.depth, a.cin)));
                 frt::bn_fold(b, p + ".shortcut_layer.1", a.depth, sc, bi);
                 for (int k = 0; k < a.depth; ++k) bi[k] *= ds;
                 a.ssc = arena.upload(sc);
@@ -189,42 +189,20 @@ void frt_embedder::build(const frt::Blob &b) {
     warm_strip_tables();
 }
 
-// The strip kernels read per-geometry tables whose first use on a device allocates and copies (kernels_arc.hip).  Every launch description
-// forward() can fill is planned here for every batch up to max_batch, so that first use happens now: never in steady state, never inside a
-// captured graph.  Only the strip family reads tables and it takes stride-1 3x3 convs only, so the launches that matter are conv1, a stride-1
-// conv2 as the plain unit tail (with its SE twin) and, for IR-SE, conv2 + BN into RES; the stride-2 descriptions (fused shortcut conv included)
-// and the 1x1 shortcut launch never reach it and are planned here only as far as they share these lines.  A description this list misses
-// would still run - its first launch makes the table - except on a stream that is being captured, where that launch is refused with a message.
+// The strip kernels read per-geometry tables whose first use on a device allocates and copies (kernels_arc.hip).  Every launch forward() can
+// make - the unit schedule of every distinct unit shape, for every batch up to max_batch and either setting of frt_embedder_set_se_fused -
+// is asked for its table here, so that first use happens now: never in steady state, never inside a captured graph.
 void frt_embedder::warm_strip_tables() {
-    const ActSet &A = act[0];
+    const ArcUnitBuffers bufs = unit_buffers(act[0], 0);
+    std::set<std::array<int, 5>> seen;  // IR-152: 49 units in 8 shapes
     for (const ArcUnit &u : units) {
-        const int h = u.h_in, ho = h / u.stride;
-        for (int F = 1; F <= max_batch; ++F) {
-            ConvMfmaArgs a{};
-            a.x = A.Z[0]; a.w = u.w1; a.wf = u.w1f;
-            a.B = F; a.H = h; a.W = h; a.Cin = u.cin; a.Ho = h; a.Wo = h; a.Cout = u.depth; a.ks = 3; a.stride = 1; a.pad = 1;
-            a.mode = EPI_PRELU;
-            a.out0 = A.T;
-            a.splits = 1;
-            conv_strip_tables_warm(a, conv_plan(a));
-            ConvMfmaArgs c{};
-            c.x = A.T; c.w = u.w2; c.wf = u.w2f; c.wf2 = u.w2f2;
-            c.B = F; c.H = h; c.W = h; c.Cin = u.depth; c.Ho = ho; c.Wo = ho; c.Cout = u.depth; c.ks = 3; c.stride = u.stride; c.pad = 1;
-            c.splits = 1;
-            c.mode = EPI_BN_ADD_BN;
-            c.sc = A.Y[0];
-            c.sc_h = h; c.sc_w = h; c.sc_stride = u.stride;
-            if (&u == &units[0] || u.wsc) c.sc_h = ho, c.sc_w = ho, c.sc_stride = 1;
-            c.out0 = A.Y[1]; c.out1 = A.Z[1];
-            if (se) c.se_pool = A.se_pool, c.se_w1 = u.se_w1, c.se_w2 = u.se_w2, c.se_counter = A.se_counter;
-            conv_strip_tables_warm(c, conv_plan(c));  // (with its SE twin, when the plan has one)
-            if (se) {  // conv2 + BN into RES, the SE tail as launches of its own
-                ConvMfmaArgs f = c;
-                f.mode = EPI_BN;
-                f.out0 = A.RES; f.out1 = nullptr; f.sc = nullptr;
-                conv_strip_tables_warm(f, conv_plan(f));
+        const bool first = &u == &units[0];
+        if (!seen.insert({u.cin, u.depth, u.stride, u.h_in, first}).second) continue;
+        for (int F = 1; F <= max_batch; ++F)
+            for (int fuse = 0; fuse <= (se ? 1 : 0); ++fuse) {
+                const ArcUnitSchedule sch = arc_unit_schedule(u, first, bufs, F, se, fuse != 0);
+                for (int i = 0; i < sch.n; ++i) conv_strip_tables_warm(sch.conv[i].args, sch.conv[i].plan);
             }
-        }
     }
 }
 
@@ -378,109 +356,26 @@ void frt_embedder::forward(int set, const float *chw_dev, int F, const int *vali
     ArcInputArgs ia{chw_dev, in_w, in_s0, in_b0, in_slope, in_s1, in_b1, A.Y[0], A.Z[0], F, 112, 112, in_wh};
     launch_arc_input(ia, s);
     int cur = 0;
+    const bool fuse = se && se_fused && conv_se_fits_device();
     for (const ArcUnit &u : units) {
-        const int h = u.h_in, ho = h / u.stride;
-        {  // conv1: BN(x) [already applied -> Z] -> conv3x3 s1 -> PReLU
-            ConvMfmaArgs a{};
-            a.x = A.Z[cur];
-            a.w = u.w1;
-            a.wf = u.w1f;
-            a.B = F; a.H = h; a.W = h; a.Cin = u.cin; a.Ho = h; a.Wo = h; a.Cout = u.depth; a.ks = 3; a.stride = 1; a.pad = 1;
-            a.mode = EPI_PRELU;
-            a.p0 = u.prelu;
-            a.out0 = A.T;
-            a.splits = 1;
-            a.zeros = zeros;
-            const ConvPlan plan = conv_plan(a);
-            ProfScope pk(1, plan.label, 2.0 * 9 * u.cin * u.depth * (double)F * h * h, s);
-            launch_conv_mfma(a, plan, s);
-        }
-        // conv2: conv3x3 stride s -> BN -> (+SE) -> + shortcut ; also emits BN_next(y).  Described once, as the plain unit tail.
-        ConvMfmaArgs a{};
-        a.x = A.T;
-        a.w = u.w2;
-        a.wf = u.w2f;
-        a.wf2 = u.w2f2;
-        a.B = F; a.H = h; a.W = h; a.Cin = u.depth; a.Ho = ho; a.Wo = ho; a.Cout = u.depth; a.ks = 3; a.stride = u.stride; a.pad = 1;
-        a.p0 = u.s2;
-        a.p1 = u.b2;
-        a.splits = 1;
-        a.zeros = zeros;
-        a.mode = EPI_BN_ADD_BN;
-        a.p2 = u.sn;
-        a.p3 = u.bn;
-        a.sc = A.Y[cur];  // identity shortcut: MaxPool2d(1, stride) of the unit's input
-        a.sc_h = h; a.sc_w = h; a.sc_stride = u.stride;
-        if (&u == &units[0]) {  // the input layer already wrote its raw output at the even positions only
-            a.sc_h = ho; a.sc_w = ho;
-            a.sc_stride = 1;
-        }
-        a.out0 = A.Y[cur ^ 1];
-        a.out1 = A.Z[cur ^ 1];
-        if (se) {
-            a.se_pool = A.se_pool;
-            a.se_w1 = u.se_w1;
-            a.se_w2 = u.se_w2;
-            a.se_counter = A.se_counter;
-            a.se_flag_off = max_batch;
-            a.se_error = d_se_error;
-        }
-        // IR-50: the stride-2 strip kernel (and the small-batch kernel) computes the 1x1 stride-2 shortcut conv itself (its input pixels are the
-        // (even, even) phase plane) - no launch, no shortcut tensor.  IR-SE keeps the tensor: the gate multiplies the residual branch only.
-        ConvPlan plan;
-        bool sc_fused = false;
-        if (u.wsc && u.wscf && !se && u.stride == 2) {
-            a.sc = nullptr;
-            a.scx = A.Y[cur]; a.wscf = u.wscf; a.psc0 = u.ssc; a.psc1 = u.bsc; a.Csc = u.cin;
-            plan = conv_plan(a);
-            sc_fused = plan.uses_scx;
-            if (!sc_fused) a.scx = nullptr, a.wscf = nullptr, a.psc0 = a.psc1 = nullptr, a.Csc = 0;
-        }
-        if (u.wsc && !sc_fused) {  // conv1x1 stride s + BN on the raw input, as a launch of its own
-            ConvMfmaArgs c{};
-            c.x = A.Y[cur];
-            c.w = u.wsc;
-            c.B = F; c.H = h; c.W = h; c.Cin = u.cin; c.Ho = ho; c.Wo = ho; c.Cout = u.depth; c.ks = 1; c.stride = u.stride; c.pad = 0;
-            c.mode = EPI_BN;
-            c.p0 = u.ssc;
-            c.p1 = u.bsc;
-            c.out0 = A.SC;
-            c.splits = 1;
-            c.zeros = zeros;
-            launch_conv_mfma(c, conv_plan(c), s);
-            a.sc = A.SC;
-            a.sc_h = ho; a.sc_w = ho;
-            a.sc_stride = 1;
-        }
-        if (!sc_fused) plan = conv_plan(a);
-        bool se_tail = false;  // IR-SE: the SE tail as separate launches behind conv2
-        SeArgs sa{};
-        if (se) {
-            if (se_fused && plan.se_fused() && conv_se_fits_device()) {  // the strip kernel runs the whole tail in its epilogue
-                if (se_epoch >= (1 << 30)) {  // the flags carry launch numbers: start over with clean flags (every allocated set)
-                    for (int i = 0; i < (has_alt ? 2 : 1); ++i) HIPCHK(hipMemsetAsync(act[i].se_counter + max_batch, 0, (size_t)max_batch * sizeof(int), s));
-                    se_epoch = 0;
-                }
-                a.se_epoch = ++se_epoch;
-                // The plan made for the EPI_BN_ADD_BN description IS the plan of this launch: the arguments are not planned again under the
-                // new mode (no planner has to treat the two modes alike) - the plan only moves to its twin instantiation, same geometry.
-                a.mode = EPI_BN_SE;
-                plan.take_se_tail();
-            } else {  // another description - conv2 + BN into RES - and so another plan
-                sa = SeArgs{A.RES, u.se_w1, u.se_w2, a.sc, a.sc_h, a.sc_w, a.sc_stride, u.sn, u.bn, a.out0, a.out1, A.se_pool, A.se_gate, F, ho, ho, u.depth, A.se_counter};
-                a.mode = EPI_BN;
-                a.out0 = A.RES;
-                a.out1 = nullptr;
-                a.sc = nullptr;
-                se_tail = true;
-                plan = conv_plan(a);
+        ArcUnitSchedule sch = arc_unit_schedule(u, &u == &units[0], unit_buffers(A, cur), F, se, fuse);
+        if (sch.se_fused) {
+            if (se_epoch >= (1 << 30)) {  // the flags carry launch numbers: start over with clean flags (every allocated set)
+                for (int i = 0; i < (has_alt ? 2 : 1); ++i) HIPCHK(hipMemsetAsync(act[i].se_counter + max_batch, 0, (size_t)max_batch * sizeof(int), s));
+                se_epoch = 0;
             }
+            sch.conv[sch.n - 1].args.se_epoch = ++se_epoch;
         }
-        {
-            ProfScope pk(1, plan.label, (2.0 * 9 * u.depth * u.depth + (sc_fused ? 2.0 * u.cin * u.depth : 0.0)) * (double)F * ho * ho, s);
-            launch_conv_mfma(a, plan, s);
+        for (int i = 0; i < sch.n; ++i) {
+            const ArcLaunch &l = sch.conv[i];
+            if (l.desc == ARC_SHORTCUT1X1) {  // (not bracketed: the recorded label sequences hold conv1 and conv2 of every unit)
+                launch_conv_mfma(l.args, l.plan, s);
+                continue;
+            }
+            ProfScope pk(1, l.plan.label, l.flops, s);
+            launch_conv_mfma(l.args, l.plan, s);
         }
-        if (se_tail) launch_se(sa, s);
+        if (sch.se_tail) launch_se(sch.se, s);
         cur ^= 1;
     }
     {  // Linear 25088 -> 512 as 49 K-slices over the NHWC-flattened BN2d output (Z), then slice sum + bias + BN1d + L2 norm

@@ -1,18 +1,7 @@
 // struct frt_embedder: the object behind frt_embedder_* (include/frt.h).  Internal header of libfrt.so.
 #pragma once
+#include "frt_arc_launches.hpp"
 #include "frt_internal.hpp"
-
-struct ArcUnit {
-    int cin, depth, stride, h_in;  // input spatial size (square)
-    half_t *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;
-    half_t *w1f = nullptr, *w2f = nullptr;  // fragment-ordered copies for the strip kernel (stride-1 3x3 convs)
-    half_t *w2f2 = nullptr;                 // ... for the stride-2 strip kernel (conv2 of the first unit of a stage)
-    half_t *wscf = nullptr;                 // 1x1 shortcut weights in fragment order (the stride-2 strip kernel computes the shortcut conv itself)
-    float *prelu = nullptr, *s2 = nullptr, *b2 = nullptr, *ssc = nullptr, *bsc = nullptr;
-    float *s2f32 = nullptr;              // closing BatchNorm's scale WITHOUT the load-time conditioning factor (the fp32 path multiplies the blob's own weights)
-    float *sn = nullptr, *bn = nullptr;  // BatchNorm that consumes this unit's output (next unit's leading BN / output_layer.0)
-    float *se_w1 = nullptr, *se_w2 = nullptr;
-};
 
 struct frt_embedder {
     int device = 0;
@@ -45,6 +34,10 @@ struct frt_embedder {
     } act[2];
     bool has_alt = false;  // act[1] is allocated
     void alloc_act_set(ActSet &a);
+    // what a unit's launches touch when its input sits at parity `cur` of the set
+    ArcUnitBuffers unit_buffers(const ActSet &a, int cur) const {
+        return {a.Z[cur], a.Y[cur], a.T, a.SC, a.RES, a.Y[cur ^ 1], a.Z[cur ^ 1], a.se_pool, a.se_gate, a.se_counter, max_batch, d_se_error, zeros};
+    }
     void ensure_alt();
     float *d_in = nullptr;  // [max_batch][3][112][112]
     float *d_out = nullptr;

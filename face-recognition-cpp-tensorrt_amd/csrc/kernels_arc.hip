@@ -1082,11 +1082,6 @@ bool conv_strip_geometry(const ConvMfmaArgs &a, const ConvPlan &p, StripGeometry
 void conv_strip_tables_warm(const ConvMfmaArgs &a, const ConvPlan &p) {
     StripGeometry g;
     if (conv_strip_geometry(a, p, g)) (void)strip_tab_device(g);
-    if (p.se_fused()) {  // the twin with the SE tail has the row's geometry; asked for all the same
-        ConvPlan q = p;
-        q.take_se_tail();
-        if (conv_strip_geometry(a, q, g)) (void)strip_tab_device(g);
-    }
 }
 
 // Strip tables (frt_kernels.h), with exact integer division.  A wrong entry would be an out-of-bounds DMA or LDS read, so every entry is checked

@@ -1,10 +1,11 @@
-// The recogniser's launch space as frt_embedder::forward() fills it: the eight unit shapes and, per unit, the launch descriptions it makes.
-// Shared by conv_plan_dump.cpp (which enumerates the plans) and arc_launch_check.cpp (which runs the launches one at a time), so that the two
-// cannot describe a launch differently.  Every pointer describe() sets is a non-null dummy: a program that launches replaces each of them.
+// The recogniser's launch space: the eight unit shapes and, per unit, the launch descriptions it can make - described by the product's own
+// functions (csrc/frt_arc_launches.hpp, the text frt_embedder::forward() compiles); no description rule lives here.  Shared by
+// conv_plan_dump.cpp, strip_tables_dump.cpp, arc_schedule_dump.cpp (which enumerate) and arc_launch_check.cpp (which runs the launches one at a
+// time).  Every pointer describe() sets is a non-null dummy: a program that launches replaces each of them.
 #pragma once
 #include <cstdint>
 
-#include "frt_kernels.h"
+#include "frt_arc_launches.hpp"
 
 namespace arc_describe {
 
@@ -20,71 +21,29 @@ T *dummy(int k) {  // non-null, never dereferenced
     return reinterpret_cast<T *>((uintptr_t)0x10000 * (k + 1));
 }
 
-// the launch description `d` of a unit of shape `u` for a pass of F faces, filled the way forward() fills it; false: the unit has no such launch
-inline bool describe(const Shape &u, bool first_unit, int d, int F, ConvMfmaArgs &a) {
-    const int h = u.h, ho = h / u.stride;
-    const bool has_sc_conv = u.cin != u.depth;  // build(): wsc / wscf exist for these units only
-    a = ConvMfmaArgs{};
-    a.B = F;
-    a.splits = 1;
-    a.zeros = dummy<half_t>(0);
-    if (d == 0) {
-        a.x = dummy<half_t>(1);
-        a.w = dummy<half_t>(2);
-        a.wf = dummy<half_t>(3);  // conv1 is stride 1: always a fragment-ordered copy
-        a.H = h; a.W = h; a.Cin = u.cin; a.Ho = h; a.Wo = h; a.Cout = u.depth; a.ks = 3; a.stride = 1; a.pad = 1;
-        a.mode = EPI_PRELU;
-        a.p0 = dummy<float>(4);
-        a.out0 = dummy<half_t>(5);
-        return true;
-    }
-    if (d == 5) {
-        if (!has_sc_conv) return false;
-        a.x = dummy<half_t>(1);
-        a.w = dummy<half_t>(2);
-        a.H = h; a.W = h; a.Cin = u.cin; a.Ho = ho; a.Wo = ho; a.Cout = u.depth; a.ks = 1; a.stride = u.stride; a.pad = 0;
-        a.mode = EPI_BN;
-        a.p0 = dummy<float>(4);
-        a.p1 = dummy<float>(6);
-        a.out0 = dummy<half_t>(5);
-        return true;
-    }
-    a.x = dummy<half_t>(1);
-    a.w = dummy<half_t>(2);
-    (u.stride == 1 ? a.wf : a.wf2) = dummy<half_t>(3);  // build() packs one of the two
-    a.H = h; a.W = h; a.Cin = u.depth; a.Ho = ho; a.Wo = ho; a.Cout = u.depth; a.ks = 3; a.stride = u.stride; a.pad = 1;
-    a.p0 = dummy<float>(4);
-    a.p1 = dummy<float>(6);
-    a.p2 = dummy<float>(7);
-    a.p3 = dummy<float>(8);
-    a.mode = EPI_BN_ADD_BN;
-    a.sc = dummy<half_t>(9);
-    a.sc_h = h; a.sc_w = h; a.sc_stride = u.stride;
-    if (first_unit) a.sc_h = ho, a.sc_w = ho, a.sc_stride = 1;
-    a.out0 = dummy<half_t>(5);
-    a.out1 = dummy<half_t>(10);
-    if (d == 2) {
-        if (!(has_sc_conv && u.stride == 2)) return false;
-        a.sc = nullptr;
-        a.scx = dummy<half_t>(9); a.wscf = dummy<half_t>(11); a.psc0 = dummy<float>(12); a.psc1 = dummy<float>(13); a.Csc = u.cin;
-        return true;
-    }
-    if (has_sc_conv) a.sc_h = ho, a.sc_w = ho, a.sc_stride = 1;  // the 1x1 launch's output
-    if (d == 3 || d == 4) {
-        a.se_pool = dummy<float>(14);
-        a.se_w1 = dummy<float>(15);
-        a.se_w2 = dummy<float>(16);
-        a.se_counter = dummy<int>(17);
-        a.se_flag_off = 256;
-        a.se_error = dummy<int>(18);
-    }
-    if (d == 4) {
-        a.mode = EPI_BN;
-        a.out0 = dummy<half_t>(19);
-        a.out1 = nullptr;
-        a.sc = nullptr;
-    }
-    return true;
+static_assert(kNumDesc == ARC_NUM_DESC, "kDesc names the product's descriptions, in their order");
+
+// a unit of shape `s` with the weight copies build() gives such a unit (and SE weights: every shape can be asked for its IR-SE launches)
+inline ArcUnit unit_of(const Shape &s) {
+    ArcUnit u;
+    u.cin = s.cin; u.depth = s.depth; u.stride = s.stride; u.h_in = s.h;
+    const ArcUnitCopies c = arc_unit_copies(s.cin, s.depth, s.stride);
+    u.w1 = dummy<half_t>(2); u.w2 = dummy<half_t>(3);
+    if (c.w1f) u.w1f = dummy<half_t>(4);
+    if (c.w2f) u.w2f = dummy<half_t>(5);
+    if (c.w2f2) u.w2f2 = dummy<half_t>(6);
+    if (c.wsc) u.wsc = dummy<half_t>(7), u.wscf = dummy<half_t>(8), u.ssc = dummy<float>(9), u.bsc = dummy<float>(10);
+    u.prelu = dummy<float>(11); u.s2 = dummy<float>(12); u.b2 = dummy<float>(13); u.sn = dummy<float>(14); u.bn = dummy<float>(15);
+    u.se_w1 = dummy<float>(16); u.se_w2 = dummy<float>(17);
+    return u;
 }
+// an activation set of an embedder with max_batch 256
+inline ArcUnitBuffers buffers() {
+    return {dummy<half_t>(20), dummy<half_t>(21), dummy<half_t>(22), dummy<half_t>(23), dummy<half_t>(24), dummy<half_t>(25), dummy<half_t>(26),
+            dummy<float>(27), dummy<float>(28), dummy<int>(29), 256, dummy<int>(30), dummy<half_t>(0)};
+}
+
+// the launch description `d` of a unit of shape `s` for a pass of F faces; false: the unit has no such launch
+inline bool describe(const Shape &s, bool first_unit, int d, int F, ConvMfmaArgs &a) { return kArcDescribe[d](unit_of(s), first_unit, buffers(), F, a); }
 
 }  // namespace arc_describe
