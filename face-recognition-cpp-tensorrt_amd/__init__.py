@@ -102,6 +102,7 @@ ABI = {
     "frt_matcher_topk_labels_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "frt_merge_topk_labels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_merge_topk_labels_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frt_matcher_build_templates": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_embeds_to_half_dev": (_i, [_vp, _sz, _vp, _vp]),
     "frt_comm_get_unique_id": (_i, [_vp]),
     "frt_comm_set_bootstrap_timeout": (ctypes.c_double, [ctypes.c_double]),
@@ -387,6 +388,23 @@ class MatMul:
         """Asynchronous, raw device addresses: queries as ``topk_dev``; label int32 [n][k], idx int32 [n][k], sim fp32 [n][k]."""
         _check(lib.frt_matcher_topk_labels_dev(self._h, _vp(embeds_ptr), 1 if fp16 else 0, int(n), int(k), _vp(label_ptr), _vp(idx_ptr), _vp(sim_ptr),
                                                _vp(hip_stream) if hip_stream else None))
+
+    def buildTemplates(self, dst=None, want_templates=False):
+        """One template per identity of this labelled gallery (frt_matcher_build_templates): the re-normalised sum of the identity's stored
+        rows, identities in first-appearance order.  Returns ``(labels, n_rows, min_sim, min_row[, templates])``, each ``[I]`` (templates
+        ``[I, numCol]`` with ``want_templates``): ``min_row`` is the member row that agrees least with its own template, ``min_sim`` its
+        similarity.  ``dst`` (another ``MatMul`` on the same device) is replaced by the template gallery, labelled with ``labels``, in its own
+        storage mode; ``None``: an audit only."""
+        n = self.labels_info()[0]
+        labels, n_rows, min_row = (np.empty(n, np.int32) for _ in range(3))
+        min_sim = np.empty(n, np.float32)
+        t = np.empty((n, self.k), np.float32) if want_templates else None
+        _check(lib.frt_matcher_build_templates(self._h, dst._h if dst is not None else None, _ptr(labels), _ptr(n_rows), _ptr(min_sim), _ptr(min_row),
+                                               _ptr(t)))
+        if dst is not None:
+            dst.k = self.k
+            dst._edited()
+        return (labels, n_rows, min_sim, min_row) + ((t,) if want_templates else ())
 
     def setRowOffset(self, row_offset):
         """Sharded gallery: local row 0 is global row ``row_offset`` (top-1 indices become global)."""

@@ -89,6 +89,20 @@ void launch_merge_topk_labels(const int32_t *label_all, const int32_t *idx_all, 
                               int32_t *idx_out, float *sim_out, hipStream_t s);
 // The fp16 gallery (shadow or stored) is kept in MFMA-fragment order and padded to whole 128-row tiles (see kernels_match.hip):
 size_t gallery16_elems(int N, int D);
+// Row g, column k of it lives at
+//   ((((g >> 7) * 4 + ((g >> 5) & 3)) * (D / 16) + (k >> 4)) * 64 + ((k >> 3) & 1) * 32 + (g & 31)) * 8 + (k & 7)
+// i.e. [128-row tile][32-row wave block][16-wide k step][lane = (k half, row)][8 halfs].  (Row-major rows made a lane of the coarse scan fetch
+// 16 bytes of its own 1 KB row per instruction: 32 different lines per load, each line requested four times - both earlier coarse kernels
+// stalled at 4.0 TB/s on it.)  Pad rows are zero.
+__device__ __forceinline__ long g16_index(long g, int k, int D) {
+    return ((((g >> 7) * 4 + ((g >> 5) & 3)) * (long)(D >> 4) + (k >> 4)) * 64 + ((k >> 3) & 1) * 32 + (g & 31)) * 8 + (k & 7);
+}
+// four columns k .. k + 3 (k % 4 == 0) of stored row g as fp32, whichever the storage type (fp16 values widen exactly)
+__device__ __forceinline__ floatx4 load_g4(const float *G, long g, int D, int k) { return *reinterpret_cast<const floatx4 *>(G + g * D + k); }
+__device__ __forceinline__ floatx4 load_g4(const half_t *G, long g, int D, int k) {  // (four columns never straddle an 8-group)
+    const half4 h = *reinterpret_cast<const half4 *>(G + g16_index(g, k, D));
+    return floatx4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
+}
 bool match_screen_supported(int D);  // D the coarse kernel is instantiated for
 // fp32 rows [n_rows][D] (first row = global row row0) -> their place in the fp16 gallery (whose rows never written must be zero)
 void launch_rows_to_half(const float *in, long row0, long n_rows, int D, half_t *g16, hipStream_t s);
@@ -100,6 +114,14 @@ void launch_rows_norm(const GT *G, int row0, int n_rows, int D, int *max_norm2_b
 void launch_gallery_shadow8_rows(const float *rows, int row0, int n_rows, uint8_t *g8, float *scale, int *max_err2_bits, int *max_norm2_bits, hipStream_t s);
 void launch_gather_rows(const float *G, int D, int a, int n_rows, const int *keys, int klo, int khi, float *bounce, hipStream_t s);
 void launch_gather_rows16(const half_t *G, int D, long tile0, long n_tiles, int n_new, const int *keys, int klo, int khi, half_t *bounce, hipStream_t s);
+
+// ---------------------------------------------------------------- template gallery (kernels_templates.hip)
+// One template per identity (include/frt.h, frt_matcher_build_templates).  rows: the stored gallery (fp32 row-major or fragment-ordered fp16);
+// identity i owns the LOCAL rows group_rows[group_off[i] .. group_off[i + 1]), ascending (frt_templates.hpp).  -> templates [I][D] fp32,
+// min_sim [I], min_row [I] (row_offset added).
+template <typename GT>
+void launch_template_build(const GT *rows, int D, const int *group_off, const int *group_rows, int I, int row_offset, float *templates, float *min_sim,
+                           int32_t *min_row, hipStream_t s);
 
 // ---------------------------------------------------------------- post-processing (kernels_post.hip)
 constexpr int DET_MAX_LEVELS = 4, DET_MAX_SIZES = 3;

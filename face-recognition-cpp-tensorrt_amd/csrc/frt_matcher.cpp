@@ -4,6 +4,7 @@
 #include "frt_matcher.hpp"
 
 #include "frt_holes.h"
+#include "frt_templates.hpp"
 
 // ------------------------------------------------------------------------------------------------------------- live gallery edits
 // Add and remove rows of the gallery the matcher is answering from (include/frt.h).  Every edit runs on the matcher's stream behind its
@@ -243,6 +244,65 @@ void remove_rows(frt_matcher *m, const int32_t *idx, int n_idx) {
         // max_rows_per_label stays: the true maximum cannot have grown, and an over-estimate only makes fewer calls screen
     }
     finish_edit(m, new_n);
+}
+
+// ------------------------------------------------------------------------------------------------------------- template gallery
+// frt_matcher_build_templates (include/frt.h) with both mutexes held by the caller.  The grouping comes from src's host mirror of the labels,
+// the pass over the rows runs on src's stream into buffers of this call, and dst takes the templates by the route every device row takes:
+// emptied as a commit of zero rows empties a matcher (which also waits for its match stages), then ONE labelled add that allocates for I rows.
+void build_templates(frt_matcher *src, frt_matcher *dst, int32_t *labels_out, int32_t *n_rows_out, float *min_sim_out, int32_t *min_row_out,
+                     float *templates_out) {
+    if (src->D <= 0) raise(FRT_ERR_INVALID, "build_templates: the source has no gallery yet (frt_matcher_init or gallery_begin + commit first)");
+    if (src->N > 0 && !src->labelled) raise(FRT_ERR_INVALID, "build_templates: the source gallery has no labels (frt_matcher_set_labels)");
+    if (dst && dst->row_offset != 0) raise(FRT_ERR_INVALID, "build_templates: the destination has a row offset (a shard); templates go to an unsharded matcher");
+    use_device(src->device);
+    const int N = src->N, D = src->D;
+    std::vector<int32_t> ident_label;
+    std::vector<int> off, rows;
+    frt_template_groups(src->h_labels.data(), N, ident_label, off, rows);
+    const int I = (int)ident_label.size();
+    Arena mem;
+    try {
+        float *d_t = nullptr;
+        if (I > 0) {
+            hipStream_t s = src->stream;
+            src->wait_idle(s);  // behind a match stage still reading src's scratch (it only reads the rows, as this pass does)
+            int *d_off = mem.alloc<int>(off.size()), *d_rows = mem.alloc<int>(rows.size());
+            d_t = mem.alloc<float>((size_t)I * D);
+            float *d_sim = mem.alloc<float>((size_t)I);
+            int32_t *d_row = mem.alloc<int32_t>((size_t)I);
+            HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, s));
+            {
+                ProfScope ps(2, "template_build", (double)N * D * (src->store16 ? 2 : 4) + (double)I * D * 4, s);  // work = bytes moved
+                src->with_rows([&](auto *g) { launch_template_build(g, D, d_off, d_rows, I, src->row_offset, d_t, d_sim, d_row, s); });
+                HIPCHK(hipGetLastError());
+            }
+            if (min_sim_out) HIPCHK(hipMemcpyAsync(min_sim_out, d_sim, (size_t)I * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (min_row_out) HIPCHK(hipMemcpyAsync(min_row_out, d_row, (size_t)I * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            if (templates_out) HIPCHK(hipMemcpyAsync(templates_out, d_t, (size_t)I * D * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        for (int i = 0; i < I; ++i) {
+            if (labels_out) labels_out[i] = ident_label[(size_t)i];
+            if (n_rows_out) n_rows_out[i] = off[(size_t)i + 1] - off[(size_t)i];
+        }
+        if (dst) {
+            dst->load_begin(0, D);
+            try {
+                dst->load_commit();
+            } catch (...) {
+                dst->load_abort();
+                throw;
+            }
+            add_rows(dst, d_t, I, true, ident_label.data(), true);
+        }
+    } catch (...) {
+        (void)hipStreamSynchronize(src->stream);
+        mem.release();
+        throw;
+    }
+    mem.release();
 }
 
 // What every host entry point that takes queries starts with (the caller holds m->mu): the queries are in d_q, on the returned stream
@@ -515,6 +575,21 @@ int frt_matcher_labels_info(frt_matcher *m, int *n_identities, int *max_rows_per
         std::lock_guard<std::mutex> lk(m->mu);
         *n_identities = m->labelled ? (int)m->label_rows.size() : 0;
         *max_rows_per_label = m->labelled ? m->max_rows_per_label : 0;
+    });
+}
+
+int frt_matcher_build_templates(frt_matcher *src, frt_matcher *dst, int32_t *labels_out, int32_t *n_rows_out, float *min_sim_out, int32_t *min_row_out,
+                                float *templates_out) {
+    return guarded([&] {
+        if (!src) raise(FRT_ERR_INVALID, "build_templates: null source");
+        if (src == dst) raise(FRT_ERR_INVALID, "build_templates: source and destination are the same matcher");
+        if (dst && dst->device != src->device) raise(FRT_ERR_INVALID, "build_templates: the two matchers are on different devices");
+        // both mutexes for the whole call, taken in address order (two concurrent builds over the same pair cannot deadlock)
+        frt_matcher *first = src, *second = dst;
+        if (dst && std::less<frt_matcher *>()(dst, src)) std::swap(first, second);
+        std::unique_lock<std::mutex> lk1(first->mu), lk2;
+        if (second) lk2 = std::unique_lock<std::mutex>(second->mu);
+        build_templates(src, dst, labels_out, n_rows_out, min_sim_out, min_row_out, templates_out);
     });
 }
 

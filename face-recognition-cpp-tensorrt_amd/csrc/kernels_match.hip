@@ -36,20 +36,8 @@ __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { retur
 // screening pass or the fp16-STORED shard of BASELINE config 5; stored values are widened exactly to fp32 on the way into LDS, all
 // arithmetic stays the same fp32 fmaf chain).
 //
-// The fp16 gallery is NOT row-major: it is kept in the order the coarse kernel's MFMA A fragments consume it, so that every
-// wave-level load of the 1 GB scan is ONE contiguous kilobyte (8 full 128-byte lines).  Row g, column k lives at
-//   ((((g >> 7) * 4 + ((g >> 5) & 3)) * (D / 16) + (k >> 4)) * 64 + ((k >> 3) & 1) * 32 + (g & 31)) * 8 + (k & 7)
-// i.e. [128-row tile][32-row wave block][16-wide k step][lane = (k half, row)][8 halfs].  (Row-major rows made a lane fetch 16 bytes
-// of its own 1 KB row per instruction: 32 different lines per load, each line requested four times - both earlier coarse kernels
-// stalled at 4.0 TB/s on it.)  The allocation is padded to whole 128-row tiles; pad rows are zero.
-__device__ __forceinline__ long g16_index(long g, int k, int D) {
-    return ((((g >> 7) * 4 + ((g >> 5) & 3)) * (long)(D >> 4) + (k >> 4)) * 64 + ((k >> 3) & 1) * 32 + (g & 31)) * 8 + (k & 7);
-}
-__device__ __forceinline__ floatx4 load_g4(const float *G, long g, int D, int k) { return *reinterpret_cast<const floatx4 *>(G + g * D + k); }
-__device__ __forceinline__ floatx4 load_g4(const half_t *G, long g, int D, int k) {  // k % 4 == 0: four columns never straddle an 8-group
-    const half4 h = *reinterpret_cast<const half4 *>(G + g16_index(g, k, D));
-    return floatx4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-}
+// The fp16 gallery is NOT row-major: it is kept in the order the coarse kernel's MFMA A fragments consume it (g16_index / load_g4,
+// frt_kernels.h), so that every wave-level load of the 1 GB scan is ONE contiguous kilobyte (8 full 128-byte lines).
 
 // EXCL (top-k passes): only rows that come strictly AFTER the query's previous winner (prev_sim, prev_idx = its GLOBAL index) in the
 // result order "higher similarity first, lower index first on ties" take part; prev_sim == nullptr: no previous winner (first pass).

@@ -308,6 +308,28 @@ int frt_merge_topk_labels(int shards, int n, int k, const int32_t *label_all, co
 int frt_merge_topk_labels_dev(int shards, int n, int k, const void *label_all_dev, const void *idx_all_dev, const void *sim_all_dev, void *label_out_dev,
                               void *idx_out_dev, void *sim_out_dev, void *hip_stream);
 
+/* Template gallery: ONE row per identity.  From a labelled matcher `src` (N rows g_r as STORED - fp16 storage: the fp16 rows widened to
+ * fp32 - labels l_r, width D) build, in one streaming pass of the device over the rows, for every identity i = 0 .. I - 1 (numbered in
+ * first-appearance order, by the lowest row that carries the label; I = n_identities of frt_matcher_labels_info), rows r_1 < ... < r_M:
+ *   s          = ((g_r1 + g_r2) + ...) + g_rM   per column, fp32, in ascending row order;
+ *   template   t_i = s / ||s||_2                (fp32; all zeros when ||s||^2 == 0, e.g. g and -g under one label);
+ *   n_rows[i]  = M,   labels[i] = the identity's label;
+ *   min_sim[i] = min_j <g_rj, t_i>  (fp32 accumulation; 0 for a zero template) and min_row[i] = the GLOBAL row (row offset added) that
+ *                attains it, the lowest among equals: the member that agrees least with its own identity - the mislabelled or poor photo.
+ * Every output pointer may be NULL; labels_out / n_rows_out / min_sim_out / min_row_out are [I], templates_out is [I][D] (host memory).
+ * dst (may be NULL: an audit only) afterwards holds exactly the I templates as a labelled gallery with labels[i], in its OWN storage mode
+ * (frt_matcher_set_storage) and screening state: it is emptied and the templates enter it device to device by the route of
+ * frt_matcher_gallery_add_labeled_dev, so its answers are those of a fresh matcher loaded with templates_out + labels_out.  dst is an
+ * ordinary labelled matcher: frt_pipeline_create, the coalescer, top1, topk and topk_labels take it, and the row they answer with is a
+ * person.  dst's mutex is held across the whole replacement (no caller sees it empty or half filled); the two mutexes are taken in address
+ * order; match stages in flight on either matcher are waited for; src is only read and its generation does not change.
+ * FRT_ERR_INVALID: src NULL, src without labels (and with rows), src == dst, matchers on different devices, dst with a row offset.  A src
+ * with zero rows is no error: dst becomes an empty gallery of src's width.
+ * Sharded galleries: a shard builds the templates of ITS rows only; an identity whose rows straddle shards gets one partial template per
+ * shard, which is out of scope here - keep an identity's rows on one shard, or build from an unsharded matcher. */
+int frt_matcher_build_templates(frt_matcher *src, frt_matcher *dst, int32_t *labels_out, int32_t *n_rows_out, float *min_sim_out, int32_t *min_row_out,
+                                float *templates_out);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU exchange.  The reference is one single-GPU C++ process (src/app.cpp:52-57, 367); north_star shards whole
  * frames over the GPUs of a node with an RCCL all-gather as the only exchange step.  These calls are that step for a C++ host: RCCL

@@ -71,7 +71,7 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     ArcFaceIR50(TRTLogger gLogger, const std::string engineFile, int frameWidth, int frameHeight, std::string inputName, std::string outputName,
                 std::vector<int> inputShape, int outputDim, int maxBatchSize, int maxFacesPerScene, float knownPersonThreshold, int device = 0)
         : croppedFaces(this), h_(nullptr), m_id(frtdetail::nextObjectId()), m_frameWidth(frameWidth), m_frameHeight(frameHeight), m_OUTPUT_D(outputDim),
-          m_maxBatchSize(maxBatchSize), m_maxFacesPerScene(maxFacesPerScene), m_knownPersonThresh(knownPersonThreshold), matmul(device) {
+          m_maxBatchSize(maxBatchSize), m_maxFacesPerScene(maxFacesPerScene), m_knownPersonThresh(knownPersonThreshold), matmul(device), m_templates(device) {
         (void)gLogger;
         (void)inputName;
         (void)outputName;
@@ -453,6 +453,39 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
             }
         return out;
     }
+    // Extension: the k best PERSONS per cropped face of the calling thread by TEMPLATE similarity - up to k (className, similarity) pairs, best
+    // first.  A second matcher owned by this object holds one row per className: the re-normalised sum of that class's rows
+    // (frt_matcher_build_templates), so a call scans one row per person instead of one per photo, and one poor enrolment photo moves a
+    // person's score less than it moves matchTopIdentities' best-photo score.  The templates are built at the first call and again whenever
+    // frt_matcher_generation of the row gallery has moved since (enrolEmbedding(s), enrolFaces, enrolImages, removeClass, initMatMul); the
+    // search itself is a plain top-k on the template gallery.  1 <= k <= 16.  A process that never calls this pays nothing.
+    std::vector<std::vector<std::pair<std::string, float>>> matchTemplates(int k) {
+        State &s = st();
+        if (classNames.empty() || s.croppedFaces.empty()) throw "Feature matching: No faces in database or no faces found";
+        const int n = (int)s.croppedFaces.size();
+        ensureTemplates();
+        std::vector<int> idx((size_t)n * k);
+        std::vector<float> sims((size_t)n * k);
+        m_templates.topk(s.embeds.data(), n, k, idx.data(), sims.data());
+        std::vector<std::vector<std::pair<std::string, float>>> out((size_t)n);
+        for (int i = 0; i < n; ++i)
+            for (int j = 0; j < k; ++j) {
+                const int r = idx[(size_t)i * k + j];
+                if (r >= 0 && (size_t)r < m_templateLabels.size()) out[(size_t)i].push_back(std::make_pair(labelName(m_templateLabels[(size_t)r]), sims[(size_t)i * k + j]));
+            }
+        return out;
+    }
+    // Extension: what enrolment needs to find a mislabelled or poor photo - per className, in first-appearance order, (name, rows of that
+    // name, the lowest similarity of one of its rows to the name's own template, the gallery row that has it).  Builds the templates as
+    // matchTemplates does.
+    std::vector<std::tuple<std::string, int, float, int>> auditTemplates() {
+        std::vector<std::tuple<std::string, int, float, int>> out;
+        if (classNames.empty()) return out;
+        ensureTemplates();
+        for (size_t i = 0; i < m_templateLabels.size(); ++i)
+            out.push_back(std::make_tuple(labelName(m_templateLabels[i]), m_templateRows[i], m_templateMinSim[i], m_templateMinRow[i]));
+        return out;
+    }
     // src/arcface.cpp:219-231: drawing only, not on the hot path (not even called by app.cpp); real OpenCV required.
     void visualize(cv::Mat &image, std::vector<std::string> names, std::vector<float> sims) {
 #ifdef FRT_HAVE_OPENCV
@@ -512,6 +545,26 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         matmul.setLabels(labels.data(), (int)labels.size());
         m_labelsSet = true;
     }
+    // the template gallery follows the row gallery: rebuilt when that one's generation has moved (the labels first - setting them moves it too)
+    void ensureTemplates() {
+        ensureLabels();
+        if (m_templatesBuilt && m_templateGen == frt_matcher_generation(matmul.handle())) return;
+        int identities = 0, maxRows = 0;
+        matmul.labelsInfo(identities, maxRows);
+        m_templateLabels.assign((size_t)identities, 0);
+        m_templateRows.assign((size_t)identities, 0);
+        m_templateMinRow.assign((size_t)identities, 0);
+        m_templateMinSim.assign((size_t)identities, 0.f);
+        m_templatesBuilt = false;
+        matmul.buildTemplates(&m_templates, m_templateLabels.data(), m_templateRows.data(), m_templateMinSim.data(), m_templateMinRow.data());
+        m_templateGen = frt_matcher_generation(matmul.handle());
+        m_templatesBuilt = true;
+    }
+    std::string labelName(int l) const { return (l >= 0 && (size_t)l < m_labelNames.size()) ? m_labelNames[(size_t)l] : std::string(); }
+    bool m_templatesBuilt = false;
+    unsigned m_templateGen = 0;
+    std::vector<int> m_templateLabels, m_templateRows, m_templateMinRow;  // per template row (identity), from the last build
+    std::vector<float> m_templateMinSim;
     frt_pipeline *m_photoPipe = nullptr;  // enrolImages: created at its first call, for m_photoDet
     frt_detector *m_photoDet = nullptr;
     bool m_labelsSet = false;
@@ -606,6 +659,7 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     std::mutex m_relink;
     std::vector<std::string> classNames;
     MatMul matmul;
+    MatMul m_templates;  // matchTemplates / auditTemplates: one row per className, created (and built) at their first use
     std::shared_ptr<frtdetail::CoalesceLink> m_link;
 };
 

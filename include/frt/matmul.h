@@ -78,6 +78,18 @@ class MatMul {
         ensure();
         checkFrtStatus(frt_matcher_topk_labels(h_, embeds, embedCount, k, labels, idx, sim));
     }
+    // Extension: the template gallery (frt.h "Template gallery"): one row per identity of this labelled gallery - the re-normalised sum of
+    // its rows - built on the device.  dst (may be null: an audit only) is replaced by the templates, labelled, in its own storage mode, and
+    // is then matched like any gallery: its rows are persons.  labels / nRows / minSim / minRow are [identities] (labelsInfo), templates
+    // [identities x numCol]; any of them may be null.  minRow names the row that agrees least with its own identity's template.
+    void buildTemplates(MatMul *dst, int *labels = nullptr, int *nRows = nullptr, float *minSim = nullptr, int *minRow = nullptr, float *templates = nullptr) {
+        ensure();
+        checkFrtStatus(frt_matcher_build_templates(h_, dst ? dst->handle() : nullptr, labels, nRows, minSim, minRow, templates));
+    }
+    void topk(const float *embeds, int embedCount, int k, int *idx, float *sim) {
+        ensure();
+        checkFrtStatus(frt_matcher_topk(h_, embeds, embedCount, k, idx, sim));
+    }
     // Extension: store the gallery rows as fp16 on the device (next init / galleryBegin); see frt_matcher_set_storage
     void setStorageFp16(bool on) {
         ensure();
