@@ -99,40 +99,6 @@ std::vector<uint16_t> pack_pw_split(const std::vector<float> &w, int cin, int co
         }
     return o;
 }
-// "set the batch, launch", once per kind of op (frt_detector::forward)
-void run(DwPwArgs &a, int n, hipStream_t s) {
-    a.B = n;
-    launch_dwpw(a, s);
-}
-void run(frt_detector::Conv3Op &o, int n, hipStream_t s) {
-    for (int k = 0; k < o.n; ++k) o.p[k].B = n;
-    launch_conv3x3_multi(o.p, o.n, s);
-}
-void run(frt_detector::HeadsOp &o, int n, hipStream_t s) {
-    for (int k = 0; k < o.n; ++k) o.p[k].B = n;
-    launch_heads_multi(o.p, o.n, s);
-}
-void run(frt_detector::SlimHeadsOp &o, int n, hipStream_t s) {
-    o.a.B = n;
-    launch_slim_heads(o.a, o.n, s);
-}
-void run(DenseHeadArgs &a, int n, hipStream_t s) {
-    a.B = n;
-    launch_dense_head(a, s);
-}
-void run(RfbProjArgs &a, int n, hipStream_t s) {
-    a.B = n;
-    launch_rfb_proj(a, s);
-}
-void run(frt_detector::RfbConvOp &o, int n, hipStream_t s) {
-    o.a.B = n;
-    launch_rfb_conv(o.a, o.n, s);
-}
-void run(RfbTailArgs &a, int n, hipStream_t s) {
-    a.B = n;
-    launch_rfb_tail(a, s);
-}
-
 // ---- Slim / RFB (conversion/retina/models/net_slim.py, net_rfb.py): the tensors of the state_dict, shapes included
 struct TensorSpec {
     std::string name;
@@ -623,7 +589,7 @@ void frt_detector::forward_frames(const uint8_t *frames_dev, int n, size_t row_s
 
 void frt_detector::forward(int n, hipStream_t s, int first_op) {
     ProfScope ps(2, "det_network", flops_per_frame * n, s);
-    for (size_t i = first_op; i < ops.size(); ++i) std::visit([&](auto &a) { run(a, n, s); }, ops[i]);
+    for (size_t i = first_op; i < ops.size(); ++i) run_op(i, n, s);
     HIPCHK(hipGetLastError());  // a failed launch (e.g. the dynamic-LDS opt-in missing on this device) must not pass silently
 }
 

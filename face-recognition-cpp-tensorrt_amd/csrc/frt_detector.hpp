@@ -57,6 +57,11 @@ struct frt_detector {
     float *d_tmp = nullptr;  // depthwise intermediate of the split conv_dw path
     float *d_wave_zeros = nullptr;  // zeros for dwpw_wave_kernel (input rows outside the image)
     std::vector<Op> ops;
+    // op i at a batch of n frames: "set the batch, launch", once per kind of op.  forward() runs the network through it, and so does
+    // tests/cpp/det_op_check.cpp, which launches every op alone.
+    void run_op(size_t i, int n, hipStream_t s) {
+        std::visit([&](auto &a) { run(a, n, s); }, ops[i]);
+    }
     double flops_per_frame = 0;
     uint8_t *d_frames = nullptr;
     float *d_input = nullptr, *d_loc = nullptr, *d_conf = nullptr;
@@ -70,6 +75,41 @@ struct frt_detector {
     int *d_kept_anchor = nullptr;  // [B][max_faces]
     float *d_landmarks = nullptr;  // decoded, frame coordinates [B][max_faces][10]
 
+  private:
+    static void run(DwPwArgs &a, int n, hipStream_t s) {
+        a.B = n;
+        launch_dwpw(a, s);
+    }
+    static void run(Conv3Op &o, int n, hipStream_t s) {
+        for (int k = 0; k < o.n; ++k) o.p[k].B = n;
+        launch_conv3x3_multi(o.p, o.n, s);
+    }
+    static void run(HeadsOp &o, int n, hipStream_t s) {
+        for (int k = 0; k < o.n; ++k) o.p[k].B = n;
+        launch_heads_multi(o.p, o.n, s);
+    }
+    static void run(SlimHeadsOp &o, int n, hipStream_t s) {
+        o.a.B = n;
+        launch_slim_heads(o.a, o.n, s);
+    }
+    static void run(DenseHeadArgs &a, int n, hipStream_t s) {
+        a.B = n;
+        launch_dense_head(a, s);
+    }
+    static void run(RfbProjArgs &a, int n, hipStream_t s) {
+        a.B = n;
+        launch_rfb_proj(a, s);
+    }
+    static void run(RfbConvOp &o, int n, hipStream_t s) {
+        o.a.B = n;
+        launch_rfb_conv(o.a, o.n, s);
+    }
+    static void run(RfbTailArgs &a, int n, hipStream_t s) {
+        a.B = n;
+        launch_rfb_tail(a, s);
+    }
+
+  public:
     void build(const frt::Blob &b);
     // the builders of one op's arguments: weights uploaded in every layout their kernels may use, flops_per_frame advanced
     DwPwArgs dwpw_op(const float *in, float *out, const std::vector<float> &w, const std::vector<float> &bias, const std::vector<float> &w2,
