@@ -420,13 +420,8 @@ bool forward_frame(frt_embedder *e, const uint8_t *bgr, int rows, int cols, size
     hipStream_t s = e->stream;
     e->wait_idle(s);
     const size_t tight = (size_t)cols * 3, need = (size_t)rows * tight;
-    if (need > e->frame_cap) {
-        if (e->d_frame) (void)hipFree(e->d_frame);
-        e->d_frame = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&e->d_frame), need));
-        e->frame_cap = need;
-    }
-    HIPCHK(hipMemcpy2DAsync(e->d_frame, tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice, s));
+    e->d_frame.reserve(need);
+    HIPCHK(hipMemcpy2DAsync(e->d_frame.get(), tight, bgr, row_stride, tight, rows, hipMemcpyHostToDevice, s));
     bool bad = false;
     for (int f0 = 0; f0 < n; f0 += e->max_batch) {
         const int nf = std::min(e->max_batch, n - f0);
@@ -501,27 +496,17 @@ void embed_face_images(frt_embedder *e, const frt_face_image *faces, int n, floa
             HIPCHK(hipEventCreateWithFlags(&fs.read[b], hipEventDisableTiming));
         }
     }
-    for (int b = 0; b < 2; ++b) {  // (both idle: every call ends with its streams drained)
-        if (fs.cap[b] >= need && fs.h_pack[b]) continue;
-        const size_t cap = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);  // grows to fit, as frame_cap does
-        if (fs.h_pack[b]) (void)hipHostFree(fs.h_pack[b]);
-        if (fs.d_pack[b]) (void)hipFree(fs.d_pack[b]);
-        fs.h_pack[b] = fs.d_pack[b] = nullptr;
-        fs.cap[b] = 0;
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&fs.h_pack[b]), hdr + cap, hipHostMallocDefault));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&fs.d_pack[b]), hdr + cap));
-        fs.cap[b] = cap;
-    }
+    for (PackPair &pk : fs.pack) pk.reserve(hdr, need);  // (both idle: every call ends with its streams drained)
     e->wait_idle(s);
     bool used[2] = {false, false};
     auto stage = [&](size_t ci) {
         const int b = (int)(ci & 1);
         const frt_face_chunk &c = chunks[ci];
         if (used[b]) wait_event_spinning(fs.uploaded[b]);  // the pinned buffer is rewritten only after its upload
-        std::memcpy(fs.h_pack[b], &desc[(size_t)c.first], (size_t)c.count * sizeof(frt_face_desc));
-        pack_face_images(faces, desc.data(), c.first, c.count, fs.h_pack[b] + hdr);
+        std::memcpy(fs.pack[b].h.get(), &desc[(size_t)c.first], (size_t)c.count * sizeof(frt_face_desc));
+        pack_face_images(faces, desc.data(), c.first, c.count, fs.pack[b].h.get() + hdr);
         if (used[b]) HIPCHK(hipStreamWaitEvent(fs.copy, fs.read[b], 0));  // the arena only after the prepare kernel that read it
-        HIPCHK(hipMemcpyAsync(fs.d_pack[b], fs.h_pack[b], hdr + c.bytes, hipMemcpyHostToDevice, fs.copy));
+        HIPCHK(hipMemcpyAsync(fs.pack[b].d.get(), fs.pack[b].h.get(), hdr + c.bytes, hipMemcpyHostToDevice, fs.copy));
         HIPCHK(hipEventRecord(fs.uploaded[b], fs.copy));
         used[b] = true;
     };
@@ -535,7 +520,7 @@ void embed_face_images(frt_embedder *e, const frt_face_image *faces, int n, floa
             {
                 ProfScope ps(2, "faces_prepare", (double)c.count * 112 * 112, s);
                 ProfScope pk(1, "faces_prepare_kernel", (double)c.count * 112 * 112, s);
-                launch_faces_prepare(fs.d_pack[b] + hdr, reinterpret_cast<const frt_face_desc *>(fs.d_pack[b]), c.count,
+                launch_faces_prepare(fs.pack[b].d.get() + hdr, reinterpret_cast<const frt_face_desc *>(fs.pack[b].d.get()), c.count,
                                      crops_out ? e->d_crops : nullptr, e->d_in, s);  // (d_in is shared: behind the previous chunk's pass on s)
             }
             HIPCHK(hipEventRecord(fs.read[b], s));
@@ -634,25 +619,21 @@ void frt_embedder_destroy(frt_embedder *e) {
         (void)hipStreamSynchronize(e->stream);
         (void)hipStreamDestroy(e->stream);
     }
-    if (e->d_frame) (void)hipFree(e->d_frame);
     if (e->faces.copy) {
         (void)hipStreamSynchronize(e->faces.copy);
         (void)hipStreamDestroy(e->faces.copy);
     }
     for (int b = 0; b < 2; ++b) {
-        if (e->faces.h_pack[b]) (void)hipHostFree(e->faces.h_pack[b]);
-        if (e->faces.d_pack[b]) (void)hipFree(e->faces.d_pack[b]);
         if (e->faces.uploaded[b]) (void)hipEventDestroy(e->faces.uploaded[b]);
         if (e->faces.read[b]) (void)hipEventDestroy(e->faces.read[b]);
     }
-    if (e->faces.d_embeds) (void)hipFree(e->faces.d_embeds);
     for (void *p : e->f32.owned) (void)hipFree(p);
     if (e->f32.done) (void)hipEventDestroy(e->f32.done);
     if (e->h_se_error) (void)hipHostFree(e->h_se_error);
     for (hipEvent_t ev : e->ev_busy)
         if (ev) (void)hipEventDestroy(ev);
     e->arena.release();
-    delete e;
+    delete e;  // d_frame and the face stage's buffers free themselves, on the device set above
 }
 
 int frt_embedder_set_se_fused(frt_embedder *e, int enable) {
@@ -717,7 +698,7 @@ int frt_embedder_forward(frt_embedder *e, const uint8_t *bgr, int rows, int cols
         if (n == 0) return;
         const bool bad = forward_frame(e, bgr, rows, cols, row_stride, n, embeds_out, crops_out, [&](int f0, int nf, size_t tight, hipStream_t s) {
             HIPCHK(hipMemcpyAsync(e->d_boxes, boxes + f0, sizeof(frt_bbox) * nf, hipMemcpyHostToDevice, s));
-            launch_crop_faces(e->d_frame, rows, cols, tight, 0, e->d_boxes, nullptr, 1, nf, 1, 112, 112, e->d_crops, e->d_in, e->d_valid, s);
+            launch_crop_faces(e->d_frame.get(), rows, cols, tight, 0, e->d_boxes, nullptr, 1, nf, 1, 112, 112, e->d_crops, e->d_in, e->d_valid, s);
         });
         if (bad) raise(FRT_ERR_EMPTY_ROI, "forward: empty or out-of-frame ROI (embedding set to zeros)");
     });
@@ -745,7 +726,7 @@ int frt_embedder_forward_aligned(frt_embedder *e, const uint8_t *bgr, int rows, 
         if (n == 0) return;
         const bool bad = forward_frame(e, bgr, rows, cols, row_stride, n, embeds_out, crops_out, [&](int f0, int nf, size_t tight, hipStream_t s) {
             HIPCHK(hipMemcpyAsync(e->d_lm, landmarks + (size_t)f0 * 10, sizeof(float) * 10 * nf, hipMemcpyHostToDevice, s));
-            launch_align_faces(e->d_frame, rows, cols, tight, 0, e->d_lm, nullptr, 1, nf, 1, e->d_crops, e->d_in, e->d_valid, s);
+            launch_align_faces(e->d_frame.get(), rows, cols, tight, 0, e->d_lm, nullptr, 1, nf, 1, e->d_crops, e->d_in, e->d_valid, s);
         });
         if (bad) raise(FRT_ERR_EMPTY_ROI, "forwardAligned: degenerate landmarks (embedding set to zeros)");
     });
@@ -816,16 +797,10 @@ int frt_embedder_enrol_faces(frt_embedder *e, frt_matcher *m, const frt_face_ima
         }
         use_device(e->device);
         frt_embedder::FaceStage &fs = e->faces;
-        if ((size_t)n > fs.embeds_cap) {
-            if (fs.d_embeds) (void)hipFree(fs.d_embeds);
-            fs.d_embeds = nullptr;
-            fs.embeds_cap = 0;
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&fs.d_embeds), (size_t)n * 512 * sizeof(float)));
-            fs.embeds_cap = (size_t)n;
-        }
-        embed_face_images(e, faces, n, embeds_out, nullptr, fs.d_embeds);
+        fs.d_embeds.reserve((size_t)n * 512);
+        embed_face_images(e, faces, n, embeds_out, nullptr, fs.d_embeds.get());
         // one edit: all n rows or none (it takes the matcher's lock itself and checks the gallery's state again)
-        const int rc = labels ? frt_matcher_gallery_add_labeled_dev(m, fs.d_embeds, labels, n) : frt_matcher_gallery_add_dev(m, fs.d_embeds, n);
+        const int rc = labels ? frt_matcher_gallery_add_labeled_dev(m, fs.d_embeds.get(), labels, n) : frt_matcher_gallery_add_dev(m, fs.d_embeds.get(), n);
         if (rc != FRT_OK) raise(rc, std::string(frthost::last_error()));
         if (first_row_out) *first_row_out = frt_matcher_num_rows(m) - n;
     });

@@ -58,19 +58,15 @@ struct frt_embedder {
     int *d_valid = nullptr;
     frt_bbox *d_boxes = nullptr;
     float *d_lm = nullptr;  // landmark staging of forward_aligned [max_batch][10]
-    uint8_t *d_frame = nullptr;
-    size_t frame_cap = 0;
+    DevBuf<uint8_t> d_frame;  // the caller's frame of frt_embedder_forward / _forward_aligned: grows to fit
     // ---- face images instead of frames (frt_embedder_embed_faces / _enrol_faces), allocated on first use: chunk i + 1 is packed into one
     //      pinned buffer and uploaded on `copy` into one arena while chunk i's prepare kernel and network pass run on `stream`
     struct FaceStage {
         hipStream_t copy = nullptr;
-        uint8_t *h_pack[2] = {nullptr, nullptr};  // pinned: [max_batch] descriptors, then the chunk's images with the row strides removed
-        uint8_t *d_pack[2] = {nullptr, nullptr};  // the same bytes on the device (descriptor table + byte arena)
-        size_t cap[2] = {0, 0};                   // image bytes either of a pair holds (they grow together)
-        hipEvent_t uploaded[2] = {nullptr, nullptr};  // h_pack[b] may be rewritten
-        hipEvent_t read[2] = {nullptr, nullptr};      // d_pack[b] may be rewritten: the prepare kernel that read it is done
-        float *d_embeds = nullptr;  // one enrolment call's embeddings [embeds_cap][512]
-        size_t embeds_cap = 0;
+        PackPair pack[2];  // pinned: [max_batch] descriptors, then the chunk's images with the row strides removed; the same bytes on the device
+        hipEvent_t uploaded[2] = {nullptr, nullptr};  // pack[b].h may be rewritten
+        hipEvent_t read[2] = {nullptr, nullptr};      // pack[b].d may be rewritten: the prepare kernel that read it is done
+        DevBuf<float> d_embeds;  // one enrolment call's embeddings [n][512]
     } faces;
     static constexpr int FC_SPLITS = 49;
     double flops_per_face = 0;

@@ -23,32 +23,24 @@ void ensure_image_stage(frt_pipeline *p, size_t need, bool crops) {
             // beside the pipeline's upload stream: the stage streams' priority class (a pool of hardware queues of its own, see ensure_async)
             HIPCHK(hipStreamCreateWithPriority(&is.ingest, hipStreamNonBlocking, p->copy_prio));
             HIPCHK(hipEventCreateWithFlags(&is.finished, hipEventDisableTiming));
-            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&is.h_count), sizeof(int32_t), hipHostMallocDefault));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_count), sizeof(int32_t)));
+            is.h_count.reserve(1);
+            is.d_count.reserve(1);
             for (int b = 0; b < ImageStage::NSET; ++b) {
                 HIPCHK(hipEventCreateWithFlags(&is.uploaded[b], hipEventDisableTiming));
                 HIPCHK(hipEventCreateWithFlags(&is.ready[b], hipEventDisableTiming));
                 HIPCHK(hipEventCreateWithFlags(&is.done[b], hipEventDisableTiming));
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_frames[b]), (size_t)p->max_frames * g.frame_h * g.frame_w * 3));
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_results[b]), F * sizeof(frt_face_result)));
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_embeds[b]), F * 512 * sizeof(float)));
-                HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&is.h_results[b]), F * sizeof(frt_face_result), hipHostMallocDefault));
-                HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&is.h_embeds[b]), F * 512 * sizeof(float), hipHostMallocDefault));
+                is.d_frames[b].reserve((size_t)p->max_frames * g.frame_h * g.frame_w * 3);
+                is.d_results[b].reserve(F);
+                is.d_embeds[b].reserve(F * 512);
+                is.h_results[b].reserve(F);
+                is.h_embeds[b].reserve(F * 512);
             }
             is.built = true;
         }
         for (int b = 0; b < ImageStage::NSET; ++b) {
-            if (crops && !is.d_crops[b]) HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_crops[b]), F * 112 * 112 * 3));
-            if (crops && !is.h_crops[b]) HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&is.h_crops[b]), F * 112 * 112 * 3, hipHostMallocDefault));
-            if (is.cap[b] >= need && is.h_pack[b] && is.d_pack[b]) continue;  // (both sets idle: every call ends with its work complete)
-            const size_t cap = (need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1);  // grows to fit
-            if (is.h_pack[b]) (void)hipHostFree(is.h_pack[b]);
-            if (is.d_pack[b]) (void)hipFree(is.d_pack[b]);
-            is.h_pack[b] = is.d_pack[b] = nullptr;
-            is.cap[b] = 0;
-            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&is.h_pack[b]), hdr + cap, hipHostMallocDefault));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_pack[b]), hdr + cap));
-            is.cap[b] = cap;
+            if (crops) is.d_crops[b].reserve(F * 112 * 112 * 3);
+            if (crops) is.h_crops[b].reserve(F * 112 * 112 * 3);
+            is.pack[b].reserve(hdr, need);  // (both sets idle: every call ends with its work complete)
         }
     } catch (...) {
         p->release_images();
@@ -74,16 +66,16 @@ void run_image_chunks(frt_pipeline *p, const frt_face_image *images, const std::
         const int b = (int)(ci & 1);
         const frt_face_chunk &c = chunks[ci];
         if (used[b]) wait_event_spinning(is.uploaded[b]);  // the pinned buffer is rewritten only after its upload
-        std::memcpy(is.h_pack[b], &desc[(size_t)c.first], (size_t)c.count * sizeof(frt_face_desc));
-        pack_face_images(images, desc.data(), c.first, c.count, is.h_pack[b] + hdr);
+        std::memcpy(is.pack[b].h.get(), &desc[(size_t)c.first], (size_t)c.count * sizeof(frt_face_desc));
+        pack_face_images(images, desc.data(), c.first, c.count, is.pack[b].h.get() + hdr);
         // the frame buffer only after the stages of the chunk that used it last (the arena: behind that chunk's resize on this stream)
         if (used[b]) HIPCHK(hipStreamWaitEvent(is.ingest, is.done[b], 0));
-        HIPCHK(hipMemcpyAsync(is.d_pack[b], is.h_pack[b], hdr + c.bytes, hipMemcpyHostToDevice, is.ingest));
+        HIPCHK(hipMemcpyAsync(is.pack[b].d.get(), is.pack[b].h.get(), hdr + c.bytes, hipMemcpyHostToDevice, is.ingest));
         HIPCHK(hipEventRecord(is.uploaded[b], is.ingest));
         {
             ProfScope ps(2, "images_resize", (double)c.count * g.frame_h * g.frame_w, is.ingest);
-            launch_images_resize(is.d_pack[b] + hdr, reinterpret_cast<const frt_face_desc *>(is.d_pack[b]), c.count, g.frame_h, g.frame_w, is.d_frames[b],
-                                 is.ingest);
+            launch_images_resize(is.pack[b].d.get() + hdr, reinterpret_cast<const frt_face_desc *>(is.pack[b].d.get()), c.count, g.frame_h, g.frame_w,
+                                 is.d_frames[b].get(), is.ingest);
         }
         HIPCHK(hipEventRecord(is.ready[b], is.ingest));
         used[b] = true;
@@ -93,11 +85,11 @@ void run_image_chunks(frt_pipeline *p, const frt_face_image *images, const std::
         const frt_face_chunk &c = chunks[ci];
         std::lock_guard<std::mutex> lk(p->run_mu);
         frt_pipeline::Request r;
-        r.frames = is.d_frames[b];
+        r.frames = is.d_frames[b].get();
         r.n = c.count;
-        r.results = is.d_results[b];
-        r.embeds = want_embeds ? is.d_embeds[b] : nullptr;
-        r.crops = want_crops ? is.d_crops[b] : nullptr;
+        r.results = is.d_results[b].get();
+        r.embeds = want_embeds ? is.d_embeds[b].get() : nullptr;
+        r.crops = want_crops ? is.d_crops[b].get() : nullptr;
         r.after = is.ready[b];
         p->run_dev(r);
         // A pairing mode that holds run_dev calls (frt_pipeline_set_pairing 1 .. 4 or -2) parks a chunk that could share a recogniser pass:
@@ -142,20 +134,10 @@ void frt_pipeline::release_images() {
         (void)hipStreamDestroy(is.ingest);
     }
     if (is.finished) (void)hipEventDestroy(is.finished);
-    if (is.h_count) (void)hipHostFree(is.h_count);
-    if (is.h_status) (void)hipHostFree(is.h_status);
-    if (is.h_face) (void)hipHostFree(is.h_face);
-    for (void *d : {(void *)is.d_count, (void *)is.d_rows, (void *)is.d_status, (void *)is.d_face})
-        if (d) (void)hipFree(d);
-    for (int b = 0; b < ImageStage::NSET; ++b) {
+    for (int b = 0; b < ImageStage::NSET; ++b)
         for (hipEvent_t ev : {is.uploaded[b], is.ready[b], is.done[b]})
             if (ev) (void)hipEventDestroy(ev);
-        for (void *h : {(void *)is.h_pack[b], (void *)is.h_results[b], (void *)is.h_embeds[b], (void *)is.h_crops[b]})
-            if (h) (void)hipHostFree(h);
-        for (void *d : {(void *)is.d_pack[b], (void *)is.d_frames[b], (void *)is.d_results[b], (void *)is.d_embeds[b], (void *)is.d_crops[b]})
-            if (d) (void)hipFree(d);
-    }
-    is = ImageStage{};
+    is = ImageStage{};  // every buffer goes: the next call starts over
 }
 
 extern "C" {
@@ -218,18 +200,18 @@ int frt_pipeline_run_images(frt_pipeline *p, const frt_face_image *images, int n
             p, images, desc, chunks, embeds_out != nullptr, crops_out != nullptr,
             [&](const frt_face_chunk &c, int b, hipStream_t s) {
                 const size_t nf = (size_t)c.count * K;
-                HIPCHK(hipMemcpyAsync(is.h_results[b], is.d_results[b], nf * sizeof(frt_face_result), hipMemcpyDeviceToHost, s));
-                if (embeds_out) HIPCHK(hipMemcpyAsync(is.h_embeds[b], is.d_embeds[b], nf * 512 * sizeof(float), hipMemcpyDeviceToHost, s));
-                if (crops_out) HIPCHK(hipMemcpyAsync(is.h_crops[b], is.d_crops[b], nf * 112 * 112 * 3, hipMemcpyDeviceToHost, s));
+                HIPCHK(hipMemcpyAsync(is.h_results[b].get(), is.d_results[b].get(), nf * sizeof(frt_face_result), hipMemcpyDeviceToHost, s));
+                if (embeds_out) HIPCHK(hipMemcpyAsync(is.h_embeds[b].get(), is.d_embeds[b].get(), nf * 512 * sizeof(float), hipMemcpyDeviceToHost, s));
+                if (crops_out) HIPCHK(hipMemcpyAsync(is.h_crops[b].get(), is.d_crops[b].get(), nf * 112 * 112 * 3, hipMemcpyDeviceToHost, s));
             },
             [&](const frt_face_chunk &c, int b) {
                 const size_t nf = (size_t)c.count * K, o = (size_t)c.first * K;
                 for (size_t f = 0; f < nf; ++f) {  // the chunk-local frame index gets the chunk's base
-                    results[o + f] = is.h_results[b][f];
+                    results[o + f] = is.h_results[b].get()[f];
                     results[o + f].frame += c.first;
                 }
-                if (embeds_out) std::memcpy(embeds_out + o * 512, is.h_embeds[b], nf * 512 * sizeof(float));
-                if (crops_out) std::memcpy(crops_out + o * 112 * 112 * 3, is.h_crops[b], nf * 112 * 112 * 3);
+                if (embeds_out) std::memcpy(embeds_out + o * 512, is.h_embeds[b].get(), nf * 512 * sizeof(float));
+                if (crops_out) std::memcpy(crops_out + o * 112 * 112 * 3, is.h_crops[b].get(), nf * 112 * 112 * 3);
             });
     });
 }
@@ -262,31 +244,21 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
         std::lock_guard<std::mutex> li(p->images_mu);
         use_device(p->det->device);
         ImageStage &is = p->images;
-        if ((size_t)n > is.enrol_cap) {  // one call's status words, faces and dense rows
-            for (void *d : {(void *)is.d_rows, (void *)is.d_status, (void *)is.d_face})
-                if (d) (void)hipFree(d);
-            for (void *h : {(void *)is.h_status, (void *)is.h_face})
-                if (h) (void)hipHostFree(h);
-            is.d_rows = nullptr;
-            is.d_status = is.h_status = nullptr;
-            is.d_face = is.h_face = nullptr;
-            is.enrol_cap = 0;
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_rows), (size_t)n * 512 * sizeof(float)));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_status), (size_t)n * sizeof(int32_t)));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&is.d_face), (size_t)n * sizeof(frt_face_result)));
-            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&is.h_status), (size_t)n * sizeof(int32_t), hipHostMallocDefault));
-            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&is.h_face), (size_t)n * sizeof(frt_face_result), hipHostMallocDefault));
-            is.enrol_cap = (size_t)n;
-        }
+        // one call's status words, faces and dense rows
+        is.d_rows.reserve((size_t)n * 512);
+        is.d_status.reserve((size_t)n);
+        is.d_face.reserve((size_t)n);
+        is.h_status.reserve((size_t)n);
+        is.h_face.reserve((size_t)n);
         bool first_chunk = true;
         run_image_chunks(
             p, images, desc, chunks, true, false,
             [&](const frt_face_chunk &c, int b, hipStream_t s) {  // after each chunk the selection kernel appends to the one dense buffer
-                if (first_chunk) HIPCHK(hipMemsetAsync(is.d_count, 0, sizeof(int32_t), s));
+                if (first_chunk) HIPCHK(hipMemsetAsync(is.d_count.get(), 0, sizeof(int32_t), s));
                 first_chunk = false;
                 ProfScope ps(2, "enrol_select", (double)c.count, s);
-                launch_enrol_select(is.d_results[b], is.d_embeds[b], c.count, p->max_faces, is.d_status + c.first, is.d_face + c.first, is.d_rows,
-                                    is.d_count, s);
+                launch_enrol_select(is.d_results[b].get(), is.d_embeds[b].get(), c.count, p->max_faces, is.d_status.get() + c.first, is.d_face.get() + c.first,
+                                    is.d_rows.get(), is.d_count.get(), s);
             },
             [](const frt_face_chunk &, int) {});
         {  // status, faces and the count come down once, behind the last chunk's selection, into pinned memory: the copies are asynchronous
@@ -294,22 +266,22 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
             std::lock_guard<std::mutex> lk(p->run_mu);
             p->ensure_stream();
             hipStream_t s = p->stream;
-            HIPCHK(hipMemcpyAsync(is.h_count, is.d_count, sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            HIPCHK(hipMemcpyAsync(is.h_status, is.d_status, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-            if (faces_out) HIPCHK(hipMemcpyAsync(is.h_face, is.d_face, (size_t)n * sizeof(frt_face_result), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(is.h_count.get(), is.d_count.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(is.h_status.get(), is.d_status.get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            if (faces_out) HIPCHK(hipMemcpyAsync(is.h_face.get(), is.d_face.get(), (size_t)n * sizeof(frt_face_result), hipMemcpyDeviceToHost, s));
             HIPCHK(hipEventRecord(is.finished, s));
         }
         wait_event_spinning(is.finished);
-        const int count = *is.h_count;
+        const int count = *is.h_count.get();
         if (count < 0 || count > n) raise(FRT_ERR_DEVICE, "enrolImages: the selection returned an impossible count");
-        std::memcpy(status_out, is.h_status, (size_t)n * sizeof(int32_t));
+        std::memcpy(status_out, is.h_status.get(), (size_t)n * sizeof(int32_t));
         if (faces_out) {
-            std::memcpy(faces_out, is.h_face, (size_t)n * sizeof(frt_face_result));
+            std::memcpy(faces_out, is.h_face.get(), (size_t)n * sizeof(frt_face_result));
             for (const frt_face_chunk &c : chunks)  // the chunk-local frame index gets the chunk's base
                 for (int i = c.first; i < c.first + c.count; ++i) faces_out[i].frame += c.first;
         }
         if (count == 0) return;  // no acceptable photo: no edit
-        if (embeds_out) HIPCHK(hipMemcpy(embeds_out, is.d_rows, (size_t)count * 512 * sizeof(float), hipMemcpyDeviceToHost));
+        if (embeds_out) HIPCHK(hipMemcpy(embeds_out, is.d_rows.get(), (size_t)count * 512 * sizeof(float), hipMemcpyDeviceToHost));
         std::vector<int32_t> accepted;
         if (labels) {
             for (int i = 0; i < n; ++i)
@@ -317,7 +289,7 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
             if ((int)accepted.size() != count) raise(FRT_ERR_DEVICE, "enrolImages: status words and row count disagree");
         }
         // one edit: all accepted rows or none (it takes the matcher's lock itself, checks the gallery's state again and says where the rows went)
-        const int first = matcher_add_rows_dev(m, is.d_rows, labels ? accepted.data() : nullptr, count);
+        const int first = matcher_add_rows_dev(m, is.d_rows.get(), labels ? accepted.data() : nullptr, count);
         if (first_row_out) *first_row_out = first;
         if (n_enrolled_out) *n_enrolled_out = count;
     });

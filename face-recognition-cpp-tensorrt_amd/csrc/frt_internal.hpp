@@ -18,6 +18,7 @@
 
 #include "frt_host.hpp"
 #include "frt_kernels.h"
+#include "frt_owned.hpp"
 #include "frt_weights.hpp"
 
 void launch_pack_results(const frt_bbox *boxes, const int *n_boxes, const int *valid, const int32_t *idx, const float *sim, int max_faces,
@@ -52,6 +53,44 @@ struct Arena {
     void release() {
         for (void *p : ptrs) (void)hipFree(p);
         ptrs.clear();
+    }
+};
+
+// Buffers that are resized or replaced after create time own themselves (frt_owned.hpp); Arena stays for what is allocated once.
+// Every object that holds one is destroyed by its *_destroy, which sets the device first.
+struct DeviceMem {
+    static void *alloc(size_t bytes) {
+        void *p = nullptr;
+        HIPCHK(hipMalloc(&p, bytes));
+        return p;
+    }
+    static void free(void *p) { (void)hipFree(p); }
+};
+struct PinnedMem {
+    static void *alloc(size_t bytes) {
+        void *p = nullptr;
+        HIPCHK(hipHostMalloc(&p, bytes, hipHostMallocDefault));
+        return p;
+    }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+template <class T>
+using DevBuf = Owned<T, DeviceMem>;
+template <class T>
+using PinnedBuf = Owned<T, PinnedMem>;
+
+// The staging of packed images (face images, whole photos): a pinned buffer and its device twin, each `hdr` bytes of descriptors in front
+// of at least `need` image bytes.  They grow together, to fit, in steps of 1 MiB.
+struct PackPair {
+    PinnedBuf<uint8_t> h;
+    DevBuf<uint8_t> d;
+    void reserve(size_t hdr, size_t need) {
+        if (h.capacity() >= hdr + need && d.capacity() >= hdr + need) return;
+        const size_t bytes = hdr + ((need + ((size_t)1 << 20) - 1) & ~(((size_t)1 << 20) - 1));
+        h.reset();
+        d.reset();
+        h.reserve(bytes);
+        d.reserve(bytes);
     }
 };
 

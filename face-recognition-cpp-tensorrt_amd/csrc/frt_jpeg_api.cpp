@@ -1,23 +1,12 @@
 // C ABI of the JPEG frame-ingest / reply steps (include/frt.h, section "Frame ingest" and "Reply step"): host threads do the
 // entropy coding, the device does the transforms (kernels_jpeg.hip).  No CPU pixel path: without a HIP device every entry point
 // except frt_jpeg_info / frt_base64_encode fails with FRT_ERR_DEVICE.
-#include <atomic>
 #include <condition_variable>
-#include <cstring>
 #include <functional>
-#include <memory>
-#include <mutex>
-#include <thread>
-#include <vector>
 
-#include "frt_host.hpp"
+#include "frt_internal.hpp"
 #include "frt_jpeg.hpp"
 #include "frt_jpeg_dev.h"
-#include "frt_kernels.h"
-
-using frthost::guarded;
-using frthost::raise;
-using frthost::use_device;
 
 namespace {
 
@@ -101,16 +90,18 @@ struct frt_jpeg_decoder {
     // two staging sets so that the host can entropy-decode batch b+1 while batch b is still being copied / transformed
     static constexpr int NSET = 2;
     struct Set {
-        int16_t *h_coef = nullptr, *d_coef = nullptr;
-        JpegImageDesc *h_desc = nullptr, *d_desc = nullptr;
-        uint8_t *d_planes = nullptr, *d_full = nullptr;  // component planes; decoded full-size frames (only when a resize follows)
+        PinnedBuf<int16_t> h_coef;
+        DevBuf<int16_t> d_coef;
+        PinnedBuf<JpegImageDesc> h_desc;
+        DevBuf<JpegImageDesc> d_desc;
+        DevBuf<uint8_t> d_planes, d_full;  // component planes; decoded full-size frames (only when a resize follows)
         hipEvent_t ev = nullptr;
         bool pending = false;
     } set[NSET];
     int cur = 0;
     size_t blocks_per_image = 0, plane_bytes_per_image = 0;
     // encoder scratch (reply step)
-    uint16_t *d_q = nullptr;
+    DevBuf<uint16_t> d_q;
     int q_quality = -1;
     // A private stream only when a caller really passes NULL: an extra non-blocking stream created before a pipeline's stage streams
     // disturbs ROCm's stream -> hardware-queue mapping (see frt_matcher::load_begin); callers that feed a pipeline pass their producer stream.
@@ -119,9 +110,9 @@ struct frt_jpeg_decoder {
         return own_stream;
     }
     frtjpeg::EncTables enc{};
-    uint8_t *d_crops = nullptr;
-    int16_t *d_eblocks = nullptr, *h_eblocks = nullptr;
-    size_t ecap_pixels = 0, ecap_blocks = 0;
+    DevBuf<uint8_t> d_crops;  // host input of the encoder; the quantised blocks on the device and pinned: all grow to fit
+    DevBuf<int16_t> d_eblocks;
+    PinnedBuf<int16_t> h_eblocks;
 };
 
 namespace {
@@ -228,13 +219,13 @@ int frt_jpeg_decoder_create(int max_images, int max_width, int max_height, int n
         d->plane_bytes_per_image = d->blocks_per_image * 64;
         // (own_stream is created on first use with a NULL caller stream: see ensure_stream)
         for (frt_jpeg_decoder::Set &s : d->set) {
-            const size_t cb = d->blocks_per_image * max_images * 128;
-            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s.h_coef), cb, hipHostMallocDefault));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&s.d_coef), cb));
-            HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&s.h_desc), sizeof(JpegImageDesc) * max_images, hipHostMallocDefault));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&s.d_desc), sizeof(JpegImageDesc) * max_images));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&s.d_planes), d->plane_bytes_per_image * max_images));
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&s.d_full), (size_t)max_width * max_height * 3 * max_images));
+            const size_t coefs = d->blocks_per_image * max_images * 64;
+            s.h_coef.reserve(coefs);
+            s.d_coef.reserve(coefs);
+            s.h_desc.reserve((size_t)max_images);
+            s.d_desc.reserve((size_t)max_images);
+            s.d_planes.reserve(d->plane_bytes_per_image * max_images);
+            s.d_full.reserve((size_t)max_width * max_height * 3 * max_images);
             HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
         }
         *out = d.release();
@@ -245,18 +236,10 @@ void frt_jpeg_decoder_destroy(frt_jpeg_decoder *d) {
     if (!d) return;
     (void)hipSetDevice(d->device);
     (void)hipDeviceSynchronize();
-    for (frt_jpeg_decoder::Set &s : d->set) {
-        if (s.h_coef) (void)hipHostFree(s.h_coef);
-        if (s.h_desc) (void)hipHostFree(s.h_desc);
-        for (void *p : {(void *)s.d_coef, (void *)s.d_desc, (void *)s.d_planes, (void *)s.d_full})
-            if (p) (void)hipFree(p);
+    for (frt_jpeg_decoder::Set &s : d->set)
         if (s.ev) (void)hipEventDestroy(s.ev);
-    }
-    for (void *p : {(void *)d->d_q, (void *)d->d_crops, (void *)d->d_eblocks})
-        if (p) (void)hipFree(p);
-    if (d->h_eblocks) (void)hipHostFree(d->h_eblocks);
     if (d->own_stream) (void)hipStreamDestroy(d->own_stream);
-    delete d;
+    delete d;  // the staging frees itself, on the device set above
 }
 
 // n JPEG byte strings -> n u8 BGR frames [out_h][out_w][3] on the device (frames_dev), asynchronous on hip_stream.
@@ -292,7 +275,7 @@ int frt_jpeg_decode_batch_dev(frt_jpeg_decoder *d, const uint8_t *const *data, c
             any_resize = any_resize || resize;
             // images that already have the output size are written straight into frames_dev
             const uint64_t out_off = resize ? (uint64_t)i * d->max_w * d->max_h * 3 : (uint64_t)i * out_w * out_h * 3;
-            fill_desc(h, s.h_desc[i], blk, pl, out_off);
+            fill_desc(h, s.h_desc.get()[i], blk, pl, out_off);
             blk += h.total_blocks;
             pl += h.total_blocks * 64;
             for (int c = 0; c < h.ncomp; ++c) max_bpc = std::max(max_bpc, h.c[c].bw * h.c[c].bh);
@@ -303,7 +286,7 @@ int frt_jpeg_decode_batch_dev(frt_jpeg_decoder *d, const uint8_t *const *data, c
         std::atomic<int> bad{0};
         d->pool->parallel_for(n, [&](int i) {
             const frtjpeg::Header &h = parsed[(size_t)i].h;
-            int16_t *c = s.h_coef + s.h_desc[i].coef_block0 * 64;
+            int16_t *c = s.h_coef.get() + s.h_desc.get()[i].coef_block0 * 64;
             std::memset(c, 0, h.total_blocks * 128);
             if (frtjpeg::decode_coefficients(data[i], sizes[i], parsed[(size_t)i], c, errs[(size_t)i])) bad.fetch_add(1);
         });
@@ -311,20 +294,20 @@ int frt_jpeg_decode_batch_dev(frt_jpeg_decoder *d, const uint8_t *const *data, c
             for (const std::string &e : errs)
                 if (!e.empty()) raise(FRT_ERR_FORMAT, e);
         // ---- device: coefficients + descriptors up, transforms, optional resize
-        HIPCHK(hipMemcpyAsync(s.d_coef, s.h_coef, blk * 128, hipMemcpyHostToDevice, st));
-        HIPCHK(hipMemcpyAsync(s.d_desc, s.h_desc, sizeof(JpegImageDesc) * n, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s.d_coef.get(), s.h_coef.get(), blk * 128, hipMemcpyHostToDevice, st));
+        HIPCHK(hipMemcpyAsync(s.d_desc.get(), s.h_desc.get(), sizeof(JpegImageDesc) * n, hipMemcpyHostToDevice, st));
         uint8_t *frames = reinterpret_cast<uint8_t *>(frames_dev);
         if (!any_resize) {
-            launch_jpeg_decode(s.d_coef, s.d_desc, n, max_bpc, max_w, max_h, s.d_planes, frames, st);
+            launch_jpeg_decode(s.d_coef.get(), s.d_desc.get(), n, max_bpc, max_w, max_h, s.d_planes.get(), frames, st);
         } else {
             // mixed batch: two destination buffers, so the descriptors of same-size images must point into frames_dev as well; simplest
             // correct form: decode everything into d_full, then resize / copy every image into its slot
-            for (int i = 0; i < n; ++i) s.h_desc[i].out_off = (uint64_t)i * d->max_w * d->max_h * 3;
-            HIPCHK(hipMemcpyAsync(s.d_desc, s.h_desc, sizeof(JpegImageDesc) * n, hipMemcpyHostToDevice, st));
-            launch_jpeg_decode(s.d_coef, s.d_desc, n, max_bpc, max_w, max_h, s.d_planes, s.d_full, st);
+            for (int i = 0; i < n; ++i) s.h_desc.get()[i].out_off = (uint64_t)i * d->max_w * d->max_h * 3;
+            HIPCHK(hipMemcpyAsync(s.d_desc.get(), s.h_desc.get(), sizeof(JpegImageDesc) * n, hipMemcpyHostToDevice, st));
+            launch_jpeg_decode(s.d_coef.get(), s.d_desc.get(), n, max_bpc, max_w, max_h, s.d_planes.get(), s.d_full.get(), st);
             for (int i = 0; i < n; ++i) {
                 const frtjpeg::Header &h = parsed[(size_t)i].h;
-                const uint8_t *src = s.d_full + (size_t)i * d->max_w * d->max_h * 3;
+                const uint8_t *src = s.d_full.get() + (size_t)i * d->max_w * d->max_h * 3;
                 uint8_t *dst = frames + (size_t)i * out_w * out_h * 3;
                 if (h.width == out_w && h.height == out_h)
                     HIPCHK(hipMemcpyAsync(dst, src, (size_t)out_w * out_h * 3, hipMemcpyDeviceToDevice, st));
@@ -346,18 +329,17 @@ int frt_jpeg_decode(frt_jpeg_decoder *d, const uint8_t *data, size_t size, uint8
         if (frt_jpeg_info(data, size, &w, &h, &c) != FRT_OK) raise(FRT_ERR_FORMAT, frthost::last_error());
         if ((size_t)w * h * 3 > capacity) raise(FRT_ERR_CAPACITY, "jpeg decode: output buffer too small");
         use_device(d->device);
-        uint8_t *dev = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&dev), (size_t)w * h * 3));
+        DevBuf<uint8_t> dev;
+        dev.reserve((size_t)w * h * 3);
         const uint8_t *one[1] = {data};
         const size_t sz[1] = {size};
-        const int rc = frt_jpeg_decode_batch_dev(d, one, sz, 1, dev, h, w, nullptr);
+        const int rc = frt_jpeg_decode_batch_dev(d, one, sz, 1, dev.get(), h, w, nullptr);
         std::string msg = frthost::last_error();
         hipError_t e = hipSuccess;
         if (rc == FRT_OK) {
             e = hipStreamSynchronize(d->ensure_stream());
-            if (e == hipSuccess) e = hipMemcpy(bgr_out, dev, (size_t)w * h * 3, hipMemcpyDeviceToHost);
+            if (e == hipSuccess) e = hipMemcpy(bgr_out, dev.get(), (size_t)w * h * 3, hipMemcpyDeviceToHost);
         }
-        (void)hipFree(dev);
         if (rc != FRT_OK) raise(rc, msg);
         HIPCHK(e);
         if (width) *width = w;
@@ -369,25 +351,14 @@ int frt_jpeg_decode(frt_jpeg_decoder *d, const uint8_t *data, size_t size, uint8
 static void encode_setup(frt_jpeg_decoder *d, int quality, int n, int rows, int cols) {
     if (d->q_quality != quality) {
         frtjpeg::make_enc_tables(quality, d->enc);
-        if (!d->d_q) HIPCHK(hipMalloc(reinterpret_cast<void **>(&d->d_q), sizeof(uint16_t) * 128));
-        HIPCHK(hipMemcpy(d->d_q, d->enc.q, sizeof(uint16_t) * 128, hipMemcpyHostToDevice));
+        d->d_q.reserve(128);
+        HIPCHK(hipMemcpy(d->d_q.get(), d->enc.q, sizeof(uint16_t) * 128, hipMemcpyHostToDevice));
         d->q_quality = quality;
     }
     const size_t px = (size_t)n * rows * cols * 3, blocks = (size_t)n * 6 * ((cols + 15) / 16) * ((rows + 15) / 16);
-    if (px > d->ecap_pixels) {
-        if (d->d_crops) (void)hipFree(d->d_crops);
-        d->d_crops = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d->d_crops), px));
-        d->ecap_pixels = px;
-    }
-    if (blocks > d->ecap_blocks) {
-        if (d->d_eblocks) (void)hipFree(d->d_eblocks);
-        if (d->h_eblocks) (void)hipHostFree(d->h_eblocks);
-        d->d_eblocks = d->h_eblocks = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d->d_eblocks), blocks * 128));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&d->h_eblocks), blocks * 128, hipHostMallocDefault));
-        d->ecap_blocks = blocks;
-    }
+    d->d_crops.reserve(px);
+    d->d_eblocks.reserve(blocks * 64);
+    d->h_eblocks.reserve(blocks * 64);
 }
 
 // cv::imencode(".jpg", crop) (src/app.cpp:328; quality 95, 4:2:0, standard tables) for n equally sized u8 BGR images.
@@ -411,16 +382,16 @@ int frt_jpeg_encode_batch_after(frt_jpeg_decoder *d, const void *bgr, int device
         if (ready_event) HIPCHK(hipStreamWaitEvent(st, reinterpret_cast<hipEvent_t>(ready_event), 0));
         const uint8_t *src = reinterpret_cast<const uint8_t *>(bgr);
         if (!device_input) {
-            HIPCHK(hipMemcpyAsync(d->d_crops, bgr, (size_t)n * rows * cols * 3, hipMemcpyHostToDevice, st));
-            src = d->d_crops;
+            HIPCHK(hipMemcpyAsync(d->d_crops.get(), bgr, (size_t)n * rows * cols * 3, hipMemcpyHostToDevice, st));
+            src = d->d_crops.get();
         }
-        launch_jpeg_encode_blocks(src, n, rows, cols, d->d_q, d->d_eblocks, st);
+        launch_jpeg_encode_blocks(src, n, rows, cols, d->d_q.get(), d->d_eblocks.get(), st);
         HIPCHK(hipGetLastError());
         const size_t per_img = (size_t)6 * ((cols + 15) / 16) * ((rows + 15) / 16);
-        HIPCHK(hipMemcpyAsync(d->h_eblocks, d->d_eblocks, per_img * n * 128, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(d->h_eblocks.get(), d->d_eblocks.get(), per_img * n * 128, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
         std::vector<std::vector<uint8_t>> bytes((size_t)n);
-        d->pool->parallel_for(n, [&](int i) { frtjpeg::write_jfif_420(d->enc, cols, rows, d->h_eblocks + (size_t)i * per_img * 64, bytes[(size_t)i]); });
+        d->pool->parallel_for(n, [&](int i) { frtjpeg::write_jfif_420(d->enc, cols, rows, d->h_eblocks.get() + (size_t)i * per_img * 64, bytes[(size_t)i]); });
         for (int i = 0; i < n; ++i) {
             if (bytes[(size_t)i].size() > out_stride) raise(FRT_ERR_CAPACITY, "jpeg encode: output slot too small");
             std::memcpy(out + (size_t)i * out_stride, bytes[(size_t)i].data(), bytes[(size_t)i].size());

@@ -6,6 +6,222 @@
 #include "frt_holes.h"
 #include "frt_templates.hpp"
 
+// ------------------------------------------------------------------------------------------------------------- gallery storage
+// fp32-stored galleries of 512 columns are screened through an INT8 shadow (half the bytes of the per-call scan; kernels_match.hip);
+// other widths through an fp16 shadow
+void frt_matcher::Gallery::alloc_shadow(int D) {
+    g8.reset();
+    g8_scale.reset();
+    rows16.reset();
+    shadow_rows = 0;
+    if (D == 512) {
+        g8.reserve(gallery8_bytes(cap_rows, D));
+        g8_scale.reserve(cap_tiles() * 128);
+    } else {
+        rows16.reserve(gallery16_elems(cap_rows, D));
+    }
+    shadow_rows = (int)(cap_tiles() * 128);
+}
+
+// int8 rows of value 0 are bytes of 0x80 (biased) under a scale of 0; fp16 rows - a shadow or the stored rows themselves - are zeros
+void frt_matcher::Gallery::pad_tiles(size_t n_tiles, int D, hipStream_t s) {
+    if (cap_tiles() <= n_tiles) return;
+    const size_t pad_rows = (cap_tiles() - n_tiles) * 128;
+    if (g8) {
+        HIPCHK(hipMemsetAsync(g8.get() + n_tiles * 128 * D, 0x80, pad_rows * D, s));
+        HIPCHK(hipMemsetAsync(g8_scale.get() + n_tiles * 128, 0, pad_rows * sizeof(float), s));
+    } else if (rows16) {
+        HIPCHK(hipMemsetAsync(rows16.get() + n_tiles * 128 * D, 0, pad_rows * D * sizeof(half_t), s));
+    }
+}
+
+void frt_matcher::build_screen_data() {
+    d_edit_bits.reserve(2);
+    int *bits = d_edit_bits.get();
+    HIPCHK(hipMemsetAsync(bits, 0, 2 * sizeof(int), stream));
+    if (gal.store16) {
+        launch_rows_norm(gal.rows16.get(), 0, N, D, bits + 1, stream);
+    } else {
+        if (gal.shadow_rows < gal.cap_rows) gal.alloc_shadow(D);
+        if (gal.g8) launch_gallery_shadow8(gal.rows32.get(), N, D, gal.g8.get(), gal.g8_scale.get(), bits, bits + 1, stream);
+        else launch_gallery_shadow(gal.rows32.get(), N, D, gal.rows16.get(), bits + 1, stream);
+        gal.pad_tiles(((size_t)N + 127) / 128, D, stream);  // the tiles an add will fill later
+    }
+    read_bounds(false);
+}
+
+void frt_matcher::read_bounds(bool merge) {
+    int bits[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(bits, d_edit_bits.get(), sizeof(bits), hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    float e2, n2;
+    std::memcpy(&e2, &bits[0], 4);
+    std::memcpy(&n2, &bits[1], 4);
+    const float e = std::sqrt(e2), n = std::sqrt(n2);
+    auto upper = [](float old, float nw) { return (old != old || nw <= old) ? old : nw; };
+    gerr = merge ? upper(gerr, e) : e;
+    gmax_norm = merge ? upper(gmax_norm, n) : n;
+}
+
+void frt_matcher::ensure_label_room(int rows, int keep, hipStream_t s) {
+    if ((size_t)rows <= d_labels.capacity()) return;
+    DevBuf<int32_t> nl;
+    nl.reserve((size_t)rows);
+    if (keep > 0 && d_labels) {
+        hipError_t e = hipMemcpyAsync(nl.get(), d_labels.get(), (size_t)keep * sizeof(int32_t), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        HIPCHK(e);
+    }
+    d_labels = std::move(nl);
+}
+
+void frt_matcher::ensure_queries(int F) {
+    if (F <= q_cap && qs.partial && scratch_rows >= gal.cap_rows && (!screen || qs.tilemax)) return;
+    const size_t cap = (size_t)std::max(std::max(F, q_cap), 128);
+    const int rows = std::max(gal.cap_rows, N);
+    ++generation;  // scratch buffers move
+    qs = Scratch{};  // everything goes before anything comes
+    qs.q.reserve(cap * D);
+    qs.sim.reserve(cap * KCAP);
+    qs.idx.reserve(cap * KCAP);
+    qs.lab.reserve(cap * KCAP);
+    qs.kth.reserve(cap);
+    qs.partial.reserve((size_t)match_top1_blocks(rows, 0) * cap);  // [blocks][cap], blocks <= those of `rows`
+    if (screen) {
+        const size_t tiles = ((size_t)rows + 127) / 128;
+        qs.tilemax.reserve(cap * tiles * 4);  // 4 coarse entries per tile (one per wave)
+        qs.pair_cap = std::max((int)cap * FRT_MATCH_SEL_SUB, 8192);  // (a multiple of the FRT_MATCH_SEL_SUB sub-lists)
+        qs.wgmax.reserve((size_t)FRT_MATCH_COARSE_WG * cap);
+        qs.pairs.reserve((size_t)qs.pair_cap);
+        qs.ctl.reserve(FRT_MATCH_CTL_WORDS);
+        HIPCHK(hipMemset(qs.ctl.get(), 0, FRT_MATCH_CTL_WORDS * sizeof(int)));
+        qs.qkey.reserve(cap);
+    }
+    q_cap = (int)cap;
+    scratch_rows = rows;
+    bind_scratch();
+}
+
+// ------------------------------------------------------------------------------------------------------------- streaming load
+void frt_matcher::load_release_staging() {
+    for (int i = 0; i < Load::NCH; ++i) {
+        ld.h_stage[i].reset();
+        ld.d_stage[i].reset();
+        if (ld.ev[i]) (void)hipEventDestroy(ld.ev[i]);
+        ld.ev[i] = nullptr;
+        ld.pending[i] = false;
+    }
+    ld.stage_floats = 0;
+}
+
+void frt_matcher::load_abort() {
+    if (ld.s) (void)hipStreamSynchronize(ld.s);
+    ld.new32.reset();
+    ld.new16.reset();
+    ld.active = false;
+}
+
+void frt_matcher::load_begin(int cap, int cols) {
+    if (ld.active) load_abort();
+    // The load runs on the matcher's own stream.  NOT on a stream of its own: one more hipStreamCreateWithFlags(hipStreamNonBlocking)
+    // stream in the process before the pipeline's stage streams exist changes how ROCm maps those onto hardware queues, and the
+    // stages of consecutive calls stop overlapping (measured: batch-1 step 0.56 -> 1.39 ms, batch-32 step +10 %).
+    ld.s = stream;
+    const size_t need = (size_t)Load::CH_ROWS * cols;
+    if (ld.stage_floats != need) {
+        load_release_staging();
+        for (int i = 0; i < Load::NCH; ++i) {
+            ld.h_stage[i].reserve(need);
+            HIPCHK(hipEventCreateWithFlags(&ld.ev[i], hipEventDisableTiming));
+        }
+        ld.stage_floats = need;
+    }
+    ld.f16 = want16;
+    ld.cap = cap;
+    ld.D = cols;
+    ld.rows = ld.fill = ld.cur = 0;
+    ld.alloc = cap > 0 ? std::max(cap, reserve_rows) : 0;
+    ld.new32.reset();  // (an aborted load left none; a committed one moved them out)
+    ld.new16.reset();
+    if (cap > 0) {
+        if (ld.f16) {
+            ld.new16.reserve(gallery16_elems(ld.alloc, cols));
+            HIPCHK(hipMemsetAsync(ld.new16.get(), 0, gallery16_elems(ld.alloc, cols) * sizeof(half_t), ld.s));  // fragment order, zero pad rows
+            for (int i = 0; i < Load::NCH; ++i) ld.d_stage[i].reserve(need);
+        } else {
+            ld.new32.reserve((size_t)ld.alloc * cols);
+        }
+    }
+    ld.active = true;
+}
+
+void frt_matcher::load_flush() {
+    if (!ld.fill) return;
+    const int c = ld.cur;
+    const size_t off = (size_t)(ld.rows - ld.fill) * ld.D, n = (size_t)ld.fill * ld.D;
+    if (ld.f16) {
+        HIPCHK(hipMemcpyAsync(ld.d_stage[c].get(), ld.h_stage[c].get(), n * sizeof(float), hipMemcpyHostToDevice, ld.s));
+        launch_rows_to_half(ld.d_stage[c].get(), (long)(ld.rows - ld.fill), (long)ld.fill, ld.D, ld.new16.get(), ld.s);  // (chunks start on 128-row tiles)
+    } else {
+        HIPCHK(hipMemcpyAsync(ld.new32.get() + off, ld.h_stage[c].get(), n * sizeof(float), hipMemcpyHostToDevice, ld.s));
+    }
+    HIPCHK(hipEventRecord(ld.ev[c], ld.s));
+    ld.pending[c] = true;
+    ld.cur = (c + 1) % Load::NCH;
+    ld.fill = 0;
+    if (ld.pending[ld.cur]) {  // the chunk about to be refilled must have left the host (and its landing buffer)
+        HIPCHK(hipEventSynchronize(ld.ev[ld.cur]));
+        ld.pending[ld.cur] = false;
+    }
+}
+
+void frt_matcher::load_append(const float *rows, int n) {
+    if (!ld.active) raise(FRT_ERR_INVALID, "gallery_append: no load in progress (call frt_matcher_gallery_begin first)");
+    if (n < 0 || (n > 0 && !rows)) raise(FRT_ERR_INVALID, "gallery_append: bad argument");
+    if ((long)ld.rows + n > ld.cap) raise(FRT_ERR_CAPACITY, "gallery_append: more rows than gallery_begin reserved (initKnownEmbeds)");
+    while (n > 0) {
+        const int take = std::min(n, Load::CH_ROWS - ld.fill);
+        std::memcpy(ld.h_stage[ld.cur].get() + (size_t)ld.fill * ld.D, rows, (size_t)take * ld.D * sizeof(float));
+        ld.fill += take;
+        ld.rows += take;
+        rows += (size_t)take * ld.D;
+        n -= take;
+        if (ld.fill == Load::CH_ROWS) load_flush();
+    }
+}
+
+void frt_matcher::load_commit() {
+    if (!ld.active) raise(FRT_ERR_INVALID, "gallery_commit: no load in progress");
+    load_flush();
+    HIPCHK(hipStreamSynchronize(ld.s));
+    for (bool &p : ld.pending) p = false;
+    HIPCHK(hipStreamSynchronize(stream));
+    if (busy) HIPCHK(hipEventSynchronize(ev_busy));  // (the streams are synchronised: no scan is reading the gallery that goes)
+    Gallery loaded;  // an empty load leaves an empty gallery: nothing to keep
+    loaded.store16 = ld.f16;
+    if (ld.rows > 0) {
+        loaded.rows32 = std::move(ld.new32);
+        loaded.rows16 = std::move(ld.new16);
+        loaded.cap_rows = ld.alloc;
+    }
+    ld.new32.reset();
+    ld.new16.reset();
+    ld.active = false;
+    gerr = 0.f;
+    drop_labels();  // a new gallery: its rows have no labels until frt_matcher_set_labels
+    ++generation;
+    N = ld.rows;
+    D = ld.D;
+    std::swap(gal, loaded);
+    loaded = Gallery{};  // the previous gallery, with the new pointers in place (hipFree waits for the device: stages of earlier pipeline calls have finished with it)
+    screen = N >= SCREEN_MIN_ROWS && match_screen_supported(D);
+    gmax_norm = 0.f;
+    if (N > 0 && (screen || gal.store16)) build_screen_data();
+    q_cap = 0;  // partial scratch depends on `blocks`
+    qs.partial.reset();
+    bind_scratch();
+}
+
 // ------------------------------------------------------------------------------------------------------------- live gallery edits
 // Add and remove rows of the gallery the matcher is answering from (include/frt.h).  Every edit runs on the matcher's stream behind its
 // in-flight match stages (wait_idle), holds the object's mutex - which the pipeline takes to queue a match stage - from start to end, and
@@ -18,61 +234,41 @@ void edit_checks(frt_matcher *m, const char *what) {
     if (m->row_offset != 0) raise(FRT_ERR_INVALID, std::string(what) + ": a gallery with a row offset (a shard) is edited by reloading it");
 }
 
-// Room for `rows` rows: allocate + device copy + free (both copies exist until the copy has run).  Counts as one reallocation when there
-// were rows to carry over.
+// Room for `rows` rows: a new gallery value beside the live one + device copy + swap (both copies exist until the copy has run).  Counts
+// as one reallocation when there were rows to carry over.
 void grow(frt_matcher *m, int rows) {
-    if (rows <= m->cap_rows) return;
+    frt_matcher::Gallery &g = m->gal;
+    if (rows <= g.cap_rows) return;
     hipStream_t s = m->stream;
-    const int N = m->N, D = m->D, cap = round_up_tile(rows);
-    const size_t cap_tiles = (size_t)cap / 128, n_tiles = ((size_t)N + 127) / 128;
-    float *new32 = nullptr;
-    half_t *new16 = nullptr, *sh16 = nullptr;
-    uint8_t *sh8 = nullptr;
-    float *sh8s = nullptr;
-    const bool shadow = !m->store16 && m->screen && m->shadow_rows > 0;  // a valid shadow moves along; a stale one is dropped
-    if (m->labelled) m->ensure_label_room(cap, N, s);                    // the labels move with the rows
+    const int N = m->N, D = m->D;
+    const size_t n_tiles = ((size_t)N + 127) / 128;
+    const bool shadow = !g.store16 && m->screen && g.shadow_rows > 0;  // a valid shadow moves along; a stale one is dropped
+    frt_matcher::Gallery ng;
+    ng.store16 = g.store16;
+    ng.cap_rows = round_up_tile(rows);
+    if (m->labelled) m->ensure_label_room(ng.cap_rows, N, s);  // the labels move with the rows
     try {
-        if (m->store16) {
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&new16), gallery16_elems(cap, D) * sizeof(half_t)));
-            HIPCHK(hipMemsetAsync(new16 + n_tiles * 128 * D, 0, (cap_tiles - n_tiles) * 128 * D * sizeof(half_t), s));
-            if (N > 0) HIPCHK(hipMemcpyAsync(new16, m->d_g16, n_tiles * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+        if (g.store16) {
+            ng.rows16.reserve(gallery16_elems(ng.cap_rows, D));
+            if (N > 0) HIPCHK(hipMemcpyAsync(ng.rows16.get(), g.rows16.get(), n_tiles * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
         } else {
-            HIPCHK(hipMalloc(reinterpret_cast<void **>(&new32), (size_t)cap * D * sizeof(float)));
-            if (N > 0) HIPCHK(hipMemcpyAsync(new32, m->d_gallery, (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if (shadow && m->d_g8) {
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&sh8), gallery8_bytes(cap, D)));
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&sh8s), cap_tiles * 128 * sizeof(float)));
-                HIPCHK(hipMemsetAsync(sh8 + n_tiles * 128 * D, 0x80, (cap_tiles - n_tiles) * 128 * D, s));
-                HIPCHK(hipMemsetAsync(sh8s + n_tiles * 128, 0, (cap_tiles - n_tiles) * 128 * sizeof(float), s));
-                HIPCHK(hipMemcpyAsync(sh8, m->d_g8, n_tiles * 128 * D, hipMemcpyDeviceToDevice, s));
-                HIPCHK(hipMemcpyAsync(sh8s, m->d_g8_scale, n_tiles * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
+            ng.rows32.reserve((size_t)ng.cap_rows * D);
+            if (N > 0) HIPCHK(hipMemcpyAsync(ng.rows32.get(), g.rows32.get(), (size_t)N * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+            if (shadow) ng.alloc_shadow(D);
+            if (ng.g8) {
+                HIPCHK(hipMemcpyAsync(ng.g8.get(), g.g8.get(), n_tiles * 128 * D, hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(ng.g8_scale.get(), g.g8_scale.get(), n_tiles * 128 * sizeof(float), hipMemcpyDeviceToDevice, s));
             } else if (shadow) {
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&sh16), gallery16_elems(cap, D) * sizeof(half_t)));
-                HIPCHK(hipMemsetAsync(sh16 + n_tiles * 128 * D, 0, (cap_tiles - n_tiles) * 128 * D * sizeof(half_t), s));
-                HIPCHK(hipMemcpyAsync(sh16, m->d_g16, n_tiles * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+                HIPCHK(hipMemcpyAsync(ng.rows16.get(), g.rows16.get(), n_tiles * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
             }
         }
+        ng.pad_tiles(n_tiles, D, s);
         HIPCHK(hipStreamSynchronize(s));
     } catch (...) {
-        (void)hipStreamSynchronize(s);
-        for (void *p : {(void *)new32, (void *)new16, (void *)sh16, (void *)sh8, (void *)sh8s})
-            if (p) (void)hipFree(p);
+        (void)hipStreamSynchronize(s);  // before `ng` goes: a queued copy may still be writing into it
         throw;
     }
-    if (m->store16) {
-        if (m->d_g16) (void)hipFree(m->d_g16);
-        m->d_g16 = new16;
-    } else {
-        if (m->d_gallery) (void)hipFree(m->d_gallery);
-        m->d_gallery = new32;
-        for (void *p : {(void *)m->d_g8, (void *)m->d_g8_scale, (void *)m->d_g16})
-            if (p) (void)hipFree(p);
-        m->d_g8 = sh8;
-        m->d_g8_scale = sh8s;
-        m->d_g16 = sh16;
-        m->shadow_rows = shadow ? cap : 0;
-    }
-    m->cap_rows = cap;
+    std::swap(g, ng);  // the previous gallery is freed when `ng` leaves, with the new pointers in place
     if (N > 0) ++m->edit_stats[3];
 }
 
@@ -103,31 +299,26 @@ void add_rows(frt_matcher *m, const void *rows, int n, bool on_device, const int
     const int N = m->N, D = m->D, new_n = N + n;
     m->wait_idle(s);
     if (N == 0) m->drop_labels();  // (rows == 0: whatever labels the emptied gallery had are gone; grow then moves none)
-    if (new_n > m->cap_rows) grow(m, std::max(new_n, std::max((int)std::min((long)m->cap_rows * 3 / 2, (long)INT32_MAX - 128), m->reserve_rows)));
+    frt_matcher::Gallery &g = m->gal;
+    if (new_n > g.cap_rows) grow(m, std::max(new_n, std::max((int)std::min((long)g.cap_rows * 3 / 2, (long)INT32_MAX - 128), m->reserve_rows)));
     if (labelled_form) {
-        m->ensure_label_room(m->cap_rows, N, s);
-        HIPCHK(hipMemcpyAsync(m->d_labels + N, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));  // (complete before finish_edit returns)
-        m->h_labels.reserve((size_t)m->cap_rows);
+        m->ensure_label_room(g.cap_rows, N, s);
+        HIPCHK(hipMemcpyAsync(m->d_labels.get() + N, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));  // (complete before finish_edit returns)
+        m->h_labels.reserve((size_t)g.cap_rows);
     }
     const float *src32 = reinterpret_cast<const float *>(rows);  // the new rows as fp32 ON THE DEVICE (conversion source)
     const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (m->store16) {
+    if (g.store16) {
         if (!on_device) {
             const size_t need = (size_t)n * D;
-            if (need > m->edit_stage_floats) {
-                if (m->d_edit_stage) (void)hipFree(m->d_edit_stage);
-                m->d_edit_stage = nullptr;
-                m->edit_stage_floats = 0;
-                HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_edit_stage), need * sizeof(float)));
-                m->edit_stage_floats = need;
-            }
-            HIPCHK(hipMemcpyAsync(m->d_edit_stage, rows, need * sizeof(float), kind, s));
-            src32 = m->d_edit_stage;
+            m->d_edit_stage.reserve(need);
+            HIPCHK(hipMemcpyAsync(m->d_edit_stage.get(), rows, need * sizeof(float), kind, s));
+            src32 = m->d_edit_stage.get();
         }
-        launch_rows_to_half(src32, N, n, D, m->d_g16, s);
+        launch_rows_to_half(src32, N, n, D, g.rows16.get(), s);
     } else {
-        HIPCHK(hipMemcpyAsync(m->d_gallery + (size_t)N * D, rows, (size_t)n * D * sizeof(float), kind, s));
-        src32 = m->d_gallery + (size_t)N * D;
+        HIPCHK(hipMemcpyAsync(g.rows32.get() + (size_t)N * D, rows, (size_t)n * D * sizeof(float), kind, s));
+        src32 = g.rows32.get() + (size_t)N * D;
     }
     m->edit_stats[0] += n;
     const bool was_screen = m->screen;
@@ -141,18 +332,19 @@ void add_rows(frt_matcher *m, const void *rows, int n, bool on_device, const int
             m->screen = was_screen;
             throw;
         }
-        if (!m->store16) m->edit_stats[2] += new_n;
+        if (!g.store16) m->edit_stats[2] += new_n;
     } else if (m->screen) {  // tail update: only the new rows are converted into their places
-        if (m->store16) {
-            launch_rows_norm(m->d_g16, N, n, D, m->d_edit_bits + 1, s);
-            HIPCHK(hipMemsetAsync(m->d_edit_bits, 0, sizeof(int), s));
-        } else if (m->d_g8 && D == 512) {
-            launch_gallery_shadow8_rows(src32, N, n, m->d_g8, m->d_g8_scale, m->d_edit_bits, m->d_edit_bits + 1, s);
+        int *bits = m->d_edit_bits.get();
+        if (g.store16) {
+            launch_rows_norm(g.rows16.get(), N, n, D, bits + 1, s);
+            HIPCHK(hipMemsetAsync(bits, 0, sizeof(int), s));
+        } else if (g.g8 && D == 512) {
+            launch_gallery_shadow8_rows(src32, N, n, g.g8.get(), g.g8_scale.get(), bits, bits + 1, s);
             m->edit_stats[2] += n;
         } else {
-            launch_rows_to_half(src32, N, n, D, m->d_g16, s);
-            launch_rows_norm(m->d_gallery, N, n, D, m->d_edit_bits + 1, s);
-            HIPCHK(hipMemsetAsync(m->d_edit_bits, 0, sizeof(int), s));
+            launch_rows_to_half(src32, N, n, D, g.rows16.get(), s);
+            launch_rows_norm(g.rows32.get(), N, n, D, bits + 1, s);
+            HIPCHK(hipMemsetAsync(bits, 0, sizeof(int), s));
             m->edit_stats[2] += n;
         }
         HIPCHK(hipGetLastError());
@@ -177,57 +369,53 @@ void remove_rows(frt_matcher *m, const int32_t *idx, int n_idx) {
     const int N = m->N, D = m->D, nk = (int)keys.size(), new_n = N - nk, r0 = keys[0];
     const long tile0 = r0 >> 7, new_tiles = ((long)new_n + 127) / 128, old_tiles = ((long)N + 127) / 128;
     m->wait_idle(s);
-    if (!m->d_bounce) HIPCHK(hipMalloc(&m->d_bounce, frt_matcher::BOUNCE_BYTES));
-    if (keys.size() > m->keys_cap) {
-        if (m->d_keys) (void)hipFree(m->d_keys);
-        m->d_keys = nullptr;
-        m->keys_cap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_keys), keys.size() * sizeof(int)));
-        m->keys_cap = keys.size();
-    }
-    HIPCHK(hipMemcpyAsync(m->d_keys, keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice, s));
+    frt_matcher::Gallery &g = m->gal;
+    m->d_bounce.reserve(frt_matcher::BOUNCE_BYTES);
+    m->d_keys.reserve(keys.size());
+    const int *d_keys = m->d_keys.get();
+    HIPCHK(hipMemcpyAsync(m->d_keys.get(), keys.data(), keys.size() * sizeof(int), hipMemcpyHostToDevice, s));
     // the keys that fall into the destination rows [a, b): those in front of them all count, those behind them never do
     auto key_range = [&](long a, long b, int &lo, int &hi) {
         lo = (int)(std::lower_bound(keys.begin(), keys.end(), (int)a) - keys.begin());
         hi = (int)(std::upper_bound(keys.begin(), keys.end(), (int)(b - 1)) - keys.begin());
     };
-    if (m->store16) {
+    if (g.store16) {
         // whole destination tiles from the first hole's tile on; the gather also zeroes the padding of the new last tile
         const long chunk = std::max<long>(1, (long)(frt_matcher::BOUNCE_BYTES / ((size_t)128 * D * sizeof(half_t))));
-        half_t *bounce = reinterpret_cast<half_t *>(m->d_bounce);
+        half_t *bounce = reinterpret_cast<half_t *>(m->d_bounce.get());
         for (long t = tile0; t < new_tiles; t += chunk) {
             const long nt = std::min(chunk, new_tiles - t);
             int lo, hi;
             key_range(t * 128, (t + nt) * 128, lo, hi);
-            launch_gather_rows16(m->d_g16, D, t, nt, new_n, m->d_keys, lo, hi, bounce, s);
-            HIPCHK(hipMemcpyAsync(m->d_g16 + (size_t)t * 128 * D, bounce, (size_t)nt * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
+            launch_gather_rows16(g.rows16.get(), D, t, nt, new_n, d_keys, lo, hi, bounce, s);
+            HIPCHK(hipMemcpyAsync(g.rows16.get() + (size_t)t * 128 * D, bounce, (size_t)nt * 128 * D * sizeof(half_t), hipMemcpyDeviceToDevice, s));
         }
-        if (old_tiles > new_tiles) HIPCHK(hipMemsetAsync(m->d_g16 + (size_t)new_tiles * 128 * D, 0, (size_t)(old_tiles - new_tiles) * 128 * D * sizeof(half_t), s));
+        if (old_tiles > new_tiles) HIPCHK(hipMemsetAsync(g.rows16.get() + (size_t)new_tiles * 128 * D, 0, (size_t)(old_tiles - new_tiles) * 128 * D * sizeof(half_t), s));
     } else {
         const long chunk = std::max<long>(1, (long)(frt_matcher::BOUNCE_BYTES / ((size_t)D * sizeof(float))));
-        float *bounce = reinterpret_cast<float *>(m->d_bounce);
+        float *bounce = reinterpret_cast<float *>(m->d_bounce.get());
         for (long a = r0; a < new_n; a += chunk) {
             const long nr = std::min(chunk, (long)new_n - a);
             int lo, hi;
             key_range(a, a + nr, lo, hi);
-            launch_gather_rows(m->d_gallery, D, (int)a, (int)nr, m->d_keys, lo, hi, bounce, s);
-            HIPCHK(hipMemcpyAsync(m->d_gallery + (size_t)a * D, bounce, (size_t)nr * D * sizeof(float), hipMemcpyDeviceToDevice, s));
+            launch_gather_rows(g.rows32.get(), D, (int)a, (int)nr, d_keys, lo, hi, bounce, s);
+            HIPCHK(hipMemcpyAsync(g.rows32.get() + (size_t)a * D, bounce, (size_t)nr * D * sizeof(float), hipMemcpyDeviceToDevice, s));
         }
     }
     HIPCHK(hipGetLastError());
     if (new_n > r0) m->edit_stats[1] += new_n - r0;
     // Below the threshold a fresh matcher does not screen, and neither does this one (the shadow's allocation stays for the way back up).
     m->screen = new_n >= frt_matcher::SCREEN_MIN_ROWS && match_screen_supported(D);
-    if (m->screen && !m->store16) {
+    if (m->screen && !g.store16) {
         // the shadow from the first affected tile on, with the build's arithmetic; gerr / gmax_norm stay (maxima over a subset are no larger)
         const long first = tile0 * 128, n_re = std::max(0L, (long)new_n - first);
-        if (m->d_g8 && D == 512) {
-            HIPCHK(hipMemsetAsync(m->d_g8 + (size_t)first * D, 0x80, (size_t)(old_tiles - tile0) * 128 * D, s));
-            HIPCHK(hipMemsetAsync(m->d_g8_scale + first, 0, (size_t)(old_tiles - tile0) * 128 * sizeof(float), s));
-            launch_gallery_shadow8_rows(m->d_gallery + (size_t)first * D, (int)first, (int)n_re, m->d_g8, m->d_g8_scale, m->d_edit_bits, m->d_edit_bits + 1, s);
+        if (g.g8 && D == 512) {
+            HIPCHK(hipMemsetAsync(g.g8.get() + (size_t)first * D, 0x80, (size_t)(old_tiles - tile0) * 128 * D, s));
+            HIPCHK(hipMemsetAsync(g.g8_scale.get() + first, 0, (size_t)(old_tiles - tile0) * 128 * sizeof(float), s));
+            launch_gallery_shadow8_rows(g.rows32.get() + (size_t)first * D, (int)first, (int)n_re, g.g8.get(), g.g8_scale.get(), m->d_edit_bits.get(), m->d_edit_bits.get() + 1, s);
         } else {
-            HIPCHK(hipMemsetAsync(m->d_g16 + (size_t)first * D, 0, (size_t)(old_tiles - tile0) * 128 * D * sizeof(half_t), s));
-            launch_rows_to_half(m->d_gallery + (size_t)first * D, first, n_re, D, m->d_g16, s);
+            HIPCHK(hipMemsetAsync(g.rows16.get() + (size_t)first * D, 0, (size_t)(old_tiles - tile0) * 128 * D * sizeof(half_t), s));
+            launch_rows_to_half(g.rows32.get() + (size_t)first * D, first, n_re, D, g.rows16.get(), s);
         }
         HIPCHK(hipGetLastError());
         m->edit_stats[2] += n_re;
@@ -240,7 +428,7 @@ void remove_rows(frt_matcher *m, const int32_t *idx, int n_idx) {
         for (int j = r0; j < new_n; ++j) m->h_labels[(size_t)j] = m->h_labels[(size_t)frt_hole_source_row(keys.data(), 0, nk, j)];
         m->h_labels.resize((size_t)new_n);
         if (new_n > r0)
-            HIPCHK(hipMemcpyAsync(m->d_labels + r0, m->h_labels.data() + r0, (size_t)(new_n - r0) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpyAsync(m->d_labels.get() + r0, m->h_labels.data() + r0, (size_t)(new_n - r0) * sizeof(int32_t), hipMemcpyHostToDevice, s));
         // max_rows_per_label stays: the true maximum cannot have grown, and an over-estimate only makes fewer calls screen
     }
     finish_edit(m, new_n);
@@ -274,7 +462,7 @@ void build_templates(frt_matcher *src, frt_matcher *dst, int32_t *labels_out, in
             HIPCHK(hipMemcpyAsync(d_off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, s));
             HIPCHK(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, s));
             {
-                ProfScope ps(2, "template_build", (double)N * D * (src->store16 ? 2 : 4) + (double)I * D * 4, s);  // work = bytes moved
+                ProfScope ps(2, "template_build", (double)N * D * (src->gal.store16 ? 2 : 4) + (double)I * D * 4, s);  // work = bytes moved
                 src->with_rows([&](auto *g) { launch_template_build(g, D, d_off, d_rows, I, src->row_offset, d_t, d_sim, d_row, s); });
                 HIPCHK(hipGetLastError());
             }
@@ -312,24 +500,18 @@ hipStream_t upload_queries(frt_matcher *m, const float *embeds, int F) {
     hipStream_t s = m->stream;
     m->wait_idle(s);
     m->ensure_queries(F);
-    HIPCHK(hipMemcpyAsync(m->d_q, embeds, sizeof(float) * (size_t)F * m->D, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(m->qs.q.get(), embeds, sizeof(float) * (size_t)F * m->D, hipMemcpyHostToDevice, s));
     return s;
 }
 
 // the full similarity matrix of the F queries in d_q -> outputs [F][N] on the host (queued on s; grows d_full)
 void full_matrix_to_host(frt_matcher *m, int F, float *outputs, hipStream_t s) {
     const size_t need = (size_t)F * m->N;
-    if (need > m->full_cap) {
-        if (m->d_full) (void)hipFree(m->d_full);
-        m->d_full = nullptr;
-        m->full_cap = 0;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&m->d_full), need * sizeof(float)));
-        m->full_cap = need;
-    }
+    m->d_full.reserve(need);
     for (int f0 = 0; f0 < F; f0 += 128)
-        m->with_rows([&](auto *g) { launch_match_full(g, m->N, m->D, m->d_q + (size_t)f0 * m->D, std::min(128, F - f0), m->d_full + (size_t)f0 * m->N, s); });
+        m->with_rows([&](auto *g) { launch_match_full(g, m->N, m->D, m->qs.q.get() + (size_t)f0 * m->D, std::min(128, F - f0), m->d_full.get() + (size_t)f0 * m->N, s); });
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(outputs, m->d_full, need * sizeof(float), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(outputs, m->d_full.get(), need * sizeof(float), hipMemcpyDeviceToHost, s));
 }
 
 // upload the queries, search, download k columns per query: the top-1 search (lists == false, k == 1) or the top-k lists.
@@ -345,14 +527,47 @@ void search_to_host(frt_matcher *m, const float *embeds, int F, bool lists, int 
     if (label_out) check_labelled(m);
     hipStream_t s = upload_queries(m, embeds, F);
     if (matrix_out) full_matrix_to_host(m, F, matrix_out, s);
+    const float *q = m->qs.q.get();
+    int32_t *idx = m->qs.idx.get();
+    float *sim = m->qs.sim.get();
     if (label_out) {
-        m->topk_labels_dev(m->d_q, F, k, m->d_lab, m->d_idx, m->d_sim, s);
-        HIPCHK(hipMemcpyAsync(label_out, m->d_lab, sizeof(int32_t) * (size_t)F * k, hipMemcpyDeviceToHost, s));
-    } else if (lists) m->topk_dev(m->d_q, F, k, m->d_idx, m->d_sim, s);
-    else m->top1_dev(m->d_q, F, m->d_idx, m->d_sim, s);
-    HIPCHK(hipMemcpyAsync(idx_out, m->d_idx, sizeof(int32_t) * (size_t)F * k, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(sim_out, m->d_sim, sizeof(float) * (size_t)F * k, hipMemcpyDeviceToHost, s));
+        m->topk_labels_dev(q, F, k, m->qs.lab.get(), idx, sim, s);
+        HIPCHK(hipMemcpyAsync(label_out, m->qs.lab.get(), sizeof(int32_t) * (size_t)F * k, hipMemcpyDeviceToHost, s));
+    } else if (lists) m->topk_dev(q, F, k, idx, sim, s);
+    else m->top1_dev(q, F, idx, sim, s);
+    HIPCHK(hipMemcpyAsync(idx_out, idx, sizeof(int32_t) * (size_t)F * k, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(sim_out, sim, sizeof(float) * (size_t)F * k, hipMemcpyDeviceToHost, s));
     sync_stream_spinning(s);
+}
+
+// What the three *_dev searches share (the caller holds m->mu): the scratch behind in-flight match stages on the caller's stream, fp16
+// queries widened exactly into the query scratch, search(fp32 queries, stream), and the scratch marked in use until the search has run
+template <typename Fn>
+void search_dev(frt_matcher *m, const void *embeds_dev, int embeds_fp16, int F, void *hip_stream, Fn &&search) {
+    if (m->N <= 0 || F <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
+    use_device(m->device);
+    hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+    m->wait_idle(s);
+    m->ensure_queries(F);
+    const float *q = reinterpret_cast<const float *>(embeds_dev);
+    if (embeds_fp16) {
+        launch_half_to_float(reinterpret_cast<const half_t *>(embeds_dev), (long)F * m->D, m->qs.q.get(), s);
+        q = m->qs.q.get();
+    }
+    search(q, s);
+    HIPCHK(hipEventRecord(m->ev_busy, s));
+    m->busy = true;
+}
+
+// the shell of the gallery entry points: the object's lock and device around fn
+template <typename Fn>
+int with_gallery(frt_matcher *m, Fn &&fn) {
+    return guarded([&] {
+        if (!m) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(m->mu);
+        use_device(m->device);
+        fn();
+    });
 }
 
 }  // namespace
@@ -395,11 +610,7 @@ void frt_matcher_destroy(frt_matcher *m) {
         (void)hipStreamDestroy(m->stream);
     }
     if (m->ev_busy) (void)hipEventDestroy(m->ev_busy);
-    for (void *p : {(void *)m->d_gallery, (void *)m->d_q, (void *)m->d_sim, (void *)m->d_idx, (void *)m->d_partial, (void *)m->d_full, (void *)m->d_g16, (void *)m->d_kth, (void *)m->d_labels, (void *)m->d_lab,
-                    (void *)m->d_g8, (void *)m->d_g8_scale, (void *)m->d_edit_bits, (void *)m->d_edit_stage, m->d_bounce, (void *)m->d_keys})
-        if (p) (void)hipFree(p);
-    m->free_screen_scratch();
-    delete m;
+    delete m;  // every buffer frees itself, on the device set above
 }
 
 static void check_gallery_shape(int num_row, int num_col) {
@@ -433,8 +644,8 @@ size_t frt_matcher_scan_bytes(frt_matcher *m) {
     if (!m) return 0;
     std::lock_guard<std::mutex> lk(m->mu);
     const size_t n = (size_t)m->N, d = (size_t)m->D;
-    if (m->screen && m->screen_on) return (m->d_g8 ? 1 : 2) * n * d;   // the coarse scan reads the shadow copy once per call
-    return (m->store16 ? 2 : 4) * n * d;
+    if (m->screen && m->screen_on) return (m->gal.g8 ? 1 : 2) * n * d;   // the coarse scan reads the shadow copy once per call
+    return (m->gal.store16 ? 2 : 4) * n * d;
 }
 
 int frt_matcher_init(frt_matcher *m, const float *gallery, int num_row, int num_col) {
@@ -467,19 +678,13 @@ int frt_matcher_gallery_begin(frt_matcher *m, int row_capacity, int num_col) {
 }
 
 int frt_matcher_gallery_append(frt_matcher *m, const void *rows, int n_rows) {
-    return guarded([&] {
-        if (!m) raise(FRT_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        use_device(m->device);
+    return with_gallery(m, [&] {
         m->load_append(reinterpret_cast<const float *>(rows), n_rows);
     });
 }
 
 int frt_matcher_gallery_commit(frt_matcher *m) {
-    return guarded([&] {
-        if (!m) raise(FRT_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        use_device(m->device);
+    return with_gallery(m, [&] {
         try {
             m->load_commit();
         } catch (...) {
@@ -496,7 +701,7 @@ int frt_matcher_gallery_reserve(frt_matcher *m, int row_capacity) {
         use_device(m->device);
         edit_checks(m, "gallery_reserve");
         m->reserve_rows = std::max(m->reserve_rows, row_capacity);
-        if (m->N > 0 && row_capacity > m->cap_rows) {  // a live gallery moves now; an empty matcher allocates with its first rows
+        if (m->N > 0 && row_capacity > m->gal.cap_rows) {  // a live gallery moves now; an empty matcher allocates with its first rows
             m->wait_idle(m->stream);
             grow(m, row_capacity);
             finish_edit(m, m->N);
@@ -505,37 +710,25 @@ int frt_matcher_gallery_reserve(frt_matcher *m, int row_capacity) {
 }
 
 int frt_matcher_gallery_add(frt_matcher *m, const float *rows, int n_rows) {
-    return guarded([&] {
-        if (!m) raise(FRT_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        use_device(m->device);
+    return with_gallery(m, [&] {
         add_rows(m, rows, n_rows, false);
     });
 }
 
 int frt_matcher_gallery_add_dev(frt_matcher *m, const void *rows_dev, int n_rows) {
-    return guarded([&] {
-        if (!m) raise(FRT_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        use_device(m->device);
+    return with_gallery(m, [&] {
         add_rows(m, rows_dev, n_rows, true);
     });
 }
 
 int frt_matcher_gallery_add_labeled(frt_matcher *m, const float *rows, const int32_t *labels, int n_rows) {
-    return guarded([&] {
-        if (!m) raise(FRT_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        use_device(m->device);
+    return with_gallery(m, [&] {
         add_rows(m, rows, n_rows, false, labels, true);
     });
 }
 
 int frt_matcher_gallery_add_labeled_dev(frt_matcher *m, const void *rows_dev, const int32_t *labels, int n_rows) {
-    return guarded([&] {
-        if (!m) raise(FRT_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        use_device(m->device);
+    return with_gallery(m, [&] {
         add_rows(m, rows_dev, n_rows, true, labels, true);
     });
 }
@@ -557,12 +750,12 @@ int frt_matcher_set_labels(frt_matcher *m, const int32_t *labels, int n) {
         m->wait_idle(s);  // a match stage in flight may be reading the old labels
         HIPCHK(hipStreamSynchronize(s));
         if (m->busy) HIPCHK(hipEventSynchronize(m->ev_busy));
-        m->ensure_label_room(std::max(m->cap_rows, n), 0, s);
-        HIPCHK(hipMemcpyAsync(m->d_labels, labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        m->ensure_label_room(std::max(m->gal.cap_rows, n), 0, s);
+        HIPCHK(hipMemcpyAsync(m->d_labels.get(), labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
         HIPCHK(hipStreamSynchronize(s));
         m->drop_labels();
         m->labelled = true;
-        m->h_labels.reserve((size_t)std::max(m->cap_rows, n));
+        m->h_labels.reserve((size_t)std::max(m->gal.cap_rows, n));
         m->h_labels.assign(labels, labels + n);
         m->count_labels(labels, n);
         ++m->generation;
@@ -594,10 +787,7 @@ int frt_matcher_build_templates(frt_matcher *src, frt_matcher *dst, int32_t *lab
 }
 
 int frt_matcher_gallery_remove(frt_matcher *m, const int32_t *idx, int n_idx) {
-    return guarded([&] {
-        if (!m) raise(FRT_ERR_INVALID, "null argument");
-        std::lock_guard<std::mutex> lk(m->mu);
-        use_device(m->device);
+    return with_gallery(m, [&] {
         remove_rows(m, idx, n_idx);
     });
 }
@@ -643,12 +833,12 @@ int frt_pinned_alloc(size_t bytes, int device, void **out) {
         if (!out) raise(FRT_ERR_INVALID, "null argument");
         *out = nullptr;
         if (device >= 0) use_device(device);
-        HIPCHK(hipHostMalloc(out, bytes ? bytes : 1, hipHostMallocDefault));
+        *out = PinnedMem::alloc(bytes ? bytes : 1);
     });
 }
 
 void frt_pinned_free(void *p) {
-    if (p) (void)hipHostFree(p);
+    if (p) PinnedMem::free(p);
 }
 
 int frt_matcher_top1(frt_matcher *m, const float *embeds, int embed_count, int32_t *idx_out, float *sim_out) {
@@ -663,14 +853,9 @@ int frt_matcher_top1_dev(frt_matcher *m, const void *embeds_dev, int embed_count
     return guarded([&] {
         if (!m || !embeds_dev || !idx_dev || !sim_dev) raise(FRT_ERR_INVALID, "top1_dev: null argument");
         std::lock_guard<std::mutex> lk(m->mu);
-        if (m->N <= 0 || embed_count <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
-        use_device(m->device);
-        hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-        m->wait_idle(s);
-        m->ensure_queries(embed_count);
-        m->top1_dev(reinterpret_cast<const float *>(embeds_dev), embed_count, reinterpret_cast<int32_t *>(idx_dev), reinterpret_cast<float *>(sim_dev), s);
-        HIPCHK(hipEventRecord(m->ev_busy, s));  // the scratch stays in use until this call has run
-        m->busy = true;
+        search_dev(m, embeds_dev, 0, embed_count, hip_stream, [&](const float *q, hipStream_t s) {
+            m->top1_dev(q, embed_count, reinterpret_cast<int32_t *>(idx_dev), reinterpret_cast<float *>(sim_dev), s);
+        });
     });
 }
 
@@ -707,19 +892,9 @@ int frt_matcher_topk_dev(frt_matcher *m, const void *embeds_dev, int embeds_fp16
         if (!m || !embeds_dev || !idx_dev || !sim_dev) raise(FRT_ERR_INVALID, "topk_dev: null argument");
         check_k(k);
         std::lock_guard<std::mutex> lk(m->mu);
-        if (m->N <= 0 || embed_count <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
-        use_device(m->device);
-        hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-        m->wait_idle(s);
-        m->ensure_queries(embed_count);
-        const float *q = reinterpret_cast<const float *>(embeds_dev);
-        if (embeds_fp16) {  // exact widening into the query scratch
-            launch_half_to_float(reinterpret_cast<const half_t *>(embeds_dev), (long)embed_count * m->D, m->d_q, s);
-            q = m->d_q;
-        }
-        m->topk_dev(q, embed_count, k, reinterpret_cast<int32_t *>(idx_dev), reinterpret_cast<float *>(sim_dev), s);
-        HIPCHK(hipEventRecord(m->ev_busy, s));  // the scratch stays in use until this call has run
-        m->busy = true;
+        search_dev(m, embeds_dev, embeds_fp16, embed_count, hip_stream, [&](const float *q, hipStream_t s) {
+            m->topk_dev(q, embed_count, k, reinterpret_cast<int32_t *>(idx_dev), reinterpret_cast<float *>(sim_dev), s);
+        });
     });
 }
 
@@ -738,19 +913,9 @@ int frt_matcher_topk_labels_dev(frt_matcher *m, const void *embeds_dev, int embe
         check_k(k);
         std::lock_guard<std::mutex> lk(m->mu);
         check_labelled(m);
-        if (m->N <= 0 || embed_count <= 0) raise(FRT_ERR_EMPTY, "Feature matching: No faces in database or no faces found");
-        use_device(m->device);
-        hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
-        m->wait_idle(s);
-        m->ensure_queries(embed_count);
-        const float *q = reinterpret_cast<const float *>(embeds_dev);
-        if (embeds_fp16) {  // exact widening into the query scratch
-            launch_half_to_float(reinterpret_cast<const half_t *>(embeds_dev), (long)embed_count * m->D, m->d_q, s);
-            q = m->d_q;
-        }
-        m->topk_labels_dev(q, embed_count, k, reinterpret_cast<int32_t *>(label_dev), reinterpret_cast<int32_t *>(idx_dev), reinterpret_cast<float *>(sim_dev), s);
-        HIPCHK(hipEventRecord(m->ev_busy, s));  // the scratch stays in use until this call has run
-        m->busy = true;
+        search_dev(m, embeds_dev, embeds_fp16, embed_count, hip_stream, [&](const float *q, hipStream_t s) {
+            m->topk_labels_dev(q, embed_count, k, reinterpret_cast<int32_t *>(label_dev), reinterpret_cast<int32_t *>(idx_dev), reinterpret_cast<float *>(sim_dev), s);
+        });
     });
 }
 

@@ -191,20 +191,23 @@ struct frt_pipeline {
         static constexpr int NSET = 2;
         bool built = false;                                  // the fixed-size part below exists, all of it
         hipStream_t ingest = nullptr;                        // upload + resize kernel of a chunk
-        uint8_t *h_pack[NSET] = {}, *d_pack[NSET] = {};      // pinned / device: [max_frames] descriptors, then the chunk's photos, row strides removed
-        size_t cap[NSET] = {};                               // photo bytes either of a pair holds (they grow together)
-        hipEvent_t uploaded[NSET] = {};                      // h_pack[b] may be rewritten
+        PackPair pack[NSET];                                 // pinned / device: [max_frames] descriptors, then the chunk's photos, row strides removed
+        hipEvent_t uploaded[NSET] = {};                      // pack[b].h may be rewritten
         hipEvent_t ready[NSET] = {};                         // d_frames[b] holds the chunk's resized frames (Request::after)
         hipEvent_t done[NSET] = {};                          // the chunk's stages and downloads are complete on the pipeline stream
-        uint8_t *d_frames[NSET] = {};                        // [max_frames][frame_h][frame_w][3]
-        frt_face_result *d_results[NSET] = {}, *h_results[NSET] = {};  // [F_cap] device / pinned
-        float *d_embeds[NSET] = {}, *h_embeds[NSET] = {};              // [F_cap][512]
-        uint8_t *d_crops[NSET] = {}, *h_crops[NSET] = {};              // [F_cap][112][112][3] (first call that asks for crops)
-        // one enrolment call: the dense rows of the accepted photos, status word and face per photo, the row count
-        float *d_rows = nullptr;
-        int32_t *d_status = nullptr, *h_status = nullptr, *d_count = nullptr, *h_count = nullptr;  // (h_*: pinned)
-        frt_face_result *d_face = nullptr, *h_face = nullptr;
-        size_t enrol_cap = 0;
+        DevBuf<uint8_t> d_frames[NSET];                      // [max_frames][frame_h][frame_w][3]
+        DevBuf<frt_face_result> d_results[NSET];             // [F_cap]; h_*: the same, pinned
+        PinnedBuf<frt_face_result> h_results[NSET];
+        DevBuf<float> d_embeds[NSET];                        // [F_cap][512]
+        PinnedBuf<float> h_embeds[NSET];
+        DevBuf<uint8_t> d_crops[NSET];                       // [F_cap][112][112][3] (first call that asks for crops)
+        PinnedBuf<uint8_t> h_crops[NSET];
+        // one enrolment call (grown to its photo count): the dense rows of the accepted photos, status word and face per photo, the row count
+        DevBuf<float> d_rows;
+        DevBuf<int32_t> d_status, d_count;
+        PinnedBuf<int32_t> h_status, h_count;
+        DevBuf<frt_face_result> d_face;
+        PinnedBuf<frt_face_result> h_face;
         hipEvent_t finished = nullptr;
     } images;
     std::mutex images_mu;

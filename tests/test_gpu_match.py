@@ -453,3 +453,85 @@ def test_smallest_screened_gallery_one_tile_per_coarse_workgroup(frt, smallest_s
 def test_screened_fp16_shadow_with_a_ragged_last_tile(frt):
     g, q, dup = _ragged_fp16_shadow_case()
     _check_screened_against_exact_scan(frt, g, q, (3,), dup)
+
+
+def test_one_matcher_reloaded_across_storage_width_and_size(frt, synth):
+    """ONE matcher through reloads and edits that change storage mode, width, size and the side of the screening threshold: whatever gallery it
+    holds is allocated, swapped in, padded and freed by the same few functions, and after every stage its top-1 and top-3 answers for 130
+    queries (two 128-query tiles) equal a FRESH matcher's on the same rows bit for bit, as do the bytes a call scans.  Every gallery has the
+    duplicates (127, 128) across the first tile edge and (126, last row) into the tail tile, queried without noise: the first index wins."""
+    T = 32768  # frt_matcher::SCREEN_MIN_ROWS
+    a = frt.MatMul(0)
+
+    def planted(g):
+        g[128] = g[127]
+        g[-1] = g[126]
+        return g
+
+    def check(rows, fp16, labels, scan_bytes, stage):
+        n = len(rows)
+        r = np.random.Generator(np.random.PCG64(n + stage))
+        q = np.concatenate([synth.make_queries(rows, [127, 128, 126, n - 1, 0], noise=0.0), synth.make_queries(rows, r.integers(0, n, 100), noise=0.02),
+                            r.standard_normal((25, rows.shape[1])).astype(np.float32)])
+        assert len(q) == 130
+        fresh = frt.MatMul(0)
+        fresh.setStorage(fp16)
+        fresh.init(rows)
+        if labels is not None:
+            fresh.set_labels(labels)
+        assert a.m == n and a.scanBytes() == fresh.scanBytes() == scan_bytes, (stage, a.scanBytes(), fresh.scanBytes(), scan_bytes)
+        for got, want in zip(a.top1(q) + a.topk(q, 3), fresh.top1(q) + fresh.topk(q, 3)):
+            assert np.array_equal(got, want), stage
+        assert a.top1(q)[0][:4].tolist() == [127, 127, 126, 126], stage
+        if labels is not None:
+            assert a.labels_info() == fresh.labels_info()
+            for got, want in zip(a.topk_labels(q, 3), fresh.topk_labels(q, 3)):
+                assert np.array_equal(got, want), stage
+        fresh.close()
+
+    # 1. fp32, 512 columns, just over the threshold: int8 shadow
+    g = planted(synth.make_gallery(T + 128, seed=21))
+    a.init(g)
+    check(g, False, None, len(g) * 512, 1)
+    # 2. fp16 storage, 128 columns: the rows are their own shadow, the int8 shadow is gone
+    g = planted(synth.make_gallery(40000, d=128, seed=22))
+    a.setStorage(True)
+    a.init(g)
+    check(g, True, None, len(g) * 128 * 2, 2)
+    # 3. fp32 again and small: unscreened (the scratch of the larger gallery is still allocated when the search starts)
+    g = planted(synth.make_gallery(1000, d=128, seed=23))
+    a.setStorage(False)
+    a.init(g)
+    check(g, False, None, len(g) * 128 * 4, 3)
+    # 4. a commit of zero rows, then a labelled add.  (Stages 4 to 6 hold the leading rows of `rows`, planted for each of their sizes.)
+    pool = synth.make_gallery(34000, d=128, seed=24)
+    lab = (np.arange(34000) // 3).astype(np.int32)
+    rows = pool[:33000].copy()
+    rows[128] = rows[127]
+    rows[199] = rows[32999] = rows[126]
+    a.galleryBegin(0, 128)
+    a.galleryCommit()
+    assert a.m == 0
+    assert a.gallery_add_labeled(rows[:200], lab[:200]) == 0
+    check(rows[:200], False, lab[:200], 200 * 128 * 4, 4)
+    assert a.editStats()["reallocations"] == 0  # (no rows to carry over)
+    # 5. reserve - the one move of live rows - then adds across the threshold: an add builds the fp16 shadow of an fp32 gallery
+    a.galleryReserve(40000)
+    for lo, hi in ((200, 20000), (20000, T - 1), (T - 1, 33000)):
+        assert a.gallery_add_labeled(rows[lo:hi], lab[lo:hi]) == lo
+    check(rows, False, lab[:33000], 33000 * 128 * 2, 5)
+    assert a.editStats()["reallocations"] == 1
+    # 6. a removal takes it back below the threshold (the shadow's allocation stays)
+    gone = np.concatenate([np.arange(300, 1200), np.arange(32900, 32999), [5000]])
+    keep = np.setdiff1d(np.arange(33000), gone)
+    a.galleryRemove(gone)
+    g, l6 = rows[keep], lab[:33000][keep]
+    assert len(g) == 32000
+    check(g, False, l6, 32000 * 128 * 4, 6)
+    # 7. and an add lifts it above again: the shadow is rebuilt inside the allocation it has
+    more = pool[33000:].copy()
+    more[-1] = g[126]
+    assert a.gallery_add_labeled(more, lab[33000:]) == 32000
+    check(np.concatenate([g, more]), False, np.concatenate([l6, lab[33000:]]), 33000 * 128 * 2, 7)
+    assert a.editStats()["reallocations"] == 1
+    a.close()

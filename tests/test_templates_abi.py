@@ -47,6 +47,16 @@ def test_grouping_header_against_brute_force_under_sanitizers(tmp_path):
     assert out.returncode == 0 and out.stdout.startswith("template groups ok"), (out.returncode, out.stdout, out.stderr)
 
 
+def test_owned_buffer_type_under_sanitizers(tmp_path):
+    """tests/cpp/owned_buf_test.cpp: the buffer type behind every resizable device / pinned allocation (csrc/frt_owned.hpp) on a counting
+    malloc policy, as a stand-alone host program with ASan + UBSan (and ASan's leak check at exit)."""
+    exe = str(tmp_path / "owned_buf_test")
+    subprocess.check_call(["/opt/rocm/lib/llvm/bin/clang++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", CSRC,
+                           os.path.join(ROOT, "tests", "cpp", "owned_buf_test.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0 and out.stdout.startswith("owned buf ok"), (out.returncode, out.stdout, out.stderr)
+
+
 def test_template_demo_is_well_formed_cpp11(tmp_path):
     """tests/cpp/template_demo.cpp (run on the GPU by tests/test_gpu_templates.py) under -Wall -Wextra -Werror."""
     subprocess.check_call(["g++", "-std=c++11", "-O1", "-Wall", "-Wextra", "-Werror", "-I", os.path.join(ROOT, "include"), "-c",
