@@ -103,6 +103,8 @@ ABI = {
     "frt_merge_topk_labels": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_merge_topk_labels_dev": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_matcher_build_templates": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frt_matcher_cluster": (_i, [_vp, _f, _vp, _i, _vp]),
+    "frt_matcher_cluster_dev": (_i, [_vp, _f, _vp, _vp, _vp]),
     "frt_embeds_to_half_dev": (_i, [_vp, _sz, _vp, _vp]),
     "frt_comm_get_unique_id": (_i, [_vp]),
     "frt_comm_set_bootstrap_timeout": (ctypes.c_double, [ctypes.c_double]),
@@ -405,6 +407,23 @@ class MatMul:
             dst.k = self.k
             dst._edited()
         return (labels, n_rows, min_sim, min_row) + ((t,) if want_templates else ())
+
+    CLUSTER_STATS = ("clusters", "edges", "screened_chunks", "dense_chunks")
+
+    def cluster(self, threshold, install=False):
+        """Single-linkage clustering of the gallery at a similarity threshold (frt_matcher_cluster): rows i < j are joined iff the matcher's
+        own exact similarity of the two stored rows is ``>= threshold``.  Returns ``(labels, stats)``: ``labels[i]`` (int32 ``[m]``) is the
+        smallest row of i's connected component, ``stats`` a dict of ``CLUSTER_STATS``.  ``install=True`` makes the labels the matcher's own,
+        as ``set_labels(labels)`` would: ``topk_labels`` and ``buildTemplates`` then work at once."""
+        labels = np.empty(int(lib.frt_matcher_num_rows(self._h)), np.int32)
+        stats = (ctypes.c_longlong * 4)()
+        _check(lib.frt_matcher_cluster(self._h, float(threshold), _ptr(labels) if labels.size else None, 1 if install else 0, stats))
+        return labels, dict(zip(self.CLUSTER_STATS, (int(v) for v in stats)))
+
+    def cluster_dev(self, threshold, labels_ptr, stats_ptr=None, hip_stream=None):
+        """Raw device addresses: labels int32 [m], stats 4 x int64 (or ``None``); complete when ``hip_stream`` has run."""
+        _check(lib.frt_matcher_cluster_dev(self._h, float(threshold), _vp(labels_ptr) if labels_ptr else None, _vp(stats_ptr) if stats_ptr else None,
+                                           _vp(hip_stream) if hip_stream else None))
 
     def setRowOffset(self, row_offset):
         """Sharded gallery: local row 0 is global row ``row_offset`` (top-1 indices become global)."""

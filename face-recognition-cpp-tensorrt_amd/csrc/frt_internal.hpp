@@ -182,6 +182,16 @@ inline hipEvent_t prof_event() {
     (void)hipEventCreate(&e);
     return e;
 }
+// a caller about to open `brackets` brackets of `kind` in a row (frt_matcher_cluster: three per chunk) fills the pool first, for the same reason
+inline void prof_reserve(int kind, size_t brackets) {
+    std::lock_guard<std::mutex> lk(g_prof_mu);
+    if (g_prof_kind != kind) return;
+    while (g_prof_pool.size() < 2 * brackets) {
+        hipEvent_t e = nullptr;
+        if (hipEventCreate(&e) != hipSuccess) break;
+        g_prof_pool.push_back(e);
+    }
+}
 
 struct ProfScope {
     bool on = false;

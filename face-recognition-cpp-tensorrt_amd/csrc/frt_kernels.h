@@ -50,6 +50,12 @@ void launch_match_full(const GT *rows, int N, int D, const float *queries, int F
 constexpr int FRT_MATCH_COARSE_WG = 256;  // persistent workgroups of the coarse scan (one per CU), each with at least one 128-row tile
 constexpr int FRT_MATCH_SEL_SUB = 64;     // sub-lists of the candidate pair list (16 tile segments x 4 query classes), one counter each
 constexpr int FRT_MATCH_CTL_WORDS = 32 + FRT_MATCH_SEL_SUB * 32;
+struct MatchPair {                        // one entry of the candidate pair list
+    int q, tile;  // tile: bits 0 - 27 the 128-row tile, bits 28 - 31 which of its four 32-row blocks are inside the band
+};
+constexpr int FRT_MATCH_PAIR_TILE_MASK = (1 << 28) - 1;
+// ctl words: [FRT_MATCH_CTL_OVERFLOW] the pair list overflowed, [FRT_MATCH_CTL_SEG0 + s * FRT_MATCH_CTL_STRIDE] number of pairs in sub-list s
+constexpr int FRT_MATCH_CTL_OVERFLOW = 1, FRT_MATCH_CTL_SEG0 = 32, FRT_MATCH_CTL_STRIDE = 32;
 struct ScreenScratch {
     float *tilemax;               // [F][tiles][4] coarse maxima: one per 32-row block of a 128-row tile
     float *wgmax;                 // [FRT_MATCH_COARSE_WG][F] maxima of a workgroup's coarse entries
@@ -77,6 +83,12 @@ void launch_match_topk(const float *gallery, const half_t *g16, int N, int D, co
                        const ScreenScratch &w, float *kth_scratch, MatchPartial *partial, int partial_blocks, int32_t *idx_out, float *sim_out,
                        int row_offset, hipStream_t s);
 int match_topk_max();
+// The two front stages of the screened search on their own, for the clustering chunks: the coarse scan (true: it read the int8 shadow), and
+// behind it the pairs whose 32-row block can hold a row with S >= threshold (absolute: not relative to the query's best entry), tiles from
+// tile_min on.  Same scratch and same need of FRT_MATCH_COARSE_WG tiles as the screened search.
+bool launch_match_coarse(const half_t *g16, int N, int D, const float *queries, int F, const ScreenScratch &w, hipStream_t s);
+void launch_match_select_threshold(int N, int D, const float *queries, int F, float threshold, int tile_min, float gmax_norm, const ScreenScratch &w, bool i8,
+                                   hipStream_t s);
 // exact top-k over identities [F][k] (labels [N]: one int32 >= 0 per local row): kth_count > 0 -> one screened search whose selection hangs on
 // the kth_count-th largest coarse entry (<= match_topk_max()), then k label-excluded re-rank passes; 0 -> k label-excluded exact scans
 void launch_match_topk_labels(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, int k, int kth_count, float gmax_norm,
@@ -114,6 +126,24 @@ void launch_rows_norm(const GT *G, int row0, int n_rows, int D, int *max_norm2_b
 void launch_gallery_shadow8_rows(const float *rows, int row0, int n_rows, uint8_t *g8, float *scale, int *max_err2_bits, int *max_norm2_bits, hipStream_t s);
 void launch_gather_rows(const float *G, int D, int a, int n_rows, const int *keys, int klo, int khi, float *bounce, hipStream_t s);
 void launch_gather_rows16(const half_t *G, int D, long tile0, long n_tiles, int n_new, const int *keys, int klo, int khi, half_t *bounce, hipStream_t s);
+
+// ---------------------------------------------------------------- clustering (kernels_cluster.hip; frt_matcher_cluster)
+// Single linkage at a similarity threshold t on a union-find forest parent[N] (parent[x] <= x: a component's root is its smallest row).
+// stats: 4 x int64 on the device = clusters, joined pairs, screened chunks, dense chunks.
+void launch_cluster_init(int32_t *parent, int N, long long *stats, hipStream_t s);
+// n stored rows from row0 on -> fp32 row-major queries [n][D] (fp16 storage: the fragment-ordered rows widened exactly)
+void launch_cluster_queries(const half_t *rows, int row0, int n, int D, float *out, hipStream_t s);
+// screened chunk: the pairs launch_match_select_threshold listed for queries = rows q_row0 .. of the gallery; every live row j > i with
+// S(i, j) >= t is united with i.  rows / N: the whole gallery; the list's tile numbers count from tile_origin (where the coarse scan and the
+// selection of this chunk began).  Does nothing when the pair list overflowed; chunk_overflow receives that flag.
+template <typename GT>
+void launch_cluster_rerank_union(const GT *rows, int N, int D, const float *queries, int q_row0, int tile_origin, const ScreenScratch &w, float t,
+                                 int32_t *parent, long long *stats, int *chunk_overflow, hipStream_t s);
+// dense chunk: full [F][N] = the similarities of queries = rows q_row0 .. q_row0 + F - 1 (match_kernel's out_full); same joins
+void launch_cluster_dense_union(const float *full, int F, int N, int q_row0, float t, int32_t *parent, long long *stats, hipStream_t s);
+// label[i] = root(i); stats[0] = number of roots, stats[2] / stats[3] = the host's chunk counts
+void launch_cluster_flatten(const int32_t *parent, int N, int32_t *labels, long long *stats, long long screened_chunks, long long dense_chunks,
+                            hipStream_t s);
 
 // ---------------------------------------------------------------- template gallery (kernels_templates.hip)
 // One template per identity (include/frt.h, frt_matcher_build_templates).  rows: the stored gallery (fp32 row-major or fragment-ordered fp16);

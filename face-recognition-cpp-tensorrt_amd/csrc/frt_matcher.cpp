@@ -559,6 +559,127 @@ void search_dev(frt_matcher *m, const void *embeds_dev, int embeds_fp16, int F, 
     m->busy = true;
 }
 
+// frt_matcher_set_labels with m->mu held by the caller
+void set_labels(frt_matcher *m, const int32_t *labels, int n) {
+    if (n == 0) {  // clear
+        if (m->labelled) ++m->generation;
+        m->drop_labels();
+        return;
+    }
+    if (n != m->N) raise(FRT_ERR_INVALID, "set_labels: one label per gallery row");
+    for (int i = 0; i < n; ++i)
+        if (labels[i] < 0) raise(FRT_ERR_INVALID, "set_labels: negative label");
+    use_device(m->device);
+    hipStream_t s = m->stream;
+    m->wait_idle(s);  // a match stage in flight may be reading the old labels
+    HIPCHK(hipStreamSynchronize(s));
+    if (m->busy) HIPCHK(hipEventSynchronize(m->ev_busy));
+    m->ensure_label_room(std::max(m->gal.cap_rows, n), 0, s);
+    HIPCHK(hipMemcpyAsync(m->d_labels.get(), labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    m->drop_labels();
+    m->labelled = true;
+    m->h_labels.reserve((size_t)std::max(m->gal.cap_rows, n));
+    m->h_labels.assign(labels, labels + n);
+    m->count_labels(labels, n);
+    ++m->generation;
+}
+
+// ------------------------------------------------------------------------------------------------------------- clustering
+// frt_matcher_cluster / _cluster_dev (include/frt.h) with m->mu held and N > 0: labels_dev [N] and stats_dev [4] are complete
+// on `s` when the stream has run.  The gallery is walked in chunks of 128 stored rows used as queries; a chunk goes through the screen
+// (coarse scan, absolute-threshold selection from the chunk's own tile on, edge re-rank + union) or through the dense pass (the chunk's
+// full similarity matrix, at most DENSE_BYTES of it at a time, then the union over it).  A screened chunk whose pair list overflowed
+// joined nothing; its flag lands in d_cluster_ovf, which the host reads once behind the walk to send those chunks through the dense pass.
+// frt_profile_enable(3) brackets every chunk's stages (cluster_coarse / _select / _rerank / _dense); kind 2 the whole call.
+constexpr size_t CLUSTER_DENSE_BYTES = (size_t)64 << 20;
+
+void cluster(frt_matcher *m, float t, int32_t *labels_dev, long long *stats_dev, hipStream_t s) {
+    const int N = m->N, D = m->D, chunks = (N + 127) / 128;
+    m->wait_idle(s);
+    m->ensure_queries(128);
+    const int dense_q = (int)std::max<size_t>(1, std::min<size_t>(128, CLUSTER_DENSE_BYTES / sizeof(float) / (size_t)N));  // queries per dense launch
+    m->d_full.reserve((size_t)dense_q * N);
+    m->d_parent.reserve((size_t)std::max(m->gal.cap_rows, N));
+    m->d_cluster_ovf.reserve((size_t)chunks);
+    int32_t *parent = m->d_parent.get();
+    ProfScope ps(2, "cluster", 2.0 * D * (double)N * N, s);
+    launch_cluster_init(parent, N, stats_dev, s);
+    // the chunk's queries: the stored fp32 rows where they lie; fp16 storage: widened into the query scratch
+    auto chunk_queries = [&](int r0, int F) -> const float * {
+        if (!m->gal.store16) return m->gal.rows32.get() + (size_t)r0 * D;
+        launch_cluster_queries(m->gal.rows16.get(), r0, F, D, m->qs.q.get(), s);
+        return m->qs.q.get();
+    };
+    auto dense_chunk = [&](int r0, int F) {
+        const float *q = chunk_queries(r0, F);
+        ProfScope p(3, "cluster_dense", 2.0 * D * (double)N * F, s);
+        for (int f0 = 0; f0 < F; f0 += dense_q) {
+            const int nf = std::min(dense_q, F - f0);
+            m->with_rows([&](auto *g) { launch_match_full(g, N, D, q + (size_t)f0 * D, nf, m->d_full.get(), s); });
+            launch_cluster_dense_union(m->d_full.get(), nf, N, r0 + f0, t, parent, stats_dev, s);
+        }
+    };
+    const bool screened = m->screen && m->screen_on;
+    const bool triangular = !getenv("FRT_CLUSTER_FULL_WALK");  // measurement only (tools/cluster_timing.py): every chunk scans from tile 0
+    const int tiles = chunks;
+    if (screened) prof_reserve(3, 3 * (size_t)chunks);
+    long long n_screened = 0, n_dense = 0;
+    for (int c = 0; c < chunks; ++c) {
+        const int r0 = c * 128, F = std::min(128, N - r0);
+        if (screened) {
+            const float *q = chunk_queries(r0, F);
+            // Triangular walk: rows j > i lie in tiles >= c, so the scan begins at the chunk's own tile - the shadow, its scales and the stored
+            // fp16 rows are whole 128-row tiles of 128 * D elements each, and the coarse kernels number tiles from the pointer they are given.
+            // They launch min(tiles, FRT_MATCH_COARSE_WG) workgroups and the selection reads FRT_MATCH_COARSE_WG rows of wgmax, so a tail
+            // with fewer tiles than that is scanned from tile 0 like the whole gallery (the selection still lists tiles >= c only).
+            const int origin = (triangular && tiles - c >= FRT_MATCH_COARSE_WG) ? c : 0;
+            const size_t skip = (size_t)origin * 128 * D;
+            const int Nl = N - origin * 128;
+            ScreenScratch w = m->screen_scratch();
+            if (w.g8) {
+                w.g8 += skip;
+                w.g8_scale += (size_t)origin * 128;
+            }
+            const half_t *g16 = m->gal.rows16 ? m->gal.rows16.get() + skip : nullptr;
+            bool i8;
+            {
+                ProfScope p(3, "cluster_coarse", 2.0 * D * (double)Nl * F, s);
+                i8 = launch_match_coarse(g16, Nl, D, q, F, w, s);
+            }
+            {
+                ProfScope p(3, "cluster_select", 0.0, s);
+                launch_match_select_threshold(Nl, D, q, F, t, c - origin, m->gmax_norm, w, i8, s);
+            }
+            ProfScope p(3, "cluster_rerank", 0.0, s);
+            m->with_rows([&](auto *g) { launch_cluster_rerank_union(g, N, D, q, r0, origin, w, t, parent, stats_dev, m->d_cluster_ovf.get() + c, s); });
+        } else {
+            dense_chunk(r0, F);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    if (screened) {
+        std::vector<int> ovf((size_t)chunks);
+        HIPCHK(hipMemcpyAsync(ovf.data(), m->d_cluster_ovf.get(), (size_t)chunks * sizeof(int), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (int c = 0; c < chunks; ++c)
+            if (ovf[(size_t)c]) {
+                dense_chunk(c * 128, std::min(128, N - c * 128));
+                ++n_dense;
+            }
+        n_screened = chunks - n_dense;
+    } else {
+        n_dense = chunks;
+    }
+    launch_cluster_flatten(parent, N, labels_dev, stats_dev, n_screened, n_dense, s);
+    HIPCHK(hipGetLastError());
+}
+
+void cluster_checks(frt_matcher *m, float threshold) {
+    if (!std::isfinite(threshold)) raise(FRT_ERR_INVALID, "cluster: the threshold is not finite");
+    if (m->row_offset != 0) raise(FRT_ERR_INVALID, "cluster: a gallery with a row offset (a shard) does not know its neighbours' rows");
+}
+
 // the shell of the gallery entry points: the object's lock and device around fn
 template <typename Fn>
 int with_gallery(frt_matcher *m, Fn &&fn) {
@@ -737,28 +858,7 @@ int frt_matcher_set_labels(frt_matcher *m, const int32_t *labels, int n) {
     return guarded([&] {
         if (!m || n < 0 || (n > 0 && !labels)) raise(FRT_ERR_INVALID, "set_labels: bad argument");
         std::lock_guard<std::mutex> lk(m->mu);
-        if (n == 0) {  // clear
-            if (m->labelled) ++m->generation;
-            m->drop_labels();
-            return;
-        }
-        if (n != m->N) raise(FRT_ERR_INVALID, "set_labels: one label per gallery row");
-        for (int i = 0; i < n; ++i)
-            if (labels[i] < 0) raise(FRT_ERR_INVALID, "set_labels: negative label");
-        use_device(m->device);
-        hipStream_t s = m->stream;
-        m->wait_idle(s);  // a match stage in flight may be reading the old labels
-        HIPCHK(hipStreamSynchronize(s));
-        if (m->busy) HIPCHK(hipEventSynchronize(m->ev_busy));
-        m->ensure_label_room(std::max(m->gal.cap_rows, n), 0, s);
-        HIPCHK(hipMemcpyAsync(m->d_labels.get(), labels, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
-        HIPCHK(hipStreamSynchronize(s));
-        m->drop_labels();
-        m->labelled = true;
-        m->h_labels.reserve((size_t)std::max(m->gal.cap_rows, n));
-        m->h_labels.assign(labels, labels + n);
-        m->count_labels(labels, n);
-        ++m->generation;
+        set_labels(m, labels, n);
     });
 }
 
@@ -783,6 +883,51 @@ int frt_matcher_build_templates(frt_matcher *src, frt_matcher *dst, int32_t *lab
         std::unique_lock<std::mutex> lk1(first->mu), lk2;
         if (second) lk2 = std::unique_lock<std::mutex>(second->mu);
         build_templates(src, dst, labels_out, n_rows_out, min_sim_out, min_row_out, templates_out);
+    });
+}
+
+int frt_matcher_cluster(frt_matcher *m, float threshold, int32_t *labels_out, int install_labels, long long stats_out[4]) {
+    return with_gallery(m, [&] {
+        cluster_checks(m, threshold);
+        long long stats[4] = {0, 0, 0, 0};
+        if (m->N > 0) {
+            const int N = m->N;
+            hipStream_t s = m->stream;
+            m->d_cluster_labels.reserve((size_t)N);
+            m->d_cluster_stats.reserve(4);
+            cluster(m, threshold, m->d_cluster_labels.get(), m->d_cluster_stats.get(), s);
+            std::vector<int32_t> own;
+            int32_t *labels = labels_out;
+            if (!labels && install_labels) {
+                own.resize((size_t)N);
+                labels = own.data();
+            }
+            if (labels) HIPCHK(hipMemcpyAsync(labels, m->d_cluster_labels.get(), (size_t)N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(stats, m->d_cluster_stats.get(), sizeof(stats), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+            if (install_labels) set_labels(m, labels, N);
+        }
+        for (int i = 0; stats_out && i < 4; ++i) stats_out[i] = stats[i];
+    });
+}
+
+int frt_matcher_cluster_dev(frt_matcher *m, float threshold, void *labels_dev, void *stats_dev, void *hip_stream) {
+    return with_gallery(m, [&] {
+        cluster_checks(m, threshold);
+        hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+        if (m->N <= 0) {
+            if (stats_dev) HIPCHK(hipMemsetAsync(stats_dev, 0, 4 * sizeof(long long), s));
+            return;
+        }
+        if (!labels_dev) raise(FRT_ERR_INVALID, "cluster_dev: null argument");
+        long long *stats = reinterpret_cast<long long *>(stats_dev);
+        if (!stats) {
+            m->d_cluster_stats.reserve(4);
+            stats = m->d_cluster_stats.get();
+        }
+        cluster(m, threshold, reinterpret_cast<int32_t *>(labels_dev), stats, s);
+        HIPCHK(hipEventRecord(m->ev_busy, s));  // the caller's stream is still using the scratch
+        m->busy = true;
     });
 }
 

@@ -68,6 +68,10 @@ struct frt_matcher {
     DevBuf<float> d_edit_stage;    // fp16 storage: fp32 landing buffer of host rows in front of the conversion kernel
     DevBuf<uint8_t> d_bounce;      // BOUNCE_BYTES of the chunked compaction
     DevBuf<int> d_keys;            // the hole keys of a removal (frt_holes.h)
+    // ---- clustering (frt_matcher_cluster): the union-find forest, one overflow flag per 128-row chunk, and the host form's results
+    DevBuf<int32_t> d_parent, d_cluster_labels;
+    DevBuf<int> d_cluster_ovf;
+    DevBuf<long long> d_cluster_stats;  // [4]
     // ---- identities (frt_matcher_set_labels / gallery_add_labeled / topk_labels): one int32 label >= 0 per row, on the device for the label
     //      test of the identity passes and mirrored on the host, where the edits and the per-label row counts are kept.
     bool labelled = false;

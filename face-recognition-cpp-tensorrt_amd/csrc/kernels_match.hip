@@ -826,15 +826,13 @@ __global__ __launch_bounds__(64) void merge_topk_labels_kernel(const int32_t *__
 // 64-bit slot with one atomicMax: high word = the similarity mapped monotonically to an unsigned integer, low word = ~row, so a higher
 // similarity wins and among equal similarities the LOWER row.  More pairs than the list holds (non-finite inputs, degenerate
 // galleries): the overflow flag routes the call through the unscreened exact scan instead (gate argument below).
-struct MatchPair {
-    int q, tile;  // tile: bits 0 - 27 the 128-row tile, bits 28 - 31 which of its four 32-row blocks are inside the band
-};
-constexpr int PAIR_TILE_MASK = (1 << 28) - 1;
+// (struct MatchPair and the positions of the control words: frt_kernels.h - the clustering kernels read the same list)
+constexpr int PAIR_TILE_MASK = FRT_MATCH_PAIR_TILE_MASK;
 // ctl words: [1] overflow flag, [CTL_SEG0 + s * CTL_STRIDE] number of pairs in sub-list s.  The pair list is SEL_SUB sub-lists of pair_cap / SEL_SUB
 // entries, one per (tile segment = blockIdx.x of the selection, query & 3): 1 400 increments of ONE counter cost 35 us of atomics (queries that match
 // nothing, int8 band).  Round 4 shared them out over sixteen counters in ONE cache line - the selection still took 27 us with ~ 2 000 pairs against
 // 7 us with 128 (returning atomics on one line queue in one L2 channel whatever the address); round 6: 64 counters, each in its own 128-byte line.
-constexpr int CTL_OVERFLOW = 1, CTL_SEG0 = 32, CTL_STRIDE = 32, SEL_QSUB = 4, SEL_SUB = FRT_MATCH_SEL_SUB;
+constexpr int CTL_OVERFLOW = FRT_MATCH_CTL_OVERFLOW, CTL_SEG0 = FRT_MATCH_CTL_SEG0, CTL_STRIDE = FRT_MATCH_CTL_STRIDE, SEL_QSUB = 4, SEL_SUB = FRT_MATCH_SEL_SUB;
 static_assert(SEL_SUB == SEL_SEG * SEL_QSUB && CTL_SEG0 + SEL_SUB * CTL_STRIDE <= CTL_WORDS, "control words");
 constexpr int FB_BLOCKS = 128;  // workgroups of the gated fallback scan (it returns at once in the normal case: keep the empty launch small)
 
@@ -849,13 +847,18 @@ __device__ __forceinline__ float unmono_bits(unsigned m) { return __uint_as_floa
 __global__ __launch_bounds__(256) void match_select_pairs_kernel(const float *__restrict__ tilemax, int num_tiles, const float *__restrict__ wgmax, int n_wg,
                                                                  int F, const float *__restrict__ Q, int D, float gmax_norm, MatchPair *__restrict__ pairs,
                                                                  int pair_cap, int *__restrict__ ctl, const float *__restrict__ kth = nullptr,
-                                                                 float c_round = 1.2e-3f, float gerr = 0.f) {
+                                                                 float c_round = 1.2e-3f, float gerr = 0.f, float abs_thr = NAN, int tile_min = 0) {
     // c_round / gerr: |S~ - S| <= ||q|| * (c_round * max||g|| + 1.02 * gerr).  fp16 shadow: two fp16 roundings (1.2e-3), no storage error;
     // int8 shadow: one rounding (the query's: 0.7e-3) + the measured quantisation error norm of the rows
     // kth != nullptr (top-k): the threshold hangs on the query's k-th largest coarse entry (match_kth_kernel) instead of its largest.  With
     // |S~ - S| <= delta: the k-th largest coarse entry m_k is the maximum of a 32-row block, k blocks have one >= m_k, hence k distinct rows
     // have S >= m_k - delta, hence the exact k-th best similarity s_k >= m_k - delta, and every row with S >= s_k has S~ >= m_k - 2*delta: it
     // lives in a listed block.  (Fewer than k coarse entries: kth = -inf -> every tile.)
+    // abs_thr not NaN (frt_matcher_cluster): the threshold is the constant t = abs_thr instead of hanging on a coarse entry.  A row with
+    // S >= t has S~ >= t - delta, so the coarse maximum of its block is >= t - delta: ONE delta, because the bound is against a constant and
+    // not against a second coarse value that is itself off by delta.  Only tiles from tile_min on are listed (the caller joins rows j > i and
+    // none of them lies in a tile in front of the query's own).  The per-workgroup maxima then only say whether a coarse entry was NaN.
+    const bool absolute = abs_thr == abs_thr;
     __shared__ float sm[4], sn[4];
     __shared__ int snan[4];
     const int q = blockIdx.y, seg = blockIdx.x, tid = threadIdx.x;
@@ -885,14 +888,16 @@ __global__ __launch_bounds__(256) void match_select_pairs_kernel(const float *__
     const float delta = qn * (c_round * gmax_norm + 1.02f * gerr);
     // fp16 overflow / non-finite inputs: no valid bound -> every tile (which overflows the pair list and sends the call through the exact
     // full scan)
-    const float thr = (!anynan && qn < 6.0e4f && gmax_norm < 6.0e4f && gerr < 6.0e4f && m == m && m > -INFINITY && m < INFINITY) ? m - 2.f * delta : -INFINITY;
+    const bool bounded = !anynan && qn < 6.0e4f && gmax_norm < 6.0e4f && gerr < 6.0e4f;
+    float thr = (bounded && m == m && m > -INFINITY && m < INFINITY) ? m - 2.f * delta : -INFINITY;
+    if (absolute) thr = bounded ? abs_thr - delta : -INFINITY;
     const int t0 = (int)((long)num_tiles * seg / SEL_SEG), t1 = (int)((long)num_tiles * (seg + 1) / SEL_SEG);
     const floatx4 *row = reinterpret_cast<const floatx4 *>(tilemax + (long)q * num_tiles * 4);
     const int lane = tid & 63;
     for (int tb = t0; tb < t1; tb += 256) {  // (uniform trip count: the ballot below needs whole waves)
         const int t = tb + tid;
         unsigned mask = 0u;
-        if (t < t1) {
+        if (t < t1 && t >= tile_min) {
             const floatx4 e = row[t];
             // (the re-rank reads only the flagged 32-row blocks: with the wider band of the int8 shadow a query that matches nothing lists
             //  a dozen tiles, and whole tiles were 256 KB of fp32 rows per pair - 125 us of re-rank at 128 such queries)
@@ -1210,10 +1215,8 @@ static void launch_coarse_t(const half_t *g16, const ScreenScratch &w, int N, co
     hipLaunchKernelGGL((match_coarse_kernel<D>), g, dim3(256), lds, s, g16, N, F, w.tilemax, tiles, q32, w.wgmax, w.ctl, w.qkey);
 }
 
-// The front of every screened call: coarse scan, then the (query, tile) pairs inside the band under the query's kth_count-th largest coarse
-// entry (kth_count == 1: its largest, taken from the per-workgroup maxima).
-static void launch_coarse_select(const half_t *g16, int N, int D, const float *queries, int F, int kth_count, float gmax_norm, const ScreenScratch &w,
-                                 float *kth_scratch, hipStream_t s) {
+// the coarse scan alone; true: it read the int8 shadow
+bool launch_match_coarse(const half_t *g16, int N, int D, const float *queries, int F, const ScreenScratch &w, hipStream_t s) {
     const int tiles = (N + BM - 1) / BM;
     const bool i8 = w.g8 && D == 512;  // int8 shadow (fp32-stored galleries): half the bytes of the scan, same answers
     if (i8) {
@@ -1226,6 +1229,15 @@ static void launch_coarse_select(const half_t *g16, int N, int D, const float *q
         case 256: launch_coarse_t<256>(g16, w, N, queries, F, tiles, s); break;
         default: launch_coarse_t<512>(g16, w, N, queries, F, tiles, s); break;  // match_screen_supported() gates the callers
     }
+    return i8;
+}
+
+// The front of every screened call: coarse scan, then the (query, tile) pairs inside the band under the query's kth_count-th largest coarse
+// entry (kth_count == 1: its largest, taken from the per-workgroup maxima).
+static void launch_coarse_select(const half_t *g16, int N, int D, const float *queries, int F, int kth_count, float gmax_norm, const ScreenScratch &w,
+                                 float *kth_scratch, hipStream_t s) {
+    const int tiles = (N + BM - 1) / BM;
+    const bool i8 = launch_match_coarse(g16, N, D, queries, F, w, s);
     const float *kth = nullptr;
     if (kth_count > 1) {
         hipLaunchKernelGGL(match_kth_kernel, dim3(F), dim3(256), 0, s, w.tilemax, tiles * 4, kth_count, kth_scratch);
@@ -1234,6 +1246,16 @@ static void launch_coarse_select(const half_t *g16, int N, int D, const float *q
     // (with F > 128 every query block y wrote its own columns of wgmax: [COARSE_WG][F])
     hipLaunchKernelGGL(match_select_pairs_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles, w.wgmax, COARSE_WG, F, queries, D, gmax_norm,
                        reinterpret_cast<MatchPair *>(w.pairs), w.pair_cap, w.ctl, kth, i8 ? 0.7e-3f : 1.2e-3f, i8 ? w.gerr : 0.f);
+}
+
+// Behind launch_match_coarse, for a clustering chunk (kernels_cluster.hip): the (query, tile) pairs whose block can hold a row with
+// S >= threshold, tiles from tile_min on.  i8: what the coarse scan returned.
+void launch_match_select_threshold(int N, int D, const float *queries, int F, float threshold, int tile_min, float gmax_norm, const ScreenScratch &w, bool i8,
+                                   hipStream_t s) {
+    const int tiles = (N + BM - 1) / BM;
+    hipLaunchKernelGGL(match_select_pairs_kernel, dim3(SEL_SEG, F), dim3(256), 0, s, w.tilemax, tiles, w.wgmax, COARSE_WG, F, queries, D, gmax_norm,
+                       reinterpret_cast<MatchPair *>(w.pairs), w.pair_cap, w.ctl, (const float *)nullptr, i8 ? 0.7e-3f : 1.2e-3f, i8 ? w.gerr : 0.f, threshold,
+                       tile_min);
 }
 
 // The screened search: exact top-k lists idx_out / sim_out [F][k] (k = 1: the top-1 search), bit for bit what the exact scan returns.

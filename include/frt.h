@@ -330,6 +330,33 @@ int frt_merge_topk_labels_dev(int shards, int n, int k, const void *label_all_de
 int frt_matcher_build_templates(frt_matcher *src, frt_matcher *dst, int32_t *labels_out, int32_t *n_rows_out, float *min_sim_out, int32_t *min_row_out,
                                 float *templates_out);
 
+/* Group an UNLABELLED gallery into identities: single-linkage clustering at a similarity threshold, on the device.  Rows i < j are joined
+ * iff S(i, j) >= threshold, S being the matcher's own exact fp32 similarity - the value frt_matcher_calculate returns for query = stored
+ * row i against row j (fp16 storage: the stored fp16 rows widened to fp32).  The comparison is >= (the caller of knownPersonThreshold
+ * treats sim < thr as unknown); a NaN similarity joins nothing; a row is never joined to itself.  The result is the connected components
+ * of that graph:
+ *   labels[i] = the smallest row index of i's component (>= 0, the same whatever order the device worked in; usable as they are by
+ *               frt_matcher_set_labels);
+ *   stats[0]  = number of components, stats[1] = number of joined pairs (i < j), stats[2] / stats[3] = 128-row query chunks that went
+ *               through the screened path (shadow gallery, exact re-rank of the candidate blocks) / through the exact dense path
+ *               (galleries without a screen, frt_matcher_set_screening(0), chunks whose candidate list overflowed).  Both paths decide on
+ *               the same similarity bits, so the result does not depend on the path.
+ * labels_out [N] (host) and stats_out may be NULL.  install_labels != 0: the result becomes the matcher's labels exactly as
+ * frt_matcher_set_labels with the same array would make it (labels_info, topk_labels and build_templates work at once; the generation
+ * moves as set_labels moves it).  Without it the gallery, its labels and its generation stay as they are.
+ * frt_matcher_cluster_dev: labels_dev [N] int32 and stats_dev (4 x int64, may be NULL) are device memory, complete when hip_stream has
+ * run; the call itself waits once for the device in the middle (the overflow flags of the chunks).
+ * A gallery that holds a non-finite row (NaN, Inf) has no error bound for its shadow: every chunk's candidate list then overflows and the
+ * whole call pays the screened front AND the dense pass for nearly every chunk (the result stays exact; the row itself joins nothing
+ * unless a similarity of +Inf comes out).  Remove such rows first if the time matters.
+ * The calls hold the matcher's mutex, wait for a match stage in flight and re-run from scratch after every edit (no incremental form).
+ * An empty gallery: FRT_OK with zero clusters.  FRT_ERR_INVALID: a threshold that is not finite; a matcher with a row offset (a shard
+ * cannot know its neighbours' rows: clustering across shards is out of scope). */
+int frt_matcher_cluster(frt_matcher *m, float threshold, int32_t *labels_out /* [N] host, may be NULL */, int install_labels,
+                        long long stats_out[4] /* clusters, edges, screened chunks, dense chunks; may be NULL */);
+int frt_matcher_cluster_dev(frt_matcher *m, float threshold, void *labels_dev /* [N] int32 */, void *stats_dev /* 4 x int64, may be NULL */,
+                            void *hip_stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU exchange.  The reference is one single-GPU C++ process (src/app.cpp:52-57, 367); north_star shards whole
  * frames over the GPUs of a node with an RCCL all-gather as the only exchange step.  These calls are that step for a C++ host: RCCL
@@ -641,6 +668,8 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).
  * ------------------------------------------------------------------------------------------------------------------ */
 /* kinds: 0 = off (drops the records), 1 = time every launch of the dominant kernel family (conv3x3 MFMA), 2 = time every stage,
+ * 3 = time the stages of every chunk of frt_matcher_cluster (two events per stage and chunk: size frt_profile_collect's arrays for them; the
+ *     call creates the events it needs before its first chunk, and the records between the launches still slow it by about a sixth),
  * -1 = pause: stop recording but keep the records (bench.py samples ONE step of its timed region: the events around every conv
  * launch cost 11 % of a step when left on for all of them).  Every call with kind >= 0 also makes sure a pool of events exists, so that
  * no event is created between the two records of a bracket (call it with 0 once before a timed region). */

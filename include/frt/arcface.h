@@ -247,6 +247,12 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
             if (classNames[i] == className) rows.push_back((int)i);
         if (rows.empty()) return 0;
         matmul.galleryRemove(rows.data(), (int)rows.size());
+        if (m_labelsFromCluster) {
+            // clusterGallery's labels are ROW INDICES of the gallery as it was: the rows have moved, and a person whose first row has just
+            // gone would keep the removed className.  The matcher goes back to no labels; the next ranked call interns classNames again.
+            matmul.setLabels(nullptr, 0);
+            forgetLabels();
+        }
         classNames.erase(std::remove(classNames.begin(), classNames.end(), className), classNames.end());
         classCount -= (int)rows.size();
         return (int)rows.size();
@@ -486,6 +492,24 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
             out.push_back(std::make_tuple(labelName(m_templateLabels[i]), m_templateRows[i], m_templateMinSim[i], m_templateMinRow[i]));
         return out;
     }
+    // Extension: which gallery rows are the same PERSON, without looking at classNames (the reference allows one person under two USR_IDs:
+    // /insert/face never looks at the gallery).  Single-linkage clustering on the device (frt_matcher_cluster): rows whose exact similarity is
+    // >= threshold are joined, the result is one label per gallery row = the smallest row of its group.  install: the groups become the
+    // matcher's labels, so matchTopIdentities, matchTemplates and auditTemplates rank and audit PERSONS from then on, each named by the
+    // className of its first row, until initMatMul / resetEmbeddings / removeClass go back to classNames (a removal shifts the rows the labels
+    // name, so it drops the grouping: call clusterGallery again afterwards).  A row enrolled after the install gets a NEW label named by its
+    // className even when that name is already a person's: the grouping is by similarity, and only a new clusterGallery call revises it.
+    std::vector<int> clusterGallery(float threshold, bool install = false) {
+        std::vector<int> labels;
+        matmul.cluster(threshold, labels, install);
+        if (install) {
+            forgetLabels();
+            m_labelNames = classNames;  // a label is a row index: its name is that row's
+            m_labelNames.resize(labels.size());
+            m_labelsSet = m_labelsFromCluster = !labels.empty();
+        }
+        return labels;
+    }
     // src/arcface.cpp:219-231: drawing only, not on the hot path (not even called by app.cpp); real OpenCV required.
     void visualize(cv::Mat &image, std::vector<std::string> names, std::vector<float> sims) {
 #ifdef FRT_HAVE_OPENCV
@@ -534,6 +558,7 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     }
     void forgetLabels() {
         m_labelsSet = false;
+        m_labelsFromCluster = false;
         m_labelOf.clear();
         m_labelNames.clear();
     }
@@ -568,6 +593,7 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     frt_pipeline *m_photoPipe = nullptr;  // enrolImages: created at its first call, for m_photoDet
     frt_detector *m_photoDet = nullptr;
     bool m_labelsSet = false;
+    bool m_labelsFromCluster = false;  // the labels are clusterGallery's row indices, not interned classNames
     std::map<std::string, int> m_labelOf;
     std::vector<std::string> m_labelNames;
 

@@ -86,6 +86,15 @@ class MatMul {
         ensure();
         checkFrtStatus(frt_matcher_build_templates(h_, dst ? dst->handle() : nullptr, labels, nRows, minSim, minRow, templates));
     }
+    // Extension: group the rows into persons without any labels (frt.h "Group an UNLABELLED gallery"): single-linkage clustering on the
+    // device at a similarity threshold.  labels[i] = the smallest row of i's component (rows i, j are joined iff their exact similarity is
+    // >= threshold); stats (may be null) = clusters, joined pairs, screened chunks, dense chunks.  install: the labels become the gallery's
+    // own, as setLabels(labels) would make them - photo dump -> cluster(t, labels, true) -> buildTemplates(&persons) never leaves the device.
+    void cluster(float threshold, std::vector<int> &labels, bool install = false, long long *stats = nullptr) {
+        ensure();
+        labels.assign((size_t)numRows(), 0);
+        checkFrtStatus(frt_matcher_cluster(h_, threshold, labels.empty() ? nullptr : labels.data(), install ? 1 : 0, stats));
+    }
     void topk(const float *embeds, int embedCount, int k, int *idx, float *sim) {
         ensure();
         checkFrtStatus(frt_matcher_topk(h_, embeds, embedCount, k, idx, sim));
