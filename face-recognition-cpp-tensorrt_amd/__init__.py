@@ -105,6 +105,8 @@ ABI = {
     "frt_matcher_build_templates": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_matcher_cluster": (_i, [_vp, _f, _vp, _i, _vp]),
     "frt_matcher_cluster_dev": (_i, [_vp, _f, _vp, _vp, _vp]),
+    "frt_matcher_separation": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "frt_matcher_separation_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "frt_embeds_to_half_dev": (_i, [_vp, _sz, _vp, _vp]),
     "frt_comm_get_unique_id": (_i, [_vp]),
     "frt_comm_set_bootstrap_timeout": (ctypes.c_double, [ctypes.c_double]),
@@ -424,6 +426,32 @@ class MatMul:
         """Raw device addresses: labels int32 [m], stats 4 x int64 (or ``None``); complete when ``hip_stream`` has run."""
         _check(lib.frt_matcher_cluster_dev(self._h, float(threshold), _vp(labels_ptr) if labels_ptr else None, _vp(stats_ptr) if stats_ptr else None,
                                            _vp(hip_stream) if hip_stream else None))
+
+    SEPARATION_STATS = ("genuine_rows", "impostor_rows", "closer_to_another", "screened_chunks", "exact_chunks")
+
+    def separation(self, thresholds=None):
+        """Leave-one-out genuine / impostor scores of this labelled gallery (frt_matcher_separation).  Returns ``(gen_sim, gen_row, imp_sim,
+        imp_row, counts, stats)``: for every row the best OTHER row of its own label and the best row of any other label by the matcher's
+        exact similarity (``-inf`` / ``-1`` without a candidate), ``counts`` int64 ``[len(thresholds), 2]`` = rows with ``gen_sim < t`` /
+        rows with ``imp_sim >= t`` per threshold (at most 64), ``stats`` a dict of ``SEPARATION_STATS``.  ``max(imp_sim)`` is the
+        threshold above which ``cluster`` merges no two labels."""
+        n = int(lib.frt_matcher_num_rows(self._h))
+        t = np.ascontiguousarray([] if thresholds is None else thresholds, np.float32).reshape(-1)
+        gen_sim, imp_sim = np.empty(n, np.float32), np.empty(n, np.float32)
+        gen_row, imp_row = np.empty(n, np.int32), np.empty(n, np.int32)
+        counts = np.zeros((t.size, 2), np.int64)
+        stats = (ctypes.c_longlong * 5)()
+        _check(lib.frt_matcher_separation(self._h, _ptr(gen_sim) if n else None, _ptr(gen_row) if n else None, _ptr(imp_sim) if n else None,
+                                          _ptr(imp_row) if n else None, _ptr(t) if t.size else None, t.size, _ptr(counts) if t.size else None, stats))
+        return gen_sim, gen_row, imp_sim, imp_row, counts, dict(zip(self.SEPARATION_STATS, (int(v) for v in stats)))
+
+    def separation_dev(self, gen_sim_ptr, gen_row_ptr, imp_sim_ptr, imp_row_ptr, thresholds=None, counts_ptr=None, stats_ptr=None, hip_stream=None):
+        """Raw device addresses (any may be ``None``): sims fp32 [m], rows int32 [m], counts int64 [len(thresholds)][2], stats 5 x int64;
+        ``thresholds`` stay on the host.  Complete when ``hip_stream`` has run."""
+        t = np.ascontiguousarray([] if thresholds is None else thresholds, np.float32).reshape(-1)
+        opt = lambda p: _vp(p) if p else None
+        _check(lib.frt_matcher_separation_dev(self._h, opt(gen_sim_ptr), opt(gen_row_ptr), opt(imp_sim_ptr), opt(imp_row_ptr), _ptr(t) if t.size else None,
+                                              t.size, opt(counts_ptr), opt(stats_ptr), opt(hip_stream)))
 
     def setRowOffset(self, row_offset):
         """Sharded gallery: local row 0 is global row ``row_offset`` (top-1 indices become global)."""

@@ -115,6 +115,25 @@ __device__ __forceinline__ floatx4 load_g4(const half_t *G, long g, int D, int k
     const half4 h = *reinterpret_cast<const half4 *>(G + g16_index(g, k, D));
     return floatx4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
 }
+// S(query, stored row g) with the bits of the exact scan: the k order of match_kernel's MFMA chain - per 8 columns, k = 8 ks + s (lanes 0-31
+// of the MFMA) then k = 8 ks + 4 + s (lanes 32-63) - and one fused multiply-add per term.  q: the query's D floats (LDS or global).  The
+// pair re-rank (kernels_match.hip) and the genuine pass (kernels_separation.hip) both call this; the chain itself stays sequential, the
+// unroll keeps 16 row loads in flight per thread.
+template <typename GT>
+__device__ __forceinline__ float exact_row_dot(const GT *__restrict__ G, long g, int D, const float *q) {
+    float acc = 0.f;
+#pragma unroll 8
+    for (int k0 = 0; k0 < D; k0 += 8) {
+        const floatx4 a = load_g4(G, g, D, k0), b = load_g4(G, g, D, k0 + 4);
+        const floatx4 x = *reinterpret_cast<const floatx4 *>(q + k0), y = *reinterpret_cast<const floatx4 *>(q + k0 + 4);
+#pragma unroll
+        for (int s2 = 0; s2 < 4; ++s2) {
+            acc = __builtin_fmaf(a[s2], x[s2], acc);
+            acc = __builtin_fmaf(b[s2], y[s2], acc);
+        }
+    }
+    return acc;
+}
 bool match_screen_supported(int D);  // D the coarse kernel is instantiated for
 // fp32 rows [n_rows][D] (first row = global row row0) -> their place in the fp16 gallery (whose rows never written must be zero)
 void launch_rows_to_half(const float *in, long row0, long n_rows, int D, half_t *g16, hipStream_t s);
@@ -144,6 +163,27 @@ void launch_cluster_dense_union(const float *full, int F, int N, int q_row0, flo
 // label[i] = root(i); stats[0] = number of roots, stats[2] / stats[3] = the host's chunk counts
 void launch_cluster_flatten(const int32_t *parent, int N, int32_t *labels, long long *stats, long long screened_chunks, long long dense_chunks,
                             hipStream_t s);
+
+// ---------------------------------------------------------------- separation (kernels_separation.hip; frt_matcher_separation)
+constexpr int FRT_SEPARATION_MAX_THRESHOLDS = 64;
+// Impostor side (kernels_match.hip).  launch_match_select_kth: the selection stage behind launch_match_coarse, pairs under every query's
+// kth_count-th largest coarse entry (kth_scratch [F] floats).  launch_match_top1_excluding: one label-excluded top-1 search, query q leaving
+// out the rows labelled excluded[q].  screened: the re-rank stage behind those two, *overflow_out (device) = the pair list overflowed and the
+// gated exact scan answered; otherwise one label-excluded exact scan, overflow_out untouched.  idx_out / sim_out [F] (local rows).
+void launch_match_select_kth(int N, int D, const float *queries, int F, int kth_count, float gmax_norm, const ScreenScratch &w, float *kth_scratch, bool i8,
+                             hipStream_t s);
+void launch_match_top1_excluding(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, bool screened, const ScreenScratch &w,
+                                 MatchPartial *partial, int partial_blocks, const int32_t *labels, const int32_t *excluded, int32_t *idx_out, float *sim_out,
+                                 int *overflow_out, hipStream_t s);
+// Genuine side: for every row the best OTHER row of its identity by the exact similarity (first maximum; NaN is no candidate; -inf / -1
+// without one).  group_off [I + 1] / group_rows [N]: frt_templates.hpp; pos_ident [N]: the identity of position p of group_rows.
+template <typename GT>
+void launch_separation_genuine(const GT *rows, int N, int D, const int *group_off, const int *group_rows, const int *pos_ident, float *gen_sim,
+                               int32_t *gen_row, hipStream_t s);
+// stats [5] and counts [n_thresholds][2] (device, int64; zeroed here) from the four arrays; thresholds: host memory, read before this returns.
+// chunk_overflow [chunks]: the impostor searches' flags (read when screened; otherwise every chunk counts as an exact scan).
+void launch_separation_reduce(const float *gen_sim, const int32_t *gen_row, const float *imp_sim, const int32_t *imp_row, int N, const float *thresholds,
+                              int n_thresholds, const int *chunk_overflow, int chunks, bool screened, long long *counts, long long *stats, hipStream_t s);
 
 // ---------------------------------------------------------------- template gallery (kernels_templates.hip)
 // One template per identity (include/frt.h, frt_matcher_build_templates).  rows: the stored gallery (fp32 row-major or fragment-ordered fp16);

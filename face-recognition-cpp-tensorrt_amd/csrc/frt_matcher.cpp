@@ -680,6 +680,82 @@ void cluster_checks(frt_matcher *m, float threshold) {
     if (m->row_offset != 0) raise(FRT_ERR_INVALID, "cluster: a gallery with a row offset (a shard) does not know its neighbours' rows");
 }
 
+// ------------------------------------------------------------------------------------------------------------- separation
+// frt_matcher_separation / _separation_dev (include/frt.h) with m->mu held, N > 0 and labels: the four arrays [N], counts
+// [n_thr][2] and stats [5] (device pointers, none null) are complete on `s` when the stream has run.  Genuine side: one launch over the
+// identity -> rows grouping (uploaded as build_templates uploads it; the host waits once for the copies, so the vectors may go).  Impostor
+// side: the gallery walked in chunks of 128 stored rows as queries, every chunk ONE label-excluded top-1 search whose taken labels are the
+// chunk's own slice of the device labels - through the screen when topk_labels would screen k = 2 (identity_kth_count), else one
+// label-excluded exact scan.  A screened chunk whose pair list overflowed is answered by the gated exact scan inside the same search; its
+// flag lands in d_sep_ovf for the statistics.  frt_profile_enable(3) brackets the stages (separation_genuine / _coarse / _select / _rerank
+// / _exact / _reduce); kind 2 the whole call.
+void separation(frt_matcher *m, float *gen_sim, int32_t *gen_row, float *imp_sim, int32_t *imp_row, const float *thresholds, int n_thr, long long *counts,
+                long long *stats, hipStream_t s) {
+    const int N = m->N, D = m->D, chunks = (N + 127) / 128;
+    m->wait_idle(s);
+    m->ensure_queries(128);
+    std::vector<int32_t> ident_label;
+    std::vector<int> off, rows;
+    frt_template_groups(m->h_labels.data(), N, ident_label, off, rows);
+    const size_t I = ident_label.size();
+    std::vector<int> pos_ident((size_t)N);
+    for (size_t i = 0; i < I; ++i) std::fill(pos_ident.begin() + off[i], pos_ident.begin() + off[i + 1], (int)i);
+    m->d_sep_groups.reserve(2 * (size_t)N + I + 1);
+    m->d_sep_ovf.reserve((size_t)chunks);
+    int *d_rows = m->d_sep_groups.get(), *d_pos = d_rows + N, *d_off = d_pos + N;
+    HIPCHK(hipMemcpyAsync(d_rows, rows.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_pos, pos_ident.data(), (size_t)N * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_off, off.data(), (I + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    ProfScope ps(2, "separation", 2.0 * D * (double)N * N, s);
+    const int kth_count = m->identity_kth_count(2);  // max_rows_per_label + 1 when the screen applies: the best M + 1 rows hold a row of another label
+    const bool screened = kth_count > 0;
+    prof_reserve(3, 3 * (size_t)chunks + 2);
+    {
+        ProfScope p(3, "separation_genuine", 0.0, s);
+        m->with_rows([&](auto *g) { launch_separation_genuine(g, N, D, d_off, d_rows, d_pos, gen_sim, gen_row, s); });
+    }
+    const int32_t *labels = m->d_labels.get();
+    for (int c = 0; c < chunks; ++c) {
+        const int r0 = c * 128, F = std::min(128, N - r0);
+        // the chunk's queries: the stored fp32 rows where they lie; fp16 storage: widened into the query scratch
+        const float *q = m->qs.q.get();
+        if (m->gal.store16) launch_cluster_queries(m->gal.rows16.get(), r0, F, D, m->qs.q.get(), s);
+        else q = m->gal.rows32.get() + (size_t)r0 * D;
+        if (screened) {
+            const ScreenScratch w = m->screen_scratch();
+            bool i8;
+            {
+                ProfScope p(3, "separation_coarse", 2.0 * D * (double)N * F, s);
+                i8 = launch_match_coarse(m->gal.rows16.get(), N, D, q, F, w, s);
+            }
+            {
+                ProfScope p(3, "separation_select", 0.0, s);
+                launch_match_select_kth(N, D, q, F, kth_count, m->gmax_norm, w, m->qs.kth.get(), i8, s);
+            }
+            ProfScope p(3, "separation_rerank", 0.0, s);
+            launch_match_top1_excluding(m->gal.rows32.get(), m->gal.rows16.get(), N, D, q, F, true, w, m->qs.partial.get(), m->blocks, labels, labels + r0,
+                                        imp_row + r0, imp_sim + r0, m->d_sep_ovf.get() + c, s);
+        } else {
+            ProfScope p(3, "separation_exact", 2.0 * D * (double)N * F, s);
+            launch_match_top1_excluding(m->gal.rows32.get(), m->gal.rows16.get(), N, D, q, F, false, m->screen_scratch(), m->qs.partial.get(), m->blocks, labels,
+                                        labels + r0, imp_row + r0, imp_sim + r0, nullptr, s);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    ProfScope p(3, "separation_reduce", 0.0, s);
+    launch_separation_reduce(gen_sim, gen_row, imp_sim, imp_row, N, thresholds, n_thr, m->d_sep_ovf.get(), chunks, screened, counts, stats, s);
+    HIPCHK(hipGetLastError());
+}
+
+void separation_checks(frt_matcher *m, const float *thresholds, int n_thr) {
+    if (n_thr < 0 || n_thr > FRT_SEPARATION_MAX_THRESHOLDS || (n_thr > 0 && !thresholds)) raise(FRT_ERR_INVALID, "separation: n_thresholds must be in 0..64");
+    for (int k = 0; k < n_thr; ++k)
+        if (!std::isfinite(thresholds[k])) raise(FRT_ERR_INVALID, "separation: a threshold is not finite");
+    if (m->row_offset != 0) raise(FRT_ERR_INVALID, "separation: a gallery with a row offset (a shard) does not know its neighbours' rows");
+    if (m->N > 0 && !m->labelled) raise(FRT_ERR_INVALID, "separation: the gallery has no labels (frt_matcher_set_labels)");
+}
+
 // the shell of the gallery entry points: the object's lock and device around fn
 template <typename Fn>
 int with_gallery(frt_matcher *m, Fn &&fn) {
@@ -926,6 +1002,60 @@ int frt_matcher_cluster_dev(frt_matcher *m, float threshold, void *labels_dev, v
             stats = m->d_cluster_stats.get();
         }
         cluster(m, threshold, reinterpret_cast<int32_t *>(labels_dev), stats, s);
+        HIPCHK(hipEventRecord(m->ev_busy, s));  // the caller's stream is still using the scratch
+        m->busy = true;
+    });
+}
+
+int frt_matcher_separation(frt_matcher *m, float *gen_sim_out, int32_t *gen_row_out, float *imp_sim_out, int32_t *imp_row_out, const float *thresholds,
+                           int n_thresholds, long long *counts_out, long long stats_out[5]) {
+    return with_gallery(m, [&] {
+        separation_checks(m, thresholds, n_thresholds);
+        long long res[5 + 2 * FRT_SEPARATION_MAX_THRESHOLDS] = {};  // stats | counts
+        if (m->N > 0) {
+            const size_t N = (size_t)m->N;
+            hipStream_t s = m->stream;
+            m->d_sep_sim.reserve(2 * N);
+            m->d_sep_row.reserve(2 * N);
+            m->d_sep_counts.reserve(5 + 2 * FRT_SEPARATION_MAX_THRESHOLDS);
+            float *sim = m->d_sep_sim.get();
+            int32_t *row = m->d_sep_row.get();
+            long long *cnt = m->d_sep_counts.get();
+            separation(m, sim, row, sim + N, row + N, thresholds, n_thresholds, cnt + 5, cnt, s);
+            if (gen_sim_out) HIPCHK(hipMemcpyAsync(gen_sim_out, sim, N * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (gen_row_out) HIPCHK(hipMemcpyAsync(gen_row_out, row, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            if (imp_sim_out) HIPCHK(hipMemcpyAsync(imp_sim_out, sim + N, N * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (imp_row_out) HIPCHK(hipMemcpyAsync(imp_row_out, row + N, N * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(res, cnt, (5 + 2 * (size_t)n_thresholds) * sizeof(long long), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipStreamSynchronize(s));
+        }
+        for (int i = 0; stats_out && i < 5; ++i) stats_out[i] = res[i];
+        for (int i = 0; counts_out && i < 2 * n_thresholds; ++i) counts_out[i] = res[5 + i];
+    });
+}
+
+int frt_matcher_separation_dev(frt_matcher *m, void *gen_sim_dev, void *gen_row_dev, void *imp_sim_dev, void *imp_row_dev, const float *thresholds,
+                               int n_thresholds, void *counts_dev, void *stats_dev, void *hip_stream) {
+    return with_gallery(m, [&] {
+        separation_checks(m, thresholds, n_thresholds);
+        hipStream_t s = reinterpret_cast<hipStream_t>(hip_stream);
+        if (m->N <= 0) {
+            if (stats_dev) HIPCHK(hipMemsetAsync(stats_dev, 0, 5 * sizeof(long long), s));
+            if (counts_dev && n_thresholds > 0) HIPCHK(hipMemsetAsync(counts_dev, 0, 2 * (size_t)n_thresholds * sizeof(long long), s));
+            return;
+        }
+        // what the caller did not ask for still feeds the reduction: it goes to the matcher's own buffers
+        const size_t N = (size_t)m->N;
+        if (!gen_sim_dev || !imp_sim_dev) m->d_sep_sim.reserve(2 * N);
+        if (!gen_row_dev || !imp_row_dev) m->d_sep_row.reserve(2 * N);
+        if (!counts_dev || !stats_dev) m->d_sep_counts.reserve(5 + 2 * FRT_SEPARATION_MAX_THRESHOLDS);
+        float *gs = gen_sim_dev ? reinterpret_cast<float *>(gen_sim_dev) : m->d_sep_sim.get();
+        float *is = imp_sim_dev ? reinterpret_cast<float *>(imp_sim_dev) : m->d_sep_sim.get() + N;
+        int32_t *gr = gen_row_dev ? reinterpret_cast<int32_t *>(gen_row_dev) : m->d_sep_row.get();
+        int32_t *ir = imp_row_dev ? reinterpret_cast<int32_t *>(imp_row_dev) : m->d_sep_row.get() + N;
+        long long *stats = stats_dev ? reinterpret_cast<long long *>(stats_dev) : m->d_sep_counts.get();
+        long long *counts = counts_dev ? reinterpret_cast<long long *>(counts_dev) : m->d_sep_counts.get() + 5;
+        separation(m, gs, gr, is, ir, thresholds, n_thresholds, counts, stats, s);
         HIPCHK(hipEventRecord(m->ev_busy, s));  // the caller's stream is still using the scratch
         m->busy = true;
     });

@@ -72,6 +72,13 @@ struct frt_matcher {
     DevBuf<int32_t> d_parent, d_cluster_labels;
     DevBuf<int> d_cluster_ovf;
     DevBuf<long long> d_cluster_stats;  // [4]
+    // ---- separation (frt_matcher_separation): the grouping (group_rows [N] | pos_ident [N] | group_off [I + 1]), one overflow flag per
+    //      128-row chunk, and the arrays a caller did not ask for or the host form downloads (sim: gen [N] | imp [N]; row likewise;
+    //      counts: stats [5] | counts [64][2])
+    DevBuf<int> d_sep_groups, d_sep_ovf;
+    DevBuf<float> d_sep_sim;
+    DevBuf<int32_t> d_sep_row;
+    DevBuf<long long> d_sep_counts;
     // ---- identities (frt_matcher_set_labels / gallery_add_labeled / topk_labels): one int32 label >= 0 per row, on the device for the label
     //      test of the identity passes and mirrored on the host, where the edits and the per-label row counts are kept.
     bool labelled = false;

@@ -103,19 +103,7 @@ __global__ __launch_bounds__(128) void cluster_rerank_union_kernel(const GT *__r
         // this row's 32-row block is inside the band, and the row comes after the query's own (i < j; never a row with itself)
         const bool live = g < N && g > i && ((((unsigned)pr.tile >> 28) >> (tid >> 5)) & 1u);
         float acc = 0.f;
-        if (live) {
-            // k order of the exact kernel (match_rerank_pairs_kernel): per 8 columns, k = 8 ks + s then k = 8 ks + 4 + s, one fused multiply-add each
-#pragma unroll 8
-            for (int k0 = 0; k0 < D; k0 += 8) {
-                const floatx4 a = load_g4(G, g, D, k0), b = load_g4(G, g, D, k0 + 4);
-                const floatx4 x = *reinterpret_cast<const floatx4 *>(qs + k0), y = *reinterpret_cast<const floatx4 *>(qs + k0 + 4);
-#pragma unroll
-                for (int s2 = 0; s2 < 4; ++s2) {
-                    acc = __builtin_fmaf(a[s2], x[s2], acc);
-                    acc = __builtin_fmaf(b[s2], y[s2], acc);
-                }
-            }
-        }
+        if (live) acc = exact_row_dot(G, g, D, qs);  // the exact kernel's k order, one fused multiply-add per term (frt_kernels.h)
         const bool hit = live && acc >= thr;  // (a NaN similarity joins nothing)
         if (hit) uf_unite(parent, i, (int)g);
         count_hits(hit, edges);

@@ -949,20 +949,7 @@ __global__ __launch_bounds__(128) void match_rerank_pairs_kernel(const GT *__res
         const long g = (long)(pr.tile & PAIR_TILE_MASK) * 128 + tid;
         const bool live = g < N && ((((unsigned)pr.tile >> 28) >> (tid >> 5)) & 1u);  // this row's 32-row block is inside the band
         float acc = 0.f;
-        if (live) {
-            // k order of the exact kernel: per 32-wide step, for ks in 0..3, for s in 0..3: k = 8 ks + s (lanes 0-31 of the MFMA), then
-            // k = 8 ks + 4 + s (lanes 32-63) - one fused multiply-add each
-#pragma unroll 8
-            for (int k0 = 0; k0 < D; k0 += 8) {  // (unrolled: 16 row loads in flight per thread; the fma chain itself stays sequential)
-                const floatx4 a = load_g4(G, g, D, k0), b = load_g4(G, g, D, k0 + 4);
-                const floatx4 x = *reinterpret_cast<const floatx4 *>(qs + k0), y = *reinterpret_cast<const floatx4 *>(qs + k0 + 4);
-#pragma unroll
-                for (int s2 = 0; s2 < 4; ++s2) {
-                    acc = __builtin_fmaf(a[s2], x[s2], acc);
-                    acc = __builtin_fmaf(b[s2], y[s2], acc);
-                }
-            }
-        }
+        if (live) acc = exact_row_dot(G, g, D, qs);  // the exact kernel's k order, one fused multiply-add per term (frt_kernels.h)
         float v = live ? acc : -INFINITY;
         int i = live ? (int)g : INT_MAX;
         if (prev_sim && i != INT_MAX) {
@@ -1236,8 +1223,15 @@ bool launch_match_coarse(const half_t *g16, int N, int D, const float *queries, 
 // entry (kth_count == 1: its largest, taken from the per-workgroup maxima).
 static void launch_coarse_select(const half_t *g16, int N, int D, const float *queries, int F, int kth_count, float gmax_norm, const ScreenScratch &w,
                                  float *kth_scratch, hipStream_t s) {
-    const int tiles = (N + BM - 1) / BM;
     const bool i8 = launch_match_coarse(g16, N, D, queries, F, w, s);
+    launch_match_select_kth(N, D, queries, F, kth_count, gmax_norm, w, kth_scratch, i8, s);
+}
+
+// The selection stage on its own (behind launch_match_coarse, for a caller that brackets its stages): every query's kth_count-th largest
+// coarse entry when kth_count > 1, then the pairs inside the band under it.  i8: what the coarse scan returned.
+void launch_match_select_kth(int N, int D, const float *queries, int F, int kth_count, float gmax_norm, const ScreenScratch &w, float *kth_scratch, bool i8,
+                             hipStream_t s) {
+    const int tiles = (N + BM - 1) / BM;
     const float *kth = nullptr;
     if (kth_count > 1) {
         hipLaunchKernelGGL(match_kth_kernel, dim3(F), dim3(256), 0, s, w.tilemax, tiles * 4, kth_count, kth_scratch);
@@ -1334,6 +1328,33 @@ void launch_match_topk_labels(const float *gallery, const half_t *g16, int N, in
                 hipLaunchKernelGGL(match_reduce_kernel<true>, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out + j, sim_out + j, k, (const int *)nullptr,
                                    labels, label_out + j, row_offset);
             }
+        }
+    });
+}
+
+// The impostor search of frt_matcher_separation: ONE label-excluded top-1 search, query q leaving out the rows that carry
+// excluded[q] - the identity passes above with one taken label per query at stride 1 and no previous winner.  Every kernel is launched
+// with arguments it already had.  screened: behind launch_match_coarse + launch_match_select_kth - the label-excluded pair re-rank with the
+// gated exact scan behind the overflow flag, whose value is copied to *overflow_out for the caller's statistics; otherwise one
+// label-excluded exact scan.  idx_out / sim_out [F], local rows.
+void launch_match_top1_excluding(const float *gallery, const half_t *g16, int N, int D, const float *queries, int F, bool screened, const ScreenScratch &w,
+                                 MatchPartial *partial, int partial_blocks, const int32_t *labels, const int32_t *excluded, int32_t *idx_out, float *sim_out,
+                                 int *overflow_out, hipStream_t s) {
+    const int *gate = w.ctl + CTL_OVERFLOW;
+    const int fb = partial_blocks < FB_BLOCKS ? partial_blocks : FB_BLOCKS;
+    with_stored_rows(gallery, g16, [&](auto *G) {
+        using GT = rows_t<decltype(G)>;
+        if (screened) {
+            hipLaunchKernelGGL((match_rerank_pairs_kernel<GT, true>), dim3(2048), dim3(128), (size_t)D * sizeof(float), s, G, N, D, queries,
+                               reinterpret_cast<const MatchPair *>(w.pairs), w.pair_cap, w.ctl, w.qkey, (const float *)nullptr, (const int32_t *)nullptr, 1, 0,
+                               labels, excluded, 1);
+            launch_t<4, false, GT, true, true>(G, N, D, queries, F, partial, nullptr, fb, 0, s, nullptr, nullptr, 1, gate, labels, excluded, 1);
+            hipLaunchKernelGGL(match_unpack_kernel<false>, dim3((F + 255) / 256), dim3(256), 0, s, w.qkey, F, 0, w.ctl, idx_out, sim_out, 1, partial, fb);
+            (void)hipMemcpyAsync(overflow_out, gate, sizeof(int), hipMemcpyDeviceToDevice, s);
+        } else {
+            if (F <= 32) launch_t<1, false, GT, true, true>(G, N, D, queries, F, partial, nullptr, partial_blocks, 0, s, nullptr, nullptr, 1, nullptr, labels, excluded, 1);
+            else launch_t<4, false, GT, true, true>(G, N, D, queries, F, partial, nullptr, partial_blocks, 0, s, nullptr, nullptr, 1, nullptr, labels, excluded, 1);
+            hipLaunchKernelGGL(match_reduce_kernel<false>, dim3(F), dim3(64), 0, s, partial, partial_blocks, F, idx_out, sim_out, 1, (const int *)nullptr);
         }
     });
 }

@@ -357,6 +357,40 @@ int frt_matcher_cluster(frt_matcher *m, float threshold, int32_t *labels_out /* 
 int frt_matcher_cluster_dev(frt_matcher *m, float threshold, void *labels_dev /* [N] int32 */, void *stats_dev /* 4 x int64, may be NULL */,
                             void *hip_stream);
 
+/* Leave-one-out genuine / impostor scores of a LABELLED gallery: how well do the labels separate, and at which threshold.  m has N rows
+ * with labels l and no row offset; S(i, j) is the exact fp32 similarity of frt_matcher_cluster above (query = stored row i against row j).
+ * For every row i:
+ *   genuine   candidates = the rows j != i with l[j] == l[i]   -> gen_sim[i], gen_row[i]
+ *   impostor  candidates = the rows j with l[j] != l[i]        -> imp_sim[i], imp_row[i]
+ * A j whose S(i, j) is NaN is no candidate; the winner is the candidate with the largest S, the lowest row among equal values (the order
+ * of frt_matcher_top1); without a candidate - a person with one photo, a gallery with one identity, a NaN row - the outputs are -inf and
+ * -1, the empty slot of frt_matcher_topk_labels.
+ *   stats[0] = rows with a genuine candidate, stats[1] = rows with an impostor candidate,
+ *   stats[2] = rows with both and imp_sim >= gen_sim: the photos that are closer to another person than to their own,
+ *   stats[3] / stats[4] = 128-row query chunks whose impostor search went through the screen / through the exact scan (galleries without a
+ *              screen, frt_matcher_set_screening(0), more than 15 rows under one label, chunks whose candidate list overflowed).  Both paths
+ *              return the exact scan's bits: the result does not depend on the path.
+ * The optional sweep over n_thresholds <= 64 finite thresholds (host memory in both forms, read before the call returns):
+ *   counts[k][0] = rows with a genuine candidate and gen_sim < thresholds[k]   (the caller's `sim < knownPersonThreshold`: "unknown"),
+ *   counts[k][1] = rows with an impostor candidate and imp_sim >= thresholds[k] (accepted as someone else if their own person were absent).
+ * Every output pointer may be NULL.  frt_matcher_separation_dev: the arrays [N], counts [n_thresholds][2] int64 and stats 5 x int64 are
+ * device memory, complete when hip_stream has run; the call waits once for that stream at its start (the upload of the identity -> rows
+ * grouping).
+ * This is the calibration of frt_matcher_cluster's threshold.  With t* = max_i imp_sim[i]:
+ *   - frt_matcher_cluster at any t > t* puts no two labels into one component (no pair of rows with different labels has S >= t);
+ *   - at t = t* it merges the two identities of the arg-max pair (i, imp_row[i]);
+ *   - for t > t*, row i is a singleton component exactly when gen_sim[i] < t (it can only be joined to rows of its own label, and the best
+ *     of them decides).
+ * The calls hold the matcher's mutex, wait for a match stage in flight and only read the gallery: rows, labels and generation stay as they
+ * are (the query scratch is allocated on first use, which moves the generation as the first search of a matcher does).  There is no
+ * incremental form: after an edit the call runs from scratch.  Cost: N / 128 screened searches, or N / 128 exact scans.
+ * An empty gallery: FRT_OK with zero stats and counts.  FRT_ERR_INVALID: m NULL; rows without labels; a matcher with a row offset (a shard
+ * does not know its neighbours' rows: sharded galleries are out of scope); n_thresholds outside 0..64; a threshold that is not finite. */
+int frt_matcher_separation(frt_matcher *m, float *gen_sim_out, int32_t *gen_row_out, float *imp_sim_out, int32_t *imp_row_out, const float *thresholds,
+                           int n_thresholds, long long *counts_out /* [n_thresholds][2] */, long long stats_out[5]);
+int frt_matcher_separation_dev(frt_matcher *m, void *gen_sim_dev, void *gen_row_dev, void *imp_sim_dev, void *imp_row_dev,
+                               const float *thresholds /* host */, int n_thresholds, void *counts_dev, void *stats_dev, void *hip_stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-GPU exchange.  The reference is one single-GPU C++ process (src/app.cpp:52-57, 367); north_star shards whole
  * frames over the GPUs of a node with an RCCL all-gather as the only exchange step.  These calls are that step for a C++ host: RCCL
@@ -668,7 +702,7 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).
  * ------------------------------------------------------------------------------------------------------------------ */
 /* kinds: 0 = off (drops the records), 1 = time every launch of the dominant kernel family (conv3x3 MFMA), 2 = time every stage,
- * 3 = time the stages of every chunk of frt_matcher_cluster (two events per stage and chunk: size frt_profile_collect's arrays for them; the
+ * 3 = time the stages of every chunk of frt_matcher_cluster / frt_matcher_separation (two events per stage and chunk: size frt_profile_collect's arrays for them; the
  *     call creates the events it needs before its first chunk, and the records between the launches still slow it by about a sixth),
  * -1 = pause: stop recording but keep the records (bench.py samples ONE step of its timed region: the events around every conv
  * launch cost 11 % of a step when left on for all of them).  Every call with kind >= 0 also makes sure a pool of events exists, so that

@@ -510,6 +510,31 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         }
         return labels;
     }
+    // Extension: how well the gallery's persons separate, and where knownPersonThreshold / clusterGallery's threshold should sit
+    // (frt_matcher_separation): per gallery row, in row order, (its className, the similarity of the best OTHER row of its person, the
+    // similarity of the best row of any other person, that row's className) - -inf where there is no such row, and then an empty name.
+    // Persons are classNames, or clusterGallery's groups after an install.  thresholds (at most 64): counts (may be null) becomes
+    // [thresholds.size() x 2] = rows that would be "unknown" from the rest of their person (sim < t) | rows that would be accepted as somebody
+    // else (sim >= t).  stats (may be null): rows with a genuine candidate, with an impostor candidate, closer to another person than to
+    // their own, screened chunks, exact chunks.  Above the largest impostor similarity clusterGallery joins no two persons.
+    std::vector<std::tuple<std::string, float, float, std::string>> gallerySeparation(const std::vector<float> &thresholds = std::vector<float>(),
+                                                                                      std::vector<long long> *counts = nullptr, long long *stats = nullptr) {
+        std::vector<std::tuple<std::string, float, float, std::string>> out;
+        if (classNames.empty()) {
+            if (counts) counts->assign(thresholds.size() * 2, 0);
+            for (int i = 0; stats && i < 5; ++i) stats[i] = 0;
+            return out;
+        }
+        ensureLabels();
+        std::vector<float> genSim, impSim;
+        std::vector<int> genRow, impRow;
+        matmul.separation(genSim, genRow, impSim, impRow, thresholds, counts, stats);
+        for (size_t i = 0; i < genSim.size() && i < classNames.size(); ++i) {
+            const int r = impRow[i];
+            out.push_back(std::make_tuple(classNames[i], genSim[i], impSim[i], (r >= 0 && (size_t)r < classNames.size()) ? classNames[(size_t)r] : std::string()));
+        }
+        return out;
+    }
     // src/arcface.cpp:219-231: drawing only, not on the hot path (not even called by app.cpp); real OpenCV required.
     void visualize(cv::Mat &image, std::vector<std::string> names, std::vector<float> sims) {
 #ifdef FRT_HAVE_OPENCV

@@ -95,6 +95,24 @@ class MatMul {
         labels.assign((size_t)numRows(), 0);
         checkFrtStatus(frt_matcher_cluster(h_, threshold, labels.empty() ? nullptr : labels.data(), install ? 1 : 0, stats));
     }
+    // Extension: how well the labels separate (frt.h "Leave-one-out genuine / impostor scores"): for every row the best OTHER row of its own
+    // label (genSim / genRow) and the best row of any other label (impSim / impRow) by the exact similarity, -inf / -1 without a candidate.
+    // thresholds (at most 64): counts (may be null) becomes [thresholds.size() x 2] = rows with genSim < t | rows with impSim >= t.  stats
+    // (may be null) = rows with a genuine candidate, with an impostor candidate, with impSim >= genSim, screened chunks, exact chunks.  The
+    // largest impSim is the threshold above which cluster() merges no two labels.
+    void separation(std::vector<float> &genSim, std::vector<int> &genRow, std::vector<float> &impSim, std::vector<int> &impRow,
+                    const std::vector<float> &thresholds = std::vector<float>(), std::vector<long long> *counts = nullptr, long long *stats = nullptr) {
+        ensure();
+        const size_t n = (size_t)numRows();
+        genSim.assign(n, 0.f);
+        impSim.assign(n, 0.f);
+        genRow.assign(n, -1);
+        impRow.assign(n, -1);
+        if (counts) counts->assign(thresholds.size() * 2, 0);
+        checkFrtStatus(frt_matcher_separation(h_, n ? genSim.data() : nullptr, n ? genRow.data() : nullptr, n ? impSim.data() : nullptr,
+                                              n ? impRow.data() : nullptr, thresholds.empty() ? nullptr : thresholds.data(), (int)thresholds.size(),
+                                              (counts && !counts->empty()) ? counts->data() : nullptr, stats));
+    }
     void topk(const float *embeds, int embedCount, int k, int *idx, float *sim) {
         ensure();
         checkFrtStatus(frt_matcher_topk(h_, embeds, embedCount, k, idx, sim));
