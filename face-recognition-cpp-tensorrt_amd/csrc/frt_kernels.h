@@ -348,7 +348,10 @@ void launch_rfb_tail(const RfbTailArgs &a, hipStream_t s);
 // Precondition of every launch below: the activation tensors (x, sc, scx, out0, out1) live in buffers of the embedder's sizes - F * 112 * 112 * 64
 // halves for a pass of at most F faces (F * 28 * 28 * 128 for a shortcut conv's output; frt_embedder::alloc_act_set).  Strip kernels compute
 // whole pixel tiles, so a compact strip READS pixel slots of images behind the batch; what it reads there is never stored, and nothing is
-// written outside the logical outputs (tests/test_gpu_arc_launches.py runs every planned launch alone on such buffers).
+// written outside the logical outputs (tests/test_gpu_arc_launches.py runs every planned launch alone on such buffers).  A launch with the SE
+// scratch (se_pool, se_counter) gets the embedder's too: F * 512 * 4 floats of partial sums, then F arrival counters and, se_flag_off = F ints behind
+// them, F gate-ready flags; counters at zero, flags at no epoch still to come.  The fused tail (EPI_BN_SE) writes se_pool[part][face][channel] for
+// the strips of a face, leaves every counter at zero and every flag at se_epoch, and touches no other word of it (the same test, fused cases).
 enum { EPI_PRELU = 0, EPI_BN = 1, EPI_BN_ADD_BN = 2, EPI_PARTIAL = 3, EPI_BN_SE = 4 };  // EPI_BN_SE: BN -> SE gate -> + shortcut -> BN_next (IR-SE unit tail)
 struct ConvMfmaArgs {
     const half_t *x;   // [B][H][W][Cin]

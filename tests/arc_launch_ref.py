@@ -5,7 +5,8 @@ Cases.  Every line of tests/golden/arc_conv_plan.txt whose description is conv1,
 first batch size F of its range and, where the range has it, at first + 1: the smallest batches that select each instantiation, the second
 leaving the last strip ragged (an odd image for two-image strips, 113 faces for the 8-image groups of the compact 14x14 strips, 111 / 112 for
 the 7x7 ones).  The reference sees plain [Cout][Cin][ks][ks] weights and [F][H][W][C] tensors only; the harness packs with the product's
-packers, so a packing bug fails the same comparison.
+packers, so a packing bug fails the same comparison.  The conv2_se lines with se=1 - conv2 with the SE tail in its epilogue - are a case family
+of their own, with their own operation and bound: "conv2 with the SE tail in its epilogue" at the end of this file.
 
 The operation (csrc/kernels_arc.hip, "Fused epilogues"), restated here in float64:
     acc  = conv(x, w)                                  zero padding, stride and kernel size of the description
@@ -58,18 +59,25 @@ Case = collections.namedtuple("Case", "id shape desc F cls label")
 Geometry = collections.namedtuple("Geometry", "H Cin Ho Cout ks stride mode sc_kind sc_h sc_stride Csc")
 
 
-def plan_lines():
-    """The selected lines of the plan golden, in file order."""
-    out = []
+def _plan():
+    """(PlanLine, the line's se flag) of every line of the plan golden, in file order."""
     for line in open(PLAN).read().splitlines():
         chans, hw, s, desc, rng, rest = line.split(" ", 5)
         cin, depth = (int(v) for v in chans.split("->"))
         shape = SHAPES.index((cin, depth, int(hw.split("x")[0]), int(s[1:])))
         label = rest[:rest.rindex(" scx=")]
         first, last = (int(v) for v in rng[2:].split(".."))
-        if desc in SELECTED:
-            assert rest.endswith("se=0"), line  # the fused SE epilogue is never run alone
-            out.append(PlanLine(shape, desc, first, last, label))
+        assert rest.endswith(("se=0", "se=1")), line
+        yield PlanLine(shape, desc, first, last, label), rest.endswith("se=1")
+
+
+def plan_lines():
+    """The selected lines of the plan golden, in file order."""
+    out = []
+    for ln, se in _plan():
+        if ln.desc in SELECTED:
+            assert not se, ln  # the fused SE epilogue is a case family of its own (fused_cases)
+            out.append(ln)
     return out
 
 
@@ -99,6 +107,9 @@ def geometry(shape, desc):
         return Geometry(h, depth, ho, depth, 3, stride, "bn", None, 0, 0, 0)
     if desc == "conv2_scx":
         return Geometry(h, depth, ho, depth, 3, stride, "add", "scx", h, 2, cin)
+    if desc == "conv2_se":  # planned as the plain tail; the strip kernels that carry the SE tail take a shortcut tensor of the output's geometry
+        assert stride == 1 or has_sc_conv
+        return Geometry(h, depth, ho, depth, 3, stride, "add", "sc", ho, 1, 0)
     assert desc == "conv2"
     if shape == 0 or has_sc_conv:  # the input layer wrote the even positions only / the 1x1 launch's output
         return Geometry(h, depth, ho, depth, 3, stride, "add", "sc", ho, 1, 0)
@@ -271,9 +282,9 @@ def exact_case(case, d, ref):
 
 
 def write_case(dirname, case, d):
-    for k in ("x", "sc", "w", "wsc", "p"):
+    for k in ("x", "sc", "w", "wsc", "p", "se", "x0", "sc0"):
         if k in d:
-            want = np.float16 if k in ("x", "sc") else np.float32
+            want = np.float16 if k in ("x", "sc", "x0", "sc0") else np.float32
             assert d[k].dtype == want, (k, d[k].dtype)
             np.ascontiguousarray(d[k]).tofile(os.path.join(dirname, "%s.%s" % (case.id, k)))
 
@@ -500,3 +511,226 @@ def read_small_outputs(dirname, c):
         outs = {k: rd(k, np.float16, (c.F, c.H, c.H, c.C)) for k in ("out0", "out1")}
         outs["gate"] = rd("gate", np.float32, (c.F, c.C))
     return outs, int(res[c.id][1]), res[c.id][2]
+
+
+# ------------------------------------------------------------------------------------------------ conv2 with the SE tail in its epilogue
+# The seven plan lines "conv2_se ... se=1" launch the twin instantiation of their planned kernel with mode EPI_BN_SE (csrc/frt_arc_launches.hpp,
+# arc_unit_schedule): se_tail_epilogue (csrc/frt_se_device.h).  Cases: class A at the first F of each line and at first + 1 (the last strip
+# ragged; one F of each pair odd, so a two-image strip's last strip holds one image); class S once per distinct (twin, unit shape) at first + 1.
+# The operation, from plain [Cout][Cin][3][3] weights and [F][H][W][C] tensors, in float64:
+#     acc = conv(x, w);  r = acc s + b;  res = fp16(r);  mean[f][c] = sum_hw res / HW;  h = relu(W1 mean);  gate = sigmoid(W2 h)
+#     y = res gate + sc;  out0 = fp16(y);  out1 = fp16(y s' + b')  (from the unrounded y);  sc: the unit's shortcut tensor [F][Ho][Wo][C]
+# Class A: the class A inputs of the conv cases and w2 = 0, so that every gate is exactly 1/2 (expf(-0) = 1): res is a multiple of 1/8, y of
+# 1/16, z of 1/32, all exact in fp32 and fp16 - out0 and out1 bit for bit.  fused_exact() asserts the premises on the reference.
+# Class S: x and w in {-1, 0, 1} (acc an exact integer under any K split: the summation is covered by the conv2 lines of the same kernel
+# families), s = U(0.5, 1.5) * sign / sqrt(K / 16) so that res is O(1), b, sc, s', b' as class B, w1 / w2 as class B of small_inputs.  Bound, u = 2^-24:
+#   r     two fp32 roundings (one if contracted):                                 e_r = u (|acc s| + |r|)
+#   res   the fp16 rounding of r.  Where the reference's r lies within e_r of the midpoint of two neighbouring fp16 numbers the device may round
+#         the other way: those elements get e_res = the spacing of fp16 at res (the wider side), every other element e_res = 0
+#   mean  pass 1 adds a lane's 2 NT pixels (two per pixel tile), then four shuffle levels (the 16 pixel lanes of a channel octet), then the
+#         n_parts partial sums in part order: no value passes more than D = 2 NT + 4 + n_parts additions; one division
+#                                                                e_mean = sum e_res / HW + u (D sum(|res| + e_res) / HW + |mean|)
+#             twin                                                   unit shape            NT  strips per image (n_parts)  images per strip   D
+#             conv_s2_kernel<7, 9, true, false>                      64->128 56x56 s2       7   4                           1                 22
+#             conv_s2_kernel<7, 9, true, false>                      128->256 28x28 s2      7   1                           1                 19
+#             conv_patch_kernel<10, 1, 5, false, false, 7, 1, 3, true>  128->128 28x28      7   4                           1                 22
+#             conv_patch_kernel<10, 1, 5, false, false, 4, 1, 3, true>  256->256 14x14      4   2                           1                 14
+#             conv_patch_kernel<10, 1, 5, false, false, 7, 1, 3, true>  256->256 14x14      7   1                           1                 19
+#             conv_s2_kernel<4, 5, true, false>                      256->512 14x14 s2      4   1                           2                 13
+#             conv_patch_kernel<10, 1, 5, false, false, 4, 1, 3, true>  512->512 7x7        4   1                           2                 13
+#         (strip heights from patch_geometry / s2_geometry at these batch sizes: 7 rows of 28, 7 or 14 rows of 14, whole 7x7 images)
+#   fc1, fc2, sigmoid   se_fc1 / se_fc2, the device functions of the stand-alone tail: the terms of small_reference, SE_GATE_ALLOW included
+#   y     e_y = |res| e_gate + gate e_res + e_res e_gate + 2 u (|res gate| + |sc|);  out1 and the fp16 store as for the conv cases.
+# A condition on the class S inputs keeps the bound from hiding a wrong gate (fused_gate_condition): the largest gate bound is at most 2e-3, and
+# in at least 90 % of (pair of images 2k / 2k + 1 - the two a two-image strip holds -, channel) the two reference gates differ by more than 0.02.
+FUSED_DESC = "conv2_se"
+Twin = collections.namedtuple("Twin", "label NT n_parts n_img")
+_S2, _PATCH = "conv_s2_kernel<%d, %d, %s, false>", "conv_patch_kernel<10, 1, 5, false, false, %d, 1, 3, %s>"
+FUSED = {  # (unit shape, planned label) -> the twin that runs and its strips
+    (2, _S2 % (7, 9, "false")): Twin(_S2 % (7, 9, "true"), 7, 4, 1),
+    (4, _S2 % (7, 9, "false")): Twin(_S2 % (7, 9, "true"), 7, 1, 1),
+    (3, _PATCH % (7, "false")): Twin(_PATCH % (7, "true"), 7, 4, 1),
+    (5, _PATCH % (4, "false")): Twin(_PATCH % (4, "true"), 4, 2, 1),
+    (5, _PATCH % (7, "false")): Twin(_PATCH % (7, "true"), 7, 1, 1),
+    (6, _S2 % (4, 5, "false")): Twin(_S2 % (4, 5, "true"), 4, 1, 2),
+    (7, _PATCH % (4, "false")): Twin(_PATCH % (4, "true"), 4, 1, 2),
+}
+# Class S case id -> the draw that is used.  With the BN bias (0.1 N(0, 1), of the size of the pooled means themselves) the share of gate pairs
+# more than 0.02 apart is 0.70 - 0.91 from draw to draw - a bias-free res ~ N(0, 1) gives 0.90 - 0.94 - so each case takes the first draw found
+# that meets fused_gate_condition (shares 0.906 - 0.933); the condition itself is asserted and stays as it is.
+_S_SEED = {"s2_conv2_se_F24_S": "#44", "s3_conv2_se_F57_S": "#24", "s4_conv2_se_F24_S": "#6", "s5_conv2_se_F57_S": "#6", "s5_conv2_se_F113_S": "#12",
+           "s6_conv2_se_F97_S": "#349", "s7_conv2_se_F112_S": "#43"}
+
+
+def fused_plan_lines():
+    return [ln for ln, se in _plan() if ln.desc == FUSED_DESC and se]
+
+
+def fused_twin(case):
+    return next(t for (shape, _), t in FUSED.items() if shape == case.shape and t.label == case.label)
+
+
+def fused_cases():
+    """Case.label is the twin's: the label that must run."""
+    out, seen = [], set()
+    for ln in fused_plan_lines():
+        twin = FUSED[(ln.shape, ln.label)].label
+        assert ln.first + 1 <= ln.last
+        for F in (ln.first, ln.first + 1):
+            out.append(Case("s%d_%s_F%d_A" % (ln.shape, ln.desc, F), ln.shape, ln.desc, F, "A", twin))
+        if (twin, ln.shape) not in seen:
+            seen.add((twin, ln.shape))
+            out.append(Case("s%d_%s_F%d_S" % (ln.shape, ln.desc, ln.first + 1), ln.shape, ln.desc, ln.first + 1, "S", twin))
+    return out
+
+
+def fused_inputs(case):
+    """The arrays of inputs(), 'se' (fp32: w1 [C/16][C] then w2 [C][C/16]) and the primer launch's tensors 'x0' / 'sc0'."""
+    g = geometry(case.shape, case.desc)
+    F, C, R_ = case.F, g.Cout, g.Cout // 16
+    r = lambda what: _rng(case.id, what + _S_SEED.get(case.id, ""))
+    w1 = (r("w1").standard_normal((R_, C)) / np.sqrt(C)).astype(np.float32)
+    if case.cls == "A":
+        d = inputs(case)
+        w2 = np.zeros((C, R_), np.float32)
+    else:
+        d = {"x": _ternary(r("x"), (F, g.H, g.H, g.Cin)), "w": _ternary(r("w"), (C, g.Cin, 3, 3)).astype(np.float32),
+             "sc": r("sc").standard_normal((F, g.sc_h, g.sc_h, C), dtype=np.float32).astype(np.float16)}
+        p = np.zeros((6, C), np.float32)
+        p[0] = r("s").uniform(0.5, 1.5, C) * r("sg").choice([-1.0, 1.0], C) / np.sqrt(9 * g.Cin / 16.0)
+        p[1] = 0.1 * r("b").standard_normal(C)
+        p[2] = r("s2").uniform(0.5, 1.5, C)
+        p[3] = 0.1 * r("b2").standard_normal(C)
+        d["p"] = p
+        w1 *= 8
+        w2 = (r("w2").standard_normal((C, R_)) * 4 / np.sqrt(R_)).astype(np.float32)
+    d["se"] = np.concatenate([w1.reshape(-1), w2.reshape(-1)])
+    d["x0"] = _ternary(r("x0"), d["x"].shape)
+    d["sc0"] = _ternary(r("sc0"), d["sc"].shape)
+    return d
+
+
+def fused_reference(case, d, bound=False, acc=None, swap_gates=False, pool_hw=None):
+    """float64 reference of one fused launch: out0 / out1 unrounded, acc, res, sum, gate; bound=True adds e_gate, bound0 / bound1.  The last two
+    arguments make it WRONG on purpose, for the test of the comparison: the gates of images 2k and 2k + 1 swapped; a pooled mean divided by
+    pool_hw instead of HW."""
+    g = geometry(case.shape, case.desc)
+    F, C, R_, HW = case.F, g.Cout, g.Cout // 16, g.Ho * g.Ho
+    p = d["p"].astype(np.float64)
+    if acc is None:
+        acc = conv64(d["x"], d["w"].astype(np.float16), g.stride, 1, dtype=np.float32)  # ternary operands (asserted there): exact
+    r = acc * p[0] + p[1]
+    assert np.abs(acc).max() < 2 ** 24 and np.abs(r).max() < 2 ** 15
+    r16 = r.astype(np.float16)
+    res = r16.astype(np.float64)
+    sc = d["sc"].astype(np.float64)
+    w1 = d["se"][:R_ * C].astype(np.float64).reshape(R_, C)
+    w2 = d["se"][R_ * C:].astype(np.float64).reshape(C, R_)
+    ssum = res.reshape(F, HW, C).sum(1)
+    mean = ssum / (pool_hw or HW)
+    h = np.maximum(mean @ w1.T, 0)
+    gate = 1 / (1 + np.exp(-(h @ w2.T)))
+    if swap_gates:
+        n = F // 2 * 2
+        gate = np.concatenate([gate[:n].reshape(-1, 2, C)[:, ::-1].reshape(n, C), gate[n:]])
+    gb = gate[:, None, None, :]
+    y = res * gb + sc
+    z = y * p[2] + p[3]
+    out = {"acc": acc, "r": r, "res": res, "sum": ssum, "gate": gate, "out0": y, "out1": z}
+    if bound:
+        t = fused_twin(case)
+        D = 2 * t.NT + 4 + t.n_parts
+        e_r = WIDE * U * (np.abs(acc * p[0]) + np.abs(r))
+        up = np.nextafter(r16, np.float16(np.inf)).astype(np.float64)
+        dn = np.nextafter(r16, np.float16(-np.inf)).astype(np.float64)
+        near = np.minimum(np.abs(r - (res + up) / 2), np.abs(r - (res + dn) / 2)) <= e_r
+        e_res = np.where(near, np.maximum(up - res, res - dn), 0.0)
+        pool = lambda v: v.reshape(F, HW, C).sum(1) / HW
+        e_mean = WIDE * (pool(e_res) + U * (D * pool(np.abs(res) + e_res) + np.abs(mean)))
+        G = 4096 // C
+        e_h = e_mean @ np.abs(w1).T + (max(C // G, 1) + int(np.log2(G)) + 1) * U * (np.abs(mean) @ np.abs(w1).T)
+        e_o = e_h @ np.abs(w2).T + (R_ + 1) * U * (h @ np.abs(w2).T)
+        e_gate = e_o / 4 + SE_GATE_ALLOW
+        eg = e_gate[:, None, None, :]
+        e_y = WIDE * (np.abs(res) * eg + gb * e_res + e_res * eg + 2 * U * (np.abs(res * gb) + np.abs(sc)))
+        e_z = e_y * np.abs(p[2]) + 2 * U * (np.abs(y * p[2]) + np.abs(p[3]) + e_y * np.abs(p[2]))
+        out.update(e_gate=e_gate, flipped=int(near.sum()), bound0=_store_bound(y, e_y), bound1=_store_bound(z, e_z))
+    return out
+
+
+def fused_exact(case, d, ref):
+    """The premises of class A, asserted on the reference alone; returns the outputs as fp16 arrays.  acc is an integer (conv64 asserted the
+    operands), s and s' are powers of two >= 1/8, b and b' multiples of 1/4: r is a multiple of 1/8 that fp16 holds (res = r); every partial
+    sum of the pooling, in any order, is a multiple of 1/8 no larger than sum|res| < 2^21: exact in fp32; w2 = 0 makes every fc2 sum 0 whatever
+    the mean's last bit and the gate 1 / (1 + 1) = 1/2; y = res / 2 + sc and z = y s' + b' are multiples of 1/16 and 1/32 below 2^7 and 2^6,
+    exact in fp32 in either rounding mode of the multiply-add, and unchanged by the store."""
+    assert case.cls == "A"
+    p = d["p"].astype(np.float64)
+    C = p.shape[1]
+    assert np.abs(ref["acc"]).max() < 2 ** 24, case.id
+    for k in (0, 2):
+        assert np.array_equal(np.log2(np.abs(p[k])), np.rint(np.log2(np.abs(p[k])))) and (np.abs(p[k]) >= 2.0 ** -3).all(), (case.id, k)
+    for k in (1, 3):
+        assert np.array_equal(p[k] * 4, np.rint(p[k] * 4)), (case.id, k)
+    assert np.array_equal(ref["res"], ref["r"]) and np.array_equal(ref["r"] * 8, np.rint(ref["r"] * 8)), case.id
+    assert np.abs(ref["res"]).reshape(case.F, -1, C).sum(1).max() < 2 ** 21, case.id  # pooled sums exact in fp32
+    assert not d["se"][C // 16 * C:].any() and np.all(ref["gate"] == 0.5), case.id
+    assert np.abs(ref["out0"]).max() < 2 ** 7 and np.abs(ref["out1"]).max() < 2 ** 6, (case.id, np.abs(ref["out0"]).max(), np.abs(ref["out1"]).max())
+    out = {}
+    for k in ("out0", "out1"):
+        out[k] = ref[k].astype(np.float16)
+        assert np.array_equal(out[k], ref[k]), (case.id, k)
+    return out
+
+
+def fused_gate_condition(case, ref):
+    """(largest gate bound, share of (image pair, channel) whose two reference gates differ by more than 0.02), asserted: the class S inputs
+    are such that the bound cannot hide a gate taken from the neighbouring image."""
+    n = case.F // 2 * 2
+    pairs = ref["gate"][:n].reshape(-1, 2, ref["gate"].shape[1])
+    share = float((np.abs(pairs[:, 0] - pairs[:, 1]) > 0.02).mean())
+    worst = float(ref["e_gate"].max())
+    assert worst <= 2e-3 and share >= 0.9, (case.id, worst, share)
+    return worst, share
+
+
+def compare_outputs(cls, want, outs):
+    """Failure messages ([] = passed) of the outputs `outs` (fp16 arrays) against `want` - class A: fp16 arrays, bit for bit; otherwise (float64
+    reference, bound) per output - and max(err / bound) (None for class A)."""
+    bad, ratio = [], None
+    for k in sorted(want):
+        if k not in outs:
+            bad.append("%s was not written" % k)
+        elif cls == "A":
+            ne = outs[k].view(np.uint16) != want[k].view(np.uint16)
+            if ne.any():
+                i = tuple(int(v) for v in np.argwhere(ne)[0])
+                bad.append("%s: %d of %d values differ, first at [f, oh, ow, c] = %s: %r, reference %r" % (k, ne.sum(), ne.size, i, float(outs[k][i]), float(want[k][i])))
+        else:
+            ref, bound = want[k]
+            err = np.abs(outs[k].astype(np.float64) - ref)
+            ratio = max(ratio or 0.0, float((err / bound).max()))
+            if not (err <= bound).all():  # (also catches a NaN)
+                i = tuple(int(v) for v in np.argwhere(~(err <= bound))[0])
+                bad.append("%s: %d values outside the bound, first at %s: %r, reference %r, bound %.3g" % (k, (~(err <= bound)).sum(), i, float(outs[k][i]), ref[i], bound[i]))
+    if set(outs) - set(want):
+        bad.append("unexpected outputs %s" % sorted(set(outs) - set(want)))
+    return bad, ratio
+
+
+FusedRun = collections.namedtuple("FusedRun", "outs label fits n_parts slack outside unwritten counters flags repeat")
+
+
+def read_fused_outputs(dirname, case):
+    """What the harness wrote for one fused case, or None when it did not reach the case."""
+    path = os.path.join(dirname, "results.txt")
+    res = {ln.split("\t")[0]: ln.split("\t")[1:] for ln in open(path).read().splitlines()} if os.path.exists(path) else {}
+    if case.id not in res:
+        return None
+    g = geometry(case.shape, case.desc)
+    outs = {}
+    for k in ("out0", "out1"):
+        f = os.path.join(dirname, "%s.%s" % (case.id, k))
+        if os.path.exists(f):
+            outs[k] = np.fromfile(f, np.float16).reshape(case.F, g.Ho, g.Ho, g.Cout)
+    return FusedRun(outs, res[case.id][0], *(int(v) for v in res[case.id][1:]))

@@ -5,7 +5,7 @@
 // weights.
 //
 //   arc_launch_check DIR          run every case of DIR/cases.txt on the current device; stops at the first HIP error (exit 1)
-//   arc_launch_check --plan DIR   print "<id>\t<label>" per case; no HIP call (runs on a machine without a device)
+//   arc_launch_check --plan DIR   print "<id>\t<label>" per case (conv2_se: the twin that runs); no HIP call (runs on a machine without a device)
 //
 // DIR/cases.txt: one line per case.  "conv <id> <unit shape 0..7> <description 0..5> <F>" is a conv launch, with the little-endian arrays
 //   <id>.x    fp16 [F][H][W][Cin]                   <id>.w    fp32 [Cout][Cin][ks][ks]
@@ -13,6 +13,11 @@
 //   <id>.wsc  fp32 [Cout][Csc] (fused shortcut conv only)
 //   <id>.p    fp32 [6][Cout]: p0 p1 p2 p3 psc0 psc1
 // Written: <id>.out0 / <id>.out1 (fp16, the logical tensors) and one line "<id>\t<changed slack elements>\t<label>" in DIR/results.txt.
+// Description 3 (conv2_se) is the IR-SE conv2 with the whole SE tail in its epilogue (run_conv_se below), with three more arrays
+//   <id>.se   fp32 fc1 weights [Cout/16][Cout], then fc2 weights [Cout][Cout/16]
+//   <id>.x0 / <id>.sc0   fp16, the tensors of the primer launch (the geometry of <id>.x / <id>.sc, other values)
+// and the line "<id>\t<twin label>\t<conv_se_fits_device>\t<n_parts>\t<changed slack halves>\t<changed scratch words outside the partial sums,
+// counters and flags>\t<partial sums not written>\t<counters not zero>\t<flags not at the epoch>\t<halves the third launch wrote differently>".
 // The three small launches go through the same buffers and checks (label: the launcher's name):
 //   "input <id> <F>"                   launch_arc_input: <id>.x fp32 [F][3][112][112], <id>.w fp32 [64][27], <id>.p fp32 [5][64] s0 b0 slope s1 b1
 //                                      -> out0 = z [F][112][112][64], out1 = y [F][56][56][64] (the even positions)
@@ -149,15 +154,28 @@ struct DeviceCase {
         HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
         return d;
     }
-    // the logical tensor -> `path` (empty: not kept); returns the number of elements outside it that no longer hold the fill pattern
     template <class T>
-    size_t download(const Buf<T> &b, const std::string &path) {
+    std::vector<T> fetch(const Buf<T> &b) {  // margin and slack included
         std::vector<T> h(b.margin + b.cap);
         HIPCHK(hipMemcpy(h.data(), b.base, h.size() * sizeof(T), hipMemcpyDeviceToHost));
+        return h;
+    }
+    template <class T>
+    void refill(const Buf<T> &b) {
+        if (sizeof(T) == 2)
+            HIPCHK(hipMemsetD16(reinterpret_cast<hipDeviceptr_t>(b.base), (unsigned short)b.fill, b.margin + b.cap));
+        else
+            HIPCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b.base), (int)b.fill, b.margin + b.cap));
+    }
+    // the logical tensor -> `path` (empty: not kept); returns the number of elements outside it that no longer hold the fill pattern
+    template <class T>
+    size_t download(const Buf<T> &b, const std::string &path, std::vector<T> *keep = nullptr) {
+        std::vector<T> h = fetch(b);
         if (!path.empty()) write_file(path, h.data() + b.margin, b.logical * sizeof(T));
         size_t changed = 0;
         for (size_t i = 0; i < b.margin; ++i) changed += h[i] != b.fill;
         for (size_t i = b.margin + b.logical; i < h.size(); ++i) changed += h[i] != b.fill;
+        if (keep) keep->assign(h.begin() + b.margin, h.begin() + b.margin + b.logical);
         return changed;
     }
 };
@@ -166,7 +184,6 @@ void run_conv(const std::string &dir, const Case &c, FILE *results) {
     const Shape &u = kShapes[c.shape];
     ConvMfmaArgs a;
     if (!describe(u, c.shape == 0, c.d, c.F, a)) die("case " + c.id + ": the unit has no such launch");
-    if (c.d == 3) die("case " + c.id + ": the fused SE epilogue is not run alone");
     const std::string pre = dir + "/" + c.id;
     DeviceCase dc;
     dc.id = c.id;
@@ -237,6 +254,93 @@ void finish(DeviceCase &dc, const std::string &id) {
     HIPCHK(hipGetLastError());
 }
 
+// IR-SE conv2 with the SE tail in its epilogue (csrc/frt_se_device.h), launched the way arc_unit_schedule (csrc/frt_arc_launches.hpp) builds it:
+// the arc_conv2_se description is planned, the plan must offer the tail, then the mode becomes EPI_BN_SE and the plan moves to its twin.  The SE
+// scratch is the embedder's (alloc_act_set): [4][F][512] partial sums, F arrival counters, F gate-ready flags - here behind a margin and, but for
+// the zeroed counters and flags, filled with a pattern.  Three launches on the same scratch and outputs, which is what consecutive units of
+// a pass are: a primer with other tensors at epoch e (a workgroup of the next launch that accepted a stale flag, or read the partial sums before
+// every part had arrived, would pool the primer's values or the pattern), the case at e + 1, and the case again at e + 2, which must write the
+// same bits (the gate does not depend on arrival order).  A raised error word ends the process like a HIP error.
+void run_conv_se(const std::string &dir, const Case &c, FILE *results) {
+    constexpr int kEpoch = 7;
+    const Shape &u = kShapes[c.shape];
+    ConvMfmaArgs a;
+    if (!describe(u, c.shape == 0, ARC_CONV2_SE, c.F, a)) die("case " + c.id + ": the unit has no such launch");
+    const std::string pre = dir + "/" + c.id, &id = c.id;
+    DeviceCase dc;
+    dc.id = c.id;
+    const size_t F = (size_t)c.F, C = (size_t)a.Cout, big = F * 112 * 112 * 64, sc_cap = F * 28 * 28 * 128;  // alloc_act_set: Y / Z / T, and SC
+    const size_t nx = F * a.H * a.W * a.Cin, nout = F * a.Ho * a.Wo * C, nsc = F * a.sc_h * a.sc_w * C;
+    const std::vector<uint16_t> x = read_file<uint16_t>(pre + ".x", nx), x0 = read_file<uint16_t>(pre + ".x0", nx);
+    const std::vector<uint16_t> sc = read_file<uint16_t>(pre + ".sc", nsc), sc0 = read_file<uint16_t>(pre + ".sc0", nsc);
+    const std::vector<float> w = read_file<float>(pre + ".w", C * a.Cin * 9), par = read_file<float>(pre + ".p", 6 * C), se = read_file<float>(pre + ".se", 2 * (C / 16) * C);
+    const ActBuf dx = dc.act(big, nx, kInFill, &x0), dsc = dc.act(u.cin != u.depth ? sc_cap : big, nsc, kInFill, &sc0);
+    a.x = dx.ptr<half_t>();
+    a.sc = dsc.ptr<half_t>();
+    a.w = reinterpret_cast<half_t *>(dc.upload(frt::conv_w_f16(w.data(), a.Cout, a.Cin, a.ks)));
+    if (a.wf) a.wf = reinterpret_cast<half_t *>(dc.upload(frt::conv_w_f16_frag(w.data(), a.Cout, a.Cin)));
+    if (a.wf2) a.wf2 = reinterpret_cast<half_t *>(dc.upload(frt::conv_w_f16_frag(w.data(), a.Cout, a.Cin, u.depth != 64)));
+    float *dpar = dc.upload(par), *dse = dc.upload(se);
+    a.p0 = dpar; a.p1 = dpar + C; a.p2 = dpar + 2 * C; a.p3 = dpar + 3 * C;
+    a.se_w1 = dse;
+    a.se_w2 = dse + (C / 16) * C;
+    a.zeros = reinterpret_cast<half_t *>(dc.upload(std::vector<uint16_t>(256, 0)));
+    const size_t pool_words = F * 512 * 4;
+    const Buf<uint32_t> scratch = dc.buf<uint32_t>(pool_words + 2 * F, pool_words + 2 * F, kOutFill32, nullptr);
+    HIPCHK(hipMemset(scratch.ptr<uint32_t>() + pool_words, 0, 2 * F * sizeof(uint32_t)));
+    a.se_pool = scratch.ptr<float>();
+    a.se_counter = scratch.ptr<int>() + pool_words;
+    a.se_flag_off = c.F;
+    struct Mapped {  // the error word: mapped host memory, as frt_embedder::build() allocates it
+        int *host = nullptr;
+        ~Mapped() { (void)hipHostFree(host); }
+    } err;
+    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&err.host), sizeof(int), hipHostMallocMapped));
+    *err.host = 0;
+    HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void **>(&a.se_error), err.host, 0));
+    const ActBuf o0 = dc.act(big, nout, kOutFill, nullptr), o1 = dc.act(big, nout, kOutFill, nullptr);
+    a.out0 = o0.ptr<half_t>();
+    a.out1 = o1.ptr<half_t>();
+
+    ConvPlan plan = conv_plan(a);
+    if (!plan.se_fused()) die("case " + c.id + ": planned as " + plan.label + ", which has no twin with the SE tail");
+    a.mode = EPI_BN_SE;
+    plan.take_se_tail();
+    const int n_parts = plan.n_img == 1 ? (a.Ho + plan.R - 1) / plan.R : 1;  // strips of one image: the parts its channel sums arrive in
+    if (!conv_se_fits_device()) {  // the embedder would run the stand-alone tail here: nothing is launched, the test reports it
+        fprintf(results, "%s\t%s\t0\t%d\t0\t0\t0\t0\t0\t0\n", c.id.c_str(), plan.label, n_parts);
+        return;
+    }
+    size_t slack = 0, outside = 0, unwritten = 0, counters = 0, flags = 0;
+    auto launch = [&](int epoch, const std::string &keep, std::vector<uint16_t> *y, std::vector<uint16_t> *z) {
+        a.se_epoch = epoch;
+        launch_conv_mfma(a, plan, nullptr);
+        finish(dc, id);
+        if (*err.host) die("case " + c.id + ": a hand-over wait of the SE tail timed out (error word " + std::to_string(*err.host) + ", epoch " + std::to_string(epoch) + ")");
+        if (y) slack += dc.download(o0, keep.empty() ? keep : keep + ".out0", y) + dc.download(o1, keep.empty() ? keep : keep + ".out1", z);
+        const std::vector<uint32_t> h = dc.fetch(scratch);
+        const uint32_t *s = h.data() + scratch.margin;
+        const size_t live = n_parts * F * C;  // se_pool[part][face][channel]: every word written, none behind them
+        for (size_t i = 0; i < scratch.margin; ++i) outside += h[i] != kOutFill32;
+        for (size_t i = 0; i < live; ++i) unwritten += s[i] == kOutFill32;
+        for (size_t i = live; i < pool_words; ++i) outside += s[i] != kOutFill32;
+        for (size_t f = 0; f < F; ++f) counters += s[pool_words + f] != 0, flags += s[pool_words + F + f] != (uint32_t)epoch;
+    };
+    launch(kEpoch, "", nullptr, nullptr);
+    HIPCHK(hipMemcpy(dx.ptr<void>(), x.data(), nx * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dsc.ptr<void>(), sc.data(), nsc * 2, hipMemcpyHostToDevice));
+    dc.refill(o0);
+    dc.refill(o1);
+    std::vector<uint16_t> y2, z2, y3, z3;
+    launch(kEpoch + 1, pre, &y2, &z2);
+    dc.refill(o0);
+    dc.refill(o1);
+    launch(kEpoch + 2, "", &y3, &z3);
+    size_t repeat = 0;
+    for (size_t i = 0; i < nout; ++i) repeat += (y2[i] != y3[i]) + (z2[i] != z3[i]);
+    fprintf(results, "%s\t%s\t1\t%d\t%zu\t%zu\t%zu\t%zu\t%zu\t%zu\n", c.id.c_str(), plan.label, n_parts, slack, outside, unwritten, counters, flags, repeat);
+}
+
 void run_input(const std::string &dir, const Case &c, FILE *results) {
     const std::string pre = dir + "/" + c.id, &id = c.id;
     DeviceCase dc;
@@ -301,7 +405,8 @@ void run_se(const std::string &dir, const Case &c, FILE *results) {
 }
 
 void run_case(const std::string &dir, const Case &c, FILE *results) {
-    if (c.kind == "conv") run_conv(dir, c, results);
+    if (c.kind == "conv" && c.d != ARC_CONV2_SE) run_conv(dir, c, results);
+    if (c.kind == "conv" && c.d == ARC_CONV2_SE) run_conv_se(dir, c, results);
     if (c.kind == "input") run_input(dir, c, results);
     if (c.kind == "fc") run_fc(dir, c, results);
     if (c.kind == "se") run_se(dir, c, results);
@@ -320,7 +425,9 @@ int main(int argc, char **argv) {
             ConvMfmaArgs a;
             if (c.kind != "conv") continue;  // only the convs are planned
             if (!describe(kShapes[c.shape], c.shape == 0, c.d, c.F, a)) die("case " + c.id + ": the unit has no such launch");
-            printf("%s\t%s\n", c.id.c_str(), conv_plan(a).label);
+            const ConvPlan p = conv_plan(a);
+            if (c.d == ARC_CONV2_SE && !p.se_fused()) die("case " + c.id + ": planned as " + p.label + ", which has no twin with the SE tail");
+            printf("%s\t%s\n", c.id.c_str(), c.d == ARC_CONV2_SE ? p.se_label : p.label);  // the fused launch runs the twin
         }
         return 0;
     }

@@ -5,6 +5,7 @@ normalisation; here each selected line of tests/golden/arc_conv_plan.txt runs on
   * class A (exact inputs): out0 and out1 equal the reference bit for bit;
   * class B (realistic inputs): every element is inside the error bound derived in arc_launch_ref's docstring; max(err / bound) is printed;
   * no half outside an output's logical tensor has changed (the buffers have the embedder's sizes, with a margin in front).
+The seven conv2_se lines with se=1 run as the twin instantiation with the whole SE tail in its epilogue (test_fused_se_launches_alone).
 One harness process per unit shape, each under its own timeout.  A process that ends on a HIP error ends the module: the remaining
 parameters fail with its message and launch nothing."""
 import shutil
@@ -26,28 +27,13 @@ def harness(tmp_path_factory):
 
 def _compare(case, want, outs, changed, label):
     """Failure messages of one case ([] = passed) and, for class B, max(err / bound)."""
-    bad, ratio = [], None
+    bad = []
     if label != case.label:
         bad.append("planned %s, the plan golden says %s" % (label, case.label))
     if changed:
         bad.append("%d halves outside the logical output changed" % changed)
-    for k in sorted(want):
-        if k not in outs:
-            bad.append("%s was not written" % k)
-        elif case.cls == "A":
-            ne = outs[k].view(np.uint16) != want[k].view(np.uint16)
-            if ne.any():
-                i = tuple(int(v) for v in np.argwhere(ne)[0])
-                bad.append("%s: %d of %d values differ, first at [f, oh, ow, c] = %s: %r, reference %r" % (k, ne.sum(), ne.size, i, float(outs[k][i]), float(want[k][i])))
-        else:
-            ref, bound = want[k]
-            err = np.abs(outs[k].astype(np.float64) - ref)
-            ratio = max(ratio or 0.0, float((err / bound).max()))
-            if not (err <= bound).all():  # (also catches a NaN)
-                i = tuple(int(v) for v in np.argwhere(~(err <= bound))[0])
-                bad.append("%s: %d values outside the bound, first at %s: %r, reference %r, bound %.3g" % (k, (~(err <= bound)).sum(), i, float(outs[k][i]), ref[i], bound[i]))
-    if set(outs) - set(want):
-        bad.append("unexpected outputs %s" % sorted(set(outs) - set(want)))
+    more, ratio = R.compare_outputs(case.cls, want, outs)
+    bad += more
     return bad, ratio
 
 
@@ -152,3 +138,85 @@ def test_small_launches_alone(kind, harness, tmp_path):
         assert not failures, "\n".join(failures[:40])
     finally:
         shutil.rmtree(str(work), ignore_errors=True)
+
+
+_ran_fused = {}  # unit shape -> (twin label, F) of the fused cases that ran and passed
+FUSED_SHAPES = sorted({ln.shape for ln in R.fused_plan_lines()})
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("shape", FUSED_SHAPES, ids=["%d-%d_%dx%d_s%d" % (R.SHAPES[s][:3] + R.SHAPES[s][2:]) for s in FUSED_SHAPES])
+def test_fused_se_launches_alone(shape, harness, tmp_path):
+    """conv2 with the whole SE tail in its epilogue (se_tail_epilogue, csrc/frt_se_device.h), built the way arc_unit_schedule builds it and launched
+    alone (arc_launch_ref, "conv2 with the SE tail in its epilogue"): behind a primer launch with other tensors on the same scratch, class A bit
+    for bit, class S inside its derived bound (max(err / bound) is printed), nothing outside the logical outputs, the partial sums, the counters
+    and the flags written, every counter back at zero, every flag at the launch's epoch, and a third launch that writes the same bits."""
+    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    cases = [c for c in R.fused_cases() if c.shape == shape]
+    work = tmp_path / "cases"
+    work.mkdir()
+    want = {}
+    try:
+        for c in cases:
+            d = R.fused_inputs(c)
+            ref = R.fused_reference(c, d, bound=c.cls == "S")
+            if c.cls == "A":
+                want[c.id] = R.fused_exact(c, d, ref)
+            else:
+                R.fused_gate_condition(c, ref)
+                want[c.id] = {k: (ref[k], ref["bound" + k[-1]]) for k in ("out0", "out1")}
+            R.write_case(str(work), c, d)
+        R.write_manifest(str(work), cases)
+        try:
+            run = subprocess.run([harness, str(work)], capture_output=True, text=True, timeout=300)
+            if run.returncode != 0:
+                _stopped.append("%s: exit status %d: %s" % (R.SHAPES[shape], run.returncode, run.stderr.strip()[-500:]))
+        except subprocess.TimeoutExpired:
+            _stopped.append("%s: no end after 300 s" % (R.SHAPES[shape],))
+        failures, passed = [], set()
+        for c in cases:
+            got = R.read_fused_outputs(str(work), c)
+            if got is None:
+                failures.append("%s: not reached" % c.id)
+                continue
+            bad = []
+            if got.label != c.label:
+                bad.append("ran %s, the twin of the plan golden's line is %s" % (got.label, c.label))
+            if not got.fits:
+                bad.append("conv_se_fits_device() is false on this device: the fused tail was not launched")
+            if got.n_parts != R.fused_twin(c).n_parts:
+                bad.append("%d strips per image, the derived bound assumes %d" % (got.n_parts, R.fused_twin(c).n_parts))
+            for n, what in ((got.slack, "halves outside a logical output changed"), (got.outside, "scratch words outside the partial sums, counters and flags changed"),
+                            (got.unwritten, "partial sums were not written"), (got.counters, "arrival counters are not back at zero"),
+                            (got.flags, "flags are not at the launch's epoch"), (got.repeat, "halves differ between the second and the third launch")):
+                if n:
+                    bad.append("%d %s" % (n, what))
+            more, ratio = R.compare_outputs(c.cls, want[c.id], got.outs)
+            if ratio is not None:
+                print("%s %s: max(err / bound) = %.3f" % (c.id, c.label, ratio))
+            failures += ["%s (%s): %s" % (c.id, c.label, b) for b in bad + more]
+            if not bad + more:
+                passed.add((got.label, c.F))
+        assert not _stopped, _stopped[0]
+        assert not failures, "%d of %d cases failed:\n%s" % (len({f.split(" ")[0] for f in failures}), len(cases), "\n".join(failures[:40]))
+        _ran_fused[shape] = passed
+    finally:
+        shutil.rmtree(str(work), ignore_errors=True)
+
+
+@pytest.mark.gpu
+def test_every_fused_plan_line_ran():
+    """The twins that ran alone (and passed) are the labels a fused IR-SE pass shows and a stand-alone one does not (tests/golden/arc_conv_labels.json):
+    four of them; and each of the seven se=1 plan lines ran at its first F and at first + 1."""
+    import json
+    import os
+    assert sorted(_ran_fused) == FUSED_SHAPES, "the fused launch checks of some unit shapes did not pass (this test runs behind them)"
+    seqs = json.load(open(os.path.join(R.ROOT, "tests", "golden", "arc_conv_labels.json")))
+    only_fused = {l for k, v in seqs.items() if k.startswith("ir_se fused") for l in v} - {l for k, v in seqs.items() if k.startswith("ir_se standalone") for l in v}
+    assert len(only_fused) == 4
+    assert {label for ran in _ran_fused.values() for label, _ in ran} == only_fused
+    lines = R.fused_plan_lines()
+    assert len(lines) == 7
+    for ln in lines:
+        twin = R.FUSED[(ln.shape, ln.label)].label
+        assert {(twin, ln.first), (twin, ln.first + 1)} <= _ran_fused[ln.shape], ln

@@ -99,13 +99,28 @@ def test_deep_fp32_mode_matches_the_fp32_oracle(frt, synth, deep, tag):
 
 @pytest.mark.parametrize("tag", ["ir_se100", "ir_se152"])
 def test_deep_se_fused_equals_stand_alone_tail(frt, synth, deep, tag):
+    """24 faces: the smallest batches whose IR-SE pass has fused launches (tests/golden/arc_conv_plan.txt: conv2_se ... se=1 from F = 23; at 8 faces
+    both settings plan the same launches).  The profiling labels show that the first pass ran twins with the SE tail and the second none."""
+    import arc_launch_ref
+    twins = {t.label for t in arc_launch_ref.FUSED.values()}
     path, _, _ = deep(tag)
-    x = face_input(synth.make_faces(8))
-    rec = frt.ArcFaceIR50(path, maxBatchSize=8)
-    fused = rec.doInference(x)
+    x = face_input(synth.make_faces(24))
+    rec = frt.ArcFaceIR50(path, maxBatchSize=24)
+
+    def profiled():
+        frt.profile_enable(1)
+        try:
+            emb = rec.doInference(x)
+            labels, _, _ = frt.profile_collect()
+        finally:
+            frt.profile_enable(0)
+        return emb, set(labels)
+
+    fused, fused_labels = profiled()
     rec.setSeFused(False)
-    alone = rec.doInference(x)
+    alone, alone_labels = profiled()
     rec.close()
+    assert fused_labels & twins and not alone_labels & twins, (sorted(fused_labels & twins), sorted(alone_labels & twins))
     assert np.isfinite(fused).all() and np.isfinite(alone).all()
     assert ((fused.astype(np.float64) * alone).sum(1) >= 1 - 1e-5).all()
     assert np.abs(fused - alone).max() < 1e-3
