@@ -1,7 +1,8 @@
 // The launches of one residual unit of the recogniser (model_irse.py:48-90), stated once: which packed weight copies a unit has, the
 // ConvMfmaArgs description of each launch it can make, and the order and form in which one pass makes them.  Host only - no HIP call,
 // every function inline - so frt_embedder::forward(), frt_embedder::warm_strip_tables() and the host programs under tests/cpp compile this
-// very text: what the plan golden, the strip-table dump and the per-launch float64 checks describe is what the product launches.
+// very text: what the plan golden, the strip-table dump and the per-launch float64 checks describe is what the product launches.  The fp32
+// mode's launches (frt_embedder::forward_f32) are described the same way at the end of this file.
 #pragma once
 #include "frt_kernels.h"
 
@@ -175,3 +176,79 @@ inline ArcUnitSchedule arc_unit_schedule(const ArcUnit &u, bool first_unit, cons
     s.add(ARC_CONV2_RES, a, conv_plan(a), flops2 * (double)F * ho * ho);
     return s;
 }
+
+// ---- the fp32 mode (frt_embedder_set_precision(e, 1); kernels_arc_f32.hip).  One unit makes conv1, the 1x1 shortcut where it has one, and
+// conv2 - plain, or (IR-SE) into RES with launch_se32 behind it.  frt_embedder::forward_f32() and tests/cpp/arc32_launch_check.cpp compile
+// this text.  The per-channel parameters are the ArcUnit's fp32 arrays; the weights are this mode's own packed copies.
+struct Arc32Weights {
+    float *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;  // [Cout][tap][Cin] fp32 in conv32_kernel's fragment order (frt::conv32_w_frag)
+};
+// the activation buffers of the mode, in floats, for passes of up to `chunk` faces (frt_embedder::build_f32)
+struct Arc32BufferSizes {
+    size_t act, sc, res, gate, fc_out;  // A[0] / A[1] / T; the 1x1 shortcut launch's output; RES; the SE gates; the Linear's sums
+};
+inline Arc32BufferSizes arc32_buffer_sizes(int chunk) {
+    const size_t C = (size_t)chunk;
+    return {C * 112 * 112 * 64, C * 56 * 56 * 128, C * 56 * 56 * 64, C * 512, C * 512};
+}
+struct Arc32Buffers {
+    const float *x;                // the unit's raw input (its leading BatchNorm is applied by conv1 on load)
+    const float *lead_s, *lead_b;  // that BatchNorm
+    float *T, *SC, *RES, *gate;    // conv1's output; the 1x1 shortcut launch's; IR-SE: BN(conv2); the SE gates [F][C]
+    float *y;                      // the unit's output
+};
+enum Arc32Desc { ARC32_CONV1, ARC32_SHORTCUT1X1, ARC32_CONV2, ARC32_CONV2_RES, ARC32_NUM_DESC };
+
+// conv1: BN(x) (on load; the zero padding pads the normalised tensor) -> conv3x3 s1 -> PReLU
+inline bool arc32_conv1(const ArcUnit &u, const Arc32Weights &w, const Arc32Buffers &b, int F, Conv32Args &a) {
+    const int h = u.h_in;
+    a = Conv32Args{b.x, w.w1, b.lead_s, b.lead_b, b.T, F, h, h, u.cin, h, h, u.depth, 3, 1, 1, 0, u.prelu, nullptr, nullptr, 0, 0, 0};
+    return true;
+}
+// conv1x1 stride s + BN on the raw input, into SC
+inline bool arc32_shortcut1x1(const ArcUnit &u, const Arc32Weights &w, const Arc32Buffers &b, int F, Conv32Args &a) {
+    if (!w.wsc) return false;
+    const int h = u.h_in, ho = h / u.stride;
+    a = Conv32Args{b.x, w.wsc, nullptr, nullptr, b.SC, F, h, h, u.cin, ho, ho, u.depth, 1, u.stride, 0, 1, u.ssc, u.bsc, nullptr, 0, 0, 0};
+    return true;
+}
+// the unit's shortcut tensor: MaxPool2d(1, stride) of the raw input, or the 1x1 launch's output
+struct Arc32Shortcut {
+    const float *sc;
+    int sc_h, sc_stride;
+};
+inline Arc32Shortcut arc32_shortcut(const ArcUnit &u, const Arc32Weights &w, const Arc32Buffers &b) {
+    if (w.wsc) return {b.SC, u.h_in / u.stride, 1};
+    return {b.x, u.h_in, u.stride};
+}
+// conv2 as the plain unit tail: conv3x3 stride s -> BN -> + shortcut
+inline bool arc32_conv2(const ArcUnit &u, const Arc32Weights &w, const Arc32Buffers &b, int F, Conv32Args &a) {
+    const int h = u.h_in, ho = h / u.stride;
+    const Arc32Shortcut sc = arc32_shortcut(u, w, b);
+    a = Conv32Args{b.T, w.w2, nullptr, nullptr, b.y, F, h, h, u.depth, ho, ho, u.depth, 3, u.stride, 1, 2, u.s2f32, u.b2, sc.sc, sc.sc_h, sc.sc_h, sc.sc_stride};
+    return true;
+}
+// IR-SE: conv2 + BN into RES, launch_se32 behind it
+inline bool arc32_conv2_res(const ArcUnit &u, const Arc32Weights &w, const Arc32Buffers &b, int F, Conv32Args &a) {
+    if (!u.se_w1) return false;
+    const int h = u.h_in, ho = h / u.stride;
+    a = Conv32Args{b.T, w.w2, nullptr, nullptr, b.RES, F, h, h, u.depth, ho, ho, u.depth, 3, u.stride, 1, 1, u.s2f32, u.b2, nullptr, 0, 0, 0};
+    return true;
+}
+typedef bool (*Arc32DescribeFn)(const ArcUnit &, const Arc32Weights &, const Arc32Buffers &, int F, Conv32Args &);
+constexpr Arc32DescribeFn kArc32Describe[ARC32_NUM_DESC] = {arc32_conv1, arc32_shortcut1x1, arc32_conv2, arc32_conv2_res};
+
+// the arguments of launch_se32, in its order: y = RES * gate + shortcut
+struct Se32Args {
+    const float *res, *w1, *w2;
+    float *gate;
+    const float *sc;
+    float *out;
+    int F, Ho, Wo, C, sc_h, sc_w, sc_stride;
+};
+inline Se32Args arc32_se(const ArcUnit &u, const Arc32Weights &w, const Arc32Buffers &b, int F) {
+    const int ho = u.h_in / u.stride;
+    const Arc32Shortcut sc = arc32_shortcut(u, w, b);
+    return {b.RES, u.se_w1, u.se_w2, b.gate, sc.sc, b.y, F, ho, ho, u.depth, sc.sc_h, sc.sc_h, sc.sc_stride};
+}
+inline void launch_se32(const Se32Args &a, hipStream_t s) { launch_se32(a.res, a.w1, a.w2, a.gate, a.sc, a.out, a.F, a.Ho, a.Wo, a.C, a.sc_h, a.sc_w, a.sc_stride, s); }

@@ -1,6 +1,6 @@
-// Host-side weight packers of the recogniser: plain fp32 weights -> the fp16 layouts its kernels read.  Host only (no HIP call): used by
-// frt_embedder::build() and, so that a packing bug shows against a reference that only ever sees plain weights, by the stand-alone launch
-// harness (tests/cpp/arc_launch_check.cpp).
+// Host-side weight packers of the recogniser: plain fp32 weights -> the fp16 layouts its kernels read (and, at the end, the fp32 mode's).
+// Host only (no HIP call): used by frt_embedder::build() / build_f32() and, so that a packing bug shows against a reference that only ever
+// sees plain weights, by the stand-alone launch harnesses (tests/cpp/arc_launch_check.cpp, tests/cpp/arc32_launch_check.cpp).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -69,6 +69,33 @@ inline std::vector<uint16_t> fc_w_f16_frag(const float *src) {
                 const size_t off = ((((size_t)(o >> 5) * (25088 / 16) + (k >> 4)) * 64) + ((k >> 3) & 1) * 32 + (o & 31)) * 8 + (k & 7);
                 w[off] = f32_to_f16(src[(size_t)o * 25088 + (size_t)c * 49 + hw]);
             }
+    return w;
+}
+
+}  // namespace frt
+
+// ---- the fp32 mode (kernels_arc_f32.hip; frt_embedder::build_f32() and tests/cpp/arc32_launch_check.cpp)
+void pack_conv32_weights(const float *w, int cout, int taps, int cin, float *out);  // frt_kernels.h
+
+namespace frt {
+
+// [Cout][Cin][ks][ks] fp32 -> [Cout][tap][Cin] -> conv32_kernel's fragment order
+inline std::vector<float> conv32_w_frag(const float *src, int cout, int cin, int ks) {
+    const int taps = ks * ks;
+    std::vector<float> w((size_t)cout * cin * taps);
+    for (int co = 0; co < cout; ++co)
+        for (int ci = 0; ci < cin; ++ci)
+            for (int t = 0; t < taps; ++t) w[((size_t)co * taps + t) * cin + ci] = src[((size_t)co * cin + ci) * taps + t];
+    std::vector<float> wf(w.size());
+    pack_conv32_weights(w.data(), cout, taps, cin, wf.data());
+    return wf;
+}
+// output Linear [512][25088] over the NCHW flatten (index c*49 + hw), re-ordered to NHWC (k = hw*512 + c) for fc32_kernel
+inline std::vector<float> fc32_w_nhwc(const float *src) {
+    std::vector<float> w((size_t)512 * 25088);
+    for (int o = 0; o < 512; ++o)
+        for (int c = 0; c < 512; ++c)
+            for (int hw = 0; hw < 49; ++hw) w[(size_t)o * 25088 + (size_t)hw * 512 + c] = src[(size_t)o * 25088 + (size_t)c * 49 + hw];
     return w;
 }
 

@@ -251,22 +251,8 @@ void frt_embedder::build_f32() {
         f32.owned.push_back(d);
         return d;
     };
-    auto w3 = [&](const std::string &name, int cout, int cin) {
-        const float *src = b.get(name, (size_t)cout * cin * 9).data;
-        std::vector<float> w((size_t)cout * cin * 9);
-        for (int co = 0; co < cout; ++co)
-            for (int ci = 0; ci < cin; ++ci)
-                for (int t = 0; t < 9; ++t) w[((size_t)co * 9 + t) * cin + ci] = src[((size_t)co * cin + ci) * 9 + t];
-        std::vector<float> wf(w.size());
-        pack_conv32_weights(w.data(), cout, 9, cin, wf.data());
-        return up(wf);
-    };
-    auto w1x1 = [&](const std::string &name, int cout, int cin) {
-        const std::vector<float> w = vec_of(b, name, (size_t)cout * cin);
-        std::vector<float> wf(w.size());
-        pack_conv32_weights(w.data(), cout, 1, cin, wf.data());
-        return up(wf);
-    };
+    auto w3 = [&](const std::string &name, int cout, int cin) { return up(frt::conv32_w_frag(b.get(name, (size_t)cout * cin * 9).data, cout, cin, 3)); };
+    auto w1x1 = [&](const std::string &name, int cout, int cin) { return up(frt::conv32_w_frag(b.get(name, (size_t)cout * cin).data, cout, cin, 1)); };
     int idx = 0;
     for (const ArcUnit &u : units) {
         const std::string p = "body." + std::to_string(idx++);
@@ -276,25 +262,18 @@ void frt_embedder::build_f32() {
         if (u.wsc) fu.wsc = w1x1(p + ".shortcut_layer.0.weight", u.depth, u.cin);
         f32.units.push_back(fu);
     }
-    {
-        const float *src = b.get("output_layer.3.weight", (size_t)512 * 25088).data;
-        std::vector<float> w((size_t)512 * 25088);
-        for (int o = 0; o < 512; ++o)
-            for (int c = 0; c < 512; ++c)
-                for (int hw = 0; hw < 49; ++hw) w[(size_t)o * 25088 + (size_t)hw * 512 + c] = src[(size_t)o * 25088 + (size_t)c * 49 + hw];
-        f32.wfc = up(w);
-    }
+    f32.wfc = up(frt::fc32_w_nhwc(b.get("output_layer.3.weight", (size_t)512 * 25088).data));
     f32.chunk = std::min(max_batch, 8);
-    const size_t C = (size_t)f32.chunk, big = C * 112 * 112 * 64;
-    f32.A[0] = dev(big);
-    f32.A[1] = dev(big);
-    f32.T = dev(big);
-    f32.SCb = dev(C * 56 * 56 * 128);
+    const Arc32BufferSizes n = arc32_buffer_sizes(f32.chunk);
+    f32.A[0] = dev(n.act);
+    f32.A[1] = dev(n.act);
+    f32.T = dev(n.act);
+    f32.SCb = dev(n.sc);
     if (se) {
-        f32.RES = dev(C * 56 * 56 * 64);
-        f32.gate = dev(C * 512);
+        f32.RES = dev(n.res);
+        f32.gate = dev(n.gate);
     }
-    f32.fc_out = dev(C * 512);
+    f32.fc_out = dev(n.fc_out);
     HIPCHK(hipEventCreateWithFlags(&f32.done, hipEventDisableTiming));
 }
 
@@ -311,30 +290,19 @@ void frt_embedder::forward_f32(const float *chw_dev, int F, const int *valid_dev
         for (size_t i = 0; i < units.size(); ++i) {
             const ArcUnit &u = units[i];
             const F32Unit &fu = f32.units[i];
-            const int h = u.h_in, ho = h / u.stride;
-            const float *x = f32.A[cur];
-            // conv1: BN(x) (on load) -> conv3x3 -> PReLU
-            Conv32Args c1{x, fu.w1, lead_s, lead_b, f32.T, n, h, h, u.cin, h, h, u.depth, 3, 1, 1, 0, u.prelu, nullptr, nullptr, 0, 0, 0};
-            launch_conv32(c1, s);
-            // shortcut: MaxPool2d(1, stride) of x, or conv1x1 stride s + BN
-            const float *sc = x;
-            int sc_h = h, sc_stride = u.stride;
-            if (fu.wsc) {
-                Conv32Args cs{x, fu.wsc, nullptr, nullptr, f32.SCb, n, h, h, u.cin, ho, ho, u.depth, 1, u.stride, 0, 1, u.ssc, u.bsc, nullptr, 0, 0, 0};
-                launch_conv32(cs, s);
-                sc = f32.SCb;
-                sc_h = ho;
-                sc_stride = 1;
-            }
-            // conv2: conv3x3 stride s -> BN (-> SE) -> + shortcut
-            float *y = f32.A[cur ^ 1];
+            // the unit's launches as csrc/frt_arc_launches.hpp describes them: conv1, the 1x1 shortcut where the unit has one, conv2 (-> SE)
+            const Arc32Buffers bufs{f32.A[cur], lead_s, lead_b, f32.T, f32.SCb, f32.RES, f32.gate, f32.A[cur ^ 1]};
+            Conv32Args a;
+            arc32_conv1(u, fu, bufs, n, a);
+            launch_conv32(a, s);
+            if (arc32_shortcut1x1(u, fu, bufs, n, a)) launch_conv32(a, s);
             if (se) {
-                Conv32Args c2{f32.T, fu.w2, nullptr, nullptr, f32.RES, n, h, h, u.depth, ho, ho, u.depth, 3, u.stride, 1, 1, u.s2f32, u.b2, nullptr, 0, 0, 0};
-                launch_conv32(c2, s);
-                launch_se32(f32.RES, u.se_w1, u.se_w2, f32.gate, sc, y, n, ho, ho, u.depth, sc_h, sc_h, sc_stride, s);
+                arc32_conv2_res(u, fu, bufs, n, a);
+                launch_conv32(a, s);
+                launch_se32(arc32_se(u, fu, bufs, n), s);
             } else {
-                Conv32Args c2{f32.T, fu.w2, nullptr, nullptr, y, n, h, h, u.depth, ho, ho, u.depth, 3, u.stride, 1, 2, u.s2f32, u.b2, sc, sc_h, sc_h, sc_stride};
-                launch_conv32(c2, s);
+                arc32_conv2(u, fu, bufs, n, a);
+                launch_conv32(a, s);
             }
             lead_s = u.sn;
             lead_b = u.bn;

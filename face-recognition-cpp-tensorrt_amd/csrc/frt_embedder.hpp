@@ -73,9 +73,7 @@ struct frt_embedder {
 
     // ---- fp32 end-to-end mode (frt_embedder_set_precision(e, 1); kernels_arc_f32.hip): its own weights and activation buffers, built on
     //      first use from the blob the object was created from
-    struct F32Unit {
-        float *w1 = nullptr, *w2 = nullptr, *wsc = nullptr;  // [Cout][tap][Cin] fp32 in conv32_kernel's fragment order
-    };
+    typedef Arc32Weights F32Unit;  // [Cout][tap][Cin] fp32 in conv32_kernel's fragment order
     struct F32 {
         std::vector<void *> owned;   // device allocations of this mode
         std::vector<F32Unit> units;
