@@ -64,6 +64,9 @@ struct ScreenScratch {
     int *ctl;                     // [FRT_MATCH_CTL_WORDS] control words: overflow flag, per-sub-list pair counts, one 128-byte line each (kernels_match.hip)
     unsigned long long *qkey;     // [F] packed (similarity, ~row) winners of the scalar re-rank
     // int8 shadow gallery (D = 512, fp32-stored galleries): null -> the fp16 shadow is scanned
+    // Row g, column k (D = 512, ks = k >> 4) of the int8 shadow lives at byte
+    //   ((((g >> 7) * 4 + ((g >> 5) & 3)) * (D / 32) + (ks >> 1)) * 64 + ((k >> 3) & 1) * 32 + (g & 31)) * 16 + (ks & 1) * 8 + (k & 7)
+    // i.e. [128-row tile][32-row wave block][32-wide k pair][lane = (k half, row)][16 bytes = k-step 2p, k-step 2p + 1]; pad rows are 0x80, scale 0.
     const uint8_t *g8;            // fragment-ordered biased bytes (value + 128), gallery8_bytes(N, D)
     const float *g8_scale;        // [tiles * 128] per-row scale (row = scale * int8 row + error)
     float gerr;                   // max over rows of || row - scale * int8 row ||

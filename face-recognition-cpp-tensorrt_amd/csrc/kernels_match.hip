@@ -362,8 +362,11 @@ __global__ __launch_bounds__(256) void match_coarse_kernel(const half_t *__restr
         }
         *reinterpret_cast<half8 *>(Qs + q * QP + c * 8) = v;
     }
-    float rmax[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};  // this wave's running maximum per query (NaN entries are tracked apart)
-    bool rnan = false;
+    // This wave's running maximum per query.  No coarse entry is ever NaN: a block maximum is an fmaxf chain that starts at -inf, and fmaxf drops
+    // a NaN operand - a NaN accumulator (NaN in the query or in a row, inf - inf) is simply no candidate, and a block of nothing but NaN
+    // keeps -inf.  Non-finite inputs reach the exact scan another way, through the selection's `bounded` test: a NaN / inf query through
+    // ||q||, a non-finite row through gmax_norm and gerr (the shadow builds poison them), an infinite accumulator through m = +-inf.
+    float rmax[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
     int tile = blockIdx.x;
     if (tile >= num_tiles) {  // (uniform per workgroup; no barrier has been executed yet)
         for (int i = tid; i < 128; i += 256)
@@ -415,25 +418,23 @@ __global__ __launch_bounds__(256) void match_coarse_kernel(const half_t *__restr
             m = fmaxf(m, __shfl_xor(m, 32));
             const int q = q0 + n * 32 + r;
             if (hi == 0 && q < F) tilemax[((long)q * num_tiles + tile) * 4 + wave] = m;
-            rnan = rnan || (m != m);
             rmax[n] = fmaxf(rmax[n], m);
         }
         __builtin_amdgcn_sched_barrier(0);  // keep the iterations apart (without it the scheduler's version needs 512 registers + spills)
     }
-    // the four waves' maxima -> one value per (workgroup, query); a NaN anywhere makes it NaN (the selection then takes every tile)
+    // the four waves' maxima -> one value per (workgroup, query)
     __syncthreads();
     float *red = reinterpret_cast<float *>(smem2);  // the query block is dead now
     if (hi == 0) {
 #pragma unroll
-        for (int n = 0; n < 4; ++n) red[wave * 128 + n * 32 + r] = rnan ? NAN : rmax[n];
+        for (int n = 0; n < 4; ++n) red[wave * 128 + n * 32 + r] = rmax[n];
     }
     __syncthreads();
     if (tid < 128 && q0 + tid < F) {
         float m = red[tid];
 #pragma unroll
         for (int w = 1; w < 4; ++w) {
-            const float o = red[w * 128 + tid];
-            m = (m != m || o != o) ? NAN : fmaxf(m, o);
+            m = fmaxf(m, red[w * 128 + tid]);
         }
         wgmax[(long)blockIdx.x * F + q0 + tid] = m;
     }
@@ -489,7 +490,8 @@ __global__ __launch_bounds__(256) void gallery_to_i8_kernel(const float *__restr
     for (int off = 32; off > 0; off >>= 1) {
         m = fmaxf(m, __shfl_xor(m, off));
         n2 += __shfl_xor(n2, off);
-        bad = bad || __shfl_xor((int)bad, off);
+        const int other_bad = __shfl_xor((int)bad, off);  // (not inside the ||: a lane that is bad itself must still take part in the exchange)
+        bad = bad || other_bad;
     }
     const float sc = m > 0.f ? m / 127.f : 0.f, inv = m > 0.f ? 127.f / m : 0.f;
     float e2 = 0.f;
@@ -547,8 +549,7 @@ __global__ __launch_bounds__(256) void match_coarse_i8_kernel(const uint8_t *__r
     }
     float rmax[NQB];
 #pragma unroll
-    for (int n = 0; n < NQB; ++n) rmax[n] = -INFINITY;
-    bool rnan = false;
+    for (int n = 0; n < NQB; ++n) rmax[n] = -INFINITY;  // (never NaN: see match_coarse_kernel)
     int tile = blockIdx.x;
     if (tile >= num_tiles) {
         for (int i = tid; i < 32 * NQB; i += 256)
@@ -634,7 +635,6 @@ __global__ __launch_bounds__(256) void match_coarse_i8_kernel(const uint8_t *__r
             m = fmaxf(m, __shfl_xor(m, 32));
             const int q = q0 + n * 32 + r;
             if (hi == 0 && q < F) tilemax[((long)q * num_tiles + tile) * 4 + wave] = m;
-            rnan = rnan || (m != m);
             rmax[n] = fmaxf(rmax[n], m);
         }
         {
@@ -648,15 +648,14 @@ __global__ __launch_bounds__(256) void match_coarse_i8_kernel(const uint8_t *__r
     float *red = reinterpret_cast<float *>(smem2);
     if (hi == 0) {
 #pragma unroll
-        for (int n = 0; n < NQB; ++n) red[wave * (32 * NQB) + n * 32 + r] = rnan ? NAN : rmax[n];
+        for (int n = 0; n < NQB; ++n) red[wave * (32 * NQB) + n * 32 + r] = rmax[n];
     }
     __syncthreads();
     if (tid < 32 * NQB && q0 + tid < F) {
         float m = red[tid];
 #pragma unroll
         for (int w = 1; w < 4; ++w) {
-            const float o = red[w * (32 * NQB) + tid];
-            m = (m != m || o != o) ? NAN : fmaxf(m, o);
+            m = fmaxf(m, red[w * (32 * NQB) + tid]);
         }
         wgmax[(long)blockIdx.x * F + q0 + tid] = m;
     }
@@ -857,7 +856,8 @@ __global__ __launch_bounds__(256) void match_select_pairs_kernel(const float *__
     // abs_thr not NaN (frt_matcher_cluster): the threshold is the constant t = abs_thr instead of hanging on a coarse entry.  A row with
     // S >= t has S~ >= t - delta, so the coarse maximum of its block is >= t - delta: ONE delta, because the bound is against a constant and
     // not against a second coarse value that is itself off by delta.  Only tiles from tile_min on are listed (the caller joins rows j > i and
-    // none of them lies in a tile in front of the query's own).  The per-workgroup maxima then only say whether a coarse entry was NaN.
+    // none of them lies in a tile in front of the query's own).  The per-workgroup maxima are then only looked at for a NaN (which the coarse scans
+    // never write: see match_coarse_kernel; a caller's own wgmax may hold one, and it lists every tile).
     const bool absolute = abs_thr == abs_thr;
     __shared__ float sm[4], sn[4];
     __shared__ int snan[4];
