@@ -648,6 +648,33 @@ void infer(frt_detector *d, const float *chw, int batch, float *loc_out, float *
 
 }  // namespace
 
+DetGeom det_geometry(int family, int levels, int in_w, int in_h, int frame_w, int frame_h, float nms_threshold, float bbox_threshold, int max_faces) {
+    DetGeom g{};
+    g.in_w = in_w; g.in_h = in_h; g.frame_w = frame_w; g.frame_h = frame_h;
+    // the anchor table of the network's own training config: cfg_mnet, or cfg_slim / cfg_rfb (conversion/retina/config.py)
+    static const int mnet_sizes[3][DET_MAX_SIZES] = {{10, 20}, {32, 64}, {128, 256}}, mnet_n[3] = {2, 2, 2};
+    static const int slim_sizes[4][DET_MAX_SIZES] = {{10, 16, 24}, {32, 48}, {64, 96}, {128, 192, 256}}, slim_n[4] = {3, 2, 2, 3};
+    const bool mnet = family == 1;
+    g.levels = levels;
+    int base = 0;
+    for (int k = 0; k < g.levels; ++k) {
+        g.step[k] = (float)(8 << k);
+        g.nsz[k] = mnet ? mnet_n[k] : slim_n[k];
+        for (int l = 0; l < DET_MAX_SIZES; ++l) g.min_size[k][l] = mnet ? mnet_sizes[k][l] : slim_sizes[k][l];
+        g.fh[k] = (int)std::ceil(in_h / g.step[k]);
+        g.fw[k] = (int)std::ceil(in_w / g.step[k]);
+        g.base[k] = base;
+        base += g.fh[k] * g.fw[k] * g.nsz[k];
+    }
+    g.A = base;
+    g.scale_h = (float)in_h / frame_h;  // retinaface.cpp:21-22
+    g.scale_w = (float)in_w / frame_w;
+    g.nms_thr = nms_threshold;
+    g.bbox_thr = bbox_threshold;
+    g.max_faces = max_faces;
+    return g;
+}
+
 extern "C" {
 
 int frt_detector_create(const char *weights_path, int frame_w, int frame_h, int in_c, int in_h, int in_w, int max_batch, int max_faces,
@@ -667,29 +694,9 @@ int frt_detector_create(const char *weights_path, int frame_w, int frame_h, int 
         d->device = device;
         d->max_batch = max_batch;
         d->family = layout.family;
-        DetGeom &g = d->g;
-        g.in_w = in_w; g.in_h = in_h; g.frame_w = frame_w; g.frame_h = frame_h;
-        // the anchor table of the network's own training config: cfg_mnet, or cfg_slim / cfg_rfb (conversion/retina/config.py)
-        static const int mnet_sizes[3][DET_MAX_SIZES] = {{10, 20}, {32, 64}, {128, 256}}, mnet_n[3] = {2, 2, 2};
-        static const int slim_sizes[4][DET_MAX_SIZES] = {{10, 16, 24}, {32, 48}, {64, 96}, {128, 192, 256}}, slim_n[4] = {3, 2, 2, 3};
+        d->g = det_geometry(layout.family, layout.levels, in_w, in_h, frame_w, frame_h, nms_threshold, bbox_threshold, max_faces);
+        const DetGeom &g = d->g;
         const bool mnet = layout.family == 1;
-        g.levels = layout.levels;
-        int base = 0;
-        for (int k = 0; k < g.levels; ++k) {
-            g.step[k] = (float)(8 << k);
-            g.nsz[k] = mnet ? mnet_n[k] : slim_n[k];
-            for (int l = 0; l < DET_MAX_SIZES; ++l) g.min_size[k][l] = mnet ? mnet_sizes[k][l] : slim_sizes[k][l];
-            g.fh[k] = (int)std::ceil(in_h / g.step[k]);
-            g.fw[k] = (int)std::ceil(in_w / g.step[k]);
-            g.base[k] = base;
-            base += g.fh[k] * g.fw[k] * g.nsz[k];
-        }
-        g.A = base;
-        g.scale_h = (float)in_h / frame_h;  // retinaface.cpp:21-22
-        g.scale_w = (float)in_w / frame_w;
-        g.nms_thr = nms_threshold;
-        g.bbox_thr = bbox_threshold;
-        g.max_faces = max_faces;
         HIPCHK(hipStreamCreate(&d->stream));
         HIPCHK(hipEventCreateWithFlags(&d->ev_busy, hipEventDisableTiming));
         const size_t B = (size_t)max_batch;

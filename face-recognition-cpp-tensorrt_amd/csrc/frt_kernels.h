@@ -211,6 +211,9 @@ struct DetGeom {  // anchor table of one detector (mnet: 3 levels x 2 sizes; Sli
     float nms_thr, bbox_thr;
     int max_faces;
 };
+// The DetGeom of one detector (host, frt_detector.cpp): family 1 = the mnet table over `levels` = 3 levels, any other family = the Slim / RFB
+// table over 4; steps 8 << level, feature maps ceil(dim / step).  frt_detector_create calls it, and so does tests/cpp/det_tail_check.cpp.
+DetGeom det_geometry(int family, int levels, int in_w, int in_h, int frame_w, int frame_h, float nms_threshold, float bbox_threshold, int max_faces);
 struct Candidate {
     frt_bbox box;
     int32_t anchor;
