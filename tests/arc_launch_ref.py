@@ -47,6 +47,8 @@ import zlib
 
 import numpy as np
 
+from launch_harness import read_results
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAN = os.path.join(ROOT, "tests", "golden", "arc_conv_plan.txt")
 
@@ -298,33 +300,17 @@ def write_manifest(dirname, case_list):
 
 def read_outputs(dirname, case):
     """(dict out0 / out1 as fp16 arrays [F][Ho][Wo][Cout], changed slack halves, planned label) or None when the harness did not reach the case."""
-    res = {}
-    path = os.path.join(dirname, "results.txt")
-    if os.path.exists(path):
-        for line in open(path).read().splitlines():
-            cid, changed, label = line.split("\t")
-            res[cid] = (int(changed), label)
+    res = read_results(dirname)
     if case.id not in res:
         return None
+    changed, label = res[case.id]
     g = geometry(case.shape, case.desc)
     outs = {}
     for k in ("out0", "out1"):
         f = os.path.join(dirname, "%s.%s" % (case.id, k))
         if os.path.exists(f):
             outs[k] = np.fromfile(f, np.float16).reshape(case.F, g.Ho, g.Ho, g.Cout)
-    return outs, res[case.id][0], res[case.id][1]
-
-
-def build_harness(outdir, program="arc_launch_check"):
-    """Compiles tests/cpp/<program>.cpp (host C++ against libfrt.so, the way test_conv_plan.py compiles conv_plan_dump); returns the path."""
-    import subprocess
-    pkg = os.path.join(ROOT, "face-recognition-cpp-tensorrt_amd")
-    exe = os.path.join(str(outdir), program)
-    # host side only, but with hipcc: frt_kernels.h uses clang's vector types
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", os.path.join(pkg, "csrc"),
-                           "-x", "c++", os.path.join(ROOT, "tests", "cpp", program + ".cpp"), "-x", "none", "-o", exe, os.path.join(pkg, "libfrt.so"),
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe
+    return outs, int(changed), label
 
 
 # ------------------------------------------------------------------------------------------------ the three small launches
@@ -502,10 +488,7 @@ def write_small_manifest(dirname, case_list):
 
 def read_small_outputs(dirname, c):
     """(dict of output arrays, changed slack elements / counters, launcher name) or None when the harness did not reach the case."""
-    res = {}
-    path = os.path.join(dirname, "results.txt")
-    if os.path.exists(path):
-        res = {ln.split("\t")[0]: ln.split("\t") for ln in open(path).read().splitlines()}
+    res = read_results(dirname)
     if c.id not in res:
         return None
     rd = lambda k, t, shape: np.fromfile(os.path.join(dirname, "%s.%s" % (c.id, k)), t).reshape(shape)
@@ -516,7 +499,7 @@ def read_small_outputs(dirname, c):
     else:
         outs = {k: rd(k, np.float16, (c.F, c.H, c.H, c.C)) for k in ("out0", "out1")}
         outs["gate"] = rd("gate", np.float32, (c.F, c.C))
-    return outs, int(res[c.id][1]), res[c.id][2]
+    return outs, int(res[c.id][0]), res[c.id][1]
 
 
 # ------------------------------------------------------------------------------------------------ conv2 with the SE tail in its epilogue
@@ -731,8 +714,7 @@ FusedRun = collections.namedtuple("FusedRun", "outs label fits n_parts slack out
 
 def read_fused_outputs(dirname, case):
     """What the harness wrote for one fused case, or None when it did not reach the case."""
-    path = os.path.join(dirname, "results.txt")
-    res = {ln.split("\t")[0]: ln.split("\t")[1:] for ln in open(path).read().splitlines()} if os.path.exists(path) else {}
+    res = read_results(dirname)
     if case.id not in res:
         return None
     g = geometry(case.shape, case.desc)
@@ -970,14 +952,9 @@ def write_manifest32(dirname, case_list, small=()):
                      "se32": "se %s %d %d %d %d\n" % (c.id, c.H, c.C, c.F, c.sc_stride)}[c.kind])
 
 
-def _results(dirname):
-    path = os.path.join(dirname, "results.txt")
-    return {ln.split("\t")[0]: ln.split("\t")[1:] for ln in open(path).read().splitlines()} if os.path.exists(path) else {}
-
-
 def read_outputs32(dirname, case):
     """(dict out0 as an fp32 array, changed floats outside the logical output, description name) or None when the harness did not reach the case."""
-    res = _results(dirname)
+    res = read_results(dirname)
     if case.id not in res:
         return None
     g = geometry32(case.shape, case.desc)
@@ -1124,7 +1101,7 @@ def write_small32(dirname, c, d):
 
 def read_small_outputs32(dirname, c):
     """(dict of fp32 output arrays, changed floats outside the logical outputs, launcher name) or None when the harness did not reach the case."""
-    res = _results(dirname)
+    res = read_results(dirname)
     if c.id not in res:
         return None
     rd = lambda k, shape: np.fromfile(os.path.join(dirname, "%s.%s" % (c.id, k)), np.float32).reshape(shape)

@@ -23,12 +23,8 @@
 // buffers are NaN everywhere outside the logical tensor, margins included: a read at a wrong but nearby address shows as a NaN in the output
 // instead of passing as a zero (the margins are longer than (W + 1) * Cin floats for every shape).  Output buffers hold a fixed bit pattern,
 // which must still be there after the launch everywhere outside the logical tensor, in front and behind.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+#define CHECK_PROGRAM "arc32_launch_check"
+#include "check_common.hpp"
 
 #include "arc_conv_describe.hpp"
 #include "frt_arc_pack.hpp"
@@ -37,117 +33,19 @@
 namespace {
 
 using namespace arc_describe;
+using namespace check;
 
 constexpr size_t kMargin = ((size_t)1 << 20) / sizeof(float);  // floats in front of and behind every activation buffer
 constexpr uint32_t kNaN = 0x7fc00000u, kOutFill = 0x5a5a5a5au;
 const char *const kDesc32[ARC32_NUM_DESC] = {"conv1", "shortcut1x1", "conv2", "conv2_res"};
 
-[[noreturn]] void die(const std::string &msg) {
-    fprintf(stderr, "arc32_launch_check: %s\n", msg.c_str());
-    exit(1);
-}
-void hipchk(hipError_t e, const char *what, const std::string &id) {
-    if (e != hipSuccess) die("case " + id + ": " + what + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(x) hipchk((x), #x, id)
+typedef MarginBuf<uint32_t> Buf;
 
-template <class T>
-std::vector<T> read_file(const std::string &path, size_t n) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) die("cannot open " + path);
-    std::vector<T> v(n);
-    const size_t got = fread(v.data(), sizeof(T), n, f);
-    char extra;
-    const bool more = fread(&extra, 1, 1, f) == 1;
-    fclose(f);
-    if (got != n || more) die(path + ": expected " + std::to_string(n) + " elements");
-    return v;
-}
-void write_file(const std::string &path, const void *p, size_t bytes) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f || fwrite(p, 1, bytes, f) != bytes) die("cannot write " + path);
-    fclose(f);
-}
-
-struct Case {
-    std::string kind, id;
-    int shape = 0, d = 0, F = 0, H = 0, C = 0, sc_stride = 0;
-};
-std::vector<Case> read_cases(const std::string &dir) {
-    FILE *f = fopen((dir + "/cases.txt").c_str(), "r");
-    if (!f) die("cannot open " + dir + "/cases.txt");
-    std::vector<Case> cs;
-    char kind[32], id[256];
-    while (fscanf(f, "%31s %255s", kind, id) == 2) {
-        Case c;
-        c.kind = kind;
-        c.id = id;
-        bool ok = false;
-        if (c.kind == "conv")
-            ok = fscanf(f, "%d %d %d", &c.shape, &c.d, &c.F) == 3 && c.shape >= 0 && c.shape < kNumShapes && c.d >= 0 && c.d < ARC32_NUM_DESC;
-        else if (c.kind == "input" || c.kind == "fc")
-            ok = fscanf(f, "%d", &c.F) == 1;
-        else if (c.kind == "se")
-            ok = fscanf(f, "%d %d %d %d", &c.H, &c.C, &c.F, &c.sc_stride) == 4 && c.H >= 1 && c.H <= 56 && c.C >= 64 && c.C <= 512 && c.C % 64 == 0 &&
-                 (size_t)c.H * c.H * c.C <= 56 * 56 * 64 && (c.sc_stride == 1 || c.sc_stride == 2);
-        if (!ok || c.F < 1 || c.F > 8) die("bad case line for " + c.id);  // 8: the mode's chunk
-        cs.push_back(c);
-    }
-    fclose(f);
-    return cs;
-}
-
-// `cap` floats between two margins, all filled with `fill`; the first `logical` floats behind the front margin are the tensor
-struct Buf {
-    uint32_t *base = nullptr;
-    size_t cap = 0, logical = 0;
-    uint32_t fill = 0;
-    float *ptr() const { return reinterpret_cast<float *>(base + kMargin); }
-};
-
-struct DeviceCase {
-    std::string id;
-    std::vector<void *> owned;
-    ~DeviceCase() {
-        for (void *p : owned) (void)hipFree(p);
-    }
-    Buf buf(size_t cap, size_t logical, uint32_t fill, const float *init) {
-        if (logical > cap) die("case " + id + ": a tensor of " + std::to_string(logical) + " floats does not fit the product's buffer of " + std::to_string(cap));
-        Buf b;
-        b.cap = cap;
-        b.logical = logical;
-        b.fill = fill;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&b.base), (2 * kMargin + cap) * sizeof(uint32_t)));
-        owned.push_back(b.base);
-        HIPCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b.base), (int)fill, 2 * kMargin + cap));
-        if (init) HIPCHK(hipMemcpy(b.base + kMargin, init, logical * sizeof(float), hipMemcpyHostToDevice));
-        return b;
-    }
-    Buf in(size_t cap, const std::vector<float> &v) { return buf(cap, v.size(), kNaN, v.data()); }
-    Buf out(size_t cap, size_t logical) { return buf(cap, logical, kOutFill, nullptr); }
-    template <class T>
-    T *upload(const std::vector<T> &v) {
-        T *d = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), v.size() * sizeof(T)));
-        owned.push_back(d);
-        HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-        return d;
-    }
-    // the logical tensor -> `path`; returns the number of floats outside it, margins included, that no longer hold the fill pattern
-    size_t download(const Buf &b, const std::string &path) {
-        std::vector<uint32_t> h(2 * kMargin + b.cap);
-        HIPCHK(hipMemcpy(h.data(), b.base, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        write_file(path, h.data() + kMargin, b.logical * sizeof(uint32_t));
-        size_t changed = 0;
-        for (size_t i = 0; i < kMargin; ++i) changed += h[i] != b.fill;
-        for (size_t i = kMargin + b.logical; i < h.size(); ++i) changed += h[i] != b.fill;
-        return changed;
-    }
-    void finish() {
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipDeviceSynchronize());
-        HIPCHK(hipGetLastError());
-    }
+// the device memory of one case: `cap` floats between two margins, all filled; the first `logical` floats behind the front margin are the tensor
+struct Dev : DeviceCase {
+    explicit Dev(const std::string &id) : DeviceCase(id, kMargin * sizeof(float), kMargin * sizeof(float), "floats") {}
+    Buf in(size_t cap, const std::vector<float> &v) { return buf<uint32_t>(cap, v.size(), kNaN, v.data()); }
+    Buf out(size_t cap, size_t logical) { return buf<uint32_t>(cap, logical, kOutFill, nullptr); }
 };
 
 // the description `d` of a unit of shape `s` as forward_f32 builds it, every pointer a dummy that names its buffer
@@ -174,8 +72,7 @@ void run_conv(const std::string &dir, const Case &c, FILE *results) {
     const Arc32Buffers &b = ds.b;
     const Arc32BufferSizes sz = arc32_buffer_sizes(c.F);
     const std::string pre = dir + "/" + c.id;
-    DeviceCase dc;
-    dc.id = c.id;
+    Dev dc(c.id);
     // the capacity of the buffer a described pointer names
     auto cap_of = [&](const float *p) -> size_t {
         if (p == b.x || p == b.T || p == b.y) return sz.act;
@@ -185,73 +82,70 @@ void run_conv(const std::string &dir, const Case &c, FILE *results) {
     };
     const size_t F = (size_t)c.F, nx = F * a.H * a.W * a.Cin, nout = F * a.Ho * a.Wo * a.Cout;
     if (kMargin < (size_t)(a.W + 1) * a.Cin) die("case " + c.id + ": the margins are shorter than a row of the input");
-    const std::vector<float> x = read_file<float>(pre + ".x", nx), w = read_file<float>(pre + ".w", (size_t)a.Cout * a.Cin * a.ks * a.ks);
-    const std::vector<float> par = read_file<float>(pre + ".p", (size_t)2 * a.Cout);
-    a.x = dc.in(cap_of(ds.a.x), x).ptr();
+    const std::vector<float> x = read_exact<float>(pre + ".x", nx), w = read_exact<float>(pre + ".w", (size_t)a.Cout * a.Cin * a.ks * a.ks);
+    const std::vector<float> par = read_exact<float>(pre + ".p", (size_t)2 * a.Cout);
+    a.x = dc.in(cap_of(ds.a.x), x).ptr<float>();
     a.w = dc.upload(frt::conv32_w_frag(w.data(), a.Cout, a.Cin, a.ks));
     if (a.ps) {
-        float *pro = dc.upload(read_file<float>(pre + ".pro", (size_t)2 * a.Cin));
+        float *pro = dc.upload(read_exact<float>(pre + ".pro", (size_t)2 * a.Cin));
         a.ps = pro;
         a.pb = pro + a.Cin;
     }
     float *dpar = dc.upload(par);
     a.p0 = dpar;
     if (a.p1) a.p1 = dpar + a.Cout;
-    if (a.sc) a.sc = dc.in(cap_of(ds.a.sc), read_file<float>(pre + ".sc", F * a.sc_h * a.sc_w * a.Cout)).ptr();
+    if (a.sc) a.sc = dc.in(cap_of(ds.a.sc), read_exact<float>(pre + ".sc", F * a.sc_h * a.sc_w * a.Cout)).ptr<float>();
     const Buf o = dc.out(cap_of(ds.a.out), nout);
-    a.out = o.ptr();
+    a.out = o.ptr<float>();
     launch_conv32(a, nullptr);
-    dc.finish();
+    sync_and_check();
     fprintf(results, "%s\t%zu\t%s\n", c.id.c_str(), dc.download(o, pre + ".out0"), kDesc32[c.d]);
 }
 
 void run_input(const std::string &dir, const Case &c, FILE *results) {
     const std::string pre = dir + "/" + c.id;
-    DeviceCase dc;
-    dc.id = c.id;
+    Dev dc(c.id);
     const size_t F = (size_t)c.F;
-    const std::vector<float> x = read_file<float>(pre + ".x", F * 3 * 112 * 112), w = read_file<float>(pre + ".w", 64 * 27), par = read_file<float>(pre + ".p", 3 * 64);
+    const std::vector<float> x = read_exact<float>(pre + ".x", F * 3 * 112 * 112), w = read_exact<float>(pre + ".w", 64 * 27), par = read_exact<float>(pre + ".p", 3 * 64);
     std::vector<float> wt(27 * 64);  // build(): [27][64]
     for (int co = 0; co < 64; ++co)
         for (int k = 0; k < 27; ++k) wt[k * 64 + co] = w[co * 27 + k];
     const Buf dx = dc.in(x.size(), x);  // d_in has no slack
     float *dpar = dc.upload(par);
     const Buf y = dc.out(arc32_buffer_sizes(c.F).act, F * 112 * 112 * 64);
-    launch_arc32_input(dx.ptr(), dc.upload(wt), dpar, dpar + 64, dpar + 128, y.ptr(), c.F, nullptr);
-    dc.finish();
+    launch_arc32_input(dx.ptr<float>(), dc.upload(wt), dpar, dpar + 64, dpar + 128, y.ptr<float>(), c.F, nullptr);
+    sync_and_check();
     fprintf(results, "%s\t%zu\tlaunch_arc32_input\n", c.id.c_str(), dc.download(y, pre + ".out0"));
 }
 
 void run_fc(const std::string &dir, const Case &c, FILE *results) {
     const std::string pre = dir + "/" + c.id;
-    DeviceCase dc;
-    dc.id = c.id;
+    Dev dc(c.id);
     const size_t F = (size_t)c.F;
     const Arc32BufferSizes sz = arc32_buffer_sizes(c.F);
-    const std::vector<float> yin = read_file<float>(pre + ".x", F * 25088), w = read_file<float>(pre + ".w", (size_t)512 * 25088);
-    const std::vector<float> pro = read_file<float>(pre + ".pro", 2 * 512), par = read_file<float>(pre + ".p", 3 * 512);
-    const std::vector<int> valid = read_file<int>(pre + ".valid", F);
+    const std::vector<float> yin = read_exact<float>(pre + ".x", F * 25088), w = read_exact<float>(pre + ".w", (size_t)512 * 25088);
+    const std::vector<float> pro = read_exact<float>(pre + ".pro", 2 * 512), par = read_exact<float>(pre + ".p", 3 * 512);
+    const std::vector<int> valid = read_exact<int>(pre + ".valid", F);
     const Buf y = dc.in(sz.act, yin), sums = dc.out(sz.fc_out, F * 512), out = dc.out(F * 512, F * 512);
     float *dpro = dc.upload(pro), *dpar = dc.upload(par);
-    launch_fc32(y.ptr(), dpro, dpro + 512, dc.upload(frt::fc32_w_nhwc(w.data())), sums.ptr(), c.F, nullptr);
-    launch_fc_finalize(sums.ptr(), 1, c.F, dpar, dpar + 512, dpar + 1024, dc.upload(valid), out.ptr(), nullptr);
-    dc.finish();
+    launch_fc32(y.ptr<float>(), dpro, dpro + 512, dc.upload(frt::fc32_w_nhwc(w.data())), sums.ptr<float>(), c.F, nullptr);
+    launch_fc_finalize(sums.ptr<float>(), 1, c.F, dpar, dpar + 512, dpar + 1024, dc.upload(valid), out.ptr<float>(), nullptr);
+    sync_and_check();
     const size_t changed = dc.download(out, pre + ".out0") + dc.download(sums, pre + ".out1");
     fprintf(results, "%s\t%zu\tlaunch_fc32\n", c.id.c_str(), changed);
 }
 
 void run_se(const std::string &dir, const Case &c, FILE *results) {
     const std::string pre = dir + "/" + c.id;
-    DeviceCase dc;
-    dc.id = c.id;
+    Dev dc(c.id);
     const size_t F = (size_t)c.F, C = c.C, n = F * c.H * c.H * C, sh = (size_t)c.H * c.sc_stride;
     const Arc32BufferSizes sz = arc32_buffer_sizes(c.F);
-    const std::vector<float> res = read_file<float>(pre + ".x", n), sc = read_file<float>(pre + ".sc", F * sh * sh * C), w = read_file<float>(pre + ".w", 2 * (C / 16) * C);
+    const std::vector<float> res = read_exact<float>(pre + ".x", n), sc = read_exact<float>(pre + ".sc", F * sh * sh * C), w = read_exact<float>(pre + ".w", 2 * (C / 16) * C);
     const Buf dres = dc.in(sz.res, res), dsc = dc.in(sz.act, sc), y = dc.out(sz.act, n), gate = dc.out(sz.gate, F * C);
     float *dw = dc.upload(w);
-    const Se32Args a{dres.ptr(), dw, dw + (C / 16) * C, gate.ptr(), dsc.ptr(), y.ptr(), c.F, c.H, c.H, c.C, (int)sh, (int)sh, c.sc_stride};
+    const Se32Args a{dres.ptr<float>(), dw, dw + (C / 16) * C, gate.ptr<float>(), dsc.ptr<float>(), y.ptr<float>(), c.F, c.H, c.H, c.C, (int)sh, (int)sh, c.sc_stride};
     launch_se32(a, nullptr);
-    dc.finish();
+    sync_and_check();
     const size_t changed = dc.download(y, pre + ".out0") + dc.download(gate, pre + ".gate");
     fprintf(results, "%s\t%zu\tlaunch_se32\n", c.id.c_str(), changed);
 }
@@ -262,7 +156,7 @@ int main(int argc, char **argv) {
     const bool describe_only = argc == 3 && std::string(argv[1]) == "--describe";
     if (argc != 2 && !describe_only) die("usage: arc32_launch_check [--describe] DIR");
     const std::string dir = argv[argc - 1];
-    const std::vector<Case> cases = read_cases(dir);
+    const std::vector<Case> cases = read_cases(dir, kNumShapes, ARC32_NUM_DESC, 8);  // 8: the mode's chunk
     if (describe_only) {
         for (const Case &c : cases) {
             if (c.kind != "conv") continue;

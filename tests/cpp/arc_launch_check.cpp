@@ -32,12 +32,8 @@
 // strips compute pixel slots of images that do not exist), each with 1 MiB in front.  Inputs are filled with a large finite fp16 value outside
 // the logical tensor - a kernel that accumulated slack into a stored value cannot pass the comparison - and outputs with a fixed bit pattern,
 // which must still be there after the launch everywhere outside the logical tensor.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+#define CHECK_PROGRAM "arc_launch_check"
+#include "check_common.hpp"
 
 #include "arc_conv_describe.hpp"
 #include "frt_arc_pack.hpp"
@@ -46,6 +42,7 @@
 namespace {
 
 using namespace arc_describe;
+using namespace check;
 
 constexpr size_t kMarginBytes = (size_t)1 << 20;  // in front of every activation buffer
 constexpr uint16_t kInFill = 0x7800;              // 32768.0: large, finite
@@ -53,131 +50,12 @@ constexpr uint16_t kOutFill = 0x5a5a;
 constexpr uint32_t kInFill32 = 0x7149f2ca;        // 1e30f
 constexpr uint32_t kOutFill32 = 0x5a5a5a5a;
 
-[[noreturn]] void die(const std::string &msg) {
-    fprintf(stderr, "arc_launch_check: %s\n", msg.c_str());
-    exit(1);
-}
-void hipchk(hipError_t e, const char *what, const std::string &id) {
-    if (e != hipSuccess) die("case " + id + ": " + what + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(x) hipchk((x), #x, id)
+typedef MarginBuf<uint16_t> ActBuf;
 
-template <class T>
-std::vector<T> read_file(const std::string &path, size_t n, bool optional = false) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) {
-        if (optional) return {};
-        die("cannot open " + path);
-    }
-    std::vector<T> v(n);
-    const size_t got = fread(v.data(), sizeof(T), n, f);
-    char extra;
-    const bool more = fread(&extra, 1, 1, f) == 1;
-    fclose(f);
-    if (got != n || more) die(path + ": expected " + std::to_string(n) + " elements");
-    return v;
-}
-void write_file(const std::string &path, const void *p, size_t bytes) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f || fwrite(p, 1, bytes, f) != bytes) die("cannot write " + path);
-    fclose(f);
-}
-
-struct Case {
-    std::string kind, id;
-    int shape = 0, d = 0, F = 0, H = 0, C = 0, sc_stride = 0;
-};
-std::vector<Case> read_cases(const std::string &dir) {
-    FILE *f = fopen((dir + "/cases.txt").c_str(), "r");
-    if (!f) die("cannot open " + dir + "/cases.txt");
-    std::vector<Case> cs;
-    char kind[32], id[256];
-    while (fscanf(f, "%31s %255s", kind, id) == 2) {
-        Case c;
-        c.kind = kind;
-        c.id = id;
-        bool ok = false;
-        if (c.kind == "conv")
-            ok = fscanf(f, "%d %d %d", &c.shape, &c.d, &c.F) == 3 && c.shape >= 0 && c.shape < kNumShapes && c.d >= 0 && c.d < kNumDesc;
-        else if (c.kind == "input" || c.kind == "fc")
-            ok = fscanf(f, "%d", &c.F) == 1;
-        else if (c.kind == "se")
-            ok = fscanf(f, "%d %d %d %d", &c.H, &c.C, &c.F, &c.sc_stride) == 4 && c.H >= 1 && c.H <= 56 && c.C >= 64 && c.C <= 512 && c.C % 64 == 0 &&
-                 (size_t)c.H * c.H * c.C <= 56 * 56 * 64 && (c.sc_stride == 1 || c.sc_stride == 2);
-        if (!ok || c.F < 1 || c.F > 256) die("bad case line for " + c.id);
-        cs.push_back(c);
-    }
-    fclose(f);
-    return cs;
-}
-
-// a buffer of `cap` elements (T = uint16_t: halves, uint32_t: floats / ints) behind the margin, filled with `fill`, its first `logical` elements being the tensor
-template <class T>
-struct Buf {
-    T *base = nullptr;
-    size_t cap = 0, logical = 0;
-    T fill = 0;
-    static constexpr size_t margin = kMarginBytes / sizeof(T);
-    template <class P>
-    P *ptr() const { return reinterpret_cast<P *>(base + margin); }
-};
-typedef Buf<uint16_t> ActBuf;
-
-struct DeviceCase {
-    std::string id;
-    std::vector<void *> owned;
-    ~DeviceCase() {
-        for (void *p : owned) (void)hipFree(p);
-    }
-    template <class T>
-    Buf<T> buf(size_t cap, size_t logical, T fill, const void *init) {
-        if (logical > cap) die("case " + id + ": a tensor of " + std::to_string(logical) + " elements does not fit the product's buffer of " + std::to_string(cap));
-        Buf<T> b;
-        b.cap = cap;
-        b.logical = logical;
-        b.fill = fill;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&b.base), (b.margin + cap) * sizeof(T)));
-        owned.push_back(b.base);
-        if (sizeof(T) == 2)
-            HIPCHK(hipMemsetD16(reinterpret_cast<hipDeviceptr_t>(b.base), (unsigned short)fill, b.margin + cap));
-        else
-            HIPCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b.base), (int)fill, b.margin + cap));
-        if (init) HIPCHK(hipMemcpy(b.base + b.margin, init, logical * sizeof(T), hipMemcpyHostToDevice));
-        return b;
-    }
+// the device memory of one case: every buffer behind kMarginBytes, nothing behind it but the product's own slack
+struct Dev : DeviceCase {
+    explicit Dev(const std::string &id) : DeviceCase(id, kMarginBytes, 0, "elements") {}
     ActBuf act(size_t cap, size_t logical, uint16_t fill, const std::vector<uint16_t> *init) { return buf<uint16_t>(cap, logical, fill, init ? init->data() : nullptr); }
-    template <class T>
-    T *upload(const std::vector<T> &v) {
-        T *d = nullptr;
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&d), v.size() * sizeof(T)));
-        owned.push_back(d);
-        HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-        return d;
-    }
-    template <class T>
-    std::vector<T> fetch(const Buf<T> &b) {  // margin and slack included
-        std::vector<T> h(b.margin + b.cap);
-        HIPCHK(hipMemcpy(h.data(), b.base, h.size() * sizeof(T), hipMemcpyDeviceToHost));
-        return h;
-    }
-    template <class T>
-    void refill(const Buf<T> &b) {
-        if (sizeof(T) == 2)
-            HIPCHK(hipMemsetD16(reinterpret_cast<hipDeviceptr_t>(b.base), (unsigned short)b.fill, b.margin + b.cap));
-        else
-            HIPCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(b.base), (int)b.fill, b.margin + b.cap));
-    }
-    // the logical tensor -> `path` (empty: not kept); returns the number of elements outside it that no longer hold the fill pattern
-    template <class T>
-    size_t download(const Buf<T> &b, const std::string &path, std::vector<T> *keep = nullptr) {
-        std::vector<T> h = fetch(b);
-        if (!path.empty()) write_file(path, h.data() + b.margin, b.logical * sizeof(T));
-        size_t changed = 0;
-        for (size_t i = 0; i < b.margin; ++i) changed += h[i] != b.fill;
-        for (size_t i = b.margin + b.logical; i < h.size(); ++i) changed += h[i] != b.fill;
-        if (keep) keep->assign(h.begin() + b.margin, h.begin() + b.margin + b.logical);
-        return changed;
-    }
 };
 
 void run_conv(const std::string &dir, const Case &c, FILE *results) {
@@ -185,16 +63,14 @@ void run_conv(const std::string &dir, const Case &c, FILE *results) {
     ConvMfmaArgs a;
     if (!describe(u, c.shape == 0, c.d, c.F, a)) die("case " + c.id + ": the unit has no such launch");
     const std::string pre = dir + "/" + c.id;
-    DeviceCase dc;
-    dc.id = c.id;
-    const std::string &id = c.id;
+    Dev dc(c.id);
     const size_t F = (size_t)c.F, big = F * 112 * 112 * 64, sc_cap = F * 28 * 28 * 128;  // alloc_act_set: Y / Z / T, and SC
     const bool has_sc_conv = u.cin != u.depth;
 
     const size_t nx = F * a.H * a.W * a.Cin, nout = F * a.Ho * a.Wo * a.Cout, nw = (size_t)a.Cout * a.Cin * a.ks * a.ks;
-    const std::vector<uint16_t> x = read_file<uint16_t>(pre + ".x", nx);
-    const std::vector<float> w = read_file<float>(pre + ".w", nw);
-    const std::vector<float> par = read_file<float>(pre + ".p", (size_t)6 * a.Cout);
+    const std::vector<uint16_t> x = read_exact<uint16_t>(pre + ".x", nx);
+    const std::vector<float> w = read_exact<float>(pre + ".w", nw);
+    const std::vector<float> par = read_exact<float>(pre + ".p", (size_t)6 * a.Cout);
     a.x = dc.act(big, nx, kInFill, &x).ptr<half_t>();
     a.w = reinterpret_cast<half_t *>(dc.upload(frt::conv_w_f16(w.data(), a.Cout, a.Cin, a.ks)));
     if (a.wf) a.wf = reinterpret_cast<half_t *>(dc.upload(frt::conv_w_f16_frag(w.data(), a.Cout, a.Cin)));
@@ -207,13 +83,13 @@ void run_conv(const std::string &dir, const Case &c, FILE *results) {
     if (a.p3) a.p3 = dpar + 3 * a.Cout;
     if (a.sc) {  // the unit's input (Y), or the 1x1 launch's output (SC) in the units that have a shortcut conv
         const size_t nsc = F * a.sc_h * a.sc_w * a.Cout;
-        const std::vector<uint16_t> sc = read_file<uint16_t>(pre + ".sc", nsc);
+        const std::vector<uint16_t> sc = read_exact<uint16_t>(pre + ".sc", nsc);
         a.sc = dc.act(has_sc_conv ? sc_cap : big, nsc, kInFill, &sc).ptr<half_t>();
     }
     if (a.scx) {
         const size_t nsc = F * a.H * a.W * a.Csc;
-        const std::vector<uint16_t> sc = read_file<uint16_t>(pre + ".sc", nsc);
-        const std::vector<float> wsc = read_file<float>(pre + ".wsc", (size_t)a.Cout * a.Csc);
+        const std::vector<uint16_t> sc = read_exact<uint16_t>(pre + ".sc", nsc);
+        const std::vector<float> wsc = read_exact<float>(pre + ".wsc", (size_t)a.Cout * a.Csc);
         a.scx = dc.act(big, nsc, kInFill, &sc).ptr<half_t>();
         a.wscf = reinterpret_cast<half_t *>(dc.upload(frt::conv1x1_w_f16_frag(wsc.data(), a.Cout, a.Csc)));
         a.psc0 = dpar + 4 * a.Cout;
@@ -239,19 +115,10 @@ void run_conv(const std::string &dir, const Case &c, FILE *results) {
 
     const ConvPlan plan = conv_plan(a);
     launch_conv_mfma(a, plan, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipGetLastError());
+    sync_and_check();
     size_t changed = dc.download(o0, pre + ".out0");
     if (o1.base) changed += dc.download(o1, pre + ".out1");
     fprintf(results, "%s\t%zu\t%s\n", c.id.c_str(), changed, plan.label);
-}
-
-
-void finish(DeviceCase &dc, const std::string &id) {
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipGetLastError());
 }
 
 // IR-SE conv2 with the SE tail in its epilogue (csrc/frt_se_device.h), launched the way arc_unit_schedule (csrc/frt_arc_launches.hpp) builds it:
@@ -266,14 +133,13 @@ void run_conv_se(const std::string &dir, const Case &c, FILE *results) {
     const Shape &u = kShapes[c.shape];
     ConvMfmaArgs a;
     if (!describe(u, c.shape == 0, ARC_CONV2_SE, c.F, a)) die("case " + c.id + ": the unit has no such launch");
-    const std::string pre = dir + "/" + c.id, &id = c.id;
-    DeviceCase dc;
-    dc.id = c.id;
+    const std::string pre = dir + "/" + c.id;
+    Dev dc(c.id);
     const size_t F = (size_t)c.F, C = (size_t)a.Cout, big = F * 112 * 112 * 64, sc_cap = F * 28 * 28 * 128;  // alloc_act_set: Y / Z / T, and SC
     const size_t nx = F * a.H * a.W * a.Cin, nout = F * a.Ho * a.Wo * C, nsc = F * a.sc_h * a.sc_w * C;
-    const std::vector<uint16_t> x = read_file<uint16_t>(pre + ".x", nx), x0 = read_file<uint16_t>(pre + ".x0", nx);
-    const std::vector<uint16_t> sc = read_file<uint16_t>(pre + ".sc", nsc), sc0 = read_file<uint16_t>(pre + ".sc0", nsc);
-    const std::vector<float> w = read_file<float>(pre + ".w", C * a.Cin * 9), par = read_file<float>(pre + ".p", 6 * C), se = read_file<float>(pre + ".se", 2 * (C / 16) * C);
+    const std::vector<uint16_t> x = read_exact<uint16_t>(pre + ".x", nx), x0 = read_exact<uint16_t>(pre + ".x0", nx);
+    const std::vector<uint16_t> sc = read_exact<uint16_t>(pre + ".sc", nsc), sc0 = read_exact<uint16_t>(pre + ".sc0", nsc);
+    const std::vector<float> w = read_exact<float>(pre + ".w", C * a.Cin * 9), par = read_exact<float>(pre + ".p", 6 * C), se = read_exact<float>(pre + ".se", 2 * (C / 16) * C);
     const ActBuf dx = dc.act(big, nx, kInFill, &x0), dsc = dc.act(u.cin != u.depth ? sc_cap : big, nsc, kInFill, &sc0);
     a.x = dx.ptr<half_t>();
     a.sc = dsc.ptr<half_t>();
@@ -286,7 +152,7 @@ void run_conv_se(const std::string &dir, const Case &c, FILE *results) {
     a.se_w2 = dse + (C / 16) * C;
     a.zeros = reinterpret_cast<half_t *>(dc.upload(std::vector<uint16_t>(256, 0)));
     const size_t pool_words = F * 512 * 4;
-    const Buf<uint32_t> scratch = dc.buf<uint32_t>(pool_words + 2 * F, pool_words + 2 * F, kOutFill32, nullptr);
+    const MarginBuf<uint32_t> scratch = dc.buf<uint32_t>(pool_words + 2 * F, pool_words + 2 * F, kOutFill32, nullptr);
     HIPCHK(hipMemset(scratch.ptr<uint32_t>() + pool_words, 0, 2 * F * sizeof(uint32_t)));
     a.se_pool = scratch.ptr<float>();
     a.se_counter = scratch.ptr<int>() + pool_words;
@@ -315,15 +181,14 @@ void run_conv_se(const std::string &dir, const Case &c, FILE *results) {
     auto launch = [&](int epoch, const std::string &keep, std::vector<uint16_t> *y, std::vector<uint16_t> *z) {
         a.se_epoch = epoch;
         launch_conv_mfma(a, plan, nullptr);
-        finish(dc, id);
+        sync_and_check();
         if (*err.host) die("case " + c.id + ": a hand-over wait of the SE tail timed out (error word " + std::to_string(*err.host) + ", epoch " + std::to_string(epoch) + ")");
         if (y) slack += dc.download(o0, keep.empty() ? keep : keep + ".out0", y) + dc.download(o1, keep.empty() ? keep : keep + ".out1", z);
         const std::vector<uint32_t> h = dc.fetch(scratch);
-        const uint32_t *s = h.data() + scratch.margin;
+        const uint32_t *s = h.data() + scratch.front;
         const size_t live = n_parts * F * C;  // se_pool[part][face][channel]: every word written, none behind them
-        for (size_t i = 0; i < scratch.margin; ++i) outside += h[i] != kOutFill32;
+        outside += changed_outside(h.data(), scratch.front + pool_words, scratch.front, live, kOutFill32);
         for (size_t i = 0; i < live; ++i) unwritten += s[i] == kOutFill32;
-        for (size_t i = live; i < pool_words; ++i) outside += s[i] != kOutFill32;
         for (size_t f = 0; f < F; ++f) counters += s[pool_words + f] != 0, flags += s[pool_words + F + f] != (uint32_t)epoch;
     };
     launch(kEpoch, "", nullptr, nullptr);
@@ -342,61 +207,58 @@ void run_conv_se(const std::string &dir, const Case &c, FILE *results) {
 }
 
 void run_input(const std::string &dir, const Case &c, FILE *results) {
-    const std::string pre = dir + "/" + c.id, &id = c.id;
-    DeviceCase dc;
-    dc.id = c.id;
+    const std::string pre = dir + "/" + c.id;
+    Dev dc(c.id);
     const size_t F = (size_t)c.F, big = F * 112 * 112 * 64;
-    const std::vector<float> x = read_file<float>(pre + ".x", F * 3 * 112 * 112), w = read_file<float>(pre + ".w", 64 * 27), par = read_file<float>(pre + ".p", 5 * 64);
+    const std::vector<float> x = read_exact<float>(pre + ".x", F * 3 * 112 * 112), w = read_exact<float>(pre + ".w", 64 * 27), par = read_exact<float>(pre + ".p", 5 * 64);
     std::vector<float> wt(27 * 64);  // build(): [27][64] for the scalar kernel
     for (int co = 0; co < 64; ++co)
         for (int k = 0; k < 27; ++k) wt[k * 64 + co] = w[co * 27 + k];
-    const Buf<uint32_t> dx = dc.buf<uint32_t>(x.size(), x.size(), kInFill32, x.data());  // d_in has no slack
+    const MarginBuf<uint32_t> dx = dc.buf<uint32_t>(x.size(), x.size(), kInFill32, x.data());  // d_in has no slack
     float *dpar = dc.upload(par);
     const ActBuf z = dc.act(big, big, kOutFill, nullptr), y = dc.act(big, big / 4, kOutFill, nullptr);  // Z[0], Y[0]
     ArcInputArgs a{dx.ptr<float>(), dc.upload(wt), dpar, dpar + 64, dpar + 128, dpar + 192, dpar + 256, y.ptr<half_t>(), z.ptr<half_t>(), c.F, 112, 112,
                    reinterpret_cast<half_t *>(dc.upload(frt::arc_input_w_f16(w.data(), par.data(), par.data() + 64)))};
     launch_arc_input(a, nullptr);
-    finish(dc, id);
+    sync_and_check();
     const size_t changed = dc.download(z, pre + ".out0") + dc.download(y, pre + ".out1");
     fprintf(results, "%s\t%zu\tlaunch_arc_input\n", c.id.c_str(), changed);
 }
 
 void run_fc(const std::string &dir, const Case &c, FILE *results) {
-    const std::string pre = dir + "/" + c.id, &id = c.id;
-    DeviceCase dc;
-    dc.id = c.id;
+    const std::string pre = dir + "/" + c.id;
+    Dev dc(c.id);
     const size_t F = (size_t)c.F;
-    const std::vector<uint16_t> zin = read_file<uint16_t>(pre + ".x", F * 25088);
-    const std::vector<float> w = read_file<float>(pre + ".w", (size_t)512 * 25088), par = read_file<float>(pre + ".p", 3 * 512);
-    const std::vector<int> valid = read_file<int>(pre + ".valid", F);
+    const std::vector<uint16_t> zin = read_exact<uint16_t>(pre + ".x", F * 25088);
+    const std::vector<float> w = read_exact<float>(pre + ".w", (size_t)512 * 25088), par = read_exact<float>(pre + ".p", 3 * 512);
+    const std::vector<int> valid = read_exact<int>(pre + ".valid", F);
     const ActBuf z = dc.act(F * 112 * 112 * 64, zin.size(), kInFill, &zin);
-    const Buf<uint32_t> partial = dc.buf<uint32_t>(49 * F * 512, 49 * F * 512, kOutFill32, nullptr), out = dc.buf<uint32_t>(F * 512, F * 512, kOutFill32, nullptr);
+    const MarginBuf<uint32_t> partial = dc.buf<uint32_t>(49 * F * 512, 49 * F * 512, kOutFill32, nullptr), out = dc.buf<uint32_t>(F * 512, F * 512, kOutFill32, nullptr);
     float *dpar = dc.upload(par);
     launch_fc_slices(z.ptr<half_t>(), reinterpret_cast<half_t *>(dc.upload(frt::fc_w_f16_frag(w.data()))), c.F, partial.ptr<float>(), nullptr);
     launch_fc_finalize(partial.ptr<float>(), 49, c.F, dpar, dpar + 512, dpar + 1024, dc.upload(valid), out.ptr<float>(), nullptr);
-    finish(dc, id);
+    sync_and_check();
     const size_t changed = dc.download(out, pre + ".out0") + dc.download(partial, pre + ".out1");
     fprintf(results, "%s\t%zu\tlaunch_fc\n", c.id.c_str(), changed);
 }
 
 void run_se(const std::string &dir, const Case &c, FILE *results) {
-    const std::string pre = dir + "/" + c.id, &id = c.id;
-    DeviceCase dc;
-    dc.id = c.id;
+    const std::string pre = dir + "/" + c.id;
+    Dev dc(c.id);
     const size_t F = (size_t)c.F, C = c.C, n = F * c.H * c.H * C, big = F * 112 * 112 * 64, sh = (size_t)c.H * c.sc_stride;
-    const std::vector<uint16_t> res = read_file<uint16_t>(pre + ".x", n), sc = read_file<uint16_t>(pre + ".sc", F * sh * sh * C);
-    const std::vector<float> w = read_file<float>(pre + ".w", 2 * (C / 16) * C), par = read_file<float>(pre + ".p", 2 * C);
+    const std::vector<uint16_t> res = read_exact<uint16_t>(pre + ".x", n), sc = read_exact<uint16_t>(pre + ".sc", F * sh * sh * C);
+    const std::vector<float> w = read_exact<float>(pre + ".w", 2 * (C / 16) * C), par = read_exact<float>(pre + ".p", 2 * C);
     // alloc_act_set: RES, Y (the shortcut), Y / Z of the other parity, se_pool with the arrival counters and flags behind it, se_gate
     const ActBuf dres = dc.act(F * 56 * 56 * 64, n, kInFill, &res), dsc = dc.act(big, sc.size(), kInFill, &sc);
     const ActBuf y = dc.act(big, n, kOutFill, nullptr), z = dc.act(big, n, kOutFill, nullptr);
-    const Buf<uint32_t> gate = dc.buf<uint32_t>(F * 512, F * C, kOutFill32, nullptr);
+    const MarginBuf<uint32_t> gate = dc.buf<uint32_t>(F * 512, F * C, kOutFill32, nullptr);
     float *pool = dc.upload(std::vector<float>(F * 512 * 4 + 2 * F, 0.f));
     int *counter = reinterpret_cast<int *>(pool + F * 512 * 4);
     float *dw = dc.upload(w), *dpar = dc.upload(par);
     SeArgs a{dres.ptr<half_t>(), dw, dw + (C / 16) * C, dsc.ptr<half_t>(), (int)sh, (int)sh, c.sc_stride, dpar, dpar + C, y.ptr<half_t>(), z.ptr<half_t>(), pool, gate.ptr<float>(),
              c.F, c.H, c.H, c.C, counter};
     launch_se(a, nullptr);
-    finish(dc, id);
+    sync_and_check();
     size_t changed = dc.download(y, pre + ".out0") + dc.download(z, pre + ".out1") + dc.download(gate, pre + ".gate");
     std::vector<int> cnt(2 * F);
     HIPCHK(hipMemcpy(cnt.data(), counter, cnt.size() * sizeof(int), hipMemcpyDeviceToHost));
@@ -419,7 +281,7 @@ int main(int argc, char **argv) {
     const bool plan_only = argc == 3 && std::string(argv[1]) == "--plan";
     if (argc != 2 && !plan_only) die("usage: arc_launch_check [--plan] DIR");
     const std::string dir = argv[argc - 1];
-    const std::vector<Case> cases = read_cases(dir);
+    const std::vector<Case> cases = read_cases(dir, kNumShapes, kNumDesc, 256);
     if (plan_only) {
         for (const Case &c : cases) {
             ConvMfmaArgs a;

@@ -21,45 +21,18 @@
 //   results.txt     "<name>\t<changed sentinel / input words>" per op that ran; u8conv / u8stem: launch_det_conv1_u8 and launch_det_stem on
 //                   DIR/frames.u8 [B][frame_h][frame_w][3] (u8 = 1; "n/a" where the launcher declined), outputs u8conv.out (op 0's) and u8stem.out (op 2's)
 // Exit status 1 on any HIP error; what was written before it stays.
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <string>
-#include <vector>
+#include <algorithm>
 
 #include "frt_detector.hpp"
+#undef HIPCHK  // the host library's own (csrc/frt_host.hpp), which returns a status: here a HIP error ends the process
+#define CHECK_PROGRAM "det_op_check"
+#include "check_common.hpp"
 
 namespace {
 
+using namespace check;
+
 constexpr uint32_t kFill = 0x7149f2ca;  // 1e30f
-
-[[noreturn]] void die(const std::string &msg) {
-    fprintf(stderr, "det_op_check: %s\n", msg.c_str());
-    exit(1);
-}
-void chk(hipError_t e, const char *what, const std::string &where) {
-    if (e != hipSuccess) die(where + ": " + what + ": " + hipGetErrorString(e));
-}
-#define CHK(x) chk((x), #x, where)
-
-std::vector<uint32_t> read_words(const std::string &path, size_t n) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) die("cannot open " + path);
-    std::vector<uint32_t> v(n);
-    const size_t got = fread(v.data(), 4, n, f);
-    char extra;
-    const bool more = fread(&extra, 1, 1, f) == 1;
-    fclose(f);
-    if (got != n || more) die(path + ": expected " + std::to_string(n) + " words");
-    return v;
-}
-void write_file(const std::string &path, const void *p, size_t bytes) {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f || fwrite(p, 1, bytes, f) != bytes) die("cannot write " + path);
-    fclose(f);
-}
 
 // channels [coff, coff + cn) of a [frames][ctotal][h][w] tensor at ptr; flat: [frames][ctotal] words per frame (d_loc / d_conf / d_ldm)
 struct Ref {
@@ -183,13 +156,13 @@ struct Buffers {
         size_t off, n;
     };
     std::vector<Range> dirty;  // what place() changed in the host images since the last fill()
-    void fill(const std::string &where) {
+    void fill() {
         for (auto &b : want) {
             if (open[b.first].size() != b.second.size()) {  // first use
                 std::fill(b.second.begin(), b.second.end(), kFill);
                 open[b.first].assign(b.second.size(), 0);
             }
-            CHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(const_cast<float *>(b.first)), (int)kFill, b.second.size()));
+            HIPCHK(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(const_cast<float *>(b.first)), (int)kFill, b.second.size()));
         }
         for (const Range &r : dirty) {
             std::fill(want.at(r.p).begin() + r.off, want.at(r.p).begin() + r.off + r.n, kFill);
@@ -202,32 +175,32 @@ struct Buffers {
         dirty.push_back({p, off, n});
     }
     // the logical tensor r of `frames` frames: uploaded from `src` (inputs) or opened for writing (outputs)
-    void place(const Ref &r, int frames, const uint32_t *src, const std::string &where) {
+    void place(const Ref &r, int frames, const uint32_t *src) {
         auto &w = want.at(r.ptr);
         const size_t hw = (size_t)r.h * r.w, n = (size_t)r.cn * hw;
         for (int b = 0; b < frames; ++b) {
             const size_t off = (size_t)b * r.frame_words() + (size_t)r.coff * hw;
-            if (off + n > w.size()) die(where + ": " + r.name + " does not fit its buffer");
+            if (off + n > w.size()) die(g_where + ": " + r.name + " does not fit its buffer");
             if (src) {
                 std::memcpy(w.data() + off, src + (size_t)b * n, n * 4);
                 dirty.push_back({r.ptr, off, n});
-                CHK(hipMemcpy(const_cast<float *>(r.ptr) + off, src + (size_t)b * n, n * 4, hipMemcpyHostToDevice));
+                HIPCHK(hipMemcpy(const_cast<float *>(r.ptr) + off, src + (size_t)b * n, n * 4, hipMemcpyHostToDevice));
             } else {
                 open_words(r.ptr, off, n);
             }
         }
     }
     // words that may not have changed and did; the buffers' contents land in `got`
-    size_t check(std::map<const float *, std::vector<uint32_t>> &got, const std::string &where) {
+    size_t check(std::map<const float *, std::vector<uint32_t>> &got) {
         size_t changed = 0;
         for (auto &b : want) {
             auto &g = got[b.first];
             g.resize(b.second.size());
-            CHK(hipMemcpy(g.data(), b.first, g.size() * 4, hipMemcpyDeviceToHost));
+            HIPCHK(hipMemcpy(g.data(), b.first, g.size() * 4, hipMemcpyDeviceToHost));
             bool touched = false;
             for (const Range &r : dirty) touched = touched || r.p == b.first;
             if (!touched) {
-                for (size_t k = 0; k < g.size(); ++k) changed += g[k] != kFill;
+                changed += changed_outside(g.data(), g.size(), 0, 0, kFill);
                 continue;
             }
             const auto &o = open.at(b.first);
@@ -288,38 +261,38 @@ int main(int argc, char **argv) {
     std::map<const float *, std::vector<uint32_t>> got;
 
     // after the launch(es) of one step: synchronise, check, write the outputs
-    auto finish = [&](const std::string &where, const std::vector<Ref> &outs, const std::vector<std::string> &names) {
-        CHK(hipGetLastError());
-        CHK(hipStreamSynchronize(s));
-        CHK(hipGetLastError());
-        const size_t changed = bufs.check(got, where);
+    auto finish = [&](const std::vector<Ref> &outs, const std::vector<std::string> &names) {
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(s));
+        HIPCHK(hipGetLastError());
+        const size_t changed = bufs.check(got);
         for (size_t k = 0; k < outs.size(); ++k) {
             Ref r = outs[k];
             if (!names.empty()) r.name = names[k];
             write_ref(dir, r, B, got.at(r.ptr));
         }
-        fprintf(results, "%s\t%zu\n", where.c_str(), changed);
+        fprintf(results, "%s\t%zu\n", g_where.c_str(), changed);
         fflush(results);
     };
 
     // op i alone; tag: the inputs are op<i>.p<k>.in.<tag> (an op's own input scaled, the range-edge cases) and the outputs carry the tag too
     auto run_alone = [&](size_t i, const std::string &tag) {
         const OpDesc &o = ops[i];
-        const std::string where = "op" + std::to_string(i) + (tag.empty() ? "" : "." + tag);
-        bufs.fill(where);
+        g_where = "op" + std::to_string(i) + (tag.empty() ? "" : "." + tag);
+        bufs.fill();
         for (const Ref &r : o.ins) {
             const bool scaled = !tag.empty() && r.name.size() > 3 && r.name.compare(r.name.size() - 3, 3, ".in") == 0;
-            const std::vector<uint32_t> x = read_words(dir + "/" + r.name + (scaled ? "." + tag : ""), (size_t)B * r.cn * r.h * r.w);
-            bufs.place(r, B, x.data(), where);
+            const std::vector<uint32_t> x = read_exact<uint32_t>(dir + "/" + r.name + (scaled ? "." + tag : ""), (size_t)B * r.cn * r.h * r.w, false, "words");
+            bufs.place(r, B, x.data());
         }
         std::vector<std::string> names;
         for (const Ref &r : o.outs) {
-            bufs.place(r, B, nullptr, where);
+            bufs.place(r, B, nullptr);
             names.push_back(r.name + (tag.empty() ? "" : "." + tag));
         }
         if (o.tmp) bufs.open_words(o.tmp, 0, o.tmp_words);
         d->run_op(i, B, s);
-        finish(where, o.outs, names);
+        finish(o.outs, names);
     };
     for (size_t i = 0; i < ops.size(); ++i) run_alone(i, "");
     for (const auto &e : extras) {
@@ -331,29 +304,25 @@ int main(int argc, char **argv) {
         if (frame_w != in_w || frame_h != in_h) die("u8 = 1 needs frames of the network's input size");
         const frt_detector::Stem st = d->stem();
         const size_t tight = (size_t)frame_w * 3, fbytes = tight * frame_h;
-        std::vector<uint8_t> frames((size_t)B * fbytes);
-        {
-            FILE *f = fopen((dir + "/frames.u8").c_str(), "rb");
-            if (!f || fread(frames.data(), 1, frames.size(), f) != frames.size()) die("cannot read " + dir + "/frames.u8");
-            fclose(f);
-        }
-        std::string where = "u8conv";
-        CHK(hipMemcpy(d->d_frames, frames.data(), frames.size(), hipMemcpyHostToDevice));
+        const std::vector<char> frames = read_all(dir + "/frames.u8");
+        if (frames.size() < (size_t)B * fbytes) die("cannot read " + dir + "/frames.u8");
+        g_where = "u8conv";
+        HIPCHK(hipMemcpy(d->d_frames, frames.data(), (size_t)B * fbytes, hipMemcpyHostToDevice));
         if (st.c) {
-            bufs.fill(where);
-            bufs.place(ops[0].outs[0], B, nullptr, where);
+            bufs.fill();
+            bufs.place(ops[0].outs[0], B, nullptr);
             Conv3Args c = *st.c;
             c.B = B;
-            if (launch_det_conv1_u8(d->d_frames, tight, fbytes, c, s)) finish(where, {ops[0].outs[0]}, {"u8conv.out"});
-            else fprintf(results, "%s\tn/a\n", where.c_str());
-            where = "u8stem";
-            bufs.fill(where);
+            if (launch_det_conv1_u8(d->d_frames, tight, fbytes, c, s)) finish({ops[0].outs[0]}, {"u8conv.out"});
+            else fprintf(results, "%s\tn/a\n", g_where.c_str());
+            g_where = "u8stem";
+            bufs.fill();
             if (st.d1) {
-                bufs.place(ops[2].outs[0], B, nullptr, where);
-                if (launch_det_stem(d->d_frames, tight, fbytes, c, *st.d1, *st.d2, s)) finish(where, {ops[2].outs[0]}, {"u8stem.out"});
-                else fprintf(results, "%s\tn/a\n", where.c_str());
+                bufs.place(ops[2].outs[0], B, nullptr);
+                if (launch_det_stem(d->d_frames, tight, fbytes, c, *st.d1, *st.d2, s)) finish({ops[2].outs[0]}, {"u8stem.out"});
+                else fprintf(results, "%s\tn/a\n", g_where.c_str());
             } else {
-                fprintf(results, "%s\tn/a\n", where.c_str());
+                fprintf(results, "%s\tn/a\n", g_where.c_str());
             }
         }
     }

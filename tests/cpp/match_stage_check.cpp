@@ -4,7 +4,8 @@
 //
 //   match_stage_check DIR     run DIR/ops.txt on the current device; stops at the first HIP error (exit 1)
 //
-// DIR/ops.txt is a list of operations, one per line, on NAMED device buffers.  Every buffer is allocated with kGuard bytes in front and behind;
+// DIR/ops.txt is a list of operations, one per line, on NAMED device buffers (read by run_ops, check_common.hpp, which owns case / buf / rbuf /
+// load / dump / end; this file holds the launches and their size checks).  Every buffer is allocated with kGuard bytes in front and behind;
 // the guards and every byte the case does not load are filled with the pattern 0x5a.  Numbers are decimal; floats travel as their 32-bit pattern
 // (decimal) so that inf / NaN / exact values arrive unchanged; "-" is a null pointer.
 //   case ID                            begins a case
@@ -26,138 +27,22 @@
 //   end                                "ID\t<changed guard bytes + changed rbuf bytes>" -> DIR/results.txt; frees every buffer
 // Every launch is followed by hipDeviceSynchronize and hipGetLastError.
 #include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <sstream>
-#include <string>
-#include <vector>
 
+#define CHECK_PROGRAM "match_stage_check"
+#include "check_common.hpp"
 #include "frt_kernels.h"
 
-namespace {
-
-constexpr size_t kGuard = (size_t)64 << 10;
-constexpr int kFill = 0x5a;
-
-std::string g_case = "(none)";
-
-[[noreturn]] void die(const std::string &msg) {
-    fprintf(stderr, "match_stage_check: case %s: %s\n", g_case.c_str(), msg.c_str());
-    exit(1);
-}
-void hipchk(hipError_t e, const char *what) {
-    if (e != hipSuccess) die(std::string(what) + ": " + hipGetErrorString(e));
-}
-#define HIPCHK(x) hipchk((x), #x)
-
-struct Buf {
-    char *base = nullptr;
-    size_t bytes = 0;
-    std::vector<char> loaded;  // rbuf: what must still be there
-    bool readonly = false;
-};
-std::map<std::string, Buf> g_bufs;
-std::string g_dir;
-
-std::vector<char> read_all(const std::string &path) {
-    FILE *f = fopen(path.c_str(), "rb");
-    if (!f) die("cannot open " + path);
-    std::vector<char> v;
-    char tmp[1 << 16];
-    size_t n;
-    while ((n = fread(tmp, 1, sizeof(tmp), f)) > 0) v.insert(v.end(), tmp, tmp + n);
-    fclose(f);
-    return v;
-}
-
-void make_buf(const std::string &name, size_t bytes, const std::string &file, bool readonly) {
-    if (g_bufs.count(name)) die("buffer " + name + " exists");
-    Buf b;
-    b.bytes = bytes;
-    b.readonly = readonly;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&b.base), bytes + 2 * kGuard));
-    HIPCHK(hipMemset(b.base, kFill, bytes + 2 * kGuard));
-    if (file != "-") {
-        std::vector<char> v = read_all(g_dir + "/" + file);
-        if (v.size() > bytes || (readonly && v.size() != bytes)) die(file + " does not fit buffer " + name);
-        if (!v.empty()) HIPCHK(hipMemcpy(b.base + kGuard, v.data(), v.size(), hipMemcpyHostToDevice));
-        if (readonly) b.loaded.swap(v);
-    } else if (readonly) {
-        die("rbuf " + name + " needs a file");
-    }
-    g_bufs[name] = std::move(b);
-}
-
-template <class T>
-T *ptr(const std::string &name, size_t need_bytes = 0) {
-    if (name == "-") return nullptr;
-    auto it = g_bufs.find(name);
-    if (it == g_bufs.end()) die("no buffer " + name);
-    if (it->second.bytes < need_bytes) die("buffer " + name + " holds " + std::to_string(it->second.bytes) + " bytes, the launch needs " + std::to_string(need_bytes));
-    return reinterpret_cast<T *>(it->second.base + kGuard);
-}
-
-void finish() {
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipGetLastError());
-}
-
-size_t end_case() {
-    size_t changed = 0;
-    for (auto &kv : g_bufs) {
-        Buf &b = kv.second;
-        std::vector<char> h(b.bytes + 2 * kGuard);
-        HIPCHK(hipMemcpy(h.data(), b.base, h.size(), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < kGuard; ++i) changed += (h[i] != (char)kFill) + (h[kGuard + b.bytes + i] != (char)kFill);
-        if (b.readonly) changed += memcmp(h.data() + kGuard, b.loaded.data(), b.bytes) != 0 ? 1 : 0;
-        HIPCHK(hipFree(b.base));
-    }
-    g_bufs.clear();
-    return changed;
-}
-
-float from_bits(unsigned long long u) {
-    const uint32_t v = (uint32_t)u;
-    float f;
-    memcpy(&f, &v, 4);
-    return f;
-}
-
-}  // namespace
+using namespace check;
 
 int main(int argc, char **argv) {
-    if (argc != 2) {
-        fprintf(stderr, "usage: match_stage_check DIR\n");
-        return 1;
-    }
-    g_dir = argv[1];
-    FILE *ops = fopen((g_dir + "/ops.txt").c_str(), "r");
-    if (!ops) die("cannot open " + g_dir + "/ops.txt");
-    FILE *results = fopen((g_dir + "/results.txt").c_str(), "w");
-    if (!results) die("cannot write " + g_dir + "/results.txt");
     ScreenScratch w{};
     float gerr = 0.f, gmax = 0.f;
     size_t n_tilemax = 0;  // what the scratch buffers hold, for the size checks below
     std::string names[7];
-    char linebuf[1024];
-    while (fgets(linebuf, sizeof(linebuf), ops)) {
-        std::istringstream in(linebuf);
-        std::string op;
-        if (!(in >> op)) continue;
-        std::vector<std::string> a;
-        for (std::string t; in >> t;) a.push_back(t);
-        auto I = [&](size_t i) -> long long {
-            if (i >= a.size()) die(op + ": too few arguments");
-            return atoll(a[i].c_str());
-        };
-        auto S = [&](size_t i) -> const std::string & {
-            if (i >= a.size()) die(op + ": too few arguments");
-            return a[i];
-        };
+    auto launch = [&](const OpLine &l) -> bool {
+        const std::string &op = l.op;
+        auto I = [&](size_t i) { return l.I(i); };
+        auto S = [&](size_t i) -> const std::string & { return l.S(i); };
         auto tiles_of = [](long long N) { return (size_t)((N + 127) / 128); };
         // the launches below write [F][tiles][4] coarse maxima, [256][F] workgroup maxima, F keys and the control words: the scratch must hold them
         auto need_scratch = [&](long long N, long long F) {
@@ -169,33 +54,29 @@ int main(int argc, char **argv) {
             (void)ptr<char>(names[4], (size_t)F * 8);
             if (w.pair_cap <= 0 || w.pair_cap % FRT_MATCH_SEL_SUB) die("pair_cap must be a positive multiple of the sub-list count");
         };
-        if (op == "case") {
-            g_case = S(0);
-        } else if (op == "buf" || op == "rbuf") {
-            make_buf(S(0), (size_t)I(1), S(2), op == "rbuf");
-        } else if (op == "shadow8") {
+        if (op == "shadow8") {
             const long long N = I(1);
             const size_t rows = tiles_of(N) * 128;
             launch_gallery_shadow8(ptr<float>(S(0), (size_t)N * 512 * 4), (int)N, 512, ptr<uint8_t>(S(2), rows * 512), ptr<float>(S(3), rows * 4), ptr<int>(S(4), 8),
                                    ptr<int>(S(4), 8) + 1, nullptr);
-            finish();
+            sync_and_check();
         } else if (op == "shadow8_rows") {
             const long long row0 = I(1), n = I(2);
             if (row0 < 0 || n < 0) die("bad row range");
             const size_t rows = tiles_of(row0 + n) * 128;
             launch_gallery_shadow8_rows(ptr<float>(S(0), (size_t)n * 512 * 4), (int)row0, (int)n, ptr<uint8_t>(S(3), rows * 512), ptr<float>(S(4), rows * 4),
                                         ptr<int>(S(5), 8), ptr<int>(S(5), 8) + 1, nullptr);
-            finish();
+            sync_and_check();
         } else if (op == "shadow16") {
             const long long N = I(1), D = I(2);
             if (D % 16) die("bad D");
             launch_gallery_shadow(ptr<float>(S(0), (size_t)N * D * 4), (int)N, (int)D, ptr<half_t>(S(3), gallery16_elems((int)N, (int)D) * 2), ptr<int>(S(4), 8) + 1, nullptr);
-            finish();
+            sync_and_check();
         } else if (op == "norm16") {
             const long long row0 = I(1), n = I(2), D = I(3);
             if (row0 < 0 || n < 0 || D % 16) die("bad row range");
             launch_rows_norm<half_t>(ptr<half_t>(S(0), gallery16_elems((int)(row0 + n), (int)D) * 2), (int)row0, (int)n, (int)D, ptr<int>(S(4), 8) + 1, nullptr);
-            finish();
+            sync_and_check();
         } else if (op == "bounds") {
             int bits[2];
             HIPCHK(hipMemcpy(bits, ptr<int>(S(0), 8), 8, hipMemcpyDeviceToHost));
@@ -232,18 +113,18 @@ int main(int argc, char **argv) {
             const half_t *g16 = ptr<half_t>(S(0), gallery16_elems((int)N, (int)D) * 2);
             if (!g16 && !(w.g8 && D == 512)) die("coarse: no shadow to scan");
             launch_match_coarse(g16, (int)N, (int)D, ptr<float>(S(3), (size_t)F * D * 4), (int)F, w, nullptr);
-            finish();
+            sync_and_check();
         } else if (op == "select_kth") {
             const long long N = I(0), D = I(1), F = I(3), K = I(4);
             need_scratch(N, F);
             if (K < 1 || K > match_topk_max()) die("select_kth: bad k");
             launch_match_select_kth((int)N, (int)D, ptr<float>(S(2), (size_t)F * D * 4), (int)F, (int)K, gmax, w, ptr<float>(S(5), (size_t)F * 4), I(6) != 0, nullptr);
-            finish();
+            sync_and_check();
         } else if (op == "select_thr") {
             const long long N = I(0), D = I(1), F = I(3);
             need_scratch(N, F);
             launch_match_select_threshold((int)N, (int)D, ptr<float>(S(2), (size_t)F * D * 4), (int)F, from_bits(I(4)), (int)I(5), gmax, w, I(6) != 0, nullptr);
-            finish();
+            sync_and_check();
         } else if (op == "screened") {
             const long long N = I(2), D = I(3), F = I(5), K = I(6), pb = I(9);
             need_scratch(N, F);
@@ -253,7 +134,7 @@ int main(int argc, char **argv) {
                                   ptr<float>(S(4), (size_t)F * D * 4), (int)F, (int)K, gmax, w, ptr<float>(S(7), (size_t)F * 4),
                                   ptr<MatchPartial>(S(8), fb * F * sizeof(MatchPartial)), (int)pb, ptr<int32_t>(S(10), (size_t)F * K * 4), ptr<float>(S(11), (size_t)F * K * 4),
                                   (int)I(12), nullptr);
-            finish();
+            sync_and_check();
         } else if (op == "rerank_excl") {
             const long long N = I(2), D = I(3), F = I(5), pb = I(7);
             need_scratch(N, F);
@@ -262,25 +143,11 @@ int main(int argc, char **argv) {
                                         ptr<float>(S(4), (size_t)F * D * 4), (int)F, true, w, ptr<MatchPartial>(S(6), fb * F * sizeof(MatchPartial)), (int)pb,
                                         ptr<int32_t>(S(8), (size_t)N * 4), ptr<int32_t>(S(9), (size_t)F * 4), ptr<int32_t>(S(10), (size_t)F * 4), ptr<float>(S(11), (size_t)F * 4),
                                         ptr<int>(S(12), 4), nullptr);
-            finish();
-        } else if (op == "dump") {
-            auto it = g_bufs.find(S(0));
-            if (it == g_bufs.end()) die("no buffer " + S(0));
-            std::vector<char> h(it->second.bytes);
-            HIPCHK(hipMemcpy(h.data(), it->second.base + kGuard, h.size(), hipMemcpyDeviceToHost));
-            FILE *f = fopen((g_dir + "/" + S(1)).c_str(), "wb");
-            if (!f || fwrite(h.data(), 1, h.size(), f) != h.size()) die("cannot write " + S(1));
-            fclose(f);
-        } else if (op == "end") {
-            fprintf(results, "%s\t%zu\n", g_case.c_str(), end_case());
-            fflush(results);
-            w = ScreenScratch{};
+            sync_and_check();
         } else {
-            die("unknown operation " + op);
+            return false;
         }
-    }
-    fclose(ops);
-    fclose(results);
-    if (!g_bufs.empty()) die("ops.txt ends inside a case");
-    return 0;
+        return true;
+    };
+    return run_ops(argc, argv, launch, [&] { w = ScreenScratch{}; });
 }

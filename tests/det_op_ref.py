@@ -388,14 +388,3 @@ def stem_chain(net, x):
         d, e_d = depthwise(y, e, wd, bd, stride)
         y, e = pointwise(d, e_d, wp, bp, runs_split(cin, wp.shape[0], y.shape[2], y.shape[3], stride))
     return y, e
-
-
-def build_harness(outdir):
-    """Compiles tests/cpp/det_op_check.cpp (host C++ against libfrt.so, the way arc_launch_ref.build_harness compiles its program); returns the path."""
-    import subprocess
-    pkg = os.path.join(ROOT, "face-recognition-cpp-tensorrt_amd")
-    exe = os.path.join(str(outdir), "det_op_check")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O2", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", os.path.join(pkg, "csrc"),
-                           "-x", "c++", os.path.join(ROOT, "tests", "cpp", "det_op_check.cpp"), "-x", "none", "-o", exe, os.path.join(pkg, "libfrt.so"),
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + pkg, "-Wl,-rpath,/opt/rocm/lib"])
-    return exe

@@ -72,7 +72,7 @@ import sys
 import numpy as np
 
 import slim_ref
-from match_stage_ref import Ops as _Ops, _bit_diff, _rng, fbits
+from launch_harness import Ops as _Ops, bit_diff as _bit_diff, fbits, rng as _rng
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -1042,8 +1042,3 @@ GROUPS = collections.OrderedDict([
     ("decode", group_decode), ("decode_nms_batched", group_batched), ("three_calls", group_sequence), ("nms_orders", group_nms_orders),
     ("slim_batched", group_slim), ("landmarks", group_landmarks), ("crop", group_crop), ("align", group_align), ("pack_results", group_pack),
 ])
-
-
-def build_harness(outdir):
-    import arc_launch_ref
-    return arc_launch_ref.build_harness(outdir, program="det_tail_check")

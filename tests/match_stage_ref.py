@@ -66,9 +66,10 @@ Stage 6, chained: every row with float64 S >= the float64 k-th best S lies in a 
 """
 import functools
 import os
-import zlib
 
 import numpy as np
+
+from launch_harness import Ops as _Ops, bit_diff as _bit_diff, fbits, rng as _rng
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24
@@ -90,14 +91,6 @@ RATIOS_SEEN = {
     "f16_D256_B": {33: 0.0690, 130: 0.0690}, "f16_D512_B": {33: 0.0723, 130: 0.0723}, "i8_D512_chain": {33: 0.7070}, "f16_D512_chain": {33: 0.0723},
     "shadow8 sqrt(max_err2) / float64 error norm": 1.0000500,
 }
-
-
-def _rng(*what):
-    return np.random.default_rng([zlib.crc32(str(w).encode()) for w in what])
-
-
-def fbits(x):
-    return int(np.array(x, np.float32).view(np.uint32))
 
 
 def tiles_of(n):
@@ -145,37 +138,7 @@ def from_g8(flat):
 
 
 # ------------------------------------------------------------------------------------------------ the harness's operation list
-class Ops:
-    def __init__(self, dirname):
-        self.dir, self.lines, self.cases = str(dirname), [], []
-
-    def case(self, cid):
-        self.cases.append(cid)
-        self.lines.append("case " + cid)
-        self.cid = cid
-
-    def _file(self, name, arr):
-        fn = "%s.%s.in" % (self.cid, name)
-        np.ascontiguousarray(arr).tofile(os.path.join(self.dir, fn))
-        return fn
-
-    def buf(self, name, nbytes, arr=None):
-        self.lines.append("buf %s %d %s" % (name, nbytes, "-" if arr is None else self._file(name, arr)))
-
-    def rbuf(self, name, arr):
-        self.lines.append("rbuf %s %d %s" % (name, arr.nbytes, self._file(name, arr)))
-
-    def op(self, *a):
-        self.lines.append(" ".join(str(v) for v in a))
-
-    def dump(self, name, tag=""):
-        fn = "%s.%s%s.out" % (self.cid, name, tag)
-        self.lines.append("dump %s %s" % (name, fn))
-        return fn
-
-    def end(self):
-        self.lines.append("end")
-
+class Ops(_Ops):
     def scratch(self, F, tiles, pair_cap=8192, g8="-", scale="-", tilemax=None, wgmax=None, ctl=None, pairs=None, qkey=None):
         """the ScreenScratch buffers, exactly as large as the launches may write (every byte behind them is a guard)"""
         self.buf("tilemax", F * tiles * 16, tilemax)
@@ -184,35 +147,6 @@ class Ops:
         self.buf("ctl", CTL_WORDS * 4, ctl)
         self.buf("qkey", F * 8, qkey)
         self.op("scratch", "tilemax", "wgmax", "pairs", pair_cap, "ctl", "qkey", g8, scale)
-
-    def write(self):
-        with open(os.path.join(self.dir, "ops.txt"), "w") as f:
-            f.write("\n".join(self.lines) + "\n")
-
-    def read(self, fn, dtype):
-        p = os.path.join(self.dir, fn)
-        return np.fromfile(p, dtype) if os.path.exists(p) else None
-
-    def results(self):
-        p = os.path.join(self.dir, "results.txt")
-        if not os.path.exists(p):
-            return {}
-        return {ln.split("\t")[0]: int(ln.split("\t")[1]) for ln in open(p).read().splitlines()}
-
-
-def _bit_diff(name, got, want):
-    """[] or one message: two arrays compared bit for bit"""
-    if got is None:
-        return ["%s was not written" % name]
-    want = np.ascontiguousarray(want)
-    if got.size != want.size:
-        return ["%s: %d elements, expected %d" % (name, got.size, want.size)]
-    bits = {1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[want.dtype.itemsize]
-    ne = got.view(bits).reshape(-1) != want.view(bits).reshape(-1)
-    if ne.any():
-        i = int(np.argmax(ne))
-        return ["%s: %d of %d values differ, first at flat index %d: %r, reference %r" % (name, ne.sum(), ne.size, i, got.reshape(-1)[i], want.reshape(-1)[i])]
-    return []
 
 
 # ------------------------------------------------------------------------------------------------ stage 1: shadow build
@@ -1232,8 +1166,3 @@ GROUPS = {
     "chain_i8": _single(build_coarse_b, "i8", 512, True),
     "chain_f16": _single(build_coarse_b, "f16", 512, True),
 }
-
-
-def build_harness(outdir):
-    import arc_launch_ref
-    return arc_launch_ref.build_harness(outdir, program="match_stage_check")

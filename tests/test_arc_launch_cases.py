@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import arc_launch_ref as R
+from launch_harness import build
 
 
 def test_cases_cover_every_selected_plan_line():
@@ -27,7 +28,7 @@ def test_cases_cover_every_selected_plan_line():
 
 
 def test_harness_plans_the_golden_label_for_every_case(tmp_path):
-    exe = R.build_harness(tmp_path)
+    exe = build(tmp_path, "arc_launch_check")
     cases = R.cases()
     R.write_manifest(str(tmp_path), cases)
     out = subprocess.run([exe, "--plan", str(tmp_path)], capture_output=True, text=True, timeout=120)
@@ -84,7 +85,7 @@ def test_fused_cases_cover_every_se_plan_line():
 
 
 def test_harness_plans_the_four_twins_for_the_fused_cases(tmp_path):
-    exe = R.build_harness(tmp_path)
+    exe = build(tmp_path, "arc_launch_check")
     cases = R.fused_cases()
     R.write_manifest(str(tmp_path), cases)
     out = subprocess.run([exe, "--plan", str(tmp_path)], capture_output=True, text=True, timeout=120)
@@ -182,7 +183,7 @@ def test_fp32_cases_cover_every_description_of_every_unit_shape():
 def test_fp32_harness_describes_every_case_as_the_reference_does(tmp_path):
     """The harness compiles here, and the Conv32Args the product's descriptions (csrc/frt_arc_launches.hpp, the text forward_f32 compiles) give for
     each case are the geometry the float64 reference restates."""
-    exe = R.build_harness(tmp_path, "arc32_launch_check")
+    exe = build(tmp_path, "arc32_launch_check")
     cases = R.cases32()
     R.write_manifest32(str(tmp_path), cases, R.small_cases32())
     out = subprocess.run([exe, "--describe", str(tmp_path)], capture_output=True, text=True, timeout=120)

@@ -16,17 +16,13 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from launch_harness import build
 
-PKG = os.path.join(ROOT, "face-recognition-cpp-tensorrt_amd")
 BATCHES = range(1, 257)
 
 
 def run_host_program(tmp, name):
-    exe = str(tmp / name)
-    # host side only, but with hipcc: frt_kernels.h uses clang's vector types
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", os.path.join(PKG, "csrc"),
-                           "-x", "c++", os.path.join(ROOT, "tests", "cpp", name + ".cpp"), "-x", "none", "-o", exe, os.path.join(PKG, "libfrt.so"),
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build(tmp, name)
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     return out.stdout.splitlines()

@@ -7,16 +7,11 @@ import os
 import subprocess
 
 from conftest import ROOT
-
-PKG = os.path.join(ROOT, "face-recognition-cpp-tensorrt_amd")
+from launch_harness import build
 
 
 def test_conv_plan_matches_the_recorded_dispatch(tmp_path):
-    exe = str(tmp_path / "conv_plan_dump")
-    # host side only, but with hipcc: frt_kernels.h uses clang's vector types
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", os.path.join(PKG, "csrc"),
-                           "-x", "c++", os.path.join(ROOT, "tests", "cpp", "conv_plan_dump.cpp"), "-x", "none", "-o", exe, os.path.join(PKG, "libfrt.so"),
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build(tmp_path, "conv_plan_dump")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     got = out.stdout.splitlines()

@@ -9,34 +9,25 @@ normalisation; here each description forward_f32 builds (csrc/frt_arc_launches.h
 One harness process per unit shape and one for the three small launches, each under its own timeout.  A process that ends on a HIP error, a
 signal or the timeout ends the module: the remaining parameters fail with its message and launch nothing."""
 import shutil
-import subprocess
 
 import pytest
 
 import arc_launch_ref as R
+from launch_harness import Runner, build
 
-_stopped = []  # the message of the harness process that ended on an error
+_runner = Runner()
 _ran = set()   # (unit shape, description, F, class) of the conv cases that ran and passed
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return R.build_harness(tmp_path_factory.mktemp("arc32_launch_check"), "arc32_launch_check")
-
-
-def _run(harness, work, what):
-    try:
-        run = subprocess.run([harness, str(work)], capture_output=True, text=True, timeout=300)
-        if run.returncode != 0:
-            _stopped.append("%s: exit status %d: %s" % (what, run.returncode, run.stderr.strip()[-500:]))
-    except subprocess.TimeoutExpired:
-        _stopped.append("%s: no end after 300 s" % (what,))
+    return build(tmp_path_factory.mktemp("arc32_launch_check"), "arc32_launch_check")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", range(len(R.SHAPES)), ids=["%d-%d_%dx%d_s%d" % (s[0], s[1], s[2], s[2], s[3]) for s in R.SHAPES])
 def test_conv32_launches_alone(shape, harness, tmp_path):
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     cases = [c for c in R.cases32() if c.shape == shape]
     work = tmp_path / "cases"
     work.mkdir()
@@ -48,7 +39,7 @@ def test_conv32_launches_alone(shape, harness, tmp_path):
             want[c.id] = R.exact_case32(c, d, ref) if c.cls == "A" else {"out0": (ref["out0"], ref["bound0"])}
             R.write_case32(str(work), c, d)
         R.write_manifest32(str(work), cases)
-        _run(harness, work, R.SHAPES[shape])
+        _runner.run(harness, work, R.SHAPES[shape], 300)
         failures, passed = [], set()
         for c in cases:
             got = R.read_outputs32(str(work), c)
@@ -67,7 +58,7 @@ def test_conv32_launches_alone(shape, harness, tmp_path):
             failures += ["%s: %s" % (c.id, b) for b in bad + more]
             if not bad + more:
                 passed.add((c.shape, c.desc, c.F, c.cls))
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "%d of %d cases failed:\n%s" % (len({f.split(":")[0] for f in failures}), len(cases), "\n".join(failures[:40]))
         _ran.update(passed)
     finally:
@@ -86,7 +77,7 @@ def test_small_fp32_launches_alone(harness, tmp_path):
     "The three small fp32 launches").  The SE gate's allowance for the device expf, addition and division is measured, not derived:
     R.SE32_GATE_SEEN is the largest |gate - float64 gate| beyond the derived part seen on an MI355X, 4 x that is allowed.  Seen: nothing beyond it
     (largest error 1.18e-6, at least 2.1e-5 inside the derived part everywhere), so the allowance is 0."""
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     cases = R.small_cases32()
     work = tmp_path / "cases"
     work.mkdir()
@@ -96,7 +87,7 @@ def test_small_fp32_launches_alone(harness, tmp_path):
             inputs[c.id] = R.small_inputs32(c)
             R.write_small32(str(work), c, inputs[c.id])
         R.write_manifest32(str(work), [], cases)
-        _run(harness, work, "the small launches")
+        _runner.run(harness, work, "the small launches", 300)
         failures, beyond, raw = [], 0.0, 0.0
         for c in cases:
             got = R.read_small_outputs32(str(work), c)
@@ -118,7 +109,7 @@ def test_small_fp32_launches_alone(harness, tmp_path):
                 print("%s gate: max |err| = %.3g, max(err - derived part) = %.3g" % (c.id, err.max(), (err - derived).max()))
             failures += ["%s %s" % (c.id, b) for b in bad]
         print("SE gates: largest |gate - float64 gate| %.3g, beyond the derived part %.3g (allowed %.3g)" % (raw, beyond, R.SE32_GATE_ALLOW))
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "\n".join(failures[:40])
     finally:
         shutil.rmtree(str(work), ignore_errors=True)

@@ -9,20 +9,20 @@ The seven conv2_se lines with se=1 run as the twin instantiation with the whole 
 One harness process per unit shape, each under its own timeout.  A process that ends on a HIP error ends the module: the remaining
 parameters fail with its message and launch nothing."""
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import arc_launch_ref as R
+from launch_harness import Runner, build
 
-_stopped = []  # the message of the harness process that ended on an error
-_ran = {}      # unit shape -> labels that ran and passed
+_runner = Runner()
+_ran = {}  # unit shape -> labels that ran and passed
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return R.build_harness(tmp_path_factory.mktemp("arc_launch_check"))
+    return build(tmp_path_factory.mktemp("arc_launch_check"), "arc_launch_check")
 
 
 def _compare(case, want, outs, changed, label):
@@ -40,7 +40,7 @@ def _compare(case, want, outs, changed, label):
 @pytest.mark.gpu
 @pytest.mark.parametrize("shape", range(len(R.SHAPES)), ids=["%d-%d_%dx%d_s%d" % (s[0], s[1], s[2], s[2], s[3]) for s in R.SHAPES])
 def test_conv_launches_alone(shape, harness, tmp_path):
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     cases = [c for c in R.cases() if c.shape == shape]
     work = tmp_path / "cases"
     work.mkdir()
@@ -55,12 +55,7 @@ def test_conv_launches_alone(shape, harness, tmp_path):
                 want[c.id] = {k: (ref[k], ref["bound" + k[-1]]) for k in ("out0", "out1") if k in ref}
             R.write_case(str(work), c, d)
         R.write_manifest(str(work), cases)
-        try:
-            run = subprocess.run([harness, str(work)], capture_output=True, text=True, timeout=300)
-            if run.returncode != 0:
-                _stopped.append("%s: exit status %d: %s" % (R.SHAPES[shape], run.returncode, run.stderr.strip()[-500:]))
-        except subprocess.TimeoutExpired:
-            _stopped.append("%s: no end after 300 s" % (R.SHAPES[shape],))
+        _runner.run(harness, work, R.SHAPES[shape], 300)
         failures, labels = [], set()
         for c in cases:
             got = R.read_outputs(str(work), c)
@@ -73,7 +68,7 @@ def test_conv_launches_alone(shape, harness, tmp_path):
             failures += ["%s (%s): %s" % (c.id, c.label, b) for b in bad]
             if not bad:
                 labels.add(got[2])
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "%d of %d cases failed:\n%s" % (len({f.split(" ")[0] for f in failures}), len(cases), "\n".join(failures[:40]))
         _ran[shape] = labels
     finally:
@@ -94,7 +89,7 @@ def test_small_launches_alone(kind, harness, tmp_path):
     """launch_arc_input, launch_fc_slices + launch_fc_finalize and launch_se through the same harness (cases, references and bounds:
     arc_launch_ref, "the three small launches").  The SE gate's allowance for the device expf is measured, not derived: largest |gate - float64|
     seen on an MI355X 4.1e-7 (7x7x512, F = 3), allowed 4 x that = 1.64e-6 on top of the derived part."""
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     cases = R.small_cases(kind)
     work = tmp_path / "cases"
     work.mkdir()
@@ -104,12 +99,7 @@ def test_small_launches_alone(kind, harness, tmp_path):
             inputs[c.id] = R.small_inputs(c)
             R.write_small(str(work), c, inputs[c.id])
         R.write_small_manifest(str(work), cases)
-        try:
-            run = subprocess.run([harness, str(work)], capture_output=True, text=True, timeout=300)
-            if run.returncode != 0:
-                _stopped.append("%s: exit status %d: %s" % (kind, run.returncode, run.stderr.strip()[-500:]))
-        except subprocess.TimeoutExpired:
-            _stopped.append("%s: no end after 300 s" % kind)
+        _runner.run(harness, work, kind, 300)
         failures = []
         for c in cases:
             got = R.read_small_outputs(str(work), c)
@@ -134,7 +124,7 @@ def test_small_launches_alone(kind, harness, tmp_path):
                 if not (err <= bound).all():
                     i = tuple(int(v) for v in np.argwhere(~(err <= bound))[0])
                     failures.append("%s %s: %d values outside the bound, first at %s: %r, reference %r, bound %.3g" % (c.id, k, (~(err <= bound)).sum(), i, float(outs[k][i]), ref[i], bound[i]))
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "\n".join(failures[:40])
     finally:
         shutil.rmtree(str(work), ignore_errors=True)
@@ -151,7 +141,7 @@ def test_fused_se_launches_alone(shape, harness, tmp_path):
     alone (arc_launch_ref, "conv2 with the SE tail in its epilogue"): behind a primer launch with other tensors on the same scratch, class A bit
     for bit, class S inside its derived bound (max(err / bound) is printed), nothing outside the logical outputs, the partial sums, the counters
     and the flags written, every counter back at zero, every flag at the launch's epoch, and a third launch that writes the same bits."""
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     cases = [c for c in R.fused_cases() if c.shape == shape]
     work = tmp_path / "cases"
     work.mkdir()
@@ -167,12 +157,7 @@ def test_fused_se_launches_alone(shape, harness, tmp_path):
                 want[c.id] = {k: (ref[k], ref["bound" + k[-1]]) for k in ("out0", "out1")}
             R.write_case(str(work), c, d)
         R.write_manifest(str(work), cases)
-        try:
-            run = subprocess.run([harness, str(work)], capture_output=True, text=True, timeout=300)
-            if run.returncode != 0:
-                _stopped.append("%s: exit status %d: %s" % (R.SHAPES[shape], run.returncode, run.stderr.strip()[-500:]))
-        except subprocess.TimeoutExpired:
-            _stopped.append("%s: no end after 300 s" % (R.SHAPES[shape],))
+        _runner.run(harness, work, R.SHAPES[shape], 300)
         failures, passed = [], set()
         for c in cases:
             got = R.read_fused_outputs(str(work), c)
@@ -197,7 +182,7 @@ def test_fused_se_launches_alone(shape, harness, tmp_path):
             failures += ["%s (%s): %s" % (c.id, c.label, b) for b in bad + more]
             if not bad + more:
                 passed.add((got.label, c.F))
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "%d of %d cases failed:\n%s" % (len({f.split(" ")[0] for f in failures}), len(cases), "\n".join(failures[:40]))
         _ran_fused[shape] = passed
     finally:

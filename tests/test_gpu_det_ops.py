@@ -52,12 +52,12 @@ the whole bound), 0.21 for the first conv, below 0.18 everywhere else - with the
 of 16 channels, no hi / lo terms) and only the launches that det_op_ref.runs_split names to the split kernels' bound."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import det_op_ref as R
+from launch_harness import Runner, build, read_results
 
 GEOM = {"640x640": (640, 640), "100x172": (100, 172), "101x173": (101, 173), "96x160": (96, 160)}
 # (blob, geometry, B, run the u8 launchers, range-edge ops)
@@ -67,13 +67,13 @@ CASES += [("det", "101x173", 1, True, ()), ("det", "101x173", 2, True, ()), ("de
 CASES += [("det", "96x160", B, True, ()) for B in (1, 3)]
 MAX_B = {("det", "640x640"): 12, ("det", "100x172"): 6, ("det", "101x173"): 2, ("det_ldm", "100x172"): 2, ("det", "96x160"): 3}
 
-_stopped = []  # the message of the harness process that ended on an error
-_refs = {}     # (blob, geometry) -> (frames, x, net, ops, cache) for the largest batch of the geometry, computed once
+_runner = Runner()
+_refs = {}  # (blob, geometry) -> (frames, x, net, ops, cache) for the largest batch of the geometry, computed once
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return R.build_harness(tmp_path_factory.mktemp("det_op_check"))
+    return build(tmp_path_factory.mktemp("det_op_check"), "det_op_check", opt="-O2")
 
 
 def _reference(synth, blobs, blob, geom):
@@ -212,7 +212,7 @@ def prepare(wd, blob_path, refs, geom, B, u8, edges):
 @pytest.mark.gpu
 @pytest.mark.parametrize("blob,geom,B,u8,edges", CASES, ids=["%s-%s-B%d" % c[:3] for c in CASES])
 def test_det_ops_alone(blob, geom, B, u8, edges, harness, synth, blobs, tmp_path):
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     refs = _reference(synth, blobs, blob, geom)
     frames, x, net, ops, cache = refs
     h, w = GEOM[geom]
@@ -221,16 +221,9 @@ def test_det_ops_alone(blob, geom, B, u8, edges, harness, synth, blobs, tmp_path
     wd = str(work)
     try:
         edge_ref = prepare(wd, blobs(blob)[0], refs, geom, B, u8, edges)
-        try:
-            run = subprocess.run([harness, wd], capture_output=True, text=True, timeout=120)
-            if run.returncode != 0:
-                _stopped.append("%s %s B = %d: exit status %d: %s" % (blob, geom, B, run.returncode, run.stderr.strip()[-500:]))
-        except subprocess.TimeoutExpired:
-            _stopped.append("%s %s B = %d: no end after 120 s" % (blob, geom, B))
+        _runner.run(harness, wd, "%s %s B = %d" % (blob, geom, B), 120)
         failures, ratios = [], {}
-        results = {}
-        if os.path.exists(os.path.join(wd, "results.txt")):
-            results = dict(ln.split("\t") for ln in open(os.path.join(wd, "results.txt")).read().splitlines())
+        results = {name: cols[0] for name, cols in read_results(wd).items()}
         if os.path.exists(os.path.join(wd, "oplist.txt")):
             listed = _parse_oplist(os.path.join(wd, "oplist.txt"))
             failures += _check_topology(listed, ops, geom, net.landmarks)
@@ -283,7 +276,7 @@ def test_det_ops_alone(blob, geom, B, u8, edges, harness, synth, blobs, tmp_path
                 failures += _compare("u8stem.out", rd("u8stem.out", (B,) + cache["stem"][0].shape[1:]), cache["stem"][0][:B], cache["stem"][1][:B], ratios)
         for name in sorted(ratios, key=lambda n: (int(n[2:].split(".")[0]) if n[2].isdigit() else 99, n)):
             print("%s %s B=%d %s: max(err / bound) = %.3f" % (blob, geom, B, name, ratios[name]))
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "%d failures:\n%s" % (len(failures), "\n".join(failures[:40]))
     finally:
         shutil.rmtree(wd, ignore_errors=True)
@@ -361,7 +354,7 @@ def _check_slim_topology(listed, net, ops):
 @pytest.mark.gpu
 @pytest.mark.parametrize("rfb,B", SLIM_CASES, ids=["%s-100x172-B%d" % ("rfb" if r else "slim", b) for r, b in SLIM_CASES])
 def test_slim_rfb_ops_alone(rfb, B, harness, frt, synth, tmp_path_factory, tmp_path):
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     path, net, ops = _slim_reference(frt, synth, tmp_path_factory, rfb)
     tag = "%s 100x172 B=%d" % ("rfb" if rfb else "slim", B)
     work = tmp_path / "ops"
@@ -369,15 +362,9 @@ def test_slim_rfb_ops_alone(rfb, B, harness, frt, synth, tmp_path_factory, tmp_p
     wd = str(work)
     try:
         prepare_slim(wd, path, ops, B)
-        try:
-            run = subprocess.run([harness, wd], capture_output=True, text=True, timeout=120)
-            if run.returncode != 0:
-                _stopped.append("%s: exit status %d: %s" % (tag, run.returncode, run.stderr.strip()[-500:]))
-        except subprocess.TimeoutExpired:
-            _stopped.append("%s: no end after 120 s" % tag)
-        failures, ratios, results, listed = [], {}, {}, {}
-        if os.path.exists(os.path.join(wd, "results.txt")):
-            results = dict(ln.split("\t") for ln in open(os.path.join(wd, "results.txt")).read().splitlines())
+        _runner.run(harness, wd, tag, 120)
+        failures, ratios, listed = [], {}, {}
+        results = {name: cols[0] for name, cols in read_results(wd).items()}
         if os.path.exists(os.path.join(wd, "oplist.txt")):
             listed = _parse_oplist(os.path.join(wd, "oplist.txt"))
         if sorted(listed) != list(range(len(ops))):
@@ -422,7 +409,7 @@ def test_slim_rfb_ops_alone(rfb, B, harness, frt, synth, tmp_path_factory, tmp_p
                     failures += _compare("%s.p%d.out2" % (name, k), rd("%s.p%d.out2" % (name, k), (B,) + p.out2.shape[1:]), p.out2[:B], p.bound2[:B], ratios)
         for name in sorted(ratios, key=lambda n: (int(n[2:].split(".")[0]), n)):
             print("%s %s: max(err / bound) = %.3f" % (tag, name, ratios[name]))
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "%d failures:\n%s" % (len(failures), "\n".join(failures[:40]))
     finally:
         shutil.rmtree(wd, ignore_errors=True)

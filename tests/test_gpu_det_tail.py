@@ -18,38 +18,33 @@ decode_kernel zeroes the score of a lane past A before it compares, so the guard
 whether or not `in_range` stands in `take`; what tells the two apart is a NEGATIVE threshold (every finite score is a candidate, and a lane
 past A with its score of 0 would be one too): the decode_*_neg cases, count == A exactly."""
 import shutil
-import subprocess
 
 import pytest
 
 import det_tail_ref as R
+from launch_harness import Runner, build
 
-_stopped = []  # the message of the harness process that ended on an error
+_runner = Runner()
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return R.build_harness(tmp_path_factory.mktemp("det_tail_check"))
+    return build(tmp_path_factory.mktemp("det_tail_check"), "det_tail_check")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("group", list(R.GROUPS))
 def test_det_tail_alone(group, harness, tmp_path):
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     work = tmp_path / "cases"
     work.mkdir()
     try:
         ops = R.Ops(work)
         check = R.GROUPS[group](ops)
         ops.write()
-        try:
-            run = subprocess.run([harness, str(work)], capture_output=True, text=True, timeout=120)
-            if run.returncode != 0:
-                _stopped.append("%s: exit status %d: %s" % (group, run.returncode, run.stderr.strip()[-500:]))
-        except subprocess.TimeoutExpired:
-            _stopped.append("%s: no end after 120 s" % group)
+        _runner.run(harness, work, group, 120)
         failures = check()
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "%d checks failed:\n%s" % (len(failures), "\n".join(failures[:40]))
     finally:
         shutil.rmtree(str(work), ignore_errors=True)

@@ -11,38 +11,33 @@ shadow; sqrt(max_err2) 1.0000500 x the float64 error norm.  The figure of every 
 One harness process per stage group, each under its own timeout.  A process that ends on a HIP error or at its timeout ends the module: the
 remaining parameters fail with its message and launch nothing."""
 import shutil
-import subprocess
 
 import pytest
 
 import match_stage_ref as R
+from launch_harness import Runner, build
 
-_stopped = []  # the message of the harness process that ended on an error
+_runner = Runner()
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return R.build_harness(tmp_path_factory.mktemp("match_stage_check"))
+    return build(tmp_path_factory.mktemp("match_stage_check"), "match_stage_check")
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("group", list(R.GROUPS))
 def test_match_stage_alone(group, harness, tmp_path):
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     work = tmp_path / "cases"
     work.mkdir()
     try:
         ops = R.Ops(work)
         check = R.GROUPS[group](ops)
         ops.write()
-        try:
-            run = subprocess.run([harness, str(work)], capture_output=True, text=True, timeout=120)
-            if run.returncode != 0:
-                _stopped.append("%s: exit status %d: %s" % (group, run.returncode, run.stderr.strip()[-500:]))
-        except subprocess.TimeoutExpired:
-            _stopped.append("%s: no end after 120 s" % group)
+        _runner.run(harness, work, group, 120)
         failures = check()
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "%d checks failed:\n%s" % (len(failures), "\n".join(failures[:40]))
     finally:
         shutil.rmtree(str(work), ignore_errors=True)

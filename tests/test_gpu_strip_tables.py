@@ -10,19 +10,19 @@ inputs - out0 and out1 must equal float64 bit for bit - on buffers with guard pa
 One process runs F = 128 and then F = 113 on the same geometry: the table cached by the first launch serves the second, so it cannot depend on
 the batch.  One harness process per group, each under its own timeout; a process that ends on an error ends the module."""
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import arc_launch_ref as R
+from launch_harness import Runner, build
 
-_stopped = []
+_runner = Runner()
 
 
 @pytest.fixture(scope="module")
 def harness(tmp_path_factory):
-    return R.build_harness(tmp_path_factory.mktemp("strip_table_check"))
+    return build(tmp_path_factory.mktemp("strip_table_check"), "arc_launch_check")
 
 
 def _label(shape, desc, F):
@@ -62,7 +62,7 @@ def test_the_groups_select_the_strip_kernels():
 @pytest.mark.gpu
 @pytest.mark.parametrize("group", list(GROUPS))
 def test_strip_launches_at_table_boundaries(group, harness, tmp_path):
-    assert not _stopped, "not run: an earlier harness process ended on an error: " + _stopped[0]
+    _runner.require_running()
     cases = GROUPS[group]
     work = tmp_path / "cases"
     work.mkdir()
@@ -73,12 +73,7 @@ def test_strip_launches_at_table_boundaries(group, harness, tmp_path):
             want[c.id] = R.exact_case(c, d, R.reference(c, d))
             R.write_case(str(work), c, d)
         R.write_manifest(str(work), cases)  # (the harness runs the cases in this order, in one process)
-        try:
-            run = subprocess.run([harness, str(work)], capture_output=True, text=True, timeout=300)
-            if run.returncode != 0:
-                _stopped.append("%s: exit status %d: %s" % (group, run.returncode, run.stderr.strip()[-500:]))
-        except subprocess.TimeoutExpired:
-            _stopped.append("%s: no end after 300 s" % group)
+        _runner.run(harness, work, group, 300)
         failures = []
         for c in cases:
             got = R.read_outputs(str(work), c)
@@ -99,7 +94,7 @@ def test_strip_launches_at_table_boundaries(group, harness, tmp_path):
                     i = tuple(int(v) for v in np.argwhere(ne)[0])
                     failures.append("%s %s: %d of %d values differ, first at [f, oh, ow, c] = %s: %r, reference %r" %
                                     (c.id, k, ne.sum(), ne.size, i, float(outs[k][i]), float(want[c.id][k][i])))
-        assert not _stopped, _stopped[0]
+        _runner.require_ended_well()
         assert not failures, "%d failures:\n%s" % (len(failures), "\n".join(failures[:40]))
     finally:
         shutil.rmtree(str(work), ignore_errors=True)

@@ -10,25 +10,19 @@ space of tests/golden/arc_conv_plan.txt.  Here
     window is staged exactly once (eight 16-byte pieces, the ninth piece of a patch row is padding), every tap of every live output pixel
     reads the patch row that holds its input pixel - or a zero row outside the image - and the output pixels of all strips of the launch
     cover [0, B * H * W) exactly once."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from launch_harness import build
 
-PKG = os.path.join(ROOT, "face-recognition-cpp-tensorrt_amd")
 PROW = 144  # bytes per patch pixel row in LDS
 
 
 @pytest.fixture(scope="module")
 def dumped(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("strip_tables") / "strip_tables_dump")
-    # host side only, but with hipcc: frt_kernels.h uses clang's vector types
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "-std=c++17", "-O1", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I", "/opt/rocm/include", "-I", os.path.join(PKG, "csrc"),
-                           "-x", "c++", os.path.join(ROOT, "tests", "cpp", "strip_tables_dump.cpp"), "-x", "none", "-o", exe, os.path.join(PKG, "libfrt.so"),
-                           "-L/opt/rocm/lib", "-lamdhip64", "-Wl,-rpath," + PKG, "-Wl,-rpath,/opt/rocm/lib"])
+    exe = build(tmp_path_factory.mktemp("strip_tables"), "strip_tables_dump")
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     geoms, lines, i = [], out.stdout.splitlines(), 0

@@ -19,7 +19,7 @@ import tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-import det_op_ref as R  # noqa: E402
+import launch_harness  # noqa: E402
 import test_gpu_det_ops as T  # noqa: E402
 from conftest import load_pkg  # noqa: E402
 
@@ -46,7 +46,7 @@ def main():
     os.makedirs(out, exist_ok=True)
     frt = load_pkg()
     tmp = tempfile.mkdtemp(prefix="det_ops_cov_")
-    harness = R.build_harness(tmp)
+    harness = launch_harness.build(tmp, "det_op_check", opt="-O2")
     blobs = {}
 
     def blob(kind):
