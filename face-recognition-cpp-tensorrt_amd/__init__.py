@@ -121,6 +121,8 @@ ABI = {
     "frt_comm_sync": (_i, [_vp]),
     "frt_embedder_set_se_fused": (_i, [_vp, _i]),
     "frt_embedder_set_precision": (_i, [_vp, _i]),
+    "frt_embedder_set_flip": (_i, [_vp, _i]),
+    "frt_embedder_get_flip": (_i, [_vp, ctypes.POINTER(_i)]),
     "frt_jpeg_encode_batch_after": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "frt_detector_geometry": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_coalescer_create": (_i, [_vp, _vp, _vp, _i, _i, ctypes.POINTER(_vp)]),
@@ -783,6 +785,18 @@ class ArcFaceIR50:
         """``True``: fp32 activations / weights / products end to end (BASELINE configs[1]'s "fp32"; slow, a few faces per call);
         ``False`` (default): fp16 on the matrix cores with fp32 accumulation."""
         _check(lib.frt_embedder_set_precision(self._h, 1 if fp32 else 0))
+
+    def setFlip(self, on):
+        """``True``: flip-augmented embeddings, ``normalize(pre(face) + pre(mirrored face))``, on every path through this object
+        (frt_embedder_set_flip; about twice the recogniser time per face).  Gallery and probes must be embedded in the same mode."""
+        _check(lib.frt_embedder_set_flip(self._h, 1 if on else 0))
+
+    @property
+    def flip(self):
+        """Whether flip-augmented embeddings are on (``setFlip``)."""
+        on = _i(0)
+        _check(lib.frt_embedder_get_flip(self._h, ctypes.byref(on)))
+        return bool(on.value)
 
     def setSeFused(self, enable):
         """IR-SE only: SE tail inside conv2's epilogue (default) or as stand-alone launches (equal to float rounding)."""

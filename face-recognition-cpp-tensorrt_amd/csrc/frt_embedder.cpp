@@ -222,13 +222,21 @@ void frt_embedder::alloc_act_set(ActSet &a) {
         HIPCHK(hipMemset(a.se_counter, 0, 2 * F * sizeof(int)));  // (kept at zero between launches by the kernel)
         a.se_gate = arena.alloc<float>(F * 512);
     }
-    a.fc_partial = arena.alloc<float>((size_t)FC_SPLITS * F * 512);
+    a.fc_partial = arena.alloc<float>((size_t)FC_SPLITS * std::max<size_t>(F, 2) * 512);  // (flip mode at max_batch 1: two one-face passes, kept apart)
+    if (flip) a.pair = arena.alloc<float>(F * 3 * 112 * 112);
 }
 
 void frt_embedder::ensure_alt() {
     if (has_alt) return;
     alloc_act_set(act[1]);
     has_alt = true;
+}
+
+void frt_embedder::set_flip(bool on) {
+    if (on)
+        for (int i = 0; i < (has_alt ? 2 : 1); ++i)
+            if (!act[i].pair) act[i].pair = arena.alloc<float>((size_t)max_batch * 3 * 112 * 112);
+    flip = on;
 }
 
 // fp32 weights: 3x3 [Cout][Cin][3][3] -> [Cout][tap][Cin]; 1x1 and Linear as described at the kernels
@@ -273,18 +281,20 @@ void frt_embedder::build_f32() {
         f32.RES = dev(n.res);
         f32.gate = dev(n.gate);
     }
-    f32.fc_out = dev(n.fc_out);
+    f32.fc_out = dev(std::max(n.fc_out, (size_t)2 * 512));  // (flip mode at chunk 1: two one-face passes, kept apart)
+    f32.pair = dev((size_t)f32.chunk * 3 * 112 * 112);
     HIPCHK(hipEventCreateWithFlags(&f32.done, hipEventDisableTiming));
 }
 
 // Backbone.forward in fp32 (model_irse.py:166-173), CHUNK faces at a time.  The per-channel parameters (folded BatchNorms, PReLU slopes, SE
 // weights, Linear bias) are the fp32 arrays the default path's epilogues use.
 void frt_embedder::forward_f32(const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s) {
-    ProfScope ps(2, "embed_network", flops_per_face * F, s);
+    ProfScope ps(2, "embed_network", flops_per_face * F * (flip ? 2 : 1), s);
     if (f32.busy) HIPCHK(hipStreamWaitEvent(s, f32.done, 0));
-    for (int f0 = 0; f0 < F; f0 += f32.chunk) {
-        const int n = std::min(f32.chunk, F - f0);
-        launch_arc32_input(chw_dev + (size_t)f0 * 3 * 112 * 112, in_w, in_s0, in_b0, in_slope, f32.A[0], n, s);
+    constexpr size_t IN = (size_t)3 * 112 * 112;
+    // the network up to the Linear's sums: x [n][3][112][112] -> sums [n][512]
+    auto network = [&](const float *x, int n, float *sums) {
+        launch_arc32_input(x, in_w, in_s0, in_b0, in_slope, f32.A[0], n, s);
         int cur = 0;
         const float *lead_s = in_s1, *lead_b = in_b1;  // the leading BatchNorm of the unit about to run
         for (size_t i = 0; i < units.size(); ++i) {
@@ -308,19 +318,38 @@ void frt_embedder::forward_f32(const float *chw_dev, int F, const int *valid_dev
             lead_b = u.bn;
             cur ^= 1;
         }
-        // output_layer: BN2d (on load) -> Flatten -> Linear -> BN1d -> L2 normalise
-        launch_fc32(f32.A[cur], lead_s, lead_b, f32.wfc, f32.fc_out, n, s);
-        launch_fc_finalize(f32.fc_out, 1, n, fc_bias, bn_s, bn_b, valid_dev ? valid_dev + f0 : nullptr, out_dev + (size_t)f0 * 512, s);
+        // output_layer: BN2d (on load) -> Flatten -> Linear (-> BN1d -> L2 normalise: the finalize launches below)
+        launch_fc32(f32.A[cur], lead_s, lead_b, f32.wfc, sums, n, s);
+    };
+    if (!flip) {
+        for (int f0 = 0; f0 < F; f0 += f32.chunk) {
+            const int n = std::min(f32.chunk, F - f0);
+            network(chw_dev + (size_t)f0 * IN, n, f32.fc_out);
+            launch_fc_finalize(f32.fc_out, 1, n, fc_bias, bn_s, bn_b, valid_dev ? valid_dev + f0 : nullptr, out_dev + (size_t)f0 * 512, s);
+        }
+    } else if (f32.chunk == 1) {  // the face and its mirror image as two one-face passes
+        for (int f = 0; f < F; ++f) {
+            network(chw_dev + (size_t)f * IN, 1, f32.fc_out);
+            launch_arc_flip_mirror(chw_dev + (size_t)f * IN, f32.pair, 1, s);
+            network(f32.pair, 1, f32.fc_out + 512);
+            launch_fc_finalize_pair(f32.fc_out, f32.fc_out + 512, 1, 1, 1, fc_bias, bn_s, bn_b, valid_dev ? valid_dev + f : nullptr, out_dev + (size_t)f * 512, s);
+        }
+    } else {
+        const int half = f32.chunk / 2;
+        for (int f0 = 0; f0 < F; f0 += half) {
+            const int n = std::min(half, F - f0);
+            launch_arc_flip_pair(chw_dev + (size_t)f0 * IN, f32.pair, n, s);
+            network(f32.pair, 2 * n, f32.fc_out);
+            launch_fc_finalize_pair(f32.fc_out, f32.fc_out + (size_t)n * 512, 1, 2 * n, n, fc_bias, bn_s, bn_b, valid_dev ? valid_dev + f0 : nullptr,
+                                    out_dev + (size_t)f0 * 512, s);
+        }
     }
     HIPCHK(hipEventRecord(f32.done, s));
     f32.busy = true;
     HIPCHK(hipGetLastError());
 }
 
-void frt_embedder::forward(int set, const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s) {
-    if (fp32_mode) return forward_f32(chw_dev, F, valid_dev, out_dev, s);
-    ProfScope ps(2, "embed_network", flops_per_face * F, s);
-    const ActSet &A = act[set];
+void frt_embedder::run_network(const ActSet &A, const float *chw_dev, int F, float *partial, hipStream_t s) {
     ArcInputArgs ia{chw_dev, in_w, in_s0, in_b0, in_slope, in_s1, in_b1, A.Y[0], A.Z[0], F, 112, 112, in_wh};
     launch_arc_input(ia, s);
     int cur = 0;
@@ -346,9 +375,39 @@ void frt_embedder::forward(int set, const float *chw_dev, int F, const int *vali
         if (sch.se_tail) launch_se(sch.se, s);
         cur ^= 1;
     }
-    {  // Linear 25088 -> 512 as 49 K-slices over the NHWC-flattened BN2d output (Z), then slice sum + bias + BN1d + L2 norm
-        launch_fc_slices(A.Z[cur], wfc, F, A.fc_partial, s);
-        launch_fc_finalize(A.fc_partial, FC_SPLITS, F, fc_bias, bn_s, bn_b, valid_dev, out_dev, s);
+    // Linear 25088 -> 512 as 49 K-slices over the NHWC-flattened BN2d output (Z); the finalize launch adds the slices
+    launch_fc_slices(A.Z[cur], wfc, F, partial, s);
+}
+
+void frt_embedder::forward(int set, const float *chw_dev, int F, const int *valid_dev, float *out_dev, hipStream_t s) {
+    if (fp32_mode) return forward_f32(chw_dev, F, valid_dev, out_dev, s);
+    ProfScope ps(2, "embed_network", flops_per_face * F * (flip ? 2 : 1), s);
+    const ActSet &A = act[set];
+    constexpr size_t IN = (size_t)3 * 112 * 112;
+    if (!flip) {
+        run_network(A, chw_dev, F, A.fc_partial, s);
+        launch_fc_finalize(A.fc_partial, FC_SPLITS, F, fc_bias, bn_s, bn_b, valid_dev, out_dev, s);  // slice sum + bias + BN1d + L2 norm
+    } else if (max_batch == 1) {  // the face and its mirror image as two one-face passes, their slice sums kept apart
+        float *partial_m = A.fc_partial + (size_t)FC_SPLITS * 512;
+        for (int f = 0; f < F; ++f) {
+            run_network(A, chw_dev + (size_t)f * IN, 1, A.fc_partial, s);
+            launch_arc_flip_mirror(chw_dev + (size_t)f * IN, A.pair, 1, s);
+            run_network(A, A.pair, 1, partial_m, s);
+            launch_fc_finalize_pair(A.fc_partial, partial_m, FC_SPLITS, 1, 1, fc_bias, bn_s, bn_b, valid_dev ? valid_dev + f : nullptr, out_dev + (size_t)f * 512, s);
+        }
+    } else {  // sub-passes of max_batch / 2 faces: one network pass over the faces and, behind them, their mirror images
+        const int half = max_batch / 2;
+        for (int f0 = 0; f0 < F; f0 += half) {
+            const int n = std::min(half, F - f0);
+            {
+                ProfScope pk(1, "flip_pair_up", (double)n * IN, s);
+                launch_arc_flip_pair(chw_dev + (size_t)f0 * IN, A.pair, n, s);
+            }
+            run_network(A, A.pair, 2 * n, A.fc_partial, s);
+            ProfScope pk(1, "fc_finalize_pair", (double)n * 512, s);
+            launch_fc_finalize_pair(A.fc_partial, A.fc_partial + (size_t)n * 512, FC_SPLITS, 2 * n, n, fc_bias, bn_s, bn_b, valid_dev ? valid_dev + f0 : nullptr,
+                                    out_dev + (size_t)f0 * 512, s);
+        }
     }
     HIPCHK(hipGetLastError());
 }
@@ -623,6 +682,25 @@ int frt_embedder_set_precision(frt_embedder *e, int fp32) {
             HIPCHK(hipDeviceSynchronize());
         }
         e->fp32_mode = fp32 != 0;
+    });
+}
+
+int frt_embedder_set_flip(frt_embedder *e, int enable) {
+    return guarded([&] {
+        if (!e) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(e->mu);
+        use_device(e->device);
+        e->wait_idle(e->stream);  // the pipeline's passes in flight on either activation set
+        HIPCHK(hipStreamSynchronize(e->stream));
+        e->set_flip(enable != 0);
+    });
+}
+
+int frt_embedder_get_flip(const frt_embedder *e, int *enabled_out) {
+    return guarded([&] {
+        if (!e || !enabled_out) raise(FRT_ERR_INVALID, "null argument");
+        std::lock_guard<std::mutex> lk(const_cast<frt_embedder *>(e)->mu);
+        *enabled_out = e->flip ? 1 : 0;
     });
 }
 

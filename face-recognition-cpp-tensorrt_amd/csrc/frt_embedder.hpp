@@ -30,7 +30,8 @@ struct frt_embedder {
         half_t *Y[2] = {nullptr, nullptr}, *Z[2] = {nullptr, nullptr}, *T = nullptr, *SC = nullptr, *RES = nullptr;
         float *se_pool = nullptr;   // IR-SE: SE_SPLIT partial sums per (face, channel) ...
         int *se_counter = nullptr;  // ... and behind them [max_batch] arrival counters + [max_batch] gate-ready flags (zero between launches)
-        float *se_gate = nullptr, *fc_partial = nullptr;
+        float *se_gate = nullptr, *fc_partial = nullptr;  // fc_partial [FC_SPLITS][max(max_batch, 2)][512]
+        float *pair = nullptr;      // flip mode: the network input of a sub-pass [max_batch][3][112][112] (set_flip)
     } act[2];
     bool has_alt = false;  // act[1] is allocated
     void alloc_act_set(ActSet &a);
@@ -39,6 +40,12 @@ struct frt_embedder {
         return {a.Z[cur], a.Y[cur], a.T, a.SC, a.RES, a.Y[cur ^ 1], a.Z[cur ^ 1], a.se_pool, a.se_gate, a.se_counter, max_batch, d_se_error, zeros};
     }
     void ensure_alt();
+    // ---- flip-augmented embeddings (frt_embedder_set_flip; kernels_arc_flip.hip): normalize(pre(x) + pre(mirror x)).  forward() then runs
+    //      sub-passes of max_batch / 2 faces: pair-up into `pair`, the unchanged network on twice the faces, pair finalize
+    bool flip = false;
+    void set_flip(bool on);  // allocates the pair-up scratch of every activation set that exists (never forward(): it may run inside a capture)
+    // the network up to the Linear's slice sums: chw_dev [F][3][112][112] -> partial [FC_SPLITS][F][512]
+    void run_network(const ActSet &A, const float *chw_dev, int F, float *partial, hipStream_t s);
     float *d_in = nullptr;  // [max_batch][3][112][112]
     float *d_out = nullptr;
     half_t *zeros = nullptr;
@@ -78,7 +85,8 @@ struct frt_embedder {
         std::vector<void *> owned;   // device allocations of this mode
         std::vector<F32Unit> units;
         float *wfc = nullptr;        // [512][hw * 512 + c]
-        float *A[2] = {nullptr, nullptr}, *T = nullptr, *SCb = nullptr, *RES = nullptr, *gate = nullptr, *fc_out = nullptr;
+        float *A[2] = {nullptr, nullptr}, *T = nullptr, *SCb = nullptr, *RES = nullptr, *gate = nullptr, *fc_out = nullptr;  // fc_out [max(chunk, 2)][512]
+        float *pair = nullptr;       // flip mode: the network input of a sub-pass [chunk][3][112][112]
         int chunk = 0;               // faces per pass of this path
         hipEvent_t done = nullptr;   // end of the last pass: one activation set, so passes on different streams run one after the other
         bool busy = false;

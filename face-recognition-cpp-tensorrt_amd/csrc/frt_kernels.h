@@ -504,6 +504,16 @@ void launch_se32(const float *res, const float *w1, const float *w2, float *gate
                  hipStream_t s);
 void launch_fc_finalize(const float *partial, int splits, int F, const float *bias, const float *s, const float *b, const int *valid,
                         float *out, hipStream_t s_);
+// flip-augmented embeddings (kernels_arc_flip.hip; frt_embedder_set_flip).  All pointers 16-byte aligned.
+// chw [n][3][112][112] -> pair [2n][3][112][112]: faces 0 .. n-1 the originals, n .. 2n-1 the same images with the W axis reversed; bit-exact
+void launch_arc_flip_pair(const float *chw, float *pair, int n, hipStream_t s);
+// ... the mirror images alone -> mirror [n][3][112][112]
+void launch_arc_flip_mirror(const float *chw, float *mirror, int n, hipStream_t s);
+// partial_a, partial_b [splits][rows][512], each addressed at row f < n: pre = (slice sums in slice order + bias) * s + b of both, then
+// out[f] = (pre_a + pre_b) / max(|pre_a + pre_b|, 1e-12), zeros where valid[f] == 0 (valid may be null).  One 2n-face pass: partial_b =
+// partial_a + n * 512, rows = 2n.
+void launch_fc_finalize_pair(const float *partial_a, const float *partial_b, int splits, int rows, int n, const float *bias, const float *s, const float *b,
+                             const int *valid, float *out, hipStream_t s_);
 // SE tail (IR-SE): pool -> fc1 -> relu -> fc2 -> sigmoid -> scale, + shortcut, + next BN
 struct SeArgs {
     const half_t *res;   // [F][H][W][C] = BN2(conv2)

@@ -181,8 +181,13 @@ void frt_pipeline::later_stages(const CallRec *c, int nc, bool pipe3) {
     };
     // (the fp32 pass is never captured: its single activation set is handed from pass to pass through the host-tracked event f32.done,
     //  which must be a real record on every pass - and a graph captured in one precision must not be replayed in the other)
-    if (nc == 1 && !emb->fp32_mode) run_part(GraphKey{1, c[0].frames, nullptr, nullptr, c[0].n, c[0].slot, akey, (unsigned)eset}, es, !c[0].serial, stage_e);
-    else stage_e(es);
+    if (nc == 1 && !emb->fp32_mode) {
+        GraphKey key{1, c[0].frames, nullptr, nullptr, c[0].n, c[0].slot, akey, (unsigned)eset};
+        key.flip = emb->flip ? 1 : 0;  // (a graph captured in one mode never replays in the other)
+        run_part(key, es, !c[0].serial, stage_e);
+    } else {
+        stage_e(es);
+    }
     HIPCHK(hipEventRecord(emb->ev_busy[eset], es));
     emb->busy[eset] = true;
     if (pipe3) {

@@ -231,8 +231,9 @@ struct frt_pipeline {
         unsigned gallery_gen;
         int nsub = 0;  // part 2 of a merged call: its tickets' frame counts; 0 for everything else
         int sub_n[MAXSUB] = {};
+        int flip = 0;  // part 1: the recogniser's flip mode (frt_embedder_set_flip), whose launches the graph holds; 0 for everything else
         bool operator==(const GraphKey &o) const {
-            if (nsub != o.nsub) return false;
+            if (nsub != o.nsub || flip != o.flip) return false;
             for (int j = 0; j < nsub; ++j)
                 if (sub_n[j] != o.sub_n[j]) return false;
             return part == o.part && frames == o.frames && results == o.results && embeds == o.embeds && n == o.n && slot == o.slot && align == o.align &&

@@ -141,6 +141,15 @@ int frt_embedder_set_se_fused(frt_embedder *e, int enable);
  * fp32 = 1 re-reads the weight blob the object was created from and uploads fp32 copies (175 MB).  Pipelines with hipGraph replay on must be
  * told to re-capture (frt_pipeline_set_graph). */
 int frt_embedder_set_precision(frt_embedder *e, int fp32);
+/* Flip-augmented embeddings (test-time flip augmentation, the way ArcFace models are evaluated; no reference counterpart).  enable = 0
+ * (default): normalize(pre(x)), pre = the 512 values in front of the L2 normalisation.  enable = 1: normalize(pre(x) + pre(mirror x)), mirror
+ * = the crop with its left and right sides swapped, on every path that goes through this embedder (frt_embedder_infer / _forward /
+ * _forward_aligned / _embed_faces / _enrol_faces, the pipeline, the coalescer, the photo routes, either precision).  Gallery and probes must be
+ * embedded in the same mode: a flip embedding is a different vector (cosine ~ 0.7 to the plain one on the synthetic weights), so switching
+ * means re-enrolling.  About twice the recogniser time per face.  The call waits for the embedder's passes in flight, allocates the mode's
+ * scratch once and holds for passes enqueued after it; a pipeline keys its captured graphs by the mode.  get: enabled_out <- 0 / 1. */
+int frt_embedder_set_flip(frt_embedder *e, int enable);
+int frt_embedder_get_flip(const frt_embedder *e, int *enabled_out);
 
 /* ArcFaceIR50::preprocessFace (src/arcface.cpp:105-114): u8 BGR [in_h][in_w][3] -> float32 planar RGB. */
 int frt_embedder_preprocess_face(frt_embedder *e, const uint8_t *bgr_crop, float *chw_out);

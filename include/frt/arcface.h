@@ -118,6 +118,14 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     }
     // Extension (round 5): fp32 end-to-end recogniser (BASELINE configs[1]'s "fp32"; see frt_embedder_set_precision).  Default: fp16 MFMA.
     void setPrecisionFp32(bool on) { checkFrtStatus(frt_embedder_set_precision(h_, on ? 1 : 0)); }
+    // Extension: flip-augmented embeddings, normalize(pre(face) + pre(mirrored face)), on every path through this object (see
+    // frt_embedder_set_flip).  Gallery and probes must be embedded in the same mode: switching means re-enrolling.  Default: off.
+    void setFlipAugment(bool on) { checkFrtStatus(frt_embedder_set_flip(h_, on ? 1 : 0)); }
+    bool flipAugment() const {
+        int on = 0;
+        checkFrtStatus(frt_embedder_get_flip(h_, &on));
+        return on != 0;
+    }
     ArcFaceIR50(const ArcFaceIR50 &) = delete;
     ArcFaceIR50 &operator=(const ArcFaceIR50 &) = delete;
 
