@@ -170,6 +170,10 @@ ABI = {
     "frt_enrol_select_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "frt_pipeline_run_images": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "frt_pipeline_enrol_images": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "frt_tile_plan": (_i, [_i, _i, _i, _i, _vp, _vp, _i, ctypes.POINTER(_i)]),
+    "frt_cut_tiles": (_i, [_vp, _i, _i, _sz, _vp, _i, _i, _i, _vp, _i]),
+    "frt_merge_boxes": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, ctypes.POINTER(_i), _i]),
+    "frt_detector_find_faces_tiled": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_i)]),
     "frt_profile_enable": (_i, [_i]),
     "frt_profile_collect": (_i, [_vp, _sz, _vp, _vp, _i]),
 }
@@ -637,6 +641,26 @@ class RetinaFace:
                                                  frames.strides[0], _ptr(out), _ptr(n)))
         return [out[i, :n[i]].copy() for i in range(nf)]
 
+    def findFaceTiled(self, img, overlap=None, overview=True, metric=1, drop_cut=True, threshold=None, max_out=256, landmarks=False,
+                      sources=False):
+        """Large photos by tiles (frt_detector_find_faces_tiled): a photo of any size -> boxes in PHOTO coordinates, found on overlapping
+        frameHeight x frameWidth tiles (and, with overview, on the whole photo resized to one) and merged by one NMS on the device.
+        overlap: None = a quarter of the tile, an int, or (rows, cols); threshold None = the detector's nms_threshold; metric 0 IoU, 1
+        intersection over the smaller area.  At most maxFacesPerScene boxes per tile.  -> boxes [, landmarks [n][5][2]] [, source indices
+        tile * maxFacesPerScene + slot]."""
+        img = _photo(img)
+        opt = tileOptions(self.frameHeight, self.frameWidth, overlap, overview, metric, drop_cut, threshold)
+        max_out = int(max_out)
+        cap = max(max_out, 1)
+        out = np.zeros(cap, BBOX_DTYPE)
+        src = np.full(cap, -1, np.int32)
+        ldm = np.zeros((cap, 5, 2), np.float32) if landmarks else None
+        n = ctypes.c_int(0)
+        _check(lib.frt_detector_find_faces_tiled(self._h, _ptr(img), img.shape[0], img.shape[1], img.strides[0], ctypes.addressof(opt), max_out,
+                                                 _ptr(out), _ptr(ldm), _ptr(src), ctypes.byref(n)))
+        res = (out[:n.value].copy(),) + ((ldm[:n.value].copy(),) if landmarks else ()) + ((src[:n.value].copy(),) if sources else ())
+        return res[0] if len(res) == 1 else res
+
     def preprocess(self, img):
         img = np.ascontiguousarray(img, np.uint8)
         out = np.empty(self.inputShape, np.float32)
@@ -696,6 +720,75 @@ def alignFaces(frame, landmarks, device=0):
     out = np.zeros((len(lm), 112, 112, 3), np.uint8)
     _check(lib.frt_align_faces(_ptr(frame), frame.shape[0], frame.shape[1], frame.strides[0], _ptr(lm), len(lm), _ptr(out), device))
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# large photos by tiles (frt_tile_plan / frt_cut_tiles / frt_merge_boxes; RetinaFace.findFaceTiled)
+# ----------------------------------------------------------------------------------------------------------------------
+class TileOptions(ctypes.Structure):  # == frt_tile_options
+    _fields_ = [("overlap_rows", ctypes.c_int32), ("overlap_cols", ctypes.c_int32), ("overview", ctypes.c_int32), ("metric", ctypes.c_int32),
+                ("drop_cut", ctypes.c_int32), ("merge_threshold", ctypes.c_float)]
+
+
+TILE_DTYPE = np.dtype([("row0", "<i4"), ("col0", "<i4"), ("rows", "<i4"), ("cols", "<i4"), ("kind", "<i4")])  # == frt_tile
+
+
+def tileOptions(tile_rows, tile_cols, overlap=None, overview=True, metric=1, drop_cut=True, threshold=None):
+    """overlap: None = a quarter of the tile on each axis, an int for both axes, or (rows, cols); threshold None = -1 (the detector's)."""
+    if overlap is None:
+        overlap = (int(tile_rows) // 4, int(tile_cols) // 4)
+    elif np.isscalar(overlap):
+        overlap = (overlap, overlap)
+    return TileOptions(int(overlap[0]), int(overlap[1]), int(bool(overview)), int(metric), int(bool(drop_cut)), -1.0 if threshold is None else float(threshold))
+
+
+def _photo(img):
+    """H x W x 3 u8 with contiguous pixels; a view with padded rows keeps its row stride."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError("a photo is an H x W x 3 uint8 array")
+    if a.shape[0] and a.shape[1] and (a.strides[2] != 1 or a.strides[1] != 3 or a.strides[0] < a.shape[1] * 3):
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def tilePlan(rows, cols, tile_rows, tile_cols, overlap=None, overview=True):
+    """frt_tile_plan -> the tiles as a TILE_DTYPE array: the grid row-major, the overview last."""
+    opt = tileOptions(tile_rows, tile_cols, overlap, overview)
+    tiles = np.zeros(4096, TILE_DTYPE)  # (the plan's own cap)
+    n = ctypes.c_int(0)
+    _check(lib.frt_tile_plan(int(rows), int(cols), int(tile_rows), int(tile_cols), ctypes.addressof(opt), _ptr(tiles), len(tiles), ctypes.byref(n)))
+    tiles = tiles[:n.value].copy()
+    return tiles
+
+
+def cutTiles(img, tiles, tile_rows, tile_cols, device=0):
+    """frt_cut_tiles -> u8 [n_tiles][tile_rows][tile_cols][3]: grid tiles cut from the photo (128 outside it), the overview resized."""
+    img = _photo(img)
+    tiles = np.ascontiguousarray(tiles, TILE_DTYPE)
+    out = np.zeros((len(tiles), int(tile_rows), int(tile_cols), 3), np.uint8)
+    _check(lib.frt_cut_tiles(_ptr(img), img.shape[0], img.shape[1], img.strides[0], _ptr(tiles), len(tiles), int(tile_rows), int(tile_cols),
+                             _ptr(out), device))
+    return out
+
+
+def mergeBoxes(boxes, n_boxes, tiles, photo_rows, photo_cols, tile_rows, tile_cols, metric=1, drop_cut=True, threshold=0.4, max_out=256,
+               device=0, full=False):
+    """frt_merge_boxes: boxes [n_tiles][slots] in tile coordinates + n_boxes [n_tiles] -> (boxes in photo coordinates, source indices
+    tile * slots + slot), best first.  full: the whole max_out-long arrays (zeros / -1 behind the count) and the count."""
+    boxes = np.ascontiguousarray(boxes, BBOX_DTYPE)
+    tiles = np.ascontiguousarray(tiles, TILE_DTYPE)
+    n_boxes = np.ascontiguousarray(n_boxes, np.int32)
+    if boxes.ndim != 2 or boxes.shape[0] != len(tiles) or n_boxes.shape != (len(tiles),):
+        raise ValueError("boxes are [n_tiles][slots], n_boxes [n_tiles]")
+    opt = tileOptions(tile_rows, tile_cols, 0, False, metric, drop_cut, threshold)
+    cap = max(int(max_out), 1)
+    out = np.zeros(cap, BBOX_DTYPE)
+    src = np.full(cap, -1, np.int32)
+    n = ctypes.c_int(0)
+    _check(lib.frt_merge_boxes(_ptr(boxes), _ptr(n_boxes), _ptr(tiles), len(tiles), boxes.shape[1], int(photo_rows), int(photo_cols), int(tile_rows),
+                               int(tile_cols), ctypes.addressof(opt), int(max_out), _ptr(out), _ptr(src), ctypes.byref(n), device))
+    return (out, src, n.value) if full else (out[:n.value].copy(), src[:n.value].copy())
 
 
 # ----------------------------------------------------------------------------------------------------------------------

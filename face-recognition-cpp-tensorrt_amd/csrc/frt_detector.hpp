@@ -74,6 +74,16 @@ struct frt_detector {
     float *d_ldm = nullptr;        // raw head output [B][A][10]
     int *d_kept_anchor = nullptr;  // [B][max_faces]
     float *d_landmarks = nullptr;  // decoded, frame coordinates [B][max_faces][10]
+    // large photos by tiles (frt_tiles.cpp): buffers that grow on demand, sized by the photo and its plan
+    struct Tiled {
+        DevBuf<uint8_t> photo;  // a frt_face_desc (launch_images_resize's, for the overview) in front of the photo's tightly packed bytes
+        DevBuf<frt_tile> tiles;
+        DevBuf<frt_bbox> boxes;  // [n_tiles][max_faces], tile coordinates
+        DevBuf<int32_t> n_boxes;
+        DevBuf<float> ldm;       // [n_tiles][max_faces][10]
+        TileMergeScratch merge;
+        DevBuf<float> ldm_out;   // [max_out][10]
+    } tiled;
 
   private:
     static void run(DwPwArgs &a, int n, hipStream_t s) {

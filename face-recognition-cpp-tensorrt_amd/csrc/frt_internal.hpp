@@ -94,6 +94,32 @@ struct PackPair {
     }
 };
 
+// Scratch and outputs of one launch_tile_merge (kernels_tiles.hip), grown to fit: the detector's tiled route keeps one, frt_merge_boxes a local one
+struct TileMergeScratch {
+    DevBuf<unsigned long long> keys, mask;
+    DevBuf<frt_bbox> mbox, out;
+    DevBuf<int> order, n_out;
+    DevBuf<int32_t> src;
+    // fills a's scratch and output pointers for `candidates` candidates and max_out outputs
+    void bind(TileMergeArgs &a, int candidates, int max_out) {
+        keys.reserve(candidates);
+        mbox.reserve(candidates);
+        order.reserve(candidates);
+        mask.reserve(tile_merge_mask_words(candidates));
+        out.reserve(max_out);
+        src.reserve(max_out);
+        n_out.reserve(1);
+        a.keys = keys.get();
+        a.mbox = mbox.get();
+        a.order = order.get();
+        a.mask = mask.get();
+        a.out = out.get();
+        a.src_out = src.get();
+        a.n_out = n_out.get();
+        a.max_out = max_out;
+    }
+};
+
 // Host waits: spin briefly, then poll at a low duty cycle, then block.
 //   1. busy-poll hipEventQuery / hipStreamQuery for FRT_WAIT_SPIN_US (default 200 us; frt_set_wait_spin_us): a reply that is about to arrive
 //      is picked up without a sleep / wake-up round trip (tens of microseconds on every synchronous call);

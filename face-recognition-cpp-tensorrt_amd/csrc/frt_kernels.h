@@ -246,6 +246,34 @@ void launch_faces_prepare(const uint8_t *arena, const frt_face_desc *desc, int F
 // the same kernel for whole photos: n images of any size at desc[i] of `arena` -> cv::resize INTER_LINEAR to dh x dw, u8 BGR [n][dh][dw][3]
 void launch_images_resize(const uint8_t *arena, const frt_face_desc *desc, int n, int dh, int dw, uint8_t *out, hipStream_t s);
 
+// ---------------------------------------------------------------- large photos by tiles (kernels_tiles.hip; semantics: include/frt.h)
+// grid tiles (kind 0) of tiles[0 .. n_tiles) cut from the photo into out [n_tiles][tile_rows][tile_cols][3], 128 outside the photo; the slot of
+// a kind 1 tile is left alone (launch_images_resize writes it).  out must be 16-byte aligned.
+void launch_cut_tiles(const uint8_t *photo, int rows, int cols, size_t row_stride, const frt_tile *tiles, int n_tiles, int tile_rows, int tile_cols,
+                      uint8_t *out, hipStream_t s);
+// boxes [n_tiles][slots] in tile coordinates -> out / src_out [max_out], n_out: map + cut test, sort, suppression bit matrix, one wave's scan.
+// 1 <= n_tiles * slots <= 16384.  Scratch per candidate: keys, mbox, order; mask: tile_merge_mask_words(n_tiles * slots) words.
+struct TileMergeArgs {
+    const frt_bbox *boxes;
+    const int32_t *n_boxes;
+    const frt_tile *tiles;
+    int n_tiles, slots, photo_rows, photo_cols, tile_rows, tile_cols, metric, drop_cut;
+    float thr;
+    int max_out;
+    unsigned long long *keys;
+    frt_bbox *mbox;
+    int *order;
+    unsigned long long *mask;
+    frt_bbox *out;
+    int32_t *src_out;
+    int *n_out;
+};
+size_t tile_merge_mask_words(int candidates);
+void launch_tile_merge(const TileMergeArgs &a, hipStream_t s);
+// landmarks of the kept boxes: ldm [n_tiles][slots][10] in tile coordinates -> out [max_out][10] in photo coordinates
+void launch_tile_landmarks(const float *ldm, const frt_tile *tiles, const int32_t *src, const int *n_out, int slots, int max_out, int photo_rows,
+                           int photo_cols, int tile_rows, int tile_cols, float *out, hipStream_t s);
+
 // ---------------------------------------------------------------- the "exactly one face" rule of /insert/face (kernels_enrol.hip)
 // results [n_frames][max_faces], embeds [n_frames][max_faces][512] -> status [n_frames] (frt_enrol_status), face_out [n_frames] (may be
 // null), the OK frames' embeddings to rows[*count ...], *count advanced; one workgroup

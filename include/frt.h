@@ -708,6 +708,65 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
                               frt_face_result *faces_out, float *embeds_out, int *first_row_out, int *n_enrolled_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Large photos by tiles.  Every route above squeezes a photo into ONE frame_w x frame_h frame, so a small face of a large photo falls below
+ * the smallest anchor.  Here the photo is cut into overlapping tiles of the detector's frame size (plus, optionally, the whole photo resized
+ * into one more tile: the overview, for the faces too large for a tile), the detector runs on the tiles in chunks of max_batch, every
+ * tile's boxes are mapped into photo coordinates and ONE greedy non-maximum suppression over all of them decides, on the device.  The
+ * reference has nothing like it, so the semantics are fixed here, to the integer (tests/tiled_ref.py restates them in numpy).
+ *   x is the row, y the column, corners inclusive (areas take + 1).  The tile is frame_h x frame_w = T_r x T_c.
+ *   Plan, per axis of length L with tile T, overlap V, stride S = T - V: L <= T is one tile at origin 0 (padded when L < T); else
+ *     n = ceil((L - T) / S) + 1 tiles at origin_i = min(i * S, L - T) - the last one is pulled inward, never padded.  Tiles are numbered
+ *     row-major over the grid, the overview last.  At most 4096 tiles per photo (FRT_ERR_CAPACITY).
+ *   Cut: grid tile t is the photo at [row0, row0 + T_r) x [col0, col0 + T_c); every byte outside the photo is 128 (the letterbox canvas
+ *     value).  The overview is frt_resize_frame(photo -> T_r x T_c).
+ *   Candidates: slot s < n_boxes[t] of tile t, source index t * slots + s; a NaN score is never one.
+ *   Cut test (kind 0, tile coordinates): x1 == 0 && row0 > 0, y1 == 0 && col0 > 0, x2 == T_r - 1 && row0 + T_r < photo_rows,
+ *     y2 == T_c - 1 && col0 + T_c < photo_cols: the box touches a tile edge that lies inside the photo.  drop_cut removes these first.
+ *   Map: kind 0 adds row0 / col0, drops a box with x1 >= photo_rows or y1 >= photo_cols (wholly in padding), clips to [0, photo - 1];
+ *     kind 1: x1' = (int64)x1 * photo_rows / T_r, x2' = (int64)(x2 + 1) * photo_rows / T_r - 1 raised to at least x1', columns alike, clip.
+ *   Merge: order by score descending, then tile, then slot ascending; greedy: the first live candidate is kept, every live one whose
+ *     overlap with it is >= the threshold dies; until none is live or max_out are kept.  Overlap is float32 in the detector's own operation
+ *     order: metric 0 = inter / (area_a + area_b - inter) (one tile with metric 0 is the detector's NMS bit for bit), metric 1 =
+ *     inter / min(area_a, area_b), which also catches a part-face box inside a whole-face box.
+ *   out[i] = box in photo coordinates + score, src_out[i] = source index; unused slots are zeros / -1.
+ *   Landmarks (blob with the LandmarkHead only) follow their box, unclipped: kind 0 x + col0, y + row0; kind 1 x * photo_cols / T_c,
+ *     y * photo_rows / T_r in float32.
+ *   Limits: n_tiles * slots <= 16384 and 1 <= max_out <= 16384, else FRT_ERR_CAPACITY.  The per-tile cap is the detector's max_faces: a
+ *     crowd wants a detector created with 16 to 32.
+ *   All arguments are checked before any device work: a NULL pointer, rows < 1, cols < 1, row_stride < cols * 3, an overlap outside
+ *     0 <= overlap < T, a metric other than 0 / 1 is FRT_ERR_INVALID; a call that fails writes nothing.
+ *   Out of scope here: the batched pipeline and the coalescer do not tile (no tiled frt_pipeline_run_images yet).  From boxes to embeddings:
+ *   frt_embedder_forward / _forward_aligned take the photo of any size with the boxes (and landmarks) this returns.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct frt_tile_options {
+    int32_t overlap_rows, overlap_cols; /* pixels neighbouring tiles share; 0 <= overlap < T on its axis                          */
+    int32_t overview;                   /* 1: one more tile, the whole photo resized to the tile                                   */
+    int32_t metric;                     /* 0: IoU, 1: intersection over the smaller area                                           */
+    int32_t drop_cut;                   /* 1: discard grid-tile boxes that touch a tile edge inside the photo                      */
+    float merge_threshold;              /* suppress at overlap >= this; negative: the detector's nms_threshold                    */
+} frt_tile_options;
+typedef struct frt_tile { int32_t row0, col0, rows, cols, kind; } frt_tile; /* kind 0: grid tile, rows / cols = its part inside the photo;
+                                                                             * kind 1: the overview, row0 = col0 = 0, rows / cols = the photo's */
+/* the plan alone (pure host, no device; of options only the overlaps and overview are read).  tiles_out may be NULL with capacity 0 to ask
+ * for the count; more tiles than capacity is FRT_ERR_CAPACITY with *n_tiles_out set and tiles_out untouched */
+int frt_tile_plan(int rows, int cols, int tile_rows, int tile_cols, const frt_tile_options *options, frt_tile *tiles_out, int capacity,
+                  int *n_tiles_out);
+/* the cut alone: host in, host out u8 [n_tiles][tile_rows][tile_cols][3] */
+int frt_cut_tiles(const uint8_t *bgr, int rows, int cols, size_t row_stride, const frt_tile *tiles, int n_tiles, int tile_rows, int tile_cols,
+                  uint8_t *out, int device);
+/* the device merge behind host pointers, also for callers who run a multi-scale scheme of their own: boxes [n_tiles][slots] in tile
+ * coordinates, n_boxes [n_tiles]; out [max_out], src_out [max_out], n_out.  There is no detector here: merge_threshold must be >= 0 */
+int frt_merge_boxes(const frt_bbox *boxes, const int32_t *n_boxes, const frt_tile *tiles, int n_tiles, int slots, int photo_rows,
+                    int photo_cols, int tile_rows, int tile_cols, const frt_tile_options *options, int max_out, frt_bbox *out,
+                    int32_t *src_out, int *n_out, int device);
+/* photo of any size -> boxes in photo coordinates: one upload, cut + detector + post-processing per chunk of max_batch tiles, one merge,
+ * one synchronisation.  options NULL: overlap = a quarter of the tile on each axis, overview 1, metric 1, drop_cut 1, threshold -1.
+ * slots = the detector's max_faces.  landmarks_out [max_out][10] may be NULL (FRT_ERR_FORMAT for a blob without the LandmarkHead);
+ * src_out [max_out] may be NULL */
+int frt_detector_find_faces_tiled(frt_detector *d, const uint8_t *bgr, int rows, int cols, size_t row_stride, const frt_tile_options *options,
+                                  int max_out, frt_bbox *out, float *landmarks_out, int32_t *src_out, int *n_out);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).
  * ------------------------------------------------------------------------------------------------------------------ */
 /* kinds: 0 = off (drops the records), 1 = time every launch of the dominant kernel family (conv3x3 MFMA), 2 = time every stage,

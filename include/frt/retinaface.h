@@ -139,6 +139,29 @@ class RetinaFace {
         landmarks.resize((size_t)n);
         return out;
     }
+    // Large photos by tiles (no reference counterpart; semantics: include/frt.h "Large photos by tiles").  photo is CV_8UC3 of ANY size: it
+    // is cut into overlapping frameHeight x frameWidth tiles on the device (plus the whole photo resized to one tile when options.overview),
+    // the detector runs on the tiles and one NMS merges their boxes.  Returns at most maxOut boxes in PHOTO coordinates, best first; at most
+    // maxFacesPerScene per tile, so a crowd wants a detector constructed with 16 to 32.  options NULL: overlap a quarter of the tile,
+    // overview, intersection over the smaller area, cut boxes dropped, the detector's nms_threshold.  landmarks (optional, engine file WITH
+    // LandmarkHead): (x0,y0,...,x4,y4) of every returned box, photo pixels.  The batched pipeline and the coalescer do not tile.
+    //   From boxes to names:  boxes = det.findFaceTiled(photo);  rec.forward(photo, boxes)  (or rec.forwardAligned(photo, boxes, landmarks)
+    //   with at most the recogniser's maxFacesPerScene boxes per call);  rec.featureMatching() - these take a photo of any size.
+    std::vector<struct Bbox> findFaceTiled(cv::Mat &photo, const frt_tile_options *options = nullptr, int maxOut = 256,
+                                           std::vector<std::array<float, 10>> *landmarks = nullptr, std::vector<int> *sources = nullptr) {
+        const size_t cap = (size_t)std::max(maxOut, 1);
+        std::vector<struct Bbox> out(cap);
+        std::vector<int32_t> src(cap);
+        if (landmarks) landmarks->assign(cap, std::array<float, 10>());
+        int n = 0;
+        checkFrtStatus(frt_detector_find_faces_tiled(h_, photo.data, photo.rows, photo.cols, (size_t)photo.step, options, maxOut,
+                                                     reinterpret_cast<frt_bbox *>(out.data()), landmarks ? (*landmarks)[0].data() : nullptr,
+                                                     src.data(), &n));
+        out.resize((size_t)n);
+        if (landmarks) landmarks->resize((size_t)n);
+        if (sources) sources->assign(src.begin(), src.begin() + n);
+        return out;
+    }
     frt_detector *handle() { return h_; }
 
   private:
