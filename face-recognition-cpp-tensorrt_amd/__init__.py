@@ -174,6 +174,8 @@ ABI = {
     "frt_cut_tiles": (_i, [_vp, _i, _i, _sz, _vp, _i, _i, _i, _vp, _i]),
     "frt_merge_boxes": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp, ctypes.POINTER(_i), _i]),
     "frt_detector_find_faces_tiled": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_i)]),
+    "frt_select_faces": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _i]),
+    "frt_pipeline_run_photo_tiled": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i)]),
     "frt_profile_enable": (_i, [_i]),
     "frt_profile_collect": (_i, [_vp, _sz, _vp, _vp, _i]),
 }
@@ -791,6 +793,34 @@ def mergeBoxes(boxes, n_boxes, tiles, photo_rows, photo_cols, tile_rows, tile_co
     return (out, src, n.value) if full else (out[:n.value].copy(), src[:n.value].copy())
 
 
+def selectFaces(boxes, src=None, landmarks=None, min_face=0, max_batch=128, device=0):
+    """frt_select_faces, the stage between the tiled merge and the recogniser: boxes [n] (+ source indices [n], landmarks [n][5][2]) -> the
+    boxes with min(x2 - x1, y2 - y1) >= min_face (min_face <= 0: all), dense and in order.  Returns a dict of the WHOLE arrays - "boxes",
+    "src" (None without src), "landmarks" (None without landmarks), "keep_pos" [n], zeros / -1 behind the count; "pass_count"
+    [ceil(n / max_batch)]: faces per recogniser pass - and "n_kept"."""
+    boxes = np.ascontiguousarray(boxes, BBOX_DTYPE).reshape(-1)
+    n = len(boxes)
+    s = l = None
+    if src is not None:
+        s = np.ascontiguousarray(src, np.int32).reshape(-1)
+        if s.size != n:
+            raise ValueError("selectFaces: one source index per box")
+    if landmarks is not None:
+        l = np.ascontiguousarray(landmarks, np.float32).reshape(-1, 5, 2)
+        if len(l) != n:
+            raise ValueError("selectFaces: five landmarks per box")
+    max_batch = int(max_batch)
+    out = np.zeros(n, BBOX_DTYPE)
+    src_out = np.full(n, -1, np.int32) if s is not None else None
+    ldm_out = np.zeros((n, 5, 2), np.float32) if l is not None else None
+    pos = np.full(n, -1, np.int32)
+    passes = np.zeros(-(-n // max_batch) if max_batch > 0 else 0, np.int32)
+    k = ctypes.c_int(0)
+    _check(lib.frt_select_faces(_ptr(boxes), _ptr(s), _ptr(l), n, int(min_face), max_batch, _ptr(out), _ptr(src_out), _ptr(ldm_out), _ptr(pos),
+                                _ptr(passes), ctypes.byref(k), device))
+    return dict(boxes=out, src=src_out, landmarks=ldm_out, keep_pos=pos, pass_count=passes, n_kept=k.value)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # face images instead of frames (frt_preprocess_faces / frt_embedder_embed_faces / frt_embedder_enrol_faces)
 # ----------------------------------------------------------------------------------------------------------------------
@@ -1134,6 +1164,29 @@ class Pipeline:
         crops = np.zeros((n * self.max_faces, 112, 112, 3), np.uint8) if want_crops else None
         _check(lib.frt_pipeline_run_images(self._h, arr, n, _ptr(res), _ptr(emb), _ptr(crops)))
         return (res, emb, crops) if want_crops else (res, emb)
+
+    def runTiled(self, photo, overlap=None, overview=True, metric=1, drop_cut=True, threshold=None, min_face=0, max_out=256, want_embeds=True,
+                 want_crops=False, landmarks=False, sources=False):
+        """A large photo by tiles, recognised in one call (frt_pipeline_run_photo_tiled): ``RetinaFace.findFaceTiled`` with these options,
+        the boxes with min(x2 - x1, y2 - y1) >= ``min_face`` kept, then ``forward`` (``forwardAligned`` after ``set_align(True)``) and the
+        top-1 match, all on the device, the photo uploaded once.  -> (records [n] with boxes in PHOTO coordinates and ``frame`` 0, embeddings
+        [n, 512] or None[, u8 crops [n, 112, 112, 3]][, landmarks [n, 5, 2]][, source indices [n]])."""
+        img = _photo(photo)
+        opt = tileOptions(self.det.frameHeight, self.det.frameWidth, overlap, overview, metric, drop_cut, threshold)
+        max_out = int(max_out)
+        cap = max(max_out, 1)
+        res = np.zeros(cap, RESULT_DTYPE)
+        emb = np.zeros((cap, 512), np.float32) if want_embeds else None
+        crops = np.zeros((cap, 112, 112, 3), np.uint8) if want_crops else None
+        ldm = np.zeros((cap, 5, 2), np.float32) if landmarks else None
+        src = np.full(cap, -1, np.int32) if sources else None
+        n = ctypes.c_int(0)
+        _check(lib.frt_pipeline_run_photo_tiled(self._h, _ptr(img), img.shape[0], img.shape[1], img.strides[0], ctypes.addressof(opt), int(min_face),
+                                                max_out, _ptr(res), _ptr(ldm), _ptr(emb), _ptr(crops), _ptr(src), ctypes.byref(n)))
+        k = n.value
+        out = (res[:k].copy(), emb[:k].copy() if want_embeds else None)
+        out += ((crops[:k].copy(),) if want_crops else ()) + ((ldm[:k].copy(),) if landmarks else ()) + ((src[:k].copy(),) if sources else ())
+        return out
 
     def enrolImages(self, classNames, images, labels=None):
         """/insert/face for whole photos: detect, require exactly one face, embed, and append the accepted photos' rows to the live gallery as

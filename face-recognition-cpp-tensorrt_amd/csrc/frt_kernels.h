@@ -273,6 +273,13 @@ void launch_tile_merge(const TileMergeArgs &a, hipStream_t s);
 // landmarks of the kept boxes: ldm [n_tiles][slots][10] in tile coordinates -> out [max_out][10] in photo coordinates
 void launch_tile_landmarks(const float *ldm, const frt_tile *tiles, const int32_t *src, const int *n_out, int slots, int max_out, int photo_rows,
                            int photo_cols, int tile_rows, int tile_cols, float *out, hipStream_t s);
+// the recogniser's work list out of a merged list: boxes / src (may be null) / ldm (may be null) [cap] with *n_in entries (device,
+// clamped to 0 .. cap) -> the boxes with min(x2 - x1, y2 - y1) >= min_face (min_face <= 0: all), dense and in order, in boxes_kept / src_kept
+// (with src) / ldm_kept (with ldm) / keep_pos [cap], zeros / -1 behind *n_kept; pass_count [ceil(cap / max_batch)] <- faces per pass of
+// max_batch.  One workgroup, cap <= 16384 is what the callers allow (any cap >= 0 works), max_batch >= 1.  Inputs and outputs must not overlap.
+void launch_tile_faces_select(const frt_bbox *boxes, const int32_t *src, const float *ldm, const int *n_in, int cap, int min_face, int max_batch,
+                              frt_bbox *boxes_kept, int32_t *src_kept, float *ldm_kept, int32_t *keep_pos, int *n_kept, int32_t *pass_count,
+                              hipStream_t s);
 
 // ---------------------------------------------------------------- the "exactly one face" rule of /insert/face (kernels_enrol.hip)
 // results [n_frames][max_faces], embeds [n_frames][max_faces][512] -> status [n_frames] (frt_enrol_status), face_out [n_frames] (may be

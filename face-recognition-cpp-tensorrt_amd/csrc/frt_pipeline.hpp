@@ -213,6 +213,19 @@ struct frt_pipeline {
     std::mutex images_mu;
     void release_images();  // (frt_pipeline_destroy)
 
+    // ---- a large photo by tiles, recognised in one call (frt_pipeline_run_photo_tiled, frt_tiles.cpp): the work list the select kernel
+    //      leaves (kept boxes / sources / landmarks / positions, faces per pass), the faces' flags, embeddings and matches, and the packed
+    //      records.  Grown on demand under images_mu, used again by later calls, freed with the pipeline.
+    struct TiledFaces {
+        DevBuf<frt_bbox> boxes;                    // [max_out]
+        DevBuf<int32_t> src, keep_pos, pass_count, idx;
+        DevBuf<int> n_kept, valid;
+        PinnedBuf<int> h_n_kept;                   // the one host read between detection and the first recogniser pass
+        DevBuf<float> ldm, embeds, sim;            // [max_out][10], [max_out][512], [max_out]
+        DevBuf<uint8_t> crops;                     // [kept][112][112][3], calls that ask for crops
+        DevBuf<frt_face_result> results;           // [max_out]
+    } tiled_faces;
+
     // ---- hipGraph replay.  A step is ~150 dependent launches; eager dispatch costs 3.1 us per dependent kernel on this part,
     //      a graph replay 1.8 us (tools/ubench/launch_gap.hip).  Each call is two graphs - the detector part on det_stream, the
     //      rest on `stream` - so the cross-call overlap of the two streams survives; the fork/join events stay ordinary stream

@@ -10,6 +10,7 @@
 //   tile_scan_kernel  ONE wave walks the sorted order 64 candidates at a time and ORs the rows of the kept ones into the dead set
 // Launch order on one stream is the only synchronisation between them: no counters, no atomics, nothing to reset between calls.
 // Overlap arithmetic is float32 in nms_kernel's operation order (this translation unit is compiled with -ffp-contract=off).
+// Behind the merge, for the route that goes on to the recogniser: tile_faces_select_kernel, the merged list -> the kept faces, dense.
 #include "frt_kernels.h"
 
 namespace {
@@ -252,6 +253,73 @@ __global__ void tile_landmarks_kernel(const float *__restrict__ ldm, const frt_t
     out[(size_t)t * 2 + 1] = y;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- faces of a tiled photo
+// The recogniser's work list out of the merged list (include/frt.h, "Recognising a large photo by tiles"): a box is kept iff
+// min(x2 - x1, y2 - y1) >= min_face - crop_faces_kernel's rh / rw, far corner excluded; min_face <= 0 keeps every box - and the kept ones
+// are packed in merge order.  ONE workgroup of 16 waves walks the list 1024 boxes at a time: a wave's ballot gives every lane its place
+// inside the wave, the 16 wave counts (LDS) the place of the wave inside the step, a running base the place of the step.  No atomics: the
+// order, and with it every output bit, is the same on every run.  Behind the count the outputs are zeros / -1; pass_count[j] is the number
+// of faces of recogniser pass j (faces [j * max_batch, (j + 1) * max_batch)), the crop / align kernels' n_boxes for that pass.
+__global__ __launch_bounds__(1024) void tile_faces_select_kernel(const frt_bbox *__restrict__ boxes, const int32_t *__restrict__ src,
+                                                                 const float *__restrict__ ldm, const int *__restrict__ n_in, int cap, int min_face,
+                                                                 int max_batch, frt_bbox *__restrict__ boxes_kept, int32_t *__restrict__ src_kept,
+                                                                 float *__restrict__ ldm_kept, int32_t *__restrict__ keep_pos,
+                                                                 int *__restrict__ n_kept, int32_t *__restrict__ pass_count) {
+    __shared__ int s_wave[16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    int n = *n_in;
+    n = n < 0 ? 0 : (n > cap ? cap : n);
+    int base = 0;
+    for (int i0 = 0; i0 < n; i0 += 1024) {  // (uniform: every thread takes every step)
+        const int i = i0 + tid;
+        frt_bbox b;
+        b.x1 = b.y1 = b.x2 = b.y2 = 0;
+        b.score = 0.f;
+        bool keep = false;
+        if (i < n) {
+            b = boxes[i];
+            const int rh = b.x2 - b.x1, rw = b.y2 - b.y1;
+            keep = min_face <= 0 || (rh < rw ? rh : rw) >= min_face;
+        }
+        const unsigned long long vote = __ballot(keep);
+        if (lane == 0) s_wave[w] = __popcll(vote);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int c = s_wave[k];
+            before += k < w ? c : 0;
+            total += c;
+        }
+        if (keep) {
+            const int pos = base + before + __popcll(vote & ((1ull << lane) - 1ull));  // pos <= i < n <= cap
+            boxes_kept[pos] = b;
+            keep_pos[pos] = i;
+            if (src_kept) src_kept[pos] = src[i];
+            if (ldm_kept)
+                for (int k = 0; k < 10; ++k) ldm_kept[(size_t)pos * 10 + k] = ldm[(size_t)i * 10 + k];
+        }
+        base += total;
+        __syncthreads();  // (s_wave is rewritten by the next step)
+    }
+    for (int i = base + tid; i < cap; i += 1024) {
+        frt_bbox z;
+        z.x1 = z.y1 = z.x2 = z.y2 = 0;
+        z.score = 0.f;
+        boxes_kept[i] = z;
+        keep_pos[i] = -1;
+        if (src_kept) src_kept[i] = -1;
+        if (ldm_kept)
+            for (int k = 0; k < 10; ++k) ldm_kept[(size_t)i * 10 + k] = 0.f;
+    }
+    if (tid == 0) *n_kept = base;
+    const int passes = (int)(((long long)cap + max_batch - 1) / max_batch);
+    for (int j = tid; j < passes; j += 1024) {
+        const long long left = (long long)base - (long long)j * max_batch;
+        pass_count[j] = (int32_t)(left < 0 ? 0 : (left > max_batch ? max_batch : left));
+    }
+}
+
 }  // namespace
 
 void launch_cut_tiles(const uint8_t *photo, int rows, int cols, size_t row_stride, const frt_tile *tiles, int n_tiles, int tile_rows, int tile_cols,
@@ -279,4 +347,11 @@ void launch_tile_landmarks(const float *ldm, const frt_tile *tiles, const int32_
                            int photo_cols, int tile_rows, int tile_cols, float *out, hipStream_t s) {
     hipLaunchKernelGGL(tile_landmarks_kernel, dim3((max_out * 5 + 255) / 256), dim3(256), 0, s, ldm, tiles, src, n_out, slots, max_out, photo_rows,
                        photo_cols, tile_rows, tile_cols, out);
+}
+
+void launch_tile_faces_select(const frt_bbox *boxes, const int32_t *src, const float *ldm, const int *n_in, int cap, int min_face, int max_batch,
+                              frt_bbox *boxes_kept, int32_t *src_kept, float *ldm_kept, int32_t *keep_pos, int *n_kept, int32_t *pass_count,
+                              hipStream_t s) {
+    hipLaunchKernelGGL(tile_faces_select_kernel, dim3(1), dim3(1024), 0, s, boxes, src, ldm, n_in, cap, min_face, max_batch, boxes_kept,
+                       src ? src_kept : nullptr, ldm ? ldm_kept : nullptr, keep_pos, n_kept, pass_count);
 }

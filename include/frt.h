@@ -735,8 +735,9 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
  *     crowd wants a detector created with 16 to 32.
  *   All arguments are checked before any device work: a NULL pointer, rows < 1, cols < 1, row_stride < cols * 3, an overlap outside
  *     0 <= overlap < T, a metric other than 0 / 1 is FRT_ERR_INVALID; a call that fails writes nothing.
- *   Out of scope here: the batched pipeline and the coalescer do not tile (no tiled frt_pipeline_run_images yet).  From boxes to embeddings:
- *   frt_embedder_forward / _forward_aligned take the photo of any size with the boxes (and landmarks) this returns.
+ *   From boxes to names in one call, on the device: "Recognising a large photo by tiles" below (frt_pipeline_run_photo_tiled).  By hand:
+ *   frt_embedder_forward / _forward_aligned take the photo of any size with the boxes (and landmarks) this returns.  The batched
+ *   frt_pipeline_submit / run_images and the coalescer do not tile.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct frt_tile_options {
     int32_t overlap_rows, overlap_cols; /* pixels neighbouring tiles share; 0 <= overlap < T on its axis                          */
@@ -765,6 +766,50 @@ int frt_merge_boxes(const frt_bbox *boxes, const int32_t *n_boxes, const frt_til
  * src_out [max_out] may be NULL */
 int frt_detector_find_faces_tiled(frt_detector *d, const uint8_t *bgr, int rows, int cols, size_t row_stride, const frt_tile_options *options,
                                   int max_out, frt_bbox *out, float *landmarks_out, int32_t *src_out, int *n_out);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Recognising a large photo by tiles.  frt_detector_find_faces_tiled stops at the boxes; this is the rest of the way - crop, embed, match -
+ * without the photo going up a second time and without the box list, the embeddings or the matches visiting the host in between.
+ *   Gate: a merged box is kept iff min(x2 - x1, y2 - y1) >= min_face - the extents of the crop's ROI, far corner excluded (a box of
+ *     11 x 11 pixels has x2 - x1 = 10).  min_face <= 0 keeps every box, a zero-extent one included: its crop is empty, valid = 0.
+ *   Work list: the kept boxes, dense and in merge order (score descending, then tile, then slot), with their source indices, their landmarks
+ *     and keep_pos = their position in the merged list; zeros / -1 behind the count.  pass_count[j] = clamp(n_kept - j * max_batch, 0,
+ *     max_batch), j < ceil(n / max_batch): the faces of recogniser pass j.  One launch for any list of 0 .. 16384 boxes, the same bits on
+ *     every run (a stable compaction, no atomics).
+ *   frt_pipeline_run_photo_tiled returns, to the bit, what this loop returns on the pipeline's three objects: frt_detector_find_faces_tiled
+ *     (max_out caps the merged list BEFORE the gate); the gate; frt_embedder_forward on the photo with the kept boxes - after
+ *     frt_pipeline_set_align(p, 1) frt_embedder_forward_aligned with the kept landmarks -; frt_matcher_top1 of those embeddings when the
+ *     pipeline has a matcher with rows.  Recogniser passes are cut every max_batch kept faces, as frt_embedder_forward cuts them; its flip
+ *     and fp32 modes apply.
+ *   results[i], i < *n_out: the box in photo coordinates with its score, frame = 0, valid / match_idx / match_sim as everywhere in the
+ *     pipeline: an empty ROI (or degenerate landmarks) is valid 0, match_idx -1, match_sim 0 and an all-zero embedding - reported here, not
+ *     as FRT_ERR_EMPTY_ROI: one bad box must not fail a 300-face photo -; no gallery: match_idx -1.  Behind *n_out: results are unused
+ *     slots (all zero but match_idx -1), src_out -1, landmarks_out 0; embeds_out and crops_out are written for the first *n_out faces only.
+ *   Flow: one upload, tiled detection and merge as above, the select launch, ONE host read (the kept count: how many passes to queue), per
+ *     pass crop or align out of the photo where the detector left it + the recogniser, one match, one pack, the downloads, one
+ *     synchronisation.  Serial on the detector's stream; never graph-captured, never paired or merged with other calls.
+ *   May run beside frt_pipeline_submit / wait / run of other threads.  Lock order: the pipeline's image-stage mutex, run_mu, then the
+ *     detector's, the embedder's and the matcher's mutex, all held to the end of the call; whatever a pairing mode holds or has pending is
+ *     flushed first, so the answers are those of pairing off.
+ *   Checked before any device work, and before the pipeline handle is looked at: a NULL bgr / results / n_out, rows < 1, cols < 1,
+ *     row_stride < cols * 3, a negative overlap, a metric other than 0 / 1: FRT_ERR_INVALID; max_out outside 1 .. 16384:
+ *     FRT_ERR_CAPACITY.  Then a NULL pipeline: FRT_ERR_INVALID.  Then what needs the detector's tile: an overlap >= T (FRT_ERR_INVALID),
+ *     landmarks_out with a blob without the LandmarkHead (FRT_ERR_FORMAT), more than 4096 tiles or n_tiles * max_faces > 16384
+ *     (FRT_ERR_CAPACITY).  A call that fails writes nothing.
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* the select launch behind host pointers: boxes [n], src [n] (may be NULL), landmarks [n][10] (may be NULL) -> boxes_out [n], src_out [n]
+ * (with src), landmarks_out [n][10] (with landmarks), keep_pos_out [n], pass_count_out [ceil(n / max_batch)], *n_kept_out.  n outside
+ * 0 .. 16384 is FRT_ERR_CAPACITY, max_batch < 1 or a NULL required pointer FRT_ERR_INVALID, before any device work; n == 0 writes
+ * *n_kept_out = 0 alone */
+int frt_select_faces(const frt_bbox *boxes, const int32_t *src /* may be NULL */, const float *landmarks /* may be NULL */, int n,
+                     int min_face, int max_batch, frt_bbox *boxes_out, int32_t *src_out, float *landmarks_out, int32_t *keep_pos_out,
+                     int32_t *pass_count_out, int *n_kept_out, int device);
+/* options NULL: frt_detector_find_faces_tiled's defaults */
+int frt_pipeline_run_photo_tiled(frt_pipeline *p, const uint8_t *bgr, int rows, int cols, size_t row_stride,
+                                 const frt_tile_options *options, int min_face, int max_out,
+                                 frt_face_result *results /* [max_out] */, float *landmarks_out /* [max_out][10], may be NULL */,
+                                 float *embeds_out /* [max_out][512], may be NULL */, uint8_t *crops_out /* [max_out][112][112][3], may be NULL */,
+                                 int32_t *src_out /* [max_out], may be NULL */, int *n_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).

@@ -223,16 +223,7 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
             matmul.galleryBegin(0, m_OUTPUT_D);
             matmul.galleryCommit();
         }
-        if (m_photoPipe && m_photoDet != detector.handle()) {
-            frt_pipeline_destroy(m_photoPipe);
-            m_photoPipe = nullptr;
-        }
-        if (!m_photoPipe) {
-            int maxBatch = 1;
-            checkFrtStatus(frt_detector_geometry(detector.handle(), nullptr, nullptr, &maxBatch, nullptr, nullptr));
-            checkFrtStatus(frt_pipeline_create(detector.handle(), h_, matmul.handle(), maxBatch, &m_photoPipe));
-            m_photoDet = detector.handle();
-        }
+        photoPipe(detector);
         const std::vector<frt_face_image> imgs = faceImages(images);
         const bool labelled = m_labelsSet && matmul.numRows() > 0;
         std::vector<int> labels;
@@ -246,6 +237,39 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         for (size_t i = 0; i < names.size(); ++i)
             if (st[i] == FRT_ENROL_OK) classNames.push_back(names[i]);
         classCount += enrolled;
+    }
+    // Extension: a large photo by tiles, recognised in one call (include/frt.h "Recognising a large photo by tiles"): what
+    // detector.findFaceTiled(photo, options, maxOut), this object's forward on the boxes with min(x2 - x1, y2 - y1) >= minFace and matchTop1
+    // return, with the photo uploaded once and everything between the stages left on the device.  photo is CV_8UC3 of ANY size.  Returns the
+    // kept boxes in PHOTO coordinates, best first; names / sims: per box the best gallery row's className and its similarity - "" and 0 for a
+    // box whose ROI is empty and for an empty gallery (valid, when asked for, tells the two apart).  Uses enrolImages' pipeline (created at
+    // the first call of either); passes are this object's maxBatchSize faces.
+    template <class Detector>
+    std::vector<struct Bbox> recognizeTiled(Detector &detector, cv::Mat &photo, std::vector<std::string> &names, std::vector<float> &sims,
+                                            const frt_tile_options *options = nullptr, int minFace = 0, int maxOut = 256,
+                                            std::vector<int> *valid = nullptr, std::vector<int> *sources = nullptr) {
+        photoPipe(detector);
+        const size_t cap = (size_t)std::max(maxOut, 1);
+        std::vector<frt_face_result> res(cap);
+        std::vector<int32_t> src(cap);
+        int n = 0;
+        checkFrtStatus(frt_pipeline_run_photo_tiled(m_photoPipe, photo.data, photo.rows, photo.cols, (size_t)photo.step, options, minFace, maxOut,
+                                                    res.data(), nullptr, nullptr, nullptr, src.data(), &n));
+        std::vector<struct Bbox> out((size_t)n);
+        names.assign((size_t)n, std::string());
+        sims.assign((size_t)n, 0.f);
+        if (valid) valid->assign((size_t)n, 0);
+        for (int i = 0; i < n; ++i) {
+            const frt_face_result &r = res[(size_t)i];
+            std::memcpy(&out[(size_t)i], &r.box, sizeof(frt_bbox));
+            if (valid) (*valid)[(size_t)i] = r.valid;
+            if (r.match_idx >= 0 && (size_t)r.match_idx < classNames.size()) {
+                names[(size_t)i] = classNames[(size_t)r.match_idx];
+                sims[(size_t)i] = r.match_sim;
+            }
+        }
+        if (sources) sources->assign(src.begin(), src.begin() + n);
+        return out;
     }
     // every row of that name, as /delete/user removes every face of the user; the rows behind them close up in order (the order a
     // /reload would read them in: src/db.cpp:316-346).  Returns how many there were.
@@ -571,6 +595,20 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     // What a call leaves behind for the next call of the same request - per calling THREAD (include/frt/coalesce.h): the reference keeps
     // it in the object and shares the object between its server's threads.
     // labels of matchTopIdentities: className <-> label, in first-appearance order; m_labelsSet: the matcher holds the labels of classNames
+    // the pipeline of enrolImages / recognizeTiled: created at the first call, again when the detector is another one
+    template <class Detector>
+    void photoPipe(Detector &detector) {
+        if (m_photoPipe && m_photoDet != detector.handle()) {
+            frt_pipeline_destroy(m_photoPipe);
+            m_photoPipe = nullptr;
+        }
+        if (!m_photoPipe) {
+            int maxBatch = 1;
+            checkFrtStatus(frt_detector_geometry(detector.handle(), nullptr, nullptr, &maxBatch, nullptr, nullptr));
+            checkFrtStatus(frt_pipeline_create(detector.handle(), h_, matmul.handle(), maxBatch, &m_photoPipe));
+            m_photoDet = detector.handle();
+        }
+    }
     static std::vector<frt_face_image> faceImages(const std::vector<cv::Mat> &faces) {  // row-strided Mats (ROIs) go as they are, not copied
         std::vector<frt_face_image> imgs(faces.size());
         for (size_t i = 0; i < faces.size(); ++i) {

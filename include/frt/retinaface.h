@@ -147,6 +147,7 @@ class RetinaFace {
     // LandmarkHead): (x0,y0,...,x4,y4) of every returned box, photo pixels.  The batched pipeline and the coalescer do not tile.
     //   From boxes to names:  boxes = det.findFaceTiled(photo);  rec.forward(photo, boxes)  (or rec.forwardAligned(photo, boxes, landmarks)
     //   with at most the recogniser's maxFacesPerScene boxes per call);  rec.featureMatching() - these take a photo of any size.
+    //   All of it in one call, the photo uploaded once:  rec.recognizeTiled(det, photo, names, sims)  (include/frt/arcface.h).
     std::vector<struct Bbox> findFaceTiled(cv::Mat &photo, const frt_tile_options *options = nullptr, int maxOut = 256,
                                            std::vector<std::array<float, 10>> *landmarks = nullptr, std::vector<int> *sources = nullptr) {
         const size_t cap = (size_t)std::max(maxOut, 1);
