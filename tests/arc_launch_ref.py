@@ -1,5 +1,6 @@
 """Cases and float64 reference for the recogniser's conv launches run one at a time (tests/cpp/arc_launch_check.cpp).  A generator and a
-reference, not a test: tests/test_arc_launch_cases.py (no GPU) and tests/test_gpu_arc_launches.py use it.  The launches of the fp32 mode
+reference, not a test: tests/test_arc_launch_cases.py (no GPU) and tests/test_gpu_arc_launches.py use it, and the two files that run the
+persistent kernels where they walk (tests/test_gpu_conv64_walk.py, tests/test_gpu_persistent_walks.py) at batches of their own.  The launches of the fp32 mode
 (tests/cpp/arc32_launch_check.cpp, tests/test_gpu_arc32_launches.py) have their cases, operation and bounds at the end of this file.
 
 Cases.  Every line of tests/golden/arc_conv_plan.txt whose description is conv1, conv2, conv2_scx, conv2_res or shortcut1x1 is run at the
@@ -84,6 +85,13 @@ def plan_lines():
     return out
 
 
+def plan_lines_of(label):
+    """Every line of the plan golden with this label, the conv2_se lines that are planned as the plain tail (se=0) included, in file order."""
+    out = [ln for ln, se in _plan() if ln.label == label]
+    assert not any(se for ln, se in _plan() if ln.label == label), label
+    return out
+
+
 def cases():
     """Class A at the first F (and first + 1) of every selected line; class B once per distinct (label, description) at first + 1."""
     out, seen = [], set()
@@ -111,7 +119,7 @@ def geometry(shape, desc):
     if desc == "conv2_scx":
         return Geometry(h, depth, ho, depth, 3, stride, "add", "scx", h, 2, cin)
     if desc == "conv2_se":  # planned as the plain tail; the strip kernels that carry the SE tail take a shortcut tensor of the output's geometry
-        assert stride == 1 or has_sc_conv
+        assert stride == 1 or has_sc_conv or shape == 0  # (unit 0: the input layer wrote the even positions only, as for conv2 below)
         return Geometry(h, depth, ho, depth, 3, stride, "add", "sc", ho, 1, 0)
     assert desc == "conv2"
     if shape == 0 or has_sc_conv:  # the input layer wrote the even positions only / the 1x1 launch's output
@@ -292,10 +300,12 @@ def write_case(dirname, case, d):
             np.ascontiguousarray(d[k]).tofile(os.path.join(dirname, "%s.%s" % (case.id, k)))
 
 
-def write_manifest(dirname, case_list):
+def write_manifest(dirname, case_list, kind="conv"):
+    """kind "conv_plain": the description is launched as it is planned - what "conv" does for every description but conv2_se, which "conv" moves
+    to its twin with the SE tail (the se=0 lines have none)."""
     with open(os.path.join(dirname, "cases.txt"), "w") as f:
         for c in case_list:
-            f.write("conv %s %d %d %d\n" % (c.id, c.shape, DESC.index(c.desc), c.F))
+            f.write("%s %s %d %d %d\n" % (kind, c.id, c.shape, DESC.index(c.desc), c.F))
 
 
 def read_outputs(dirname, case):
@@ -317,6 +327,16 @@ def read_outputs(dirname, case):
 # Input layer (launch_arc_input), F = 1, 2, 3, on what the product feeds: (u8 - 127.5) * 2^-7, exact in fp16.  The kernel multiplies fp16
 # weights w * s0 (rounded once, by the packer) and adds the fp16-rounded bias as a 28th product, so with K = 28
 #     e_acc = K u (sum|wh||x| + |bh|),   v = prelu(acc): e_v = max(1, |slope|) e_acc + u |v|,   y = fp16(v),   z = fp16(v s1 + b1) as out1 above.
+#   Class A of the input layer (input_cases(batches, "A"); run by tests/test_gpu_persistent_walks.py at F = 1, 6, 11), built as class A of
+#   launch_arc32_input below: the same x (odd multiples of 2^-8 below 1, a different random image in every batch slot), w in {-1, 0, 1}, s0 in
+#   +-{1/2, 1/4, 1/8} - the folded fp16 weights fp16(w s0) are exact -, the folded bias b0 distinct multiples of 1/4 (|b0| <= 8, fp16 numbers),
+#   slopes in {1/2, 1/4, 1/8, -1/4}, s1 in +-{1, 2}, b1 distinct multiples of 1/4.  Every product is a multiple of 2^-11 below 1/2 and every
+#   partial sum of the 28 terms, in any order, a multiple of 2^-11 below 2^5: exact in fp32.  v is a multiple of 2^-14 below 2^5 and
+#   t = v s1 + b1 one below 2^7 - 21 bits, exact in fp32 whether or not the multiply-add is contracted.  So y and z are each ONE fp16
+#   rounding (to nearest even) of a value the device holds exactly, the rounding float64 -> fp16 makes of the reference: bit for bit.  There
+#   is no tie to break differently, because no fp32 rounding comes before the store; and a multiple of 2^-14 is never an fp16 subnormal.
+#   small_reference asserts all of it in float64: x, fp16(w s0) and fp16(b0) exact, (sum|wh||x| + |bh|) 2^11 < 2^24, |v| 2^14 < 2^24, s1 a power of
+#   two >= 1, (|v s1| + |b1|) 2^14 < 2^24, t unchanged by astype(float32), everything far below the fp16 overflow, no two images equal.
 # Output Linear (launch_fc_slices + launch_fc_finalize), F = 1, 2, 33, 129: z and w in {-1, 0, 1} make every slice sum an integer, exact in
 # fp32 - the 49 slice sums are compared bit for bit - and their sum `pre` exact.  What remains is fp32: t = pre + bias, m = t s, v = m + b
 # (three roundings: e_v = u (2 |t s| + |v|)), tot = sum v^2 over 512 outputs (one rounding per square, a tree of depth <= 16:
@@ -342,9 +362,14 @@ WIDE = 1 + 2.0 ** -10
 Small = collections.namedtuple("Small", "kind id F H C sc_stride cls")
 
 
+def input_cases(batches, cls="B"):
+    """The input layer at these batches; class A (exact inputs) has ids of its own."""
+    return [Small("input", "input_F%d%s" % (F, "_A" if cls == "A" else ""), F, 112, 64, 0, cls) for F in batches]
+
+
 def small_cases(kind):
     if kind == "input":
-        return [Small("input", "input_F%d" % F, F, 112, 64, 0, "B") for F in (1, 2, 3)]
+        return input_cases((1, 2, 3))
     if kind == "fc":
         return [Small("fc", "fc_F%d" % F, F, 7, 512, 0, "A") for F in (1, 2, 33, 129)]
     assert kind == "se"
@@ -362,11 +387,19 @@ def small_inputs(c):
     if c.kind == "input":
         u8 = r("x").integers(0, 256, size=(c.F, 3, 112, 112))
         d["x"] = ((u8 - 127.5) * 2.0 ** -7).astype(np.float32)
-        d["w"] = (r("w").standard_normal((64, 27)) * np.sqrt(2.0 / 27)).astype(np.float32)
         p = np.zeros((5, 64), np.float32)
-        p[0], p[1] = _bn_like(r, "bn0", 64)
-        p[2] = 0.25 + 0.1 * r("slope").standard_normal(64)
-        p[3], p[4] = _bn_like(r, "bn1", 64)
+        if c.cls == "A":
+            d["w"] = _ternary(r("w"), (64, 27)).astype(np.float32)
+            p[0] = r("s0").choice([-1.0, 1.0], 64) * 2.0 ** r("s0e").choice([-1, -2, -3], 64)
+            p[1] = (r("b0").permutation(64) - 32) / 4.0
+            p[2] = r("slope").choice([0.5, 0.25, 0.125, -0.25], 64)
+            p[3] = r("s1").choice([-1.0, 1.0], 64) * 2.0 ** r("s1e").choice([0, 1], 64)
+            p[4] = (r("b1").permutation(64) - 32) / 4.0
+        else:
+            d["w"] = (r("w").standard_normal((64, 27)) * np.sqrt(2.0 / 27)).astype(np.float32)
+            p[0], p[1] = _bn_like(r, "bn0", 64)
+            p[2] = 0.25 + 0.1 * r("slope").standard_normal(64)
+            p[3], p[4] = _bn_like(r, "bn1", 64)
         d["p"] = p
     elif c.kind == "fc":
         d["x"] = _ternary(r("x"), (c.F, 25088))
@@ -427,6 +460,22 @@ def small_reference(c, d, gate_dev=None):
         x = np.ascontiguousarray(d["x"].transpose(0, 2, 3, 1)).astype(np.float16)
         assert np.array_equal(x.astype(np.float32).transpose(0, 3, 1, 2), d["x"])
         acc = conv64(x, wh, 1, 1) + bh
+        if c.cls == "A":  # the premises of the comment above, asserted; the outputs as the fp16 numbers they must be, bit for bit
+            mag = conv64(x, wh, 1, 1, absolute=True) + np.abs(bh)  # no partial sum, in any order, exceeds it
+            x8 = d["x"].astype(np.float64) * 256
+            assert np.array_equal(x8, np.rint(x8)) and (x8 % 2 != 0).all() and np.abs(x8).max() < 256, c.id
+            assert len({zlib.crc32(np.ascontiguousarray(img).tobytes()) for img in d["x"]}) == c.F, c.id  # a different image in every batch slot
+            assert set(np.unique(d["w"])) <= {-1.0, 0.0, 1.0} and set(np.unique(np.abs(p[0]))) <= {0.5, 0.25, 0.125}, c.id
+            assert np.array_equal(wh.astype(np.float64).reshape(64, 27), d["w"].astype(np.float64) * p[0][:, None]) and np.array_equal(bh, p[1]), c.id
+            assert np.array_equal(p[1] * 4, np.rint(p[1] * 4)) and len(np.unique(p[1])) == 64 and len(np.unique(p[4])) == 64, c.id
+            assert np.array_equal(acc * 2 ** 11, np.rint(acc * 2 ** 11)) and mag.max() * 2 ** 11 < 2 ** 24, (c.id, mag.max())
+            assert set(np.unique(p[2])) <= {0.5, 0.25, 0.125, -0.25} and set(np.unique(np.abs(p[3]))) <= {1.0, 2.0} and np.array_equal(p[4] * 4, np.rint(p[4] * 4)), c.id
+            v = np.where(acc > 0, acc, acc * p[2])
+            t = v * p[3] + p[4]
+            assert np.array_equal(v * 2 ** 14, np.rint(v * 2 ** 14)) and np.abs(v).max() * 2 ** 14 < 2 ** 24, c.id
+            assert np.array_equal(t * 2 ** 14, np.rint(t * 2 ** 14)) and (np.abs(v * p[3]) + np.abs(p[4])).max() * 2 ** 14 < 2 ** 24, c.id
+            assert np.array_equal(t.astype(np.float32), t) and np.array_equal(v.astype(np.float32), v) and max(np.abs(v).max(), np.abs(t).max()) < 2 ** 15, c.id
+            return {"out0": (t.astype(np.float16).astype(np.float64), None), "out1": (v[:, ::2, ::2].astype(np.float16).astype(np.float64), None)}
         e_acc = 28 * U * WIDE * (conv64(x, wh, 1, 1, absolute=True, dtype=np.float32) + np.abs(bh))
         v = np.where(acc > 0, acc, acc * p[2])
         e_v = np.maximum(1.0, np.abs(p[2])) * e_acc + U * np.abs(v)

@@ -18,6 +18,8 @@
 //   <id>.x0 / <id>.sc0   fp16, the tensors of the primer launch (the geometry of <id>.x / <id>.sc, other values)
 // and the line "<id>\t<twin label>\t<conv_se_fits_device>\t<n_parts>\t<changed slack halves>\t<changed scratch words outside the partial sums,
 // counters and flags>\t<partial sums not written>\t<counters not zero>\t<flags not at the epoch>\t<halves the third launch wrote differently>".
+// "conv_plain <id> <unit shape> <description> <F>" launches the description AS IT IS PLANNED, with the files and the result line of "conv": the
+// same for every description but conv2_se, whose se=0 plan lines are the plain tail (with the SE scratch) and have no twin to move to.
 // The three small launches go through the same buffers and checks (label: the launcher's name):
 //   "input <id> <F>"                   launch_arc_input: <id>.x fp32 [F][3][112][112], <id>.w fp32 [64][27], <id>.p fp32 [5][64] s0 b0 slope s1 b1
 //                                      -> out0 = z [F][112][112][64], out1 = y [F][56][56][64] (the even positions)
@@ -267,7 +269,7 @@ void run_se(const std::string &dir, const Case &c, FILE *results) {
 }
 
 void run_case(const std::string &dir, const Case &c, FILE *results) {
-    if (c.kind == "conv" && c.d != ARC_CONV2_SE) run_conv(dir, c, results);
+    if ((c.kind == "conv" && c.d != ARC_CONV2_SE) || c.kind == "conv_plain") run_conv(dir, c, results);
     if (c.kind == "conv" && c.d == ARC_CONV2_SE) run_conv_se(dir, c, results);
     if (c.kind == "input") run_input(dir, c, results);
     if (c.kind == "fc") run_fc(dir, c, results);
@@ -285,11 +287,12 @@ int main(int argc, char **argv) {
     if (plan_only) {
         for (const Case &c : cases) {
             ConvMfmaArgs a;
-            if (c.kind != "conv") continue;  // only the convs are planned
+            if (c.kind != "conv" && c.kind != "conv_plain") continue;  // only the convs are planned
             if (!describe(kShapes[c.shape], c.shape == 0, c.d, c.F, a)) die("case " + c.id + ": the unit has no such launch");
             const ConvPlan p = conv_plan(a);
-            if (c.d == ARC_CONV2_SE && !p.se_fused()) die("case " + c.id + ": planned as " + p.label + ", which has no twin with the SE tail");
-            printf("%s\t%s\n", c.id.c_str(), c.d == ARC_CONV2_SE ? p.se_label : p.label);  // the fused launch runs the twin
+            const bool twin = c.kind == "conv" && c.d == ARC_CONV2_SE;
+            if (twin && !p.se_fused()) die("case " + c.id + ": planned as " + p.label + ", which has no twin with the SE tail");
+            printf("%s\t%s\n", c.id.c_str(), twin ? p.se_label : p.label);  // the fused launch runs the twin
         }
         return 0;
     }

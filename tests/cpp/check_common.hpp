@@ -228,7 +228,7 @@ struct Case {
     int shape = 0, d = 0, F = 0, H = 0, C = 0, sc_stride = 0;
 };
 
-// DIR/cases.txt: "conv <id> <unit shape> <description> <F>", "input <id> <F>", "fc <id> <F>", "se <id> <H> <C> <F> <sc_stride>"
+// DIR/cases.txt: "conv <id> <unit shape> <description> <F>" (or "conv_plain ..."), "input <id> <F>", "fc <id> <F>", "se <id> <H> <C> <F> <sc_stride>"
 inline std::vector<Case> read_cases(const std::string &dir, int n_shapes, int n_desc, int max_F) {
     FILE *f = fopen((dir + "/cases.txt").c_str(), "r");
     if (!f) die("cannot open " + dir + "/cases.txt");
@@ -239,7 +239,7 @@ inline std::vector<Case> read_cases(const std::string &dir, int n_shapes, int n_
         c.kind = kind;
         c.id = id;
         bool ok = false;
-        if (c.kind == "conv")
+        if (c.kind == "conv" || c.kind == "conv_plain")
             ok = fscanf(f, "%d %d %d", &c.shape, &c.d, &c.F) == 3 && c.shape >= 0 && c.shape < n_shapes && c.d >= 0 && c.d < n_desc;
         else if (c.kind == "input" || c.kind == "fc")
             ok = fscanf(f, "%d", &c.F) == 1;

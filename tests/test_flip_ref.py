@@ -62,8 +62,10 @@ def test_flip_reference_is_symmetric_and_the_sum_is_no_cancellation(synth, blobs
     assert ratio.min() >= 1.3
     ref = FR.normalize(pre + pre_m)
     assert np.array_equal(ref, FR.normalize(pre_m + pre))
-    again = FR.flip_reference(sd, x[:2, :, :, ::-1])
-    assert np.abs(again - ref[:2]).max() < 1e-12
+    # (all nine mirror images in one batch, as above: the oracle is torch's fp32 on the CPU, and on some hosts its sums differ in their last
+    #  bits - 6e-7 of a unit vector - from one batch size to another, which is no asymmetry of the reference)
+    again = FR.flip_reference(sd, x[:, :, :, ::-1])
+    assert np.abs(again - ref).max() < 1e-12
     # and the mode is no near no-op: the flip embedding is far from the plain one
     cos_plain = (ref * FR.normalize(pre)).sum(1)
     assert cos_plain.max() < 0.9

@@ -7,7 +7,11 @@ normalisation; here each selected line of tests/golden/arc_conv_plan.txt runs on
   * no half outside an output's logical tensor has changed (the buffers have the embedder's sizes, with a margin in front).
 The seven conv2_se lines with se=1 run as the twin instantiation with the whole SE tail in its epilogue (test_fused_se_launches_alone).
 One harness process per unit shape, each under its own timeout.  A process that ends on a HIP error ends the module: the remaining
-parameters fail with its message and launch nothing."""
+parameters fail with its message and launch nothing.
+The batches here are the smallest that select each instantiation, and at those the three persistent kernels walk nothing: a workgroup of
+conv64_kernel owns one strip, a wave of arc_input_mfma_kernel one tile, a workgroup of conv_s2c64_kernel one or two output rows.  Their walks -
+what they carry from one work item to the next - are checked by tests/test_gpu_conv64_walk.py (conv64_kernel) and
+tests/test_gpu_persistent_walks.py (the input layer and the 112 -> 56 conv), with this harness, these references and these bounds."""
 import shutil
 
 import numpy as np

@@ -3,7 +3,8 @@
 The launch-alone cases of tests/test_gpu_arc_launches.py run this kernel at the first batch of its plan lines and at first + 1: 4 faces at
 112x112 (448 strips) and 11 at 56x56 (308 strips).  The launcher's grid is min(512, strips), so there every workgroup owns exactly one strip:
 the persistent walk, the hand-over of the two patch buffers and the rotation of the two accumulator halves (a strip's second half drains
-under the NEXT strip's first K loop, the last one behind the loop) are never reached.  Here the same harness (tests/cpp/arc_launch_check.cpp,
+under the NEXT strip's first K loop, the last one behind the loop) are never reached.  (The walks of the recogniser's other two persistent
+kernels, arc_input_mfma_kernel over tiles and conv_s2c64_kernel over output rows: tests/test_gpu_persistent_walks.py.)  Here the same harness (tests/cpp/arc_launch_check.cpp,
 tests/launch_harness.py), the same cases, references and bounds (tests/arc_launch_ref.py) run the plan lines whose label is
 conv64_kernel<0 | 1 | 2> at four other batches, all inside the lines' ranges.  A strip is 2 rows x 56 columns, so with a grid of 512:
 
