@@ -176,6 +176,13 @@ ABI = {
     "frt_detector_find_faces_tiled": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _vp, _vp, _vp, ctypes.POINTER(_i)]),
     "frt_select_faces": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _i]),
     "frt_pipeline_run_photo_tiled": (_i, [_vp, _vp, _i, _i, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i)]),
+    "frt_tracker_create": (_i, [_i, _i, _i, _i, _vp, _i, ctypes.POINTER(_vp)]),
+    "frt_tracker_destroy": (None, [_vp]),
+    "frt_tracker_update_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "frt_tracker_update": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "frt_tracker_tracks": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "frt_tracker_reset": (_i, [_vp, _i]),
+    "frt_pipeline_run_tracked": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "frt_profile_enable": (_i, [_i]),
     "frt_profile_collect": (_i, [_vp, _sz, _vp, _vp, _i]),
 }
@@ -1131,6 +1138,88 @@ class Coalescer:
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# face tracker: the state that joins the consecutive frames of a video stream, on the device (include/frt.h "Face tracker")
+# ----------------------------------------------------------------------------------------------------------------------
+TRACK_DTYPE = np.dtype([("track_id", "<i4"), ("slot", "<i4"), ("age", "<i4"), ("hits", "<i4"), ("n_embeds", "<i4"), ("confirmed", "<i4"),
+                        ("match_idx", "<i4"), ("match_sim", "<f4")])  # == frt_track_result
+TRACK_STATE_DTYPE = np.dtype([("live", "<i4"), ("id", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("score", "<f4"),
+                              ("born", "<i4"), ("hits", "<i4"), ("missed", "<i4"), ("n_embeds", "<i4"), ("match_idx", "<i4"),
+                              ("match_sim", "<f4")])  # == frt_track_state
+assert TRACK_DTYPE.itemsize == 32 and TRACK_STATE_DTYPE.itemsize == 52
+
+
+class TrackOptions(ctypes.Structure):  # == frt_track_options
+    _fields_ = [("iou_threshold", ctypes.c_float), ("max_missed", ctypes.c_int32), ("min_hits", ctypes.c_int32), ("decay", ctypes.c_float)]
+
+
+def _stream_ids(stream_ids, n):
+    if stream_ids is None:
+        return None
+    ids = np.ascontiguousarray(stream_ids, np.int32).reshape(-1)
+    if ids.size != n:
+        raise ValueError("one stream id per frame")
+    return ids
+
+
+class Tracker:
+    """``n_streams`` independent video streams of up to ``max_tracks`` tracks each.  An update takes the pipeline's records and embeddings
+    of one frame per stream and returns, per face slot, a stable track id, the track's age / hits / confirmed flag and the identity of the
+    track's running template (when a matcher - a ``MatMul`` - with rows is given)."""
+
+    def __init__(self, n_streams, max_tracks=16, max_faces=4, dim=512, iou_threshold=0.3, max_missed=5, min_hits=3, decay=1.0, device=0):
+        self._h = _vp()
+        self.n_streams, self.max_tracks, self.max_faces, self.dim = int(n_streams), int(max_tracks), int(max_faces), int(dim)
+        opt = TrackOptions(iou_threshold, max_missed, min_hits, decay)
+        _check(lib.frt_tracker_create(self.n_streams, self.max_tracks, self.max_faces, self.dim, ctypes.addressof(opt), int(device), ctypes.byref(self._h)))
+
+    def update(self, results, embeds, stream_ids=None, matcher=None, want_templates=True):
+        """results RESULT_DTYPE [n * max_faces], embeds float32 [n * max_faces, dim] (host) -> (TRACK_DTYPE [n, max_faces], templates
+        float32 [n, max_faces, dim] or None)."""
+        results = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
+        if results.size == 0 or results.size % self.max_faces:
+            raise ValueError("results must hold max_faces records per frame")
+        n = results.size // self.max_faces
+        embeds = np.ascontiguousarray(embeds, np.float32)
+        if embeds.size != results.size * self.dim:
+            raise ValueError("embeds must be [n * max_faces, dim]")
+        ids = _stream_ids(stream_ids, n)
+        trk = np.zeros((n, self.max_faces), TRACK_DTYPE)
+        tpl = np.zeros((n, self.max_faces, self.dim), np.float32) if want_templates else None
+        _check(lib.frt_tracker_update(self._h, matcher._h if matcher is not None else None, _ptr(results), _ptr(embeds), n, _ptr(ids), _ptr(trk), _ptr(tpl)))
+        return trk, tpl
+
+    def updateDev(self, results_ptr, embeds_ptr, n_frames, tracks_ptr, templates_ptr=None, stream_ids=None, matcher=None, hip_stream=None):
+        """Asynchronous on ``hip_stream``; the pointers are raw device addresses (``frt_pipeline_run_dev``'s results_dev / embeds_dev)."""
+        ids = _stream_ids(stream_ids, int(n_frames))
+        _check(lib.frt_tracker_update_dev(self._h, matcher._h if matcher is not None else None, _vp(results_ptr), _vp(embeds_ptr), int(n_frames), _ptr(ids),
+                                          _vp(tracks_ptr), _vp(templates_ptr) if templates_ptr else None, _vp(hip_stream) if hip_stream else None))
+
+    def tracks(self, stream, want_sums=False):
+        """-> (slots TRACK_STATE_DTYPE [max_tracks], every slot, live or not; counters dict(next_id, tick, dropped)[; sums [max_tracks, dim]])"""
+        slots = np.zeros(self.max_tracks, TRACK_STATE_DTYPE)
+        sums = np.zeros((self.max_tracks, self.dim), np.float32) if want_sums else None
+        cnt = np.zeros(3, np.int32)
+        _check(lib.frt_tracker_tracks(self._h, int(stream), _ptr(slots), _ptr(sums), _ptr(cnt)))
+        counters = dict(next_id=int(cnt[0]), tick=int(cnt[1]), dropped=int(cnt[2]))
+        return (slots, counters, sums) if want_sums else (slots, counters)
+
+    def reset(self, stream=-1):
+        """Free the slots of ``stream`` (-1: of every stream) and zero its tick / dropped; track ids are never reused."""
+        _check(lib.frt_tracker_reset(self._h, int(stream)))
+
+    def close(self):
+        if self._h:
+            lib.frt_tracker_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # batched device-resident pipeline (new surface)
 # ----------------------------------------------------------------------------------------------------------------------
 class Pipeline:
@@ -1187,6 +1276,22 @@ class Pipeline:
         out = (res[:k].copy(), emb[:k].copy() if want_embeds else None)
         out += ((crops[:k].copy(),) if want_crops else ()) + ((ldm[:k].copy(),) if landmarks else ()) + ((src[:k].copy(),) if sources else ())
         return out
+
+    def runTracked(self, tracker, frames, stream_ids=None, want_embeds=True, want_templates=True):
+        """``run`` with a :class:`Tracker` behind it on the pipeline stream (frt_pipeline_run_tracked): ``frames`` are the current frames of
+        the streams ``stream_ids`` (None: frame i is stream i) -> (records, embeddings or None - exactly ``run``'s -, track records
+        TRACK_DTYPE [n, max_faces], templates [n, max_faces, 512] or None)."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != (self.det.frameHeight, self.det.frameWidth, 3):
+            raise ValueError("runTracked: frames must be [n, frameHeight, frameWidth, 3]")
+        ids = _stream_ids(stream_ids, n)
+        res = np.zeros(n * self.max_faces, RESULT_DTYPE)
+        emb = np.zeros((n * self.max_faces, 512), np.float32) if want_embeds else None
+        trk = np.zeros((n, self.max_faces), TRACK_DTYPE)
+        tpl = np.zeros((n, self.max_faces, 512), np.float32) if want_templates else None
+        _check(lib.frt_pipeline_run_tracked(self._h, tracker._h, _ptr(frames), n, _ptr(ids), _ptr(res), _ptr(trk), _ptr(emb), _ptr(tpl)))
+        return res, emb, trk, tpl
 
     def enrolImages(self, classNames, images, labels=None):
         """/insert/face for whole photos: detect, require exactly one face, embed, and append the accepted photos' rows to the live gallery as

@@ -563,3 +563,27 @@ struct SeArgs {
     int *counter;        // [F] arrival counters of the pooling pass, zero between launches
 };
 void launch_se(const SeArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------- face tracker (kernels_track.hip; frt_tracker.cpp, include/frt.h "Face tracker")
+constexpr int FRT_TRACK_MAX_FRAMES = 256, FRT_TRACK_MAX_STREAMS = 1024, FRT_TRACK_MAX_SLOTS = 64, FRT_TRACK_MAX_DIM = 2048;
+struct TrackStreamIds {  // by value with the launch: the ids reach the kernel without a staging copy or a host synchronisation
+    uint16_t id[FRT_TRACK_MAX_FRAMES];
+};
+struct TrackArgs {
+    frt_track_state *slots;  // [n_streams][max_tracks]
+    float *sums;             // [n_streams][max_tracks][dim]; the rows of free slots are zero
+    int32_t *counters;       // [n_streams][4]: next_id, tick, dropped, -
+    int max_tracks, max_faces, dim;
+    float iou_threshold, decay;
+    int max_missed, min_hits;
+    const frt_face_result *results;  // [n_frames][max_faces]
+    const float *embeds;             // [n_frames][max_faces][dim], 16-byte aligned
+    frt_track_result *tracks;        // [n_frames][max_faces]
+    float *templates;                // [n_frames][max_faces][dim], 16-byte aligned, or null
+};
+// steps 1 - 6 and 8 of an update, one workgroup per frame; the records leave with match_idx -1 / match_sim 0
+void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s);
+// step 7 behind the top-1 search of the template rows: idx / sim [n_frames * max_faces] -> the tracked records with n_embeds > 0 and their slots
+void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, const int32_t *idx, const float *sim, hipStream_t s);
+// frees the slots of `stream` (-1: of every one of n_streams) and zeroes tick / dropped; next_id stays
+void launch_track_reset(const TrackArgs &a, int n_streams, int stream, hipStream_t s);

@@ -1,0 +1,265 @@
+// Face tracker, host side (include/frt.h "Face tracker"): the object, the argument checks that run before any device work, the three
+// launches of an update, the host forms and frt_pipeline_run_tracked.  The kernels are in kernels_track.hip.
+#include "frt_pipeline.hpp"
+#include "frt_tracker.hpp"
+
+TrackStreamIds tracker_check_ids(const frt_tracker *t, int n_frames, const int32_t *stream_ids) {
+    if (n_frames < 1) raise(FRT_ERR_INVALID, "tracker: n_frames < 1");
+    if (n_frames > FRT_TRACK_MAX_FRAMES) raise(FRT_ERR_CAPACITY, "tracker: more than 256 frames in one update");
+    TrackStreamIds ids{};
+    bool seen[FRT_TRACK_MAX_STREAMS] = {};
+    for (int i = 0; i < n_frames; ++i) {
+        const int s = stream_ids ? stream_ids[i] : i;
+        if (s < 0 || s >= t->n_streams) raise(FRT_ERR_INVALID, "tracker: stream id " + std::to_string(s) + " of frame " + std::to_string(i) + " is outside 0 .. n_streams - 1");
+        if (seen[s]) raise(FRT_ERR_INVALID, "tracker: stream id " + std::to_string(s) + " appears twice in one update");
+        seen[s] = true;
+        ids.id[i] = (uint16_t)s;
+    }
+    return ids;
+}
+
+void tracker_check_matcher(const frt_tracker *t, frt_matcher *m) {
+    if (!m) return;
+    std::lock_guard<std::mutex> lk(m->mu);
+    if (m->device != t->device) raise(FRT_ERR_INVALID, "tracker: the matcher lives on another device");
+    if (m->N > 0 && m->D != t->dim) raise(FRT_ERR_INVALID, "tracker: the matcher's num_col is not the tracker's dim");
+}
+
+void tracker_update_locked(frt_tracker *t, frt_matcher *m, const frt_face_result *results_dev, const float *embeds_dev, int n_frames,
+                           const TrackStreamIds &ids, frt_track_result *tracks_dev, float *templates_dev, hipStream_t s) {
+    const int F = n_frames * t->max_faces;
+    std::unique_lock<std::mutex> lm;
+    if (m) {
+        lm = std::unique_lock<std::mutex>(m->mu);
+        if (m->N > 0 && (m->D != t->dim || m->device != t->device)) raise(FRT_ERR_INVALID, "tracker: the matcher's num_col is not the tracker's dim");
+    }
+    const bool identity = m && m->N > 0;
+    if (identity) {
+        if (!templates_dev) {
+            t->q_templates.reserve((size_t)F * t->dim);
+            templates_dev = t->q_templates.get();
+        }
+        t->q_idx.reserve(F);
+        t->q_sim.reserve(F);
+    }
+    TrackArgs a = t->args();
+    a.results = results_dev;
+    a.embeds = embeds_dev;
+    a.tracks = tracks_dev;
+    a.templates = templates_dev;
+    {
+        ProfScope ps(2, "track_update", (double)F, s);
+        launch_track_update(a, ids, n_frames, s);
+        HIPCHK(hipGetLastError());
+    }
+    if (identity) {
+        // what frt_matcher_top1_dev does, with the matcher's mutex already held
+        m->wait_idle(s);
+        m->ensure_queries(F);
+        m->top1_dev(templates_dev, F, t->q_idx.get(), t->q_sim.get(), s);
+        HIPCHK(hipEventRecord(m->ev_busy, s));
+        m->busy = true;
+        ProfScope ps(2, "track_identity", (double)F, s);
+        launch_track_identity(a, ids, n_frames, t->q_idx.get(), t->q_sim.get(), s);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(t->ev_last, s));
+    t->pending = true;
+}
+
+namespace {
+
+void check_options(const frt_track_options &o) {
+    if (!(o.iou_threshold > 0.f && o.iou_threshold <= 1.f)) raise(FRT_ERR_INVALID, "tracker: iou_threshold outside (0, 1]");
+    if (o.max_missed < 0) raise(FRT_ERR_INVALID, "tracker: max_missed < 0");
+    if (o.min_hits < 1) raise(FRT_ERR_INVALID, "tracker: min_hits < 1");
+    if (!(o.decay > 0.f && o.decay <= 1.f)) raise(FRT_ERR_INVALID, "tracker: decay outside (0, 1]");
+}
+
+// The stream, the events and the zeroed state, on the first call that passed its checks.  All of it or nothing: a failure leaves the
+// object as it was created
+void ensure_state(frt_tracker *t) {
+    use_device(t->device);
+    if (t->slots) return;
+    try {
+        if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
+        if (!t->ev_last) HIPCHK(hipEventCreateWithFlags(&t->ev_last, hipEventDisableTiming));
+        if (!t->ev_up) HIPCHK(hipEventCreateWithFlags(&t->ev_up, hipEventDisableTiming));
+        const size_t S = (size_t)t->n_streams * t->max_tracks;
+        t->sums.reserve(S * t->dim);
+        t->counters.reserve((size_t)t->n_streams * 4);
+        t->slots.reserve(S);
+        HIPCHK(hipMemsetAsync(t->slots.get(), 0, S * sizeof(frt_track_state), t->stream));
+        HIPCHK(hipMemsetAsync(t->sums.get(), 0, S * t->dim * sizeof(float), t->stream));
+        HIPCHK(hipMemsetAsync(t->counters.get(), 0, (size_t)t->n_streams * 4 * sizeof(int32_t), t->stream));
+        HIPCHK(hipStreamSynchronize(t->stream));
+    } catch (...) {
+        t->slots.reset();
+        t->sums.reset();
+        t->counters.reset();
+        throw;
+    }
+}
+
+// `stream` behind the last update queued on any stream
+void join_updates(frt_tracker *t) {
+    if (t->pending) HIPCHK(hipStreamWaitEvent(t->stream, t->ev_last, 0));
+}
+
+void destroy(frt_tracker *t) {
+    if (t->stream || t->slots) (void)hipSetDevice(t->device);
+    if (t->stream) {
+        (void)hipStreamSynchronize(t->stream);
+        (void)hipStreamDestroy(t->stream);
+    }
+    if (t->ev_last) {
+        if (t->pending) (void)hipEventSynchronize(t->ev_last);
+        (void)hipEventDestroy(t->ev_last);
+    }
+    if (t->ev_up) (void)hipEventDestroy(t->ev_up);
+    delete t;
+}
+
+}  // namespace
+
+extern "C" {
+
+int frt_tracker_create(int n_streams, int max_tracks, int max_faces, int dim, const frt_track_options *options, int device, frt_tracker **out) {
+    return guarded([&] {
+        if (!out) raise(FRT_ERR_INVALID, "tracker: null out");
+        if (n_streams < 1 || n_streams > FRT_TRACK_MAX_STREAMS) raise(FRT_ERR_INVALID, "tracker: n_streams outside 1 .. 1024");
+        if (max_tracks < 1 || max_tracks > FRT_TRACK_MAX_SLOTS) raise(FRT_ERR_INVALID, "tracker: max_tracks outside 1 .. 64");
+        if (max_faces < 1 || max_faces > FRT_TRACK_MAX_SLOTS) raise(FRT_ERR_INVALID, "tracker: max_faces outside 1 .. 64");
+        if (dim < 4 || dim > FRT_TRACK_MAX_DIM || (dim & 3)) raise(FRT_ERR_INVALID, "tracker: dim must be a multiple of 4 in 4 .. 2048");
+        frt_track_options o{0.3f, 5, 3, 1.0f};
+        if (options) o = *options;
+        check_options(o);
+        if (device < 0) raise(FRT_ERR_INVALID, "tracker: bad device");
+        frt_tracker *t = new frt_tracker;  // (no device work here: the state is allocated by the first call that needs it, ensure_state)
+        t->device = device;
+        t->n_streams = n_streams;
+        t->max_tracks = max_tracks;
+        t->max_faces = max_faces;
+        t->dim = dim;
+        t->opt = o;
+        *out = t;
+    });
+}
+
+void frt_tracker_destroy(frt_tracker *t) {
+    if (t) destroy(t);
+}
+
+int frt_tracker_update_dev(frt_tracker *t, frt_matcher *m, const void *results_dev, const void *embeds_dev, int n_frames, const int32_t *stream_ids,
+                           void *tracks_dev, void *templates_dev, void *hip_stream) {
+    return guarded([&] {
+        if (!t || !results_dev || !embeds_dev || !tracks_dev) raise(FRT_ERR_INVALID, "tracker update: null argument");
+        if (((uintptr_t)embeds_dev | (uintptr_t)templates_dev) & 15) raise(FRT_ERR_INVALID, "tracker update: embeds_dev and templates_dev must be 16-byte aligned");
+        std::lock_guard<std::mutex> lk(t->mu);
+        const TrackStreamIds ids = tracker_check_ids(t, n_frames, stream_ids);
+        tracker_check_matcher(t, m);
+        ensure_state(t);
+        tracker_update_locked(t, m, reinterpret_cast<const frt_face_result *>(results_dev), reinterpret_cast<const float *>(embeds_dev), n_frames, ids,
+                              reinterpret_cast<frt_track_result *>(tracks_dev), reinterpret_cast<float *>(templates_dev),
+                              reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int frt_tracker_update(frt_tracker *t, frt_matcher *m, const frt_face_result *results, const float *embeds, int n_frames, const int32_t *stream_ids,
+                       frt_track_result *tracks_out, float *templates_out) {
+    return guarded([&] {
+        if (!t || !results || !embeds || !tracks_out) raise(FRT_ERR_INVALID, "tracker update: null argument");
+        std::lock_guard<std::mutex> lk(t->mu);
+        const TrackStreamIds ids = tracker_check_ids(t, n_frames, stream_ids);
+        tracker_check_matcher(t, m);
+        ensure_state(t);
+        const size_t F = (size_t)n_frames * t->max_faces;
+        hipStream_t s = t->stream;
+        join_updates(t);
+        HIPCHK(hipStreamSynchronize(s));  // the staging is rewritten below
+        t->reserve_staging(n_frames, 0);
+        HIPCHK(hipMemcpyAsync(t->d_results.get(), results, F * sizeof(frt_face_result), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpyAsync(t->d_embeds.get(), embeds, F * t->dim * sizeof(float), hipMemcpyHostToDevice, s));
+        tracker_update_locked(t, m, t->d_results.get(), t->d_embeds.get(), n_frames, ids, t->d_tracks.get(), templates_out ? t->d_templates.get() : nullptr, s);
+        HIPCHK(hipMemcpyAsync(tracks_out, t->d_tracks.get(), F * sizeof(frt_track_result), hipMemcpyDeviceToHost, s));
+        if (templates_out) HIPCHK(hipMemcpyAsync(templates_out, t->d_templates.get(), F * t->dim * sizeof(float), hipMemcpyDeviceToHost, s));
+        sync_stream_spinning(s);
+    });
+}
+
+int frt_tracker_tracks(frt_tracker *t, int stream, frt_track_state *slots_out, float *sums_out, int32_t *counters_out) {
+    return guarded([&] {
+        if (!t || !slots_out) raise(FRT_ERR_INVALID, "tracker tracks: null argument");
+        if (stream < 0 || stream >= t->n_streams) raise(FRT_ERR_INVALID, "tracker tracks: stream outside 0 .. n_streams - 1");
+        std::lock_guard<std::mutex> lk(t->mu);
+        ensure_state(t);
+        hipStream_t s = t->stream;
+        join_updates(t);
+        const size_t T = (size_t)t->max_tracks;
+        int32_t cnt[4] = {};
+        HIPCHK(hipMemcpyAsync(slots_out, t->slots.get() + stream * T, T * sizeof(frt_track_state), hipMemcpyDeviceToHost, s));
+        if (sums_out) HIPCHK(hipMemcpyAsync(sums_out, t->sums.get() + stream * T * t->dim, T * t->dim * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (counters_out) HIPCHK(hipMemcpyAsync(cnt, t->counters.get() + (size_t)stream * 4, sizeof(cnt), hipMemcpyDeviceToHost, s));
+        sync_stream_spinning(s);
+        if (counters_out) std::memcpy(counters_out, cnt, 3 * sizeof(int32_t));
+    });
+}
+
+int frt_tracker_reset(frt_tracker *t, int stream) {
+    return guarded([&] {
+        if (!t) raise(FRT_ERR_INVALID, "tracker reset: null argument");
+        if (stream < -1 || stream >= t->n_streams) raise(FRT_ERR_INVALID, "tracker reset: stream outside -1 .. n_streams - 1");
+        std::lock_guard<std::mutex> lk(t->mu);
+        ensure_state(t);
+        join_updates(t);
+        launch_track_reset(t->args(), t->n_streams, stream, t->stream);
+        HIPCHK(hipGetLastError());
+        sync_stream_spinning(t->stream);
+    });
+}
+
+int frt_pipeline_run_tracked(frt_pipeline *p, frt_tracker *t, const uint8_t *frames, int n_frames, const int32_t *stream_ids, frt_face_result *results,
+                             frt_track_result *tracks_out, float *embeds_out, float *templates_out) {
+    return guarded([&] {
+        if (!p || !t || !frames || !results || !tracks_out) raise(FRT_ERR_INVALID, "runTracked: null argument");
+        std::lock_guard<std::mutex> lk(t->mu);
+        if (t->max_faces != p->max_faces || t->dim != 512) raise(FRT_ERR_INVALID, "runTracked: the tracker's max_faces and dim must be the pipeline's");
+        if (t->device != p->det->device) raise(FRT_ERR_INVALID, "runTracked: tracker and pipeline live on different devices");
+        const TrackStreamIds ids = tracker_check_ids(t, n_frames, stream_ids);
+        if (n_frames > p->max_frames) raise(FRT_ERR_INVALID, "runTracked: more frames than the pipeline's max_frames");
+        tracker_check_matcher(t, p->mat);
+        ensure_state(t);
+        const size_t frame_bytes = (size_t)p->det->g.frame_h * p->det->g.frame_w * 3, F = (size_t)n_frames * t->max_faces;
+        join_updates(t);
+        HIPCHK(hipStreamSynchronize(t->stream));  // a host form may still be reading the staging
+        t->reserve_staging(n_frames, frame_bytes);
+        std::lock_guard<std::mutex> lr(p->run_mu);
+        p->ensure_stream();
+        hipStream_t s = p->stream;
+        try {
+            HIPCHK(hipMemcpyAsync(t->d_frames.get(), frames, n_frames * frame_bytes, hipMemcpyHostToDevice, s));
+            HIPCHK(hipEventRecord(t->ev_up, s));
+            frt_pipeline::Request r;
+            r.frames = t->d_frames.get();
+            r.n = n_frames;
+            r.results = t->d_results.get();
+            r.embeds = t->d_embeds.get();
+            r.after = t->ev_up;
+            p->run_dev(r);
+            p->flush();  // (a pairing mode that holds run_dev calls: the join must be on the stream before the tracker reads the results)
+            tracker_update_locked(t, p->mat, t->d_results.get(), t->d_embeds.get(), n_frames, ids, t->d_tracks.get(),
+                                  templates_out ? t->d_templates.get() : nullptr, s);
+            HIPCHK(hipMemcpyAsync(results, t->d_results.get(), F * sizeof(frt_face_result), hipMemcpyDeviceToHost, s));
+            if (embeds_out) HIPCHK(hipMemcpyAsync(embeds_out, t->d_embeds.get(), F * 512 * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(tracks_out, t->d_tracks.get(), F * sizeof(frt_track_result), hipMemcpyDeviceToHost, s));
+            if (templates_out) HIPCHK(hipMemcpyAsync(templates_out, t->d_templates.get(), F * 512 * sizeof(float), hipMemcpyDeviceToHost, s));
+            sync_stream_spinning(s);
+        } catch (...) {  // leave nothing in flight that reads or writes the staging of a call that has returned
+            p->drain(false);
+            throw;
+        }
+        p->emb->check_se_error();
+    });
+}
+
+}  // extern "C"

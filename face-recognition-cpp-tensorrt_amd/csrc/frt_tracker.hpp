@@ -1,0 +1,63 @@
+// struct frt_tracker: the object behind frt_tracker_* (include/frt.h "Face tracker").  Internal header of libfrt.so.  The track state
+// lives in HBM for the object's lifetime; the scratch of an update and the staging of the host forms grow to fit.  Every buffer is a
+// DevBuf member: frt_tracker_destroy sets the device, retires the stream and the events, and `delete` frees the rest.
+#pragma once
+#include "frt_internal.hpp"
+
+struct frt_tracker {
+    int device = 0;
+    int n_streams = 0, max_tracks = 0, max_faces = 0, dim = 0;
+    frt_track_options opt{};
+    std::mutex mu;
+    hipStream_t stream = nullptr;   // the host forms, frt_tracker_tracks and frt_tracker_reset
+    hipEvent_t ev_last = nullptr;   // end of the last update queued (on whichever stream): what `stream` waits for before it reads the state
+    bool pending = false;
+    hipEvent_t ev_up = nullptr;     // frt_pipeline_run_tracked: the frames are on the device
+
+    // ---- the state
+    DevBuf<frt_track_state> slots;  // [n_streams][max_tracks]; a free slot is all zero
+    DevBuf<float> sums;             // [n_streams][max_tracks][dim]; the rows of free slots are zero
+    DevBuf<int32_t> counters;       // [n_streams][4]: next_id, tick, dropped, -
+    // ---- scratch of an update with a matcher: the template rows when the caller takes none, and the search's answers
+    DevBuf<float> q_templates, q_sim;
+    DevBuf<int32_t> q_idx;
+    // ---- staging of the host forms
+    DevBuf<uint8_t> d_frames;
+    DevBuf<frt_face_result> d_results;
+    DevBuf<float> d_embeds, d_templates;
+    DevBuf<frt_track_result> d_tracks;
+
+    TrackArgs args() const {
+        TrackArgs a{};
+        a.slots = slots.get();
+        a.sums = sums.get();
+        a.counters = counters.get();
+        a.max_tracks = max_tracks;
+        a.max_faces = max_faces;
+        a.dim = dim;
+        a.iou_threshold = opt.iou_threshold;
+        a.decay = opt.decay;
+        a.max_missed = opt.max_missed;
+        a.min_hits = opt.min_hits;
+        return a;
+    }
+    // room for the host forms' n_frames frames (frame_bytes: 0 without frames)
+    void reserve_staging(int n_frames, size_t frame_bytes) {
+        const size_t F = (size_t)n_frames * max_faces;
+        if (frame_bytes) d_frames.reserve((size_t)n_frames * frame_bytes);
+        d_results.reserve(F);
+        d_embeds.reserve(F * dim);
+        d_tracks.reserve(F);
+        d_templates.reserve(F * dim);
+    }
+};
+
+// What an update checks before any device work (frt_tracker.cpp); both need t->mu.
+//   the call's own arguments -> the stream ids by value
+TrackStreamIds tracker_check_ids(const frt_tracker *t, int n_frames, const int32_t *stream_ids);
+//   the matcher: on the tracker's device, and dim columns when it has rows.  Takes m->mu for the look; m may be null
+void tracker_check_matcher(const frt_tracker *t, frt_matcher *m);
+// One update, queued on s, with t->mu held and every argument checked: the update kernel, then - m with rows - the top-1 search of the
+// template rows and the identity kernel.  Takes m->mu for the search.
+void tracker_update_locked(frt_tracker *t, frt_matcher *m, const frt_face_result *results_dev, const float *embeds_dev, int n_frames,
+                           const TrackStreamIds &ids, frt_track_result *tracks_dev, float *templates_dev, hipStream_t s);

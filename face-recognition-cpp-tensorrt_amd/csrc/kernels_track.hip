@@ -1,0 +1,253 @@
+// Face tracker for gfx950: the per-stream track state in HBM and one update of it (include/frt.h "Face tracker"; DESIGN §3.37;
+// tests/track_ref.py is the contract, to the integer and - for the sums - to the bit).
+//
+// track_update_kernel, one workgroup of four waves per frame:
+//   - wave 0 holds the stream's slots one per lane and walks the frame's detections in slot order: the overlap of the detection with every
+//     candidate track is one value per lane, the winner one 64-lane max-reduction over (overlap bits, 63 - lane) - the largest overlap, the
+//     lowest slot among equals -, the free-slot mask of a birth one ballot and the slot its first set bit.  It writes the slots, the
+//     counters and the records, and leaves the detection -> slot table and the mask of the slots that expired in LDS;
+//   - behind one barrier every wave zeroes the sums of the expired slots, and behind a second one the waves take the detections in turn:
+//     a row of `dim` floats is 16 bytes per lane and 256-column group, as template_build_kernel holds a row, the squared norm is its fmaf
+//     chain per lane and its xor butterfly over the wave, the template is scaled in registers.
+// The sum is fl(fl(decay * sum) + e): two roundings.  This file is compiled without fp contraction (Makefile: EXACT) and the update is
+// written with the rounding intrinsics as well, so neither the sums nor the overlaps can turn into an fma.
+// Bounds: a frame index is blockIdx.x < n_frames, a stream id was checked on the host against n_streams, a slot index is < max_tracks <= 64,
+// a column is tested against dim before every access.
+#include "frt_kernels.h"
+
+namespace {
+
+constexpr int WAVES = 4, GROUPS = FRT_TRACK_MAX_DIM / 256;
+
+__device__ __forceinline__ float wave_sum(float v) {  // xor butterfly: every lane ends with the same bits
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ float dot4(floatx4 a, floatx4 b, float acc) { return fmaf(a[3], b[3], fmaf(a[2], b[2], fmaf(a[1], b[1], fmaf(a[0], b[0], acc)))); }
+
+__device__ __forceinline__ float box_area(const frt_bbox &b) {  // (float) of the exact product
+    return (float)(((long long)b.x2 - b.x1 + 1) * ((long long)b.y2 - b.y1 + 1));
+}
+// nms_kernel's statements (kernels_post.hip), metric 0
+__device__ __forceinline__ float iou(const frt_bbox &a, const frt_bbox &b) {
+    const float xx1 = (float)(a.x1 > b.x1 ? a.x1 : b.x1);
+    const float yy1 = (float)(a.y1 > b.y1 ? a.y1 : b.y1);
+    const float xx2 = (float)(a.x2 < b.x2 ? a.x2 : b.x2);
+    const float yy2 = (float)(a.y2 < b.y2 ? a.y2 : b.y2);
+    float w = xx2 - xx1 + 1;
+    float h = yy2 - yy1 + 1;
+    if (w < 0.f) w = 0.f;
+    if (h < 0.f) h = 0.f;
+    const float inter = w * h;
+    return inter / (box_area(a) + box_area(b) - inter);
+}
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const unsigned lo = __shfl_xor((unsigned)v, off), hi = __shfl_xor((unsigned)(v >> 32), off);
+        const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, TrackStreamIds ids) {
+    __shared__ int s_slot[FRT_TRACK_MAX_SLOTS];  // detection -> slot; -1: untracked or absent
+    __shared__ unsigned long long s_expired;     // slots freed by this update (their sums are zeroed before a birth's embedding lands)
+    const int f = blockIdx.x, stream = ids.id[f];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int T = a.max_tracks, MF = a.max_faces, D = a.dim;
+    const frt_face_result *res = a.results + (long)f * MF;
+    frt_track_state *slots = a.slots + (long)stream * T;
+    float *sums = a.sums + (long)stream * T * D;
+
+    if (wave == 0) {
+        int32_t *cnt = a.counters + stream * 4;
+        int next_id = cnt[0], dropped = cnt[2];
+        const int tick = cnt[1];
+        const bool mine = lane < T;
+        frt_track_state st = {};
+        if (mine) st = slots[lane];
+        const bool live_entry = mine && st.live != 0;
+        bool taken = false;
+        int my_slot = -1;        // lane d: the slot of detection d
+        bool my_present = false;
+
+        // ---- steps 1, 2: association, detections in slot order
+        for (int d = 0; d < MF; ++d) {
+            const frt_face_result r = res[d];
+            if (!(r.box.score > 0.f)) continue;  // (wave-uniform)
+            if (lane == d) my_present = true;
+            unsigned long long key = 0;  // (overlap bits, 63 - lane); an overlap that reaches the threshold is > 0, so 0 is "no candidate"
+            if (live_entry && !taken) {
+                const float ovr = iou(r.box, st.box);
+                if (ovr >= a.iou_threshold) key = ((unsigned long long)__float_as_uint(ovr) << 32) | (unsigned)(63 - lane);
+            }
+            key = wave_max_u64(key);
+            if (key == 0) continue;
+            const int win = 63 - (int)(key & 63);
+            if (lane == win) {
+                st.box = r.box;
+                st.hits += 1;
+                st.missed = 0;
+                taken = true;
+            }
+            if (lane == d) my_slot = win;
+        }
+        // ---- step 3: expiry
+        bool expired = false;
+        if (live_entry && !taken) {
+            st.missed += 1;
+            if (st.missed > a.max_missed) {
+                st = frt_track_state{};
+                expired = true;
+            }
+        }
+        const unsigned long long expired_mask = __ballot(expired);
+        // ---- step 4: births, the lowest free slot each
+        for (int d = 0; d < MF; ++d) {
+            const int present = __shfl((int)my_present, d), slot_d = __shfl(my_slot, d);
+            if (!present || slot_d >= 0) continue;  // (wave-uniform)
+            const unsigned long long free_mask = __ballot(mine && st.live == 0);
+            if (free_mask == 0) {
+                ++dropped;
+                continue;
+            }
+            const int b = __ffsll((long long)free_mask) - 1;
+            if (lane == b) {
+                st.live = 1;
+                st.id = next_id;
+                st.box = res[d].box;
+                st.born = tick;
+                st.hits = 1;
+                st.missed = 0;
+                st.n_embeds = 0;
+                st.match_idx = -1;
+                st.match_sim = 0.f;
+            }
+            ++next_id;
+            if (lane == d) my_slot = b;
+        }
+        // ---- step 5, the count: a track is matched by at most one detection
+        for (int d = 0; d < MF; ++d) {
+            const int slot_d = __shfl(my_slot, d);
+            if (slot_d >= 0 && res[d].valid != 0 && lane == slot_d) st.n_embeds += 1;
+        }
+        // ---- the records: lane d fetches the state of its slot
+        {
+            const int src = my_slot >= 0 ? my_slot : 0;
+            const int id = __shfl(st.id, src), born = __shfl(st.born, src), hits = __shfl(st.hits, src), ne = __shfl(st.n_embeds, src);
+            if (lane < MF) {
+                frt_track_result o = {};
+                o.track_id = o.slot = o.match_idx = -1;
+                if (my_slot >= 0) {
+                    o.track_id = id;
+                    o.slot = my_slot;
+                    o.age = tick - born + 1;
+                    o.hits = hits;
+                    o.n_embeds = ne;
+                    o.confirmed = hits >= a.min_hits ? 1 : 0;
+                }
+                a.tracks[(long)f * MF + lane] = o;
+                s_slot[lane] = my_slot;
+            }
+        }
+        if (mine) slots[lane] = st;
+        if (lane == 0) {
+            cnt[0] = next_id;
+            cnt[1] = tick + 1;  // step 8
+            cnt[2] = dropped;
+            s_expired = expired_mask;
+        }
+    }
+    __syncthreads();
+
+    // ---- the sums of the slots that expired: zero, whether or not a birth has taken the slot again
+    const unsigned long long expired_mask = s_expired;
+    for (int t = wave; t < T; t += WAVES) {
+        if (!((expired_mask >> t) & 1)) continue;
+        for (int k = lane * 4; k < D; k += 256) *reinterpret_cast<floatx4 *>(sums + (long)t * D + k) = floatx4{0.f, 0.f, 0.f, 0.f};
+    }
+    __syncthreads();
+
+    // ---- steps 5, 6: one wave per detection
+    for (int d = wave; d < MF; d += WAVES) {
+        const int slot = s_slot[d];
+        float *tout = a.templates ? a.templates + ((long)f * MF + d) * D : nullptr;
+        if (slot < 0) {
+            if (tout)
+                for (int k = lane * 4; k < D; k += 256) *reinterpret_cast<floatx4 *>(tout + k) = floatx4{0.f, 0.f, 0.f, 0.f};
+            continue;
+        }
+        const bool valid = res[d].valid != 0;
+        float *sum = sums + (long)slot * D;
+        const float *e = a.embeds + ((long)f * MF + d) * D;
+        floatx4 v[GROUPS];
+        float n2 = 0.f;
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            const int k = g * 256 + lane * 4;
+            v[g] = floatx4{0.f, 0.f, 0.f, 0.f};
+            if (k < D) {
+                v[g] = *reinterpret_cast<const floatx4 *>(sum + k);
+                if (valid) {
+                    const floatx4 x = *reinterpret_cast<const floatx4 *>(e + k);
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) v[g][j] = __fadd_rn(__fmul_rn(a.decay, v[g][j]), x[j]);
+                    *reinterpret_cast<floatx4 *>(sum + k) = v[g];
+                }
+            }
+            n2 = dot4(v[g], v[g], n2);
+        }
+        if (!tout) continue;
+        n2 = wave_sum(n2);
+        const bool zero = n2 == 0.f;
+        const float nrm = sqrtf(n2);
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            const int k = g * 256 + lane * 4;
+            if (k < D) *reinterpret_cast<floatx4 *>(tout + k) = zero ? floatx4{0.f, 0.f, 0.f, 0.f} : v[g] / nrm;
+        }
+    }
+}
+
+// one thread per face slot of the call
+__global__ __launch_bounds__(256) void track_identity_kernel(TrackArgs a, TrackStreamIds ids, int n_frames, const int32_t *__restrict__ idx,
+                                                             const float *__restrict__ sim) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_frames * a.max_faces) return;
+    frt_track_result &o = a.tracks[i];
+    if (o.slot < 0 || o.n_embeds <= 0) return;  // (the update kernel left -1 / 0 there)
+    frt_track_state &st = a.slots[(long)ids.id[i / a.max_faces] * a.max_tracks + o.slot];
+    st.match_idx = o.match_idx = idx[i];
+    st.match_sim = o.match_sim = sim[i];
+}
+
+// grid (slots, streams to reset): a wave zeroes one slot and its sums; slot 0's wave the stream's tick and dropped
+__global__ __launch_bounds__(64) void track_reset_kernel(TrackArgs a, int first_stream) {
+    const int stream = first_stream + blockIdx.y, t = blockIdx.x, lane = threadIdx.x;
+    float *sum = a.sums + ((long)stream * a.max_tracks + t) * a.dim;
+    for (int k = lane * 4; k < a.dim; k += 256) *reinterpret_cast<floatx4 *>(sum + k) = floatx4{0.f, 0.f, 0.f, 0.f};
+    if (lane == 0) {
+        a.slots[(long)stream * a.max_tracks + t] = frt_track_state{};
+        if (t == 0) a.counters[stream * 4 + 1] = a.counters[stream * 4 + 2] = 0;
+    }
+}
+
+}  // namespace
+
+void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s) {
+    if (n_frames <= 0) return;
+    hipLaunchKernelGGL(track_update_kernel, dim3((unsigned)n_frames), dim3(64 * WAVES), 0, s, a, ids);
+}
+
+void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, const int32_t *idx, const float *sim, hipStream_t s) {
+    if (n_frames <= 0) return;
+    hipLaunchKernelGGL(track_identity_kernel, dim3((unsigned)((n_frames * a.max_faces + 255) / 256)), dim3(256), 0, s, a, ids, n_frames, idx, sim);
+}
+
+void launch_track_reset(const TrackArgs &a, int n_streams, int stream, hipStream_t s) {
+    const int first = stream < 0 ? 0 : stream, count = stream < 0 ? n_streams : 1;
+    hipLaunchKernelGGL(track_reset_kernel, dim3((unsigned)a.max_tracks, (unsigned)count), dim3(64), 0, s, a, first);
+}

@@ -812,6 +812,86 @@ int frt_pipeline_run_photo_tiled(frt_pipeline *p, const uint8_t *bgr, int rows, 
                                  int32_t *src_out /* [max_out], may be NULL */, int *n_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Face tracker: follow faces across the consecutive frames of a video stream, on the device.  The hot path this library replaces is
+ * /inference, a WebSocket that receives the frames of ONE camera one after the other (src/app.cpp:293-352); every call above answers a frame
+ * as if it were the only one.  A tracker carries, in HBM and for up to 1024 independent streams, what joins the frames: which face of this
+ * frame is which face of the last one (a stable track id), the running template of the track (the re-normalised sum of its embeddings, the
+ * template of frt_matcher_build_templates) and the identity of THAT TEMPLATE rather than of the single frame.  It follows the results_dev /
+ * embeds_dev frt_pipeline_run_dev leaves on the pipeline stream; nothing visits the host.  The reference has no tracker, so the semantics
+ * are fixed here, to the integer (tests/track_ref.py restates them in numpy).
+ *   Object: n_streams (1 .. 1024) streams; each has max_tracks (1 .. 64) slots, next_id (starts at 0, never reused, survives reset), tick
+ *     (the updates the stream took part in) and dropped.  max_faces (1 .. 64) and dim (a multiple of 4, 4 .. 2048) are fixed at creation.
+ *   One update takes n_frames (1 .. 256, else FRT_ERR_CAPACITY) frames and stream_ids[n_frames] on the host (NULL: frame i is stream i); the
+ *     ids lie in 0 .. n_streams - 1 and are pairwise distinct.  A stream absent from the call is not touched at all.  Per frame f of stream
+ *     s, with results[f][0 .. max_faces) as the pipeline writes them:
+ *     1. detection slot d is PRESENT iff box.score > 0 (an unused slot has score 0; an empty-ROI slot - valid 0, score > 0 - is present).
+ *     2. Association: present detections in slot order (the detector emits them score-descending); candidates are the tracks of s that were
+ *        live at entry and are not yet taken; ovr = the float32 IoU of the detector's NMS (metric 0 of "Large photos by tiles") of the
+ *        detection's box with the track's; the winner is the largest ovr, the lowest slot among equals, and it is matched iff
+ *        ovr >= iou_threshold (a NaN never matches).  A match: track.box = det.box (score included), hits += 1, missed = 0.
+ *     3. Expiry: every track live at entry and not matched gets missed += 1; missed > max_missed frees the slot and zeroes its state.
+ *     4. Births: every present, unmatched detection, in slot order, takes the lowest free slot (those freed in step 3 included):
+ *        id = next_id++, born = tick, hits = 1, missed = 0, n_embeds = 0, sum = 0, match_idx = -1, match_sim = 0.  Without a free slot the
+ *        detection is UNTRACKED (track_id = slot = -1) and dropped += 1.
+ *     5. Embedding, every tracked detection with valid != 0: sum[k] = fl(fl(decay * sum[k]) + e[k]) (two roundings, never an fma: the bits
+ *        of numpy float32), n_embeds += 1.
+ *     6. Template of a tracked detection: sum / ||sum||_2 when n_embeds > 0 and the norm is non-zero, else zeros (the norm reduced as
+ *        frt_matcher_build_templates reduces it) -> templates[f][d][dim]; rows of absent or untracked detections are zeros.
+ *     7. Identity, only with a matcher that has rows: ONE frt_matcher_top1_dev over all n_frames * max_faces template rows on the caller's
+ *        stream; for tracked detections with n_embeds > 0 the answer goes to the track (match_idx, match_sim) and to the output, every
+ *        other detection reports -1 / 0.  A coasting track (not seen in this frame) keeps its last identity.
+ *     8. tick += 1.
+ *   Output per face slot: frt_track_result.  age = tick - born + 1 (tick before step 8), confirmed = hits >= min_hits; an absent detection
+ *     is all zero with track_id = slot = match_idx = -1.
+ *   Every argument check runs before any device work - NULL pointers and ranges, then duplicate or out-of-range stream ids, then a matcher
+ *     whose num_col != dim (FRT_ERR_INVALID) -; a refused call writes nothing and changes no state.  embeds_dev / templates_dev must be
+ *     16-byte aligned.  The tracker has one mutex; updates queued on different HIP streams are the caller's to order.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct frt_tracker frt_tracker;
+typedef struct frt_track_options {
+    float iou_threshold; /* default 0.3; (0, 1]                                                                        */
+    int32_t max_missed;  /* default 5;   >= 0: updates a track may coast unseen                                        */
+    int32_t min_hits;    /* default 3;   >= 1: matched detections (the birth included) that make a track `confirmed` */
+    float decay;         /* default 1.0; (0, 1]: weight of the running sum against the new embedding                   */
+} frt_track_options;
+typedef struct frt_track_result {
+    int32_t track_id, slot, age, hits, n_embeds, confirmed, match_idx;
+    float match_sim;
+} frt_track_result; /* 32 bytes */
+typedef struct frt_track_state {
+    int32_t live, id;
+    frt_bbox box;
+    int32_t born, hits, missed, n_embeds, match_idx;
+    float match_sim;
+} frt_track_state; /* 52 bytes: one slot as frt_tracker_tracks returns it; a free slot is all zero */
+
+/* options NULL: the defaults; a value outside its range is FRT_ERR_INVALID.  Creation itself does no device work: the state is allocated
+ * and zeroed by the first call that passes its checks (a device that does not exist is FRT_ERR_DEVICE there). */
+int frt_tracker_create(int n_streams, int max_tracks, int max_faces, int dim, const frt_track_options *options, int device, frt_tracker **out);
+void frt_tracker_destroy(frt_tracker *t);
+/* results_dev frt_face_result [n_frames][max_faces], embeds_dev float [n_frames][max_faces][dim], tracks_dev frt_track_result
+ * [n_frames][max_faces], templates_dev float [n_frames][max_faces][dim] (may be NULL); m may be NULL (or hold no rows): no identity.
+ * Asynchronous on hip_stream (a hipStream_t as void*, NULL = default stream), no host synchronisation. */
+int frt_tracker_update_dev(frt_tracker *t, frt_matcher *m, const void *results_dev, const void *embeds_dev, int n_frames,
+                           const int32_t *stream_ids /* host, may be NULL */, void *tracks_dev, void *templates_dev, void *hip_stream);
+/* the same behind host pointers: upload, update, download, one synchronisation */
+int frt_tracker_update(frt_tracker *t, frt_matcher *m, const frt_face_result *results, const float *embeds, int n_frames,
+                       const int32_t *stream_ids, frt_track_result *tracks_out, float *templates_out /* may be NULL */);
+/* one stream's state, after everything queued on the streams the tracker has been updated on: slots_out [max_tracks] (every slot, live or
+ * not), sums_out [max_tracks][dim] (may be NULL), counters_out [3] = next_id, tick, dropped (may be NULL) */
+int frt_tracker_tracks(frt_tracker *t, int stream, frt_track_state *slots_out, float *sums_out, int32_t *counters_out);
+/* frees the slots and zeroes tick / dropped of one stream (-1: of all); next_id is kept */
+int frt_tracker_reset(frt_tracker *t, int stream);
+/* frt_pipeline_run with the tracker behind it: the upload, frt_pipeline_run_dev on the pipeline stream, frt_tracker_update_dev on that same
+ * stream with the pipeline's matcher, the downloads, one synchronisation.  results / embeds_out are frt_pipeline_run's, bit for bit;
+ * tracks_out [n_frames][max_faces], templates_out [n_frames][max_faces][512] (may be NULL).  Serial under the pipeline's run mutex, like
+ * frt_pipeline_run_photo_tiled.  The tracker's max_faces and dim must equal the pipeline's, n_frames <= max_frames, both on one device:
+ * FRT_ERR_INVALID before any device work otherwise. */
+int frt_pipeline_run_tracked(frt_pipeline *p, frt_tracker *t, const uint8_t *frames, int n_frames, const int32_t *stream_ids,
+                             frt_face_result *results, frt_track_result *tracks_out, float *embeds_out /* may be NULL */,
+                             float *templates_out /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).
  * ------------------------------------------------------------------------------------------------------------------ */
 /* kinds: 0 = off (drops the records), 1 = time every launch of the dominant kernel family (conv3x3 MFMA), 2 = time every stage,

@@ -25,6 +25,7 @@
 #include "common.h"
 #include "cvlite.h"
 #include "matmul.h"
+#include "tracker.h"
 
 struct CroppedFace {
     cv::Mat face;     // u8 BGR crop
@@ -270,6 +271,39 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         }
         if (sources) sources->assign(src.begin(), src.begin() + n);
         return out;
+    }
+    // Extension: the /inference loop for video (include/frt.h "Face tracker"): the current frames of several streams (each CV_8UC3 of the
+    // frame size; frame i belongs to stream streamIds[i], empty: to stream i) go through detector -> crop -> recogniser -> match as one
+    // pipeline call, and the tracker follows the faces on the device.  Returns the pipeline's records [frames x maxFacesPerScene]; tracks
+    // receives one record per face slot (a stable track_id, age, hits, confirmed), names the className of the row the TRACK's running
+    // template matches best - as getOutputs names rows - and "" for a face without a track, without an embedding yet, or with an empty
+    // gallery; sims (may be null) the template's similarity.  Uses enrolImages' pipeline; the tracker's maxFaces must be maxFacesPerScene.
+    template <class Detector>
+    std::vector<frt_face_result> trackFaces(Detector &detector, FaceTracker &tracker, const std::vector<cv::Mat> &frames, const std::vector<int> &streamIds,
+                                            std::vector<frt_track_result> &tracks, std::vector<std::string> &names, std::vector<float> *sims = nullptr) {
+        photoPipe(detector);
+        const size_t n = frames.size(), slots = n * (size_t)tracker.maxFaces(), rowBytes = (size_t)m_frameWidth * 3;
+        std::vector<uint8_t> packed(n * (size_t)m_frameHeight * rowBytes);
+        for (size_t i = 0; i < n; ++i) {
+            if (frames[i].rows != m_frameHeight || frames[i].cols != m_frameWidth) throw std::logic_error("trackFaces: a frame is not frameHeight x frameWidth");
+            for (int r = 0; r < m_frameHeight; ++r)
+                std::memcpy(&packed[(i * (size_t)m_frameHeight + (size_t)r) * rowBytes], frames[i].data + (size_t)r * (size_t)frames[i].step, rowBytes);
+        }
+        std::vector<frt_face_result> res(slots);
+        tracks.assign(slots, frt_track_result());
+        const std::vector<int32_t> ids(streamIds.begin(), streamIds.end());
+        checkFrtStatus(frt_pipeline_run_tracked(m_photoPipe, tracker.handle(), packed.data(), (int)n, ids.empty() ? nullptr : ids.data(), res.data(),
+                                                tracks.data(), nullptr, nullptr));
+        names.assign(slots, std::string());
+        if (sims) sims->assign(slots, 0.f);
+        for (size_t i = 0; i < slots; ++i) {
+            const frt_track_result &t = tracks[i];
+            if (t.match_idx >= 0 && (size_t)t.match_idx < classNames.size()) {
+                names[i] = classNames[(size_t)t.match_idx];
+                if (sims) (*sims)[i] = t.match_sim;
+            }
+        }
+        return res;
     }
     // every row of that name, as /delete/user removes every face of the user; the rows behind them close up in order (the order a
     // /reload would read them in: src/db.cpp:316-346).  Returns how many there were.

@@ -1,0 +1,59 @@
+// Extension (no counterpart in the reference, which answers every frame of the /inference WebSocket as if it were the only one): the face
+// tracker of include/frt.h ("Face tracker") behind a C++11 class.  One FaceTracker serves up to 1024 video streams - one stream per
+// WebSocket connection -; its state lives on the device.  ArcFaceIR50::trackFaces (arcface.h) puts it behind the pipeline.
+#ifndef FRT_TRACKER_H
+#define FRT_TRACKER_H
+
+#include <vector>
+
+#include "common.h"
+
+class FaceTracker {
+  public:
+    // options null: iou_threshold 0.3, max_missed 5, min_hits 3, decay 1.0
+    FaceTracker(int nStreams, int maxTracks, int maxFaces, int dim = 512, const frt_track_options *options = nullptr, int device = 0)
+        : h_(nullptr), nStreams_(nStreams), maxTracks_(maxTracks), maxFaces_(maxFaces), dim_(dim) {
+        checkFrtStatus(frt_tracker_create(nStreams, maxTracks, maxFaces, dim, options, device, &h_));
+    }
+    ~FaceTracker() { frt_tracker_destroy(h_); }
+    FaceTracker(const FaceTracker &) = delete;
+    FaceTracker &operator=(const FaceTracker &) = delete;
+
+    // One update from host memory: results [nFrames x maxFaces] and embeds [nFrames x maxFaces x dim] as the pipeline returns them, frame i
+    // belonging to stream streamIds[i] (empty: to stream i).  matcher (may be null): the gallery the tracks' templates are identified in.
+    // Returns the track records [nFrames x maxFaces]; templates (may be null) receives [nFrames x maxFaces x dim].
+    std::vector<frt_track_result> update(const std::vector<frt_face_result> &results, const std::vector<float> &embeds,
+                                         const std::vector<int> &streamIds = std::vector<int>(), frt_matcher *matcher = nullptr,
+                                         std::vector<float> *templates = nullptr) {
+        const int nFrames = (int)(results.size() / (size_t)maxFaces_);
+        std::vector<frt_track_result> out(results.size());
+        if (templates) templates->assign(results.size() * (size_t)dim_, 0.f);
+        const std::vector<int32_t> ids(streamIds.begin(), streamIds.end());
+        checkFrtStatus(frt_tracker_update(h_, matcher, results.data(), embeds.data(), nFrames, ids.empty() ? nullptr : ids.data(), out.data(),
+                                          templates ? templates->data() : nullptr));
+        return out;
+    }
+    // every slot of one stream, live or not; counters (may be null) <- next_id, tick, dropped
+    std::vector<frt_track_state> tracks(int stream, int counters[3] = nullptr, std::vector<float> *sums = nullptr) {
+        std::vector<frt_track_state> out((size_t)maxTracks_);
+        if (sums) sums->assign((size_t)maxTracks_ * (size_t)dim_, 0.f);
+        int32_t cnt[3] = {0, 0, 0};
+        checkFrtStatus(frt_tracker_tracks(h_, stream, out.data(), sums ? sums->data() : nullptr, cnt));
+        for (int i = 0; counters && i < 3; ++i) counters[i] = cnt[i];
+        return out;
+    }
+    // a connection closed (stream), or all of them (-1): its tracks go, track ids are never reused
+    void reset(int stream = -1) { checkFrtStatus(frt_tracker_reset(h_, stream)); }
+
+    int numStreams() const { return nStreams_; }
+    int maxTracks() const { return maxTracks_; }
+    int maxFaces() const { return maxFaces_; }
+    int dim() const { return dim_; }
+    frt_tracker *handle() { return h_; }
+
+  private:
+    frt_tracker *h_;
+    int nStreams_, maxTracks_, maxFaces_, dim_;
+};
+
+#endif  // FRT_TRACKER_H

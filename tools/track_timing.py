@@ -1,0 +1,176 @@
+"""What following faces across frames costs on the device, against doing it on the host.
+
+32 streams, max_faces 4, max_tracks 16, one 1M x 512 gallery, one process.  The tracker alone (a, b) is fed the records and embeddings of a
+seeded random walk (4 faces per stream, resident in HBM); the pipeline legs (c) run synthetic 640 x 640 frames.
+  a  frt_tracker_update_dev alone: the whole call by device events on its stream, and split by the library's profiling hooks
+     (frt_profile_enable(2)) into track_update (the update kernel), match_top1 (the extra search) and track_identity
+  b  the same update done the only way possible without the tracker: records and embeddings to the host, tests/track_ref.py, MatMul.top1 of
+     the templates (host wall time, the downloads included)
+  c  frt_pipeline_run_tracked against frt_pipeline_run of the same frames, on alternating legs in one process: --legs pairs of
+     --repeat calls each; per leg the median call, then the spread of the leg medians
+Needs the GPU.  Run it under a time limit, one process:
+
+    timeout 900 python tools/track_timing.py [--rows 1000000] [--streams 32] [--repeat 30] [--legs 3] --out result.json
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import numpy as np
+
+import __graft_entry__ as entry
+
+
+def walk(rng, n_streams, max_faces, updates):
+    """records of a random walk: max_faces faces per stream drifting over a 640 x 640 frame, nine in ten seen -> [updates][n_streams * max_faces]"""
+    import track_ref as tk
+    pos = rng.uniform(40, 500, (n_streams, max_faces, 2))
+    vel = rng.uniform(-5, 5, (n_streams, max_faces, 2))
+    out = []
+    for _ in range(updates):
+        pos += vel
+        vel[(pos < 10) | (pos > 540)] *= -1
+        r = np.zeros((n_streams, max_faces), tk.RESULT_DTYPE)
+        r["match_idx"] = -1
+        for s in range(n_streams):
+            seen = [f for f in range(max_faces) if rng.random() < 0.9]
+            for d, f in enumerate(seen):
+                x, y = int(pos[s, f, 0]), int(pos[s, f, 1])
+                r[s, d] = (x, y, x + 80, y + 80, 0.9 - 0.1 * d, s, -1, 0.0, 1)
+        out.append(r.reshape(-1))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--streams", type=int, default=32)
+    ap.add_argument("--repeat", type=int, default=30)
+    ap.add_argument("--legs", type=int, default=3)
+    ap.add_argument("--frame", type=int, default=640)
+    ap.add_argument("--out", required=True)
+    a = ap.parse_args()
+    import torch
+    import track_ref as tk
+    frt = entry.load_pkg()
+    S, MF, T, D, N = a.streams, 4, 16, 512, a.rows
+    F = S * MF
+    rng = np.random.default_rng(1)
+    g = frt.synth.make_gallery(N)
+    mm = frt.MatMul(0)
+    mm.init(g)
+    out = {"streams": S, "max_faces": MF, "max_tracks": T, "gallery_rows": N, "repeat": a.repeat, "legs": a.legs, "unit": "ms", "cases": {}}
+
+    def stats(ts):
+        return {"median": statistics.median(ts), "min": min(ts), "max": max(ts)}
+
+    def report(name, r):
+        out["cases"][name] = r
+        print("%-28s %s" % (name, json.dumps(r)), flush=True)
+
+    # ---- the walk, resident in HBM: each face's embeddings are a gallery row plus noise, so the screened search sees queries that match
+    steps = walk(rng, S, MF, a.repeat + 5)
+    who = rng.integers(0, N, (S, MF))
+    embeds = [frt.synth.make_queries(g, who.reshape(-1), noise=0.05).astype(np.float32) for _ in range(4)]
+    d_res = [torch.from_numpy(r.view(np.uint8).copy()).cuda() for r in steps]
+    d_emb = [torch.from_numpy(e).cuda() for e in embeds]
+    d_trk = torch.zeros(F * 32, dtype=torch.uint8, device="cuda")
+    d_tpl = torch.zeros((F, D), dtype=torch.float32, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    # ---- a: update_dev alone
+    trk = frt.Tracker(S, T, MF, D)
+    upd = lambda k: trk.updateDev(d_res[k].data_ptr(), d_emb[k % 4].data_ptr(), S, d_trk.data_ptr(), d_tpl.data_ptr(), None, mm, stream)
+    for k in range(5):
+        upd(k)
+    torch.cuda.synchronize()
+    ts = []
+    for k in range(5, 5 + a.repeat):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        upd(k)
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    report("a_update_dev", stats(ts))
+    trk.reset()
+    frt.profile_enable(2)
+    for k in range(a.repeat):
+        upd(k)
+    torch.cuda.synchronize()
+    names, ms, _ = frt.profile_collect()
+    frt.profile_enable(0)
+    for part in ("track_update", "match_top1", "track_identity"):
+        ks = [float(t) for n, t in zip(names, ms) if n == part]
+        assert len(ks) == a.repeat, (part, len(ks), set(names))
+        report("a_" + part, stats(ks))
+    live = sum(int((trk.tracks(s)[0]["live"] != 0).sum()) for s in range(S))
+    out["live_tracks_after_a"] = live
+
+    # ---- b: the same update on the host
+    ref = tk.Tracker(S, T, MF, D)
+    ts, parts = [], {"download": [], "track_ref": [], "top1": []}
+    for k in range(a.repeat):
+        t0 = time.perf_counter()
+        res = d_res[k].cpu().numpy().view(tk.RESULT_DTYPE)
+        emb = d_emb[k % 4].cpu().numpy()
+        t1 = time.perf_counter()
+        tracks, tpl = ref.update(res, emb)
+        t2 = time.perf_counter()
+        idx, sim = mm.top1(tpl.reshape(-1, D).astype(np.float32))
+        ref.apply_identity(tracks, None, idx, sim)
+        t3 = time.perf_counter()
+        ts.append((t3 - t0) * 1e3)
+        for name, dt in (("download", t1 - t0), ("track_ref", t2 - t1), ("top1", t3 - t2)):
+            parts[name].append(dt * 1e3)
+    report("b_host_update", stats(ts))
+    for name, v in parts.items():
+        report("b_" + name, stats(v))
+    trk.close()
+    mm.close()
+
+    # ---- c: the pipeline with and without the tracker behind it, alternating legs
+    tmp = tempfile.mkdtemp(prefix="frt_track_timing_")
+    s = frt.synth
+    det_path = frt.write_weights(os.path.join(tmp, "det.frtw"), s.retinaface_state(1), 1)
+    rec_path = frt.write_weights(os.path.join(tmp, "rec.frtw"), s.arcface_state(2, "ir", calib=s.load_calibration("ir")), 2)
+    W = H = a.frame
+    det = frt.RetinaFace(det_path, W, H, (3, H, W), S, MF, 0.4, 0.6)
+    rec = frt.ArcFaceIR50(rec_path, W, H, (3, 112, 112), 512, F, MF, 0.65)
+    rec.setGallery(g)
+    rec.initMatMul()
+    pipe = frt.Pipeline(det, rec, S)
+    frames = s.make_frames(S, H, W)
+    trk = frt.Tracker(S, T, MF, D)
+    legs = {"run": [], "run_tracked": []}
+
+    def leg(fn):
+        for _ in range(3):
+            fn()
+        ts = []
+        for _ in range(a.repeat):
+            t0 = time.perf_counter()
+            fn()
+            ts.append((time.perf_counter() - t0) * 1e3)
+        return statistics.median(ts)
+
+    for _ in range(a.legs):
+        legs["run"].append(leg(lambda: pipe.run(frames)))
+        legs["run_tracked"].append(leg(lambda: pipe.runTracked(trk, frames)))
+    for name, v in legs.items():
+        report("c_" + name, {"leg_medians": v, "median": statistics.median(v), "min": min(v), "max": max(v)})
+    out["c_faces_per_call"] = int((pipe.run(frames)[0]["score"] > 0).sum())
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+    trk.close(), pipe.close(), rec.close(), det.close()
+
+
+if __name__ == "__main__":
+    main()
