@@ -1,4 +1,4 @@
-// The shared core of the launch-alone check programs (det_tail_check, match_stage_check, arc_launch_check, arc32_launch_check, det_op_check):
+// The shared core of the launch-alone check programs (det_tail_check, match_stage_check, match_exact_check, arc_launch_check, arc32_launch_check, det_op_check):
 // what they all need to stop at the first error, to read and write the files of a case directory, and to count what a launch changed outside
 // the memory it was given.  Two buffer models sit on top of the small utilities:
 //   * NAMED GUARDED BUFFERS driven by an op list (run_ops: DIR/ops.txt): every buffer between two guards of kGuard bytes, the guards and every

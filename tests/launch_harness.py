@@ -1,6 +1,6 @@
 """What the launch-alone checks share on the Python side (the C++ side: tests/cpp/check_common.hpp): the one compile line for the host programs
 under tests/cpp/, the runner that starts a harness process under its own timeout and ends a module at the first process error, the reader of
-results.txt, and the writer of the op list that the named-guarded-buffer programs (det_tail_check, match_stage_check) run."""
+results.txt, and the writer of the op list that the named-guarded-buffer programs (det_tail_check, match_stage_check, match_exact_check) run."""
 import os
 import subprocess
 import zlib
