@@ -35,6 +35,7 @@ lib = ctypes.CDLL(LIB_PATH)
 # ----------------------------------------------------------------------------------------------------------------------
 FRT_OK, FRT_ERR_INVALID, FRT_ERR_NOT_FOUND, FRT_ERR_FORMAT, FRT_ERR_DEVICE, FRT_ERR_EMPTY, FRT_ERR_EMPTY_ROI, FRT_ERR_CAPACITY = range(8)
 FRT_ENROL_OK, FRT_ENROL_MANY, FRT_ENROL_NONE, FRT_ENROL_EMPTY_ROI = 1, 2, 3, 4  # frt_enrol_status: the "exactly one face" rule of /insert/face
+FRT_ENROL_LOW_QUALITY = 5  # ... and the gate of the quality-gated calls: one valid face whose quality record carries a flag
 
 BBOX_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("score", "<f4")])  # == struct Bbox, common.h:13-16
 RESULT_DTYPE = np.dtype([("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("score", "<f4"), ("frame", "<i4"),
@@ -183,6 +184,11 @@ ABI = {
     "frt_tracker_tracks": (_i, [_vp, _i, _vp, _vp, _vp]),
     "frt_tracker_reset": (_i, [_vp, _i]),
     "frt_pipeline_run_tracked": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "frt_face_quality_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    "frt_face_quality": (_i, [_vp, _vp, _i, _vp, _vp, _i]),
+    "frt_enrol_select_gated_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "frt_pipeline_run_quality": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "frt_pipeline_enrol_images_gated": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
     "frt_profile_enable": (_i, [_i]),
     "frt_profile_collect": (_i, [_vp, _sz, _vp, _vp, _i]),
 }
@@ -881,6 +887,60 @@ def enrol_select_dev(results_ptr, embeds_ptr, n_frames, max_faces, status_ptr, f
 # ----------------------------------------------------------------------------------------------------------------------
 # class ArcFaceIR50 (src/arcface.h)
 # ----------------------------------------------------------------------------------------------------------------------
+def enrol_select_gated_dev(results_ptr, embeds_ptr, n_frames, max_faces, status_ptr, face_ptr, rows_ptr, count_ptr, hip_stream=None, quality_ptr=None):
+    """frt_enrol_select_gated_dev: ``enrol_select_dev`` with the quality gate - an OK frame whose slot 0 record (``quality_ptr``:
+    QUALITY_DTYPE [n_frames, max_faces] on the device, None: no gate) carries a flag is FRT_ENROL_LOW_QUALITY and adds no row."""
+    _check(lib.frt_enrol_select_gated_dev(_vp(results_ptr), _vp(embeds_ptr), int(n_frames), int(max_faces), _vp(status_ptr),
+                                          _vp(face_ptr) if face_ptr else None, _vp(rows_ptr), _vp(count_ptr), _vp(hip_stream) if hip_stream else None,
+                                          _vp(quality_ptr) if quality_ptr else None))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# face quality: is a crop good enough to use (include/frt.h "Face quality"; tests/quality_ref.py restates it in numpy)
+# ----------------------------------------------------------------------------------------------------------------------
+QUALITY_DTYPE = np.dtype([("sum_y", "<u4"), ("sum_y2", "<u4"), ("sum_lap", "<i4"), ("n_dark", "<u4"), ("n_bright", "<u4"), ("size", "<i4"),
+                          ("sum_lap2", "<u8"), ("mean", "<f4"), ("luma_var", "<f4"), ("sharpness", "<f4"), ("score", "<f4"), ("flags", "<u4"),
+                          ("present", "<i4")])  # == struct frt_face_quality
+assert QUALITY_DTYPE.itemsize == 56 and QUALITY_DTYPE.fields["sum_lap2"][1] == 24
+QUALITY_SMALL, QUALITY_BLURRED, QUALITY_FLAT, QUALITY_DARK, QUALITY_BRIGHT, QUALITY_CLIPPED, QUALITY_LOW_SCORE = 1, 2, 4, 8, 16, 32, 64
+
+
+class QualityOptions(ctypes.Structure):  # == frt_quality_options; the defaults flag nothing - there are no recommended thresholds
+    _fields_ = [("min_size", ctypes.c_int32), ("min_sharpness", ctypes.c_float), ("min_luma_var", ctypes.c_float), ("min_mean", ctypes.c_float),
+                ("max_mean", ctypes.c_float), ("max_clipped", ctypes.c_int32), ("min_score", ctypes.c_float)]
+
+    def __init__(self, min_size=0, min_sharpness=0.0, min_luma_var=0.0, min_mean=0.0, max_mean=255.0, max_clipped=12544, min_score=0.0):
+        super().__init__(min_size, min_sharpness, min_luma_var, min_mean, max_mean, max_clipped, min_score)
+
+
+def _quality_options(options):
+    if options is not None and not isinstance(options, QualityOptions):
+        raise TypeError("options must be a QualityOptions or None")
+    return ctypes.addressof(options) if options is not None else None
+
+
+def faceQuality(crops, results=None, options=None, device=0):
+    """frt_face_quality: u8 BGR crops [n, 112, 112, 3] (and, optionally, their RESULT_DTYPE records [n]: a record with valid == 0 marks an
+    absent slot, whose crop is not read) -> QUALITY_DTYPE [n].  A face passes iff ``present`` and ``flags == 0``."""
+    crops = np.ascontiguousarray(crops, np.uint8)
+    if crops.ndim != 4 or crops.shape[1:] != (112, 112, 3):
+        raise ValueError("crops must be [n, 112, 112, 3]")
+    n = crops.shape[0]
+    if results is not None:
+        results = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
+        if results.size != n:
+            raise ValueError("one record per crop")
+    out = np.zeros(n, QUALITY_DTYPE)
+    _check(lib.frt_face_quality(_ptr(crops), _ptr(results), n, _quality_options(options), _ptr(out), int(device)))
+    return out
+
+
+def face_quality_dev(crops_ptr, results_ptr, n, quality_ptr, options=None, hip_stream=None):
+    """frt_face_quality_dev: asynchronous on ``hip_stream``; raw device addresses (``results_ptr`` may be None)."""
+    _check(lib.frt_face_quality_dev(_vp(crops_ptr), _vp(results_ptr) if results_ptr else None, int(n), _quality_options(options), _vp(quality_ptr),
+                                    _vp(hip_stream) if hip_stream else None))
+
+
 class ArcFaceIR50:
     classCount = 0  # the reference keeps this as a process-wide static (arcface.cpp:19); per-instance here (SURVEY App. C.14)
 
@@ -1293,11 +1353,28 @@ class Pipeline:
         _check(lib.frt_pipeline_run_tracked(self._h, tracker._h, _ptr(frames), n, _ptr(ids), _ptr(res), _ptr(trk), _ptr(emb), _ptr(tpl)))
         return res, emb, trk, tpl
 
-    def enrolImages(self, classNames, images, labels=None):
+    def runQuality(self, frames, options=None, want_embeds=True, want_crops=False):
+        """``run`` that also scores every face slot on the pipeline stream (frt_pipeline_run_quality) -> (records, embeddings or None -
+        exactly ``run``'s -, QUALITY_DTYPE [n * max_faces], an unused or empty-ROI slot all zero[, u8 crops [n * max_faces, 112, 112, 3]])."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != (self.det.frameHeight, self.det.frameWidth, 3):
+            raise ValueError("runQuality: frames must be [n, frameHeight, frameWidth, 3]")
+        res = np.zeros(n * self.max_faces, RESULT_DTYPE)
+        emb = np.zeros((n * self.max_faces, 512), np.float32) if want_embeds else None
+        qual = np.zeros(n * self.max_faces, QUALITY_DTYPE)
+        crops = np.zeros((n * self.max_faces, 112, 112, 3), np.uint8) if want_crops else None
+        _check(lib.frt_pipeline_run_quality(self._h, _ptr(frames), n, _quality_options(options), _ptr(res), _ptr(qual), _ptr(emb), _ptr(crops)))
+        return (res, emb, qual, crops) if want_crops else (res, emb, qual)
+
+    def enrolImages(self, classNames, images, labels=None, quality=None, want_quality=False):
         """/insert/face for whole photos: detect, require exactly one face, embed, and append the accepted photos' rows to the live gallery as
         ONE edit, device to device.  ``labels``: one int per image for a labelled gallery.  Returns (status [n] of FRT_ENROL_*, first new
         row index, embeddings [n_enrolled, 512] - exactly the rows added, faces [n] records with the match against the gallery as it was
-        before the call).  The recogniser's ``classNames`` / ``classCount`` grow by the accepted names only."""
+        before the call).  The recogniser's ``classNames`` / ``classCount`` grow by the accepted names only.
+        ``quality`` (a QualityOptions) or ``want_quality`` takes the gated route (frt_pipeline_enrol_images_gated): a photo whose one face
+        carries a quality flag comes back FRT_ENROL_LOW_QUALITY and adds no row, and with ``want_quality`` the face's QUALITY_DTYPE record
+        [n] is returned as a fifth value."""
         arr, keep = _face_images(images)
         names = list(classNames)
         n = len(keep)
@@ -1318,11 +1395,17 @@ class Pipeline:
         faces = np.zeros(n, RESULT_DTYPE)
         embeds = np.zeros((n, 512), np.float32)
         first, count = _i(0), _i(0)
-        _check(lib.frt_pipeline_enrol_images(self._h, arr, n, _ptr(l), _ptr(status), _ptr(faces), _ptr(embeds), ctypes.byref(first), ctypes.byref(count)))
+        qual = np.zeros(n, QUALITY_DTYPE) if want_quality else None
+        if quality is not None or want_quality:
+            _check(lib.frt_pipeline_enrol_images_gated(self._h, arr, n, _ptr(l), _quality_options(quality), _ptr(status), _ptr(faces), _ptr(qual),
+                                                       _ptr(embeds), ctypes.byref(first), ctypes.byref(count)))
+        else:
+            _check(lib.frt_pipeline_enrol_images(self._h, arr, n, _ptr(l), _ptr(status), _ptr(faces), _ptr(embeds), ctypes.byref(first), ctypes.byref(count)))
         mm._edited()
         self.rec.classNames = list(self.rec.classNames) + [nm for nm, st in zip(names, status) if st == FRT_ENROL_OK]
         self.rec.classCount = len(self.rec.classNames)
-        return status, first.value, embeds[:count.value].copy(), faces
+        out = (status, first.value, embeds[:count.value].copy(), faces)
+        return out + (qual,) if want_quality else out
 
     def submit(self, frames, results, embeds=None, crops=None):
         """Asynchronous host boundary: queue one batch (``frames`` u8 [n, H, W, 3], ``results`` a RESULT_DTYPE array of

@@ -1,5 +1,5 @@
 // libfrt.so: whole photos of any sizes (include/frt.h "Whole photos of any sizes"): frt_resize_images, frt_enrol_select_dev,
-// frt_pipeline_run_images, frt_pipeline_enrol_images - the ragged front end of the pipeline.  A batch is cut into chunks of at most
+// frt_pipeline_run_images, frt_pipeline_enrol_images (and its quality-gated twin, include/frt.h "Face quality") - the ragged front end of the pipeline.  A batch is cut into chunks of at most
 // max_frames photos (frt_plan_face_chunks); per chunk the photos are packed into pinned memory, uploaded and resized into a device frame
 // buffer on the ingest stream, and handed to the pipeline's run_dev path with the resize's event as the call's "frames are ready" event.
 // Two staging sets: chunk i + 1 uploads and resizes while chunk i runs, and the pipeline's own stage overlap carries across chunks.
@@ -134,6 +134,7 @@ void frt_pipeline::release_images() {
         (void)hipStreamDestroy(is.ingest);
     }
     if (is.finished) (void)hipEventDestroy(is.finished);
+    if (is.q_up) (void)hipEventDestroy(is.q_up);
     for (int b = 0; b < ImageStage::NSET; ++b)
         for (hipEvent_t ev : {is.uploaded[b], is.ready[b], is.done[b]})
             if (ev) (void)hipEventDestroy(ev);
@@ -216,9 +217,17 @@ int frt_pipeline_run_images(frt_pipeline *p, const frt_face_image *images, int n
     });
 }
 
-int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int n, const int32_t *labels, int32_t *status_out,
-                              frt_face_result *faces_out, float *embeds_out, int *first_row_out, int *n_enrolled_out) {
-    return guarded([&] {
+}  // extern "C"
+
+namespace {
+
+// frt_pipeline_enrol_images and frt_pipeline_enrol_images_gated.  gate null: the first, as it always was - no crops, no quality launch,
+// the selection without records.  gate set (its ranges checked by the caller, before anything here): every chunk also leaves its crops,
+// the quality launch and the gated selection follow its stages on the pipeline stream, and quality_out (may be null) gets slot 0's
+// record of every photo.
+void enrol_images(frt_pipeline *p, const frt_face_image *images, int n, const int32_t *labels, const frt_quality_options *gate, int32_t *status_out,
+                  frt_face_result *faces_out, struct frt_face_quality *quality_out, float *embeds_out, int *first_row_out, int *n_enrolled_out) {
+    {  // (a scope of its own, indented as the entry point's guarded block was: what the ungated call runs reads as it did)
         check_face_images(images, n, "enrolImages");
         if (!p) raise(FRT_ERR_INVALID, "enrolImages: null pipeline");
         if (n > 65536) raise(FRT_ERR_CAPACITY, "enrolImages: more than 65536 images in one call");
@@ -250,17 +259,33 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
         is.d_face.reserve((size_t)n);
         is.h_status.reserve((size_t)n);
         is.h_face.reserve((size_t)n);
+        const size_t K = (size_t)p->max_faces;
+        for (int b = 0; gate && b < ImageStage::NSET; ++b) {
+            is.d_quality[b].reserve((size_t)p->F_cap);
+            if (quality_out) is.h_quality[b].reserve((size_t)p->F_cap);
+        }
         bool first_chunk = true;
         run_image_chunks(
-            p, images, desc, chunks, true, false,
+            p, images, desc, chunks, true, gate != nullptr,
             [&](const frt_face_chunk &c, int b, hipStream_t s) {  // after each chunk the selection kernel appends to the one dense buffer
                 if (first_chunk) HIPCHK(hipMemsetAsync(is.d_count.get(), 0, sizeof(int32_t), s));
                 first_chunk = false;
-                ProfScope ps(2, "enrol_select", (double)c.count, s);
-                launch_enrol_select(is.d_results[b].get(), is.d_embeds[b].get(), c.count, p->max_faces, is.d_status.get() + c.first, is.d_face.get() + c.first,
-                                    is.d_rows.get(), is.d_count.get(), s);
+                if (gate) {  // every slot of the chunk is scored; the selection reads slot 0's record of each photo
+                    ProfScope ps(2, "face_quality", (double)c.count * K, s);
+                    launch_face_quality(is.d_crops[b].get(), is.d_results[b].get(), c.count * (int)K, *gate, is.d_quality[b].get(), s);
+                }
+                {
+                    ProfScope ps(2, "enrol_select", (double)c.count, s);
+                    launch_enrol_select(is.d_results[b].get(), is.d_embeds[b].get(), c.count, p->max_faces, is.d_status.get() + c.first,
+                                        is.d_face.get() + c.first, is.d_rows.get(), is.d_count.get(), s, gate ? is.d_quality[b].get() : nullptr);
+                }
+                if (gate && quality_out)
+                    HIPCHK(hipMemcpyAsync(is.h_quality[b].get(), is.d_quality[b].get(), (size_t)c.count * K * sizeof(struct frt_face_quality), hipMemcpyDeviceToHost, s));
             },
-            [](const frt_face_chunk &, int) {});
+            [&](const frt_face_chunk &c, int b) {
+                if (!gate || !quality_out) return;
+                for (int i = 0; i < c.count; ++i) quality_out[c.first + i] = is.h_quality[b].get()[(size_t)i * K];  // slot 0 of photo i
+            });
         {  // status, faces and the count come down once, behind the last chunk's selection, into pinned memory: the copies are asynchronous
            // and run_mu is held for the enqueue alone
             std::lock_guard<std::mutex> lk(p->run_mu);
@@ -292,6 +317,24 @@ int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int
         const int first = matcher_add_rows_dev(m, is.d_rows.get(), labels ? accepted.data() : nullptr, count);
         if (first_row_out) *first_row_out = first;
         if (n_enrolled_out) *n_enrolled_out = count;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int frt_pipeline_enrol_images(frt_pipeline *p, const frt_face_image *images, int n, const int32_t *labels, int32_t *status_out,
+                              frt_face_result *faces_out, float *embeds_out, int *first_row_out, int *n_enrolled_out) {
+    return guarded([&] { enrol_images(p, images, n, labels, nullptr, status_out, faces_out, nullptr, embeds_out, first_row_out, n_enrolled_out); });
+}
+
+int frt_pipeline_enrol_images_gated(frt_pipeline *p, const frt_face_image *images, int n, const int32_t *labels, const frt_quality_options *options,
+                                    int32_t *status_out, frt_face_result *faces_out, struct frt_face_quality *quality_out, float *embeds_out,
+                                    int *first_row_out, int *n_enrolled_out) {
+    return guarded([&] {
+        const frt_quality_options gate = quality_checked_options(options, "enrolImages");
+        enrol_images(p, images, n, labels, &gate, status_out, faces_out, quality_out, embeds_out, first_row_out, n_enrolled_out);
     });
 }
 

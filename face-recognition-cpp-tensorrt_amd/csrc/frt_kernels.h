@@ -283,9 +283,16 @@ void launch_tile_faces_select(const frt_bbox *boxes, const int32_t *src, const f
 
 // ---------------------------------------------------------------- the "exactly one face" rule of /insert/face (kernels_enrol.hip)
 // results [n_frames][max_faces], embeds [n_frames][max_faces][512] -> status [n_frames] (frt_enrol_status), face_out [n_frames] (may be
-// null), the OK frames' embeddings to rows[*count ...], *count advanced; one workgroup
+// null), the OK frames' embeddings to rows[*count ...], *count advanced; one workgroup.  quality [n_frames][max_faces] (may be null): an OK
+// frame whose slot 0 record carries a flag is FRT_ENROL_LOW_QUALITY instead and adds no row
 void launch_enrol_select(const frt_face_result *results, const float *embeds, int n_frames, int max_faces, int32_t *status, frt_face_result *face_out,
-                         float *rows, int32_t *count, hipStream_t s);
+                         float *rows, int32_t *count, hipStream_t s, const struct frt_face_quality *quality = nullptr);
+
+// ---------------------------------------------------------------- face quality (kernels_quality.hip; frt_quality.cpp, include/frt.h "Face quality")
+// crops u8 [n][112][112][3] (16-byte aligned), results [n] (may be null: every slot present) -> out [n], every record written; one
+// workgroup per slot; n < 1 launches nothing
+void launch_face_quality(const uint8_t *crops, const frt_face_result *results, int n, const frt_quality_options &opt, struct frt_face_quality *out,
+                         hipStream_t s);
 
 // ---------------------------------------------------------------- detector network (kernels_det.hip), fp32 NCHW
 struct DwPwArgs {

@@ -209,6 +209,15 @@ struct frt_pipeline {
         DevBuf<frt_face_result> d_face;
         PinnedBuf<frt_face_result> h_face;
         hipEvent_t finished = nullptr;
+        // face quality (frt_quality.cpp, include/frt.h "Face quality"): a chunk's records of the gated enrolment, and the staging of one
+        // frt_pipeline_run_quality call (grown to its frame count) with its "frames are on the device" event
+        DevBuf<struct frt_face_quality> d_quality[NSET];            // [F_cap]
+        PinnedBuf<struct frt_face_quality> h_quality[NSET];
+        DevBuf<uint8_t> q_frames, q_crops;
+        DevBuf<frt_face_result> q_results;
+        DevBuf<float> q_embeds;
+        DevBuf<struct frt_face_quality> q_quality;
+        hipEvent_t q_up = nullptr;
     } images;
     std::mutex images_mu;
     void release_images();  // (frt_pipeline_destroy)
@@ -307,3 +316,7 @@ struct frt_pipeline {
     long submit(const uint8_t *frames, int n_frames, frt_face_result *results, float *embeds_out, bool synchronous = false, uint8_t *crops_host = nullptr);
     void wait(long ticket);
 };
+
+// The gate's thresholds, checked as every "Face quality" entry point checks them before any device work (frt_quality.cpp): null gives the
+// defaults, under which nothing can be flagged; a negative min_size / max_clipped, a NaN or min_mean > max_mean raises FRT_ERR_INVALID.
+frt_quality_options quality_checked_options(const frt_quality_options *options, const char *who);

@@ -5,7 +5,9 @@
 // frt_face_result[n_frames][max_faces] (boxes fill a frame's slots from slot 0, an unused slot has score 0) and embeddings
 // [n_frames][max_faces][512] - and per frame
 //   - counts the slots with box.score > 0 and writes status[frame] (FRT_ENROL_*: one box with valid != 0 is OK, one box whose ROI is empty
-//     - valid == 0, score > 0 - is EMPTY_ROI: OpenCV would throw there);
+//     - valid == 0, score > 0 - is EMPTY_ROI: OpenCV would throw there); with quality records [n_frames][max_faces] (may be null: the
+//     gate is off and nothing below changes) an OK frame whose SLOT 0 record has flags != 0 is LOW_QUALITY instead: its face is written
+//     as for OK, its row is not copied;
 //   - writes face_out[frame] (may be null): slot 0's record for OK and EMPTY_ROI, zeros otherwise, `frame` kept either way;
 //   - copies slot 0's embedding of every OK frame to rows[base + rank], in frame order: base = *count at entry, rank = exclusive prefix sum
 //     of the OK flags; 16-byte loads and stores;
@@ -21,7 +23,7 @@ constexpr int SEL_THREADS = 256, SEL_WAVES = SEL_THREADS / 64, ROW_VEC = 512 / 4
 __global__ __launch_bounds__(SEL_THREADS) void enrol_select_kernel(const frt_face_result *__restrict__ results, const float *__restrict__ embeds,
                                                                    int n_frames, int max_faces, int32_t *__restrict__ status,
                                                                    frt_face_result *__restrict__ face_out, float *__restrict__ rows,
-                                                                   int32_t *__restrict__ count) {
+                                                                   int32_t *__restrict__ count, const struct frt_face_quality *__restrict__ quality) {
     __shared__ int s_wave[SEL_WAVES];
     __shared__ int s_dst[SEL_THREADS];  // rank of the tile's frame among the call's OK frames, -1: not OK
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -37,12 +39,13 @@ __global__ __launch_bounds__(SEL_THREADS) void enrol_select_kernel(const frt_fac
             int boxes = 0;
             for (int k = 0; k < max_faces; ++k) boxes += r[k].box.score > 0.f ? 1 : 0;
             const frt_face_result r0 = r[0];
-            const int st = boxes == 0 ? FRT_ENROL_NONE : boxes > 1 ? FRT_ENROL_MANY : r0.valid != 0 ? FRT_ENROL_OK : FRT_ENROL_EMPTY_ROI;
+            int st = boxes == 0 ? FRT_ENROL_NONE : boxes > 1 ? FRT_ENROL_MANY : r0.valid != 0 ? FRT_ENROL_OK : FRT_ENROL_EMPTY_ROI;
+            if (quality && st == FRT_ENROL_OK && quality[(size_t)frame * max_faces].flags != 0u) st = FRT_ENROL_LOW_QUALITY;
             ok = st == FRT_ENROL_OK;
             status[frame] = st;
             if (face_out) {
                 frt_face_result o = r0;
-                if (st != FRT_ENROL_OK && st != FRT_ENROL_EMPTY_ROI) {
+                if (st != FRT_ENROL_OK && st != FRT_ENROL_EMPTY_ROI && st != FRT_ENROL_LOW_QUALITY) {
                     o.box = frt_bbox{0, 0, 0, 0, 0.f};
                     o.match_idx = 0;
                     o.match_sim = 0.f;
@@ -79,6 +82,7 @@ __global__ __launch_bounds__(SEL_THREADS) void enrol_select_kernel(const frt_fac
 }  // namespace
 
 void launch_enrol_select(const frt_face_result *results, const float *embeds, int n_frames, int max_faces, int32_t *status, frt_face_result *face_out,
-                         float *rows, int32_t *count, hipStream_t s) {
-    hipLaunchKernelGGL(enrol_select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, results, embeds, n_frames, max_faces, status, face_out, rows, count);
+                         float *rows, int32_t *count, hipStream_t s, const struct frt_face_quality *quality) {
+    hipLaunchKernelGGL(enrol_select_kernel, dim3(1), dim3(SEL_THREADS), 0, s, results, embeds, n_frames, max_faces, status, face_out, rows, count,
+                       quality);
 }

@@ -677,7 +677,8 @@ typedef enum frt_enrol_status {
     FRT_ENROL_MANY = 2,      /* more than one box (src/app.cpp:172-174).  With maxFacesPerScene == 1 the cap behind NMS leaves at most
                               * one box, so this status cannot occur - the reference behaves the same                               */
     FRT_ENROL_NONE = 3,      /* no box (src/app.cpp:175-177)                                                                        */
-    FRT_ENROL_EMPTY_ROI = 4  /* one box whose ROI is empty (valid == 0, score > 0): OpenCV would throw there                       */
+    FRT_ENROL_EMPTY_ROI = 4, /* one box whose ROI is empty (valid == 0, score > 0): OpenCV would throw there                       */
+    FRT_ENROL_LOW_QUALITY = 5 /* one valid box whose quality record carries a flag ("Face quality" below); only the gated calls answer it */
 } frt_enrol_status;
 /* ragged counterpart of frt_resize_frame: n images of any sizes -> out u8 [n][out_rows][out_cols][3], one launch */
 int frt_resize_images(const frt_face_image *images, int n, uint8_t *out, int out_rows, int out_cols, int device);
@@ -890,6 +891,102 @@ int frt_tracker_reset(frt_tracker *t, int stream);
 int frt_pipeline_run_tracked(frt_pipeline *p, frt_tracker *t, const uint8_t *frames, int n_frames, const int32_t *stream_ids,
                              frt_face_result *results, frt_track_result *tracks_out, float *embeds_out /* may be NULL */,
                              float *templates_out /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Face quality: is a face good enough to use?  Every route above takes pixels to identities and none asks.  /insert/face applies the
+ * "exactly one face" rule and nothing else, so a 20-pixel, blurred or blown-out face is embedded and appended to the live gallery, where it
+ * costs false matches for as long as it stays; the reply step of /inference sends one crop back (src/app.cpp:328) with no measure by which
+ * a caller could pick or drop one.  These entry points score the u8 BGR 112x112 crops the pipeline already keeps in HBM
+ * (frt_pipeline_submit_crops) and gate enrolment by the score.  The reference has no quality measure, so the semantics are fixed here, to
+ * the integer (tests/quality_ref.py restates them in numpy): every answer is compared for equality, not within a tolerance.
+ *   Per crop u8 [112][112][3], B G R:
+ *     Y = (29 * B + 150 * G + 77 * R + 128) >> 8                                   luma, 0 .. 255 (the weights sum to 256)
+ *     sum_y = sum Y, sum_y2 = sum Y * Y                                            over all N = 12544 pixels (both fit uint32)
+ *     L = 4 * Y[r][c] - Y[r-1][c] - Y[r+1][c] - Y[r][c-1] - Y[r][c+1]              on the M = 12100 interior pixels (rows, columns 1 .. 110)
+ *     sum_lap = sum L (int32), sum_lap2 = sum L * L (uint64: a 0 / 255 checkerboard gives 12 588 840 000)
+ *     n_dark = #{Y < 32}, n_bright = #{Y > 223}
+ *     mean      = float32(sum_y / 12544.0)
+ *     luma_var  = float32((N * sum_y2 - sum_y^2) / float64(N^2))
+ *     sharpness = float32((M * sum_lap2 - sum_lap^2) / float64(M^2))               the variance of the Laplacian
+ *     The numerators are exact integers below 2^53 and the denominators are exact: one correctly rounded float64 division, one rounding to
+ *     float32.
+ *   With a record (frt_face_result) beside the crop: size = min(x2 - x1, y2 - y1) - the extents of the crop's ROI, as the gate of
+ *     frt_pipeline_run_photo_tiled takes them - and score = box.score.  Without records size = 0 and score = 0.
+ *   Presence: a slot is PRESENT iff there is no record array or its record has valid != 0 (the crops of unused and empty-ROI slots are
+ *     unspecified).  An absent slot's record is all zero and its crop is not read.
+ *   flags (frt_quality_flag): each comparison is strict as written - a value EQUAL to its threshold passes; SMALL and LOW_SCORE are
+ *     evaluated only with records.  A face PASSES iff it is present and flags == 0.
+ *   options NULL: {0, 0, 0, 0, 255, 12544, 0}, under which nothing can be flagged.  A negative min_size or max_clipped, a NaN, or
+ *     min_mean > max_mean is FRT_ERR_INVALID before any device work.
+ *   THERE ARE NO RECOMMENDED THRESHOLDS.  Nobody has measured these values on real faces with this library (the tests run on synthetic
+ *     weights and synthetic faces): measure sharpness / luma_var / mean on your own cameras' accepted and rejected faces before gating.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct frt_quality_options {
+    int32_t min_size;    /* default 0;     >= 0                                                                          */
+    float min_sharpness; /* default 0                                                                                    */
+    float min_luma_var;  /* default 0                                                                                    */
+    float min_mean;      /* default 0;     <= max_mean                                                                   */
+    float max_mean;      /* default 255                                                                                  */
+    int32_t max_clipped; /* default 12544; >= 0: pixels that may be darker than 32 or brighter than 223, together        */
+    float min_score;     /* default 0                                                                                    */
+} frt_quality_options;
+typedef enum frt_quality_flag {
+    FRT_QUALITY_SMALL = 1,      /* size < min_size              (records only) */
+    FRT_QUALITY_BLURRED = 2,    /* sharpness < min_sharpness                   */
+    FRT_QUALITY_FLAT = 4,       /* luma_var < min_luma_var                     */
+    FRT_QUALITY_DARK = 8,       /* mean < min_mean                             */
+    FRT_QUALITY_BRIGHT = 16,    /* mean > max_mean                             */
+    FRT_QUALITY_CLIPPED = 32,   /* n_dark + n_bright > max_clipped             */
+    FRT_QUALITY_LOW_SCORE = 64  /* score < min_score            (records only) */
+} frt_quality_flag;
+struct frt_face_quality {
+    uint32_t sum_y, sum_y2;               /* offsets  0,  4     */
+    int32_t sum_lap;                      /*          8         */
+    uint32_t n_dark, n_bright;            /*         12, 16     */
+    int32_t size;                         /*         20         */
+    uint64_t sum_lap2;                    /*         24         */
+    float mean, luma_var, sharpness, score; /*       32, 36, 40, 44 */
+    uint32_t flags;                       /*         48: frt_quality_flag bits */
+    int32_t present;                      /*         52: 1 or 0 */
+}; /* 56 bytes; an absent slot is all zero.  The record shares its name with the host entry point below, so there is no typedef:
+    * the type is always written `struct frt_face_quality`, in C and in C++ */
+
+/* crops_dev u8 [n][112][112][3] (16-byte aligned; read for the present slots only), results_dev frt_face_result [n] (may be NULL: every
+ * slot is present, size = score = 0), options on the HOST (may be NULL, read before the call returns) -> quality_dev frt_face_quality [n]
+ * (8-byte aligned), every record written.  One launch of one workgroup per slot, asynchronous on hip_stream (the current device's; a
+ * hipStream_t as void*, NULL = default stream), no host synchronisation.  Checked before any device work: n < 0 or n > 1 048 576 is
+ * FRT_ERR_CAPACITY; then the option ranges; n == 0 does nothing; a NULL or misaligned crops_dev / quality_dev is FRT_ERR_INVALID.  A
+ * refused call writes nothing. */
+int frt_face_quality_dev(const void *crops_dev, const void *results_dev /* may be NULL */, int n, const frt_quality_options *options /* host, may be NULL */,
+                         void *quality_dev, void *hip_stream);
+/* the same behind host pointers: upload (the crops, and the records when given), one launch, download, one synchronisation.  device < 0:
+ * the current device.  The same checks, before any device work; a refused call leaves quality_out untouched. */
+int frt_face_quality(const uint8_t *crops, const frt_face_result *results /* may be NULL */, int n, const frt_quality_options *options,
+                     struct frt_face_quality *quality_out, int device);
+/* frt_enrol_select_dev with the gate: quality_dev frt_face_quality [n_frames][max_faces] (may be NULL) as frt_face_quality_dev leaves it
+ * for the call's results / crops.  A frame that would be FRT_ENROL_OK and whose SLOT 0 record has flags != 0 is FRT_ENROL_LOW_QUALITY
+ * instead: face_dev gets its record as for OK, no row is appended.  The other slots' records are not looked at.  quality_dev NULL: exactly
+ * frt_enrol_select_dev, which is unchanged.  Reads, writes and checks are frt_enrol_select_dev's. */
+int frt_enrol_select_gated_dev(const void *results_dev, const void *embeds_dev, int n_frames, int max_faces, void *status_dev, void *face_dev,
+                               void *rows_dev, void *count_dev, void *hip_stream, const void *quality_dev /* may be NULL */);
+/* frt_pipeline_run that also scores every face slot: the upload, frt_pipeline_run_dev with the crop buffer on the pipeline stream, the
+ * quality launch over [n_frames][max_faces] on that same stream, the downloads, one synchronisation.  results / embeds_out are
+ * frt_pipeline_run's, bit for bit; crops_out [n_frames * max_faces][112][112][3] (may be NULL) is frt_pipeline_submit_crops's;
+ * quality_out [n_frames * max_faces], an unused or empty-ROI slot all zero.  Serial under the pipeline's run mutex, like
+ * frt_pipeline_run_tracked; whatever a pairing mode holds or has pending is flushed behind the call's stages, so the answers are those of
+ * pairing off.  Checked before any device work: a NULL p / frames / results / quality_out and the option ranges are FRT_ERR_INVALID,
+ * n_frames < 1 or > max_frames FRT_ERR_CAPACITY; a refused call writes nothing. */
+int frt_pipeline_run_quality(frt_pipeline *p, const uint8_t *frames, int n_frames, const frt_quality_options *options, frt_face_result *results,
+                             struct frt_face_quality *quality_out, float *embeds_out /* may be NULL */, uint8_t *crops_out /* may be NULL */);
+/* frt_pipeline_enrol_images with the gate at the door: every chunk also leaves its crops on the device, the quality launch follows the
+ * chunk's stages on the pipeline stream, and the gated selection follows that: a photo with exactly one valid face whose record carries a
+ * flag is FRT_ENROL_LOW_QUALITY - faces_out[i] filled as for OK, no row added.  quality_out [n] (may be NULL) <- slot 0's record of photo i,
+ * all zero when slot 0 is absent (no face, or an empty ROI).  Everything else - arguments, checks, the ONE edit, the error behaviour - is
+ * frt_pipeline_enrol_images's; the option ranges are checked with the other arguments, before any device work.  options NULL flags
+ * nothing: status, faces, rows and the gallery are then those of frt_pipeline_enrol_images (which is unchanged and computes no quality). */
+int frt_pipeline_enrol_images_gated(frt_pipeline *p, const frt_face_image *images, int n, const int32_t *labels, const frt_quality_options *options,
+                                    int32_t *status_out, frt_face_result *faces_out, struct frt_face_quality *quality_out /* [n], may be NULL */,
+                                    float *embeds_out, int *first_row_out, int *n_enrolled_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).

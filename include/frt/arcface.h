@@ -33,6 +33,21 @@ struct CroppedFace {
     int x1, y1, x2, y2;
 };
 
+// Extension (include/frt.h "Face quality"): the record and the gate's thresholds under their C++ names.  The defaults flag nothing; there
+// are no recommended thresholds - measure on your own faces first.
+struct FaceQuality : frt_face_quality {
+    FaceQuality() : frt_face_quality() {}
+    bool passes() const { return present != 0 && flags == 0; }
+};
+struct QualityOptions : frt_quality_options {
+    QualityOptions() {
+        min_size = 0;
+        min_sharpness = min_luma_var = min_mean = min_score = 0.f;
+        max_mean = 255.f;
+        max_clipped = 112 * 112;
+    }
+};
+
 // src/arcface.cpp:3-17 (ROI = cols [y1,y2) x rows [x1,x2); INTER_CUBIC to resize_w x resize_h)
 inline void getCroppedFaces(cv::Mat frame, std::vector<struct Bbox> &outputBbox, int resize_w, int resize_h, std::vector<struct CroppedFace> &croppedFaces) {
     croppedFaces.clear();
@@ -219,25 +234,43 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     template <class Detector>
     void enrolImages(Detector &detector, const std::vector<std::string> &names, const std::vector<cv::Mat> &images, std::vector<int> &status,
                      float *embeddingsOut = nullptr) {
-        assert(names.size() == images.size());
-        if (matmul.numRows() == 0 && classNames.empty()) {
-            matmul.galleryBegin(0, m_OUTPUT_D);
-            matmul.galleryCommit();
+        enrolPhotos(detector, names, images, status, nullptr, nullptr, embeddingsOut);
+    }
+    // Extension: enrolImages with the quality gate at the door (frt_pipeline_enrol_images_gated): a photo whose one face carries a quality
+    // flag under `quality` comes back FRT_ENROL_LOW_QUALITY (5) and is not enrolled; qualityOut[i] is the face's record (all zero without a
+    // valid face).  A default-constructed QualityOptions flags nothing.
+    template <class Detector>
+    void enrolImages(Detector &detector, const std::vector<std::string> &names, const std::vector<cv::Mat> &images, std::vector<int> &status,
+                     const QualityOptions &quality, std::vector<FaceQuality> &qualityOut, float *embeddingsOut = nullptr) {
+        qualityOut.assign(images.size(), FaceQuality());
+        enrolPhotos(detector, names, images, status, &quality, qualityOut.data(), embeddingsOut);
+    }
+    // Extension: the quality records of croppedFaces - the u8 crops forward() left - in one launch (frt_face_quality).  boxes: the
+    // outputBbox forward() was given (size and score come from them, and SMALL / LOW_SCORE are evaluated); null: crops alone.
+    std::vector<FaceQuality> faceQuality(const QualityOptions &options = QualityOptions(), const std::vector<struct Bbox> *boxes = nullptr) {
+        const size_t n = croppedFaces.size(), bytes = (size_t)112 * 112 * 3;
+        std::vector<FaceQuality> out(n);
+        if (!n) return out;
+        if (boxes && boxes->size() != n) throw std::logic_error("faceQuality: one box per cropped face");
+        std::vector<unsigned char> crops(n * bytes);
+        std::vector<frt_face_result> recs(boxes ? n : 0);
+        for (size_t i = 0; i < n; ++i) {
+            const cv::Mat &f = croppedFaces[i].face;
+            if (f.rows != 112 || f.cols != 112 || f.type() != CV_8UC3) throw std::logic_error("faceQuality: a cropped face is not 112 x 112 8UC3");
+            for (int r = 0; r < 112; ++r) std::memcpy(&crops[i * bytes + (size_t)r * 112 * 3], f.data + (size_t)r * f.step, 112 * 3);
+            if (boxes) {
+                frt_face_result rec = frt_face_result();
+                rec.box.x1 = (*boxes)[i].x1;
+                rec.box.y1 = (*boxes)[i].y1;
+                rec.box.x2 = (*boxes)[i].x2;
+                rec.box.y2 = (*boxes)[i].y2;
+                rec.box.score = (*boxes)[i].score;
+                rec.valid = 1;
+                recs[i] = rec;
+            }
         }
-        photoPipe(detector);
-        const std::vector<frt_face_image> imgs = faceImages(images);
-        const bool labelled = m_labelsSet && matmul.numRows() > 0;
-        std::vector<int> labels;
-        for (size_t i = 0; labelled && i < names.size(); ++i) labels.push_back(internLabel(names[i]));
-        std::vector<int32_t> st(images.size(), 0);
-        int first = 0, enrolled = 0;
-        checkFrtStatus(frt_pipeline_enrol_images(m_photoPipe, imgs.data(), (int)imgs.size(), labelled ? labels.data() : nullptr, st.data(), nullptr,
-                                                 embeddingsOut, &first, &enrolled));
-        status.assign(st.begin(), st.end());
-        if (!labelled && enrolled > 0) m_labelsSet = false;
-        for (size_t i = 0; i < names.size(); ++i)
-            if (st[i] == FRT_ENROL_OK) classNames.push_back(names[i]);
-        classCount += enrolled;
+        checkFrtStatus(::frt_face_quality(crops.data(), boxes ? recs.data() : nullptr, (int)n, &options, out.data(), m_device));
+        return out;
     }
     // Extension: a large photo by tiles, recognised in one call (include/frt.h "Recognising a large photo by tiles"): what
     // detector.findFaceTiled(photo, options, maxOut), this object's forward on the boxes with min(x2 - x1, y2 - y1) >= minFace and matchTop1
@@ -629,6 +662,34 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
     // What a call leaves behind for the next call of the same request - per calling THREAD (include/frt/coalesce.h): the reference keeps
     // it in the object and shares the object between its server's threads.
     // labels of matchTopIdentities: className <-> label, in first-appearance order; m_labelsSet: the matcher holds the labels of classNames
+    // both enrolImages: quality null is frt_pipeline_enrol_images, else the gated call
+    template <class Detector>
+    void enrolPhotos(Detector &detector, const std::vector<std::string> &names, const std::vector<cv::Mat> &images, std::vector<int> &status,
+                     const frt_quality_options *quality, FaceQuality *qualityOut, float *embeddingsOut) {
+        assert(names.size() == images.size());
+        if (matmul.numRows() == 0 && classNames.empty()) {
+            matmul.galleryBegin(0, m_OUTPUT_D);
+            matmul.galleryCommit();
+        }
+        photoPipe(detector);
+        const std::vector<frt_face_image> imgs = faceImages(images);
+        const bool labelled = m_labelsSet && matmul.numRows() > 0;
+        std::vector<int> labels;
+        for (size_t i = 0; labelled && i < names.size(); ++i) labels.push_back(internLabel(names[i]));
+        std::vector<int32_t> st(images.size(), 0);
+        int first = 0, enrolled = 0;
+        if (quality)
+            checkFrtStatus(frt_pipeline_enrol_images_gated(m_photoPipe, imgs.data(), (int)imgs.size(), labelled ? labels.data() : nullptr, quality, st.data(),
+                                                           nullptr, qualityOut, embeddingsOut, &first, &enrolled));
+        else
+            checkFrtStatus(frt_pipeline_enrol_images(m_photoPipe, imgs.data(), (int)imgs.size(), labelled ? labels.data() : nullptr, st.data(), nullptr,
+                                                     embeddingsOut, &first, &enrolled));
+        status.assign(st.begin(), st.end());
+        if (!labelled && enrolled > 0) m_labelsSet = false;
+        for (size_t i = 0; i < names.size(); ++i)
+            if (st[i] == FRT_ENROL_OK) classNames.push_back(names[i]);
+        classCount += enrolled;
+    }
     // the pipeline of enrolImages / recognizeTiled: created at the first call, again when the detector is another one
     template <class Detector>
     void photoPipe(Detector &detector) {
