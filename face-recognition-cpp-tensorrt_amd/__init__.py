@@ -181,6 +181,10 @@ ABI = {
     "frt_tracker_destroy": (None, [_vp]),
     "frt_tracker_update_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "frt_tracker_update": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
+    "frt_tracker_set_appearance": (_i, [_vp, ctypes.c_float, ctypes.c_float]),
+    "frt_tracker_get_appearance": (_i, [_vp, _vp, _vp]),
+    "frt_tracker_update_assoc_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "frt_tracker_update_assoc": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "frt_tracker_tracks": (_i, [_vp, _i, _vp, _vp, _vp]),
     "frt_tracker_reset": (_i, [_vp, _i]),
     "frt_pipeline_run_tracked": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -1205,7 +1209,10 @@ TRACK_DTYPE = np.dtype([("track_id", "<i4"), ("slot", "<i4"), ("age", "<i4"), ("
 TRACK_STATE_DTYPE = np.dtype([("live", "<i4"), ("id", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("score", "<f4"),
                               ("born", "<i4"), ("hits", "<i4"), ("missed", "<i4"), ("n_embeds", "<i4"), ("match_idx", "<i4"),
                               ("match_sim", "<f4")])  # == frt_track_state
-assert TRACK_DTYPE.itemsize == 32 and TRACK_STATE_DTYPE.itemsize == 52
+TRACK_ASSOC_DTYPE = np.dtype([("how", "<i4"), ("gap", "<i4"), ("ovr", "<f4"), ("sim", "<f4")])  # == frt_track_assoc
+TRACK_ASSOC_ABSENT, TRACK_ASSOC_IOU, TRACK_ASSOC_APPEARANCE, TRACK_ASSOC_BIRTH, TRACK_ASSOC_UNTRACKED = range(5)  # frt_track_assoc.how
+TRACK_REID_OFF, TRACK_MIN_SIM_OFF = 2.0, -2.0
+assert TRACK_DTYPE.itemsize == 32 and TRACK_STATE_DTYPE.itemsize == 52 and TRACK_ASSOC_DTYPE.itemsize == 16
 
 
 class TrackOptions(ctypes.Structure):  # == frt_track_options
@@ -1224,17 +1231,37 @@ def _stream_ids(stream_ids, n):
 class Tracker:
     """``n_streams`` independent video streams of up to ``max_tracks`` tracks each.  An update takes the pipeline's records and embeddings
     of one frame per stream and returns, per face slot, a stable track id, the track's age / hits / confirmed flag and the identity of the
-    track's running template (when a matcher - a ``MatMul`` - with rows is given)."""
+    track's running template (when a matcher - a ``MatMul`` - with rows is given).  ``reid_threshold`` / ``iou_min_sim`` (None: off) switch
+    the appearance term on (include/frt.h "Appearance"): a lost face whose embedding is at least ``reid_threshold`` like a track's running sum
+    is re-attached to it, and an overlap match whose similarity is below ``iou_min_sim`` is refused."""
 
-    def __init__(self, n_streams, max_tracks=16, max_faces=4, dim=512, iou_threshold=0.3, max_missed=5, min_hits=3, decay=1.0, device=0):
+    def __init__(self, n_streams, max_tracks=16, max_faces=4, dim=512, iou_threshold=0.3, max_missed=5, min_hits=3, decay=1.0, device=0,
+                 reid_threshold=None, iou_min_sim=None):
         self._h = _vp()
         self.n_streams, self.max_tracks, self.max_faces, self.dim = int(n_streams), int(max_tracks), int(max_faces), int(dim)
         opt = TrackOptions(iou_threshold, max_missed, min_hits, decay)
         _check(lib.frt_tracker_create(self.n_streams, self.max_tracks, self.max_faces, self.dim, ctypes.addressof(opt), int(device), ctypes.byref(self._h)))
+        if reid_threshold is not None or iou_min_sim is not None:
+            try:
+                self.setAppearance(reid_threshold, iou_min_sim)
+            except Exception:
+                self.close()
+                raise
 
-    def update(self, results, embeds, stream_ids=None, matcher=None, want_templates=True):
+    def setAppearance(self, reid_threshold=None, iou_min_sim=None):
+        """``reid_threshold`` in (0, 1], ``iou_min_sim`` in [-1, 1]; None switches either off.  Takes effect with the next update."""
+        _check(lib.frt_tracker_set_appearance(self._h, TRACK_REID_OFF if reid_threshold is None else float(reid_threshold),
+                                              TRACK_MIN_SIM_OFF if iou_min_sim is None else float(iou_min_sim)))
+
+    def getAppearance(self):
+        """-> (reid_threshold, iou_min_sim), None where off"""
+        r, m = ctypes.c_float(), ctypes.c_float()
+        _check(lib.frt_tracker_get_appearance(self._h, ctypes.addressof(r), ctypes.addressof(m)))
+        return (None if r.value == TRACK_REID_OFF else r.value, None if m.value == TRACK_MIN_SIM_OFF else m.value)
+
+    def update(self, results, embeds, stream_ids=None, matcher=None, want_templates=True, want_assoc=False):
         """results RESULT_DTYPE [n * max_faces], embeds float32 [n * max_faces, dim] (host) -> (TRACK_DTYPE [n, max_faces], templates
-        float32 [n, max_faces, dim] or None)."""
+        float32 [n, max_faces, dim] or None[, with ``want_assoc``: TRACK_ASSOC_DTYPE [n, max_faces], how each detection was associated])."""
         results = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
         if results.size == 0 or results.size % self.max_faces:
             raise ValueError("results must hold max_faces records per frame")
@@ -1245,14 +1272,21 @@ class Tracker:
         ids = _stream_ids(stream_ids, n)
         trk = np.zeros((n, self.max_faces), TRACK_DTYPE)
         tpl = np.zeros((n, self.max_faces, self.dim), np.float32) if want_templates else None
+        if want_assoc:
+            assoc = np.zeros((n, self.max_faces), TRACK_ASSOC_DTYPE)
+            _check(lib.frt_tracker_update_assoc(self._h, matcher._h if matcher is not None else None, _ptr(results), _ptr(embeds), n, _ptr(ids), _ptr(trk),
+                                                _ptr(tpl), _ptr(assoc)))
+            return trk, tpl, assoc
         _check(lib.frt_tracker_update(self._h, matcher._h if matcher is not None else None, _ptr(results), _ptr(embeds), n, _ptr(ids), _ptr(trk), _ptr(tpl)))
         return trk, tpl
 
-    def updateDev(self, results_ptr, embeds_ptr, n_frames, tracks_ptr, templates_ptr=None, stream_ids=None, matcher=None, hip_stream=None):
-        """Asynchronous on ``hip_stream``; the pointers are raw device addresses (``frt_pipeline_run_dev``'s results_dev / embeds_dev)."""
+    def updateDev(self, results_ptr, embeds_ptr, n_frames, tracks_ptr, templates_ptr=None, stream_ids=None, matcher=None, hip_stream=None, assoc_ptr=None):
+        """Asynchronous on ``hip_stream``; the pointers are raw device addresses (``frt_pipeline_run_dev``'s results_dev / embeds_dev);
+        ``assoc_ptr``: room for n_frames * max_faces TRACK_ASSOC_DTYPE records, or None."""
         ids = _stream_ids(stream_ids, int(n_frames))
-        _check(lib.frt_tracker_update_dev(self._h, matcher._h if matcher is not None else None, _vp(results_ptr), _vp(embeds_ptr), int(n_frames), _ptr(ids),
-                                          _vp(tracks_ptr), _vp(templates_ptr) if templates_ptr else None, _vp(hip_stream) if hip_stream else None))
+        _check(lib.frt_tracker_update_assoc_dev(self._h, matcher._h if matcher is not None else None, _vp(results_ptr), _vp(embeds_ptr), int(n_frames),
+                                                _ptr(ids), _vp(tracks_ptr), _vp(templates_ptr) if templates_ptr else None,
+                                                _vp(assoc_ptr) if assoc_ptr else None, _vp(hip_stream) if hip_stream else None))
 
     def tracks(self, stream, want_sums=False):
         """-> (slots TRACK_STATE_DTYPE [max_tracks], every slot, live or not; counters dict(next_id, tick, dropped)[; sums [max_tracks, dim]])"""

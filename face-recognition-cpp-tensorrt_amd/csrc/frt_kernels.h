@@ -587,9 +587,18 @@ struct TrackArgs {
     const float *embeds;             // [n_frames][max_faces][dim], 16-byte aligned
     frt_track_result *tracks;        // [n_frames][max_faces]
     float *templates;                // [n_frames][max_faces][dim], 16-byte aligned, or null
+    // ---- appearance (include/frt.h "Appearance"): read by the similarity kernel and by the update kernel's APPEARANCE instantiation only
+    float reid_threshold, iou_min_sim;  // 2.0 / -2.0: off
+    float *sim;                         // scratch S [n_frames][max_faces][max_tracks]; an entry is written iff its bit below is set
+    unsigned long long *sim_defined;    // scratch [n_frames][max_faces]: bit t set iff S[f][d][t] is DEFINED
+    frt_track_assoc *assoc;             // [n_frames][max_faces], or null
 };
-// steps 1 - 6 and 8 of an update, one workgroup per frame; the records leave with match_idx -1 / match_sim 0
-void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s);
+// S and its defined bits of every detection x slot pair of the call, from the sums as they are BEFORE the update: one workgroup per detection
+void launch_track_similarity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s);
+// steps 1 - 6 and 8 of an update, one workgroup per frame; the records leave with match_idx -1 / match_sim 0.  appearance: the instantiation
+// that reads a.sim / a.sim_defined (steps 2a, 2b; launch_track_similarity ran before it on s) and writes a.assoc; without it the launch is
+// the one of a tracker that has no appearance settings
+void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, bool appearance, hipStream_t s);
 // step 7 behind the top-1 search of the template rows: idx / sim [n_frames * max_faces] -> the tracked records with n_embeds > 0 and their slots
 void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, const int32_t *idx, const float *sim, hipStream_t s);
 // frees the slots of `stream` (-1: of every one of n_streams) and zeroes tick / dropped; next_id stays

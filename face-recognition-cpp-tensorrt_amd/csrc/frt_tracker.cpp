@@ -1,5 +1,6 @@
 // Face tracker, host side (include/frt.h "Face tracker"): the object, the argument checks that run before any device work, the three
-// launches of an update, the host forms and frt_pipeline_run_tracked.  The kernels are in kernels_track.hip.
+// launches of an update (four with appearance on: the similarity kernel goes first), the appearance settings, the host forms and
+// frt_pipeline_run_tracked.  The kernels are in kernels_track.hip.
 #include "frt_pipeline.hpp"
 #include "frt_tracker.hpp"
 
@@ -26,7 +27,7 @@ void tracker_check_matcher(const frt_tracker *t, frt_matcher *m) {
 }
 
 void tracker_update_locked(frt_tracker *t, frt_matcher *m, const frt_face_result *results_dev, const float *embeds_dev, int n_frames,
-                           const TrackStreamIds &ids, frt_track_result *tracks_dev, float *templates_dev, hipStream_t s) {
+                           const TrackStreamIds &ids, frt_track_result *tracks_dev, float *templates_dev, frt_track_assoc *assoc_dev, hipStream_t s) {
     const int F = n_frames * t->max_faces;
     std::unique_lock<std::mutex> lm;
     if (m) {
@@ -42,14 +43,28 @@ void tracker_update_locked(frt_tracker *t, frt_matcher *m, const frt_face_result
         t->q_idx.reserve(F);
         t->q_sim.reserve(F);
     }
+    // the association records name S of the matched pair, so a call that asks for them takes the appearance launches whatever the settings
+    const bool appearance = t->appearance_on() || assoc_dev;
+    if (appearance) {
+        t->sim.reserve((size_t)F * t->max_tracks);
+        t->sim_defined.reserve(F);
+    }
     TrackArgs a = t->args();
     a.results = results_dev;
     a.embeds = embeds_dev;
     a.tracks = tracks_dev;
     a.templates = templates_dev;
+    a.sim = t->sim.get();
+    a.sim_defined = t->sim_defined.get();
+    a.assoc = assoc_dev;
+    if (appearance) {
+        ProfScope ps(2, "track_similarity", (double)F * t->max_tracks, s);
+        launch_track_similarity(a, ids, n_frames, s);
+        HIPCHK(hipGetLastError());
+    }
     {
         ProfScope ps(2, "track_update", (double)F, s);
-        launch_track_update(a, ids, n_frames, s);
+        launch_track_update(a, ids, n_frames, appearance, s);
         HIPCHK(hipGetLastError());
     }
     if (identity) {
@@ -74,6 +89,14 @@ void check_options(const frt_track_options &o) {
     if (o.max_missed < 0) raise(FRT_ERR_INVALID, "tracker: max_missed < 0");
     if (o.min_hits < 1) raise(FRT_ERR_INVALID, "tracker: min_hits < 1");
     if (!(o.decay > 0.f && o.decay <= 1.f)) raise(FRT_ERR_INVALID, "tracker: decay outside (0, 1]");
+}
+
+// (written so that a NaN fails both)
+void check_appearance(float reid_threshold, float iou_min_sim) {
+    if (!((reid_threshold > 0.f && reid_threshold <= 1.f) || reid_threshold == FRT_TRACK_REID_OFF))
+        raise(FRT_ERR_INVALID, "tracker: reid_threshold outside (0, 1] and not the off value 2.0");
+    if (!((iou_min_sim >= -1.f && iou_min_sim <= 1.f) || iou_min_sim == FRT_TRACK_MIN_SIM_OFF))
+        raise(FRT_ERR_INVALID, "tracker: iou_min_sim outside [-1, 1] and not the off value -2.0");
 }
 
 // The stream, the events and the zeroed state, on the first call that passed its checks.  All of it or nothing: a failure leaves the
@@ -150,8 +173,32 @@ void frt_tracker_destroy(frt_tracker *t) {
     if (t) destroy(t);
 }
 
+int frt_tracker_set_appearance(frt_tracker *t, float reid_threshold, float iou_min_sim) {
+    return guarded([&] {
+        if (!t) raise(FRT_ERR_INVALID, "tracker appearance: null argument");
+        check_appearance(reid_threshold, iou_min_sim);
+        std::lock_guard<std::mutex> lk(t->mu);
+        t->reid_threshold = reid_threshold;
+        t->iou_min_sim = iou_min_sim;
+    });
+}
+
+int frt_tracker_get_appearance(frt_tracker *t, float *reid_threshold_out, float *iou_min_sim_out) {
+    return guarded([&] {
+        if (!t || !reid_threshold_out || !iou_min_sim_out) raise(FRT_ERR_INVALID, "tracker appearance: null argument");
+        std::lock_guard<std::mutex> lk(t->mu);
+        *reid_threshold_out = t->reid_threshold;
+        *iou_min_sim_out = t->iou_min_sim;
+    });
+}
+
 int frt_tracker_update_dev(frt_tracker *t, frt_matcher *m, const void *results_dev, const void *embeds_dev, int n_frames, const int32_t *stream_ids,
                            void *tracks_dev, void *templates_dev, void *hip_stream) {
+    return frt_tracker_update_assoc_dev(t, m, results_dev, embeds_dev, n_frames, stream_ids, tracks_dev, templates_dev, nullptr, hip_stream);
+}
+
+int frt_tracker_update_assoc_dev(frt_tracker *t, frt_matcher *m, const void *results_dev, const void *embeds_dev, int n_frames,
+                                 const int32_t *stream_ids, void *tracks_dev, void *templates_dev, void *assoc_dev, void *hip_stream) {
     return guarded([&] {
         if (!t || !results_dev || !embeds_dev || !tracks_dev) raise(FRT_ERR_INVALID, "tracker update: null argument");
         if (((uintptr_t)embeds_dev | (uintptr_t)templates_dev) & 15) raise(FRT_ERR_INVALID, "tracker update: embeds_dev and templates_dev must be 16-byte aligned");
@@ -161,12 +208,17 @@ int frt_tracker_update_dev(frt_tracker *t, frt_matcher *m, const void *results_d
         ensure_state(t);
         tracker_update_locked(t, m, reinterpret_cast<const frt_face_result *>(results_dev), reinterpret_cast<const float *>(embeds_dev), n_frames, ids,
                               reinterpret_cast<frt_track_result *>(tracks_dev), reinterpret_cast<float *>(templates_dev),
-                              reinterpret_cast<hipStream_t>(hip_stream));
+                              reinterpret_cast<frt_track_assoc *>(assoc_dev), reinterpret_cast<hipStream_t>(hip_stream));
     });
 }
 
 int frt_tracker_update(frt_tracker *t, frt_matcher *m, const frt_face_result *results, const float *embeds, int n_frames, const int32_t *stream_ids,
                        frt_track_result *tracks_out, float *templates_out) {
+    return frt_tracker_update_assoc(t, m, results, embeds, n_frames, stream_ids, tracks_out, templates_out, nullptr);
+}
+
+int frt_tracker_update_assoc(frt_tracker *t, frt_matcher *m, const frt_face_result *results, const float *embeds, int n_frames,
+                             const int32_t *stream_ids, frt_track_result *tracks_out, float *templates_out, frt_track_assoc *assoc_out) {
     return guarded([&] {
         if (!t || !results || !embeds || !tracks_out) raise(FRT_ERR_INVALID, "tracker update: null argument");
         std::lock_guard<std::mutex> lk(t->mu);
@@ -178,10 +230,13 @@ int frt_tracker_update(frt_tracker *t, frt_matcher *m, const frt_face_result *re
         join_updates(t);
         HIPCHK(hipStreamSynchronize(s));  // the staging is rewritten below
         t->reserve_staging(n_frames, 0);
+        if (assoc_out) t->d_assoc.reserve(F);
         HIPCHK(hipMemcpyAsync(t->d_results.get(), results, F * sizeof(frt_face_result), hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(t->d_embeds.get(), embeds, F * t->dim * sizeof(float), hipMemcpyHostToDevice, s));
-        tracker_update_locked(t, m, t->d_results.get(), t->d_embeds.get(), n_frames, ids, t->d_tracks.get(), templates_out ? t->d_templates.get() : nullptr, s);
+        tracker_update_locked(t, m, t->d_results.get(), t->d_embeds.get(), n_frames, ids, t->d_tracks.get(), templates_out ? t->d_templates.get() : nullptr,
+                              assoc_out ? t->d_assoc.get() : nullptr, s);
         HIPCHK(hipMemcpyAsync(tracks_out, t->d_tracks.get(), F * sizeof(frt_track_result), hipMemcpyDeviceToHost, s));
+        if (assoc_out) HIPCHK(hipMemcpyAsync(assoc_out, t->d_assoc.get(), F * sizeof(frt_track_assoc), hipMemcpyDeviceToHost, s));
         if (templates_out) HIPCHK(hipMemcpyAsync(templates_out, t->d_templates.get(), F * t->dim * sizeof(float), hipMemcpyDeviceToHost, s));
         sync_stream_spinning(s);
     });
@@ -248,7 +303,7 @@ int frt_pipeline_run_tracked(frt_pipeline *p, frt_tracker *t, const uint8_t *fra
             p->run_dev(r);
             p->flush();  // (a pairing mode that holds run_dev calls: the join must be on the stream before the tracker reads the results)
             tracker_update_locked(t, p->mat, t->d_results.get(), t->d_embeds.get(), n_frames, ids, t->d_tracks.get(),
-                                  templates_out ? t->d_templates.get() : nullptr, s);
+                                  templates_out ? t->d_templates.get() : nullptr, nullptr, s);
             HIPCHK(hipMemcpyAsync(results, t->d_results.get(), F * sizeof(frt_face_result), hipMemcpyDeviceToHost, s));
             if (embeds_out) HIPCHK(hipMemcpyAsync(embeds_out, t->d_embeds.get(), F * 512 * sizeof(float), hipMemcpyDeviceToHost, s));
             HIPCHK(hipMemcpyAsync(tracks_out, t->d_tracks.get(), F * sizeof(frt_track_result), hipMemcpyDeviceToHost, s));

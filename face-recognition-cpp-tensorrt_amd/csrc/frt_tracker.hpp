@@ -8,6 +8,7 @@ struct frt_tracker {
     int device = 0;
     int n_streams = 0, max_tracks = 0, max_faces = 0, dim = 0;
     frt_track_options opt{};
+    float reid_threshold = FRT_TRACK_REID_OFF, iou_min_sim = FRT_TRACK_MIN_SIM_OFF;  // frt_tracker_set_appearance
     std::mutex mu;
     hipStream_t stream = nullptr;   // the host forms, frt_tracker_tracks and frt_tracker_reset
     hipEvent_t ev_last = nullptr;   // end of the last update queued (on whichever stream): what `stream` waits for before it reads the state
@@ -21,11 +22,15 @@ struct frt_tracker {
     // ---- scratch of an update with a matcher: the template rows when the caller takes none, and the search's answers
     DevBuf<float> q_templates, q_sim;
     DevBuf<int32_t> q_idx;
+    // ---- scratch of an update with appearance on (or one that reports the association): S and its defined bits, for the most frames seen
+    DevBuf<float> sim;                       // [n_frames][max_faces][max_tracks]
+    DevBuf<unsigned long long> sim_defined;  // [n_frames][max_faces]
     // ---- staging of the host forms
     DevBuf<uint8_t> d_frames;
     DevBuf<frt_face_result> d_results;
     DevBuf<float> d_embeds, d_templates;
     DevBuf<frt_track_result> d_tracks;
+    DevBuf<frt_track_assoc> d_assoc;  // (only once a host form has asked for it)
 
     TrackArgs args() const {
         TrackArgs a{};
@@ -39,8 +44,11 @@ struct frt_tracker {
         a.decay = opt.decay;
         a.max_missed = opt.max_missed;
         a.min_hits = opt.min_hits;
+        a.reid_threshold = reid_threshold;
+        a.iou_min_sim = iou_min_sim;
         return a;
     }
+    bool appearance_on() const { return reid_threshold != FRT_TRACK_REID_OFF || iou_min_sim != FRT_TRACK_MIN_SIM_OFF; }
     // room for the host forms' n_frames frames (frame_bytes: 0 without frames)
     void reserve_staging(int n_frames, size_t frame_bytes) {
         const size_t F = (size_t)n_frames * max_faces;
@@ -57,7 +65,7 @@ struct frt_tracker {
 TrackStreamIds tracker_check_ids(const frt_tracker *t, int n_frames, const int32_t *stream_ids);
 //   the matcher: on the tracker's device, and dim columns when it has rows.  Takes m->mu for the look; m may be null
 void tracker_check_matcher(const frt_tracker *t, frt_matcher *m);
-// One update, queued on s, with t->mu held and every argument checked: the update kernel, then - m with rows - the top-1 search of the
-// template rows and the identity kernel.  Takes m->mu for the search.
+// One update, queued on s, with t->mu held and every argument checked: - appearance on, or assoc_dev given - the similarity kernel, the
+// update kernel, then - m with rows - the top-1 search of the template rows and the identity kernel.  Takes m->mu for the search.
 void tracker_update_locked(frt_tracker *t, frt_matcher *m, const frt_face_result *results_dev, const float *embeds_dev, int n_frames,
-                           const TrackStreamIds &ids, frt_track_result *tracks_dev, float *templates_dev, hipStream_t s);
+                           const TrackStreamIds &ids, frt_track_result *tracks_dev, float *templates_dev, frt_track_assoc *assoc_dev, hipStream_t s);

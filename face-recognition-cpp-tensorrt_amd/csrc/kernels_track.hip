@@ -13,6 +13,19 @@
 // written with the rounding intrinsics as well, so neither the sums nor the overlaps can turn into an fma.
 // Bounds: a frame index is blockIdx.x < n_frames, a stream id was checked on the host against n_streams, a slot index is < max_tracks <= 64,
 // a column is tested against dim before every access.
+//
+// Appearance (include/frt.h "Appearance"; tests/track_reid_ref.py), only for a tracker that has it on:
+//   - track_similarity_kernel, one workgroup of four waves per detection, runs BEFORE the update and so reads the sums at entry.  Every wave
+//     holds the detection's row in registers, 16 bytes per lane and 256-column group, and takes the slots wave, wave + 4, ...: a pair is
+//     one wave.  dot2r is a chain of __fadd_rn(acc, __fmul_rn(x, y)) per lane - two roundings, the order of the header - and the xor
+//     butterfly; S = dot2r(e, sum) / sqrtf(dot2r(sum, sum)), both correctly rounded in this build (the toolchain's __fsqrt_rn is the native
+//     square root, which is not).  A pair that cannot be DEFINED is skipped before its sum is read; lane 0 writes S[f][d][t], and the
+//     workgroup one 64-bit mask of the defined slots per detection (four words of LDS carry the waves' parts to thread 0).
+//   - track_update_kernel<true>: lane t of wave 0 reads S[d][t] and its bit per detection; 2a drops the vetoed candidates, 2b is a second
+//     walk over the detections under the same reduction, keyed by (S bits, 63 - lane) - S >= reid_threshold > 0 keeps the bits monotone.
+//     Lane d collects how its detection was associated.  track_update_kernel<false> is the kernel of a tracker without appearance.
+//   Bounds: the grid of the similarity kernel is (max_faces, n_frames); its slot index is tested against max_tracks, its columns against dim;
+//   the update kernel reads S[d][lane] only where the defined bit of lane is set, and bits are set for slots < max_tracks only.
 #include "frt_kernels.h"
 
 namespace {
@@ -51,6 +64,66 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     return v;
 }
 
+// columns k .. k + 3 of a row of dim floats, zeros past dim: the load is of column 0 there and a select drops it, so no lane branches
+__device__ __forceinline__ floatx4 row_at(const float *row, int k, int dim) {
+    const floatx4 v = *reinterpret_cast<const floatx4 *>(row + (k < dim ? k : 0));
+    return k < dim ? v : floatx4{0.f, 0.f, 0.f, 0.f};
+}
+
+// grid (max_faces, n_frames)
+__global__ __launch_bounds__(64 * WAVES) void track_similarity_kernel(TrackArgs a, TrackStreamIds ids) {
+    __shared__ unsigned long long s_defined[WAVES];
+    const int d = blockIdx.x, f = blockIdx.y, stream = ids.id[f];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int T = a.max_tracks, MF = a.max_faces, D = a.dim;
+    const frt_face_result *r = a.results + (long)f * MF + d;
+    unsigned long long defined = 0;  // (wave-uniform) the slots this wave found DEFINED
+    if (r->box.score > 0.f && r->valid != 0) {
+        const float *e = a.embeds + ((long)f * MF + d) * D;
+        const frt_track_state *slots = a.slots + (long)stream * T;
+        const float *sums = a.sums + (long)stream * T * D;
+        float *S = a.sim + ((long)f * MF + d) * T;
+        floatx4 x[GROUPS];
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            const int k = g * 256 + lane * 4;
+            x[g] = row_at(e, k, D);
+        }
+        for (int t = wave; t < T; t += WAVES) {
+            if (slots[t].live == 0 || slots[t].n_embeds <= 0) continue;  // (wave-uniform) not DEFINED: the sum is not read
+            const float *sum = sums + (long)t * D;
+            float n2 = 0.f, dp = 0.f;
+#pragma unroll
+            for (int g = 0; g < GROUPS; ++g) {
+                if (g * 256 >= D) break;  // (wave-uniform)
+                const int k = g * 256 + lane * 4;
+                const floatx4 y = row_at(sum, k, D);
+                // a column past dim adds fl(0 * 0) = +0, which leaves acc as it is: acc is never -0 (it starts at +0, and a sum that
+                // cancels rounds to +0), so the lanes of a partial group need no branch of their own
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    n2 = __fadd_rn(n2, __fmul_rn(y[j], y[j]));
+                    dp = __fadd_rn(dp, __fmul_rn(x[g][j], y[j]));
+                }
+            }
+            n2 = wave_sum(n2);
+            dp = wave_sum(dp);
+            if (!(n2 > 0.f)) continue;
+            if (lane == 0) S[t] = dp / sqrtf(n2);
+            defined |= 1ull << t;
+        }
+    }
+    if (lane == 0) s_defined[wave] = defined;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long all = 0;
+        for (int w = 0; w < WAVES; ++w) all |= s_defined[w];
+        a.sim_defined[(long)f * MF + d] = all;
+    }
+}
+
+template <bool APPEARANCE>
 __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, TrackStreamIds ids) {
     __shared__ int s_slot[FRT_TRACK_MAX_SLOTS];  // detection -> slot; -1: untracked or absent
     __shared__ unsigned long long s_expired;     // slots freed by this update (their sums are zeroed before a birth's embedding lands)
@@ -73,20 +146,36 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
         bool taken = false;
         int my_slot = -1;        // lane d: the slot of detection d
         bool my_present = false;
+        // APPEARANCE: lane d keeps how detection d was associated; S and its defined bits of this frame, [max_faces][max_tracks] / [max_faces]
+        frt_track_assoc my_assoc = {};
+        const bool veto_on = APPEARANCE && a.iou_min_sim >= -1.f, reid_on = APPEARANCE && a.reid_threshold <= 1.f;
+        const float *S = APPEARANCE ? a.sim + (long)f * MF * T : nullptr;
+        const unsigned long long *S_defined = APPEARANCE ? a.sim_defined + (long)f * MF : nullptr;
 
-        // ---- steps 1, 2: association, detections in slot order
+        // ---- steps 1, 2 (2a): association by overlap, detections in slot order
         for (int d = 0; d < MF; ++d) {
             const frt_face_result r = res[d];
             if (!(r.box.score > 0.f)) continue;  // (wave-uniform)
             if (lane == d) my_present = true;
+            bool defined = false;  // lane t: S[d][t] is DEFINED, and s is its value
+            float s = 0.f;
+            if constexpr (APPEARANCE) {
+                defined = (S_defined[d] >> lane) & 1;
+                if (defined) s = S[(long)d * T + lane];
+            }
             unsigned long long key = 0;  // (overlap bits, 63 - lane); an overlap that reaches the threshold is > 0, so 0 is "no candidate"
-            if (live_entry && !taken) {
+            if (live_entry && !taken && !(veto_on && defined && s < a.iou_min_sim)) {
                 const float ovr = iou(r.box, st.box);
                 if (ovr >= a.iou_threshold) key = ((unsigned long long)__float_as_uint(ovr) << 32) | (unsigned)(63 - lane);
             }
             key = wave_max_u64(key);
             if (key == 0) continue;
             const int win = 63 - (int)(key & 63);
+            if constexpr (APPEARANCE) {
+                const int gap = __shfl(st.missed, win);
+                const float sim = __shfl(s, win);
+                if (lane == d) my_assoc = frt_track_assoc{1, gap, __uint_as_float((unsigned)(key >> 32)), sim};
+            }
             if (lane == win) {
                 st.box = r.box;
                 st.hits += 1;
@@ -94,6 +183,35 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
                 taken = true;
             }
             if (lane == d) my_slot = win;
+        }
+        // ---- step 2b: what 2a left unmatched, by appearance, detections in slot order
+        if constexpr (APPEARANCE) {
+            for (int d = 0; reid_on && d < MF; ++d) {
+                const int present = __shfl((int)my_present, d), slot_d = __shfl(my_slot, d);
+                if (!present || slot_d >= 0) continue;  // (wave-uniform)
+                const unsigned long long defined_d = S_defined[d];  // (0 for a detection with valid == 0)
+                if (defined_d == 0) continue;
+                const frt_face_result r = res[d];
+                const bool defined = (defined_d >> lane) & 1;
+                const float s = defined ? S[(long)d * T + lane] : 0.f;
+                unsigned long long key = 0;  // (S bits, 63 - lane): S >= reid_threshold > 0, so the bits order as the values do
+                if (live_entry && !taken && defined && s >= a.reid_threshold) key = ((unsigned long long)__float_as_uint(s) << 32) | (unsigned)(63 - lane);
+                key = wave_max_u64(key);
+                if (key == 0) continue;
+                const int win = 63 - (int)(key & 63);
+                const int gap = __shfl(st.missed, win);
+                const float ovr = __shfl(iou(r.box, st.box), win);
+                if (lane == d) {
+                    my_assoc = frt_track_assoc{2, gap, ovr, __uint_as_float((unsigned)(key >> 32))};
+                    my_slot = win;
+                }
+                if (lane == win) {
+                    st.box = r.box;
+                    st.hits += 1;
+                    st.missed = 0;
+                    taken = true;
+                }
+            }
         }
         // ---- step 3: expiry
         bool expired = false;
@@ -112,6 +230,7 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
             const unsigned long long free_mask = __ballot(mine && st.live == 0);
             if (free_mask == 0) {
                 ++dropped;
+                if (lane == d) my_assoc.how = 4;
                 continue;
             }
             const int b = __ffsll((long long)free_mask) - 1;
@@ -127,7 +246,10 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
                 st.match_sim = 0.f;
             }
             ++next_id;
-            if (lane == d) my_slot = b;
+            if (lane == d) {
+                my_slot = b;
+                my_assoc.how = 3;
+            }
         }
         // ---- step 5, the count: a track is matched by at most one detection
         for (int d = 0; d < MF; ++d) {
@@ -151,6 +273,8 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
                 }
                 a.tracks[(long)f * MF + lane] = o;
                 s_slot[lane] = my_slot;
+                if constexpr (APPEARANCE)
+                    if (a.assoc) a.assoc[(long)f * MF + lane] = my_assoc;
             }
         }
         if (mine) slots[lane] = st;
@@ -237,9 +361,17 @@ __global__ __launch_bounds__(64) void track_reset_kernel(TrackArgs a, int first_
 
 }  // namespace
 
-void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s) {
+void launch_track_similarity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s) {
     if (n_frames <= 0) return;
-    hipLaunchKernelGGL(track_update_kernel, dim3((unsigned)n_frames), dim3(64 * WAVES), 0, s, a, ids);
+    hipLaunchKernelGGL(track_similarity_kernel, dim3((unsigned)a.max_faces, (unsigned)n_frames), dim3(64 * WAVES), 0, s, a, ids);
+}
+
+void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, bool appearance, hipStream_t s) {
+    if (n_frames <= 0) return;
+    if (appearance)
+        hipLaunchKernelGGL(track_update_kernel<true>, dim3((unsigned)n_frames), dim3(64 * WAVES), 0, s, a, ids);
+    else
+        hipLaunchKernelGGL(track_update_kernel<false>, dim3((unsigned)n_frames), dim3(64 * WAVES), 0, s, a, ids);
 }
 
 void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, const int32_t *idx, const float *sim, hipStream_t s) {

@@ -847,6 +847,34 @@ int frt_pipeline_run_photo_tiled(frt_pipeline *p, const uint8_t *bgr, int rows, 
  *   Every argument check runs before any device work - NULL pointers and ranges, then duplicate or out-of-range stream ids, then a matcher
  *     whose num_col != dim (FRT_ERR_INVALID) -; a refused call writes nothing and changes no state.  embeds_dev / templates_dev must be
  *     16-byte aligned.  The tracker has one mutex; updates queued on different HIP streams are the caller's to order.
+ *
+ *   Appearance (frt_tracker_set_appearance; off by default, and with it off an update is launch for launch and byte for byte the one
+ *   described above).  Overlap alone loses a face that stays away longer than max_missed or jumps further than iou_threshold allows, and
+ *   swaps two faces that cross.  With appearance on, the detection's embedding is compared with the track's running sum, in the same call
+ *   (tests/track_reid_ref.py restates this block in numpy, to the bit).
+ *     The reduction dot2r(x, y), with G = ceil(dim / 256): lane l (0 .. 63) starts at acc = 0; for g = 0 .. G-1 and j = 0 .. 3, with
+ *       k = 256 g + 4 l + j < dim: acc = fl(acc + fl(x[k] * y[k])) - two roundings, never an fma -; then six butterfly steps, off = 32, 16,
+ *       8, 4, 2, 1: v_l = fl(v_l + v_(l xor off)).  The result is lane 0's value (all lanes hold the same bits).  It is NOT step 6's fmaf
+ *       chain: numpy float32 reproduces it bit for bit (pad to [G][64][4] with zeros, chain, then the six v + v[perm] steps).
+ *     The similarity of detection d of a frame and slot t of its stream, sum_t being the track's sum AT ENTRY (before this update's step 5):
+ *       n2 = dot2r(sum_t, sum_t), S[d][t] = fl(dot2r(e_d, sum_t) / fl(sqrt(n2))), division and square root correctly rounded.
+ *       S[d][t] is DEFINED iff d is present with valid != 0, t was live at entry with n_embeds > 0, and n2 > 0.  The embedding is taken as
+ *       the recogniser leaves it (unit norm) and is not re-normalised.  A NaN S never vetoes and never matches: every comparison below
+ *       fails for it.
+ *     Two settings per tracker: reid_threshold in (0, 1] or the off value 2.0; iou_min_sim in [-1, 1] or the off value -2.0.  Any other
+ *       value, a NaN included, is FRT_ERR_INVALID.  Both default to off.
+ *     Step 2 becomes 2a and 2b.
+ *       2a is step 2 with one more exclusion: when iou_min_sim is on, track t is no candidate for detection d if S[d][t] is DEFINED and
+ *          S[d][t] < iou_min_sim.
+ *       2b runs only when reid_threshold is on.  It walks every present detection with valid != 0 that 2a left unmatched, in slot order;
+ *          candidates are the tracks live at entry, not yet taken (by 2a or by an earlier detection of 2b), with S[d][t] DEFINED and
+ *          S[d][t] >= reid_threshold; the winner is the largest S, the lowest slot among equals.  A match does what a 2a match does:
+ *          track.box = det.box, hits += 1, missed = 0.
+ *       Steps 3 to 8 are unchanged; expiry sees the tracks 2b took as taken.
+ *     How each detection was associated: frt_track_assoc per face slot, an optional output of the frt_tracker_update_assoc* entry points
+ *       (with both settings off they report how / gap / ovr / sim of the update above).
+ *     Nobody has measured S on real faces with this library: no threshold is recommended here, and the synthetic weights of the tests say
+ *       nothing about where genuine and impostor similarities lie.  frt_matcher_separation over an enrolled gallery is the place to start.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct frt_tracker frt_tracker;
 typedef struct frt_track_options {
@@ -865,6 +893,19 @@ typedef struct frt_track_state {
     int32_t born, hits, missed, n_embeds, match_idx;
     float match_sim;
 } frt_track_state; /* 52 bytes: one slot as frt_tracker_tracks returns it; a free slot is all zero */
+#define FRT_TRACK_ASSOC_ABSENT 0     /* the detection slot is not present */
+#define FRT_TRACK_ASSOC_IOU 1        /* matched by overlap (step 2a) */
+#define FRT_TRACK_ASSOC_APPEARANCE 2 /* matched by appearance (step 2b) */
+#define FRT_TRACK_ASSOC_BIRTH 3      /* a new track (step 4) */
+#define FRT_TRACK_ASSOC_UNTRACKED 4  /* no free slot (step 4) */
+typedef struct frt_track_assoc {
+    int32_t how; /* FRT_TRACK_ASSOC_* */
+    int32_t gap; /* how 1, 2: the matched track's `missed` at entry; else 0 */
+    float ovr;   /* how 1, 2: the IoU of the detection with the matched track's box at entry; else 0 */
+    float sim;   /* how 1, 2: S[d][t] of the matched pair where DEFINED; else 0 */
+} frt_track_assoc; /* 16 bytes */
+#define FRT_TRACK_REID_OFF 2.0f     /* reid_threshold: step 2b does not run */
+#define FRT_TRACK_MIN_SIM_OFF -2.0f /* iou_min_sim: step 2a excludes nothing */
 
 /* options NULL: the defaults; a value outside its range is FRT_ERR_INVALID.  Creation itself does no device work: the state is allocated
  * and zeroed by the first call that passes its checks (a device that does not exist is FRT_ERR_DEVICE there). */
@@ -878,6 +919,19 @@ int frt_tracker_update_dev(frt_tracker *t, frt_matcher *m, const void *results_d
 /* the same behind host pointers: upload, update, download, one synchronisation */
 int frt_tracker_update(frt_tracker *t, frt_matcher *m, const frt_face_result *results, const float *embeds, int n_frames,
                        const int32_t *stream_ids, frt_track_result *tracks_out, float *templates_out /* may be NULL */);
+/* "Appearance" above.  Takes effect with the next update (the settings travel with its launches); under the tracker's mutex, no device
+ * work.  reid_threshold in (0, 1] or FRT_TRACK_REID_OFF, iou_min_sim in [-1, 1] or FRT_TRACK_MIN_SIM_OFF: anything else, a NaN included, is
+ * FRT_ERR_INVALID and changes nothing.  frt_tracker_update_dev, frt_tracker_update and frt_pipeline_run_tracked honour the settings. */
+int frt_tracker_set_appearance(frt_tracker *t, float reid_threshold, float iou_min_sim);
+int frt_tracker_get_appearance(frt_tracker *t, float *reid_threshold_out, float *iou_min_sim_out);
+/* frt_tracker_update_dev / frt_tracker_update with how each detection was associated: assoc_dev / assoc_out frt_track_assoc
+ * [n_frames][max_faces] (may be NULL: the call is then the plain one).  The same checks, all before any device work. */
+int frt_tracker_update_assoc_dev(frt_tracker *t, frt_matcher *m, const void *results_dev, const void *embeds_dev, int n_frames,
+                                 const int32_t *stream_ids /* host, may be NULL */, void *tracks_dev, void *templates_dev, void *assoc_dev,
+                                 void *hip_stream);
+int frt_tracker_update_assoc(frt_tracker *t, frt_matcher *m, const frt_face_result *results, const float *embeds, int n_frames,
+                             const int32_t *stream_ids, frt_track_result *tracks_out, float *templates_out /* may be NULL */,
+                             frt_track_assoc *assoc_out /* may be NULL */);
 /* one stream's state, after everything queued on the streams the tracker has been updated on: slots_out [max_tracks] (every slot, live or
  * not), sums_out [max_tracks][dim] (may be NULL), counters_out [3] = next_id, tick, dropped (may be NULL) */
 int frt_tracker_tracks(frt_tracker *t, int stream, frt_track_state *slots_out, float *sums_out, int32_t *counters_out);

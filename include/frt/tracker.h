@@ -33,6 +33,25 @@ class FaceTracker {
                                           templates ? templates->data() : nullptr));
         return out;
     }
+    // The same, and how each detection was associated: assoc receives [nFrames x maxFaces] records (frt_track_assoc: by overlap, by
+    // appearance, a birth, untracked or absent; the matched track's gap, overlap and similarity).
+    std::vector<frt_track_result> update(const std::vector<frt_face_result> &results, const std::vector<float> &embeds,
+                                         std::vector<frt_track_assoc> &assoc, const std::vector<int> &streamIds = std::vector<int>(),
+                                         frt_matcher *matcher = nullptr, std::vector<float> *templates = nullptr) {
+        const int nFrames = (int)(results.size() / (size_t)maxFaces_);
+        std::vector<frt_track_result> out(results.size());
+        assoc.assign(results.size(), frt_track_assoc());
+        if (templates) templates->assign(results.size() * (size_t)dim_, 0.f);
+        const std::vector<int32_t> ids(streamIds.begin(), streamIds.end());
+        checkFrtStatus(frt_tracker_update_assoc(h_, matcher, results.data(), embeds.data(), nFrames, ids.empty() ? nullptr : ids.data(), out.data(),
+                                                templates ? templates->data() : nullptr, assoc.data()));
+        return out;
+    }
+    // Appearance (include/frt.h "Appearance"): re-attach a lost face to its track when its embedding is at least reidThreshold (0 .. 1] like
+    // the track's running sum, and refuse an overlap match whose similarity is below iouMinSim [-1 .. 1].  FRT_TRACK_REID_OFF /
+    // FRT_TRACK_MIN_SIM_OFF switch either off; both are off until set.  No threshold is recommended: measure on your own faces.
+    void setAppearance(float reidThreshold, float iouMinSim) { checkFrtStatus(frt_tracker_set_appearance(h_, reidThreshold, iouMinSim)); }
+    void getAppearance(float &reidThreshold, float &iouMinSim) { checkFrtStatus(frt_tracker_get_appearance(h_, &reidThreshold, &iouMinSim)); }
     // every slot of one stream, live or not; counters (may be null) <- next_id, tick, dropped
     std::vector<frt_track_state> tracks(int stream, int counters[3] = nullptr, std::vector<float> *sums = nullptr) {
         std::vector<frt_track_state> out((size_t)maxTracks_);

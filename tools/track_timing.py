@@ -6,8 +6,11 @@ seeded random walk (4 faces per stream, resident in HBM); the pipeline legs (c) 
      (frt_profile_enable(2)) into track_update (the update kernel), match_top1 (the extra search) and track_identity
   b  the same update done the only way possible without the tracker: records and embeddings to the host, tests/track_ref.py, MatMul.top1 of
      the templates (host wall time, the downloads included)
-  c  frt_pipeline_run_tracked against frt_pipeline_run of the same frames, on alternating legs in one process: --legs pairs of
-     --repeat calls each; per leg the median call, then the spread of the leg medians
+  c  frt_pipeline_run_tracked - appearance off, and on - against frt_pipeline_run of the same frames, on alternating legs in one process:
+     --legs triples of --repeat calls each; per leg the median call, then the spread of the leg medians
+With appearance on (--reid / --min-sim, 0.5 / 0.2):
+  a_on_*  leg a again: the whole call, and its split into track_similarity (the similarity kernel), track_update and the rest
+  w_*     the similarity kernel's worst case, once: 256 frames x 64 detections x 64 live tracks, dim 512, no matcher
 Needs the GPU.  Run it under a time limit, one process:
 
     timeout 900 python tools/track_timing.py [--rows 1000000] [--streams 32] [--repeat 30] [--legs 3] --out result.json
@@ -55,6 +58,8 @@ def main():
     ap.add_argument("--repeat", type=int, default=30)
     ap.add_argument("--legs", type=int, default=3)
     ap.add_argument("--frame", type=int, default=640)
+    ap.add_argument("--reid", type=float, default=0.5, help="reid_threshold of the legs with appearance on")
+    ap.add_argument("--min-sim", dest="min_sim", type=float, default=0.2, help="iou_min_sim of the legs with appearance on")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     import torch
@@ -114,6 +119,63 @@ def main():
     live = sum(int((trk.tracks(s)[0]["live"] != 0).sum()) for s in range(S))
     out["live_tracks_after_a"] = live
 
+    # ---- a, appearance on: the same updates with reid_threshold 0.5 / iou_min_sim 0.2 - the similarity kernel in
+    #      front of the update kernel's other instantiation
+    on = frt.Tracker(S, T, MF, D, reid_threshold=a.reid, iou_min_sim=a.min_sim)
+    upd_on = lambda k: on.updateDev(d_res[k].data_ptr(), d_emb[k % 4].data_ptr(), S, d_trk.data_ptr(), d_tpl.data_ptr(), None, mm, stream)
+    for k in range(5):
+        upd_on(k)
+    torch.cuda.synchronize()
+    ts = []
+    for k in range(5, 5 + a.repeat):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        upd_on(k)
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    report("a_on_update_dev", stats(ts))
+    on.reset()
+    frt.profile_enable(2)
+    for k in range(a.repeat):
+        upd_on(k)
+    torch.cuda.synchronize()
+    names, ms, _ = frt.profile_collect()
+    frt.profile_enable(0)
+    for part in ("track_similarity", "track_update", "match_top1", "track_identity"):
+        ks = [float(t) for n, t in zip(names, ms) if n == part]
+        assert len(ks) == a.repeat, (part, len(ks), set(names))
+        report("a_on_" + part, stats(ks))
+    on.close()
+
+    # ---- w: the worst case of the similarity kernel, once: 256 frames x 64 detections x 64 live tracks with embeddings (no matcher)
+    WF, WS = 256, 64
+    wrng = np.random.default_rng(2)
+    wres = np.zeros((WF, WS), tk.RESULT_DTYPE)
+    wres["match_idx"] = -1
+    for d in range(WS):
+        x, y = 80 * (d % 8), 80 * (d // 8)
+        wres[:, d] = (x, y, x + 60, y + 60, 0.99 - 0.01 * d, 0, -1, 0.0, 1)
+    wemb = wrng.standard_normal((WF * WS, D)).astype(np.float32)
+    wemb /= np.linalg.norm(wemb, axis=1, keepdims=True)
+    w_res, w_emb = torch.from_numpy(wres.reshape(-1).view(np.uint8).copy()).cuda(), torch.from_numpy(wemb).cuda()
+    w_trk = torch.zeros(WF * WS * 32, dtype=torch.uint8, device="cuda")
+    worst = frt.Tracker(WF, WS, WS, D, reid_threshold=a.reid, iou_min_sim=a.min_sim)
+    upd_w = lambda: worst.updateDev(w_res.data_ptr(), w_emb.data_ptr(), WF, w_trk.data_ptr(), None, None, None, stream)
+    for _ in range(3):   # the first one gives every slot a track with an embedding
+        upd_w()
+    torch.cuda.synchronize()
+    frt.profile_enable(2)
+    for _ in range(10):
+        upd_w()
+    torch.cuda.synchronize()
+    names, ms, _ = frt.profile_collect()
+    frt.profile_enable(0)
+    for part in ("track_similarity", "track_update"):
+        report("w_" + part, stats([float(t) for n, t in zip(names, ms) if n == part]))
+    out["w_live_tracks"] = sum(int((worst.tracks(s)[0]["n_embeds"] > 0).sum()) for s in (0, WF - 1))
+    worst.close()
+
     # ---- b: the same update on the host
     ref = tk.Tracker(S, T, MF, D)
     ts, parts = [], {"download": [], "track_ref": [], "top1": []}
@@ -149,7 +211,8 @@ def main():
     pipe = frt.Pipeline(det, rec, S)
     frames = s.make_frames(S, H, W)
     trk = frt.Tracker(S, T, MF, D)
-    legs = {"run": [], "run_tracked": []}
+    trk_on = frt.Tracker(S, T, MF, D, reid_threshold=a.reid, iou_min_sim=a.min_sim)
+    legs = {"run": [], "run_tracked": [], "run_tracked_on": []}
 
     def leg(fn):
         for _ in range(3):
@@ -164,12 +227,13 @@ def main():
     for _ in range(a.legs):
         legs["run"].append(leg(lambda: pipe.run(frames)))
         legs["run_tracked"].append(leg(lambda: pipe.runTracked(trk, frames)))
+        legs["run_tracked_on"].append(leg(lambda: pipe.runTracked(trk_on, frames)))
     for name, v in legs.items():
         report("c_" + name, {"leg_medians": v, "median": statistics.median(v), "min": min(v), "max": max(v)})
     out["c_faces_per_call"] = int((pipe.run(frames)[0]["score"] > 0).sum())
     with open(a.out, "w") as f:
         json.dump(out, f, indent=1)
-    trk.close(), pipe.close(), rec.close(), det.close()
+    trk.close(), trk_on.close(), pipe.close(), rec.close(), det.close()
 
 
 if __name__ == "__main__":
