@@ -188,6 +188,9 @@ ABI = {
     "frt_tracker_tracks": (_i, [_vp, _i, _vp, _vp, _vp]),
     "frt_tracker_reset": (_i, [_vp, _i]),
     "frt_pipeline_run_tracked": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "frt_tracker_gate_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "frt_tracker_gate": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "frt_pipeline_run_tracked_gated": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_face_quality_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp]),
     "frt_face_quality": (_i, [_vp, _vp, _i, _vp, _vp, _i]),
     "frt_enrol_select_gated_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -1219,6 +1222,17 @@ class TrackOptions(ctypes.Structure):  # == frt_track_options
     _fields_ = [("iou_threshold", ctypes.c_float), ("max_missed", ctypes.c_int32), ("min_hits", ctypes.c_int32), ("decay", ctypes.c_float)]
 
 
+# the gate in front of the recogniser (include/frt.h "Gate")
+TRACK_GATE_DTYPE = np.dtype([("decision", "<i4"), ("slot", "<i4"), ("ovr", "<f4"), ("why", "<i4")])  # == frt_track_gate
+TRACK_GATE_ABSENT, TRACK_GATE_EMBED, TRACK_GATE_FOLLOW = range(3)  # frt_track_gate.decision
+TRACK_GATE_NO_TRACK, TRACK_GATE_UNCONFIRMED, TRACK_GATE_FEW_EMBEDS, TRACK_GATE_LOW_OVERLAP, TRACK_GATE_REFRESH = 1, 2, 4, 8, 16  # .why
+assert TRACK_GATE_DTYPE.itemsize == 16
+
+
+class TrackGateOptions(ctypes.Structure):  # == frt_track_gate_options; no defaults: nobody has measured these on real video
+    _fields_ = [("refresh", ctypes.c_int32), ("min_embeds", ctypes.c_int32), ("skip_iou", ctypes.c_float)]
+
+
 def _stream_ids(stream_ids, n):
     if stream_ids is None:
         return None
@@ -1287,6 +1301,39 @@ class Tracker:
         _check(lib.frt_tracker_update_assoc_dev(self._h, matcher._h if matcher is not None else None, _vp(results_ptr), _vp(embeds_ptr), int(n_frames),
                                                 _ptr(ids), _vp(tracks_ptr), _vp(templates_ptr) if templates_ptr else None,
                                                 _vp(assoc_ptr) if assoc_ptr else None, _vp(hip_stream) if hip_stream else None))
+
+    def gate(self, boxes, refresh, min_embeds, skip_iou, stream_ids=None, n_boxes=None, max_batch=128):
+        """The gate alone (frt_tracker_gate; include/frt.h "Gate"): boxes BBOX_DTYPE [n * max_faces] of one frame per stream (``n_boxes``
+        int32 [n]: the detector's counts, None: every slot with score > 0 is present) -> (TRACK_GATE_DTYPE [n, max_faces], the work list int32
+        [n * max_faces] - the face indices to embed, ascending, -1 behind them -, n_embed, pass_count int32 [ceil(n * max_faces / max_batch)]).
+        Reads the state, writes none.  ``refresh`` / ``min_embeds`` / ``skip_iou`` have no defaults."""
+        boxes = np.ascontiguousarray(boxes, BBOX_DTYPE).reshape(-1)
+        if boxes.size == 0 or boxes.size % self.max_faces:
+            raise ValueError("boxes must hold max_faces boxes per frame")
+        n = boxes.size // self.max_faces
+        ids = _stream_ids(stream_ids, n)
+        if n_boxes is not None:
+            n_boxes = np.ascontiguousarray(n_boxes, np.int32).reshape(-1)
+            if n_boxes.size != n:
+                raise ValueError("one box count per frame")
+        opt = TrackGateOptions(int(refresh), int(min_embeds), float(skip_iou))
+        max_batch = int(max_batch)
+        gate = np.zeros((n, self.max_faces), TRACK_GATE_DTYPE)
+        lst = np.zeros(boxes.size, np.int32)
+        cnt = np.zeros(1, np.int32)
+        passes = np.zeros(max(-(-boxes.size // max(max_batch, 1)), 1), np.int32)
+        _check(lib.frt_tracker_gate(self._h, ctypes.addressof(opt), _ptr(boxes), _ptr(n_boxes), n, _ptr(ids), _ptr(gate), _ptr(lst), _ptr(cnt),
+                                    _ptr(passes), max_batch))
+        return gate, lst, int(cnt[0]), passes
+
+    def gateDev(self, boxes_ptr, n_frames, refresh, min_embeds, skip_iou, gate_ptr, list_ptr, n_embed_ptr, pass_count_ptr, max_batch, stream_ids=None,
+                n_boxes_ptr=None, hip_stream=None):
+        """Asynchronous on ``hip_stream`` (frt_tracker_gate_dev); the pointers are raw device addresses."""
+        ids = _stream_ids(stream_ids, int(n_frames))
+        opt = TrackGateOptions(int(refresh), int(min_embeds), float(skip_iou))
+        _check(lib.frt_tracker_gate_dev(self._h, ctypes.addressof(opt), _vp(boxes_ptr), _vp(n_boxes_ptr) if n_boxes_ptr else None, int(n_frames),
+                                        _ptr(ids), _vp(gate_ptr), _vp(list_ptr), _vp(n_embed_ptr), _vp(pass_count_ptr), int(max_batch),
+                                        _vp(hip_stream) if hip_stream else None))
 
     def tracks(self, stream, want_sums=False):
         """-> (slots TRACK_STATE_DTYPE [max_tracks], every slot, live or not; counters dict(next_id, tick, dropped)[; sums [max_tracks, dim]])"""
@@ -1386,6 +1433,31 @@ class Pipeline:
         tpl = np.zeros((n, self.max_faces, 512), np.float32) if want_templates else None
         _check(lib.frt_pipeline_run_tracked(self._h, tracker._h, _ptr(frames), n, _ptr(ids), _ptr(res), _ptr(trk), _ptr(emb), _ptr(tpl)))
         return res, emb, trk, tpl
+
+    def runTrackedGated(self, tracker, frames, refresh, min_embeds, skip_iou, stream_ids=None, want_gate=False, want_embeds=True,
+                        want_templates=True, want_crops=False):
+        """``runTracked`` with the gate in front of the recogniser (frt_pipeline_run_tracked_gated; include/frt.h "Gate"): only the faces no
+        confirmed track follows are cropped, embedded and matched; a followed face keeps its box, has valid 0 and a zero embedding row, and its
+        identity is its track's -> (records, embeddings [n * max_faces, 512] or None, track records, templates or None, n_embed[, gate
+        records TRACK_GATE_DTYPE [n, max_faces]][, u8 crops [n_embed, 112, 112, 3] of the embedded faces in list order])."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != (self.det.frameHeight, self.det.frameWidth, 3):
+            raise ValueError("runTrackedGated: frames must be [n, frameHeight, frameWidth, 3]")
+        ids = _stream_ids(stream_ids, n)
+        F = n * self.max_faces
+        opt = TrackGateOptions(int(refresh), int(min_embeds), float(skip_iou))
+        res = np.zeros(F, RESULT_DTYPE)
+        emb = np.zeros((F, 512), np.float32) if want_embeds else None
+        trk = np.zeros((n, self.max_faces), TRACK_DTYPE)
+        tpl = np.zeros((n, self.max_faces, 512), np.float32) if want_templates else None
+        gate = np.zeros((n, self.max_faces), TRACK_GATE_DTYPE) if want_gate else None
+        crops = np.zeros((F, 112, 112, 3), np.uint8) if want_crops else None
+        ne = ctypes.c_int32(0)
+        _check(lib.frt_pipeline_run_tracked_gated(self._h, tracker._h, ctypes.addressof(opt), _ptr(frames), n, _ptr(ids), _ptr(res), _ptr(trk), _ptr(gate),
+                                                  _ptr(emb), _ptr(tpl), _ptr(crops), ctypes.addressof(ne)))
+        out = (res, emb, trk, tpl, ne.value)
+        return out + ((gate,) if want_gate else ()) + ((crops[:ne.value].copy(),) if want_crops else ())
 
     def runQuality(self, frames, options=None, want_embeds=True, want_crops=False):
         """``run`` that also scores every face slot on the pipeline stream (frt_pipeline_run_quality) -> (records, embeddings or None -

@@ -236,6 +236,15 @@ void launch_det_preprocess(const uint8_t *frames, int n, int frame_h, int frame_
 void launch_crop_faces(const uint8_t *frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride, const frt_bbox *boxes,
                        const int *n_boxes, int max_faces, int F, int frames_shared, int oh, int ow, uint8_t *crops, float *chw, int *valid,
                        hipStream_t s);
+// The gather forms of launch_crop_faces (112 x 112) and launch_align_faces, the same arithmetic: face j < *count (device) of the launch is
+// face i = list[j] of a call of n_slots = n_frames * max_faces slots - frame i / max_faces, boxes[i] / landmarks[i] - and is written at the
+// compact position j of crops (may be null) / chw / valid.  cap: the faces the grid covers; positions *count .. cap - 1 are left alone.
+void launch_crop_faces_gather(const uint8_t *frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride, const frt_bbox *boxes,
+                              const int32_t *list, const int32_t *count, int max_faces, int n_slots, int cap, uint8_t *crops, float *chw, int *valid,
+                              hipStream_t s);
+void launch_align_faces_gather(const uint8_t *frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride, const float *landmarks,
+                               const int32_t *list, const int32_t *count, int max_faces, int n_slots, int cap, uint8_t *crops, float *chw, int *valid,
+                               hipStream_t s);
 // n frames u8 HWC [sh][sw][3] -> [dh][dw][3], cv::resize INTER_LINEAR semantics (frame ingest, app.cpp:301)
 void launch_resize_linear(const uint8_t *src, int n, int sh, int sw, size_t sstride, size_t sframe, uint8_t *dst, int dh, int dw, size_t dstride,
                           size_t dframe, hipStream_t s);
@@ -603,3 +612,38 @@ void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_fr
 void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, const int32_t *idx, const float *sim, hipStream_t s);
 // frees the slots of `stream` (-1: of every one of n_streams) and zeroes tick / dropped; next_id stays
 void launch_track_reset(const TrackArgs &a, int n_streams, int stream, hipStream_t s);
+// ---- the gate in front of the recogniser (include/frt.h "Gate")
+struct TrackGateArgs {
+    const frt_track_state *slots;  // [n_streams][max_tracks], read only
+    int max_tracks, max_faces;
+    float iou_threshold;
+    int min_hits;
+    int refresh, min_embeds;  // frt_track_gate_options, checked on the host: refresh >= 1
+    float skip_iou;
+    const frt_bbox *boxes;    // [n_frames][max_faces]
+    const int32_t *n_boxes;   // [n_frames], or null: every slot with score > 0 is present
+    int n_frames;             // 1 .. FRT_TRACK_MAX_FRAMES
+    frt_track_gate *gate;     // [n_frames][max_faces]
+    int32_t *list;            // [n_frames * max_faces]: the EMBED face indices ascending, -1 behind them
+    int32_t *n_embed;         // [1]
+    int32_t *pass_count;      // [ceil(n_frames * max_faces / max_batch)]
+    int max_batch;            // >= 1
+};
+// G1 - G4 and the work list of one call in one launch of one workgroup; writes no tracker state
+void launch_track_gate(const TrackGateArgs &a, const TrackStreamIds &ids, hipStream_t s);
+// the compact rows of the recogniser back into face slots: embeds [F][dim] (zero rows for the slots not in the list), valid / idx / sim [F]
+// (0 / -1 / 0 there).  idx_c / sim_c may be null (no gallery: -1 / 0 everywhere), idx / sim may be null (not written).  embeds and embeds_c
+// 16-byte aligned, dim a multiple of 4; *n_embed is clamped to 0 .. F
+struct TrackScatterArgs {
+    const int32_t *list, *n_embed;
+    const float *embeds_c;
+    const int *valid_c;
+    const int32_t *idx_c;
+    const float *sim_c;
+    int F, dim;
+    float *embeds;
+    int *valid;
+    int32_t *idx;
+    float *sim;
+};
+void launch_track_gate_scatter(const TrackScatterArgs &a, hipStream_t s);

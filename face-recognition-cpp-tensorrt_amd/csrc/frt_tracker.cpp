@@ -1,6 +1,8 @@
 // Face tracker, host side (include/frt.h "Face tracker"): the object, the argument checks that run before any device work, the three
 // launches of an update (four with appearance on: the similarity kernel goes first), the appearance settings, the host forms and
-// frt_pipeline_run_tracked.  The kernels are in kernels_track.hip.
+// frt_pipeline_run_tracked; the gate in front of the recogniser ("Gate": frt_tracker_gate / _gate_dev) and frt_pipeline_run_tracked_gated,
+// which strings detector, gate, gather crop, recogniser, search, scatter and the unchanged update together.  The kernels are in
+// kernels_track.hip (the gather crop and alignment in kernels_image.hip).
 #include "frt_pipeline.hpp"
 #include "frt_tracker.hpp"
 
@@ -97,6 +99,42 @@ void check_appearance(float reid_threshold, float iou_min_sim) {
         raise(FRT_ERR_INVALID, "tracker: reid_threshold outside (0, 1] and not the off value 2.0");
     if (!((iou_min_sim >= -1.f && iou_min_sim <= 1.f) || iou_min_sim == FRT_TRACK_MIN_SIM_OFF))
         raise(FRT_ERR_INVALID, "tracker: iou_min_sim outside [-1, 1] and not the off value -2.0");
+}
+
+// "Gate": no defaults, so a null pointer is refused like a value out of range (written so that a NaN fails)
+frt_track_gate_options checked_gate_options(const frt_track_gate_options *o) {
+    if (!o) raise(FRT_ERR_INVALID, "tracker gate: null options (the gate has no defaults)");
+    if (o->refresh < 1) raise(FRT_ERR_INVALID, "tracker gate: refresh < 1");
+    if (o->min_embeds < 1) raise(FRT_ERR_INVALID, "tracker gate: min_embeds < 1");
+    if (!(o->skip_iou > 0.f && o->skip_iou <= 1.f)) raise(FRT_ERR_INVALID, "tracker gate: skip_iou outside (0, 1]");
+    return *o;
+}
+
+// One gate launch queued on s, with t->mu held, the state allocated and every argument checked
+void gate_locked(frt_tracker *t, const frt_track_gate_options &o, const frt_bbox *boxes_dev, const int32_t *n_boxes_dev, int n_frames,
+                 const TrackStreamIds &ids, frt_track_gate *gate_dev, int32_t *list_dev, int32_t *n_embed_dev, int32_t *pass_count_dev, int max_batch,
+                 hipStream_t s) {
+    TrackGateArgs a{};
+    a.slots = t->slots.get();
+    a.max_tracks = t->max_tracks;
+    a.max_faces = t->max_faces;
+    a.iou_threshold = t->opt.iou_threshold;
+    a.min_hits = t->opt.min_hits;
+    a.refresh = o.refresh;
+    a.min_embeds = o.min_embeds;
+    a.skip_iou = o.skip_iou;
+    a.boxes = boxes_dev;
+    a.n_boxes = n_boxes_dev;
+    a.n_frames = n_frames;
+    a.gate = gate_dev;
+    a.list = list_dev;
+    a.n_embed = n_embed_dev;
+    a.pass_count = pass_count_dev;
+    a.max_batch = max_batch;
+    if (t->pending) HIPCHK(hipStreamWaitEvent(s, t->ev_last, 0));  // the state the gate reads is the last queued update's
+    ProfScope ps(2, "track_gate", (double)n_frames * t->max_faces, s);
+    launch_track_gate(a, ids, s);
+    HIPCHK(hipGetLastError());
 }
 
 // The stream, the events and the zeroed state, on the first call that passed its checks.  All of it or nothing: a failure leaves the
@@ -314,6 +352,178 @@ int frt_pipeline_run_tracked(frt_pipeline *p, frt_tracker *t, const uint8_t *fra
             throw;
         }
         p->emb->check_se_error();
+    });
+}
+
+int frt_tracker_gate_dev(frt_tracker *t, const frt_track_gate_options *options, const void *boxes_dev, const void *n_boxes_dev, int n_frames,
+                         const int32_t *stream_ids, void *gate_dev, void *list_dev, void *n_embed_dev, void *pass_count_dev, int max_batch,
+                         void *hip_stream) {
+    return guarded([&] {
+        if (!t || !boxes_dev || !gate_dev || !list_dev || !n_embed_dev || !pass_count_dev) raise(FRT_ERR_INVALID, "tracker gate: null argument");
+        const frt_track_gate_options o = checked_gate_options(options);
+        if (max_batch < 1) raise(FRT_ERR_INVALID, "tracker gate: max_batch < 1");
+        std::lock_guard<std::mutex> lk(t->mu);
+        const TrackStreamIds ids = tracker_check_ids(t, n_frames, stream_ids);
+        ensure_state(t);
+        gate_locked(t, o, reinterpret_cast<const frt_bbox *>(boxes_dev), reinterpret_cast<const int32_t *>(n_boxes_dev), n_frames, ids,
+                    reinterpret_cast<frt_track_gate *>(gate_dev), reinterpret_cast<int32_t *>(list_dev), reinterpret_cast<int32_t *>(n_embed_dev),
+                    reinterpret_cast<int32_t *>(pass_count_dev), max_batch, reinterpret_cast<hipStream_t>(hip_stream));
+    });
+}
+
+int frt_tracker_gate(frt_tracker *t, const frt_track_gate_options *options, const frt_bbox *boxes, const int32_t *n_boxes, int n_frames,
+                     const int32_t *stream_ids, frt_track_gate *gate_out, int32_t *list_out, int32_t *n_embed_out, int32_t *pass_count_out,
+                     int max_batch) {
+    return guarded([&] {
+        if (!t || !boxes || !gate_out || !list_out || !n_embed_out || !pass_count_out) raise(FRT_ERR_INVALID, "tracker gate: null argument");
+        const frt_track_gate_options o = checked_gate_options(options);
+        if (max_batch < 1) raise(FRT_ERR_INVALID, "tracker gate: max_batch < 1");
+        std::lock_guard<std::mutex> lk(t->mu);
+        const TrackStreamIds ids = tracker_check_ids(t, n_frames, stream_ids);
+        ensure_state(t);
+        const size_t F = (size_t)n_frames * t->max_faces, passes = (F + (size_t)max_batch - 1) / (size_t)max_batch;
+        hipStream_t s = t->stream;
+        join_updates(t);
+        HIPCHK(hipStreamSynchronize(s));  // the staging is rewritten below
+        frt_tracker::Gated &g = t->gated;
+        g.boxes.reserve(F);
+        g.n_boxes.reserve((size_t)n_frames);
+        g.gate.reserve(F);
+        g.list.reserve(F);
+        g.n_embed.reserve(1);
+        g.pass_count.reserve(passes);
+        HIPCHK(hipMemcpyAsync(g.boxes.get(), boxes, F * sizeof(frt_bbox), hipMemcpyHostToDevice, s));
+        if (n_boxes) HIPCHK(hipMemcpyAsync(g.n_boxes.get(), n_boxes, (size_t)n_frames * sizeof(int32_t), hipMemcpyHostToDevice, s));
+        gate_locked(t, o, g.boxes.get(), n_boxes ? g.n_boxes.get() : nullptr, n_frames, ids, g.gate.get(), g.list.get(), g.n_embed.get(),
+                    g.pass_count.get(), max_batch, s);
+        HIPCHK(hipMemcpyAsync(gate_out, g.gate.get(), F * sizeof(frt_track_gate), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(list_out, g.list.get(), F * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(n_embed_out, g.n_embed.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(pass_count_out, g.pass_count.get(), passes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        sync_stream_spinning(s);
+    });
+}
+
+int frt_pipeline_run_tracked_gated(frt_pipeline *p, frt_tracker *t, const frt_track_gate_options *options, const uint8_t *frames, int n_frames,
+                                   const int32_t *stream_ids, frt_face_result *results, frt_track_result *tracks_out, frt_track_gate *gate_out,
+                                   float *embeds_out, float *templates_out, uint8_t *crops_out, int32_t *n_embed_out) {
+    return guarded([&] {
+        if (!p || !t || !frames || !results || !tracks_out || !n_embed_out) raise(FRT_ERR_INVALID, "runTrackedGated: null argument");
+        const frt_track_gate_options o = checked_gate_options(options);
+        // ---- tracker -> run_mu -> detector, embedder -> matcher
+        std::lock_guard<std::mutex> lk(t->mu);
+        if (t->max_faces != p->max_faces || t->dim != 512) raise(FRT_ERR_INVALID, "runTrackedGated: the tracker's max_faces and dim must be the pipeline's");
+        if (t->device != p->det->device) raise(FRT_ERR_INVALID, "runTrackedGated: tracker and pipeline live on different devices");
+        const TrackStreamIds ids = tracker_check_ids(t, n_frames, stream_ids);
+        if (n_frames > p->max_frames) raise(FRT_ERR_INVALID, "runTrackedGated: more frames than the pipeline's max_frames");
+        tracker_check_matcher(t, p->mat);
+        ensure_state(t);
+        frt_detector *d = p->det;
+        frt_embedder *e = p->emb;
+        frt_matcher *m = p->mat;
+        const DetGeom &dg = d->g;
+        const int MF = t->max_faces, Fi = n_frames * MF, B = e->max_batch;
+        const size_t row = (size_t)dg.frame_w * 3, frame_bytes = (size_t)dg.frame_h * row, F = (size_t)Fi;
+        constexpr size_t CROP = (size_t)112 * 112 * 3;
+        join_updates(t);
+        HIPCHK(hipStreamSynchronize(t->stream));  // a host form may still be reading the staging
+        t->reserve_staging(n_frames, frame_bytes);
+        frt_tracker::Gated &g = t->gated;
+        g.boxes.reserve(F);
+        g.n_boxes.reserve((size_t)n_frames);
+        if (d->has_landmarks) g.ldm.reserve(F * 10);
+        g.gate.reserve(F);
+        g.list.reserve(F);
+        g.n_embed.reserve(1);
+        g.h_n_embed.reserve(1);
+        g.pass_count.reserve((F + (size_t)B - 1) / (size_t)B);
+        g.embeds_c.reserve(F * 512);
+        g.sim_c.reserve(F);
+        g.sim.reserve(F);
+        g.idx_c.reserve(F);
+        g.idx.reserve(F);
+        g.valid_c.reserve(F);
+        g.valid.reserve(F);
+        if (crops_out) g.crops.reserve(F * CROP);
+
+        std::lock_guard<std::mutex> lr(p->run_mu);
+        p->flush();  // whatever a pairing mode holds or has pending goes first (takes the object mutexes itself)
+        p->ensure_stream();
+        hipStream_t s = p->stream;
+        std::lock_guard<std::mutex> ld(d->mu), le(e->mu);
+        std::unique_lock<std::mutex> lm;
+        if (m) lm = std::unique_lock<std::mutex>(m->mu);
+        const bool align = p->align;  // (frt_pipeline_set_align refuses a detector without the LandmarkHead)
+        try {
+            d->wait_idle(s);
+            e->wait_idle(s);
+            HIPCHK(hipMemcpyAsync(t->d_frames.get(), frames, n_frames * frame_bytes, hipMemcpyHostToDevice, s));
+            d->forward_frames(t->d_frames.get(), n_frames, row, frame_bytes, s);
+            d->postprocess(n_frames, s, g.boxes.get(), g.n_boxes.get(), d->has_landmarks ? g.ldm.get() : nullptr);
+            HIPCHK(hipEventRecord(d->ev_busy, s));
+            d->busy = true;
+            gate_locked(t, o, g.boxes.get(), g.n_boxes.get(), n_frames, ids, g.gate.get(), g.list.get(), g.n_embed.get(), g.pass_count.get(), B, s);
+            // the one host read in front of the recogniser: how many passes to queue
+            HIPCHK(hipMemcpyAsync(g.h_n_embed.get(), g.n_embed.get(), sizeof(int32_t), hipMemcpyDeviceToHost, s));
+            sync_stream_spinning(s);
+            const int ne = *g.h_n_embed.get();
+            if (ne < 0 || ne > Fi) raise(FRT_ERR_DEVICE, "runTrackedGated: the gate returned an impossible count");
+            for (int f0 = 0, j = 0; f0 < ne; f0 += B, ++j) {  // passes cut as frt_embedder_forward cuts them
+                const int nf = std::min(B, ne - f0);
+                uint8_t *crops = crops_out ? g.crops.get() + (size_t)f0 * CROP : nullptr;
+                if (align) {
+                    ProfScope ps(2, "align_faces_gather", (double)nf * CROP, s);
+                    launch_align_faces_gather(t->d_frames.get(), dg.frame_h, dg.frame_w, row, frame_bytes, g.ldm.get(), g.list.get() + f0,
+                                              g.pass_count.get() + j, MF, Fi, nf, crops, e->d_in, g.valid_c.get() + f0, s);
+                } else {
+                    ProfScope ps(2, "crop_faces_gather", (double)nf * CROP, s);
+                    launch_crop_faces_gather(t->d_frames.get(), dg.frame_h, dg.frame_w, row, frame_bytes, g.boxes.get(), g.list.get() + f0,
+                                             g.pass_count.get() + j, MF, Fi, nf, crops, e->d_in, g.valid_c.get() + f0, s);
+                }
+                HIPCHK(hipGetLastError());
+                e->forward(0, e->d_in, nf, g.valid_c.get() + f0, g.embeds_c.get() + (size_t)f0 * 512, s);
+            }
+            if (ne > 0) {
+                HIPCHK(hipEventRecord(e->ev_busy[0], s));
+                e->busy[0] = true;
+            }
+            const bool gallery = m && m->N > 0, searched = gallery && ne > 0;
+            if (searched) {
+                m->wait_idle(s);
+                m->ensure_queries(ne);
+                m->top1_dev(g.embeds_c.get(), ne, g.idx_c.get(), g.sim_c.get(), s);
+                HIPCHK(hipEventRecord(m->ev_busy, s));
+                m->busy = true;
+            }
+            {
+                ProfScope ps(2, "track_gate_scatter", (double)F * 512, s);
+                TrackScatterArgs sa{g.list.get(), g.n_embed.get(), g.embeds_c.get(), g.valid_c.get(), searched ? g.idx_c.get() : nullptr,
+                                    searched ? g.sim_c.get() : nullptr, Fi, 512, t->d_embeds.get(), g.valid.get(), g.idx.get(), g.sim.get()};
+                launch_track_gate_scatter(sa, s);
+                HIPCHK(hipGetLastError());
+            }
+            {
+                ProfScope ps(2, "pack_results", (double)F, s);
+                launch_pack_results(g.boxes.get(), g.n_boxes.get(), g.valid.get(), gallery ? g.idx.get() : nullptr, gallery ? g.sim.get() : nullptr, MF,
+                                    Fi, t->d_results.get(), s);
+                HIPCHK(hipGetLastError());
+            }
+            if (m) lm.unlock();  // (the update takes the matcher's mutex itself)
+            tracker_update_locked(t, m, t->d_results.get(), t->d_embeds.get(), n_frames, ids, t->d_tracks.get(),
+                                  templates_out ? t->d_templates.get() : nullptr, nullptr, s);
+            HIPCHK(hipMemcpyAsync(results, t->d_results.get(), F * sizeof(frt_face_result), hipMemcpyDeviceToHost, s));
+            HIPCHK(hipMemcpyAsync(tracks_out, t->d_tracks.get(), F * sizeof(frt_track_result), hipMemcpyDeviceToHost, s));
+            if (gate_out) HIPCHK(hipMemcpyAsync(gate_out, g.gate.get(), F * sizeof(frt_track_gate), hipMemcpyDeviceToHost, s));
+            if (embeds_out) HIPCHK(hipMemcpyAsync(embeds_out, t->d_embeds.get(), F * 512 * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (templates_out) HIPCHK(hipMemcpyAsync(templates_out, t->d_templates.get(), F * 512 * sizeof(float), hipMemcpyDeviceToHost, s));
+            if (crops_out && ne > 0) HIPCHK(hipMemcpyAsync(crops_out, g.crops.get(), (size_t)ne * CROP, hipMemcpyDeviceToHost, s));
+            sync_stream_spinning(s);
+            *n_embed_out = ne;
+        } catch (...) {  // leave nothing in flight that reads the caller's frames or writes the caller's arrays
+            (void)hipStreamSynchronize(s);
+            throw;
+        }
+        e->check_se_error();
     });
 }
 

@@ -31,6 +31,19 @@ struct frt_tracker {
     DevBuf<float> d_embeds, d_templates;
     DevBuf<frt_track_result> d_tracks;
     DevBuf<frt_track_assoc> d_assoc;  // (only once a host form has asked for it)
+    // ---- the gate (frt_tracker_gate, frt_pipeline_run_tracked_gated), grown to the call: the detector's boxes / counts / landmarks, the
+    //      gate's records and work list, the compact rows the recogniser and the search leave, and their scatter into face slots
+    struct Gated {
+        DevBuf<frt_bbox> boxes;                             // [n_frames][max_faces]
+        DevBuf<float> ldm;                                  // [n_frames][max_faces][10] (a detector with the LandmarkHead)
+        DevBuf<frt_track_gate> gate;                        // [n_frames][max_faces]
+        DevBuf<int32_t> n_boxes, list, n_embed, pass_count; // [n_frames], [F], [1], [ceil(F / max_batch)]
+        PinnedBuf<int32_t> h_n_embed;                       // the one host read in front of the recogniser
+        DevBuf<float> embeds_c, sim_c, sim;                 // [F][512], [F], [F]
+        DevBuf<int32_t> idx_c, idx;                         // [F]
+        DevBuf<int> valid_c, valid;                         // [F]
+        DevBuf<uint8_t> crops;                              // [F][112][112][3], calls that ask for crops
+    } gated;
 
     TrackArgs args() const {
         TrackArgs a{};

@@ -135,22 +135,20 @@ __device__ __forceinline__ void cubic_coeffs(float x, int *c) {
     for (int k = 0; k < 4; ++k) c[k] = sat_short_round(w[k] * COEF_SCALE);
 }
 
-__global__ void crop_faces_kernel(const uint8_t *__restrict__ frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride,
-                                  const frt_bbox *__restrict__ boxes, const int *__restrict__ n_boxes, int max_faces, int frames_shared,
-                                  int oh, int ow, uint8_t *__restrict__ crops, float *__restrict__ chw, int *__restrict__ valid) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const int f = blockIdx.y;
-    if (p >= oh * ow) return;
+// Pixel p (< oh * ow) of one face: box b of the frame at `frame` (frame_h x frame_w, row_stride bytes a row), cut, resized and normalised
+// into position `out` of crops (may be null) / chw / valid (may be null).  present: what the caller knows beyond the box (the frame's box
+// count).  The one copy of the crop arithmetic: crop_faces_kernel places face f at f, crop_faces_gather_kernel face list[j] at j.
+__device__ __forceinline__ void crop_face(const uint8_t *__restrict__ frame, int frame_h, int frame_w, size_t row_stride, const frt_bbox b,
+                                          bool present, int oh, int ow, int p, size_t out, uint8_t *__restrict__ crops, float *__restrict__ chw,
+                                          int *__restrict__ valid) {
+    const int f = (int)out;
     const int dy = p / ow, dx = p - dy * ow;
-    const int frame = frames_shared ? 0 : f / max_faces;
-    const frt_bbox b = boxes[f];
     const int rh = b.x2 - b.x1, rw = b.y2 - b.y1;  // rows = x, cols = y; far corner excluded (cv::Rect(Point,Point))
-    bool ok = rh > 0 && rw > 0 && b.x1 >= 0 && b.y1 >= 0 && b.x2 <= frame_h && b.y2 <= frame_w;
-    if (n_boxes) ok = ok && (f % max_faces) < n_boxes[f / max_faces];
+    const bool ok = rh > 0 && rw > 0 && b.x1 >= 0 && b.y1 >= 0 && b.x2 <= frame_h && b.y2 <= frame_w && present;
     if (p == 0 && valid) valid[f] = ok ? 1 : 0;
     int v[3] = {0, 0, 0};
     if (ok) {
-        const uint8_t *src = frames + (size_t)frame * frame_stride + (size_t)b.x1 * row_stride + (size_t)b.y1 * 3;
+        const uint8_t *src = frame + (size_t)b.x1 * row_stride + (size_t)b.y1 * 3;
         if (rh == oh && rw == ow) {
             const uint8_t *s = src + (size_t)dy * row_stride + (size_t)dx * 3;
             v[0] = s[0];
@@ -193,6 +191,32 @@ __global__ void crop_faces_kernel(const uint8_t *__restrict__ frames, int frame_
     float *o = chw + (size_t)f * 3 * oh * ow + p;
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[(size_t)c * oh * ow] = ok ? ((float)v[2 - c] - 127.5f) * 0.0078125f : 0.f;
+}
+
+__global__ void crop_faces_kernel(const uint8_t *__restrict__ frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride,
+                                  const frt_bbox *__restrict__ boxes, const int *__restrict__ n_boxes, int max_faces, int frames_shared,
+                                  int oh, int ow, uint8_t *__restrict__ crops, float *__restrict__ chw, int *__restrict__ valid) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const int f = blockIdx.y;
+    if (p >= oh * ow) return;
+    const int frame = frames_shared ? 0 : f / max_faces;
+    const bool present = !n_boxes || (f % max_faces) < n_boxes[f / max_faces];
+    crop_face(frames + (size_t)frame * frame_stride, frame_h, frame_w, row_stride, boxes[f], present, oh, ow, p, (size_t)f, crops, chw, valid);
+}
+
+// The gather form (frt_pipeline_run_tracked_gated): face j of the pass is face i = list[j] of a call of n_slots = n_frames * max_faces
+// slots - frame i / max_faces, box i - and lands at the compact position j.  The grid is the pass's capacity; *count (device) faces are
+// live, the threads behind them leave, and so do those of an entry outside 0 .. n_slots - 1.
+__global__ void crop_faces_gather_kernel(const uint8_t *__restrict__ frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride,
+                                         const frt_bbox *__restrict__ boxes, const int32_t *__restrict__ list, const int32_t *__restrict__ count,
+                                         int max_faces, int n_slots, int oh, int ow, uint8_t *__restrict__ crops, float *__restrict__ chw,
+                                         int *__restrict__ valid) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const int j = blockIdx.y;
+    if (p >= oh * ow || j >= *count) return;
+    const int i = list[j];
+    if (i < 0 || i >= n_slots) return;
+    crop_face(frames + (size_t)(i / max_faces) * frame_stride, frame_h, frame_w, row_stride, boxes[i], true, oh, ow, p, (size_t)j, crops, chw, valid);
 }
 
 __global__ void face_normalize_kernel(const uint8_t *__restrict__ crops, int hw, float *__restrict__ chw) {
@@ -311,6 +335,15 @@ void launch_crop_faces(const uint8_t *frames, int frame_h, int frame_w, size_t r
                        frames_shared, oh, ow, crops, chw, valid);
 }
 
+void launch_crop_faces_gather(const uint8_t *frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride, const frt_bbox *boxes,
+                              const int32_t *list, const int32_t *count, int max_faces, int n_slots, int cap, uint8_t *crops, float *chw, int *valid,
+                              hipStream_t s) {
+    if (cap <= 0) return;
+    dim3 grid((112 * 112 + 255) / 256, cap);
+    hipLaunchKernelGGL(crop_faces_gather_kernel, grid, dim3(256), 0, s, frames, frame_h, frame_w, row_stride, frame_stride, boxes, list, count,
+                       max_faces, n_slots, 112, 112, crops, chw, valid);
+}
+
 // ---------------------------------------------------------------- 5-point alignment (optional mode; absent from the reference)
 // Least-squares similarity (scale * rotation + translation; equals Umeyama's solution whenever that is not a reflection) from the
 // 5 detected landmarks to the public ArcFace 112x112 template, then an inverse-mapped bilinear warp with zero border, fused
@@ -318,16 +351,13 @@ void launch_crop_faces(const uint8_t *frames, int frame_h, int frame_w, size_t r
 namespace {
 __constant__ float c_arc_template[10] = {38.2946f, 51.6963f, 73.5318f, 51.5014f, 56.0252f, 71.7366f, 41.5493f, 92.3655f, 70.7299f, 92.2041f};
 
-__global__ __launch_bounds__(256) void align_faces_kernel(const uint8_t *__restrict__ frames, int frame_h, int frame_w, size_t row_stride,
-                                                          size_t frame_stride, const float *__restrict__ landmarks, const int *__restrict__ n_boxes,
-                                                          int max_faces, int frames_shared, uint8_t *__restrict__ crops, float *__restrict__ chw,
-                                                          int *__restrict__ valid) {
-    const int f = blockIdx.y;
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    const int frame = frames_shared ? 0 : f / max_faces;
-    bool ok = !n_boxes || (f % max_faces) < n_boxes[f / max_faces];
+// Pixel p (any p of the 256-thread blocks that cover 112 x 112) of one face: the landmarks lm[10] of the frame at `src`, warped and
+// normalised into position `out` of crops (may be null) / chw / valid (may be null).  ok on entry: what the caller knows beyond the landmarks
+// (the frame's box count).  The one copy of the warp: align_faces_kernel places face f at f, align_faces_gather_kernel face list[j] at j.
+__device__ __forceinline__ void align_face(const uint8_t *__restrict__ src, int frame_h, int frame_w, size_t row_stride, const float *__restrict__ lm,
+                                           bool ok, int p, size_t out, uint8_t *__restrict__ crops, float *__restrict__ chw, int *__restrict__ valid) {
+    const size_t f = out;
     // every thread derives the same 2x3 inverse transform (25 flops; cheaper than a broadcast)
-    const float *lm = landmarks + (long)f * 10;
     float msx = 0.f, msy = 0.f, mdx = 0.f, mdy = 0.f;
 #pragma unroll
     for (int k = 0; k < 5; ++k) {
@@ -361,7 +391,6 @@ __global__ __launch_bounds__(256) void align_faces_kernel(const uint8_t *__restr
         const float fx0 = floorf(sxf), fy0 = floorf(syf);
         const int x0 = (int)fx0, y0 = (int)fy0;
         const float wx = sxf - fx0, wy = syf - fy0;
-        const uint8_t *src = frames + (size_t)frame * frame_stride;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             float t4[4];
@@ -385,7 +414,42 @@ __global__ __launch_bounds__(256) void align_faces_kernel(const uint8_t *__restr
 #pragma unroll
     for (int c = 0; c < 3; ++c) o[(size_t)c * 112 * 112] = ok ? ((float)v[2 - c] - 127.5f) * 0.0078125f : 0.f;
 }
+
+__global__ __launch_bounds__(256) void align_faces_kernel(const uint8_t *__restrict__ frames, int frame_h, int frame_w, size_t row_stride,
+                                                          size_t frame_stride, const float *__restrict__ landmarks, const int *__restrict__ n_boxes,
+                                                          int max_faces, int frames_shared, uint8_t *__restrict__ crops, float *__restrict__ chw,
+                                                          int *__restrict__ valid) {
+    const int f = blockIdx.y;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    const int frame = frames_shared ? 0 : f / max_faces;
+    const bool ok = !n_boxes || (f % max_faces) < n_boxes[f / max_faces];
+    align_face(frames + (size_t)frame * frame_stride, frame_h, frame_w, row_stride, landmarks + (long)f * 10, ok, p, (size_t)f, crops, chw, valid);
+}
+
+// the gather form, as crop_faces_gather_kernel: landmarks [n_slots][10], face list[j] -> position j
+__global__ __launch_bounds__(256) void align_faces_gather_kernel(const uint8_t *__restrict__ frames, int frame_h, int frame_w, size_t row_stride,
+                                                                 size_t frame_stride, const float *__restrict__ landmarks,
+                                                                 const int32_t *__restrict__ list, const int32_t *__restrict__ count, int max_faces,
+                                                                 int n_slots, uint8_t *__restrict__ crops, float *__restrict__ chw,
+                                                                 int *__restrict__ valid) {
+    const int j = blockIdx.y;
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= *count) return;
+    const int i = list[j];
+    if (i < 0 || i >= n_slots) return;
+    align_face(frames + (size_t)(i / max_faces) * frame_stride, frame_h, frame_w, row_stride, landmarks + (long)i * 10, true, p, (size_t)j, crops, chw,
+               valid);
+}
 }  // namespace
+
+void launch_align_faces_gather(const uint8_t *frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride, const float *landmarks,
+                               const int32_t *list, const int32_t *count, int max_faces, int n_slots, int cap, uint8_t *crops, float *chw, int *valid,
+                               hipStream_t s) {
+    if (cap <= 0) return;
+    dim3 grid((112 * 112 + 255) / 256, cap);
+    hipLaunchKernelGGL(align_faces_gather_kernel, grid, dim3(256), 0, s, frames, frame_h, frame_w, row_stride, frame_stride, landmarks, list, count,
+                       max_faces, n_slots, crops, chw, valid);
+}
 
 void launch_align_faces(const uint8_t *frames, int frame_h, int frame_w, size_t row_stride, size_t frame_stride, const float *landmarks,
                         const int *n_boxes, int max_faces, int F, int frames_shared, uint8_t *crops, float *chw, int *valid, hipStream_t s) {

@@ -26,6 +26,21 @@
 //     Lane d collects how its detection was associated.  track_update_kernel<false> is the kernel of a tracker without appearance.
 //   Bounds: the grid of the similarity kernel is (max_faces, n_frames); its slot index is tested against max_tracks, its columns against dim;
 //   the update kernel reads S[d][lane] only where the defined bit of lane is set, and bits are set for slots < max_tracks only.
+//
+// Gate (include/frt.h "Gate"; tests/track_gate_ref.py), in front of the recogniser of frt_pipeline_run_tracked_gated:
+//   - track_gate_kernel, ONE workgroup of sixteen waves for the whole call; wave w takes the frames w, w + 16, ...  A wave holds its frame's
+//     stream one slot per lane as wave 0 of the update does and walks the detections with the update's own reduction (step 2 without the
+//     appearance terms, and without writing the state: a winner is only marked taken).  Lane d keeps the record of detection d; the frame's
+//     EMBED set is one ballot, kept in LDS.  Behind one barrier wave 0 turns the 256 popcounts into exclusive offsets (four frames per lane,
+//     a shuffle scan over the lanes); behind a second one every wave writes its frames' part of the list - a detection's place is the frame's
+//     offset plus the set bits below its own -, so the list is ascending without a sort and the same on every run.  The entries past the count
+//     are -1, pass_count[j] is tile_faces_select_kernel's.
+//   - track_gate_scatter_kernel, one wave per face slot: the list is ascending, so whether slot i is in it, and where, is a binary search of
+//     at most 14 wave-uniform steps; the row is 16 bytes per lane and 256-column group, zeros for a slot that is not in the list.
+//   Bounds: a frame index is < n_frames <= 256 (the LDS tables' length), a stream id was checked on the host, a slot index is the lane and
+//   tested against max_tracks, a detection index is < max_faces <= 64; a list position is offset + bits below < the count <= n_frames *
+//   max_faces, the list's length; n_boxes[f] is only compared.  The scatter clamps the count it reads to 0 .. n_frames * max_faces, reads
+//   list[j] for j below it only and the compact rows at such j only; its own row index is tested against n_frames * max_faces.
 #include "frt_kernels.h"
 
 namespace {
@@ -359,6 +374,125 @@ __global__ __launch_bounds__(64) void track_reset_kernel(TrackArgs a, int first_
     }
 }
 
+constexpr int GATE_WAVES = 16;
+
+// one workgroup for the call (see the header comment)
+__global__ __launch_bounds__(64 * GATE_WAVES) void track_gate_kernel(TrackGateArgs a, TrackStreamIds ids) {
+    __shared__ unsigned long long s_mask[FRT_TRACK_MAX_FRAMES];  // the EMBED detections of a frame
+    __shared__ int s_off[FRT_TRACK_MAX_FRAMES];                  // list entries in front of a frame's
+    __shared__ int s_total;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int T = a.max_tracks, MF = a.max_faces, NF = a.n_frames;
+    if (tid < FRT_TRACK_MAX_FRAMES && tid >= NF) s_mask[tid] = 0;
+
+    for (int f = wave; f < NF; f += GATE_WAVES) {
+        const int stream = ids.id[f];
+        const frt_bbox *boxes = a.boxes + (long)f * MF;
+        const int n_present = a.n_boxes ? a.n_boxes[f] : MF;
+        frt_track_state st = {};
+        if (lane < T) st = a.slots[(long)stream * T + lane];
+        const bool live_entry = lane < T && st.live != 0;
+        bool taken = false;
+        frt_track_gate mine = {0, -1, 0.f, 0};  // lane d: the record of detection d
+        // ---- G1, G2: the update's steps 1 and 2, overlap only
+        for (int d = 0; d < MF; ++d) {
+            if (d >= n_present) break;  // (wave-uniform)
+            const frt_bbox b = boxes[d];
+            if (!(b.score > 0.f)) continue;  // (wave-uniform)
+            unsigned long long key = 0;
+            if (live_entry && !taken) {
+                const float ovr = iou(b, st.box);
+                if (ovr >= a.iou_threshold) key = ((unsigned long long)__float_as_uint(ovr) << 32) | (unsigned)(63 - lane);
+            }
+            key = wave_max_u64(key);
+            frt_track_gate g = {FRT_TRACK_GATE_EMBED, -1, 0.f, FRT_TRACK_GATE_NO_TRACK};
+            if (key != 0) {
+                const int win = 63 - (int)(key & 63);
+                const int hits = __shfl(st.hits, win), ne = __shfl(st.n_embeds, win);
+                const float ovr = __uint_as_float((unsigned)(key >> 32));
+                if (lane == win) taken = true;
+                // ---- G3
+                int why = 0;
+                if (hits < a.min_hits) why |= FRT_TRACK_GATE_UNCONFIRMED;
+                if (ne < a.min_embeds) why |= FRT_TRACK_GATE_FEW_EMBEDS;
+                if (!(ovr >= a.skip_iou)) why |= FRT_TRACK_GATE_LOW_OVERLAP;
+                if ((hits + 1) % a.refresh == 0) why |= FRT_TRACK_GATE_REFRESH;
+                g = frt_track_gate{why ? FRT_TRACK_GATE_EMBED : FRT_TRACK_GATE_FOLLOW, win, ovr, why};
+            }
+            if (lane == d) mine = g;
+        }
+        // ---- G4
+        if (lane < MF) a.gate[(long)f * MF + lane] = mine;
+        const unsigned long long embed = __ballot(lane < MF && mine.decision == FRT_TRACK_GATE_EMBED);
+        if (lane == 0) s_mask[f] = embed;
+    }
+    __syncthreads();
+
+    // ---- the work list: exclusive offsets of the frames, four frames per lane of wave 0
+    if (wave == 0) {
+        int c[4], sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            c[k] = __popcll(s_mask[lane * 4 + k]);
+            sum += c[k];
+        }
+        int incl = sum;
+        for (int off = 1; off < 64; off <<= 1) {
+            const int o = __shfl_up(incl, off);
+            if (lane >= off) incl += o;
+        }
+        int run = incl - sum;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            s_off[lane * 4 + k] = run;
+            run += c[k];
+        }
+        if (lane == 63) s_total = incl;
+    }
+    __syncthreads();
+    const int n_embed = s_total, cap = NF * MF;
+    for (int f = wave; f < NF; f += GATE_WAVES) {
+        const unsigned long long m = s_mask[f];
+        if ((m >> lane) & 1) a.list[s_off[f] + __popcll(m & ((1ull << lane) - 1ull))] = f * MF + lane;
+    }
+    for (int i = n_embed + tid; i < cap; i += 64 * GATE_WAVES) a.list[i] = -1;
+    if (tid == 0) *a.n_embed = n_embed;
+    const int passes = (cap + a.max_batch - 1) / a.max_batch;
+    for (int j = tid; j < passes; j += 64 * GATE_WAVES) {
+        const long long left = (long long)n_embed - (long long)j * a.max_batch;
+        a.pass_count[j] = (int32_t)(left < 0 ? 0 : (left > a.max_batch ? a.max_batch : left));
+    }
+}
+
+// one wave per face slot of the call, four to a workgroup (see the header comment)
+__global__ __launch_bounds__(64 * WAVES) void track_gate_scatter_kernel(TrackScatterArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int i = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * WAVES + (threadIdx.x >> 6)));
+    if (i >= a.F) return;
+    int n = *a.n_embed;
+    n = n < 0 ? 0 : (n > a.F ? a.F : n);
+    int lo = 0, hi = n;  // the first position whose entry is >= i
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a.list[mid] < i) lo = mid + 1;
+        else hi = mid;
+    }
+    const bool found = lo < n && a.list[lo] == i;
+    float *out = a.embeds + (long)i * a.dim;
+    if (found) {  // (wave-uniform)
+        const float *row = a.embeds_c + (long)lo * a.dim;
+        for (int k = lane * 4; k < a.dim; k += 256) *reinterpret_cast<floatx4 *>(out + k) = *reinterpret_cast<const floatx4 *>(row + k);
+    } else {
+        for (int k = lane * 4; k < a.dim; k += 256) *reinterpret_cast<floatx4 *>(out + k) = floatx4{0.f, 0.f, 0.f, 0.f};
+    }
+    if (lane == 0) {
+        a.valid[i] = found ? a.valid_c[lo] : 0;
+        if (a.idx) a.idx[i] = (found && a.idx_c) ? a.idx_c[lo] : -1;
+        if (a.sim) a.sim[i] = (found && a.sim_c) ? a.sim_c[lo] : 0.f;
+    }
+}
+
 }  // namespace
 
 void launch_track_similarity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s) {
@@ -377,6 +511,16 @@ void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_fr
 void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, const int32_t *idx, const float *sim, hipStream_t s) {
     if (n_frames <= 0) return;
     hipLaunchKernelGGL(track_identity_kernel, dim3((unsigned)((n_frames * a.max_faces + 255) / 256)), dim3(256), 0, s, a, ids, n_frames, idx, sim);
+}
+
+void launch_track_gate(const TrackGateArgs &a, const TrackStreamIds &ids, hipStream_t s) {
+    if (a.n_frames <= 0) return;
+    hipLaunchKernelGGL(track_gate_kernel, dim3(1), dim3(64 * GATE_WAVES), 0, s, a, ids);
+}
+
+void launch_track_gate_scatter(const TrackScatterArgs &a, hipStream_t s) {
+    if (a.F <= 0) return;
+    hipLaunchKernelGGL(track_gate_scatter_kernel, dim3((unsigned)((a.F + WAVES - 1) / WAVES)), dim3(64 * WAVES), 0, s, a);
 }
 
 void launch_track_reset(const TrackArgs &a, int n_streams, int stream, hipStream_t s) {

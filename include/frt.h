@@ -946,6 +946,80 @@ int frt_pipeline_run_tracked(frt_pipeline *p, frt_tracker *t, const uint8_t *fra
                              frt_face_result *results, frt_track_result *tracks_out, float *embeds_out /* may be NULL */,
                              float *templates_out /* may be NULL */);
 
+/* Gate: skip the recogniser for the faces a confirmed track follows.  frt_pipeline_run_tracked embeds every face of every frame; on a video
+ * stream a face that sat on a confirmed track one frame ago and overlaps its old box is the same person, and the track already carries a
+ * template and an identity.  The gate runs between the detector and the recogniser and sorts the detections into those the recogniser must
+ * see (EMBED) and those the tracker can follow by their boxes alone (FOLLOW).  The reference has no tracker, so the rules are fixed here, to
+ * the integer (tests/track_gate_ref.py restates them in numpy).
+ *   Options, frt_track_gate_options: refresh >= 1, min_embeds >= 1, skip_iou in (0, 1]; anything else, a NaN included, is FRT_ERR_INVALID
+ *     before any device work.  There are NO defaults and no recommended values - nobody has measured these on real video with this library
+ *     -: a NULL options pointer is FRT_ERR_INVALID.
+ *   Per frame f of stream s; the gate reads the tracker's state AT ENTRY and writes no state.
+ *     G1. detection d is PRESENT iff d < n_boxes[f] (when n_boxes is given) and box.score > 0 - step 1 of the update.
+ *     G2. Peek - step 2 of the update, exactly, by overlap only (the appearance settings are ignored): present detections in slot order;
+ *         candidates are the tracks live at entry and not yet taken by an earlier detection of this peek; ovr is the same float32 IoU; the
+ *         largest ovr wins, the lowest slot among equals; a match needs ovr >= iou_threshold.  -> peek[d] (a slot, or -1) and ovr[d].
+ *     G3. d is FOLLOWED iff peek[d] = t >= 0 and track t at entry has hits >= min_hits, n_embeds >= min_embeds, ovr[d] >= skip_iou and
+ *         (hits + 1) % refresh != 0.  Every other present detection is EMBED; refresh == 1 therefore embeds everything.
+ *     G4. One frt_track_gate per face slot: decision (0 absent, 1 EMBED, 2 FOLLOW); slot / ovr, the peek's, or -1 / 0 without a match; why,
+ *         set only for EMBED, the OR of FRT_TRACK_GATE_NO_TRACK (no match), _UNCONFIRMED (hits < min_hits), _FEW_EMBEDS (n_embeds <
+ *         min_embeds), _LOW_OVERLAP (ovr < skip_iou) and _REFRESH ((hits + 1) % refresh == 0: at refresh == 1 every matched detection
+ *         carries it).  An absent slot is all zero with slot = -1.
+ *   The work list: the face indices f * max_faces + d of the EMBED detections, ascending; n_embed of them; every entry behind them is -1.
+ *     pass_count[j] = min(max_batch, max(0, n_embed - j * max_batch)) for j < ceil(n_frames * max_faces / max_batch): the faces of
+ *     recogniser pass j, as frt_select_faces writes it.
+ *   The peek is a PREDICTION, not a promise.  With appearance off it IS the update's step 2: the update that follows associates every
+ *     present detection exactly as the peek said.  With appearance on, a FOLLOWED detection reaches the update with valid == 0: its S is
+ *     never DEFINED, so it is never vetoed and never re-attached by appearance, and the update does with it what it always does with such a
+ *     detection; the embedded ones take part in 2a / 2b as always, and the update - not the gate - decides.
+ *   Staleness: a FOLLOWED face gets no frame-level match - its record has valid = 0, match_idx = -1, match_sim = 0 and keeps its box -; its
+ *     identity is the track's, from the unchanged step 7, which searches the template rows on every call: a gallery edit still reaches a
+ *     followed track in the next call.
+ *   How much time a gated call saves depends on the stream; DESIGN 3.40 has what was measured. */
+typedef struct frt_track_gate_options {
+    int32_t refresh;    /* >= 1: a followed track is embedded again whenever (hits + 1) % refresh == 0; 1 embeds everything */
+    int32_t min_embeds; /* >= 1: embeddings a track must hold before its faces may be followed                              */
+    float skip_iou;     /* (0, 1]: overlap with the track's box below which the face is embedded                            */
+} frt_track_gate_options;
+#define FRT_TRACK_GATE_ABSENT 0
+#define FRT_TRACK_GATE_EMBED 1
+#define FRT_TRACK_GATE_FOLLOW 2
+#define FRT_TRACK_GATE_NO_TRACK 1
+#define FRT_TRACK_GATE_UNCONFIRMED 2
+#define FRT_TRACK_GATE_FEW_EMBEDS 4
+#define FRT_TRACK_GATE_LOW_OVERLAP 8
+#define FRT_TRACK_GATE_REFRESH 16
+typedef struct frt_track_gate {
+    int32_t decision; /* FRT_TRACK_GATE_ABSENT / _EMBED / _FOLLOW */
+    int32_t slot;     /* the peek's slot, or -1 */
+    float ovr;        /* the peek's overlap, or 0 */
+    int32_t why;      /* EMBED only: the OR of the reasons above; else 0 */
+} frt_track_gate; /* 16 bytes */
+/* The gate alone, asynchronous on hip_stream behind the tracker's last queued update: boxes_dev frt_bbox [n_frames][max_faces], n_boxes_dev
+ * int32 [n_frames] (may be NULL), stream_ids on the host (may be NULL) -> gate_dev frt_track_gate [n_frames][max_faces], list_dev int32
+ * [n_frames * max_faces], n_embed_dev int32 [1], pass_count_dev int32 [ceil(n_frames * max_faces / max_batch)].  max_batch >= 1.  The
+ * checks are the update's, all before any device work; a refused call writes nothing. */
+int frt_tracker_gate_dev(frt_tracker *t, const frt_track_gate_options *options, const void *boxes_dev, const void *n_boxes_dev, int n_frames,
+                         const int32_t *stream_ids /* host, may be NULL */, void *gate_dev, void *list_dev, void *n_embed_dev,
+                         void *pass_count_dev, int max_batch, void *hip_stream);
+/* the same behind host pointers: upload, gate, download, one synchronisation */
+int frt_tracker_gate(frt_tracker *t, const frt_track_gate_options *options, const frt_bbox *boxes, const int32_t *n_boxes /* may be NULL */,
+                     int n_frames, const int32_t *stream_ids, frt_track_gate *gate_out, int32_t *list_out, int32_t *n_embed_out,
+                     int32_t *pass_count_out, int max_batch);
+/* frt_pipeline_run_tracked with the gate in front of the recogniser: upload, detector, gate, ONE host read of n_embed, gather crop (or
+ * alignment, frt_pipeline_set_align) + recogniser over the n_embed listed faces in passes of the recogniser's max_batch, one top-1 search
+ * of the compact rows (none when n_embed == 0 or there is no gallery), scatter into face slots, the records, the tracker's update with the
+ * pipeline's matcher, the downloads, one synchronisation.  results / tracks_out / gate_out (may be NULL) [n_frames][max_faces], embeds_out
+ * / templates_out [n_frames][max_faces][512] (may be NULL; a slot that was not embedded has a zero embedding row), crops_out
+ * [*n_embed_out][112][112][3] (may be NULL; room for n_frames * max_faces crops) in LIST order.  The embeddings are those of passes cut from
+ * the compact list: the same faces as frt_pipeline_run_tracked's, not bit for bit its embeddings.  Serial under the pipeline's run mutex
+ * with whatever a pairing mode holds flushed first, like frt_pipeline_run_photo_tiled.  The checks are frt_pipeline_run_tracked's and the
+ * options', all before any device work; a refused call writes nothing. */
+int frt_pipeline_run_tracked_gated(frt_pipeline *p, frt_tracker *t, const frt_track_gate_options *options, const uint8_t *frames, int n_frames,
+                                   const int32_t *stream_ids, frt_face_result *results, frt_track_result *tracks_out,
+                                   frt_track_gate *gate_out /* may be NULL */, float *embeds_out /* may be NULL */,
+                                   float *templates_out /* may be NULL */, uint8_t *crops_out /* may be NULL */, int32_t *n_embed_out);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Face quality: is a face good enough to use?  Every route above takes pixels to identities and none asks.  /insert/face applies the
  * "exactly one face" rule and nothing else, so a 20-pixel, blurred or blown-out face is embedded and appended to the live gallery, where it

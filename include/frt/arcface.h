@@ -338,6 +338,41 @@ class ArcFaceIR50 : public ArcFaceIR50Statics<> {
         }
         return res;
     }
+    // trackFaces with the gate in front of the recogniser (include/frt.h "Gate"): a face that a confirmed track follows is neither cropped
+    // nor embedded nor matched - its record keeps the box and has valid 0 -, and its name is its track's as above.  gate receives one record
+    // per face slot (embedded, and why, or followed); nEmbed (may be null) how many faces went through the recogniser.  The options have no
+    // defaults.
+    template <class Detector>
+    std::vector<frt_face_result> trackFaces(Detector &detector, FaceTracker &tracker, const frt_track_gate_options &options, const std::vector<cv::Mat> &frames,
+                                            const std::vector<int> &streamIds, std::vector<frt_track_result> &tracks, std::vector<frt_track_gate> &gate,
+                                            std::vector<std::string> &names, std::vector<float> *sims = nullptr, int *nEmbed = nullptr) {
+        photoPipe(detector);
+        const size_t n = frames.size(), slots = n * (size_t)tracker.maxFaces(), rowBytes = (size_t)m_frameWidth * 3;
+        std::vector<uint8_t> packed(n * (size_t)m_frameHeight * rowBytes);
+        for (size_t i = 0; i < n; ++i) {
+            if (frames[i].rows != m_frameHeight || frames[i].cols != m_frameWidth) throw std::logic_error("trackFaces: a frame is not frameHeight x frameWidth");
+            for (int r = 0; r < m_frameHeight; ++r)
+                std::memcpy(&packed[(i * (size_t)m_frameHeight + (size_t)r) * rowBytes], frames[i].data + (size_t)r * (size_t)frames[i].step, rowBytes);
+        }
+        std::vector<frt_face_result> res(slots);
+        tracks.assign(slots, frt_track_result());
+        gate.assign(slots, frt_track_gate());
+        const std::vector<int32_t> ids(streamIds.begin(), streamIds.end());
+        int32_t embedded = 0;
+        checkFrtStatus(frt_pipeline_run_tracked_gated(m_photoPipe, tracker.handle(), &options, packed.data(), (int)n, ids.empty() ? nullptr : ids.data(),
+                                                      res.data(), tracks.data(), gate.data(), nullptr, nullptr, nullptr, &embedded));
+        if (nEmbed) *nEmbed = embedded;
+        names.assign(slots, std::string());
+        if (sims) sims->assign(slots, 0.f);
+        for (size_t i = 0; i < slots; ++i) {
+            const frt_track_result &t = tracks[i];
+            if (t.match_idx >= 0 && (size_t)t.match_idx < classNames.size()) {
+                names[i] = classNames[(size_t)t.match_idx];
+                if (sims) (*sims)[i] = t.match_sim;
+            }
+        }
+        return res;
+    }
     // every row of that name, as /delete/user removes every face of the user; the rows behind them close up in order (the order a
     // /reload would read them in: src/db.cpp:316-346).  Returns how many there were.
     int removeClass(const std::string &className) {

@@ -52,6 +52,24 @@ class FaceTracker {
     // FRT_TRACK_MIN_SIM_OFF switch either off; both are off until set.  No threshold is recommended: measure on your own faces.
     void setAppearance(float reidThreshold, float iouMinSim) { checkFrtStatus(frt_tracker_set_appearance(h_, reidThreshold, iouMinSim)); }
     void getAppearance(float &reidThreshold, float &iouMinSim) { checkFrtStatus(frt_tracker_get_appearance(h_, &reidThreshold, &iouMinSim)); }
+    // The gate alone (include/frt.h "Gate"): which of these boxes [nFrames x maxFaces] - nBoxes (may be empty) the detector's counts per
+    // frame - must go through the recogniser and which a confirmed track follows.  Returns one record per face slot; list receives the face
+    // indices to embed, ascending (list.size() is n_embed), passCount (may be null) the faces of each recogniser pass of maxBatch.  Reads the
+    // state and writes none.  The options have no defaults: nobody has measured them on real video with this library.
+    std::vector<frt_track_gate> gate(const std::vector<frt_bbox> &boxes, const frt_track_gate_options &options, std::vector<int> &list,
+                                     const std::vector<int> &streamIds = std::vector<int>(), const std::vector<int> &nBoxes = std::vector<int>(),
+                                     int maxBatch = 128, std::vector<int> *passCount = nullptr) {
+        const int nFrames = (int)(boxes.size() / (size_t)maxFaces_);
+        std::vector<frt_track_gate> out(boxes.size());
+        std::vector<int32_t> l(boxes.size() ? boxes.size() : 1), pc(maxBatch > 0 ? (boxes.size() + (size_t)maxBatch - 1) / (size_t)maxBatch + 1 : 1);
+        const std::vector<int32_t> ids(streamIds.begin(), streamIds.end()), nb(nBoxes.begin(), nBoxes.end());
+        int32_t nEmbed = 0;
+        checkFrtStatus(frt_tracker_gate(h_, &options, boxes.data(), nb.empty() ? nullptr : nb.data(), nFrames, ids.empty() ? nullptr : ids.data(),
+                                        out.data(), l.data(), &nEmbed, pc.data(), maxBatch));
+        list.assign(l.begin(), l.begin() + nEmbed);
+        if (passCount) passCount->assign(pc.begin(), pc.begin() + (long)((boxes.size() + (size_t)maxBatch - 1) / (size_t)maxBatch));
+        return out;
+    }
     // every slot of one stream, live or not; counters (may be null) <- next_id, tick, dropped
     std::vector<frt_track_state> tracks(int stream, int counters[3] = nullptr, std::vector<float> *sums = nullptr) {
         std::vector<frt_track_state> out((size_t)maxTracks_);
