@@ -16,6 +16,7 @@ The directory name is not an importable identifier; load it with::
 import ctypes
 import os
 import sys
+import weakref
 
 import numpy as np
 
@@ -196,6 +197,14 @@ ABI = {
     "frt_enrol_select_gated_dev": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "frt_pipeline_run_quality": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "frt_pipeline_enrol_images_gated": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), ctypes.POINTER(_i)]),
+    "frt_sightings_create": (_i, [_vp, _i, _vp, ctypes.POINTER(_vp)]),
+    "frt_sightings_destroy": (None, [_vp]),
+    "frt_sightings_update_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "frt_sightings_update": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "frt_sightings_close": (_i, [_vp, _i]),
+    "frt_sightings_drain": (_i, [_vp, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(_i), _vp]),
+    "frt_sightings_open": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
+    "frt_pipeline_run_sighted": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "frt_profile_enable": (_i, [_i]),
     "frt_profile_collect": (_i, [_vp, _sz, _vp, _vp, _i]),
 }
@@ -1349,6 +1358,8 @@ class Tracker:
         _check(lib.frt_tracker_reset(self._h, int(stream)))
 
     def close(self):
+        for book in list(getattr(self, "_books", ())):  # the books borrow this tracker: they go first
+            book.destroy()
         if self._h:
             lib.frt_tracker_destroy(self._h)
             self._h = _vp()
@@ -1356,6 +1367,114 @@ class Tracker:
     def __del__(self):
         try:
             self.close()
+        except Exception:
+            pass
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# sighting book: one record per finished track, with its best shot (include/frt.h "Sightings")
+# ----------------------------------------------------------------------------------------------------------------------
+SIGHTING_DTYPE = np.dtype([("stream", "<i4"), ("track_id", "<i4"), ("first_tick", "<i4"), ("last_tick", "<i4"), ("close_tick", "<i4"),
+                           ("reason", "<i4"), ("hits", "<i4"), ("n_embeds", "<i4"), ("confirmed", "<i4"), ("match_idx", "<i4"), ("match_sim", "<f4"),
+                           ("n_shots", "<i4"), ("best_tick", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("x2", "<i4"), ("y2", "<i4"), ("score", "<f4"),
+                           ("best_sharpness", "<f4"), ("best_luma_var", "<f4"), ("best_mean", "<f4"), ("best_flags", "<u4"), ("best_size", "<i4"),
+                           ("reserved", "<i4")])  # == frt_sighting; x1 .. score: best_box
+SHOT_RANK_SHARPNESS, SHOT_RANK_SIZE, SHOT_RANK_SCORE = range(3)
+SIGHTING_EXPIRED, SIGHTING_REPLACED, SIGHTING_CLOSED = 1, 2, 3  # frt_sighting.reason; 0: open
+assert SIGHTING_DTYPE.itemsize == 96
+
+
+class SightingOptions(ctypes.Structure):  # == frt_sighting_options
+    _fields_ = [("rank", ctypes.c_int32), ("min_hits", ctypes.c_int32), ("keep_crops", ctypes.c_int32)]
+
+
+class Sightings:
+    """The sighting book of one :class:`Tracker` (which it borrows: close the book first).  It shadows every live track, keeps the track's
+    best shot - ``rank``: by sharpness, size or detector score, an unflagged shot before a flagged one - and queues one SIGHTING_DTYPE record,
+    with the best shot's embedding, the track's template and (``keep_crops``) the crop, when the track ends.  One ``update`` follows one
+    tracker update of the same frames and stream ids."""
+
+    def __init__(self, tracker, capacity, rank=SHOT_RANK_SHARPNESS, min_hits=1, keep_crops=True):
+        self._h = _vp()
+        self.tracker, self.capacity, self.keep_crops = tracker, int(capacity), bool(keep_crops)
+        opt = SightingOptions(int(rank), int(min_hits), int(keep_crops))
+        _check(lib.frt_sightings_create(tracker._h, self.capacity, ctypes.addressof(opt), ctypes.byref(self._h)))
+        tracker.__dict__.setdefault("_books", weakref.WeakSet()).add(self)  # Tracker.close destroys its books before itself
+
+    def update(self, results, tracks, embeds, quality, templates=None, crops=None, stream_ids=None):
+        """Host arrays of one tracker update: results RESULT_DTYPE, tracks TRACK_DTYPE, quality QUALITY_DTYPE [n * max_faces]; embeds,
+        templates (or None) float32 [n * max_faces, dim]; crops u8 [n * max_faces, 112, 112, 3], required iff the book keeps crops."""
+        t = self.tracker
+        results = np.ascontiguousarray(results, RESULT_DTYPE).reshape(-1)
+        if results.size == 0 or results.size % t.max_faces:
+            raise ValueError("results must hold max_faces records per frame")
+        F, n = results.size, results.size // t.max_faces
+        tracks = np.ascontiguousarray(tracks, TRACK_DTYPE).reshape(-1)
+        quality = np.ascontiguousarray(quality, QUALITY_DTYPE).reshape(-1)
+        embeds = np.ascontiguousarray(embeds, np.float32)
+        if tracks.size != F or quality.size != F or embeds.size != F * t.dim:
+            raise ValueError("tracks, quality [n * max_faces] and embeds [n * max_faces, dim] must match results")
+        if templates is not None:
+            templates = np.ascontiguousarray(templates, np.float32)
+            if templates.size != F * t.dim:
+                raise ValueError("templates must be [n * max_faces, dim]")
+        if crops is not None:
+            crops = np.ascontiguousarray(crops, np.uint8)
+            if crops.size != F * 112 * 112 * 3:
+                raise ValueError("crops must be [n * max_faces, 112, 112, 3]")
+        ids = _stream_ids(stream_ids, n)
+        _check(lib.frt_sightings_update(self._h, _ptr(results), _ptr(tracks), _ptr(embeds), _ptr(templates), _ptr(quality), _ptr(crops), n, _ptr(ids)))
+
+    def updateDev(self, results_ptr, tracks_ptr, embeds_ptr, quality_ptr, n_frames, templates_ptr=None, crops_ptr=None, stream_ids=None, hip_stream=None):
+        """Asynchronous on ``hip_stream`` behind the tracker's last queued update; the pointers are raw device addresses."""
+        ids = _stream_ids(stream_ids, int(n_frames))
+        _check(lib.frt_sightings_update_dev(self._h, _vp(results_ptr), _vp(tracks_ptr), _vp(embeds_ptr), _vp(templates_ptr) if templates_ptr else None,
+                                            _vp(quality_ptr), _vp(crops_ptr) if crops_ptr else None, int(n_frames), _ptr(ids),
+                                            _vp(hip_stream) if hip_stream else None))
+
+    def close(self, stream=-1):
+        """End every open entry of ``stream`` (-1: of every stream) with reason SIGHTING_CLOSED: the end of a stream, or before
+        ``Tracker.reset``.  (``destroy`` frees the book.)"""
+        _check(lib.frt_sightings_close(self._h, int(stream)))
+
+    def drain(self, max_out, want_embeds=True, want_templates=True, want_crops=None):
+        """The oldest ``min(queued, max_out)`` sightings, removed from the queue -> (records SIGHTING_DTYPE [n], best embeddings [n, dim] or
+        None, templates [n, dim] or None, crops u8 [n, 112, 112, 3] or None, counters dict(queued - before the call -, overflowed, discarded,
+        closed))."""
+        max_out, D = int(max_out), self.tracker.dim
+        want_crops = self.keep_crops if want_crops is None else bool(want_crops)
+        cap = max(max_out, 1)
+        rec = np.zeros(cap, SIGHTING_DTYPE)
+        emb = np.zeros((cap, D), np.float32) if want_embeds else None
+        tpl = np.zeros((cap, D), np.float32) if want_templates else None
+        crops = np.zeros((cap, 112, 112, 3), np.uint8) if want_crops else None
+        n, cnt = ctypes.c_int(0), np.zeros(4, np.int32)
+        _check(lib.frt_sightings_drain(self._h, max_out, _ptr(rec), _ptr(crops), _ptr(emb), _ptr(tpl), ctypes.byref(n), _ptr(cnt)))
+        k = n.value
+        counters = dict(queued=int(cnt[0]), overflowed=int(cnt[1]), discarded=int(cnt[2]), closed=int(cnt[3]))
+        return (rec[:k].copy(), emb[:k].copy() if want_embeds else None, tpl[:k].copy() if want_templates else None,
+                crops[:k].copy() if want_crops else None, counters)
+
+    def open(self, stream, want_embeds=True, want_templates=True, want_crops=None):
+        """The open entries of one stream -> (records SIGHTING_DTYPE [max_tracks], a free slot all zero, best embeddings, templates
+        [max_tracks, dim] or None, crops [max_tracks, 112, 112, 3] or None)."""
+        T, D = self.tracker.max_tracks, self.tracker.dim
+        want_crops = self.keep_crops if want_crops is None else bool(want_crops)
+        rec = np.zeros(T, SIGHTING_DTYPE)
+        emb = np.zeros((T, D), np.float32) if want_embeds else None
+        tpl = np.zeros((T, D), np.float32) if want_templates else None
+        crops = np.zeros((T, 112, 112, 3), np.uint8) if want_crops else None
+        _check(lib.frt_sightings_open(self._h, int(stream), _ptr(rec), _ptr(emb), _ptr(tpl), _ptr(crops)))
+        return rec, emb, tpl, crops
+
+    def destroy(self):
+        if self._h:
+            lib.frt_sightings_destroy(self._h)
+            self._h = _vp()
+
+    def __del__(self):
+        try:
+            self.destroy()
         except Exception:
             pass
 
@@ -1458,6 +1577,23 @@ class Pipeline:
                                                   _ptr(emb), _ptr(tpl), _ptr(crops), ctypes.addressof(ne)))
         out = (res, emb, trk, tpl, ne.value)
         return out + ((gate,) if want_gate else ()) + ((crops[:ne.value].copy(),) if want_crops else ())
+
+    def runSighted(self, tracker, book, frames, quality=None, stream_ids=None, want_embeds=True, want_quality=True):
+        """``runTracked`` and ``runQuality`` in one call with a :class:`Sightings` book behind them on the pipeline stream
+        (frt_pipeline_run_sighted) -> (records, embeddings or None, track records - exactly ``runTracked``'s -, QUALITY_DTYPE [n * max_faces]
+        or None - exactly ``runQuality``'s).  The finished tracks wait in the book: ``book.drain``."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n = frames.shape[0]
+        if frames.shape[1:] != (self.det.frameHeight, self.det.frameWidth, 3):
+            raise ValueError("runSighted: frames must be [n, frameHeight, frameWidth, 3]")
+        ids = _stream_ids(stream_ids, n)
+        res = np.zeros(n * self.max_faces, RESULT_DTYPE)
+        emb = np.zeros((n * self.max_faces, 512), np.float32) if want_embeds else None
+        trk = np.zeros((n, self.max_faces), TRACK_DTYPE)
+        qual = np.zeros(n * self.max_faces, QUALITY_DTYPE) if want_quality else None
+        _check(lib.frt_pipeline_run_sighted(self._h, tracker._h, book._h, _quality_options(quality), _ptr(frames), n, _ptr(ids), _ptr(res), _ptr(trk),
+                                            _ptr(qual), _ptr(emb)))
+        return res, emb, trk, qual
 
     def runQuality(self, frames, options=None, want_embeds=True, want_crops=False):
         """``run`` that also scores every face slot on the pipeline stream (frt_pipeline_run_quality) -> (records, embeddings or None -

@@ -647,3 +647,40 @@ struct TrackScatterArgs {
     float *sim;
 };
 void launch_track_gate_scatter(const TrackScatterArgs &a, hipStream_t s);
+
+// ---------------------------------------------------------------- sighting book (kernels_sightings.hip; frt_sightings.cpp, include/frt.h "Sightings")
+constexpr int FRT_SIGHTING_CROP_BYTES = 112 * 112 * 3;
+// What one entry (an open one of a tracker slot, or a queue row) has to have moved, written by the plan kernels and read by the copy kernel
+struct SightingJob {
+    int32_t entry;  // the row of the open entry, stream * max_tracks + slot
+    int32_t qrow;   // -1: the entry did not end; -2: it ended and nothing is queued; >= 0: its payload goes to this queue row first
+    int32_t face;   // -1, or the face slot f * max_faces + d that was observed: its template row is taken, and with `replace` its embedding and crop
+    int32_t replace;
+};
+struct SightingArgs {
+    // ---- the book: rows 0 .. n_open - 1 are the open entries [n_streams][max_tracks], rows n_open .. n_open + capacity - 1 the queue
+    frt_sighting *records;
+    float *best_embeds, *templates;  // [rows][dim]
+    uint8_t *crops;                  // [rows][112][112][3], or null (keep_crops 0)
+    uint32_t *best_key;              // [n_open]: the bits of the best shot's metric
+    int32_t *state;                  // [4]: rows queued (those the host has taken and not yet reported included), overflowed, discarded, closed
+    SightingJob *jobs;               // [n_open]
+    int n_open, capacity, head, taken;  // head: the queue row of the oldest sighting; taken: rows drained since the last launch
+    int max_tracks, max_faces, dim, rank, min_hits;
+    // ---- the tracker's state, read only, as its update left it
+    const frt_track_state *slots;
+    const int32_t *counters;
+    // ---- the call
+    const frt_face_result *results;
+    const frt_track_result *tracks;
+    const float *embeds, *call_templates;  // call_templates may be null
+    const struct frt_face_quality *quality;
+    const uint8_t *call_crops;             // null iff crops is null
+};
+// S1 - S3 of one update: the records, the queue rows and the job list, in one launch of one workgroup; then the payloads, one workgroup per
+// entry of the call's streams.  Both on s, in this order.
+void launch_sightings_plan(const SightingArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s);
+void launch_sightings_copy(const SightingArgs &a, int n_jobs, hipStream_t s);
+// frt_sightings_close: ends every open entry of `stream` (-1: of each of n_streams) with reason CLOSED; jobs [n_streams * max_tracks] or
+// [max_tracks], to be followed by launch_sightings_copy over as many
+void launch_sightings_close(const SightingArgs &a, int n_streams, int stream, hipStream_t s);

@@ -183,6 +183,9 @@ void destroy(frt_tracker *t) {
 
 }  // namespace
 
+void tracker_ensure_state(frt_tracker *t) { ensure_state(t); }
+void tracker_join_updates(frt_tracker *t) { join_updates(t); }
+
 extern "C" {
 
 int frt_tracker_create(int n_streams, int max_tracks, int max_faces, int dim, const frt_track_options *options, int device, frt_tracker **out) {

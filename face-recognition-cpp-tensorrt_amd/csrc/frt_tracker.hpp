@@ -78,6 +78,10 @@ struct frt_tracker {
 TrackStreamIds tracker_check_ids(const frt_tracker *t, int n_frames, const int32_t *stream_ids);
 //   the matcher: on the tracker's device, and dim columns when it has rows.  Takes m->mu for the look; m may be null
 void tracker_check_matcher(const frt_tracker *t, frt_matcher *m);
+// For the objects attached to a tracker (frt_sightings.cpp), with t->mu held: the stream, the events and the zeroed state exist after the
+// first; the second puts t->stream behind the last update queued on any stream
+void tracker_ensure_state(frt_tracker *t);
+void tracker_join_updates(frt_tracker *t);
 // One update, queued on s, with t->mu held and every argument checked: - appearance on, or assoc_dev given - the similarity kernel, the
 // update kernel, then - m with rows - the top-1 search of the template rows and the identity kernel.  Takes m->mu for the search.
 void tracker_update_locked(frt_tracker *t, frt_matcher *m, const frt_face_result *results_dev, const float *embeds_dev, int n_frames,

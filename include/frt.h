@@ -1117,6 +1117,106 @@ int frt_pipeline_enrol_images_gated(frt_pipeline *p, const frt_face_image *image
                                     float *embeds_out, int *first_row_out, int *n_enrolled_out);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Sightings: one event per finished track, with its best shot.  (The section follows the gate in subject; it stands behind "Face quality"
+ * because it uses that section's types.)  The tracker frees an expired slot by zeroing it (step 3) - id, hits, template and identity are
+ * gone in that launch -, and the crop the quality record measured is overwritten by the next call.  A sighting book is attached to ONE
+ * tracker and shadows every live track: it keeps each track's best shot - the crop, its embedding, the quality numbers - and, when the
+ * track ends, appends one frt_sighting to a FIFO on the device that the host drains when it likes.  The reference has no tracker, so the
+ * semantics are fixed here, to the integer (tests/sightings_ref.py restates them in numpy); every answer is compared for equality.
+ *   Memory: n_streams * max_tracks + capacity rows of 96 + 8 * dim (+ 37 632 with keep_crops) bytes, allocated by the first call that
+ *     passes its checks.  keep_crops = 0 is the setting for trackers with many streams: 1024 x 64 tracks with crops would be 2.5 GB.
+ *   Beside every record, open or queued, sit two or three payload rows: best_embed float [dim], template float [dim] and - keep_crops -
+ *     best_crop u8 [112][112][3].  The best_embed and best_crop rows of an entry with best_tick < 0 are zeros wherever they become visible.
+ *   One book update follows ONE tracker update of the same frames and the same stream_ids: it reads the tracker's slots and ticks as that
+ *     update left them.  This is a contract on the caller, not checked on the device (a slot index outside 0 .. max_tracks - 1 in tracks
+ *     is skipped).  tick of a frame of stream s is counters[s].tick - 1, the tick the tracker update just used.  Frames of one call belong
+ *     to pairwise distinct streams; they are independent except for the order of the queue.  Per frame f of stream s:
+ *     S1. Close, slots t ascending: an open entry E[s][t] ends iff the tracker's slot is not (live != 0 and id == E.track_id); reason is
+ *         FRT_SIGHTING_EXPIRED when live == 0, else _REPLACED (a birth of this same update took the slot step 3 had just freed);
+ *         close_tick = tick.  E.hits < min_hits: discarded += 1, nothing is queued.  Otherwise, with fewer than capacity rows queued, the
+ *         record and its payload rows are appended; else overflowed += 1 and the sighting is lost.  The entry is free in every case (all
+ *         zero, its payload rows zero).  Queue order: frames in call order, then slots ascending.
+ *     S2. Observe, detection slots d ascending with tracks[f][d].track_id >= 0, t = tracks[f][d].slot: a free entry opens - stream,
+ *         track_id, first_tick = tick - age + 1, close_tick = -1, reason = 0, n_shots = 0, best_tick = -1, the best fields zero -; then
+ *         last_tick = tick, and hits, n_embeds, confirmed, match_idx, match_sim are copied from tracks[f][d].  The template row becomes
+ *         templates[f][d] when the call has templates, else it is left as it is (zeros if it was never written).
+ *     S3. Best shot: a tracked detection is a CANDIDATE iff results[f][d].valid != 0 and quality[f][d].present != 0; n_shots += 1.  Its key
+ *         is (quality.flags == 0, metric), metric = quality.sharpness (rank FRT_SHOT_RANK_SHARPNESS), quality.size (_SIZE) or quality.score
+ *         (_SCORE).  It replaces the best shot iff best_tick < 0, or its pass bit is greater, or the pass bits are equal and its metric is
+ *         strictly greater than the metric the best shot was taken with (a float or int32 comparison: a tie keeps the earlier shot, a NaN
+ *         never replaces a shot that exists).  On replace: best_tick = tick, best_box = results.box, best_sharpness / _luma_var / _mean /
+ *         _flags / _size = the record's, best_embed = embeds[f][d], best_crop = crops[f][d].
+ *   The thresholds inside the quality options that produced `flags` are the caller's: THERE ARE NO RECOMMENDED THRESHOLDS ("Face quality").
+ *   Every argument check runs before any device work; a refused call writes nothing and changes no state.  Every call takes the tracker's
+ *     mutex; the book borrows the tracker and must be destroyed before it.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct frt_sightings frt_sightings;
+#define FRT_SHOT_RANK_SHARPNESS 0
+#define FRT_SHOT_RANK_SIZE 1
+#define FRT_SHOT_RANK_SCORE 2
+#define FRT_SIGHTING_EXPIRED 1
+#define FRT_SIGHTING_REPLACED 2
+#define FRT_SIGHTING_CLOSED 3
+typedef struct frt_sighting_options {
+    int32_t rank;        /* FRT_SHOT_RANK_SHARPNESS 0 | _SIZE 1 | _SCORE 2: what "best" means                  */
+    int32_t min_hits;    /* >= 1: a track that ends with fewer hits is discarded (counted), not queued         */
+    int32_t keep_crops;  /* 0 | 1: keep the u8 112x112x3 crop of the best shot (37 632 B per track and per queue row) */
+} frt_sighting_options;   /* NULL: {0, 1, 1}; anything outside its range is FRT_ERR_INVALID */
+typedef struct frt_sighting {       /* 96 bytes, every field 4 bytes, reserved words zero */
+    int32_t stream, track_id;
+    int32_t first_tick, last_tick;  /* the track's birth; the last update in which it had a detection */
+    int32_t close_tick;             /* the update that saw it end; -1 while open */
+    int32_t reason;                 /* 0 open, FRT_SIGHTING_EXPIRED 1, _REPLACED 2, _CLOSED 3 */
+    int32_t hits, n_embeds, confirmed, match_idx;  float match_sim;   /* as the tracker last reported them */
+    int32_t n_shots, best_tick;     /* candidates seen; tick of the best one, -1 without one */
+    frt_bbox best_box;
+    float best_sharpness, best_luma_var, best_mean;  uint32_t best_flags;  int32_t best_size;
+    int32_t reserved;
+} frt_sighting;
+
+/* capacity 1 .. 65 536 (else FRT_ERR_CAPACITY): the rows of the queue.  n_streams, max_tracks, max_faces, dim and the device are the
+ * tracker's.  Creation does no device work. */
+int frt_sightings_create(frt_tracker *t, int capacity, const frt_sighting_options *options /* may be NULL */, frt_sightings **out);
+void frt_sightings_destroy(frt_sightings *b);
+/* One book update (S1 - S3) behind the tracker update of the same frames: results_dev frt_face_result, tracks_dev frt_track_result,
+ * quality_dev struct frt_face_quality (8-byte aligned) [n_frames][max_faces]; embeds_dev, templates_dev (may be NULL) float
+ * [n_frames][max_faces][dim], 16-byte aligned; crops_dev u8 [n_frames][max_faces][112][112][3], 16-byte aligned as frt_face_quality_dev
+ * asks, required iff keep_crops (NULL without: FRT_ERR_INVALID either way round).  stream_ids on the host (may be NULL), checked as the
+ * tracker checks them.  Two launches, asynchronous on hip_stream behind the tracker's last queued update, no host synchronisation; the
+ * tracker's host forms then wait for it. */
+int frt_sightings_update_dev(frt_sightings *b, const void *results_dev, const void *tracks_dev, const void *embeds_dev, const void *templates_dev,
+                             const void *quality_dev, const void *crops_dev, int n_frames, const int32_t *stream_ids /* host, may be NULL */,
+                             void *hip_stream);
+/* the same behind host pointers: upload, update, one synchronisation */
+int frt_sightings_update(frt_sightings *b, const frt_face_result *results, const frt_track_result *tracks, const float *embeds,
+                         const float *templates /* may be NULL */, const struct frt_face_quality *quality, const uint8_t *crops, int n_frames,
+                         const int32_t *stream_ids);
+/* Ends every open entry of `stream` (-1: of every stream, ascending), slots ascending, with reason FRT_SIGHTING_CLOSED and close_tick =
+ * last_tick; S1's rules for min_hits and capacity apply.  Synchronous, like frt_tracker_reset.  Meant for the end of a stream, or to be
+ * called before frt_tracker_reset: without it the next update closes the entries as EXPIRED (REPLACED where a birth took the slot), with
+ * first_tick / last_tick from before the reset.  A track
+ * that goes on after a close opens a second sighting with the same track_id (first_tick is still the track's birth). */
+int frt_sightings_close(frt_sightings *b, int stream);
+/* The oldest min(queued, max_out) sightings in queue order, removed: records_out [max_out]; crops_out [max_out][112][112][3] (keep_crops
+ * only, else it must be NULL), embeds_out, templates_out float [max_out][dim] - all three may be NULL -; *n_out of them are returned, the
+ * rows of the output arrays at and behind *n_out are unspecified.  counters_out [4] (may be NULL): queued before the call, and the running
+ * totals overflowed, discarded, closed (every entry that ended: queued, overflowed or discarded).  max_out >= 1.  Runs after everything
+ * queued on the book; the rest keep their order and the room is free at once.  One synchronisation. */
+int frt_sightings_drain(frt_sightings *b, int max_out, frt_sighting *records_out, uint8_t *crops_out, float *embeds_out, float *templates_out,
+                        int *n_out, int32_t *counters_out);
+/* The open entries of one stream, every slot, a free one all zero: records_out [max_tracks]; best_embeds_out, templates_out
+ * [max_tracks][dim], crops_out [max_tracks][112][112][3] (keep_crops only) may be NULL.  One synchronisation. */
+int frt_sightings_open(frt_sightings *b, int stream, frt_sighting *records_out, float *best_embeds_out, float *templates_out, uint8_t *crops_out);
+/* frt_pipeline_run_tracked and frt_pipeline_run_quality in one call, with the book behind them, on the pipeline stream: the upload,
+ * frt_pipeline_run_dev with the crop buffer, the quality launch, the tracker update with templates, the book update; the downloads, one
+ * synchronisation.  results / tracks_out are frt_pipeline_run_tracked's and quality_out (may be NULL) frt_pipeline_run_quality's, bit for
+ * bit; embeds_out may be NULL.  The checks are those two calls' plus one: b must belong to t.  Serial under the run mutex with pairing
+ * flushed, like its parents.  frt_pipeline_run_tracked_gated has no sighted variant: a followed face has no crop to rank. */
+int frt_pipeline_run_sighted(frt_pipeline *p, frt_tracker *t, frt_sightings *b, const frt_quality_options *quality, const uint8_t *frames,
+                             int n_frames, const int32_t *stream_ids, frt_face_result *results, frt_track_result *tracks_out,
+                             struct frt_face_quality *quality_out /* may be NULL */, float *embeds_out /* may be NULL */);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Profiling hooks (HIP events on the library's own stream; used by bench.py for the roofline object).
  * ------------------------------------------------------------------------------------------------------------------ */
 /* kinds: 0 = off (drops the records), 1 = time every launch of the dominant kernel family (conv3x3 MFMA), 2 = time every stage,
