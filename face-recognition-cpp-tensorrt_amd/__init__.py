@@ -184,6 +184,9 @@ ABI = {
     "frt_tracker_update": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp]),
     "frt_tracker_set_appearance": (_i, [_vp, ctypes.c_float, ctypes.c_float]),
     "frt_tracker_get_appearance": (_i, [_vp, _vp, _vp]),
+    "frt_tracker_set_motion": (_i, [_vp, _i]),
+    "frt_tracker_get_motion": (_i, [_vp, _vp]),
+    "frt_tracker_motion": (_i, [_vp, _i, _vp, _vp]),
     "frt_tracker_update_assoc_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "frt_tracker_update_assoc": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "frt_tracker_tracks": (_i, [_vp, _i, _vp, _vp, _vp]),
@@ -1256,20 +1259,23 @@ class Tracker:
     of one frame per stream and returns, per face slot, a stable track id, the track's age / hits / confirmed flag and the identity of the
     track's running template (when a matcher - a ``MatMul`` - with rows is given).  ``reid_threshold`` / ``iou_min_sim`` (None: off) switch
     the appearance term on (include/frt.h "Appearance"): a lost face whose embedding is at least ``reid_threshold`` like a track's running sum
-    is re-attached to it, and an overlap match whose similarity is below ``iou_min_sim`` is refused."""
+    is re-attached to it, and an overlap match whose similarity is below ``iou_min_sim`` is refused.  ``motion_gain`` (None or 0: off; 1 ..
+    256) switches the constant-velocity term on (include/frt.h "Motion"): every overlap is then taken with the track's predicted box."""
 
     def __init__(self, n_streams, max_tracks=16, max_faces=4, dim=512, iou_threshold=0.3, max_missed=5, min_hits=3, decay=1.0, device=0,
-                 reid_threshold=None, iou_min_sim=None):
+                 reid_threshold=None, iou_min_sim=None, motion_gain=None):
         self._h = _vp()
         self.n_streams, self.max_tracks, self.max_faces, self.dim = int(n_streams), int(max_tracks), int(max_faces), int(dim)
         opt = TrackOptions(iou_threshold, max_missed, min_hits, decay)
         _check(lib.frt_tracker_create(self.n_streams, self.max_tracks, self.max_faces, self.dim, ctypes.addressof(opt), int(device), ctypes.byref(self._h)))
-        if reid_threshold is not None or iou_min_sim is not None:
-            try:
+        try:
+            if reid_threshold is not None or iou_min_sim is not None:
                 self.setAppearance(reid_threshold, iou_min_sim)
-            except Exception:
-                self.close()
-                raise
+            if motion_gain is not None:
+                self.setMotion(motion_gain)
+        except Exception:
+            self.close()
+            raise
 
     def setAppearance(self, reid_threshold=None, iou_min_sim=None):
         """``reid_threshold`` in (0, 1], ``iou_min_sim`` in [-1, 1]; None switches either off.  Takes effect with the next update."""
@@ -1281,6 +1287,25 @@ class Tracker:
         r, m = ctypes.c_float(), ctypes.c_float()
         _check(lib.frt_tracker_get_appearance(self._h, ctypes.addressof(r), ctypes.addressof(m)))
         return (None if r.value == TRACK_REID_OFF else r.value, None if m.value == TRACK_MIN_SIM_OFF else m.value)
+
+    def setMotion(self, gain=None):
+        """``gain`` 1 .. 256: the weight of a new measurement in a track's velocity, in 1/256; None or 0 switches motion off.  Takes effect
+        with the next update or gate; off -> on starts every velocity from zero."""
+        _check(lib.frt_tracker_set_motion(self._h, 0 if gain is None else int(gain)))
+
+    def getMotion(self):
+        """-> the gain, 0 where off"""
+        g = ctypes.c_int(-1)
+        _check(lib.frt_tracker_get_motion(self._h, ctypes.addressof(g)))
+        return g.value
+
+    def motion(self, stream):
+        """-> (vel int32 [max_tracks, 2]: (vx, vy) of every slot in 1/256 pixel per update, pred BBOX_DTYPE [max_tracks]: the box each slot
+        is compared with in the NEXT update, zeros for a free slot).  Refused while motion is off."""
+        vel = np.zeros((self.max_tracks, 2), np.int32)
+        pred = np.zeros(self.max_tracks, BBOX_DTYPE)
+        _check(lib.frt_tracker_motion(self._h, int(stream), _ptr(vel), _ptr(pred)))
+        return vel, pred
 
     def update(self, results, embeds, stream_ids=None, matcher=None, want_templates=True, want_assoc=False):
         """results RESULT_DTYPE [n * max_faces], embeds float32 [n * max_faces, dim] (host) -> (TRACK_DTYPE [n, max_faces], templates

@@ -601,12 +601,15 @@ struct TrackArgs {
     float *sim;                         // scratch S [n_frames][max_faces][max_tracks]; an entry is written iff its bit below is set
     unsigned long long *sim_defined;    // scratch [n_frames][max_faces]: bit t set iff S[f][d][t] is DEFINED
     frt_track_assoc *assoc;             // [n_frames][max_faces], or null
+    // ---- motion (include/frt.h "Motion"): read by the update kernel's MOTION instantiations only (and, for null, by the reset kernel)
+    int2 *vel;        // [n_streams][max_tracks]: (vx, vy) of the box centre in 1/256 pixel per update; null until a call with motion on needs it
+    int motion_gain;  // 0: off; 1 .. 256
 };
 // S and its defined bits of every detection x slot pair of the call, from the sums as they are BEFORE the update: one workgroup per detection
 void launch_track_similarity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, hipStream_t s);
 // steps 1 - 6 and 8 of an update, one workgroup per frame; the records leave with match_idx -1 / match_sim 0.  appearance: the instantiation
 // that reads a.sim / a.sim_defined (steps 2a, 2b; launch_track_similarity ran before it on s) and writes a.assoc; without it the launch is
-// the one of a tracker that has no appearance settings
+// the one of a tracker that has no appearance settings.  a.motion_gain > 0: the instantiation that reads and writes a.vel (M1 - M3)
 void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, bool appearance, hipStream_t s);
 // step 7 behind the top-1 search of the template rows: idx / sim [n_frames * max_faces] -> the tracked records with n_embeds > 0 and their slots
 void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, const int32_t *idx, const float *sim, hipStream_t s);
@@ -628,6 +631,9 @@ struct TrackGateArgs {
     int32_t *n_embed;         // [1]
     int32_t *pass_count;      // [ceil(n_frames * max_faces / max_batch)]
     int max_batch;            // >= 1
+    // ---- motion: read by the MOTION instantiation only, which the launch takes iff motion_gain > 0
+    const int2 *vel;  // [n_streams][max_tracks], read only
+    int motion_gain;
 };
 // G1 - G4 and the work list of one call in one launch of one workgroup; writes no tracker state
 void launch_track_gate(const TrackGateArgs &a, const TrackStreamIds &ids, hipStream_t s);

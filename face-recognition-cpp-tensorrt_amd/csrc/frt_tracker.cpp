@@ -1,5 +1,5 @@
 // Face tracker, host side (include/frt.h "Face tracker"): the object, the argument checks that run before any device work, the three
-// launches of an update (four with appearance on: the similarity kernel goes first), the appearance settings, the host forms and
+// launches of an update (four with appearance on: the similarity kernel goes first), the appearance and motion settings, the host forms and
 // frt_pipeline_run_tracked; the gate in front of the recogniser ("Gate": frt_tracker_gate / _gate_dev) and frt_pipeline_run_tracked_gated,
 // which strings detector, gate, gather crop, recogniser, search, scatter and the unchanged update together.  The kernels are in
 // kernels_track.hip (the gather crop and alignment in kernels_image.hip).
@@ -52,6 +52,7 @@ void tracker_update_locked(frt_tracker *t, frt_matcher *m, const frt_face_result
         t->sim_defined.reserve(F);
     }
     TrackArgs a = t->args();
+    if (a.motion_gain > 0 && !a.vel) raise(FRT_ERR_DEVICE, "tracker: motion is on and the velocities are not allocated");  // (ensure_state ran: cannot happen)
     a.results = results_dev;
     a.embeds = embeds_dev;
     a.tracks = tracks_dev;
@@ -131,17 +132,35 @@ void gate_locked(frt_tracker *t, const frt_track_gate_options &o, const frt_bbox
     a.n_embed = n_embed_dev;
     a.pass_count = pass_count_dev;
     a.max_batch = max_batch;
+    a.vel = t->vel.get();
+    a.motion_gain = t->motion_gain;
+    if (a.motion_gain > 0 && !a.vel) raise(FRT_ERR_DEVICE, "tracker gate: motion is on and the velocities are not allocated");
     if (t->pending) HIPCHK(hipStreamWaitEvent(s, t->ev_last, 0));  // the state the gate reads is the last queued update's
     ProfScope ps(2, "track_gate", (double)n_frames * t->max_faces, s);
     launch_track_gate(a, ids, s);
     HIPCHK(hipGetLastError());
 }
 
-// The stream, the events and the zeroed state, on the first call that passed its checks.  All of it or nothing: a failure leaves the
-// object as it was created
+// "Motion": the velocities, zeroed, on the first call that needs the state with motion on
+void ensure_vel(frt_tracker *t) {
+    if (t->motion_gain <= 0 || t->vel) return;
+    const size_t S = (size_t)t->n_streams * t->max_tracks;
+    try {
+        t->vel.reserve(S);
+        HIPCHK(hipMemsetAsync(t->vel.get(), 0, S * sizeof(int2), t->stream));
+        HIPCHK(hipStreamSynchronize(t->stream));
+    } catch (...) {
+        t->vel.reset();
+        throw;
+    }
+}
+
+// The stream, the events and the zeroed state (with motion on, the velocities among it), on the first call that passed its checks.  All
+// of it or nothing: a failure leaves the object without state, as it was created.  Where the state exists and only the velocities are
+// missing (motion was switched on later), a failure leaves the state as it was and the velocities missing; the next call tries again
 void ensure_state(frt_tracker *t) {
     use_device(t->device);
-    if (t->slots) return;
+    if (t->slots) return ensure_vel(t);
     try {
         if (!t->stream) HIPCHK(hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking));
         if (!t->ev_last) HIPCHK(hipEventCreateWithFlags(&t->ev_last, hipEventDisableTiming));
@@ -154,12 +173,20 @@ void ensure_state(frt_tracker *t) {
         HIPCHK(hipMemsetAsync(t->sums.get(), 0, S * t->dim * sizeof(float), t->stream));
         HIPCHK(hipMemsetAsync(t->counters.get(), 0, (size_t)t->n_streams * 4 * sizeof(int32_t), t->stream));
         HIPCHK(hipStreamSynchronize(t->stream));
+        ensure_vel(t);  // (drops the velocities itself where it fails)
     } catch (...) {
         t->slots.reset();
         t->sums.reset();
         t->counters.reset();
         throw;
     }
+}
+
+// M1 on the host, for frt_tracker_motion: kernels_track.hip's predicted_box
+int32_t clamp_i32(long long v) { return (int32_t)std::min<long long>(std::max<long long>(v, INT32_MIN), INT32_MAX); }
+long long motion_shift(int32_t v, int32_t missed) {
+    const long long lim = 1ll << 30;
+    return std::min(std::max((long long)v * ((long long)missed + 1) / 256, -lim), lim);  // C's division truncates toward zero
 }
 
 // `stream` behind the last update queued on any stream
@@ -230,6 +257,55 @@ int frt_tracker_get_appearance(frt_tracker *t, float *reid_threshold_out, float 
         std::lock_guard<std::mutex> lk(t->mu);
         *reid_threshold_out = t->reid_threshold;
         *iou_min_sim_out = t->iou_min_sim;
+    });
+}
+
+int frt_tracker_set_motion(frt_tracker *t, int gain) {
+    return guarded([&] {
+        if (!t) raise(FRT_ERR_INVALID, "tracker motion: null argument");
+        if (gain < 0 || gain > 256) raise(FRT_ERR_INVALID, "tracker motion: gain outside 0 .. 256");
+        std::lock_guard<std::mutex> lk(t->mu);
+        if (t->motion_gain == 0 && gain > 0 && t->vel) {  // off -> on: every velocity starts from zero, behind the last queued update
+            use_device(t->device);
+            join_updates(t);
+            HIPCHK(hipMemsetAsync(t->vel.get(), 0, (size_t)t->n_streams * t->max_tracks * sizeof(int2), t->stream));
+            sync_stream_spinning(t->stream);
+        }
+        t->motion_gain = gain;
+    });
+}
+
+int frt_tracker_get_motion(frt_tracker *t, int *gain_out) {
+    return guarded([&] {
+        if (!t || !gain_out) raise(FRT_ERR_INVALID, "tracker motion: null argument");
+        std::lock_guard<std::mutex> lk(t->mu);
+        *gain_out = t->motion_gain;
+    });
+}
+
+int frt_tracker_motion(frt_tracker *t, int stream, int32_t *vel_out, frt_bbox *pred_out) {
+    return guarded([&] {
+        if (!t || !vel_out) raise(FRT_ERR_INVALID, "tracker motion: null argument");
+        if (stream < 0 || stream >= t->n_streams) raise(FRT_ERR_INVALID, "tracker motion: stream outside 0 .. n_streams - 1");
+        std::lock_guard<std::mutex> lk(t->mu);
+        if (t->motion_gain == 0) raise(FRT_ERR_INVALID, "tracker motion: motion is off (frt_tracker_set_motion)");
+        ensure_state(t);
+        hipStream_t s = t->stream;
+        join_updates(t);
+        const size_t T = (size_t)t->max_tracks;
+        std::vector<frt_track_state> slots(pred_out ? T : 0);
+        HIPCHK(hipMemcpyAsync(vel_out, t->vel.get() + stream * T, T * sizeof(int2), hipMemcpyDeviceToHost, s));
+        if (pred_out) HIPCHK(hipMemcpyAsync(slots.data(), t->slots.get() + stream * T, T * sizeof(frt_track_state), hipMemcpyDeviceToHost, s));
+        sync_stream_spinning(s);
+        for (size_t i = 0; pred_out && i < T; ++i) {
+            const frt_track_state &st = slots[i];
+            frt_bbox b{};
+            if (st.live != 0) {
+                const long long sx = motion_shift(vel_out[2 * i], st.missed), sy = motion_shift(vel_out[2 * i + 1], st.missed);
+                b = frt_bbox{clamp_i32(st.box.x1 + sx), clamp_i32(st.box.y1 + sy), clamp_i32(st.box.x2 + sx), clamp_i32(st.box.y2 + sy), st.box.score};
+            }
+            pred_out[i] = b;
+        }
     });
 }
 

@@ -9,6 +9,7 @@ struct frt_tracker {
     int n_streams = 0, max_tracks = 0, max_faces = 0, dim = 0;
     frt_track_options opt{};
     float reid_threshold = FRT_TRACK_REID_OFF, iou_min_sim = FRT_TRACK_MIN_SIM_OFF;  // frt_tracker_set_appearance
+    int motion_gain = 0;  // frt_tracker_set_motion: 0 off, 1 .. 256
     std::mutex mu;
     hipStream_t stream = nullptr;   // the host forms, frt_tracker_tracks and frt_tracker_reset
     hipEvent_t ev_last = nullptr;   // end of the last update queued (on whichever stream): what `stream` waits for before it reads the state
@@ -19,6 +20,7 @@ struct frt_tracker {
     DevBuf<frt_track_state> slots;  // [n_streams][max_tracks]; a free slot is all zero
     DevBuf<float> sums;             // [n_streams][max_tracks][dim]; the rows of free slots are zero
     DevBuf<int32_t> counters;       // [n_streams][4]: next_id, tick, dropped, -
+    DevBuf<int2> vel;               // [n_streams][max_tracks]: "Motion"; allocated and zeroed by the first call that needs it with motion on
     // ---- scratch of an update with a matcher: the template rows when the caller takes none, and the search's answers
     DevBuf<float> q_templates, q_sim;
     DevBuf<int32_t> q_idx;
@@ -59,6 +61,8 @@ struct frt_tracker {
         a.min_hits = opt.min_hits;
         a.reid_threshold = reid_threshold;
         a.iou_min_sim = iou_min_sim;
+        a.vel = vel.get();
+        a.motion_gain = motion_gain;
         return a;
     }
     bool appearance_on() const { return reid_threshold != FRT_TRACK_REID_OFF || iou_min_sim != FRT_TRACK_MIN_SIM_OFF; }

@@ -41,6 +41,15 @@
 //   tested against max_tracks, a detection index is < max_faces <= 64; a list position is offset + bits below < the count <= n_frames *
 //   max_faces, the list's length; n_boxes[f] is only compared.  The scatter clamps the count it reads to 0 .. n_frames * max_faces, reads
 //   list[j] for j below it only and the compact rows at such j only; its own row index is tested against n_frames * max_faces.
+//
+// Motion (include/frt.h "Motion"; tests/track_motion_ref.py), only for a tracker that has it on: track_update_kernel<.., true>
+// and track_gate_kernel<true>.  Lane t of the wave that holds the slots loads its slot's (vx, vy) as one 8-byte load and computes its
+// predicted box once, in front of the detection walk (M1: the state at entry decides it); every iou() with a track's box takes that box
+// instead.  The lane that wins a detection applies M2 before it overwrites its box, expiry and birth zero the pair (M3), and the update
+// stores it beside the slot; the gate stores nothing.  Integers throughout: the one real division is an unsigned 32-bit one, the two / 256
+// are a 64-bit multiply and a sign-corrected shift.  The MOTION = false instantiations do not touch the vel / motion_gain arguments.
+//   Bounds: the velocity index is stream * max_tracks + lane with lane < max_tracks, the index of the slot it sits beside; the array holds
+//   n_streams * max_tracks pairs and exists whenever motion_gain > 0 (frt_tracker.cpp: ensure_state, checked again before the launch).
 #include "frt_kernels.h"
 
 namespace {
@@ -77,6 +86,35 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
         v = o > v ? o : v;
     }
     return v;
+}
+
+// ---- motion (include/frt.h "Motion"): integers throughout; tests/track_motion_ref.py restates them
+// tdiv(a, 256) for an int64: the arithmetic shift floors, so a negative a gets 255 first - truncation toward zero without a 64-bit divide
+__device__ __forceinline__ long long tdiv256(long long a) { return (a + ((a >> 63) & 255)) >> 8; }
+__device__ __forceinline__ int clamp_i32(long long v) { return (int)(v < -2147483648ll ? -2147483648ll : (v > 2147483647ll ? 2147483647ll : v)); }
+// M1: the box of a track live at entry, moved by its velocity times (missed + 1)
+__device__ __forceinline__ frt_bbox predicted_box(const frt_track_state &st, int vx, int vy) {
+    const long long k = (long long)st.missed + 1, lim = 1ll << 30;
+    long long sx = tdiv256((long long)vx * k), sy = tdiv256((long long)vy * k);
+    sx = sx < -lim ? -lim : (sx > lim ? lim : sx);
+    sy = sy < -lim ? -lim : (sy > lim ? lim : sy);
+    return frt_bbox{clamp_i32(st.box.x1 + sx), clamp_i32(st.box.y1 + sy), clamp_i32(st.box.x2 + sx), clamp_i32(st.box.y2 + sy), st.box.score};
+}
+// M2, one axis: dc2 the doubled centre displacement from the last measured box, g = missed at entry + 1 (as unsigned: 1 .. 2^31).  |dc * 128|
+// <= 2^29, so the one real division is an unsigned 32-bit one and its sign is put back
+__device__ __forceinline__ int matched_velocity(int v, long long dc2, unsigned g, bool first, int gain) {
+    const long long lim = 1ll << 22;
+    const int num = (int)(dc2 < -lim ? -lim : (dc2 > lim ? lim : dc2)) * 128;
+    const int q = (int)((unsigned)(num < 0 ? -num : num) / g), raw = num < 0 ? -q : q;
+    return first ? raw : v + (int)tdiv256((long long)(raw - v) * gain);
+}
+
+// M2 of the lane that won: st is its state at entry (the last measured box, hits, missed), det the detection it takes
+__device__ __forceinline__ int2 matched(int2 v, const frt_bbox &det, const frt_track_state &st, int gain) {
+    const unsigned g = (unsigned)st.missed + 1u;
+    const bool first = st.hits == 1;
+    return int2{matched_velocity(v.x, ((long long)det.x1 + det.x2) - ((long long)st.box.x1 + st.box.x2), g, first, gain),
+                matched_velocity(v.y, ((long long)det.y1 + det.y2) - ((long long)st.box.y1 + st.box.y2), g, first, gain)};
 }
 
 // columns k .. k + 3 of a row of dim floats, zeros past dim: the load is of column 0 there and a select drops it, so no lane branches
@@ -138,7 +176,7 @@ __global__ __launch_bounds__(64 * WAVES) void track_similarity_kernel(TrackArgs 
     }
 }
 
-template <bool APPEARANCE>
+template <bool APPEARANCE, bool MOTION>
 __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, TrackStreamIds ids) {
     __shared__ int s_slot[FRT_TRACK_MAX_SLOTS];  // detection -> slot; -1: untracked or absent
     __shared__ unsigned long long s_expired;     // slots freed by this update (their sums are zeroed before a birth's embedding lands)
@@ -158,6 +196,13 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
         frt_track_state st = {};
         if (mine) st = slots[lane];
         const bool live_entry = mine && st.live != 0;
+        // MOTION: lane t holds its slot's velocity and, from the state at entry, the box every overlap below is taken with (M1)
+        int2 v = {0, 0};
+        frt_bbox pred = st.box;
+        if constexpr (MOTION) {
+            if (mine) v = a.vel[(long)stream * T + lane];
+            if (live_entry) pred = predicted_box(st, v.x, v.y);
+        }
         bool taken = false;
         int my_slot = -1;        // lane d: the slot of detection d
         bool my_present = false;
@@ -180,7 +225,7 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
             }
             unsigned long long key = 0;  // (overlap bits, 63 - lane); an overlap that reaches the threshold is > 0, so 0 is "no candidate"
             if (live_entry && !taken && !(veto_on && defined && s < a.iou_min_sim)) {
-                const float ovr = iou(r.box, st.box);
+                const float ovr = iou(r.box, MOTION ? pred : st.box);
                 if (ovr >= a.iou_threshold) key = ((unsigned long long)__float_as_uint(ovr) << 32) | (unsigned)(63 - lane);
             }
             key = wave_max_u64(key);
@@ -192,6 +237,7 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
                 if (lane == d) my_assoc = frt_track_assoc{1, gap, __uint_as_float((unsigned)(key >> 32)), sim};
             }
             if (lane == win) {
+                if constexpr (MOTION) v = matched(v, r.box, st, a.motion_gain);
                 st.box = r.box;
                 st.hits += 1;
                 st.missed = 0;
@@ -215,12 +261,13 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
                 if (key == 0) continue;
                 const int win = 63 - (int)(key & 63);
                 const int gap = __shfl(st.missed, win);
-                const float ovr = __shfl(iou(r.box, st.box), win);
+                const float ovr = __shfl(iou(r.box, MOTION ? pred : st.box), win);
                 if (lane == d) {
                     my_assoc = frt_track_assoc{2, gap, ovr, __uint_as_float((unsigned)(key >> 32))};
                     my_slot = win;
                 }
                 if (lane == win) {
+                    if constexpr (MOTION) v = matched(v, r.box, st, a.motion_gain);
                     st.box = r.box;
                     st.hits += 1;
                     st.missed = 0;
@@ -234,6 +281,7 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
             st.missed += 1;
             if (st.missed > a.max_missed) {
                 st = frt_track_state{};
+                if constexpr (MOTION) v = int2{0, 0};  // M3
                 expired = true;
             }
         }
@@ -259,6 +307,7 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
                 st.n_embeds = 0;
                 st.match_idx = -1;
                 st.match_sim = 0.f;
+                if constexpr (MOTION) v = int2{0, 0};  // M3
             }
             ++next_id;
             if (lane == d) {
@@ -292,7 +341,10 @@ __global__ __launch_bounds__(64 * WAVES) void track_update_kernel(TrackArgs a, T
                     if (a.assoc) a.assoc[(long)f * MF + lane] = my_assoc;
             }
         }
-        if (mine) slots[lane] = st;
+        if (mine) {
+            slots[lane] = st;
+            if constexpr (MOTION) a.vel[(long)stream * T + lane] = v;
+        }
         if (lane == 0) {
             cnt[0] = next_id;
             cnt[1] = tick + 1;  // step 8
@@ -370,6 +422,7 @@ __global__ __launch_bounds__(64) void track_reset_kernel(TrackArgs a, int first_
     for (int k = lane * 4; k < a.dim; k += 256) *reinterpret_cast<floatx4 *>(sum + k) = floatx4{0.f, 0.f, 0.f, 0.f};
     if (lane == 0) {
         a.slots[(long)stream * a.max_tracks + t] = frt_track_state{};
+        if (a.vel) a.vel[(long)stream * a.max_tracks + t] = int2{0, 0};
         if (t == 0) a.counters[stream * 4 + 1] = a.counters[stream * 4 + 2] = 0;
     }
 }
@@ -377,6 +430,7 @@ __global__ __launch_bounds__(64) void track_reset_kernel(TrackArgs a, int first_
 constexpr int GATE_WAVES = 16;
 
 // one workgroup for the call (see the header comment)
+template <bool MOTION>
 __global__ __launch_bounds__(64 * GATE_WAVES) void track_gate_kernel(TrackGateArgs a, TrackStreamIds ids) {
     __shared__ unsigned long long s_mask[FRT_TRACK_MAX_FRAMES];  // the EMBED detections of a frame
     __shared__ int s_off[FRT_TRACK_MAX_FRAMES];                  // list entries in front of a frame's
@@ -391,8 +445,17 @@ __global__ __launch_bounds__(64 * GATE_WAVES) void track_gate_kernel(TrackGateAr
         const frt_bbox *boxes = a.boxes + (long)f * MF;
         const int n_present = a.n_boxes ? a.n_boxes[f] : MF;
         frt_track_state st = {};
-        if (lane < T) st = a.slots[(long)stream * T + lane];
+        int2 v = {0, 0};
+        if (lane < T) {
+            st = a.slots[(long)stream * T + lane];
+            // loaded beside the slot, not behind its `live`: a free slot's velocity is (0, 0) and is not used
+            if constexpr (MOTION) v = a.vel[(long)stream * T + lane];
+        }
         const bool live_entry = lane < T && st.live != 0;
+        frt_bbox pred = st.box;  // MOTION: M1's box, from the state at entry; the gate reads the velocities and writes none
+        if constexpr (MOTION) {
+            if (live_entry) pred = predicted_box(st, v.x, v.y);
+        }
         bool taken = false;
         frt_track_gate mine = {0, -1, 0.f, 0};  // lane d: the record of detection d
         // ---- G1, G2: the update's steps 1 and 2, overlap only
@@ -402,7 +465,7 @@ __global__ __launch_bounds__(64 * GATE_WAVES) void track_gate_kernel(TrackGateAr
             if (!(b.score > 0.f)) continue;  // (wave-uniform)
             unsigned long long key = 0;
             if (live_entry && !taken) {
-                const float ovr = iou(b, st.box);
+                const float ovr = iou(b, MOTION ? pred : st.box);
                 if (ovr >= a.iou_threshold) key = ((unsigned long long)__float_as_uint(ovr) << 32) | (unsigned)(63 - lane);
             }
             key = wave_max_u64(key);
@@ -502,10 +565,16 @@ void launch_track_similarity(const TrackArgs &a, const TrackStreamIds &ids, int 
 
 void launch_track_update(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, bool appearance, hipStream_t s) {
     if (n_frames <= 0) return;
-    if (appearance)
-        hipLaunchKernelGGL(track_update_kernel<true>, dim3((unsigned)n_frames), dim3(64 * WAVES), 0, s, a, ids);
+    const dim3 grid((unsigned)n_frames), block(64 * WAVES);
+    const bool motion = a.motion_gain > 0;
+    if (appearance && motion)
+        hipLaunchKernelGGL((track_update_kernel<true, true>), grid, block, 0, s, a, ids);
+    else if (appearance)
+        hipLaunchKernelGGL((track_update_kernel<true, false>), grid, block, 0, s, a, ids);
+    else if (motion)
+        hipLaunchKernelGGL((track_update_kernel<false, true>), grid, block, 0, s, a, ids);
     else
-        hipLaunchKernelGGL(track_update_kernel<false>, dim3((unsigned)n_frames), dim3(64 * WAVES), 0, s, a, ids);
+        hipLaunchKernelGGL((track_update_kernel<false, false>), grid, block, 0, s, a, ids);
 }
 
 void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_frames, const int32_t *idx, const float *sim, hipStream_t s) {
@@ -515,7 +584,10 @@ void launch_track_identity(const TrackArgs &a, const TrackStreamIds &ids, int n_
 
 void launch_track_gate(const TrackGateArgs &a, const TrackStreamIds &ids, hipStream_t s) {
     if (a.n_frames <= 0) return;
-    hipLaunchKernelGGL(track_gate_kernel, dim3(1), dim3(64 * GATE_WAVES), 0, s, a, ids);
+    if (a.motion_gain > 0)
+        hipLaunchKernelGGL(track_gate_kernel<true>, dim3(1), dim3(64 * GATE_WAVES), 0, s, a, ids);
+    else
+        hipLaunchKernelGGL(track_gate_kernel<false>, dim3(1), dim3(64 * GATE_WAVES), 0, s, a, ids);
 }
 
 void launch_track_gate_scatter(const TrackScatterArgs &a, hipStream_t s) {

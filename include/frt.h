@@ -875,6 +875,35 @@ int frt_pipeline_run_photo_tiled(frt_pipeline *p, const uint8_t *bgr, int rows, 
  *       (with both settings off they report how / gap / ovr / sim of the update above).
  *     Nobody has measured S on real faces with this library: no threshold is recommended here, and the synthetic weights of the tests say
  *       nothing about where genuine and impostor similarities lie.  frt_matcher_separation over an enrolled gallery is the place to start.
+ *
+ *   Motion (frt_tracker_set_motion; off by default, and a tracker that never switches it on allocates nothing more and produces the bytes
+ *   described above).  The overlap of step 2 is taken with the track's last measured box: a face that moves more than about half its width
+ *   between two updates is born again under a new id, a coasting track is compared where it was last seen, and the gate's skip_iou sends a
+ *   walking person through the recogniser on every frame.  With motion on every track carries a constant-velocity term and every place
+ *   that compares a detection with a track's box uses the PREDICTED box (tests/track_motion_ref.py restates this block in Python ints).
+ *     State: vel int32 [n_streams][max_tracks][2] beside the sums, (vx, vy) of the box centre in 1/256 pixel per update; allocated and
+ *       zeroed by the first call that needs it with motion on.  A free slot's velocity is (0, 0).  frt_track_state, frt_track_result and
+ *       frt_tracker_tracks do not change: a slot's box stays the last MEASURED box.
+ *     Setting: gain 0 is off (the default), 1 .. 256 on; anything else is FRT_ERR_INVALID and changes nothing.  Off -> on zeroes every
+ *       velocity (no device work while the array does not exist; otherwise synchronous behind the last queued update, like
+ *       frt_tracker_reset); on -> another on value keeps them; on -> off leaves the array alone - it is never read while off.
+ *       frt_tracker_reset zeroes the velocity rows of the streams it resets when the array exists.
+ *     All arithmetic is in integers; tdiv(a, b) = sign(a) * (|a| / b) for b > 0 is truncation toward zero (C's division, not a floor).
+ *     M1. Prediction, for a track live at entry: k = missed + 1; sx = clamp(tdiv((int64) vx * k, 256), -2^30, 2^30), sy likewise; the
+ *         predicted box is (x1 + sx, y1 + sy, x2 + sx, y2 + sy, score), each coordinate computed in int64 and clamped to the int32 range
+ *         (the clamp is monotone: x1 <= x2 survives).  It replaces the track's box in step 2 / 2a's overlap, in the ovr 2b reports, in
+ *         the gate's peek (G2) and skip_iou comparison (G3), and so in frt_track_assoc.ovr and frt_track_gate.ovr.  Nothing else reads it.
+ *     M2. Velocity update, on every match (2a or 2b), of the track that won: g = missed at entry + 1;
+ *         dcx = clamp((int64) (det.x1 + det.x2) - (trk.x1 + trk.x2), -2^22, 2^22), the doubled centre displacement from the last MEASURED
+ *         box; raw_x = tdiv(dcx * 128, g).  If the track's hits at entry is 1 (the first match after the birth) vx = raw_x; otherwise
+ *         vx = vx + tdiv((int64) (raw_x - vx) * gain, 256).  The same for y.  |v| <= 2^29 follows.  Then the match does what it always
+ *         does: box = det.box, hits += 1, missed = 0.
+ *     M3. Expiry zeroes the slot's velocity; a birth sets it to (0, 0).
+ *     M4. The gate reads the velocities and writes none; with appearance off its peek is still the update's step 2, exactly.
+ *     M5. Steps 3 to 8, the sums, the templates, the identity search and the sightings are unchanged.
+ *     A track that was already live when motion is switched on starts from (0, 0) with hits > 1, so its first match takes the EMA branch
+ *       and reaches only gain / 256 of the measured velocity.  That is intended: the switch does not pretend to a first measurement.
+ *     Nobody has measured a gain on real video with this library: none is recommended here.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct frt_tracker frt_tracker;
 typedef struct frt_track_options {
@@ -924,6 +953,15 @@ int frt_tracker_update(frt_tracker *t, frt_matcher *m, const frt_face_result *re
  * FRT_ERR_INVALID and changes nothing.  frt_tracker_update_dev, frt_tracker_update and frt_pipeline_run_tracked honour the settings. */
 int frt_tracker_set_appearance(frt_tracker *t, float reid_threshold, float iou_min_sim);
 int frt_tracker_get_appearance(frt_tracker *t, float *reid_threshold_out, float *iou_min_sim_out);
+/* "Motion" above.  gain 0 switches it off, 1 .. 256 on; anything else is FRT_ERR_INVALID and changes nothing.  Takes effect with the next
+ * update or gate; under the tracker's mutex.  Off -> on zeroes the velocities: no device work while they do not exist yet, otherwise
+ * synchronous behind the last queued update.  frt_tracker_update*, frt_tracker_gate*, frt_pipeline_run_tracked, _run_tracked_gated and
+ * _run_sighted honour the setting. */
+int frt_tracker_set_motion(frt_tracker *t, int gain);
+int frt_tracker_get_motion(frt_tracker *t, int *gain_out);
+/* one stream's velocities, after everything queued (like frt_tracker_tracks): vel_out int32 [max_tracks][2]; pred_out [max_tracks] (may be
+ * NULL) M1's box of every slot for the NEXT update, all zero for a free slot.  FRT_ERR_INVALID while motion is off. */
+int frt_tracker_motion(frt_tracker *t, int stream, int32_t *vel_out, frt_bbox *pred_out /* may be NULL */);
 /* frt_tracker_update_dev / frt_tracker_update with how each detection was associated: assoc_dev / assoc_out frt_track_assoc
  * [n_frames][max_faces] (may be NULL: the call is then the plain one).  The same checks, all before any device work. */
 int frt_tracker_update_assoc_dev(frt_tracker *t, frt_matcher *m, const void *results_dev, const void *embeds_dev, int n_frames,

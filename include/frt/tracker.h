@@ -52,6 +52,23 @@ class FaceTracker {
     // FRT_TRACK_MIN_SIM_OFF switch either off; both are off until set.  No threshold is recommended: measure on your own faces.
     void setAppearance(float reidThreshold, float iouMinSim) { checkFrtStatus(frt_tracker_set_appearance(h_, reidThreshold, iouMinSim)); }
     void getAppearance(float &reidThreshold, float &iouMinSim) { checkFrtStatus(frt_tracker_get_appearance(h_, &reidThreshold, &iouMinSim)); }
+    // Motion (include/frt.h "Motion"): a constant-velocity term per track; with it on every overlap - the association's, the gate's - is
+    // taken with the track's PREDICTED box.  gain 0 switches it off (the default), 1 .. 256 is the weight of a new measurement in the
+    // velocity's running mean, in 1/256.  No gain is recommended: nobody has measured one on real video with this library.
+    void setMotion(int gain) { checkFrtStatus(frt_tracker_set_motion(h_, gain)); }
+    int getMotion() {
+        int gain = 0;
+        checkFrtStatus(frt_tracker_get_motion(h_, &gain));
+        return gain;
+    }
+    // One stream's velocities [maxTracks x 2] (vx, vy in 1/256 pixel per update); predicted (may be null) receives the box each slot is
+    // compared with in the NEXT update, zeros for a free slot.  Throws while motion is off.
+    std::vector<int32_t> motion(int stream, std::vector<frt_bbox> *predicted = nullptr) {
+        std::vector<int32_t> vel((size_t)maxTracks_ * 2, 0);
+        if (predicted) predicted->assign((size_t)maxTracks_, frt_bbox());
+        checkFrtStatus(frt_tracker_motion(h_, stream, vel.data(), predicted ? predicted->data() : nullptr));
+        return vel;
+    }
     // The gate alone (include/frt.h "Gate"): which of these boxes [nFrames x maxFaces] - nBoxes (may be empty) the detector's counts per
     // frame - must go through the recogniser and which a confirmed track follows.  Returns one record per face slot; list receives the face
     // indices to embed, ascending (list.size() is n_embed), passCount (may be null) the faces of each recogniser pass of maxBatch.  Reads the

@@ -10,6 +10,10 @@ steady state of a still camera, the best case of the gate.
            n_embed of every call.
   --profile  instead of the legs: the gate, the gather crop and the scatter by the library's profiling hooks (frt_profile_enable(2)), which
            run every call serially; a run of its own, so that the legs above are not taken with the hooks on.
+  --motion GAIN  instead of the legs: a MOVING scene - the frames rolled --roll pixels further on every call, a
+           demonstration of the mechanism and not a rate anyone will see on video -, runTrackedGated at --refresh[0] with motion off and on,
+           alternating legs, the roll itself outside the timed region: the mean time per call and n_embed per call; then, hooks on, the gate
+           kernel alone (track_gate) off and on, alternating legs.
 The measurement's own settings, not recommendations: --min-embeds 1, --skip-iou 0.5.
 Needs the GPU.  Run it under a time limit, one process per mode:
 
@@ -41,6 +45,8 @@ def main():
     ap.add_argument("--min-embeds", dest="min_embeds", type=int, default=1)
     ap.add_argument("--skip-iou", dest="skip_iou", type=float, default=0.5)
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--motion", type=int, default=0, help="the moving-scene legs, motion off against this gain (1 .. 256)")
+    ap.add_argument("--roll", type=int, default=8, help="--motion: pixels per call")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     frt = entry.load_pkg()
@@ -66,6 +72,53 @@ def main():
     pipe = frt.Pipeline(det, rec, S)
     frames = s.make_frames(S, H, W)
     out["faces_per_call"] = int((pipe.run(frames)[0]["score"] > 0).sum())
+    if a.motion:
+        out["motion_gain"], out["roll"], out["refresh"] = a.motion, a.roll, a.refresh[0]
+        trk = {"gated_off": frt.Tracker(S, T, MF, 512), "gated_on": frt.Tracker(S, T, MF, 512, motion_gain=a.motion)}
+        at = {n: 0 for n in trk}
+
+        def moving(n):
+            at[n] += 1
+            return np.roll(frames, a.roll * at[n], axis=2)
+
+        def gated(n, f):
+            return pipe.runTrackedGated(trk[n], f, a.refresh[0], a.min_embeds, a.skip_iou, want_embeds=False, want_templates=False)[4]
+
+        times, embedded, leg_means = {n: [] for n in trk}, {n: [] for n in trk}, {n: [] for n in trk}
+        for _ in range(a.legs):
+            for n in trk:
+                for _ in range(5):
+                    gated(n, moving(n))
+                ts = []
+                for _ in range(a.repeat):
+                    f = moving(n)
+                    t0 = time.perf_counter()
+                    ne = gated(n, f)
+                    ts.append((time.perf_counter() - t0) * 1e3)
+                    embedded[n].append(ne)
+                times[n] += ts
+                leg_means[n].append(statistics.mean(ts))
+        for n in trk:
+            e, t = np.asarray(embedded[n]), np.asarray(times[n])
+            report(n, {"calls": len(t), "mean": float(t.mean()), "median": float(np.median(t)), "min": float(t.min()), "max": float(t.max()),
+                       "leg_means": leg_means[n], "n_embed_mean": float(e.mean()), "n_embed_min": int(e.min()), "n_embed_max": int(e.max())})
+        gate_medians = {n: [] for n in trk}
+        for _ in range(a.legs):
+            for n in trk:
+                frt.profile_enable(2)
+                for _ in range(a.repeat):
+                    gated(n, moving(n))
+                kn, ms, _ = frt.profile_collect()
+                frt.profile_enable(0)
+                gate_medians[n].append(statistics.median([float(t) for k, t in zip(kn, ms) if k == "track_gate"]))
+        for n, v in gate_medians.items():
+            report("p_track_gate_" + n.split("_")[1], {"leg_medians": v, "median": statistics.median(v), "min": min(v), "max": max(v)})
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+        for t in trk.values():
+            t.close()
+        pipe.close(), rec.close(), det.close()
+        return
     names = ["run_tracked"] + ["gated_refresh_%d" % r for r in a.refresh]
     trackers = {n: frt.Tracker(S, T, MF, 512) for n in names}
     embedded = {n: [] for n in names}

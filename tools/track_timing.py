@@ -11,9 +11,14 @@ seeded random walk (4 faces per stream, resident in HBM); the pipeline legs (c) 
 With appearance on (--reid / --min-sim, 0.5 / 0.2):
   a_on_*  leg a again: the whole call, and its split into track_similarity (the similarity kernel), track_update and the rest
   w_*     the similarity kernel's worst case, once: 256 frames x 64 detections x 64 live tracks, dim 512, no matcher
+With --motion GAIN (a run of its own, instead of everything above, same shape, no gallery):
+  m_update_*   the update kernel alone (frt_profile_enable(2): track_update) over the same walk, motion off and on - and, with --parent-lib,
+               the kernel of another build of the library (the parent commit's) - on alternating legs in one process
+  m_tracked_*  frt_pipeline_run_tracked with motion off and on, alternating legs
 Needs the GPU.  Run it under a time limit, one process:
 
     timeout 900 python tools/track_timing.py [--rows 1000000] [--streams 32] [--repeat 30] [--legs 3] --out result.json
+    timeout 600 python tools/track_timing.py --motion 128 [--parent-lib old/libfrt.so] [--legs 5] --out result.json
 """
 import argparse
 import json
@@ -51,6 +56,89 @@ def walk(rng, n_streams, max_faces, updates):
     return out
 
 
+def load_other_build(path):
+    """the binding once more, over another build of the library (symbols it lacks are skipped, as bench.py --ab-old-lib loads it)"""
+    import importlib.util
+    import types
+    os.environ["FRT_LIB"] = os.path.abspath(path)
+    sys.modules["frt_amd_ab_old_library"] = types.ModuleType("frt_amd_ab_old_library")
+    try:
+        spec = importlib.util.spec_from_file_location("frt_amd_other", os.path.join(entry.PKG_DIR, "__init__.py"), submodule_search_locations=[entry.PKG_DIR])
+        mod = importlib.util.module_from_spec(spec)
+        sys.modules["frt_amd_other"] = mod
+        spec.loader.exec_module(mod)
+    finally:
+        del os.environ["FRT_LIB"], sys.modules["frt_amd_ab_old_library"]
+    return mod
+
+
+def motion_legs(a, frt, report, out):
+    """--motion: the update kernel and frt_pipeline_run_tracked with motion off and on, alternating legs (see the module docstring)"""
+    import torch
+    S, MF, T, D = a.streams, 4, 16, 512
+    F = S * MF
+    rng = np.random.default_rng(1)
+    steps = walk(rng, S, MF, a.repeat + 5)
+    emb = rng.standard_normal((F, D)).astype(np.float32)
+    emb /= np.linalg.norm(emb, axis=1, keepdims=True)
+    d_res = [torch.from_numpy(r.view(np.uint8).copy()).cuda() for r in steps]
+    d_emb = torch.from_numpy(emb).cuda()
+    d_trk = torch.zeros(F * 32, dtype=torch.uint8, device="cuda")
+    stream = torch.cuda.current_stream().cuda_stream
+    builds = {"off": (frt, None), "on": (frt, a.motion)}
+    if a.parent_lib:
+        builds["parent"] = (load_other_build(a.parent_lib), None)
+    trackers = {n: (lib, lib.Tracker(S, T, MF, D) if gain is None else lib.Tracker(S, T, MF, D, motion_gain=gain)) for n, (lib, gain) in builds.items()}
+    medians = {n: [] for n in trackers}
+    for _ in range(a.legs):
+        for n, (lib, trk) in trackers.items():
+            trk.reset()
+            for k in range(5):
+                trk.updateDev(d_res[k].data_ptr(), d_emb.data_ptr(), S, d_trk.data_ptr(), None, None, None, stream)
+            torch.cuda.synchronize()
+            lib.profile_enable(2)
+            for k in range(5, 5 + a.repeat):
+                trk.updateDev(d_res[k].data_ptr(), d_emb.data_ptr(), S, d_trk.data_ptr(), None, None, None, stream)
+            torch.cuda.synchronize()
+            names, ms, _ = lib.profile_collect()
+            lib.profile_enable(0)
+            ks = [float(t) for nm, t in zip(names, ms) if nm == "track_update"]
+            assert len(ks) == a.repeat, (n, len(ks))
+            medians[n].append(statistics.median(ks))
+    for n, v in medians.items():
+        report("m_update_" + n, {"leg_medians": v, "median": statistics.median(v), "min": min(v), "max": max(v)})
+    out["m_live_tracks"] = {n: sum(int((trk.tracks(s)[0]["live"] != 0).sum()) for s in range(S)) for n, (_, trk) in trackers.items()}
+    for _, trk in trackers.values():
+        trk.close()
+    # ---- the pipeline, the frames repeated (a still scene: the velocities stay zero, the cost is the instantiation's)
+    tmp = tempfile.mkdtemp(prefix="frt_track_timing_")
+    s = frt.synth
+    det_path = frt.write_weights(os.path.join(tmp, "det.frtw"), s.retinaface_state(1), 1)
+    rec_path = frt.write_weights(os.path.join(tmp, "rec.frtw"), s.arcface_state(2, "ir", calib=s.load_calibration("ir")), 2)
+    W = H = a.frame
+    det = frt.RetinaFace(det_path, W, H, (3, H, W), S, MF, 0.4, 0.6)
+    rec = frt.ArcFaceIR50(rec_path, W, H, (3, 112, 112), 512, F, MF, 0.65)
+    pipe = frt.Pipeline(det, rec, S, match=False)
+    frames = s.make_frames(S, H, W)
+    trk = {"off": frt.Tracker(S, T, MF, D), "on": frt.Tracker(S, T, MF, D, motion_gain=a.motion)}
+    legs = {n: [] for n in trk}
+    for _ in range(a.legs):
+        for n in trk:
+            for _ in range(3):
+                pipe.runTracked(trk[n], frames)
+            ts = []
+            for _ in range(a.repeat):
+                t0 = time.perf_counter()
+                pipe.runTracked(trk[n], frames)
+                ts.append((time.perf_counter() - t0) * 1e3)
+            legs[n].append(statistics.median(ts))
+    for n, v in legs.items():
+        report("m_tracked_" + n, {"leg_medians": v, "median": statistics.median(v), "min": min(v), "max": max(v)})
+    for t in trk.values():
+        t.close()
+    pipe.close(), rec.close(), det.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -60,6 +148,8 @@ def main():
     ap.add_argument("--frame", type=int, default=640)
     ap.add_argument("--reid", type=float, default=0.5, help="reid_threshold of the legs with appearance on")
     ap.add_argument("--min-sim", dest="min_sim", type=float, default=0.2, help="iou_min_sim of the legs with appearance on")
+    ap.add_argument("--motion", type=int, default=0, help="the motion legs alone, with this gain (1 .. 256) for the legs with motion on")
+    ap.add_argument("--parent-lib", dest="parent_lib", default=None, help="--motion: another build of libfrt.so whose update kernel joins the legs")
     ap.add_argument("--out", required=True)
     a = ap.parse_args()
     import torch
@@ -67,6 +157,17 @@ def main():
     frt = entry.load_pkg()
     S, MF, T, D, N = a.streams, 4, 16, 512, a.rows
     F = S * MF
+    if a.motion:
+        out = {"streams": S, "max_faces": MF, "max_tracks": T, "repeat": a.repeat, "legs": a.legs, "unit": "ms", "motion_gain": a.motion, "cases": {}}
+
+        def report(name, r):
+            out["cases"][name] = r
+            print("%-28s %s" % (name, json.dumps(r)), flush=True)
+
+        motion_legs(a, frt, report, out)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+        return
     rng = np.random.default_rng(1)
     g = frt.synth.make_gallery(N)
     mm = frt.MatMul(0)
